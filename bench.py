@@ -1,6 +1,6 @@
 """Benchmark of the rule-editing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--batch B] [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json's metric: images/sec of the StyleGANv2-1024 sequential
 generator forward (SeqStyleGAN2 size 1024, mconv='seq', truncation 0.5, synthetic seeded
@@ -11,9 +11,12 @@ itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --ma
 partitioned rank-wise (no data-path collective, weak scaling); the timed region is bracketed by barrier +
 synchronize and the MAX over ranks is reported.
 
-Rank 0 prints ONE JSON line with `roofline` (the dominant conv kernel: the matrix FLOPs its launches ISSUE /
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up (W + 1 untimed steps), times exactly K steps
+(`ms_per_step` = their wall time / K), writes the outputs of the last timed step if --dump-outputs DIR is given
+(dump_images) and prints the line with `roofline` null.  With --full the forward workloads then also measure
+`roofline` (the dominant conv kernel: the matrix FLOPs its launches ISSUE /
 their HIP-event time, against the 157.3 TFLOP/s fp32-MFMA peak; the direct-sum figure beside it) and
-`cpu_baseline` (the reference's own files when /root/reference is present, else the oracle restatement, timed
+`cpu_baseline` (the reference's own files when a checkout of it is present, else the oracle restatement, timed
 on the host cores on a bounded sample at the best of several thread counts; N=1 only) and `extra`: the other
 half of BASELINE.json's metric (seconds per rank-1 edit = 1000-seed key statistics + 2001-step solve), the
 256^2 forward (configs[1]), the key-statistics sweeps at layers 8/10/14 (configs[3]; each with `context_layers`, the
@@ -567,7 +570,23 @@ def timed(fn, steps, warmup, world):
     return dt
 
 
-def run_forward(args, rank, world, device, size, batch, name, cpu=True):
+DUMP_SAMPLE = 1 << 22          # elements of the seeded sample of a batch that --dump-outputs writes (16 MB in float32)
+
+
+def dump_images(img, out_dir):
+    """--dump-outputs: what the last timed step returned, as float32 .npy files in `out_dir` (29 MB at 1024^2): the first
+    image of the batch whole (image0.npy) and DUMP_SAMPLE elements of the whole batch at fixed, seeded, sorted flat
+    indices (images_sample.npy; the same indices for the same batch shape)."""
+    import numpy
+    os.makedirs(out_dir, exist_ok=True)
+    flat = img.detach().reshape(-1)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(0))
+    idx = idx.sort().values.to(flat.device)
+    numpy.save(os.path.join(out_dir, 'image0.npy'), img[0].detach().float().cpu().numpy())
+    numpy.save(os.path.join(out_dir, 'images_sample.npy'), flat[idx].float().cpu().numpy())
+
+
+def run_forward(args, rank, world, device, size, batch, name, cpu=True, dump_dir=None):
     from rewriting_amd.utils import zdataset
     g = build_generator(size, device)
     # seed i -> rank i mod world; every rank holds its own `batch` seeds, resident in HBM
@@ -581,6 +600,8 @@ def run_forward(args, rank, world, device, size, batch, name, cpu=True):
             last[0] = g(z)
     timed(step, 1, args.warmup, world)                      # warm-up incl. weight repack caches
     dt = timed(step, args.steps, 0, world)                  # THE number: nothing installed around the kernels
+    if dump_dir and rank == 0:
+        dump_images(last[0], dump_dir)
     from rewriting_amd.utils.stylegan2 import models as sg_models
     split = sg_models.matrix_mode_of_image_path() == 'split'
     images = batch * world * args.steps
@@ -596,6 +617,8 @@ def run_forward(args, rank, world, device, size, batch, name, cpu=True):
                            conv_gflop_per_image=round(conv_flops(size) / 1e9, 2),
                            matrix_mode='split' if split else 'f32',
                            direct_sums=os.environ.get('RW_MM_DIRECT16', 'auto') if split else None))
+    if not args.full:
+        return out
     # second pass, NOT the headline: HIP events around every convolution call (on torch's current stream, the one the
     # kernels are launched on) -> the per-kernel table and the dominant kernel's roofline
     timer = ConvTimer()
@@ -1082,8 +1105,14 @@ def main():
     ap.add_argument('--seeds', type=int, default=1000)
     ap.add_argument('--niters', type=int, default=2001, help='watermark workload: solver steps per erase (reference: 2001)')
     ap.add_argument('--wm-size', type=int, default=256, help='watermark workload: generator resolution (reference: 256)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='headline workload only')
+    ap.add_argument('--full', action='store_true',
+                    help='forward workloads: after the headline steps also measure the roofline pass, the step roofs, the '
+                         'parity of the timed output and the CPU baseline; the default workload adds the other '
+                         'configurations (`extra`).  Off: set up, warm up, time --steps steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='forward workloads: write what the last timed step returned (rank 0) as float32 .npy files in DIR')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: headline workload only')
     ap.add_argument('--precision', default='f32', choices=['f32', 'bf16x6'],
                     help='bf16x6: opt-in split-precision stride-1 convolutions (fp32-product accuracy); '
                          'the default and the headline number are exact fp32 MFMA')
@@ -1091,6 +1120,8 @@ def main():
                     help='stride-1 3x3 convolutions: winograd F(2x2,3x3) in fp32 (default where it applies) or '
                          'direct implicit GEMM')
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ('ffhq1024', 'ffhq256'):
+        raise SystemExit('bench.py: --dump-outputs is implemented for the forward workloads (ffhq1024, ffhq256)')
 
     if args.gpus > 1 and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))
@@ -1105,12 +1136,13 @@ def main():
     device = bench_device(local)
     if args.workload == 'ffhq1024':
         out = run_forward(args, rank, world, device, 1024, args.batch or 64,
-                          'stylegan2-1024 generator forward (FFHQ-1024 architecture)')
-        if not args.no_extra:
+                          'stylegan2-1024 generator forward (FFHQ-1024 architecture)', dump_dir=args.dump_outputs)
+        if args.full and not args.no_extra:
             out['extra'] = extras(args, rank, world, device)
     elif args.workload == 'ffhq256':
         out = run_forward(args, rank, world, device, 256, args.batch or 64,
-                          'stylegan2-256 generator forward, 64-seed batch (FFHQ-256 architecture)')
+                          'stylegan2-256 generator forward, 64-seed batch (FFHQ-256 architecture)',
+                          dump_dir=args.dump_outputs)
     elif args.workload == 'edit':
         out = run_edit(args, rank, world, device)
     elif args.workload == 'sweep':

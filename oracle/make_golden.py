@@ -1206,6 +1206,189 @@ def golden_edit_full_exact(ref, name):
     save(name, **arrays)
 
 
+def _pil(a):
+    return numpy.asarray(a).copy()
+
+
+def golden_reference_checks(ref, name):
+    """What the CPU tests once asked of the reference executed live, recorded so that they need no checkout of it:
+    restate/ -- a 16^2 generator forward; viz/ -- imgviz.ImageVisualizer pictures; render/ -- the rewriter's
+    rendering calls on a 64^2 generator; fid/ -- metrics/fid.py calculate_frechet_distance; r2m/, rv/, cache/ -- the
+    statistics caches (the reference's notebooks/masks/reflections/progan-kitchen/r2m.npz is stored beside this file
+    as r2m_progan_kitchen_triu.npz: its symmetric mom2 as the upper triangle, the other fields as they are); rq/ -- the quantile sketch's cache in both directions.  ours/... = what this package
+    wrote at recording time and the reference read back (the tests check that it still writes the same)."""
+    import hashlib
+    import shutil
+    import tempfile
+    from scipy import linalg
+    from rewriting_amd import samples
+    from rewriting_amd.utils import imgviz, runningstats, tally
+    from rewriting_amd.utils.stylegan2 import models as our_models
+    A = {}
+    # --- restate/: test_restatement_against_live_reference
+    g = ref.models.SeqStyleGAN2(16, 512, 8, truncation=0.7, mconv='seq')
+    synthetic.randomize_(g, seed=3)
+    g.eval()
+    z = ref.zdataset.standard_z_sample(2, 512, seed=5)
+    with torch.no_grad():
+        A['restate/image'] = g(z).numpy()
+    A['restate/z'] = z.numpy()
+    mine = our_models.SeqStyleGAN2(16, 512, 8, truncation=0.7, mconv='seq')
+    synthetic.randomize_(mine, seed=3)
+    theirs_sd, mine_sd = g.state_dict(), mine.state_dict()
+    assert set(theirs_sd) == set(mine_sd) and all(torch.equal(theirs_sd[k], mine_sd[k]) for k in theirs_sd)
+    # --- viz/: test_image_visualizer_equals_the_reference
+    gen = torch.Generator().manual_seed(0)
+    img = torch.randn(1, 3, 64, 64, generator=gen).clamp(-1, 1)
+    act = torch.randn(16, 16, generator=gen)
+    for si, size in enumerate((64, (48, 80), 128)):
+        a = ref.ganrewrite.imgviz.ImageVisualizer(size)
+        for ki, kw in enumerate(VIZ_CASES):
+            A['viz/%d/masked/%d' % (si, ki)] = _pil(a.masked_image(img, act, **kw))
+        shape = (size, size) if isinstance(size, int) else size
+        m = torch.rand(*shape, generator=gen) > 0.5
+        A['viz/%d/masked_mask' % si] = _pil(a.masked_image(img, mask=m))
+        for mode in ('bilinear', 'nearest'):
+            A['viz/%d/heatmap/%s' % (si, mode)] = _pil(a.heatmap(act, mode=mode))
+        A['viz/%d/image' % si] = _pil(a.image(img))
+    # --- render/: test_rewriter_rendering_matches_the_reference
+    nseeds, layer = 60, 8
+    gm = ref.models.SeqStyleGAN2(64, 512, 8, truncation=0.5, mconv='seq')
+    synthetic.randomize_(gm, seed=0)
+    gm.eval()
+    gt = ref.ganrewrite.SeqStyleGanRewriter(gm, ref.zdataset.z_dataset_for_model(gm, size=nseeds), layer, cachedir=None)
+    with open(os.path.join(MASKS, 'recorded_horse_hat.json')) as f:
+        req = remap_request(json.load(f), nseeds)
+    key = gt.query_key_from_selection(*req['key'][0])
+    A['render/key'] = key.numpy()
+    A['render/plain'] = _pil(gt.render_image(3))
+    A['render/key_level'] = _pil(gt.render_image(5, key=key, level=0.2))
+    mask = torch.zeros(64, 64, dtype=torch.bool)
+    mask[10:30, 20:50] = True
+    A['render/mask'] = _pil(gt.render_image(7, mask=mask))
+    for i, x in enumerate(gt.render_image_batch([1, 2, 4, 8])):
+        A['render/batch/%d' % i] = _pil(x)
+    for i, x in enumerate(gt.render_image_batch([1, 2], key=key, level=0.1)):
+        A['render/batch_key/%d' % i] = _pil(x)
+    obj = gt.object_from_selection(*req['object'])
+    A['render/object_box'] = _pil(gt.render_object(obj[1], box=obj[3]))
+    A['render/object'] = _pil(gt.render_object(obj[1]))
+    # --- fid/: test_frechet_distance_equals_the_reference_function
+    rs = numpy.random.RandomState(0)
+    a = (rs.randn(300, 24) * (1 + numpy.arange(24) / 8) + 0.3).astype('float32')
+    b = (rs.randn(280, 24) * 1.3 - 0.2).astype('float32')
+    sa, sb = samples.FeatureStatistics(), samples.FeatureStatistics()
+    sa.add(torch.from_numpy(a))
+    sb.add(torch.from_numpy(b))
+    (mu1, s1), (mu2, s2) = sa.mean_cov(), sb.mean_cov()
+    ns = {'np': numpy, 'linalg': linalg, 'warnings': __import__('warnings')}
+    fd = reference_shim._extract_function(os.path.join(reference_shim.REFERENCE_ROOT, 'metrics', 'fid.py'),
+                                          'calculate_frechet_distance', ns)
+    A.update({'fid/mu1': mu1, 'fid/s1': s1, 'fid/mu2': mu2, 'fid/s2': s2, 'fid/d': numpy.float64(fd(mu1, s1, mu2, s2))})
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        zero = numpy.zeros_like(s1)
+        A['fid/d_singular'] = numpy.float64(fd(mu1, zero, mu2, zero))
+    tmp = tempfile.mkdtemp(prefix='golden_ref_')
+    # --- r2m/, cache/, rv/: test_statistics_cache_interoperates_with_the_reference
+    src = os.path.join(reference_shim.REFERENCE_ROOT, 'notebooks/masks/reflections/progan-kitchen/r2m.npz')
+    theirs = numpy.load(src, allow_pickle=True)
+    m = theirs['mom2']
+    assert numpy.array_equal(m, m.T) and theirs['sample_size'].item() is None
+    save('r2m_progan_kitchen_triu', mom2_triu=m[numpy.triu_indices(m.shape[0])], count=theirs['count'],
+         constructor=theirs['constructor'], mom2_sha256=numpy.array(hashlib.sha256(m.tobytes()).hexdigest()))
+    want = ref.runningstats.RunningSecondMoment(state=theirs).moment()
+    A['r2m/moment_sha256'] = numpy.array(hashlib.sha256(want.numpy().tobytes()).hexdigest())
+    A['r2m/moment_dtype'] = numpy.array(str(want.dtype))
+    r = runningstats.RunningSecondMoment(state=theirs)
+    tally.save_cached_state(os.path.join(tmp, 'r2m.npz'), r, dict(sample_size=None))
+    back = numpy.load(os.path.join(tmp, 'r2m.npz'), allow_pickle=True)
+    assert torch.equal(ref.runningstats.RunningSecondMoment(state=back).moment(), want)
+    got = ref.tally.tally_second_moment(lambda z: None, torch.zeros(1, 1), sample_size=None,
+                                        cachefile=os.path.join(tmp, 'r2m.npz'))
+    assert torch.equal(got.moment(), want)
+    rows = torch.randn(300, 16, generator=torch.Generator().manual_seed(0))
+    A['cache/rows'] = rows.numpy()
+    fresh = runningstats.RunningSecondMoment()
+    fresh.mom2, fresh.count = rows.t() @ rows, 300
+    bfile = os.path.join(tmp, 'b.npz')
+    tally.save_cached_state(bfile, fresh, dict(sample_size=7))
+    A['cache/ref_accepts_7'] = numpy.bool_(ref.tally.load_cached_state(bfile, dict(sample_size=7)) is not None)
+    A['cache/ref_accepts_8'] = numpy.bool_(ref.tally.load_cached_state(bfile, dict(sample_size=8)) is not None)
+    theirs2 = ref.runningstats.RunningSecondMoment(state=numpy.load(bfile, allow_pickle=True))
+    A['cache/ref_moment'] = theirs2.moment().numpy()
+    for k, v in numpy.load(bfile, allow_pickle=True).items():
+        if v.dtype != object:
+            A['cache/ours/%s' % k] = v
+    rv = ref.runningstats.RunningVariance()
+    rv.add(rows)
+    for k, v in rv.state_dict().items():
+        A['rv/theirs/%s' % k] = numpy.asarray(v)
+    A['rv/mean'], A['rv/variance'] = rv.mean().numpy(), rv.variance().numpy()
+    ours_rv = runningstats.RunningVariance(state=numpy.load(_savez(tmp, 'rs.npz', rv.state_dict()), allow_pickle=True))
+    back2 = ref.runningstats.RunningVariance(
+        state=numpy.load(_savez(tmp, 'rs2.npz', ours_rv.state_dict()), allow_pickle=True))
+    assert torch.allclose(back2.mean(), rv.mean()) and torch.allclose(back2.variance(), rv.variance())
+    for k, v in ours_rv.state_dict().items():
+        A['rv/ours/%s' % k] = numpy.asarray(v)
+    # --- rq/: test_quantile_cache_interoperates_with_the_reference
+    gen = torch.Generator().manual_seed(3)
+    units, n = 6, 40000
+    x = torch.randn(n, units, generator=gen) * torch.linspace(0.5, 3, units) + torch.linspace(-1, 1, units)
+    x[:, 2] = x[:, 2].exp()
+    A['rq/x_head'], A['rq/x_sum'] = x[:16].numpy().copy(), numpy.float64(x.double().sum().item())
+    data = torch.utils.data.TensorDataset(x)
+    qs = torch.tensor(RQ_QS)
+    tails = torch.tensor(RQ_TAILS)
+    probe = x[:500].t().contiguous()
+    theirs = ref.tally.tally_quantile(lambda b: b, data, batch_size=1000, r=512)
+    st = theirs.state_dict()
+    for k, v in st.items():
+        if k == 'data':
+            for l, lv in enumerate(v):
+                A['rq/theirs/data/%d' % l] = numpy.asarray(lv)
+        else:
+            A['rq/theirs/%s' % k] = numpy.asarray(v)
+    A['rq/theirs_out/quantiles'] = theirs.quantiles(qs).numpy()
+    A['rq/theirs_out/tails'] = theirs.quantiles(tails).numpy()
+    A['rq/theirs_out/minmax'] = theirs.minmax().numpy()
+    A['rq/theirs_out/normalize'] = theirs.normalize(probe).numpy()
+    A['rq/theirs_out/mean'], A['rq/theirs_out/stdev'] = theirs.mean().numpy(), theirs.stdev().numpy()
+    ours_file = os.path.join(tmp, 'ours', 'unit_rq.npz')
+    ours = tally.tally_quantile(lambda b: b, data, batch_size=1000, r=512, cachefile=ours_file)
+    for l, lv in enumerate(ours.state_dict()['data']):
+        A['rq/ours/data/%d' % l] = numpy.asarray(lv)
+    back = ref.tally.tally_quantile(lambda b: 1 / 0, data, batch_size=1000, r=512, cachefile=ours_file)
+    A['rq/back/size'] = numpy.int64(back.size())
+    A['rq/back/quantiles'] = back.quantiles(qs).numpy()
+    A['rq/back/normalize'] = back.normalize(probe).numpy()
+    small = runningstats.RunningQuantile(r=4096)
+    small.add(x[:3000])
+    small.compress_()
+    sfile = _savez(tmp, 'small.npz', small.state_dict())
+    for k, v in numpy.load(sfile, allow_pickle=True).items():
+        if v.dtype != object:
+            A['rq/small/%s' % k] = v
+    for l, lv in enumerate(small.state_dict()['data']):
+        A['rq/small/data/%d' % l] = numpy.asarray(lv)
+    A['rq/small_theirs/quantiles'] = ref.runningstats.RunningQuantile(state=sfile).quantiles(qs).numpy()
+    shutil.rmtree(tmp)
+    save(name, **A)
+
+
+VIZ_CASES = (dict(level=0.3), dict(level=0.0, border_color=[255, 0, 0], thickness=3), dict(percent_level=0.9),
+             dict(level=0.5, inside_color=[0, 255, 0], outside_bright=0.25))
+RQ_QS = [0.0, 1e-4, 0.01, 0.25, 0.5, 0.9, 0.99, 0.999, 1.0]
+RQ_TAILS = [2e-4, 1e-3, 3e-3, 0.01, 0.99, 0.997, 0.999, 0.9998]
+
+
+def _savez(d, fname, state):
+    path = os.path.join(d, fname)
+    numpy.savez(path, **state)
+    return path
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default=None)
@@ -1250,6 +1433,7 @@ def main():
         'pg256_l6_spire2tree_1000': lambda: golden_proggan_full(ref, 'pg256_l6_spire2tree_1000'),
         'rw_s256_l6_watermark_1000': lambda: golden_watermark_full(ref, 'rw_s256_l6_watermark_1000'),
         'rw_s256_l6_watermark_1000_scatter': lambda: golden_watermark_scatter(ref, 'rw_s256_l6_watermark_1000_scatter'),
+        'reference_checks': lambda: golden_reference_checks(ref, 'reference_checks'),
     }
     for nm, fn in jobs.items():
         if args.only in (None, nm):

@@ -8,6 +8,6 @@ done
 for rep in 1 2; do
 for m in 0 1; do
   echo "== bench RW_W4_PSPLIT=$m"
-  RW_W4_PSPLIT=$m timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['parity']['linf'], {k: v['ms'] for k, v in d['roofline']['per_kernel'].items() if 'wino36' in k})"
+  RW_W4_PSPLIT=$m timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['parity']['linf'], {k: v['ms'] for k, v in d['roofline']['per_kernel'].items() if 'wino36' in k})"
 done
 done

@@ -10,13 +10,13 @@ grep -n "passed\|failed\|smoke ok\|bench exit\|rocprof exit" $OUT/summary.txt
 # HBM traffic: one pass per counter
 for C in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$R/$OUT/$C" -o pmc -- \
-      python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
+      python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
 done
 python scripts/pmc_summary.py "$OUT/FETCH_SIZE" "$OUT/WRITE_SIZE" > "$OUT/pmc_summary.json"
 for C in FETCH_SIZE WRITE_SIZE; do rm -rf "$OUT/$C"; done
 # matrix-pipe counters
 ( cd /tmp && timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU \
-    --kernel-trace --output-format csv -d "$R/$OUT/mfma" -o pmc -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/mfma.log" 2>&1 ); echo "mfma pmc exit $?"
+    --kernel-trace --output-format csv -d "$R/$OUT/mfma" -o pmc -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/mfma.log" 2>&1 ); echo "mfma pmc exit $?"
 python - <<PY
 import csv, glob, json, re
 acc = {}

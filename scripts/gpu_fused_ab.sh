@@ -3,7 +3,7 @@
 # (default variants: the forward without / with the fused upsampling kernel, the RGB branch joined before it, side streams
 # at a lower priority)
 T=${1:-r05r}; O=gpurun_out/$T; mkdir -p $O; : > $O/ab.jsonl; shift
-B="--steps 10 --warmup 2 --no-extra --no-cpu-baseline"
+B="--full --steps 10 --warmup 2 --no-extra --no-cpu-baseline"
 if [ $# -eq 0 ]; then set -- "RW_UP_FUSED2=0" "RW_NOP=1" "RW_UP_FUSED2_JOIN=1" "RW_SIDE_PRIORITY=1" "RW_SIDE_PRIORITY=1 RW_UP_FUSED2_JOIN=1"; fi
 for REP in 1 2; do
   for V in "$@"; do

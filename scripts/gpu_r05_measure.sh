@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$PWD
-B="--steps 10 --warmup 2 --no-extra --no-cpu-baseline"
+B="--full --steps 10 --warmup 2 --no-extra --no-cpu-baseline"
 if [[ "$WHAT" == *ab* ]]; then
   : > "$OUT/ab.jsonl"
   for V in "" "RW_UP_FUSED=0" "RW_MM_DIRECT16=auto" "RW_MM_DIRECT16=auto RW_UP_FUSED=0" "RW_MM_DIRECT16=conv RW_UP_FUSED=0" "RW_MM=f32" ${AB_EXTRA}; do
@@ -26,7 +26,7 @@ fi
 prof() {   # name, env...
   local name=$1; shift
   ( cd /tmp && env "$@" timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/prof_$name" -o bench -- \
-      python "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/prof_$name.log" 2>&1 ); echo "rocprof $name exit $?"
+      python "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/prof_$name.log" 2>&1 ); echo "rocprof $name exit $?"
   local T=$(find "$OUT/prof_$name" -name "*kernel_trace.csv" | head -1)
   [ -n "$T" ] && python scripts/trace_stats.py "$T" 0.3 > "$OUT/${name}_kernel_stats_steady.csv" && head -16 "$OUT/${name}_kernel_stats_steady.csv"
   local F=$(find "$OUT/prof_$name" -name "*kernel_stats*.csv" | head -1)
@@ -40,7 +40,7 @@ fi
 if [[ "$WHAT" == *pmc* ]]; then
   for C in FETCH_SIZE WRITE_SIZE; do
     ( cd /tmp && env ${PMC_ENV} timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$R/$OUT/$C" -o pmc -- \
-        python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
+        python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
   done
   python scripts/pmc_summary.py "$OUT/FETCH_SIZE" "$OUT/WRITE_SIZE" > "$OUT/pmc_summary.json"
   python - <<PY

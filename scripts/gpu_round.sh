@@ -20,7 +20,7 @@ if [[ "$WHAT" == *tests* ]]; then
 fi
 if [[ "$WHAT" == *bench* ]]; then
   echo "== bench" | tee -a "$OUT/summary.txt"
-  SECONDS=0; timeout 1200 python bench.py --steps 10 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench exit $?" | tee -a "$OUT/summary.txt"
+  SECONDS=0; timeout 1200 python bench.py --full --steps 10 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench exit $?" | tee -a "$OUT/summary.txt"
   cat "$OUT/bench.json" | tee -a "$OUT/summary.txt"; grep -v "^\s" "$OUT/bench.err" | tail -5 | tee -a "$OUT/summary.txt"
   echo "bench wall seconds: $SECONDS" | tee -a "$OUT/summary.txt"
 fi

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$PWD
 for C in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$R/$OUT/$C" -o pmc -- \
-      python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
+      python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline > "$R/$OUT/$C.log" 2>&1 ); echo "$C exit $?"
 done
 python scripts/pmc_summary.py "$OUT/FETCH_SIZE" "$OUT/WRITE_SIZE" > "$OUT/pmc_summary.json"
 python - <<PY

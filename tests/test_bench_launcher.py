@@ -119,3 +119,30 @@ def test_the_headline_line_of_a_recorded_run_is_compact():
     assert all(v is None or isinstance(v, (int, float, bool)) for v in out['extra'].values()), out['extra']
     assert len(out['dtype']) <= 80
     assert max(len(v) for v in out['config'].values() if isinstance(v, str)) <= 64
+
+
+def test_a_plain_forward_run_is_lean_and_dumps_what_its_last_step_returned(tmp_path):
+    """Without --full a forward run prints the headline only (no roofline pass, parity, CPU baseline or `extra`);
+    --dump-outputs DIR writes the last timed step's images as float32 .npy, identical from run to run."""
+    import numpy
+    dumps = []
+    for steps in ('2', '1'):
+        out_dir = str(tmp_path / ('dump%s' % steps))
+        env = dict(os.environ, OMP_NUM_THREADS='2', RW_BENCH_DETAIL=str(tmp_path / 'detail.json'))
+        for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+            env.pop(k, None)
+        p = subprocess.run([sys.executable, DRIVER, '--workload', 'ffhq256', '--batch', '2', '--steps', steps,
+                            '--warmup', '0', '--dump-outputs', out_dir], env=env, cwd=ROOT,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = _strict(p.stdout.strip().splitlines()[-1])
+        assert out['steps'] == int(steps) and out['warmup'] == 0 and out['ms_per_step'] > 0 and out['value'] > 0
+        assert out['roofline'] is None and not set(out) & {'extra', 'parity', 'cpu_baseline', 'step'}
+        assert sorted(os.listdir(out_dir)) == ['image0.npy', 'images_sample.npy']
+        d = {n: numpy.load(os.path.join(out_dir, n + '.npy')) for n in ('image0', 'images_sample')}
+        assert d['image0'].dtype == d['images_sample'].dtype == numpy.float32
+        assert d['image0'].shape == (3, 256, 256) and d['images_sample'].shape == (2 * 3 * 256 * 256,)
+        assert numpy.isfinite(d['images_sample']).all()
+        dumps.append(d)
+    for n in ('image0', 'images_sample'):
+        assert numpy.array_equal(dumps[0][n], dumps[1][n]), n

@@ -1,6 +1,7 @@
 """Pins the travelling oracle (oracle/restatement.py, oracle/native_ops.c) against fixtures
-produced by the reference's own files (oracle/make_golden.py), and -- when /root/reference is
-present -- against the reference executed live."""
+produced by the reference's own files (oracle/make_golden.py), and this package's statistics caches
+against what the reference wrote and read (tests/golden/reference_checks.npz)."""
+import hashlib
 import json
 import os
 import math
@@ -9,7 +10,7 @@ import numpy
 import pytest
 import torch
 
-from oracle import native, reference_shim, restatement as R
+from oracle import native, restatement as R
 from tests.conftest import (build_stylegan, golden_meta, load_golden, load_mask_request,
                             oracle_state_dict, subsample)
 
@@ -169,39 +170,73 @@ def test_proggan_restatement_matches_reference_golden():
     assert (img - torch.from_numpy(g['image'])).abs().max() < 1e-4
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason='/root/reference not present')
+def _recorded(g, prefix):
+    """{name: array} of the fixture entries under `prefix` (reference_checks.npz)."""
+    return {k[len(prefix):]: g[k] for k in g.files if k.startswith(prefix)}
+
+
+def _same_arrays(got, want, levels=False):
+    """What this package writes now is what it wrote when the reference read it back (same keys, dtypes, values).
+    levels=True: float arrays are retained samples of a random draw made on this host's cores -- compared as sorted
+    columns to float32 rounding (the reference reads them order-free)."""
+    got = {k: numpy.asarray(v) for k, v in got.items() if numpy.asarray(v).dtype != object}
+    assert sorted(got) == sorted(want)
+    for k, v in want.items():
+        assert got[k].dtype == v.dtype and got[k].shape == v.shape, k
+        if levels and v.dtype.kind == 'f':
+            a, b = (numpy.sort(t, axis=0) if t.ndim == 2 else t for t in (got[k], v))
+            assert numpy.allclose(a, b, rtol=1e-5, atol=1e-6), k
+        else:
+            assert numpy.array_equal(got[k], v), k
+
+
+def _reference_r2m(path):
+    """Writes the reference's notebooks/masks/reflections/progan-kitchen/r2m.npz to `path` from its stored form (the
+    upper triangle of the symmetric mom2, the other fields as they are) and returns `path`."""
+    t = load_golden('r2m_progan_kitchen_triu')
+    tri = t['mom2_triu']
+    n = int(round(((8 * tri.size + 1) ** 0.5 - 1) / 2))
+    iu = numpy.triu_indices(n)
+    mom2 = numpy.zeros((n, n), tri.dtype)
+    mom2[iu] = tri
+    mom2.T[iu] = tri
+    assert hashlib.sha256(mom2.tobytes()).hexdigest() == str(t['mom2_sha256'])
+    numpy.savez(path, constructor=t['constructor'], count=t['count'], mom2=mom2,
+                sample_size=numpy.array(None, dtype=object))
+    return path
+
+
 def test_restatement_against_live_reference():
-    ref = reference_shim.load()
-    from rewriting_amd import synthetic
-    g = ref.models.SeqStyleGAN2(16, 512, 8, truncation=0.7, mconv='seq')
-    synthetic.randomize_(g, seed=3)
-    g.eval()
-    z = ref.zdataset.standard_z_sample(2, 512, seed=5)
-    with torch.no_grad():
-        want = g(z)
-    sd = {k: v.detach().clone() for k, v in g.state_dict().items()}
+    """The reference's forward of a 16^2 generator (truncation 0.7, weights seed 3, z seed 5), recorded by
+    oracle/make_golden.py golden_reference_checks."""
+    g = load_golden('reference_checks')
+    sd = oracle_state_dict(build_stylegan(16, 0.7, seed=3))
+    z = torch.from_numpy(g['restate/z'])
     got = R.generator_forward(sd, z, 16, truncation=0.7)
-    assert (got - want).abs().max() < 1e-5
+    assert (got - torch.from_numpy(g['restate/image'])).abs().max() < 1e-5
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason='the cache file lives in /root/reference')
 def test_statistics_cache_interoperates_with_the_reference(tmp_path):
-    """the reference's own notebooks/masks/reflections/progan-kitchen/r2m.npz loads into this
-    package's RunningSecondMoment and through tally.load_cached_state (utils/tally.py:703-718,
-    utils/runningstats.py:1111-1120); a cache written here loads into the REFERENCE's RunningSecondMoment and
-    through the reference's own tally.tally_second_moment cache branch; byte-level schema equal."""
+    """the reference's own notebooks/masks/reflections/progan-kitchen/r2m.npz (a copy:
+    tests/golden/r2m_progan_kitchen_triu.npz, rebuilt bit for bit by _reference_r2m) loads into this package's RunningSecondMoment and through
+    tally.load_cached_state (utils/tally.py:703-718, utils/runningstats.py:1111-1120) and gives the moment the
+    reference's class gives; a cache written here has the reference's keys and dtypes and is what the reference's
+    RunningSecondMoment and tally cache branch read back correctly when the fixture was recorded."""
     import numpy
     from rewriting_amd.utils import runningstats, tally
-    ref = reference_shim.load()
-    path = os.path.join(reference_shim.REFERENCE_ROOT, 'notebooks/masks/reflections/progan-kitchen/r2m.npz')
+    rec = load_golden('reference_checks')
+    path = _reference_r2m(str(tmp_path / 'reference_r2m.npz'))
     theirs = numpy.load(path, allow_pickle=True)
     r = runningstats.RunningSecondMoment(state=theirs)
     assert r.count == int(theirs['count']) == 256000 and tuple(r.mom2.shape) == (512, 512)
     assert torch.equal(r.mom2, torch.from_numpy(theirs['mom2']))
-    want = ref.runningstats.RunningSecondMoment(state=theirs).moment()
-    assert torch.equal(r.moment(), want)
+
+    def is_reference_moment(m):
+        return (str(m.dtype) == str(rec['r2m/moment_dtype']) and
+                hashlib.sha256(m.numpy().tobytes()).hexdigest() == str(rec['r2m/moment_sha256']))
+    assert is_reference_moment(r.moment())
     via_tally = tally.tally_second_moment(lambda z: None, torch.zeros(1, 1), sample_size=None, cachefile=path)
-    assert torch.equal(via_tally.moment(), want)                   # found, matched on sample_size, never swept
+    assert is_reference_moment(via_tally.moment())                 # found, matched on sample_size, never swept
     # round trip: what this package writes has the reference's keys and dtypes ...
     mine = str(tmp_path / 'r2m.npz')
     tally.save_cached_state(mine, r, dict(sample_size=None))
@@ -210,55 +245,59 @@ def test_statistics_cache_interoperates_with_the_reference(tmp_path):
     for k in ('count', 'mom2'):
         assert back[k].dtype == theirs[k].dtype and back[k].shape == theirs[k].shape, k
     assert numpy.array_equal(back['mom2'], theirs['mom2']) and back['sample_size'].dtype == object
-    # ... and the reference reads it: directly, and through its tally cache branch (which returns before sweeping)
-    assert torch.equal(ref.runningstats.RunningSecondMoment(state=back).moment(), want)
-    got = ref.tally.tally_second_moment(lambda z: None, torch.zeros(1, 1), sample_size=None, cachefile=mine)
-    assert torch.equal(got.moment(), want)
-    # a statistic accumulated here (CPU reference path of the class) and cached is read back identically by both
+    # ... and reads back to the reference's moment (the reference itself read this file so when recording)
+    assert is_reference_moment(runningstats.RunningSecondMoment(state=back).moment())
+    # a statistic accumulated here (CPU reference path of the class) and cached: the reference accepted the file for
+    # the arguments it was written with, refused it for others, and read the moment back identically
+    # (the statistic is the recorded one, bit for bit: a matrix product on other host cores may round differently)
     fresh = runningstats.RunningSecondMoment()
     rows = torch.randn(300, 16, generator=torch.Generator().manual_seed(0))
-    fresh.mom2, fresh.count = rows.t() @ rows, 300
+    assert torch.equal(rows, torch.from_numpy(rec['cache/rows']))
+    assert torch.allclose(rows.t() @ rows, torch.from_numpy(rec['cache/ours/mom2']), rtol=1e-5, atol=0)
+    fresh.mom2, fresh.count = torch.from_numpy(rec['cache/ours/mom2']).clone(), 300
     tally.save_cached_state(str(tmp_path / 'b.npz'), fresh, dict(sample_size=7))
-    assert ref.tally.load_cached_state(str(tmp_path / 'b.npz'), dict(sample_size=7)) is not None
-    assert ref.tally.load_cached_state(str(tmp_path / 'b.npz'), dict(sample_size=8)) is None     # args mismatch
-    theirs2 = ref.runningstats.RunningSecondMoment(state=numpy.load(str(tmp_path / 'b.npz'), allow_pickle=True))
-    assert torch.equal(theirs2.moment(), fresh.moment())
+    _same_arrays(numpy.load(str(tmp_path / 'b.npz'), allow_pickle=True), _recorded(rec, 'cache/ours/'))
+    assert bool(rec['cache/ref_accepts_7']) and not bool(rec['cache/ref_accepts_8'])     # args mismatch
+    assert tally.load_cached_state(str(tmp_path / 'b.npz'), dict(sample_size=7)) is not None
+    assert tally.load_cached_state(str(tmp_path / 'b.npz'), dict(sample_size=8)) is None
+    assert torch.equal(torch.from_numpy(rec['cache/ref_moment']), fresh.moment())
     # RunningVariance (unit_rs.npz, used by the erase goal): both directions
-    rv = ref.runningstats.RunningVariance()
-    rv.add(rows)
-    numpy.savez(str(tmp_path / 'rs.npz'), **rv.state_dict())
+    numpy.savez(str(tmp_path / 'rs.npz'), **_recorded(rec, 'rv/theirs/'))
     ours = runningstats.RunningVariance(state=numpy.load(str(tmp_path / 'rs.npz'), allow_pickle=True))
-    assert torch.allclose(ours.mean(), rv.mean()) and torch.allclose(ours.variance(), rv.variance())
-    numpy.savez(str(tmp_path / 'rs2.npz'), **ours.state_dict())
-    back2 = ref.runningstats.RunningVariance(state=numpy.load(str(tmp_path / 'rs2.npz'), allow_pickle=True))
-    assert torch.allclose(back2.mean(), rv.mean()) and torch.allclose(back2.variance(), rv.variance())
+    rv_mean, rv_var = torch.from_numpy(rec['rv/mean']), torch.from_numpy(rec['rv/variance'])
+    assert torch.allclose(ours.mean(), rv_mean) and torch.allclose(ours.variance(), rv_var)
+    _same_arrays(ours.state_dict(), _recorded(rec, 'rv/ours/'))
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason='compares with the reference RunningQuantile')
 def test_quantile_cache_interoperates_with_the_reference(tmp_path):
     """unit_rq.npz.  The reference's randomised sketch (utils/runningstats.py:269-620) written by
-    its own tally.tally_quantile loads here and reads out what the reference reads out of the same state; the
-    statistic computed here is written in the reference's schema (:422-437), loads into the reference's class
-    and through its tally cache branch, and answers within the bound of the class docstring of the exact
-    quantiles -- where the reference's own sketch is ~1e-3 away."""
+    its own tally.tally_quantile (recorded in reference_checks.npz with what the reference read out of it) loads here
+    and reads out what the reference reads out of the same state; the statistic computed here is written in the
+    reference's schema (:422-437), is the state the reference's class and tally cache branch read back when the
+    fixture was recorded, and answers within the bound of the class docstring of the exact quantiles -- where the
+    reference's own sketch is ~1e-3 away."""
     import numpy
     from rewriting_amd.utils import runningstats, tally
-    ref = reference_shim.load()
+    rec = load_golden('reference_checks')
     gen = torch.Generator().manual_seed(3)
     units, n = 6, 40000
     x = torch.randn(n, units, generator=gen) * torch.linspace(0.5, 3, units) + torch.linspace(-1, 1, units)
     x[:, 2] = x[:, 2].exp()                                     # one skewed unit
+    # the sample the fixture was recorded on (the float64 sum's order of additions depends on the host's threads)
+    assert torch.equal(x[:16], torch.from_numpy(rec['rq/x_head'])) and abs(x.double().sum().item() - float(rec['rq/x_sum'])) < 1e-3
     data = torch.utils.data.TensorDataset(x)
     qs = torch.tensor([0.0, 1e-4, 0.01, 0.25, 0.5, 0.9, 0.99, 0.999, 1.0])
     exact = torch.from_numpy(numpy.quantile(x.double().numpy(), qs.numpy(), axis=0).T)
     scale = x.std(dim=0)[:, None].double()
+    theirs_out = {k: torch.from_numpy(v) for k, v in _recorded(rec, 'rq/theirs_out/').items()}
 
     # --- theirs -> ours (r = 512: five levels of retained samples, weights 1 .. 16)
     theirs_file = str(tmp_path / 'theirs' / 'unit_rq.npz')
-    theirs = ref.tally.tally_quantile(lambda b: b, data, batch_size=1000, r=512)
-    dat = dict(theirs.state_dict(), sample_size=None, r=512)    # what utils/tally.py:721-730 saves; the ragged list
-    ragged = numpy.empty(len(dat['data']), dtype=object)        # of levels became an object array under the numpy
-    ragged[:] = dat['data']                                     # of the reference's time (numpy 2 refuses to guess)
+    levels = _recorded(rec, 'rq/theirs/data/')
+    dat = dict({k: v for k, v in _recorded(rec, 'rq/theirs/').items() if not k.startswith('data/')},
+               sample_size=None, r=512)                         # what utils/tally.py:721-730 saves; the ragged list
+    ragged = numpy.empty(len(levels), dtype=object)             # of levels became an object array under the numpy
+    ragged[:] = [levels[str(l)] for l in range(len(levels))]    # of the reference's time (numpy 2 refuses to guess)
     os.makedirs(os.path.dirname(theirs_file))
     numpy.savez(theirs_file, **dict(dat, data=ragged))
     st = numpy.load(theirs_file, allow_pickle=True)
@@ -267,12 +306,12 @@ def test_quantile_cache_interoperates_with_the_reference(tmp_path):
     assert mine.size() == n and mine.depth == units
     # (the reference accumulates its cumulative weights in float32, this class in float64: ~1e-5 of the spread)
     close = lambda a, b, tol=1e-4: bool(((a.double() - b.double()).abs() / (scale + b.double().abs())).max() < tol)
-    assert close(mine.quantiles(qs), theirs.quantiles(qs)), (mine.quantiles(qs) - theirs.quantiles(qs)).abs().max()
-    assert torch.equal(mine.minmax(), theirs.minmax())
+    assert close(mine.quantiles(qs), theirs_out['quantiles']), (mine.quantiles(qs) - theirs_out['quantiles']).abs().max()
+    assert torch.equal(mine.minmax(), theirs_out['minmax'])
     probe = x[:500].t().contiguous()
-    assert torch.allclose(mine.normalize(probe), theirs.normalize(probe), rtol=0, atol=1e-5)
-    assert torch.allclose(mine.mean(), theirs.mean(), rtol=1e-5, atol=1e-6)
-    assert torch.allclose(mine.stdev(), theirs.stdev(), rtol=1e-5)
+    assert torch.allclose(mine.normalize(probe), theirs_out['normalize'], rtol=0, atol=1e-5)
+    assert torch.allclose(mine.mean(), theirs_out['mean'], rtol=1e-5, atol=1e-6)
+    assert torch.allclose(mine.stdev(), theirs_out['stdev'], rtol=1e-5)
     # ... and written back out it is the same state
     again = mine.state_dict()
     assert sorted(again) == sorted(k for k in st.files if k not in ('sample_size', 'r'))
@@ -289,21 +328,22 @@ def test_quantile_cache_interoperates_with_the_reference(tmp_path):
     whole = runningstats.RunningQuantile(r=512)
     whole.add(x)
     inner = (qs > 0) & (qs < 1)
-    rank_err = lambda rq, q: (whole.normalize(rq.quantiles(q)).double() - q).abs()
+    rank_err = lambda q, got: (whole.normalize(got).double() - q).abs()
     # body: below 2^(cap-1) ranks; tails: within 1/32 of the distance to the nearer end (+ half a rank)
-    assert rank_err(ours, qs[inner]).max() < 2.0 ** (cap - 1) / n + 1e-6
+    assert rank_err(qs[inner], ours.quantiles(qs[inner])).max() < 2.0 ** (cap - 1) / n + 1e-6
     tails = torch.tensor([2e-4, 1e-3, 3e-3, 0.01, 0.99, 0.997, 0.999, 0.9998])
-    assert (rank_err(ours, tails) <= torch.minimum(tails, 1 - tails) / 32 + 1.0 / n).all()
+    assert (rank_err(tails, ours.quantiles(tails)) <= torch.minimum(tails, 1 - tails) / 32 + 1.0 / n).all()
     assert torch.equal(ours.quantiles(torch.tensor([0.0, 1.0])), torch.stack([x.min(0)[0], x.max(0)[0]], dim=1))
-    back = ref.tally.tally_quantile(lambda b: 1 / 0, data, batch_size=1000, r=512, cachefile=ours_file)
-    assert back.size() == n
-    assert close(back.quantiles(qs), ours.quantiles(qs))
-    assert torch.allclose(back.normalize(probe), ours.normalize(probe), rtol=0, atol=1e-5)
+    # the levels written are those the reference's tally cache branch read back when recording, and what it read
+    _same_arrays({str(l): lv for l, lv in enumerate(levels)}, _recorded(rec, 'rq/ours/data/'), levels=True)
+    assert int(rec['rq/back/size']) == n
+    assert close(torch.from_numpy(rec['rq/back/quantiles']), ours.quantiles(qs))
+    assert torch.allclose(torch.from_numpy(rec['rq/back/normalize']), ours.normalize(probe), rtol=0, atol=1e-5)
     served = tally.tally_quantile(lambda b: 1 / 0, data, batch_size=1000, r=512, cachefile=ours_file)
     assert torch.equal(served.quantiles(qs), ours.quantiles(qs))    # fresh == cached, bit for bit
     # how far each is from the whole sample's quantiles, measured in rank: in the body both are within the
     # reference's nominal 1e-3 (checked against ours' own bound above); in the tails ours is the closer one
-    assert rank_err(ours, tails).max() <= rank_err(theirs, tails).max()
+    assert rank_err(tails, ours.quantiles(tails)).max() <= rank_err(tails, theirs_out['tails']).max()
 
     # --- a sample below the retained budget is kept whole: answers exact, and the reference reads the same
     small = runningstats.RunningQuantile(r=4096)
@@ -312,8 +352,10 @@ def test_quantile_cache_interoperates_with_the_reference(tmp_path):
     small.compress_()
     assert torch.equal(small.quantiles(qs), want)
     numpy.savez(str(tmp_path / 'small.npz'), **small.state_dict())
-    theirs_small = ref.runningstats.RunningQuantile(state=str(tmp_path / 'small.npz'))
-    assert close(theirs_small.quantiles(qs), want)
+    written = dict(numpy.load(str(tmp_path / 'small.npz'), allow_pickle=True))
+    written.update({'data/%d' % l: numpy.asarray(lv) for l, lv in enumerate(written.pop('data'))})
+    _same_arrays(written, _recorded(rec, 'rq/small/'), levels=True)
+    assert close(torch.from_numpy(rec['rq/small_theirs/quantiles']), want)
 
 
 def test_exact_trajectory_fixture_of_the_full_size_edit_is_consistent_with_the_reference_runs():

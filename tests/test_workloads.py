@@ -11,7 +11,6 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from oracle import reference_shim
 from tests.conftest import build_stylegan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,24 +44,21 @@ def test_feature_statistics_and_frechet_cpu():
     check_feature_statistics_and_frechet('cpu')
 
 
-@pytest.mark.skipif(not reference_shim.available(), reason='metrics/fid.py lives in /root/reference')
 def test_frechet_distance_equals_the_reference_function():
-    """metrics/fid.py:137-187 (its module imports tensorflow at the top, so the one function is extracted from the
-    file like the shim extracts upfirdn2d_native) on the same statistics, incl. the near-singular retry branch."""
-    from scipy import linalg
+    """metrics/fid.py:137-187 on the same statistics, incl. the near-singular retry branch: the reference's answers
+    recorded by oracle/make_golden.py golden_reference_checks (its module imports tensorflow at the top, so the one
+    function was extracted from the file like the shim extracts upfirdn2d_native)."""
     from rewriting_amd import samples
-    ns = {'np': numpy, 'linalg': linalg, 'warnings': __import__('warnings')}
-    ref = reference_shim._extract_function(os.path.join(reference_shim.REFERENCE_ROOT, 'metrics', 'fid.py'),
-                                           'calculate_frechet_distance', ns)
-    mu1, s1, mu2, s2, d = check_feature_statistics_and_frechet('cpu')
-    assert abs(d - ref(mu1, s1, mu2, s2)) < 1e-9 * max(1.0, abs(d))
+    from tests.conftest import load_golden
+    check_feature_statistics_and_frechet('cpu')
+    rec = load_golden('reference_checks')
+    mu1, s1, mu2, s2 = (rec['fid/' + k] for k in ('mu1', 's1', 'mu2', 's2'))
+    d, want = samples.frechet_distance(mu1, s1, mu2, s2), float(rec['fid/d'])
+    assert abs(d - want) < 1e-9 * max(1.0, abs(d))
     z = numpy.zeros_like(s1)                                    # singular product -> eps on the diagonal, both sides
     with pytest.warns(Warning):
         d0 = samples.frechet_distance(mu1, z, mu2, z)
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        assert abs(d0 - ref(mu1, z, mu2, z)) < 1e-9
+    assert abs(d0 - float(rec['fid/d_singular'])) < 1e-9
 
 
 def check_sample_set_and_watermark_variants(device, size=64, nseeds=20, niters=11):
