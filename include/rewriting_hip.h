@@ -43,12 +43,23 @@ const char* rw_error_string(int code);
 /* ---------------------------------------------------------------------------------------
  * L1 native ops -- replace the two pybind entry points of utils/stylegan2/op/
  *
- * fp32 ONLY.  The reference's modules dispatch float, double and half (AT_DISPATCH_FLOATING_TYPES_AND_HALF,
- * fused_bias_act_kernel.cu:79, upfirdn2d_kernel.cu:225); every entry of this library takes `float` pointers -- the
- * path it accelerates runs in fp32 end to end (BASELINE.json: "images within 1e-3 L-inf fp32").  A model cast with
- * .double() or .half() does not reach these entries: the Python wrappers (rewriting_amd/hip.py, the ctypes stub of
- * INTEGRATION.md) refuse any other dtype with an error that names this limit (the status of the refusal is
- * RW_ERR_UNSUPPORTED: nothing was launched), they never convert silently.
+ * Three dtypes here, fp32 everywhere else.  These three ops -- fused_bias_act, bias_grad, upfirdn2d -- take float
+ * (_f32), double (_f64) and half (_f16) buffers, as the reference's modules dispatch float, double and half
+ * (AT_DISPATCH_FLOATING_TYPES_AND_HALF, fused_bias_act_kernel.cu:79, upfirdn2d_kernel.cu:225).  Each dtype form takes
+ * the same arguments as its _f32 twin, and every operand (bias, refer, filter taps) comes in the dtype
+ * of the input (the reference reads them through data_ptr<scalar_t>()).  Half buffers are uint16_t* holding IEEE
+ * binary16.
+ *   - _f64: the fp32 kernel's arithmetic in double; alpha and scale are passed as double.
+ *   - _f16: each value is widened to float on load, goes through exactly the fp32 kernel's arithmetic in the same
+ *     order, and is rounded to half ONCE, at the store: an _f16 result equals the _f32 entry run on the widened inputs,
+ *     then rounded (round to nearest even).  bias_grad sums in float, as torch.sum does for half.  This differs from
+ *     the reference's half path, which rounds after every operation and rounds alpha and scale to half.
+ * Every other entry of this library is fp32 ONLY: it takes `float` pointers -- the path it accelerates runs in fp32 end
+ * to end (BASELINE.json: "images within 1e-3 L-inf fp32").  A model cast with .double() or .half() does not reach those
+ * entries: the Python wrappers (rewriting_amd/hip.py) refuse any other dtype with an error that names this limit (the
+ * status of the refusal is RW_ERR_UNSUPPORTED: nothing was launched), they never convert silently.  The ctypes stub
+ * of INTEGRATION.md dispatches on the input's dtype to the three forms above and refuses any other dtype, or an
+ * operand of another dtype, before anything is launched.
  * ------------------------------------------------------------------------------------- */
 
 /* fused_bias_act(input, bias, refer, act, grad, alpha, scale)
@@ -59,10 +70,20 @@ const char* rw_error_string(int code);
 int rw_fused_bias_act_f32(const float* x, const float* b, const float* ref, float* y,
                           int64_t n, int64_t step_b, int64_t size_b,
                           int act, int grad, float alpha, float scale, rw_stream_t stream);
+int rw_fused_bias_act_f16(const uint16_t* x, const uint16_t* b, const uint16_t* ref, uint16_t* y,
+                          int64_t n, int64_t step_b, int64_t size_b,
+                          int act, int grad, float alpha, float scale, rw_stream_t stream);
+int rw_fused_bias_act_f64(const double* x, const double* b, const double* ref, double* y,
+                          int64_t n, int64_t step_b, int64_t size_b,
+                          int act, int grad, double alpha, double scale, rw_stream_t stream);
 
 /* grad_bias = grad_input.sum(all dims but 1)   (utils/stylegan2/op/fused_act.py:32-39)
  * g viewed as (outer, channels, inner); gb[c] = sum_{o,i} g[o][c][i]. */
 int rw_bias_grad_f32(const float* g, float* gb, int64_t outer, int64_t channels, int64_t inner,
+                     rw_stream_t stream);
+int rw_bias_grad_f16(const uint16_t* g, uint16_t* gb, int64_t outer, int64_t channels, int64_t inner,
+                     rw_stream_t stream);
+int rw_bias_grad_f64(const double* g, double* gb, int64_t outer, int64_t channels, int64_t inner,
                      rw_stream_t stream);
 
 /* upfirdn2d(input[major,H,W,minor], kernel[kh,kw], up_x, up_y, down_x, down_y,
@@ -73,6 +94,14 @@ int rw_bias_grad_f32(const float* g, float* gb, int64_t outer, int64_t channels,
  * allocates y with that shape.  Any up/down/pad/kernel size (the reference compiles only
  * six modes, :178-210). */
 int rw_upfirdn2d_f32(const float* x, const float* k, float* y,
+                     int major, int in_h, int in_w, int minor, int kh, int kw,
+                     int up_x, int up_y, int down_x, int down_y,
+                     int pad_x0, int pad_x1, int pad_y0, int pad_y1, rw_stream_t stream);
+int rw_upfirdn2d_f16(const uint16_t* x, const uint16_t* k, uint16_t* y,
+                     int major, int in_h, int in_w, int minor, int kh, int kw,
+                     int up_x, int up_y, int down_x, int down_y,
+                     int pad_x0, int pad_x1, int pad_y0, int pad_y1, rw_stream_t stream);
+int rw_upfirdn2d_f64(const double* x, const double* k, double* y,
                      int major, int in_h, int in_w, int minor, int kh, int kw,
                      int up_x, int up_y, int down_x, int down_y,
                      int pad_x0, int pad_x1, int pad_y0, int pad_y1, rw_stream_t stream);

@@ -8,7 +8,7 @@ wrappers raise.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint,
                     c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -51,8 +51,16 @@ SIGNATURES = {
     'rw_error_string': (c_char_p, [c_int]),
     'rw_fused_bias_act_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                       c_int64, c_int, c_int, c_float, c_float, c_void_p]),
+    'rw_fused_bias_act_f16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                      c_int64, c_int, c_int, c_float, c_float, c_void_p]),
+    'rw_fused_bias_act_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                      c_int64, c_int, c_int, c_double, c_double, c_void_p]),
     'rw_bias_grad_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    'rw_bias_grad_f16': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    'rw_bias_grad_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     'rw_upfirdn2d_f32': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
+    'rw_upfirdn2d_f16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
+    'rw_upfirdn2d_f64': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 14 + [c_void_p]),
     'rw_pixel_norm_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     'rw_equal_linear_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_int64, c_float, c_float, c_int, c_float, c_float, c_void_p]),

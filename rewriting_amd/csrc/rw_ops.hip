@@ -1,4 +1,7 @@
-// hipcc-flags: -fno-slp-vectorize -fno-vectorize
+// hipcc-flags: -fno-slp-vectorize -fno-vectorize -Xclang -target-feature -Xclang -fma-mix-insts
+// (no v_fma_mix* either: the half forms of the L1 ops would otherwise fold their widening into v_fma_mix_f32, a VOP3P
+// instruction, and their rounding into v_fma_mixlo_f16, which rounds a product straight to half -- not the f32 result
+// rounded once that the header promises.  The f32 kernels are the same code with or without it.)
 // (no PACKED fp32 math -- v_pk_fma_f32 / v_pk_mul_f32 -- in this file's kernels: they are the streaming kernels that run on the
 // side streams BESIDE the convolutions' MFMAs.  Round 5 found (scripts/interference_repro.py, profiles/r05i, r05l): with
 // rw_tconv.hip's kernel running on another stream, to_rgb_kernel's v_pk_fma_f32 results came back wrong in the low half of
@@ -29,95 +32,169 @@ extern "C" const char* rw_error_string(int code) {
 }
 
 // ---------------------------------------------------------------------------------------
+// The three L1 ops below take three storage types (include/rewriting_hip.h): float, double and IEEE binary16 (_Float16
+// here, uint16_t at the ABI).  RwAcc<T> is the type each computes in: float and double compute in themselves; a half is
+// widened to float on load, goes through exactly the fp32 arithmetic in the same order, and is rounded to half once, at
+// the store -- so an f16 result is the f32 entry's result on the widened inputs, rounded.  The float instantiations keep
+// the fp32 kernels' arithmetic, operation for operation.
+// ---------------------------------------------------------------------------------------
+template <typename T> struct RwAcc { typedef T type; };
+template <> struct RwAcc<_Float16> { typedef float type; };
+
+// ---------------------------------------------------------------------------------------
 // fused_bias_act   (reference: utils/stylegan2/op/fused_bias_act_kernel.cu:18-49)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float rw_bias_act_one(float x, float ref, int code, float alpha, float scale) {
-  float y;
+template <typename A>
+__device__ __forceinline__ A rw_bias_act_one(A x, A ref, int code, A alpha, A scale) {
+  A y;
   switch (code) {
     default:
     case 10: y = x; break;
     case 11: y = x; break;
-    case 12: y = 0.0f; break;
-    case 30: y = (x > 0.0f) ? x : x * alpha; break;
-    case 31: y = (ref > 0.0f) ? x : x * alpha; break;
-    case 32: y = 0.0f; break;
+    case 12: y = A(0); break;
+    case 30: y = (x > A(0)) ? x : x * alpha; break;
+    case 31: y = (ref > A(0)) ? x : x * alpha; break;
+    case 32: y = A(0); break;
   }
   return y * scale;
 }
 
-template <bool VEC4>
+// VEC: one 16-byte access per lane and operand -- 4 floats, 2 doubles or 8 halves (L); the host takes it when x, ref and
+// y are 16-byte aligned and n and step_b are multiples of L (then the L elements of a lane share one bias entry).
+template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) fused_bias_act_kernel(
-    const float* __restrict__ x, const float* __restrict__ b, const float* __restrict__ ref,
-    float* __restrict__ y, int64_t n, int64_t step_b, int64_t size_b, int code, float alpha,
-    float scale) {
+    const T* __restrict__ x, const T* __restrict__ b, const T* __restrict__ ref,
+    T* __restrict__ y, int64_t n, int64_t step_b, int64_t size_b, int code, typename RwAcc<T>::type alpha,
+    typename RwAcc<T>::type scale) {
+  typedef typename RwAcc<T>::type A;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (VEC4) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-      float4 v = reinterpret_cast<const float4*>(x)[i];
-      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ref) r = reinterpret_cast<const float4*>(ref)[i];
-      if (b) {  // step_b % 4 == 0: the four lanes of the vector share one bias entry
-        const float bv = b[((i << 2) / step_b) % size_b];
-        v.x += bv; v.y += bv; v.z += bv; v.w += bv;
+  if (VEC) {
+    constexpr int L = 16 / sizeof(T), LOG2_L = L == 8 ? 3 : L == 4 ? 2 : 1;
+    typedef T vec_t __attribute__((ext_vector_type(L)));
+    const int64_t nv = n >> LOG2_L;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+      const vec_t xv = reinterpret_cast<const vec_t*>(x)[i];
+      A v[L];
+#pragma unroll
+      for (int e = 0; e < L; ++e) v[e] = (A)xv[e];
+      vec_t r = (T)0;
+      if (ref) r = reinterpret_cast<const vec_t*>(ref)[i];
+      if (b) {  // step_b % L == 0: the L lanes of the vector share one bias entry
+        const A bv = (A)b[((i << LOG2_L) / step_b) % size_b];
+#pragma unroll
+        for (int e = 0; e < L; ++e) v[e] += bv;
       }
-      float4 o;
-      o.x = rw_bias_act_one(v.x, r.x, code, alpha, scale);
-      o.y = rw_bias_act_one(v.y, r.y, code, alpha, scale);
-      o.z = rw_bias_act_one(v.z, r.z, code, alpha, scale);
-      o.w = rw_bias_act_one(v.w, r.w, code, alpha, scale);
-      reinterpret_cast<float4*>(y)[i] = o;
+      vec_t o;
+#pragma unroll
+      for (int e = 0; e < L; ++e) o[e] = (T)rw_bias_act_one<A>(v[e], (A)r[e], code, alpha, scale);
+      reinterpret_cast<vec_t*>(y)[i] = o;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-      float v = x[i];
-      if (b) v += b[(i / step_b) % size_b];
-      const float r = ref ? ref[i] : 0.0f;
-      y[i] = rw_bias_act_one(v, r, code, alpha, scale);
+      A v = (A)x[i];
+      if (b) v += (A)b[(i / step_b) % size_b];
+      const A r = ref ? (A)ref[i] : A(0);
+      y[i] = (T)rw_bias_act_one<A>(v, r, code, alpha, scale);
     }
   }
+}
+
+template <typename T>
+static int rw_fused_bias_act(const T* x, const T* b, const T* ref, T* y, int64_t n, int64_t step_b, int64_t size_b,
+                             int act, int grad, typename RwAcc<T>::type alpha, typename RwAcc<T>::type scale,
+                             rw_stream_t stream) {
+  if (n == 0) return 0;
+  RW_CHECK_ARG(x && y && n > 0);
+  RW_CHECK_ARG(!b || (step_b > 0 && size_b > 0));
+  const int code = act * 10 + grad;
+  const int64_t L = 16 / sizeof(T);
+  const bool aligned = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ref) & 15) == 0;
+  const bool vec = aligned && (n % L == 0) && (!b || step_b % L == 0);
+  if (vec) {
+    hipLaunchKernelGGL((fused_bias_act_kernel<T, true>), dim3(rw_stream_grid(n / L, 256)), dim3(256), 0,
+                       rw_s(stream), x, b, ref, y, n, step_b, size_b, code, alpha, scale);
+  } else {
+    hipLaunchKernelGGL((fused_bias_act_kernel<T, false>), dim3(rw_stream_grid(n, 256)), dim3(256), 0,
+                       rw_s(stream), x, b, ref, y, n, step_b, size_b, code, alpha, scale);
+  }
+  return RW_LAUNCH_RESULT();
 }
 
 extern "C" int rw_fused_bias_act_f32(const float* x, const float* b, const float* ref, float* y,
                                      int64_t n, int64_t step_b, int64_t size_b, int act, int grad,
                                      float alpha, float scale, rw_stream_t stream) {
-  if (n == 0) return 0;
-  RW_CHECK_ARG(x && y && n > 0);
-  RW_CHECK_ARG(!b || (step_b > 0 && size_b > 0));
-  const int code = act * 10 + grad;
-  const bool aligned = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)ref) & 15) == 0;
-  const bool vec = aligned && (n % 4 == 0) && (!b || step_b % 4 == 0);
-  if (vec) {
-    hipLaunchKernelGGL(fused_bias_act_kernel<true>, dim3(rw_stream_grid(n / 4, 256)), dim3(256), 0,
-                       rw_s(stream), x, b, ref, y, n, step_b, size_b, code, alpha, scale);
-  } else {
-    hipLaunchKernelGGL(fused_bias_act_kernel<false>, dim3(rw_stream_grid(n, 256)), dim3(256), 0,
-                       rw_s(stream), x, b, ref, y, n, step_b, size_b, code, alpha, scale);
-  }
-  return RW_LAUNCH_RESULT();
+  return rw_fused_bias_act<float>(x, b, ref, y, n, step_b, size_b, act, grad, alpha, scale, stream);
 }
 
-// grad_bias[c] = sum_{outer, inner} g[o][c][i]        (op/fused_act.py:32-39)
-__global__ void __launch_bounds__(256) bias_grad_kernel(const float* __restrict__ g,
-                                                        float* __restrict__ gb, int64_t outer,
+extern "C" int rw_fused_bias_act_f16(const uint16_t* x, const uint16_t* b, const uint16_t* ref, uint16_t* y,
+                                     int64_t n, int64_t step_b, int64_t size_b, int act, int grad,
+                                     float alpha, float scale, rw_stream_t stream) {
+  return rw_fused_bias_act<_Float16>(reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(b),
+                                     reinterpret_cast<const _Float16*>(ref), reinterpret_cast<_Float16*>(y), n, step_b,
+                                     size_b, act, grad, alpha, scale, stream);
+}
+
+extern "C" int rw_fused_bias_act_f64(const double* x, const double* b, const double* ref, double* y,
+                                     int64_t n, int64_t step_b, int64_t size_b, int act, int grad,
+                                     double alpha, double scale, rw_stream_t stream) {
+  return rw_fused_bias_act<double>(x, b, ref, y, n, step_b, size_b, act, grad, alpha, scale, stream);
+}
+
+// the double forms of rw_common.h's float reductions (bias_grad_kernel<double>)
+__device__ __forceinline__ double rw_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ double rw_block_sum_256(double v, double* lds4) {
+  v = rw_wave_sum(v);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) lds4[wave] = v;
+  __syncthreads();
+  return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+}
+
+// grad_bias[c] = sum_{outer, inner} g[o][c][i]        (op/fused_act.py:32-39); halves are summed in float, as
+// torch.sum sums them
+template <typename T>
+__global__ void __launch_bounds__(256) bias_grad_kernel(const T* __restrict__ g, T* __restrict__ gb, int64_t outer,
                                                         int64_t channels, int64_t inner) {
-  __shared__ float red[4];
+  typedef typename RwAcc<T>::type A;
+  __shared__ A red[4];
   const int64_t c = blockIdx.x;
-  float acc = 0.f;
+  A acc = A(0);
   for (int64_t o = 0; o < outer; ++o) {
-    const float* row = g + (o * channels + c) * inner;
-    for (int64_t i = threadIdx.x; i < inner; i += 256) acc += row[i];
+    const T* row = g + (o * channels + c) * inner;
+    for (int64_t i = threadIdx.x; i < inner; i += 256) acc += (A)row[i];
   }
   acc = rw_block_sum_256(acc, red);
-  if (threadIdx.x == 0) gb[c] = acc;
+  if (threadIdx.x == 0) gb[c] = (T)acc;
+}
+
+template <typename T>
+static int rw_bias_grad(const T* g, T* gb, int64_t outer, int64_t channels, int64_t inner, rw_stream_t stream) {
+  RW_CHECK_ARG(g && gb && outer > 0 && channels > 0 && inner > 0);
+  hipLaunchKernelGGL(bias_grad_kernel<T>, dim3((unsigned)channels), dim3(256), 0, rw_s(stream), g, gb,
+                     outer, channels, inner);
+  return RW_LAUNCH_RESULT();
 }
 
 extern "C" int rw_bias_grad_f32(const float* g, float* gb, int64_t outer, int64_t channels,
                                 int64_t inner, rw_stream_t stream) {
-  RW_CHECK_ARG(g && gb && outer > 0 && channels > 0 && inner > 0);
-  hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)channels), dim3(256), 0, rw_s(stream), g, gb,
-                     outer, channels, inner);
-  return RW_LAUNCH_RESULT();
+  return rw_bias_grad<float>(g, gb, outer, channels, inner, stream);
+}
+
+extern "C" int rw_bias_grad_f16(const uint16_t* g, uint16_t* gb, int64_t outer, int64_t channels,
+                                int64_t inner, rw_stream_t stream) {
+  return rw_bias_grad<_Float16>(reinterpret_cast<const _Float16*>(g), reinterpret_cast<_Float16*>(gb), outer,
+                                channels, inner, stream);
+}
+
+extern "C" int rw_bias_grad_f64(const double* g, double* gb, int64_t outer, int64_t channels,
+                                int64_t inner, rw_stream_t stream) {
+  return rw_bias_grad<double>(g, gb, outer, channels, inner, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -130,13 +207,15 @@ struct UpfirdnParams {
   int major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, px0, py0, out_h, out_w;
 };
 
-__global__ void __launch_bounds__(256) upfirdn2d_kernel(const float* __restrict__ x,
-                                                        const float* __restrict__ k,
-                                                        float* __restrict__ y, UpfirdnParams p) {
-  __shared__ float sk[64];
+template <typename T>
+__global__ void __launch_bounds__(256) upfirdn2d_kernel(const T* __restrict__ x,
+                                                        const T* __restrict__ k,
+                                                        T* __restrict__ y, UpfirdnParams p) {
+  typedef typename RwAcc<T>::type A;
+  __shared__ A sk[64];
   for (int t = threadIdx.x; t < p.kh * p.kw; t += 256) {
     const int ky = t / p.kw, kx = t - ky * p.kw;
-    sk[t] = k[(p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx)];
+    sk[t] = (A)k[(p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx)];
   }
   __syncthreads();
   const int64_t total = (int64_t)p.major * p.out_h * p.out_w * p.minor;
@@ -147,8 +226,8 @@ __global__ void __launch_bounds__(256) upfirdn2d_kernel(const float* __restrict_
     const int ox = (int)(r % p.out_w); r /= p.out_w;
     const int oy = (int)(r % p.out_h); r /= p.out_h;
     const int64_t ma = r;
-    const float* xm = x + ma * (int64_t)p.in_h * p.in_w * p.minor + mi;
-    float acc = 0.f;
+    const T* xm = x + ma * (int64_t)p.in_h * p.in_w * p.minor + mi;
+    A acc = A(0);
     for (int a = 0; a < p.kh; ++a) {
       const int vy = oy * p.down_y + a - p.py0;     // position in the zero-inserted image
       if (vy < 0 || vy % p.up_y) continue;
@@ -159,29 +238,31 @@ __global__ void __launch_bounds__(256) upfirdn2d_kernel(const float* __restrict_
         if (vx < 0 || vx % p.up_x) continue;
         const int ix = vx / p.up_x;
         if (ix >= p.in_w) continue;
-        acc += xm[((int64_t)iy * p.in_w + ix) * p.minor] * sk[a * p.kw + c];
+        acc += (A)xm[((int64_t)iy * p.in_w + ix) * p.minor] * sk[a * p.kw + c];
       }
     }
-    y[idx] = acc;
+    y[idx] = (T)acc;
   }
 }
 
 // minor == 1 with up / down factors in {1, 2} (every caller on the generator path): a 256 x 16
-// output tile per workgroup, four consecutive samples per thread (one 16-byte store), 32-bit index
+// output tile per workgroup, four consecutive samples per thread (one 4-element store), 32-bit index
 // arithmetic, compile-time factors and a polyphase tap walk instead of three 64-bit divisions and
 // kh*kw guarded taps per sample.  Same taps in the same order as the kernel above -> bit-identical
 // results.
 #define UF_TW 256
 #define UF_TH 16
-template <int UP, int DOWN>
-__global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const float* __restrict__ x,
-                                                              const float* __restrict__ k,
-                                                              float* __restrict__ y, UpfirdnParams p,
+template <typename T, int UP, int DOWN>
+__global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const T* __restrict__ x,
+                                                              const T* __restrict__ k,
+                                                              T* __restrict__ y, UpfirdnParams p,
                                                               int tiles_x, int tiles_y) {
-  __shared__ float sk[64];
+  typedef typename RwAcc<T>::type A;
+  typedef T vec4_t __attribute__((ext_vector_type(4)));
+  __shared__ A sk[64];
   for (int t = threadIdx.x; t < p.kh * p.kw; t += 256) {
     const int ky = t / p.kw, kx = t - ky * p.kw;
-    sk[t] = k[(p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx)];
+    sk[t] = (A)k[(p.kh - 1 - ky) * p.kw + (p.kw - 1 - kx)];
   }
   __syncthreads();
   int blk = blockIdx.x;
@@ -190,18 +271,18 @@ __global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const float* __res
   const int ma = blk / tiles_y;
   const int ox = tx * UF_TW + (threadIdx.x & 63) * 4;
   if (ox >= p.out_w) return;
-  const float* xm = x + (int64_t)ma * p.in_h * p.in_w;
-  float* ym = y + (int64_t)ma * p.out_h * p.out_w;
-  const bool vec = (p.out_w % 4 == 0);             // then ox + 3 < out_w and rows start 16-byte aligned
+  const T* xm = x + (int64_t)ma * p.in_h * p.in_w;
+  T* ym = y + (int64_t)ma * p.out_h * p.out_w;
+  const bool vec = (p.out_w % 4 == 0);             // then ox + 3 < out_w and rows start 4-element aligned
   for (int oy = ty * UF_TH + (threadIdx.x >> 6); oy < min((ty + 1) * UF_TH, p.out_h); oy += 4) {
     // polyphase: only taps a = a0, a0 + UP, ... land on real samples (ascending, like the loop above)
     const int a0 = (((p.py0 - oy * DOWN) % UP) + UP) % UP;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    A acc[4] = {A(0), A(0), A(0), A(0)};
     for (int a = a0; a < p.kh; a += UP) {
       const int vy = oy * DOWN + a - p.py0;
       const int iy = vy / UP;
       if (vy < 0 || iy >= p.in_h) continue;
-      const float* xr = xm + (int64_t)iy * p.in_w;
+      const T* xr = xm + (int64_t)iy * p.in_w;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c0 = (((p.px0 - (ox + e) * DOWN) % UP) + UP) % UP;
@@ -209,20 +290,21 @@ __global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const float* __res
           const int vx = (ox + e) * DOWN + c - p.px0;
           const int ix = vx / UP;
           if (vx < 0 || ix >= p.in_w) continue;
-          acc[e] += xr[ix] * sk[a * p.kw + c];
+          acc[e] += (A)xr[ix] * sk[a * p.kw + c];
         }
       }
     }
-    float* yo = ym + (int64_t)oy * p.out_w + ox;
+    T* yo = ym + (int64_t)oy * p.out_w + ox;
     if (vec) {
+      const vec4_t o = {(T)acc[0], (T)acc[1], (T)acc[2], (T)acc[3]};
 #if OPS_NTS & 1
-      __builtin_nontemporal_store(rw_f32x4{acc[0], acc[1], acc[2], acc[3]}, reinterpret_cast<rw_f32x4*>(yo));
+      __builtin_nontemporal_store(o, reinterpret_cast<vec4_t*>(yo));
 #else
-      *reinterpret_cast<float4*>(yo) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      *reinterpret_cast<vec4_t*>(yo) = o;
 #endif
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) if (ox + e < p.out_w) yo[e] = acc[e];
+      for (int e = 0; e < 4; ++e) if (ox + e < p.out_w) yo[e] = (T)acc[e];
     }
   }
 }
@@ -232,13 +314,16 @@ __global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const float* __res
 // computed once per thread -- per output column its two input columns, their validity and kernel columns -- and a row
 // costs two row pointers, sixteen loads and sixteen FMAs per four outputs.  Same taps in the same order as
 // upfirdn2d_kernel (a ascending, then c ascending; out-of-map taps skipped, not added as zeros) -> bit-identical.
-__global__ void __launch_bounds__(256) upfirdn2d_up2k4_kernel(const float* __restrict__ x, const float* __restrict__ k,
-                                                              float* __restrict__ y, UpfirdnParams p, int tiles_x,
+template <typename T>
+__global__ void __launch_bounds__(256) upfirdn2d_up2k4_kernel(const T* __restrict__ x, const T* __restrict__ k,
+                                                              T* __restrict__ y, UpfirdnParams p, int tiles_x,
                                                               int tiles_y) {
-  __shared__ float sk[16];
+  typedef typename RwAcc<T>::type A;
+  typedef T vec4_t __attribute__((ext_vector_type(4)));
+  __shared__ A sk[16];
   if (threadIdx.x < 16) {
     const int ky = threadIdx.x >> 2, kx = threadIdx.x & 3;
-    sk[threadIdx.x] = k[(3 - ky) * 4 + (3 - kx)];
+    sk[threadIdx.x] = (A)k[(3 - ky) * 4 + (3 - kx)];
   }
   __syncthreads();
   int blk = blockIdx.x;
@@ -247,8 +332,8 @@ __global__ void __launch_bounds__(256) upfirdn2d_up2k4_kernel(const float* __res
   const int ma = blk / tiles_y;
   const int ox = tx * UF_TW + (threadIdx.x & 63) * 4;
   if (ox >= p.out_w) return;
-  const float* xm = x + (int64_t)ma * p.in_h * p.in_w;
-  float* ym = y + (int64_t)ma * p.out_h * p.out_w;
+  const T* xm = x + (int64_t)ma * p.in_h * p.in_w;
+  T* ym = y + (int64_t)ma * p.out_h * p.out_w;
   int ix[4][2], kc[4][2];
   bool okc[4][2];
 #pragma unroll
@@ -267,33 +352,33 @@ __global__ void __launch_bounds__(256) upfirdn2d_up2k4_kernel(const float* __res
   const int oy1 = min((ty + 1) * UF_TH, p.out_h);
   for (int oy = ty * UF_TH + (threadIdx.x >> 6); oy < oy1; oy += 4) {
     const int a0 = (p.py0 - oy) & 1;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    A acc[4] = {A(0), A(0), A(0), A(0)};
 #pragma unroll
     for (int j2 = 0; j2 < 2; ++j2) {
       const int a = a0 + 2 * j2, vy = oy + a - p.py0, iy = vy >> 1;
       if (vy < 0 || iy >= p.in_h) continue;
-      const float* xr = xm + (int64_t)iy * p.in_w;
-      const float* kr = sk + 4 * a;
+      const T* xr = xm + (int64_t)iy * p.in_w;
+      const A* kr = sk + 4 * a;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          if (okc[e][j]) acc[e] += xr[ix[e][j]] * kr[kc[e][j]];
+          if (okc[e][j]) acc[e] += (A)xr[ix[e][j]] * kr[kc[e][j]];
     }
-    float* yo = ym + (int64_t)oy * p.out_w + ox;
+    T* yo = ym + (int64_t)oy * p.out_w + ox;
     if (vec) {
-      *reinterpret_cast<float4*>(yo) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      *reinterpret_cast<vec4_t*>(yo) = vec4_t{(T)acc[0], (T)acc[1], (T)acc[2], (T)acc[3]};
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) if (ox + e < p.out_w) yo[e] = acc[e];
+      for (int e = 0; e < 4; ++e) if (ox + e < p.out_w) yo[e] = (T)acc[e];
     }
   }
 }
 
-extern "C" int rw_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int in_h,
-                                int in_w, int minor, int kh, int kw, int up_x, int up_y,
-                                int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
-                                int pad_y1, rw_stream_t stream) {
+template <typename T>
+static int rw_upfirdn2d(const T* x, const T* k, T* y, int major, int in_h, int in_w, int minor, int kh, int kw,
+                        int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                        rw_stream_t stream) {
   RW_CHECK_ARG(x && k && y && major >= 0 && in_h > 0 && in_w > 0 && minor > 0);
   RW_CHECK_ARG(kh > 0 && kw > 0 && kh * kw <= 64 && up_x > 0 && up_y > 0 && down_x > 0 && down_y > 0);
   UpfirdnParams p;
@@ -310,20 +395,45 @@ extern "C" int rw_upfirdn2d_f32(const float* x, const float* k, float* y, int ma
     const dim3 grid((unsigned)blocks), block(256);
     hipStream_t st = rw_s(stream);
     if (up_x == 2 && down_x == 1 && kh == 4 && kw == 4)
-      hipLaunchKernelGGL(upfirdn2d_up2k4_kernel, grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
+      hipLaunchKernelGGL(upfirdn2d_up2k4_kernel<T>, grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
     else if (up_x == 1 && down_x == 1)
-      hipLaunchKernelGGL((upfirdn2d_plane_kernel<1, 1>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
+      hipLaunchKernelGGL((upfirdn2d_plane_kernel<T, 1, 1>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
     else if (up_x == 2 && down_x == 1)
-      hipLaunchKernelGGL((upfirdn2d_plane_kernel<2, 1>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
+      hipLaunchKernelGGL((upfirdn2d_plane_kernel<T, 2, 1>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
     else if (up_x == 1 && down_x == 2)
-      hipLaunchKernelGGL((upfirdn2d_plane_kernel<1, 2>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
+      hipLaunchKernelGGL((upfirdn2d_plane_kernel<T, 1, 2>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
     else
-      hipLaunchKernelGGL((upfirdn2d_plane_kernel<2, 2>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
+      hipLaunchKernelGGL((upfirdn2d_plane_kernel<T, 2, 2>), grid, block, 0, st, x, k, y, p, tiles_x, tiles_y);
     return RW_LAUNCH_RESULT();
   }
-  hipLaunchKernelGGL(upfirdn2d_kernel, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream),
+  hipLaunchKernelGGL(upfirdn2d_kernel<T>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream),
                      x, k, y, p);
   return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int in_h,
+                                int in_w, int minor, int kh, int kw, int up_x, int up_y,
+                                int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                                int pad_y1, rw_stream_t stream) {
+  return rw_upfirdn2d<float>(x, k, y, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1,
+                             pad_y0, pad_y1, stream);
+}
+
+extern "C" int rw_upfirdn2d_f16(const uint16_t* x, const uint16_t* k, uint16_t* y, int major, int in_h,
+                                int in_w, int minor, int kh, int kw, int up_x, int up_y,
+                                int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                                int pad_y1, rw_stream_t stream) {
+  return rw_upfirdn2d<_Float16>(reinterpret_cast<const _Float16*>(x), reinterpret_cast<const _Float16*>(k),
+                                reinterpret_cast<_Float16*>(y), major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x,
+                                down_y, pad_x0, pad_x1, pad_y0, pad_y1, stream);
+}
+
+extern "C" int rw_upfirdn2d_f64(const double* x, const double* k, double* y, int major, int in_h,
+                                int in_w, int minor, int kh, int kw, int up_x, int up_y,
+                                int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
+                                int pad_y1, rw_stream_t stream) {
+  return rw_upfirdn2d<double>(x, k, y, major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1,
+                              pad_y0, pad_y1, stream);
 }
 
 // ---------------------------------------------------------------------------------------

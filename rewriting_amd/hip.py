@@ -3,7 +3,8 @@
 PyTorch is used here for device memory and streams only: every wrapper allocates its output
 with torch, passes ``data_ptr()`` and ``torch.cuda.current_stream().cuda_stream`` to the
 library and returns the torch tensor -- the ownership rule of SURVEY.md section 8b.  Inputs
-must be float32 tensors on a HIP device; anything else raises (no CPU path).
+must be float32 tensors on a HIP device (the _f16 / _f64 forms of the three L1 ops: float16 /
+float64); anything else raises (no CPU path).
 """
 import ctypes
 import os
@@ -21,16 +22,18 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _dev(t, name='tensor'):
+def _dev(t, name='tensor', dtype=torch.float32):
     if not isinstance(t, torch.Tensor):
         raise TypeError('%s must be a torch.Tensor' % name)
     if not t.is_cuda:
         raise RuntimeError('rewriting_amd: %s is on %s; the HIP kernels need a GPU tensor '
                            '(there is no CPU fallback)' % (name, t.device))
-    if t.dtype != torch.float32:
-        raise RuntimeError('rewriting_amd: %s is %s; the C ABI is fp32 only (RW_ERR_UNSUPPORTED, include/rewriting_hip.h: '
-                           'the reference\'s pybind modules also dispatch half and double, this library does not) -- '
-                           'cast the model / tensor with .float()' % (name, t.dtype))
+    if t.dtype != dtype:
+        if dtype == torch.float32:
+            raise RuntimeError('rewriting_amd: %s is %s; the C ABI is fp32 only (RW_ERR_UNSUPPORTED, include/rewriting_hip.h: '
+                               'the reference\'s pybind modules also dispatch half and double, this library does not) -- '
+                               'cast the model / tensor with .float()' % (name, t.dtype))
+        raise RuntimeError('rewriting_amd: %s is %s; this entry takes %s (nothing is converted)' % (name, t.dtype, dtype))
     return t.detach().contiguous()
 
 
@@ -53,47 +56,96 @@ def on_device(t):
 
 
 # ------------------------------------------------------------------ L1 native ops
-def fused_bias_act(x, b, ref, act, grad, alpha, scale):
-    """fused.fused_bias_act(input, bias, refer, act, grad, alpha, scale)
-    (utils/stylegan2/op/fused_bias_act.cpp:11-20); empty tensor = absent."""
-    x = _dev(x, 'input')
-    b = _dev(b, 'bias') if b is not None and b.numel() else None
-    ref = _dev(ref, 'refer') if ref is not None and ref.numel() else None
+# These three ops take half and double as well as fp32 (include/rewriting_hip.h): fused_bias_act, bias_grad and
+# upfirdn2d_major stay fp32 only, and their _f16 / _f64 forms take the same arguments with every tensor in their one
+# dtype (bias, refer and the filter taps included) and return their results in it.  The op layer
+# (utils/stylegan2/op/) picks the form by the input's dtype.
+_ABI_SUFFIX = {torch.float32: 'f32', torch.float16: 'f16', torch.float64: 'f64'}
+
+
+def _fused_bias_act_as(dtype, x, b, ref, act, grad, alpha, scale):
+    x = _dev(x, 'input', dtype)
+    b = _dev(b, 'bias', dtype) if b is not None and b.numel() else None
+    ref = _dev(ref, 'refer', dtype) if ref is not None and ref.numel() else None
     y = torch.empty_like(x)
     step_b = 1
     for d in x.shape[2:]:
         step_b *= d
     size_b = b.numel() if b is not None else 1
-    check(lib().rw_fused_bias_act_f32(_p(x), _p(b), _p(ref), _p(y), x.numel(), step_b, size_b,
-                                      int(act), int(grad), float(alpha), float(scale), _stream()))
+    entry = getattr(lib(), 'rw_fused_bias_act_' + _ABI_SUFFIX[dtype])
+    check(entry(_p(x), _p(b), _p(ref), _p(y), x.numel(), step_b, size_b, int(act), int(grad), float(alpha),
+                float(scale), _stream()))
     return y
 
 
-def bias_grad(g):
-    g = _dev(g, 'grad')
+def _bias_grad_as(dtype, g):
+    g = _dev(g, 'grad', dtype)
     outer = g.shape[0]
     channels = g.shape[1] if g.ndim > 1 else 1
     inner = 1
     for d in g.shape[2:]:
         inner *= d
     gb = torch.empty(channels, device=g.device, dtype=g.dtype)
-    check(lib().rw_bias_grad_f32(_p(g), _p(gb), outer, channels, inner, _stream()))
+    check(getattr(lib(), 'rw_bias_grad_' + _ABI_SUFFIX[dtype])(_p(g), _p(gb), outer, channels, inner, _stream()))
     return gb
 
 
-def upfirdn2d_major(x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
-    """upfirdn2d_op.upfirdn2d on (major, H, W, minor) (utils/stylegan2/op/upfirdn2d.cpp:12-22)."""
-    x = _dev(x, 'input')
-    k = _dev(k, 'kernel')
+def _upfirdn2d_major_as(dtype, x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    x = _dev(x, 'input', dtype)
+    k = _dev(k, 'kernel', dtype)
     major, in_h, in_w, minor = x.shape
     kh, kw = k.shape
     out_h = (in_h * up_y + py0 + py1 - kh + down_y) // down_y
     out_w = (in_w * up_x + px0 + px1 - kw + down_x) // down_x
     y = torch.empty(major, max(out_h, 0), max(out_w, 0), minor, device=x.device, dtype=x.dtype)
     if y.numel():
-        check(lib().rw_upfirdn2d_f32(_p(x), _p(k), _p(y), major, in_h, in_w, minor, kh, kw,
-                                     up_x, up_y, down_x, down_y, px0, px1, py0, py1, _stream()))
+        check(getattr(lib(), 'rw_upfirdn2d_' + _ABI_SUFFIX[dtype])(
+            _p(x), _p(k), _p(y), major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1,
+            _stream()))
     return y
+
+
+def fused_bias_act(x, b, ref, act, grad, alpha, scale):
+    """fused.fused_bias_act(input, bias, refer, act, grad, alpha, scale)
+    (utils/stylegan2/op/fused_bias_act.cpp:11-20); empty tensor = absent."""
+    return _fused_bias_act_as(torch.float32, x, b, ref, act, grad, alpha, scale)
+
+
+def fused_bias_act_f16(x, b, ref, act, grad, alpha, scale):
+    """fused_bias_act on float16: the fp32 arithmetic on the widened values, rounded to half once."""
+    return _fused_bias_act_as(torch.float16, x, b, ref, act, grad, alpha, scale)
+
+
+def fused_bias_act_f64(x, b, ref, act, grad, alpha, scale):
+    """fused_bias_act on float64, alpha and scale in double."""
+    return _fused_bias_act_as(torch.float64, x, b, ref, act, grad, alpha, scale)
+
+
+def bias_grad(g):
+    return _bias_grad_as(torch.float32, g)
+
+
+def bias_grad_f16(g):
+    """bias_grad on float16, summed in fp32 as torch.sum sums half."""
+    return _bias_grad_as(torch.float16, g)
+
+
+def bias_grad_f64(g):
+    return _bias_grad_as(torch.float64, g)
+
+
+def upfirdn2d_major(x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    """upfirdn2d_op.upfirdn2d on (major, H, W, minor) (utils/stylegan2/op/upfirdn2d.cpp:12-22)."""
+    return _upfirdn2d_major_as(torch.float32, x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1)
+
+
+def upfirdn2d_major_f16(x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    """upfirdn2d_major on float16: fp32 accumulation of the widened values, rounded to half once."""
+    return _upfirdn2d_major_as(torch.float16, x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1)
+
+
+def upfirdn2d_major_f64(x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
+    return _upfirdn2d_major_as(torch.float64, x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1)
 
 
 # ------------------------------------------------------------------ generator pieces

@@ -3,12 +3,13 @@
 Same call signature as utils/stylegan2/op/upfirdn2d.py:144-149.  The adjoint is the same
 operator with up and down exchanged, the flipped kernel and the ``g_pad`` algebra of
 :100-115 (restated in ``_adjoint_pads``); because the operator is linear the double backward
-is the forward again (:52-84).  Kernels: ``rw_upfirdn2d_f32``.
+is the forward again (:52-84).  Kernels: ``rw_upfirdn2d_f32``, and ``rw_upfirdn2d_f16`` /
+``rw_upfirdn2d_f64`` for half and double input (``_dtype.wrapper``; the kernel in the input's dtype).
 """
 import torch
 from torch.autograd import Function
 
-from .... import hip
+from ._dtype import wrapper
 
 
 def _out_size(n, up, down, pad0, pad1, k):
@@ -23,7 +24,8 @@ def _adjoint_pads(in_size, out_size, k, up, down, pad0):
 
 def _run(x4, kernel, up, down, pads):
     b, c, h, w = x4.shape
-    out = hip.upfirdn2d_major(x4.reshape(-1, h, w, 1), kernel, up[0], up[1], down[0], down[1], *pads)
+    upfirdn2d_major = wrapper('upfirdn2d_major', x4, kernel=kernel)
+    out = upfirdn2d_major(x4.reshape(-1, h, w, 1), kernel, up[0], up[1], down[0], down[1], *pads)
     return out.view(b, c, out.shape[1], out.shape[2])
 
 
