@@ -11,8 +11,8 @@ runs as ONE fused block (style multiply folded into the implicit-GEMM gather; de
 noise, bias and leaky-ReLU in its epilogue) -- invisible at the module boundaries the
 rewriter observes, because any hook or split turns the fusion off for that block.
 """
+import contextlib
 import math
-import os
 import re
 import threading
 import warnings
@@ -22,7 +22,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import grad, op
+from . import grad, op, routing
+from .routing import switches
 from ... import hip
 
 # ------------------------------------------------------------------------------------------
@@ -124,10 +125,6 @@ def _unhooked(*modules):
     return all('forward' not in m.__dict__ for m in modules)
 
 
-def fusion_enabled():
-    return os.environ.get('RW_FUSE', '1') != '0'
-
-
 # The RGB branch (up_rgbK, to_rgbK) is HBM-bound and hangs off the feature-map trunk, whose convolutions
 # are MFMA-bound: when the WHOLE generator runs un-hooked (SeqStyleGAN2.forward below) the branch is
 # issued on a second HIP stream so that it overlaps the next styled convolutions, and is joined
@@ -139,7 +136,8 @@ class _RgbBranch(threading.local):      # per thread: two threads may run genera
         self.aux = None
         self.keep = []
         self.final = None        # (last StyledConvSeq, its ToRGBF, latent index of the ToRGB) of the running forward
-        self.image_path = False  # inside the un-hooked forward of a whole generator (see conv_algo)
+        self.image_path = False  # inside the un-hooked forward of a whole generator (see routing.conv_algo)
+        self.switches = None     # routing.switches() of the running generator forward
         self.successor = {}      # id(upsampling StyledConvSeq) -> (the StyledConvSeq that reads its result, latent index)
         self.reader = {}         # id(StyledConvSeq) -> the StyledConvSeq that reads its feature map (any kind), if any
         self.torgb = {}          # id(StyledConvSeq) -> (the ToRGBF that reads its feature map, its latent index), if any
@@ -154,7 +152,7 @@ _rgb_side_streams = {}          # one per device, module-level: models are deep-
 def _side_stream(device):
     """A stream for the work beside the trunk (RGB branch, border strips, prefetch).  RW_SIDE_PRIORITY (default 0): the
     priority torch gives it (positive = below the trunk's stream; clamped to the device's range)."""
-    return torch.cuda.Stream(device=device, priority=int(os.environ.get('RW_SIDE_PRIORITY', '0')))
+    return torch.cuda.Stream(device=device, priority=_switches().side_priority)
 
 
 def _rgb_stream():
@@ -172,103 +170,55 @@ def _prefetched(module):
     return entry
 
 
-_CONV_IMPLS = {'auto': 0, 'mfma': 0, 'direct': 1, 'generic': 2, 'halo': 3, 'nosplitk': 5}
+def _switches():
+    """The snapshot of the RW_* switches that the running generator forward took at its start, else a fresh one."""
+    return _rgb_branch.switches or switches()
+
+
+def fusion_enabled():
+    return _switches().fuse
 
 
 def conv_impl():
-    """Kernel choice for the 3x3 convolutions (include/rewriting_hip.h, rw_conv3x3_f32 impl):
-    auto = halo-tile MFMA kernel where the map is >= 24 wide else the im2col MFMA kernel;
-    'generic' / 'halo' force one of them, 'direct' is the VALU cross-check."""
-    return _CONV_IMPLS[os.environ.get('RW_CONV_IMPL', 'auto')]
+    """rw_conv3x3_f32's impl for the 3x3 convolutions (RW_CONV_IMPL, see routing.Switches)."""
+    return _switches().conv_impl
 
 
 def conv_precision():
-    """'f32' (default: exact fp32 MFMA) or 'bf16x6' (RW_CONV_PRECISION=bf16x6, opt-in): the stride-1 3x3
-    convolutions of eligible shapes run on the bf16 matrix pipe with exact three-way operand splits
-    (hip.conv3x3_bf16x6, fp32-product accuracy); every other kernel is unchanged."""
-    return os.environ.get('RW_CONV_PRECISION', 'f32')
+    """'f32' (default: exact fp32 MFMA) or 'bf16x6' (RW_CONV_PRECISION=bf16x6, opt-in)."""
+    return _switches().conv_precision
 
 
 def conv_algo():
-    """Algorithm of the stride-1 3x3 convolutions where more than one exists.
-
-    Without RW_CONV_ALGO the answer depends on HOW the modules are being run:
-      * inside the un-hooked forward of the whole generator (SeqStyleGAN2.forward sets a thread-local flag; image
-        generation): 'winograd4' = F(4x4,3x3) where hip.wino4_supported says so -- 4x fewer matrix FLOPs at ~1e-5
-        relative error per layer, 3e-5 measured on the 1024^2 image against the reference (the path's image
-        tolerance is 1e-3) -- and F(2x2,3x3) elsewhere;
-      * every other way -- a hooked model, a nethook.subsequence slice (key statistics, goal maps, the solve's
-        context and its rendering), RW_FUSE=0: 'winograd' = F(2x2,3x3) (hip.conv3x3_wino: 2.25x fewer matrix FLOPs,
-        the fp32 error class of the direct sum) -- which since round 5 is what runs BELOW 32^2 only: from 32^2 up these
-        models' stride-1 layers are direct sums on the 16-bit pipe (DemodulatedConv2dF.hooked_direct16: exact f16
-        operand pairs, 4e-7 from the fp32 direct sum; not a layer whose weight is being optimised) and their upsampling layers
-        the fused split kernel (fused_upsample); the statistics goldens hold at 4e-6 - 5e-6 from the reference's.
-    Consequence: model(z) and the same weights run through rewriter.sample_image_from_latent differ by 1e-5 .. 1e-4
-    on the image.  RW_CONV_ALGO=direct|winograd|winograd4 forces one algorithm everywhere; shapes an algorithm
-    does not take always run the next one down ('direct' = the implicit GEMM takes everything)."""
-    explicit = os.environ.get('RW_CONV_ALGO')
-    if explicit:
-        return explicit
-    return _IMAGE_CONV_ALGO if _rgb_branch.image_path else _DEFAULT_CONV_ALGO
+    """routing.conv_algo for the way the modules are being run right now."""
+    return routing.conv_algo(_switches(), _rgb_branch.image_path)
 
 
 def up_conv_algo():
-    """Algorithm of the stride-2 transposed convolutions: 'winograd' = F(2,2) on the four output-parity phases
-    (hip.conv_transpose3x3s2_wino: 25 instead of 36 multiplies per 2x2 block of quads; coefficients 0, +-1, the direct
-    sum's error class -- the default everywhere it applies) or 'direct'.  RW_UP_ALGO selects."""
-    return os.environ.get('RW_UP_ALGO', 'winograd')
+    """Algorithm of the stride-2 transposed convolutions (RW_UP_ALGO, see routing.Switches)."""
+    return _switches().up_algo
 
 
 def matrix_mode(kind=None):
-    """Which matrix pipe multiplies inside the F(4x4,3x3) and F(2,2) kernels: 'f32' (fp32 MFMAs) or 'split' -- every
-    transformed operand as an exact pair of f16 numbers, the piece products on the 16-bit pipe, fp32 accumulation
-    (hip.pack_conv_weight_wino4(split=True) ...: per-product error <= 2^-21, the kernels pass their parity tests at the
-    fp32 bars).  Inside the un-hooked forward of the whole generator (image generation): 'split' for every kind of
-    kernel.  Hooked / sliced models -- key statistics, goal maps, the solve's context -- run their stride-1
-    convolutions on F(2x2,3x3) in fp32 below 32^2 and as direct sums on the 16-bit pipe from there up (F(4x4,3x3) never
-    runs there: conv_algo; DemodulatedConv2dF.hooked_direct16), and run the F(2,2) transposed
-    convolutions (kind 'up') in the split form too, which holds the DIRECT kernels' bars (test_transposed_conv_f22_...:
-    3e-6 relative) and is 1.4 - 1.5 x faster on the 64^2 ... 512^2 maps of a layer-10 / layer-14 sweep; RW_MM_HOOKED=f32
-    keeps them on fp32.  Where that split form applies, an upsampling layer without a hook inside runs as ONE launch of the
-    fused kernel (DemodulatedConv2dF.fused_upsample; +13 - 16 % on those sweeps).  RW_MM=f32|split forces one everywhere."""
-    explicit = os.environ.get('RW_MM')
-    if explicit:
-        return explicit
-    if _rgb_branch.image_path:
-        return 'split'
-    return 'split' if kind == 'up' and os.environ.get('RW_MM_HOOKED', 'split') != 'f32' else 'f32'
+    """routing.matrix_mode for the way the modules are being run right now."""
+    return routing.matrix_mode(_switches(), _rgb_branch.image_path, kind)
 
 
 def matrix_mode_of_image_path():
     """matrix_mode() as the un-hooked forward of a whole generator sees it (bench.py labels its line with it)."""
-    return os.environ.get('RW_MM') or 'split'
+    return routing.matrix_mode(_switches(), True)
 
 
-def _split_part(kind):
-    """Diagnostics: RW_MM_PARTS=w4,up,up1 restricts the split form to the stride-1 F(4x4,3x3) kernels / the F(2,2)
-    transposed convolutions / the one-pass upsampling layer."""
-    parts = os.environ.get('RW_MM_PARTS')
-    return matrix_mode(kind) == 'split' and (parts is None or kind in parts.split(','))
+def micro_batch():
+    """(images per slice, first resolution run in slices) of SeqStyleGAN2._forward_micro: RW_MICRO_BATCH = "k[:res]"."""
+    return _switches().micro_batch
 
 
-def _direct16(dconv, h, w, kind):
-    """Inside the split form: the DIRECT sums on the 16-bit matrix pipe (csrc/rw_dconv.hip) in place of the
-    split-operand F(4x4,3x3) kernels, kind 'conv' / 'up' / 'rgb'.  RW_MM_DIRECT16: 'auto' (the default) = 'conv,up', the
-    two that measure faster INSIDE the forward of the 1024 generator (same box, batch 64, profiles/r05c_ab.jsonl: 1262
-    against 1221 img/s; per launch the stride-1 layers 3.4 / 4.3 ms against 3.7 - 4.7, the one-pass upsampling layer 10.2
-    against 10.4; the last layer + ToRGB is slower as a direct sum: 7.0 against 5.8); '1' = all three, '0' = none, or a
-    comma-separated list of kinds.  (Round 4 left them opt-in because sequences of un-synced forwards were occasionally
-    wrong with them -- the device scalars of that round's bound hand-over; tests/test_gpu_zz_sequences.py holds both
-    selections to bit-identical sequences now.)"""
-    mode = os.environ.get('RW_MM_DIRECT16', 'auto')
-    kinds = ('conv', 'up') if mode == 'auto' else ('conv', 'up', 'rgb') if mode == '1' else mode.split(',')
-    if dconv.in_channel < 32 or kind not in kinds:
-        return False
-    if kind == 'up':
-        return hip.dconv_transpose_blur_supported(dconv.out_channel, dconv.in_channel, h, w)
-    if kind == 'rgb':
-        return hip.dconv_to_rgb_supported(dconv.out_channel, dconv.in_channel, h, w)
-    return hip.dconv_supported(dconv.out_channel, dconv.in_channel, h, w)
+def _context(tensor, weight_changes=False):
+    """routing.Context of a layer that is about to run on `tensor`'s device."""
+    on_device = tensor.is_cuda
+    return routing.Context(_rgb_branch.image_path, on_device, on_device and torch.cuda.is_current_stream_capturing(),
+                           _rgb_branch.stream is not None, _rgb_branch.aux is not None, weight_changes)
 
 
 def _amax_of(fmap):
@@ -283,26 +233,6 @@ def _amax_of(fmap):
     if entry is not None and entry[1] == fmap._version:
         return entry[0]
     return None
-
-
-# Default: F(2x2,3x3) wherever a model is hooked, sliced (nethook.subsequence: the key statistics, the goal maps,
-# the solve's context) or run module by module; F(4x4,3x3) inside the un-hooked forward of the whole generator --
-# image generation, where the measured deviation from the reference image is the same 2e-5 with either.
-_DEFAULT_CONV_ALGO = 'winograd'
-_IMAGE_CONV_ALGO = 'winograd4'
-_ONE_PASS_UP_MAX_IN = 64       # see DemodulatedConv2dF.one_pass_upsample
-_FUSED_UP_MAX_IN = 512         # see DemodulatedConv2dF.fused_upsample
-
-
-def micro_batch():
-    """(images per slice, first resolution run in slices) of SeqStyleGAN2._forward_micro, from
-    RW_MICRO_BATCH = "k" or "k:res" (0 = one launch per step for the whole batch)."""
-    spec = os.environ.get('RW_MICRO_BATCH', _DEFAULT_MICRO_BATCH)
-    k, _, res = spec.partition(':')
-    return int(k or 0), int(res or 256)
-
-
-_DEFAULT_MICRO_BATCH = '0'
 
 
 class DataBag(dict):
@@ -494,64 +424,12 @@ class DemodulatedConv2dF(nn.Module):
         return self._derived.get('wino', self.weight, lambda: hip.pack_conv_weight_wino(self.weight))
 
     def up_wino_weight(self, split=False):
-        if split:
-            return self._derived.get('upwino_split', self.weight,
-                                     lambda: hip.pack_conv_transpose_weight_wino(self.weight, split=True))
-        return self._derived.get('upwino', self.weight, lambda: hip.pack_conv_transpose_weight_wino(self.weight))
+        return self._derived.get('upwino_split' if split else 'upwino', self.weight,
+                                 lambda: hip.pack_conv_transpose_weight_wino(self.weight, split=split))
 
     def up_blur_wino4_weight(self, k4, split=False):
-        if split:
-            return self._derived.get('upblur4_split', self.weight,
-                                     lambda: hip.pack_conv_transpose_blur_weight_wino4(self.weight, k4, split=True))
-        return self._derived.get('upblur4', self.weight,
-                                 lambda: hip.pack_conv_transpose_blur_weight_wino4(self.weight, k4))
-
-    def one_pass_upsample(self, fmap, blur):
-        """Transposed conv + blur + noise + activation in ONE pass (hip.conv_transpose3x3s2_blur_wino4: the four
-        output-parity phases as virtual channels of the F(4x4,3x3) kernel) -- where F(4x4,3x3) runs at all (the
-        un-hooked whole-generator forward, conv_algo() == 'winograd4') and where it pays: it does 1.44x the matrix work
-        of the F(2,2) kernel and saves writing + reading the (2H+1)x(2W+1) map and the blur pass, which wins at
-        <= 64 input channels (layer 17 of the 1024 model: 12.4 -> 9.x ms).  RW_UP_ALGO=winograd4 forces it wherever
-        the shape allows, RW_UP_ALGO=direct / RW_UP_FUSED=0 turn it off."""
-        algo = up_conv_algo()
-        if not self.upsample or conv_impl() != 0 or conv_precision() != 'f32' or algo == 'direct':
-            return False
-        if os.environ.get('RW_UP_FUSED', '1') == '0' or tuple(blur.pad) != (1, 1) or tuple(blur.kernel.shape) != (4, 4):
-            return False
-        if not hip.conv_transpose_blur_wino4_supported(self.out_channel, self.in_channel, fmap.shape[-2],
-                                                       fmap.shape[-1]):
-            return False
-        if algo == 'winograd4':
-            return True
-        return conv_algo() == 'winograd4' and self.in_channel <= _ONE_PASS_UP_MAX_IN
-
-    def fused_upsample(self, fmap, blur):
-        """Transposed conv + blur + noise + activation in one pass at the transposed convolution's OWN multiply count
-        (hip.conv_transpose3x3s2_blur_fused, csrc/rw_tconv.hip: a direct sum on the 16-bit matrix pipe, the (2H+1)^2 map
-        kept in LDS) -- the default for every upsampling layer it takes (w % 32 == 0, h % 16 == 0: 32^2 maps and up; at most
-        RW_UP_FUSED2_MAX_IN input channels) inside the un-hooked whole-generator forward in split mode, and of hooked / sliced
-        models too (the statistics sweeps; RW_UP_FUSED2_HOOKED=0: not there); RW_UP_FUSED2=0 brings back the two-pass /
-        phase-kernel routes.  History (round 5): the first forms were
-        +1.6 % on the forward and stayed opt-in because to_rgb_kernel on the second stream came back wrong beside them (its
-        packed fp32 FMAs; the streaming kernels are compiled without packed fp32 math since: csrc/rw_ops.hip, first line);
-        the persistent form with specialised waves on the layers of few channels and the one-workgroup-per-CU form on the
-        others (both fill a CU's register file: nothing else runs beside them) are +7 % (profiles/r05r), and the sequence /
-        stress / parity tests of the forward run with them."""
-        if not self.upsample or conv_impl() != 0 or conv_precision() != 'f32' or up_conv_algo() == 'direct':
-            return False
-        if os.environ.get('RW_UP_FUSED2', '1') != '1':
-            return False
-        # the un-hooked forward: with the one-pass kinds of the split form; a hooked / sliced model (the statistics sweeps,
-        # the rewriter's sub-models: no hook INSIDE this layer, or StyledConvSeq would not be on its fused path): where
-        # the F(2,2) transposed convolutions run in the split form (matrix_mode('up')), unless RW_UP_FUSED2_HOOKED=0
-        if not (_split_part('up1') if _rgb_branch.image_path
-                else _split_part('up') and os.environ.get('RW_UP_FUSED2_HOOKED', '1') == '1'):
-            return False
-        if tuple(blur.pad) != (1, 1) or tuple(blur.kernel.shape) != (4, 4):
-            return False
-        if self.in_channel > int(os.environ.get('RW_UP_FUSED2_MAX_IN', _FUSED_UP_MAX_IN)):
-            return False
-        return hip.tconv_blur_supported(self.out_channel, self.in_channel, fmap.shape[-2], fmap.shape[-1])
+        return self._derived.get('upblur4_split' if split else 'upblur4', self.weight,
+                                 lambda: hip.pack_conv_transpose_blur_weight_wino4(self.weight, k4, split=split))
 
     def direct16_weight(self):
         return self._derived.get('direct16', self.weight, lambda: hip.pack_conv_weight_direct16(self.weight))
@@ -561,40 +439,20 @@ class DemodulatedConv2dF(nn.Module):
                                  lambda: hip.pack_conv_transpose_blur_weight_direct16(self.weight, k4))
 
     def wino4_weight(self, split=False):
-        if split:
-            return self._derived.get('wino4_split', self.weight,
-                                     lambda: hip.pack_conv_weight_wino4(self.weight, split=True))
-        return self._derived.get('wino4', self.weight, lambda: hip.pack_conv_weight_wino4(self.weight))
+        return self._derived.get('wino4_split' if split else 'wino4', self.weight,
+                                 lambda: hip.pack_conv_weight_wino4(self.weight, split=split))
 
-    def runs_split_wino4(self, h, w):
-        """Will run() on a map of h x w execute the split-operand F(4x4,3x3) kernel (which reports max |result|)?"""
-        return (not self.upsample and _split_part('w4') and conv_algo() == 'winograd4' and conv_impl() == 0
-                and conv_precision() == 'f32' and hip.wino4_supported(self.out_channel, self.in_channel, h, w))
-
-    def runs_small_direct16(self, h, w):
-        """Inside the un-hooked forward: the 32^2 stride-1 layer -- too narrow for F(4x4,3x3); the fp32 F(2x2,3x3) kernel until
-        round 6 -- as a direct sum on the 16-bit pipe (0.8 against 1.4 ms at batch 64; the forward +1.7 %, same box,
-        interleaved: profiles/r06aq).  It measures its input itself (the layer in front runs an fp32 kernel that reports
-        nothing) and reports the bound of its result like the other split-operand kernels.  RW_DIRECT16_SMALL=0: off."""
-        return (not self.upsample and _rgb_branch.image_path and _split_part('w4')
-                and os.environ.get('RW_DIRECT16_SMALL', '1') != '0' and conv_algo() == 'winograd4' and conv_impl() == 0
-                and conv_precision() == 'f32' and min(h, w) >= 32
-                and not hip.wino4_supported(self.out_channel, self.in_channel, h, w) and _direct16(self, h, w, 'conv'))
+    def route(self, ctx, h, w, blur=None):
+        """THE routing decision for a map of h x w.  blur: the layer's BlurF where the caller runs the whole StyledConv."""
+        if not self.upsample:
+            return routing.stride1_route(_switches(), ctx, self.in_channel, self.out_channel, h, w)
+        whole = blur is not None and tuple(blur.pad) == (1, 1) and tuple(blur.kernel.shape) == (4, 4)
+        return routing.upsample_route(_switches(), ctx, self.in_channel, self.out_channel, h, w, whole)
 
     def hooked_direct16(self, h, w):
-        """A hooked / sliced model (statistics sweeps, goal maps, the solve's context): the stride-1 convolutions of maps from
-        32^2 up as DIRECT sums on the 16-bit matrix pipe (exact f16 operand pairs, fp32 accumulation: 4e-7 from the fp32
-        direct sum, the error class these models are held to) in place of the fp32 F(2x2,3x3) kernel -- where their F(2,2)
-        transposed convolutions run in the split form too (matrix_mode('up')).  The kernel measures its input itself: nobody
-        hands a bound over outside the un-hooked forward.  RW_DIRECT16_HOOKED=0: off.  Not where the weight itself is being
-        optimised (run(weight_changes=True), from grad.DemodConv: an autograd `insert` changes it every step, and each
-        re-packing reads the weights' maximum back to the host -- hip._split_scale -- two launches and a sync per layer and
-        iteration that the fp32 kernel does not have) and not while the stream is being captured (the read-back would fail)."""
-        if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
-            return False
-        return (not self.upsample and not _rgb_branch.image_path and os.environ.get('RW_DIRECT16_HOOKED', '1') == '1'
-                and os.environ.get('RW_CONV_ALGO') is None and matrix_mode('up') == 'split' and conv_impl() == 0
-                and conv_precision() == 'f32' and _direct16(self, h, w, 'conv'))
+        """The hooked branch of routing.stride1_route (the one direct sum that reports no bound) for a map of h x w?"""
+        route = self.route(_context(self.weight), h, w)
+        return route.kernel == 'direct16' and not route.reports_bound
 
     def squared_sums(self):
         return self._derived.get('wsq', self.weight, lambda: hip.weight_sqsum(self.weight, self.scale))
@@ -602,117 +460,76 @@ class DemodulatedConv2dF(nn.Module):
     def demod_factors(self, style):
         return hip.demod(self.squared_sums(), style) if self.demodulate else None
 
-    def specialised_direct16(self, h, w):
-        """Inside the un-hooked forward: will this stride-1 layer run the direct sum with SPECIALISED waves (rw_dconv.hip's
-        dconv_ws_w2 kernels: one persistent twelve-wave workgroup per CU; 64 out-channels and 64 columns per tile, a style
-        on load)?  Then the layer in front does not pre-scale its result for it.  RW_DCONV_WS_FWD=0: the one-role kernels
-        on a pre-scaled map, as in round 5."""
-        return (not self.upsample and _rgb_branch.image_path and os.environ.get('RW_DCONV_WS_FWD', '1') != '0'
-                and os.environ.get('RW_DCONV_V') != '1' and _split_part('w4') and conv_algo() == 'winograd4'
-                and conv_impl() == 0 and conv_precision() == 'f32'
-                and self.in_channel >= 32 and self.out_channel % 64 == 0 and h % 8 == 0 and w % 64 == 0
-                and hip.wino4_supported(self.out_channel, self.in_channel, h, w) and _direct16(self, h, w, 'conv'))
-
-    def leaves_rgb_partials(self, h, w):
-        """Will run(..., rgb=...) on a map of h x w execute the direct-sum kernel that also leaves the channel sums of the
-        ToRGB reading its result (hip.conv3x3_direct16_rgb_partial)?  Inside the un-hooked forward only; RW_RGB_PARTIAL=0:
-        off (ToRGB then re-reads the feature map on the RGB stream, as before round 6)."""
-        return (not self.upsample and _rgb_branch.image_path and os.environ.get('RW_RGB_PARTIAL', '1') != '0'
-                and _split_part('w4') and conv_algo() == 'winograd4' and conv_impl() == 0 and conv_precision() == 'f32'
-                and self.out_channel % 32 == 0
-                and hip.wino4_supported(self.out_channel, self.in_channel, h, w) and _direct16(self, h, w, 'conv'))
-
     def run(self, fmap, style, style_on_load, demod=None, x_amax=None, y_amax=None, rgb=None, weight_changes=False,
-            **epilogue):
-        """x_amax: the bound of |fmap| if the producer of fmap left one (hip.new_bound; split-operand kernels -- they
-        measure the map themselves otherwise); y_amax: a hip.new_bound buffer that receives the bound of the result
-        where the split-operand F(4x4,3x3) kernel runs (`runs_split_wino4` says whether it will); rgb: only where
-        `leaves_rgb_partials` says so; weight_changes: the caller differentiates with respect to the weight (see hooked_direct16)."""
-        if rgb is not None and not self.leaves_rgb_partials(fmap.shape[-2], fmap.shape[-1]):
+            route=None, **epilogue):
+        """Dispatches on `route` (self.route(...) of the map; computed here if the caller has not).  x_amax: the bound of
+        |fmap| if the producer of fmap left one (hip.new_bound; the kernels of route.reads_bound take it and measure the
+        map themselves otherwise); y_amax: a hip.new_bound buffer that receives the bound of the result where
+        route.reports_bound; rgb: (ToRGB weight (3, out), its style (B, out), its scale), only where route.rgb_partials --
+        the result is then (map, partial images); weight_changes: the caller differentiates with respect to the weight."""
+        if route is None:
+            route = self.route(_context(fmap, weight_changes), fmap.shape[-2], fmap.shape[-1])
+        if rgb is not None and (self.upsample or not route.rgb_partials):
             raise RuntimeError('run(rgb=...) on a layer that does not leave ToRGB partial sums')
         if demod is None:
             demod = self.demod_factors(style)
-        load_style = style if style_on_load else None
-        split = _split_part('up' if self.upsample else 'w4')
+        args = dict(style=style if style_on_load else None, demod=demod)
         if self.upsample:
-            # the border strips go to an auxiliary stream beside the tiles: the one of the running whole-generator
-            # forward, else (a sliced or hooked model: the statistics sweeps, the rewriter's sub-models) the
-            # device's own -- in a 250-seed sweep launch the three strip kernels were 17 % of the time, in line
-            aux = _rgb_branch.aux
-            if (aux is None and fmap.is_cuda and os.environ.get('RW_STRIP_STREAM', '1') != '0'
-                    and not torch.cuda.is_current_stream_capturing()):
-                aux = _rgb_side_streams.get((fmap.device, 'aux'))
-                if aux is None:
-                    aux = _rgb_side_streams[(fmap.device, 'aux')] = _side_stream(fmap.device)
-            b, _, h, w = fmap.shape
-            f22 = (up_conv_algo() == 'winograd' and conv_impl() == 0
-                   and hip.up_strips_applicable(self.out_channel, self.in_channel)
-                   and hip.conv_transpose_wino_supported(self.out_channel, self.in_channel, h, w))
-            if conv_impl() == 0 and (f22 or (aux is not None and hip.up_halo_applicable(
-                    self.out_channel, self.in_channel, w))):
-                # quad tiles (F(2,2) where it applies, else the direct kernel) and the border row / column strips
-                # write disjoint elements of the same map; in the un-hooked full forward the strips
-                # (latency-bound, 2 % of the step) go to a third stream beside the tiles
-                out = torch.empty(b, self.out_channel, 2 * h + 1, 2 * w + 1, device=fmap.device, dtype=fmap.dtype)
-                wp = self.packed_weight()      # (re)packed on the trunk's stream BEFORE the fork
-                f22_split = f22 and split and hip.conv_transpose_wino_split_supported(self.out_channel, self.in_channel, h, w)
-                uf = self.up_wino_weight(f22_split) if f22 else None
-                if f22_split and x_amax is None:
-                    x_amax = hip.absmax(fmap)
-                main = torch.cuda.current_stream() if aux is not None else None
-                if aux is not None:
-                    aux.wait_stream(main)
-                    with torch.cuda.stream(aux):
-                        hip.conv_transpose3x3s2(fmap, wp, self.out_channel, self.scale,
-                                                style=load_style, demod=demod, impl=8, out=out)
-                else:
-                    hip.conv_transpose3x3s2(fmap, wp, self.out_channel, self.scale,
-                                            style=load_style, demod=demod, impl=8, out=out)
-                if f22_split:
-                    hip.conv_transpose3x3s2_wino(fmap, uf, self.out_channel, self.scale, style=load_style,
-                                                 demod=demod, out=out, x_amax=x_amax)
-                elif f22:
-                    hip.conv_transpose3x3s2_wino(fmap, uf, self.out_channel, self.scale, style=load_style,
-                                                 demod=demod, out=out)
-                else:
-                    hip.conv_transpose3x3s2(fmap, wp, self.out_channel, self.scale,
-                                            style=load_style, demod=demod, impl=7, out=out)
-                if aux is not None:
-                    main.wait_stream(aux)      # queued while fmap / style / demod / out are still referenced
-                return out
-            return hip.conv_transpose3x3s2(fmap, self.packed_weight(), self.out_channel, self.scale,
-                                           style=load_style, demod=demod, impl=conv_impl())
-        if (conv_algo() == 'winograd4' and conv_impl() == 0 and conv_precision() == 'f32'
-                and hip.wino4_supported(self.out_channel, self.in_channel, fmap.shape[-2], fmap.shape[-1])):
-            if split and _direct16(self, fmap.shape[-2], fmap.shape[-1], 'conv'):
-                if rgb is not None:             # (weight (3, out), style (B, out), scale): returns (map, partial images)
-                    return hip.conv3x3_direct16_rgb_partial(fmap, self.direct16_weight(), self.out_channel, self.scale,
-                                                            rgb[0], rgb[1], rgb[2], style=load_style, demod=demod,
-                                                            x_amax=x_amax, y_amax=y_amax, **epilogue)
-                return hip.conv3x3_direct16(fmap, self.direct16_weight(), self.out_channel, self.scale, style=load_style,
-                                            demod=demod, x_amax=x_amax, y_amax=y_amax, **epilogue)
-            if split:
-                return hip.conv3x3_wino4(fmap, self.wino4_weight(True), self.out_channel, self.scale, style=load_style,
-                                         demod=demod, x_amax=x_amax, y_amax=y_amax, **epilogue)
-            return hip.conv3x3_wino4(fmap, self.wino4_weight(), self.out_channel, self.scale, style=load_style,
-                                     demod=demod, **epilogue)
-        if self.runs_small_direct16(fmap.shape[-2], fmap.shape[-1]):
-            return hip.conv3x3_direct16(fmap, self.direct16_weight(), self.out_channel, self.scale, style=load_style,
-                                        demod=demod, x_amax=x_amax, y_amax=y_amax, **epilogue)
-        if not weight_changes and self.hooked_direct16(fmap.shape[-2], fmap.shape[-1]):
-            return hip.conv3x3_direct16(fmap, self.direct16_weight(), self.out_channel, self.scale, style=load_style,
-                                        demod=demod, x_amax=x_amax, **epilogue)
-        if (conv_algo() in ('winograd', 'winograd4') and conv_impl() == 0 and conv_precision() == 'f32'
-                and hip.wino_supported(self.out_channel, self.in_channel, fmap.shape[-2], fmap.shape[-1])):
-            return hip.conv3x3_wino(fmap, self.wino_weight(), self.out_channel, self.scale, style=load_style,
-                                    demod=demod, **epilogue)
-        if (conv_precision() == 'bf16x6' and conv_impl() == 0
-                and hip.bf16x6_supported(self.out_channel, self.in_channel, fmap.shape[-1])):
+            return self._run_two_pass(fmap, route, x_amax, args)
+        args.update(epilogue)
+        if route.reads_bound:
+            args['x_amax'] = x_amax
+        if route.reports_bound:
+            args['y_amax'] = y_amax
+        kernel = route.kernel
+        if kernel == 'direct16' and rgb is not None:
+            return hip.conv3x3_direct16_rgb_partial(fmap, self.direct16_weight(), self.out_channel, self.scale,
+                                                    rgb[0], rgb[1], rgb[2], **args)
+        if kernel == 'direct16':
+            return hip.conv3x3_direct16(fmap, self.direct16_weight(), self.out_channel, self.scale, **args)
+        if kernel in ('wino4_split', 'wino4'):
+            return hip.conv3x3_wino4(fmap, self.wino4_weight(kernel == 'wino4_split'), self.out_channel, self.scale, **args)
+        if kernel == 'wino':
+            return hip.conv3x3_wino(fmap, self.wino_weight(), self.out_channel, self.scale, **args)
+        if kernel == 'bf16x6':
             wb = self._derived.get('packed_bf16x3', self.weight, lambda: hip.pack_conv_weight_bf16x3(self.weight))
-            return hip.conv3x3_bf16x6(fmap, wb, self.out_channel, self.scale, style=load_style, demod=demod,
-                                      **epilogue)
-        return hip.conv3x3(fmap, self.packed_weight(), self.out_channel, self.scale,
-                           style=load_style, demod=demod, impl=conv_impl(), **epilogue)
+            return hip.conv3x3_bf16x6(fmap, wb, self.out_channel, self.scale, **args)
+        return hip.conv3x3(fmap, self.packed_weight(), self.out_channel, self.scale, impl=conv_impl(), **args)
+
+    def _run_two_pass(self, fmap, route, x_amax, args):
+        """The transposed convolution alone, to the (2H+1) x (2W+1) map (its blur is the caller's)."""
+        if route.kernel == 'plain':
+            return hip.conv_transpose3x3s2(fmap, self.packed_weight(), self.out_channel, self.scale, impl=conv_impl(), **args)
+        # quad tiles (F(2,2) where it applies, else the direct halo kernel) and the border row / column strips write
+        # disjoint elements of the same map.  The strips (latency-bound, 2 % of the step) go to an auxiliary stream beside
+        # the tiles: the one of the running whole-generator forward, else (a sliced or hooked model: the statistics
+        # sweeps, the rewriter's sub-models) the device's own -- in a 250-seed sweep launch the three strip kernels were
+        # 17 % of the time, in line
+        b, _, h, w = fmap.shape
+        aux = None
+        if route.side_strips:
+            aux = _rgb_branch.aux if _rgb_branch.aux is not None else _rgb_side_streams.get((fmap.device, 'aux'))
+            if aux is None:
+                aux = _rgb_side_streams[(fmap.device, 'aux')] = _side_stream(fmap.device)
+        out = torch.empty(b, self.out_channel, 2 * h + 1, 2 * w + 1, device=fmap.device, dtype=fmap.dtype)
+        wp = self.packed_weight()      # (re)packed on the trunk's stream BEFORE the fork
+        f22 = route.kernel == 'f22_strips'
+        uf = self.up_wino_weight(route.split) if f22 else None
+        if f22 and route.split and x_amax is None:
+            x_amax = hip.absmax(fmap)
+        if aux is not None:
+            main = torch.cuda.current_stream()
+            aux.wait_stream(main)
+        with torch.cuda.stream(aux) if aux is not None else contextlib.nullcontext():
+            hip.conv_transpose3x3s2(fmap, wp, self.out_channel, self.scale, impl=8, out=out, **args)
+        if f22:
+            hip.conv_transpose3x3s2_wino(fmap, uf, self.out_channel, self.scale, out=out,
+                                         x_amax=x_amax if route.split else None, **args)
+        else:
+            hip.conv_transpose3x3s2(fmap, wp, self.out_channel, self.scale, impl=7, out=out, **args)
+        if aux is not None:
+            main.wait_stream(aux)      # queued while fmap / style / demod / out are still referenced
+        return out
 
     def forward(self, d):
         # through torch.autograd (grad.DemodConv: backward to the input map, the weight -- both terms, quirk Q3 --
@@ -972,125 +789,111 @@ class StyledConvSeq(nn.Sequential):
             return False
         return _unhooked(mconv, self.noise, self.activate, *mconv._modules.values())
 
-    def _reads_bound(self, h, w):
-        """Would this layer, fed a map of h x w inside the un-hooked forward, run a split-operand kernel -- i.e. use a
-        bound on its input if the producer left one?  A wrong 'yes' costs the producer one small reduction launch, a wrong
-        'no' makes this layer measure its input itself (hip.absmax): neither changes a result."""
-        if not self._fusable() or matrix_mode() != 'split' or conv_impl() != 0 or conv_precision() != 'f32':
-            return False
-        dconv = self.mconv.dconv
-        if not self.mconv.upsample:
-            return dconv.runs_split_wino4(h, w) or dconv.runs_small_direct16(h, w)
-        probe = torch.empty(0, dconv.in_channel, h, w, device='meta')
-        if dconv.fused_upsample(probe, self.mconv.blur):
-            return True
-        if _split_part('up1') and dconv.one_pass_upsample(probe, self.mconv.blur):
-            return True
-        return (_split_part('up') and up_conv_algo() == 'winograd' and hip.up_strips_applicable(dconv.out_channel, dconv.in_channel)
-                and hip.conv_transpose_wino_supported(dconv.out_channel, dconv.in_channel, h, w)
-                and hip.conv_transpose_wino_split_supported(dconv.out_channel, dconv.in_channel, h, w))
+    def _standard_activation(self):
+        act = self.activate
+        return act.negative_slope == 0.2 and abs(act.scale - 2 ** 0.5) <= 1e-12         # what the kernels' epilogues compute
 
-    def _hands_over_prescaled(self, h, w):
-        """Would this (stride-1) layer, fed a map of h x w, run an F(4x4,3x3) kernel with the style applied on load?
-        Then the layer in front may multiply the style into its own result (see forward)."""
-        mconv, act = self.mconv, self.activate
-        if (os.environ.get('RW_PRESCALE', '1') == '0' or not self._fusable() or mconv.upsample
-                or act.negative_slope != 0.2 or abs(act.scale - 2 ** 0.5) > 1e-12):
-            return False
-        dconv = mconv.dconv
-        if dconv.specialised_direct16(h, w):
-            return False            # that kernel's staging waves apply the style themselves (it needs one on load)
-        return (conv_algo() == 'winograd4' and conv_impl() == 0 and conv_precision() == 'f32'
-                and hip.wino4_supported(dconv.out_channel, dconv.in_channel, h, w))
+    def _module_by_module(self, d):
+        if d.get('prescaled') is not None:
+            raise RuntimeError('a pre-scaled feature map reached a layer that runs module by module')
+        return super().forward(d)
+
+    def _route(self, ctx, h, w):
+        """The route of this layer's convolution when the block runs fused on a map of h x w."""
+        mconv = self.mconv
+        return mconv.dconv.route(ctx, h, w, mconv.blur if mconv.upsample else None)
 
     def forward(self, d):
+        # ONE reading of the RW_* switches per layer where no generator forward took one (a sliced model: the sweeps)
+        saved, _rgb_branch.switches = _rgb_branch.switches, _switches()
+        try:
+            return self._forward(d)
+        finally:
+            _rgb_branch.switches = saved
+
+    def _forward(self, d):
         pre = d.get('prescaled')
         if not self._fusable(d):
-            if pre is not None:
-                raise RuntimeError('a pre-scaled feature map reached a layer that runs module by module')
-            return super().forward(d)
+            return self._module_by_module(d)
         mconv, act = self.mconv, self.activate
         # `pre`: the layer in front already multiplied this layer's style into fmap (and computed it)
         ahead = _prefetched(self)
         style = pre if pre is not None else ahead[0] if ahead is not None else \
             mconv.modulation(DataBag(style=d.style)).style
         demod = ahead[1] if ahead is not None else None        # else: computed where it is used
-        on_load = pre is None
         fmap = d.fmap
         b = fmap.shape[0]
         dconv = mconv.dconv
-        if act.negative_slope != 0.2 or abs(act.scale - 2 ** 0.5) > 1e-12:
-            if pre is not None:
-                raise RuntimeError('a pre-scaled feature map reached a layer that runs module by module')
-            return super().forward(d)
+        if not self._standard_activation():
+            return self._module_by_module(d)
+        sw = _switches()
+        ctx = _context(fmap)
         d_in = d                    # as received (with the hand-over key, if any): what a re-entry must see
-        x_amax = _amax_of(fmap)     # the producer's bound on |fmap| (split-operand kernels), else None
-        if os.environ.get('RW_MM_NO_HANDOVER') == '1':
-            x_amax = None
+        # the producer's bound on |fmap| (for the kernels that read one), else None
+        x_amax = None if sw.mm_no_handover else _amax_of(fmap)
         if pre is not None:
             d = DataBag(d)
             d.pop('prescaled', None)
-        split = matrix_mode() == 'split'
-        # ... and this layer's bound for the next one, inside the un-hooked forward only (a hooked model under RW_MM=split
-        # lets the kernels measure their inputs)
-        reader = _rgb_branch.reader.get(id(self)) if _rgb_branch.image_path else None
-        want_amax = split and reader is not None
+        # ... and this layer's bound for the layer that reads its result, inside the un-hooked forward only (a hooked
+        # model under RW_MM=split lets the kernels measure their inputs)
+        reader = _rgb_branch.reader.get(id(self)) if ctx.image_path else None
+        want_amax = reader is not None and routing.matrix_mode(sw, True) == 'split'
 
         def y_bound(height, width):
-            if not want_amax or not reader._reads_bound(height, width):
+            if not want_amax or not reader._fusable() or not reader._route(ctx, height, width).reads_bound:
                 return None
             return hip.new_bound(b * dconv.out_channel * height * width, fmap.device)
-        y_amax = None
-        y_amax_set = False
         post = None
         rgb_partials = None
-        if mconv.upsample and pre is not None:
-            raise RuntimeError('a pre-scaled feature map reached an upsampling layer')
+        epilogue = dict(noise_w=self.noise.weight, bias=act.bias, act=True)
         if mconv.upsample:
+            if pre is not None:
+                raise RuntimeError('a pre-scaled feature map reached an upsampling layer')
+            route = self._route(ctx, fmap.shape[2], fmap.shape[3])
+            h, w = 2 * fmap.shape[2], 2 * fmap.shape[3]
             # inside the un-hooked whole-generator forward the result is read by exactly one consumer, the next
             # styled convolution: where that one runs F(4x4,3x3) -- whose loop is bound by vector instructions beside
             # the MFMAs -- its style multiply (18 packed multiplies per 6x6 item) moves into this layer's epilogue
-            nxt = _rgb_branch.successor.get(id(self)) if _rgb_branch.image_path and pre is None else None
-            if nxt is not None and nxt[0]._hands_over_prescaled(2 * fmap.shape[2], 2 * fmap.shape[3]):
+            nxt = _rgb_branch.successor.get(id(self)) if ctx.image_path else None
+            if (nxt is not None and nxt[0]._fusable() and nxt[0]._standard_activation()
+                    and not nxt[0].mconv.upsample and nxt[0]._route(ctx, h, w).prescaled):
                 nxt_ahead = _prefetched(nxt[0])
                 post = nxt_ahead[0] if nxt_ahead is not None else \
                     nxt[0].mconv.modulation(DataBag(style=d.latent[:, nxt[1]])).style
-            h, w = 2 * fmap.shape[2], 2 * fmap.shape[3]
             noise = self.noise.noise_for(d, b, h, w, fmap.device)
             y_amax = y_bound(h, w)
-            if dconv.fused_upsample(fmap, mconv.blur):
-                mm = dict(y_amax=y_amax) if y_amax is not None else {}
-                if os.environ.get('RW_UP_FUSED2_JOIN') == '1' and _rgb_branch.stream is not None:
-                    torch.cuda.current_stream().wait_stream(_rgb_branch.stream)      # see fused_upsample
+            bound = dict(y_amax=y_amax) if y_amax is not None else {}
+            if route.kernel == 'fused':
+                if sw.up_fused2_join and _rgb_branch.stream is not None:
+                    torch.cuda.current_stream().wait_stream(_rgb_branch.stream)
                 out = hip.conv_transpose3x3s2_blur_fused(
                     fmap, dconv.direct16_weight(), mconv.blur.kernel, dconv.out_channel, dconv.scale,
                     style=style, demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
-                    noise_w=self.noise.weight, bias=act.bias, act=True, post_scale=post, x_amax=x_amax, **mm)
-                y_amax_set = y_amax is not None
-            elif dconv.one_pass_upsample(fmap, mconv.blur):
-                split1 = _split_part('up1')
-                mm = dict(x_amax=x_amax, y_amax=y_amax) if split1 else {}
-                if split1 and _direct16(dconv, fmap.shape[2], fmap.shape[3], 'up'):
+                    post_scale=post, x_amax=x_amax, **bound, **epilogue)
+            elif route.kernel in ('one_pass_direct16', 'one_pass_wino4'):
+                if route.kernel == 'one_pass_direct16':
                     one_pass, packed = hip.conv_transpose3x3s2_blur_direct16, dconv.up_blur_direct16_weight(mconv.blur.kernel)
                 else:
-                    one_pass, packed = hip.conv_transpose3x3s2_blur_wino4, dconv.up_blur_wino4_weight(mconv.blur.kernel, split1)
+                    one_pass, packed = hip.conv_transpose3x3s2_blur_wino4, dconv.up_blur_wino4_weight(mconv.blur.kernel, route.split)
+                if not route.split:
+                    y_amax = None           # the fp32 phase kernel neither reads nor reports a bound
+                mm = dict(x_amax=x_amax, y_amax=y_amax) if route.split else {}
                 out = one_pass(
                     fmap, packed, dconv.out_channel, dconv.scale,
                     style=style, demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
-                    noise_w=self.noise.weight, bias=act.bias, act=True, post_scale=post, **mm)
-                y_amax_set = split1 and y_amax is not None
+                    post_scale=post, **mm, **epilogue)
             else:
-                wide = dconv.run(fmap, style, style_on_load=True, demod=demod, x_amax=x_amax)
-                mm = dict(y_amax=y_amax) if y_amax is not None else {}
+                wide = dconv.run(fmap, style, style_on_load=True, demod=demod, x_amax=x_amax, route=route)
                 out = hip.blur_noise_act(wide, mconv.blur.kernel, noise, self.noise.weight, act.bias, post_scale=post,
-                                         **mm)
-                y_amax_set = y_amax is not None
+                                         **bound)
         else:
             h, w = fmap.shape[2:]
             noise = self.noise.noise_for(d, b, h, w, fmap.device)
             fin = _rgb_branch.final
-            if (fin is not None and fin[0] is self and conv_impl() == 0 and conv_precision() == 'f32'
-                    and hip.to_rgb_fusable(dconv.out_channel, dconv.in_channel, w)):
+            final = None
+            if fin is not None and fin[0] is self:
+                final = routing.final_rgb_route(sw, ctx, dconv.in_channel, dconv.out_channel, h, w)
+            if final is not None:
                 # last styled conv of the un-hooked generator: ToRGB runs in its epilogue and the feature
                 # map, which nothing else reads, is never written (models.py:639-655 fused)
                 torgb, idx = fin[1], fin[2]
@@ -1102,47 +905,40 @@ class StyledConvSeq(nn.Sequential):
                     main.wait_stream(_rgb_branch.stream)           # the running image comes from the RGB stream
                 rgb_ahead = _prefetched(torgb)
                 rgb_style = rgb_ahead if rgb_ahead is not None else torgb.conv.modulation(d.latent[:, idx])
-                wino = (conv_algo() in ('winograd', 'winograd4') and dconv.out_channel == 32
-                        and hip.wino_supported(dconv.out_channel, dconv.in_channel, h, w))
-                wino4 = (conv_algo() == 'winograd4' and os.environ.get('RW_RGB_F4', '1') != '0'
-                         and hip.wino4_to_rgb_supported(dconv.out_channel, dconv.in_channel, h, w))
-                fused = (hip.conv3x3_wino4_to_rgb if wino4 else
-                         hip.conv3x3_wino_to_rgb if wino else hip.conv3x3_to_rgb)
-                split4 = wino4 and _split_part('w4')
-                mm = dict(x_amax=x_amax) if split4 else {}
-                direct = split4 and _direct16(dconv, h, w, 'rgb')
-                if direct:
-                    fused = hip.conv3x3_direct16_to_rgb
+                if final == 'direct16':
+                    fused, packed = hip.conv3x3_direct16_to_rgb, dconv.direct16_weight()
+                elif final in ('wino4_split', 'wino4'):
+                    fused, packed = hip.conv3x3_wino4_to_rgb, dconv.wino4_weight(final == 'wino4_split')
+                elif final == 'wino':
+                    fused, packed = hip.conv3x3_wino_to_rgb, dconv.wino_weight()
+                else:
+                    fused, packed = hip.conv3x3_to_rgb, dconv.packed_weight()
+                mm = dict(x_amax=x_amax) if final in ('direct16', 'wino4_split') else {}
                 _, rgb = fused(
-                    fmap, dconv.direct16_weight() if direct else dconv.wino4_weight(split4) if wino4 else dconv.wino_weight() if wino
-                    else dconv.packed_weight(),
-                    dconv.out_channel, dconv.scale,
+                    fmap, packed, dconv.out_channel, dconv.scale,
                     torgb.conv.weight.view(3, torgb.conv.in_channel), rgb_style, torgb.bias.view(3), skip,
-                    torgb.conv.scale, style=style if on_load else None,
-                    demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
-                    noise_w=self.noise.weight, bias=act.bias, act=True, **mm)
+                    torgb.conv.scale, style=style if pre is None else None,
+                    demod=demod if demod is not None else dconv.demod_factors(style), noise=noise, **mm, **epilogue)
                 return DataBag(d, style=style, fmap=None, fused_rgb=rgb)
-            y_amax = y_bound(h, w) if want_amax and (dconv.runs_split_wino4(h, w) or dconv.runs_small_direct16(h, w)) else None
-            y_amax_set = y_amax is not None
+            route = self._route(ctx, h, w)
+            y_amax = y_bound(h, w) if route.reports_bound else None
             # the ToRGB that reads this layer's result (to_rgbK follows layer 2K): its channel sums are left by the
-            # convolution itself where the direct-sum kernel runs -- the RGB stream then adds a few small images instead
-            # of re-reading the feature map (4.3 GB for layer 16 at batch 64)
-            tr = _rgb_branch.torgb.get(id(self)) if _rgb_branch.stream is not None else None
+            # convolution itself where the direct-sum kernel runs
+            tr = _rgb_branch.torgb.get(id(self)) if route.rgb_partials else None
             rgb = None
-            if tr is not None and dconv.leaves_rgb_partials(h, w):
+            if tr is not None:
                 rgb_ahead = _prefetched(tr[0])
                 rgb_style = rgb_ahead if rgb_ahead is not None else tr[0].conv.modulation(d.latent[:, tr[1]])
                 rgb = (tr[0].conv.weight.view(3, tr[0].conv.in_channel), rgb_style, tr[0].conv.scale)
-            out = dconv.run(fmap, style, style_on_load=on_load, demod=demod, x_amax=x_amax,
-                            y_amax=y_amax if y_amax_set else None, rgb=rgb, noise=noise,
-                            noise_w=self.noise.weight, bias=act.bias, act=True)
+            out = dconv.run(fmap, style, style_on_load=pre is None, demod=demod, x_amax=x_amax, y_amax=y_amax, rgb=rgb,
+                            route=route, noise=noise, **epilogue)
             if rgb is not None:
                 out, rgb_partials = out
         # hand-overs, only inside the un-hooked forward: the bound rides on the tensor itself (_amax_of)
         extra = {}
         if rgb_partials is not None:
             extra['rgb_partials'] = rgb_partials
-        if y_amax_set:
+        if y_amax is not None:
             out.rw_amax = (y_amax, out._version)
         if post is not None:        # bags that callers see never carry the key
             extra['prescaled'] = post
@@ -1211,10 +1007,15 @@ class SeqStyleGAN2(nn.Sequential):
         super().__init__(OrderedDict(steps))
 
     def forward(self, input):
-        whole = (fusion_enabled() and torch.is_tensor(input) and not self.bag_output and not self.bag_input
-                 and not _rgb_branch.image_path and _unhooked(*self.modules()))
-        if not whole:
-            return self._forward(input)
+        saved, _rgb_branch.switches = _rgb_branch.switches, switches()     # ONE reading of the RW_* switches per forward
+        try:
+            whole = (fusion_enabled() and torch.is_tensor(input) and not self.bag_output and not self.bag_input
+                     and not _rgb_branch.image_path and _unhooked(*self.modules()))
+            return self._forward_whole(input) if whole else self._forward(input)
+        finally:
+            _rgb_branch.switches = saved
+
+    def _forward_whole(self, input):
         _rgb_branch.image_path = True
         _rgb_branch.successor = self._successors()
         _rgb_branch.reader = self._readers()
@@ -1233,7 +1034,7 @@ class SeqStyleGAN2(nn.Sequential):
                 and not self.bag_input and input.shape[0] > mb and 'up_rgb%d' % (int(math.log2(from_res)) - 2)
                 in self._modules and _rgb_branch.stream is None and _unhooked(*self.modules())):
             return self._forward_micro(input, mb, from_res)
-        side_ok = (fusion_enabled() and os.environ.get('RW_RGB_STREAM', '1') != '0' and torch.is_tensor(input)
+        side_ok = (fusion_enabled() and _switches().rgb_stream and torch.is_tensor(input)
                    and input.is_cuda and not self.bag_output and _rgb_branch.stream is None
                    and not torch.cuda.is_current_stream_capturing()
                    and _unhooked(*self.modules()))
@@ -1253,7 +1054,7 @@ class SeqStyleGAN2(nn.Sequential):
             out = input
             for name, module in self._modules.items():
                 out = module(out)
-                if name == 'latents' and _rgb_branch.image_path and os.environ.get('RW_PREFETCH_STYLES', '1') != '0':
+                if name == 'latents' and _rgb_branch.image_path and _switches().prefetch_styles:
                     self._prefetch_modulations(out, aux)
         finally:
             _rgb_branch.stream = None
@@ -1381,7 +1182,7 @@ class SeqStyleGAN2(nn.Sequential):
 
     def _final_pair(self):
         """(last StyledConvSeq, the ToRGBF that consumes it, latent index of that ToRGB) or None."""
-        if os.environ.get('RW_FUSE_FINAL_RGB', '1') == '0':
+        if not _switches().fuse_final_rgb:
             return None
         names = list(self._modules)
         last_rgb = 'to_rgb%d' % (self.log_size - 1)

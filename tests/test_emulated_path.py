@@ -470,7 +470,7 @@ def test_bounds_are_produced_only_where_the_next_layer_reads_them(emulated_hip, 
     b = z.shape[0]
     # 64-model: layer 10 (64^2, F(4x4,3x3) + ToRGB) reads the bound of layer 9's result (the blur pass reports it); layer 9
     # (32^2 -> 64^2, F(2,2) split) reads layer 8's -- since round 6 the 32^2 stride-1 layer is a direct sum on the 16-bit
-    # pipe (runs_small_direct16), which reports its result's bound and reads the one layer 7's blur pass leaves; the
+    # pipe (the small-map branch of routing.stride1_route), which reports its result's bound and reads the one layer 7's blur pass leaves; the
     # layers in front ask for none; the last layer has no reader; nobody measures a map
     n32 = b * model.channels[32] * 32 * 32
     assert made == [n32, n32, b * model.channels[64] * 64 * 64], made
@@ -520,7 +520,7 @@ def test_bounds_are_produced_only_where_the_next_layer_reads_them(emulated_hip, 
 
 
 def test_fused_transposed_conv_and_blur_layer_stays_inside_the_image_tolerance(emulated_hip, monkeypatch):
-    """DemodulatedConv2dF.fused_upsample: inside the un-hooked forward an upsampling StyledConv whose shape
+    """routing.upsample_route, kernel 'fused': inside the un-hooked forward an upsampling StyledConv whose shape
     hip.tconv_blur_supported takes runs as ONE launch of hip.conv_transpose3x3s2_blur_fused (the transposed convolution at
     its own multiply count, the blur from LDS) with the layer's plain direct-16 packing; same generator, reference
     golden, image tolerance; RW_UP_FUSED2=0 and a layer above RW_UP_FUSED2_MAX_IN channels never take it; hooked models do
@@ -541,7 +541,7 @@ def test_fused_transposed_conv_and_blur_layer_stays_inside_the_image_tolerance(e
     assert not calls                                                    # layer 9 has 512 input channels
     monkeypatch.delenv('RW_UP_FUSED2_MAX_IN')
     with torch.no_grad():
-        got = model(z)                                                  # the default (models.DemodulatedConv2dF.fused_upsample)
+        got = model(z)                                                  # the default (routing.upsample_route: 'fused')
     assert [tuple(sh[2:]) for sh, _ in calls] == [(32, 32)]             # layer 9: 32^2 -> 64^2 (h % 16 == 0, w % 32 == 0)
     assert 'y_amax' in calls[0][1] and 'post_scale' in calls[0][1]      # its reader (layer 10, F(4x4,3x3)) takes bound and style
     assert (got - want).abs().max().item() < 1e-3

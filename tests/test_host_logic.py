@@ -520,7 +520,7 @@ def test_running_quantile_keeps_streaming_after_a_save_and_after_a_cache_load():
 
 def test_hooked_models_leave_a_layer_whose_weight_requires_grad_on_the_fp32_kernel(emulated_hip, monkeypatch):
     """A hooked / sliced model runs its stride-1 layers of maps from 32^2 up as direct sums on the 16-bit pipe
-    (DemodulatedConv2dF.hooked_direct16; tests/test_emulated_path.py holds which layers and the statistics bar) -- but not
+    (the hooked branch of routing.stride1_route; tests/test_emulated_path.py holds which layers and the statistics bar) -- but not
     a layer whose weight requires grad (an autograd `insert`): every re-packing of a changing weight would read its maximum
     back to the host, two launches and a sync per layer and optimiser step."""
     import torch
