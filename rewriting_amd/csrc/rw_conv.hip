@@ -17,7 +17,6 @@
 // stride-1 layers -- noise, bias and leaky-ReLU, so a styled-conv block reads its input once
 // and writes its output once.
 #include "rw_common.h"
-#include <stdlib.h>
 #include <string.h>
 
 __host__ __device__ __forceinline__ int rw_tap_off(unsigned bits, int t) {
@@ -47,15 +46,6 @@ struct ConvBatch {
   int work0[5];
   ConvProblem p[4];
 };
-
-// Block id -> work item so that consecutive work items (the out-channel tiles of one pixel
-// tile, which share the gathered input) sit on ONE XCD's L2.  Bijective for any total.
-__device__ __forceinline__ int rw_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
 
 // Epilogue of the im2col kernels for a wave's TM x TN accumulator tiles (C/D layout: col = lane&31
 // is the position n, row r of a tile is out-channel o_first + 32a + (r&3) + 8(r>>2)).  Every value
@@ -457,15 +447,12 @@ __global__ void __launch_bounds__(256) conv_mfma_ksplit_kernel(const ConvBatch c
 // its use, which frees the LDS and the VALU for the matrix pipe.  (FRAG = false: the per-phase
 // variant of the transposed convolution, impl 4, reads wp[tap][i][o] with dword loads.)
 // ---------------------------------------------------------------------------------------
-template <int N> struct rw_int { static constexpr int value = N; };
-
 // Timing ablations for kernel work (build with -DRW_ABLATION, select with RW_CONV_ABL=<bits>; results
 // are WRONG when a bit is set): 1 = no LDS operand reads in the loop, 2 = no weight refills,
 // 4 = no halo fetch / staging, 8 = no barrier, 16 = no epilogue stores.  Compiled out otherwise.
 #ifdef RW_ABLATION
-#include <stdlib.h>
 #define RW_ABL(p, bit) ((p).abl & (bit))
-static int rw_abl_env() { const char* e = getenv("RW_CONV_ABL"); return e ? atoi(e) : 0; }
+static int rw_abl_env() { return rw_env_int("RW_CONV_ABL", 0); }
 #else
 #define RW_ABL(p, bit) false
 static int rw_abl_env() { return 0; }
@@ -1246,14 +1233,10 @@ static void launch_halo_frag(int bm, int work, const HaloProblem& h, hipStream_t
 }
 
 // ps: 1 (stride-1 conv) or 4 (transposed-conv phases) problems sharing x / y / epilogue.
-struct RgbFusion { const float* weight; const float* style; const float* bias; const float* skip; float* out; float scale; };
-
-static int launch_halo(const ConvProblem* ps, int n, const float* wfrag, hipStream_t s, const RgbFusion* rgb = nullptr) {
+static int launch_halo(const ConvProblem* ps, int n, const float* wfrag, hipStream_t s, const rw_rgb_epilogue* rgb = nullptr) {
   const ConvProblem& c = ps[0];
   HaloProblem h;
-  h.rgb_weight = rgb ? rgb->weight : nullptr; h.rgb_style = rgb ? rgb->style : nullptr;
-  h.rgb_bias = rgb ? rgb->bias : nullptr; h.rgb_skip = rgb ? rgb->skip : nullptr; h.rgb_out = rgb ? rgb->out : nullptr;
-  h.rgb_scale = rgb ? rgb->scale : 0.f;
+  rw_fill_rgb(h, rgb);
   h.x = c.x; h.wp = ps[0].wp; h.wfrag = wfrag; h.y = c.y; h.style = c.style; h.demod = c.demod; h.noise = c.noise;
   h.noise_w = c.noise_w; h.bias = c.bias; h.batch = c.batch; h.in_ch = c.in_ch; h.out_ch = c.out_ch;
   h.h = c.h; h.w = c.w; h.oh = c.oh; h.ow = c.ow; h.sy = c.sy; h.sx = c.sx; h.w_scale = c.w_scale;
@@ -1369,9 +1352,9 @@ static int launch_batch(const ConvProblem* ps, int n, int impl, hipStream_t s) {
     else if (c.out_ch % 64 == 0 && c.in_ch % 32 == 0) ksplit = 2;
   }
   if (ksplit) {
-    const char* ek = getenv("RW_KSPLIT");             // experiment: force the 32x32 (1) or 64x64 (2) tile
-    if (ek && atoi(ek) == 1 && c.in_ch % 64 == 0) ksplit = 1;
-    if (ek && atoi(ek) == 2 && c.out_ch % 64 == 0 && c.in_ch % 32 == 0) ksplit = 2;
+    const int ek = rw_env_int("RW_KSPLIT", 0);        // experiment: force the 32x32 (1) or 64x64 (2) tile
+    if (ek == 1 && c.in_ch % 64 == 0) ksplit = 1;
+    if (ek == 2 && c.out_ch % 64 == 0 && c.in_ch % 32 == 0) ksplit = 2;
     bm = bn = (ksplit == 2) ? 64 : 32;
   }
   int64_t work = 0;
@@ -1396,12 +1379,7 @@ static void fill_common(ConvProblem& p, const float* x, const float* wp, float* 
                         int in_ch, int out_ch, int h, int w, float w_scale,
                         const rw_conv_epilogue* ep) {
   p.x = x; p.wp = wp; p.y = y;
-  p.style = ep ? ep->style : nullptr;
-  p.demod = ep ? ep->demod : nullptr;
-  p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr;
-  p.bias = ep ? ep->bias : nullptr;
-  p.act = ep ? ep->act : 0;
+  rw_fill_epilogue(p, ep);
   p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w;
   p.w_scale = w_scale;
   p.dy_bits = 0; p.dx_bits = 0;
@@ -1417,7 +1395,7 @@ extern "C" int rw_conv3x3_f32(const float* x, const float* wp, float* y, int bat
                               int out_ch, int h, int w, float w_scale, const rw_conv_epilogue* ep,
                               int impl, rw_stream_t stream) {
   RW_CHECK_ARG(x && wp && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   ConvProblem p;
   fill_common(p, x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep);
   p.ph = h; p.pw = w; p.oh = h; p.ow = w; p.sy = 1; p.sx = 1; p.oy0 = 0; p.ox0 = 0;
@@ -1432,8 +1410,8 @@ extern "C" int rw_conv3x3_f32(const float* x, const float* wp, float* y, int bat
 extern "C" int rw_conv3x3_to_rgb_f32(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch,
                                     int h, int w, float w_scale, const rw_conv_epilogue* ep,
                                     const rw_rgb_epilogue* rgb, rw_stream_t stream) {
-  RW_CHECK_ARG(x && wp && rgb && rgb->weight && rgb->style && rgb->out && batch > 0 && in_ch > 0 && out_ch > 0);
-  RW_CHECK_ARG(h > 0 && w > 0 && (!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias))));
+  RW_CHECK_ARG(x && wp && rw_rgb_ok(rgb) && batch > 0 && in_ch > 0 && out_ch > 0);
+  RW_CHECK_ARG(h > 0 && w > 0 && rw_epilogue_ok(ep));
   // ONE WAVE must hold every out-channel of its pixels (the 32- and 64-channel tile shapes), 32-pixel column tiles
   if (!(out_ch == 32 || out_ch == 64) || w < 24 || in_ch % 16 || in_ch > 1024)
     return RW_ERR_UNSUPPORTED;
@@ -1442,8 +1420,7 @@ extern "C" int rw_conv3x3_to_rgb_f32(const float* x, const float* wp, float* y, 
   p.ph = h; p.pw = w; p.oh = h; p.ow = w; p.sy = 1; p.sx = 1; p.oy0 = 0; p.ox0 = 0;
   p.ntaps = 9;
   for (int t = 0; t < 9; ++t) set_tap(p, t, t / 3 - 1, t % 3 - 1);
-  const RgbFusion f = {rgb->weight, rgb->style, rgb->bias, rgb->skip, rgb->out, rgb->scale};
-  return launch_halo(&p, 1, wp + (int64_t)9 * in_ch * out_ch, rw_s(stream), &f);
+  return launch_halo(&p, 1, wp + (int64_t)9 * in_ch * out_ch, rw_s(stream), rgb);
 }
 
 extern "C" int rw_conv_transpose3x3s2_f32(const float* x, const float* wp, float* y, int batch,
@@ -1694,12 +1671,11 @@ extern "C" int rw_pack_conv_weight_bf16x3(const float* w, void* wb, int out_ch, 
 extern "C" int rw_conv3x3_bf16x6_f32(const float* x, const void* wb, float* y, int batch, int in_ch, int out_ch,
                                      int h, int w, float w_scale, const rw_conv_epilogue* ep, rw_stream_t stream) {
   RW_CHECK_ARG(x && wb && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (w < 24 || in_ch % 16 || in_ch > 1024 || out_ch % 64) return RW_ERR_UNSUPPORTED;
   HaloProblem hp;
   hp.x = x; hp.wp = nullptr; hp.wfrag = reinterpret_cast<const float*>(wb); hp.y = y;
-  hp.style = ep ? ep->style : nullptr; hp.demod = ep ? ep->demod : nullptr; hp.noise = ep ? ep->noise : nullptr;
-  hp.noise_w = ep ? ep->noise_w : nullptr; hp.bias = ep ? ep->bias : nullptr; hp.act = ep ? ep->act : 0;
+  rw_fill_epilogue(hp, ep);
   hp.batch = batch; hp.in_ch = in_ch; hp.out_ch = out_ch; hp.h = h; hp.w = w; hp.oh = h; hp.ow = w;
   hp.sy = 1; hp.sx = 1; hp.w_scale = w_scale; hp.nphase = 1; hp.abl = rw_abl_env();
   hp.rgb_weight = nullptr; hp.rgb_style = nullptr; hp.rgb_bias = nullptr; hp.rgb_skip = nullptr; hp.rgb_out = nullptr;

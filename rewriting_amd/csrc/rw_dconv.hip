@@ -35,13 +35,6 @@
 // MODE 2 (RGB) = the last styled convolution with ToRGB in the epilogue (out_ch == 32, WM == 1: a wave holds all 32
 // channels of its pixels; the sum over channels is a 16-lane DPP reduction).
 #include "rw_common.h"
-#include <stdlib.h>
-typedef float dc_f32x4 __attribute__((ext_vector_type(4)));
-typedef float dc_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned dc_u32x4 __attribute__((ext_vector_type(4)));
-typedef int dc_i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 dc_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 dc_f16x8 __attribute__((ext_vector_type(8)));
 
 struct DconvProblem {
   const float* x; const unsigned char* wp; float* y;
@@ -73,26 +66,7 @@ extern "C" int rw_dconv_prof(unsigned long long* out) {
 #define DC_T() ((unsigned long long)clock64())
 #endif
 
-__device__ __forceinline__ int dc_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
-
-template <int N> struct rw_int { static constexpr int value = N; };
-
-// position of channel quad g inside the 64 bytes of window column cc: g ^ dc_swz(cc).  ds_read_b128 is serviced in the
-// lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32): with this swizzle the 16 lanes of every group -- 16 pixels of
-// one quad in the MFMA operand order, at any of the three tap columns -- hit 16 distinct 16-byte slots of the 256-byte bank
-// row (searched exhaustively; (cc >> 2) & 3 is 2-way: SQ_LDS_BANK_CONFLICT was 48 % of the LDS cycles), and the eight
-// consecutive pixels of a ds_write_b128 group hit eight distinct slots of its 128-byte row.
-__device__ __forceinline__ int dc_swz(int cc) { return (cc >> 1) & 3; }
-// the operand [u0 u1 u2 u3 u0 u1 u2 u3] of the four halves in w
-__device__ __forceinline__ dc_f16x8 dc_expand(dc_f32x2 w) {
-  const dc_f32x4 d = {w[0], w[1], w[0], w[1]};
-  return __builtin_bit_cast(dc_f16x8, d);
-}
+// (rw_swz, rw_expand, rw_pair -- the f16-pair operand helpers -- and the LDS-direct loads: rw_common.h)
 // ---- THREE piece products per multiply where four were issued (round 5).  Vl Ul is <= 2^-22 of a product whose other
 // pieces are already rounded at 2^-22: it buys nothing.  A pixel word is [Vh c0..3 | Vl c0..3]; against [Uh | Uh] one MFMA
 // gives Vh Uh + Vl Uh, and the Vh Ul of TWO taps share a second one: the rows r and r + 1 of a window column meet the taps
@@ -104,20 +78,6 @@ __device__ __forceinline__ dc_f16x8 dc_expand(dc_f32x2 w) {
 #ifndef DC_PRODUCTS
 #define DC_PRODUCTS 3
 #endif
-// [a0 a1 a2 a3 b0 b1 b2 b3]: the first four halves of two operands (their Vh parts) / two 4-half weight pieces
-__device__ __forceinline__ dc_f16x8 dc_pair(dc_f16x8 a, dc_f16x8 b) {
-  return dc_f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-__device__ __forceinline__ dc_f16x8 dc_pair(dc_f32x2 a, dc_f32x2 b) {
-  const dc_f32x4 d = {a[0], a[1], b[0], b[1]};
-  return __builtin_bit_cast(dc_f16x8, d);
-}
-
-// LDS-direct load: lane L's 16 bytes at sbase + voffset land at LDS byte address lds_addr + 16 L
-__device__ __forceinline__ void dc_dma_global_b128(unsigned lds_addr, int voffset, const void* sbase) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_addr), "v"(voffset), "s"(sbase)
-               : "memory");
-}
 
 // sum over the 16 lanes of a DPP row (every lane ends with the sum)
 __device__ __forceinline__ float dc_row_sum(float v) {
@@ -149,7 +109,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   const int wm = wave / WN, wn = wave % WN;
   const int lk = lane >> 4, lt = lane & 15;
 
-  const int local = dc_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int ot = local % p.o_tiles;
   int pg = local / p.o_tiles;
   const int tx = pg % p.tiles_x; pg /= p.tiles_x;
@@ -203,7 +163,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
     const int iy = y0 - 1 + r, ix = x0 - 1 + cc;
     const bool ok = pi < NPIX && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
     xoff[s] = ok ? (iy * p.w + ix) * 4 : 0x7fffffff;
-    loff[s] = pi < NPIX ? pi * 64 + ((wave ^ dc_swz(cc)) << 4) : -1;
+    loff[s] = pi < NPIX ? pi * 64 + ((wave ^ rw_swz(cc)) << 4) : -1;
   }
   // the window of a chunk is staged in two halves (iterations [0, SH) and [SH, SI)): the first is in flight during the
   // first third of the previous chunk's MFMAs and converted after it, the second during the rest -- half the registers
@@ -220,39 +180,39 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   };
   auto stage_store = [&](int c, int buf, auto half_tag) __attribute__((always_inline)) {
     constexpr int S0 = decltype(half_tag)::value ? SH : 0, S1 = decltype(half_tag)::value ? SI : SH;
-    const dc_f32x4 sv = *reinterpret_cast<const dc_f32x4*>(&St[16 * c + 4 * wave]);
+    const rw_f32x4 sv = *reinterpret_cast<const rw_f32x4*>(&St[16 * c + 4 * wave]);
     unsigned char* dst = Ls + buf * BUFB;
 #pragma unroll
     for (int s = S0; s < S1; ++s) {
       const float (&rw)[4] = raw[s - S0];
       const float v0 = rw[0] * sv[0], v1 = rw[1] * sv[1], v2 = rw[2] * sv[2], v3 = rw[3] * sv[3];
-      const dc_f16x2 h01 = __builtin_convertvector(dc_f32x2{v0, v1}, dc_f16x2);
-      const dc_f16x2 h23 = __builtin_convertvector(dc_f32x2{v2, v3}, dc_f16x2);
+      const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+      const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
       float r0, r1, r2, r3;                        // v - (float)h, exact
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-      const dc_f16x2 l01 = __builtin_convertvector(dc_f32x2{r0, r1}, dc_f16x2);
-      const dc_f16x2 l23 = __builtin_convertvector(dc_f32x2{r2, r3}, dc_f16x2);
-      const dc_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
-      if (loff[s] >= 0) *reinterpret_cast<dc_f16x8*>(dst + loff[s]) = word;
+      const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+      const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+      const rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+      if (loff[s] >= 0) *reinterpret_cast<rw_f16x8*>(dst + loff[s]) = word;
     }
   };
 
   // ---- weight operands of this wave's two blocks: the three taps (ky = 0..2) of one kernel COLUMN kx in registers.  In
-  // memory (and in flight) an operand is its four distinct halves; dc_expand() doubles them on arrival.
+  // memory (and in flight) an operand is its four distinct halves; rw_expand() doubles them on arrival.
   const int vb0 = ot * (2 * WM) + 2 * wm;
   const unsigned char* wbase = p.wp + (int64_t)vb0 * T * 1024 + lane * 8;
-  dc_f16x8 W[3][2][2];
-  dc_f32x2 Wc[3][2][2];
+  rw_f16x8 W[3][2][2];
+  rw_f32x2 Wc[3][2][2];
   auto wload = [&](int ky, int t) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
       for (int part = 0; part < 2; ++part) {
-        if (DC_ABL & 4) Wc[ky][ob][part] = dc_f32x2{1.f, 1.f};
-        else Wc[ky][ob][part] = *reinterpret_cast<const dc_f32x2*>(wbase + ((int64_t)ob * T + t) * 1024 + part * 512);
+        if (DC_ABL & 4) Wc[ky][ob][part] = rw_f32x2{1.f, 1.f};
+        else Wc[ky][ob][part] = *reinterpret_cast<const rw_f32x2*>(wbase + ((int64_t)ob * T + t) * 1024 + part * 512);
       }
   };
   // W[ky][ob][0] = [Uh | Uh] of tap ky; DC_PRODUCTS == 3: W[0][ob][1] = [Ul(ky 0) | Ul(ky 1)], W[2][ob][1] = [Ul | Ul] of
@@ -260,17 +220,17 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   auto wexpand = [&](int ky) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob) {
-      W[ky][ob][0] = dc_expand(Wc[ky][ob][0]);
-      if (DC_PRODUCTS == 4 || ky == 2) W[ky][ob][1] = dc_expand(Wc[ky][ob][1]);
-      else if (ky == 1) W[0][ob][1] = dc_pair(Wc[0][ob][1], Wc[1][ob][1]);       // first used in row 1
+      W[ky][ob][0] = rw_expand(Wc[ky][ob][0]);
+      if (DC_PRODUCTS == 4 || ky == 2) W[ky][ob][1] = rw_expand(Wc[ky][ob][1]);
+      else if (ky == 1) W[0][ob][1] = rw_pair(Wc[0][ob][1], Wc[1][ob][1]);       // first used in row 1
     }
   };
 
-  dc_f32x4 acc[2][8];
+  rw_f32x4 acc[2][8];
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
-    for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = dc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
 
   // pixel operand of window row 4 wn + r (r = 0..5), column 16 half + lt + kx, quad lk: it serves the taps (ky, kx) of
   // the pixel blocks of row r - ky -- read ONCE per kernel column (36 reads per chunk for 288 MFMAs)
@@ -278,10 +238,10 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
     const int cc = lt + kx;
-    bbase[kx] = (unsigned)((4 * wn * DC_PW + cc) * 64 + ((lk ^ dc_swz(cc)) << 4));
+    bbase[kx] = (unsigned)((4 * wn * DC_PW + cc) * 64 + ((lk ^ rw_swz(cc)) << 4));
   }
   auto bread = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
-    return *reinterpret_cast<const dc_f16x8*>(lb + bbase[kx] + ((idx >> 1) * DC_PW + 16 * (idx & 1)) * 64);
+    return *reinterpret_cast<const rw_f16x8*>(lb + bbase[kx] + ((idx >> 1) * DC_PW + 16 * (idx & 1)) * 64);
   };
 
   // One chunk.  Kernel column kx: rows r = 0..5, halves 0 / 1 (idx = 2 r + half); the operand of idx + 1 is read before
@@ -292,8 +252,8 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
     const int buf = c & 1;
     const unsigned char* lb = Ls + buf * BUFB;
     if (!LAST) stage_load(c + 1, rw_int<0>());
-    dc_f16x8 bcur = bread(lb, 0, 0);
-    dc_f16x8 bprev[2] = {bcur, bcur};               // the operand one row up, per half (DC_PRODUCTS == 3)
+    rw_f16x8 bcur = bread(lb, 0, 0);
+    rw_f16x8 bprev[2] = {bcur, bcur};               // the operand one row up, per half (DC_PRODUCTS == 3)
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
       const bool more = !LAST || kx < 2;            // is there a next column
@@ -302,7 +262,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
       for (int idx = 0; idx < 12; ++idx) {
         const int r = idx >> 1, half = idx & 1;
         if (half == 0 && r < 3) wexpand(r);         // tap ky = r is first used in row r
-        dc_f16x8 bnext = bcur;
+        rw_f16x8 bnext = bcur;
         if (idx + 1 < 12) bnext = bread(lb, kx, idx + 1);
         else if (kx < 2) bnext = bread(lb, kx + 1, 0);
 #pragma unroll
@@ -320,7 +280,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
         }
         if (DC_PRODUCTS == 3 && r >= 1 && r <= 4 && !(DC_ABL & 2)) {      // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
           const int pb = 2 * (r - 1) + half;
-          const dc_f16x8 hh = dc_pair(bprev[half], bcur);
+          const rw_f16x8 hh = rw_pair(bprev[half], bcur);
           acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][0][1], acc[0][pb], 0, 0, 0);
           acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][1][1], acc[1][pb], 0, 0, 0);
         }
@@ -375,9 +335,9 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 #pragma unroll
     for (int pb = 0; pb < 8; ++pb) {
       const int64_t pix = (int64_t)(y0 + 4 * wn + (pb >> 1)) * p.w + x0 + 16 * (pb & 1) + 4 * lk;
-      dc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-      if (p.noise) nz = *reinterpret_cast<const dc_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
-      dc_f32x4 v[2];
+      rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+      if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
+      rw_f32x4 v[2];
 #pragma unroll
       for (int ob = 0; ob < 2; ++ob) {
 #pragma unroll
@@ -386,16 +346,16 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
           v[ob][j] = fmaxf(u, u * slope);
           ymax = fmaxf(ymax, fabsf(v[ob][j]));
         }
-        *reinterpret_cast<dc_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
+        *reinterpret_cast<rw_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
       }
       if (RGBP) {
-        dc_f32x4 sum[3];
+        rw_f32x4 sum[3];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int cc = 0; cc < 3; ++cc) sum[cc][j] = dc_row_sum(v[0][j] * cr[0][cc] + v[1][j] * cr[1][cc]);
         // every lane of the row holds the sums: lane lt == cc stores colour cc
-        if (lt < 3) *reinterpret_cast<dc_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
+        if (lt < 3) *reinterpret_cast<rw_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
       }
     }
   } else if (UP) {
@@ -409,22 +369,22 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 #pragma unroll
     for (int pb = 0; pb < 8; ++pb) {
       const int64_t pix = (int64_t)(2 * (y0 + 4 * wn + (pb >> 1)) + wm) * W2 + 2 * (x0 + 16 * (pb & 1) + 4 * lk);
-      dc_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
+      rw_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
       if (p.noise) {
         const float* np = p.noise + (int64_t)ib * hw2 + pix;
-        n0 = *reinterpret_cast<const dc_f32x4*>(np) * noise_wg;
-        n1 = *reinterpret_cast<const dc_f32x4*>(np + 4) * noise_wg;
+        n0 = *reinterpret_cast<const rw_f32x4*>(np) * noise_wg;
+        n1 = *reinterpret_cast<const rw_f32x4*>(np + 4) * noise_wg;
       }
-      dc_f32x4 q0 = {acc[0][pb][0], acc[1][pb][0], acc[0][pb][1], acc[1][pb][1]};
-      dc_f32x4 q1 = {acc[0][pb][2], acc[1][pb][2], acc[0][pb][3], acc[1][pb][3]};
+      rw_f32x4 q0 = {acc[0][pb][0], acc[1][pb][0], acc[0][pb][1], acc[1][pb][1]};
+      rw_f32x4 q1 = {acc[0][pb][2], acc[1][pb][2], acc[0][pb][3], acc[1][pb][3]};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float u0 = q0[k] * sc + n0[k] + bs, u1 = q1[k] * sc + n1[k] + bs;
         q0[k] = fmaxf(u0, u0 * slope) * post; q1[k] = fmaxf(u1, u1 * slope) * post;
         ymax = fmaxf(ymax, fmaxf(fabsf(q0[k]), fabsf(q1[k])));
       }
-      *reinterpret_cast<dc_f32x4*>(yb + pix) = q0;
-      *reinterpret_cast<dc_f32x4*>(yb + pix + 4) = q1;
+      *reinterpret_cast<rw_f32x4*>(yb + pix) = q0;
+      *reinterpret_cast<rw_f32x4*>(yb + pix + 4) = q1;
     }
   } else {
     // RGB: channels lt and 16 + lt of the wave's pixels; the sum over channels = over the 16 lanes of a DPP row
@@ -437,9 +397,9 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 #pragma unroll
     for (int pb = 0; pb < 8; ++pb) {
       const int64_t pix = (int64_t)(y0 + 4 * wn + (pb >> 1)) * p.w + x0 + 16 * (pb & 1) + 4 * lk;
-      dc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-      if (p.noise) nz = *reinterpret_cast<const dc_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
-      dc_f32x4 sum[3];
+      rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+      if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
+      rw_f32x4 sum[3];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float u0 = acc[0][pb][j] * sc[0] + nz[j] + bs[0], u1 = acc[1][pb][j] * sc[1] + nz[j] + bs[1];
@@ -449,11 +409,11 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
       }
       // every lane of the row holds the sums: lane lt == cc stores colour cc
       if (lt < 3) {
-        const dc_f32x4 mine = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
+        const rw_f32x4 mine = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
         const int64_t off = ((int64_t)ib * 3 + lt) * hw + pix;
-        dc_f32x4 o4 = mine + (p.rgb_bias ? p.rgb_bias[lt] : 0.f);
-        if (p.rgb_skip) o4 += *reinterpret_cast<const dc_f32x4*>(p.rgb_skip + off);
-        *reinterpret_cast<dc_f32x4*>(p.rgb_out + off) = o4;
+        rw_f32x4 o4 = mine + (p.rgb_bias ? p.rgb_bias[lt] : 0.f);
+        if (p.rgb_skip) o4 += *reinterpret_cast<const rw_f32x4*>(p.rgb_skip + off);
+        *reinterpret_cast<rw_f32x4*>(p.rgb_out + off) = o4;
       }
     }
   }
@@ -519,7 +479,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   const int per = (int)((total + gridDim.x - 1) / gridDim.x);
   // strided: the workgroups that run at the same time work on NEIGHBOURING tiles (those of one XCD on 32 consecutive ones)
   // -- their stores fill whole rows of the output planes together; contiguous: a workgroup walks its own run of tiles
-  const int bx = p.strided ? dc_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int bx = p.strided ? rw_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
   const int t0 = p.strided ? 0 : bx * per;
   const int t1 = p.strided ? (int)((total - bx + gridDim.x - 1) / gridDim.x)
                            : (int)((int64_t)t0 + per < total ? t0 + per : total);       // run = positions [t0, t1)
@@ -562,7 +522,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     int xoff[SI];
     __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0, 0x00020000);
     // the chunk that is in flight / waits for its conversion
-    dc_f32x4 raw[QW][SI][4];                         // [channel k]: four pixels
+    rw_f32x4 raw[QW][SI][4];                         // [channel k]: four pixels
     float psv[QW][4];
     float a_demod = 1.f, a_bias = 0.f, a_rgb = 0.f, a_post = 1.f, a_oscale = 1.f, a_iscale = 1.f;
     float a_crw[3] = {0.f, 0.f, 0.f};                // RGBP: the ToRGB weights of the tile's out-channel block
@@ -638,19 +598,19 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     // count, so its waits leave exactly the younger loads in flight (LDS-direct weight loads from inline assembly, which it
     // cannot see, made every count nine too small: each interval waited for the weights it had just requested)
     static_assert(NL == 2 * WM && SI == 3, "wave j stages weight block j, three tap pieces per pixel piece");
-    dc_f32x4 wraw[SI][3];
+    rw_f32x4 wraw[SI][3];
     auto request_s = [&](int s) __attribute__((always_inline)) {
 #pragma unroll
       for (int q = 0; q < QW; ++q)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          if (DC_ABL & 1) raw[q][s][k] = dc_f32x4{1.f, 1.f, 1.f, 1.f};
-          else raw[q][s][k] = __builtin_bit_cast(dc_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + (4 * q + k) * hw4, 0));
+          if (DC_ABL & 1) raw[q][s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
+          else raw[q][s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + (4 * q + k) * hw4, 0));
         }
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        if (DC_ABL & 4) wraw[s][k] = dc_f32x4{1.f, 1.f, 1.f, 1.f};
-        else wraw[s][k] = *reinterpret_cast<const dc_f32x4*>(l_wsrc + (3 * s + k) * 1024 + lane * 16);
+        if (DC_ABL & 4) wraw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
+        else wraw[s][k] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + (3 * s + k) * 1024 + lane * 16);
       }
     };
     // what setup() requested beside the pixels -> registers / LDS (the first wait of an interval)
@@ -675,7 +635,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
       unsigned char* dst = Ls + buf * BUFB;
       unsigned char* wdst = Wl + buf * WBUF + (wave - MW) * 9216 + lane * 16;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) *reinterpret_cast<dc_f32x4*>(wdst + (3 * s + k) * 1024) = wraw[s][k];
+      for (int k = 0; k < 3; ++k) *reinterpret_cast<rw_f32x4*>(wdst + (3 * s + k) * 1024) = wraw[s][k];
       const int it = 64 * s + lane;
       const int j = it % IPR;
 #pragma unroll
@@ -684,19 +644,19 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         for (int e = 0; e < 4; ++e) {
           const float v0 = raw[q][s][0][e] * sv[q][0], v1 = raw[q][s][1][e] * sv[q][1], v2 = raw[q][s][2][e] * sv[q][2],
                       v3 = raw[q][s][3][e] * sv[q][3];
-          const dc_f16x2 h01 = __builtin_convertvector(dc_f32x2{v0, v1}, dc_f16x2);
-          const dc_f16x2 h23 = __builtin_convertvector(dc_f32x2{v2, v3}, dc_f16x2);
+          const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+          const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
           float r0, r1, r2, r3;                      // v - (float)h, exact
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-          const dc_f16x2 l01 = __builtin_convertvector(dc_f32x2{r0, r1}, dc_f16x2);
-          const dc_f16x2 l23 = __builtin_convertvector(dc_f32x2{r2, r3}, dc_f16x2);
-          const dc_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+          const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+          const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+          const rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
           const int cc = 4 * j - 3 + e;              // window column of this pixel
           if (it < NITEM && cc >= 0 && cc < PW)
-            *reinterpret_cast<dc_f16x8*>(dst + loff[s] + e * 64 + (((g2 + q) ^ dc_swz(cc)) << 4)) = word;
+            *reinterpret_cast<rw_f16x8*>(dst + loff[s] + e * 64 + (((g2 + q) ^ rw_swz(cc)) << 4)) = word;
         }
     };
 
@@ -752,34 +712,34 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
     const int cc = lt + kx;
-    bbase[kx] = (unsigned)((4 * wr * PW + 32 * wc + cc) * 64 + ((lk ^ dc_swz(cc)) << 4));
+    bbase[kx] = (unsigned)((4 * wr * PW + 32 * wc + cc) * 64 + ((lk ^ rw_swz(cc)) << 4));
   }
   auto bread = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
-    return *reinterpret_cast<const dc_f16x8*>(lb + bbase[kx] + ((idx >> 1) * PW + 16 * (idx & 1)) * 64);
+    return *reinterpret_cast<const rw_f16x8*>(lb + bbase[kx] + ((idx >> 1) * PW + 16 * (idx & 1)) * 64);
   };
   // weights.  A chunk is six HALF-steps (kernel column kx, piece Uh / Ul): 48 MFMAs on 48 different accumulators with the
   // six operands [ky][ob] of that piece -- 24 registers where a whole column's twelve take 48, which is what lets three waves
   // share a SIMD (168 registers; the pixel operands are then read once per half-step: 72 reads per chunk).  They come from
   // the chunk's copy in LDS (8 bytes per lane, doubled into the operand), one half-step ahead: through the L1 they were
   // 288 loads per chunk and CU -- three quarters of everything the CU's memory path carried, and it was full (r04q).
-  dc_f16x8 W[3][2];
-  dc_f32x2 Wc[3][2];
+  rw_f16x8 W[3][2];
+  rw_f32x2 Wc[3][2];
   auto wread = [&](const unsigned char* wb, int kx, int part) __attribute__((always_inline)) {
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int ob = 0; ob < 2; ++ob) {
-        if (DC_ABL & 4) Wc[ky][ob] = dc_f32x2{1.f, 1.f};
-        else Wc[ky][ob] = *reinterpret_cast<const dc_f32x2*>(wb + ((2 * wm + ob) * 9 + 3 * ky + kx) * 1024 + part * 512 + lane * 8);
+        if (DC_ABL & 4) Wc[ky][ob] = rw_f32x2{1.f, 1.f};
+        else Wc[ky][ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 3 * ky + kx) * 1024 + part * 512 + lane * 8);
       }
   };
   const float noise_wg = p.noise ? p.noise_w[0] * gain : 0.f;
-  dc_f32x4 nzp[PLAIN ? 8 : 1];
-  dc_f32x4 acc[2][8];
+  rw_f32x4 nzp[PLAIN ? 8 : 1];
+  rw_f32x4 acc[2][8];
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
-    for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = dc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;
   float rgb_b[3] = {0.f, 0.f, 0.f};
   if (RGB && p.rgb_bias) { rgb_b[0] = p.rgb_bias[0]; rgb_b[1] = p.rgb_bias[1]; rgb_b[2] = p.rgb_bias[2]; }
@@ -801,13 +761,13 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     if (PLAIN && c == NC - 1 && p.noise) {          // the tile's noise, requested a chunk of MFMAs before its epilogue
       const float* np = p.noise + (int64_t)ib * hw + (int64_t)(ty * TR + 4 * wr) * p.w + tx * TC + 32 * wc + 4 * lk;
 #pragma unroll
-      for (int pb = 0; pb < 8; ++pb) nzp[pb] = *reinterpret_cast<const dc_f32x4*>(np + (int64_t)(pb >> 1) * p.w + 16 * (pb & 1));
+      for (int pb = 0; pb < 8; ++pb) nzp[pb] = *reinterpret_cast<const rw_f32x4*>(np + (int64_t)(pb >> 1) * p.w + 16 * (pb & 1));
     }
-    dc_f16x8 bq[3];
+    rw_f16x8 bq[3];
     wread(wb, 0, 0);
     bq[0] = bread(lb, 0, 0);
     bq[1] = bread(lb, 0, 1);
-    dc_f16x8 bprev[2] = {bq[0], bq[1]};             // the operand one row up, per half (DC_PRODUCTS == 3, part 1)
+    rw_f16x8 bprev[2] = {bq[0], bq[1]};             // the operand one row up, per half (DC_PRODUCTS == 3, part 1)
 #pragma unroll
     for (int hs = 0; hs < 6; ++hs) {
       const int kx = hs >> 1, part = hs & 1;
@@ -817,10 +777,10 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
       for (int ob = 0; ob < 2; ++ob) {
         if (DC_PRODUCTS == 4 || part == 0) {
 #pragma unroll
-          for (int ky = 0; ky < 3; ++ky) W[ky][ob] = dc_expand(Wc[ky][ob]);
+          for (int ky = 0; ky < 3; ++ky) W[ky][ob] = rw_expand(Wc[ky][ob]);
         } else {
-          W[0][ob] = dc_pair(Wc[0][ob], Wc[1][ob]);
-          W[2][ob] = dc_expand(Wc[2][ob]);
+          W[0][ob] = rw_pair(Wc[0][ob], Wc[1][ob]);
+          W[2][ob] = rw_expand(Wc[2][ob]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -829,7 +789,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
       for (int idx = 0; idx < 12; ++idx) {
         const int r = idx >> 1, half = idx & 1;
-        const dc_f16x8 b = bq[idx % 3];
+        const rw_f16x8 b = bq[idx % 3];
         if (idx + 2 < 12) bq[(idx + 2) % 3] = bread(lb, kx, idx + 2);
         else if (hs < 5) bq[(idx + 2) % 3] = bread(lb, (hs + 1) >> 1, idx + 2 - 12);
         if (DC_PRODUCTS == 4 || part == 0) {
@@ -847,7 +807,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         } else {
           if (r >= 1 && r <= 4) {                   // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
             const int pb = 2 * (r - 1) + half;
-            const dc_f16x8 hh = dc_pair(bprev[half], b);
+            const rw_f16x8 hh = rw_pair(bprev[half], b);
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][1], acc[1][pb], 0, 0, 0);
           }
@@ -894,9 +854,9 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
         for (int pb = 0; pb < 8; ++pb) {
           const int64_t pix = (int64_t)(y0 + 4 * wr + (pb >> 1)) * p.w + x0 + 32 * wc + 16 * (pb & 1) + 4 * lk;
-          dc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+          rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
           if (p.noise) nz = nzp[pb] * noise_wg;
-          dc_f32x4 v[2];
+          rw_f32x4 v[2];
 #pragma unroll
           for (int ob = 0; ob < 2; ++ob) {
 #pragma unroll
@@ -905,16 +865,16 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
               v[ob][j] = fmaxf(u, u * slope);
               ymax = fmaxf(ymax, fabsf(v[ob][j]));
             }
-            if (!(DC_ABL & 16)) *reinterpret_cast<dc_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
+            if (!(DC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
           }
           if (RGBP) {
-            dc_f32x4 sum[3];
+            rw_f32x4 sum[3];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
               for (int cc = 0; cc < 3; ++cc) sum[cc][j] = dc_row_sum(v[0][j] * cr[0][cc] + v[1][j] * cr[1][cc]);
             // every lane of the row holds the sums: lane lt == cc stores colour cc
-            if (lt < 3 && !(DC_ABL & 16)) *reinterpret_cast<dc_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
+            if (lt < 3 && !(DC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
           }
         }
       } else if (UP) {
@@ -927,14 +887,14 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         for (int pb = 0; pb < 8; ++pb) {
           const int orow = 2 * (4 * wr + (pb >> 1)) + wm, ocol = 2 * (32 * wc + 16 * (pb & 1) + 4 * lk);
           const int64_t pix = (int64_t)(2 * y0 + orow) * W2 + 2 * x0 + ocol;
-          dc_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
+          rw_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
           if (p.noise) {
             const float* np = p.noise + (int64_t)ib * (4 * hw) + pix;
-            n0 = *reinterpret_cast<const dc_f32x4*>(np) * noise_wg;
-            n1 = *reinterpret_cast<const dc_f32x4*>(np + 4) * noise_wg;
+            n0 = *reinterpret_cast<const rw_f32x4*>(np) * noise_wg;
+            n1 = *reinterpret_cast<const rw_f32x4*>(np + 4) * noise_wg;
           }
-          dc_f32x4 q0 = {acc[0][pb][0], acc[1][pb][0], acc[0][pb][1], acc[1][pb][1]};
-          dc_f32x4 q1 = {acc[0][pb][2], acc[1][pb][2], acc[0][pb][3], acc[1][pb][3]};
+          rw_f32x4 q0 = {acc[0][pb][0], acc[1][pb][0], acc[0][pb][1], acc[1][pb][1]};
+          rw_f32x4 q1 = {acc[0][pb][2], acc[1][pb][2], acc[0][pb][3], acc[1][pb][3]};
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float u0 = q0[k] * sc + n0[k] + bs, u1 = q1[k] * sc + n1[k] + bs;
@@ -942,8 +902,8 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             ymax = fmaxf(ymax, fmaxf(fabsf(q0[k]), fabsf(q1[k])));
           }
           if (!(DC_ABL & 16)) {
-            *reinterpret_cast<dc_f32x4*>(yb + pix) = q0;
-            *reinterpret_cast<dc_f32x4*>(yb + pix + 4) = q1;
+            *reinterpret_cast<rw_f32x4*>(yb + pix) = q0;
+            *reinterpret_cast<rw_f32x4*>(yb + pix + 4) = q1;
           }
         }
       } else {
@@ -956,9 +916,9 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
         for (int pb = 0; pb < 8; ++pb) {
           const int64_t pix = (int64_t)(y0 + 4 * wr + (pb >> 1)) * p.w + x0 + 32 * wc + 16 * (pb & 1) + 4 * lk;
-          dc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-          if (p.noise) nz = *reinterpret_cast<const dc_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
-          dc_f32x4 sum[3];
+          rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+          if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw + pix) * noise_wg;
+          rw_f32x4 sum[3];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float u0 = acc[0][pb][j] * sc[0] + nz[j] + bs[0], u1 = acc[1][pb][j] * sc[1] + nz[j] + bs[1];
@@ -967,11 +927,11 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             for (int cc = 0; cc < 3; ++cc) sum[cc][j] = dc_row_sum(u0 * cr[0][cc] + u1 * cr[1][cc]);
           }
           if (lt < 3) {
-            const dc_f32x4 mine = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
+            const rw_f32x4 mine = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
             const int64_t off = ((int64_t)ib * 3 + lt) * hw + pix;
-            dc_f32x4 o4 = mine + (lt == 0 ? rgb_b[0] : (lt == 1 ? rgb_b[1] : rgb_b[2]));
-            if (p.rgb_skip) o4 += *reinterpret_cast<const dc_f32x4*>(p.rgb_skip + off);
-            *reinterpret_cast<dc_f32x4*>(p.rgb_out + off) = o4;
+            rw_f32x4 o4 = mine + (lt == 0 ? rgb_b[0] : (lt == 1 ? rgb_b[1] : rgb_b[2]));
+            if (p.rgb_skip) o4 += *reinterpret_cast<const rw_f32x4*>(p.rgb_skip + off);
+            *reinterpret_cast<rw_f32x4*>(p.rgb_out + off) = o4;
           }
         }
       }
@@ -979,7 +939,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
-      for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = dc_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     if (++tile < t1) decode(tile, ot, tx, ty, ib);
 #if DC_PROF
     pt_epi += DC_T();
@@ -1080,13 +1040,11 @@ __global__ void __launch_bounds__(256) pack_dconv_kernel(const float* __restrict
 
 // RW_DCONV_V=1: the one-role kernels (two workgroups per CU); default: the specialised ones (in_ch >= 32)
 static bool dconv_specialised(int in_ch, const rw_conv_epilogue* ep) {
-  const char* e = getenv("RW_DCONV_V");
-  return in_ch >= 32 && ep && ep->style && !(e && e[0] == '1');
+  return in_ch >= 32 && ep && ep->style && !rw_env_is("RW_DCONV_V", '1');
 }
 // as many workgroups as fit the chip at once, each taking every (grid)th tile
 static unsigned dconv_ws_grid(int64_t tiles, int per_cu = 1) {
-  const char* e = getenv("RW_DCONV_GRID");
-  int64_t g = e ? atoi(e) : (int64_t)rw_cu_count() * per_cu;
+  int64_t g = rw_env_int("RW_DCONV_GRID", rw_cu_count() * per_cu);
   if (g < 1) g = 1;
   return (unsigned)(tiles < g ? tiles : g);
 }
@@ -1108,9 +1066,7 @@ static int dconv_absmax(const float* w, const float* k4, int vch, int in_ch, flo
   const int grid = rw_stream_grid(total, 256);
   hipLaunchKernelGGL((pack_dconv_kernel<1, UP>), dim3(grid), dim3(256), 0, rw_s(stream), w, k4, (unsigned char*)nullptr,
                      (float*)nullptr, vch, in_ch, 1.f, bound);
-  const int rc = RW_LAUNCH_RESULT();
-  if (rc) return rc;
-  return rw_bound_finish(bound, grid, rw_s(stream));
+  return rw_finish_bound(bound, grid, stream);
 }
 
 template <bool UP>
@@ -1135,41 +1091,32 @@ extern "C" int rw_pack_dconv_weight_f32(const float* w, float* wp, int out_ch, i
   return dconv_pack<false>(w, nullptr, wp, out_ch, in_ch, u_scale, stream);
 }
 
-// after a launch whose waves stored their maxima: the bound of the result
-static int dconv_finish(float* y_amax, int64_t nslots, rw_stream_t stream) {
-  const int rc = RW_LAUNCH_RESULT();
-  if (rc || !y_amax) return rc;
-  return rw_bound_finish(y_amax, nslots, rw_s(stream));
-}
-
 static void dconv_fill(DconvProblem& p, const float* x, const float* wp, int batch, int in_ch, int vch, int h, int w,
                        float w_scale, const rw_conv_epilogue* ep, float u_inv, const float* x_amax, float* y_amax) {
   p.x = x; p.wp = reinterpret_cast<const unsigned char*>(wp);
   p.u_inv = u_inv;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
+  rw_fill_epilogue(p, ep);
   p.batch = batch; p.in_ch = in_ch; p.out_ch = vch; p.h = h; p.w = w; p.w_scale = w_scale;
   p.x_amax = x_amax; p.y_amax = y_amax;
   p.tiles_x = w / 32;
-  const char* e = getenv("RW_DCONV_ORDER");
-  p.strided = e ? atoi(e) : 1;
+  p.strided = rw_env_int("RW_DCONV_ORDER", 1);
 }
 
-extern "C" int rw_dconv3x3_f32(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch, int h, int w,
-                               float w_scale, const rw_conv_epilogue* ep, float u_inv, const float* x_amax, float* y_amax,
-                               rw_stream_t stream) {
-  RW_CHECK_ARG(x && wp && y && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+// The stride-1 convolution, with (rgb: rw_dconv3x3_rgb_partial_f32) or without the partial sums of the ToRGB behind it.
+static int dconv3x3_launch(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch, int h, int w,
+                           float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, float u_inv,
+                           const float* x_amax, float* y_amax, rw_stream_t stream) {
   if (!dconv_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   if ((int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return RW_ERR_UNSUPPORTED;
   DconvProblem p = {};
   dconv_fill(p, x, wp, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
   p.y = y;
+  if (rgb) { p.rgb_weight = rgb->weight; p.rgb_style = rgb->style; p.rgb_out = rgb->out; p.rgb_scale = rgb->scale; }
   const int64_t cap = rw_bound_slot_capacity((int64_t)batch * out_ch * h * w);
   // out-channels of a workgroup: 128 / 64 / 32 -- the widest that divides (the window is staged once for all of them)
-  const char* e = getenv("RW_DCONV_WM");
   int wm = out_ch % 128 == 0 ? 4 : (out_ch % 64 == 0 ? 2 : 1);
-  if (e && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4) && out_ch % (32 * atoi(e)) == 0) wm = atoi(e);
+  const int force = rw_env_int("RW_DCONV_WM", 0);
+  if ((force == 1 || force == 2 || force == 4) && out_ch % (32 * force) == 0) wm = force;
   p.o_tiles = out_ch / (32 * wm);
   p.tiles_y = h / (16 / wm);
   const int64_t work = (int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles;
@@ -1180,14 +1127,24 @@ extern "C" int rw_dconv3x3_f32(const float* x, const float* wp, float* y, int ba
     p.o_tiles = out_ch / 64; p.tiles_y = h / 8; p.tiles_x = w / 64;
     const unsigned grid = dconv_ws_grid((int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles);
     if (y_amax && 12LL * grid > cap) return RW_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dconv_ws_w2_kernel, dim3(grid), dim3(768), 0, rw_s(stream), p);
-    return dconv_finish(y_amax, 12LL * grid, stream);
+    void (*const ws_kernel)(DconvProblem) = rgb ? dconv_ws_w2_rgbp_kernel : dconv_ws_w2_kernel;
+    hipLaunchKernelGGL(ws_kernel, dim3(grid), dim3(768), 0, rw_s(stream), p);
+    return rw_finish_bound(y_amax, 12LL * grid, stream);
   }
   if (y_amax && 4 * work > cap) return RW_ERR_UNSUPPORTED;
-  if (wm == 4) hipLaunchKernelGGL(dconv_w4_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  else if (wm == 2) hipLaunchKernelGGL(dconv_w2_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  else hipLaunchKernelGGL(dconv_w1_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  return dconv_finish(y_amax, 4 * work, stream);
+  void (*const kernel)(DconvProblem) = wm == 4 ? (rgb ? dconv_w4_rgbp_kernel : dconv_w4_kernel)
+                                     : wm == 2 ? (rgb ? dconv_w2_rgbp_kernel : dconv_w2_kernel)
+                                               : (rgb ? dconv_w1_rgbp_kernel : dconv_w1_kernel);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
+  return rw_finish_bound(y_amax, 4 * work, stream);
+}
+
+extern "C" int rw_dconv3x3_f32(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch, int h, int w,
+                               float w_scale, const rw_conv_epilogue* ep, float u_inv, const float* x_amax, float* y_amax,
+                               rw_stream_t stream) {
+  RW_CHECK_ARG(x && wp && y && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
+  return dconv3x3_launch(x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep, nullptr, u_inv, x_amax, y_amax, stream);
 }
 
 // ---- the same convolution + the partial sums of the ToRGB that consumes its result (ToRGBF.forward, models.py:639-655: a 1x1
@@ -1200,34 +1157,9 @@ extern "C" int rw_dconv3x3_rgb_partial_f32(const float* x, const float* wp, floa
                                            int w, float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb,
                                            float u_inv, const float* x_amax, float* y_amax, rw_stream_t stream) {
   RW_CHECK_ARG(x && wp && y && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(rgb && rgb->weight && rgb->style && rgb->out);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
-  if (!dconv_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
-  if ((int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return RW_ERR_UNSUPPORTED;
-  DconvProblem p = {};
-  dconv_fill(p, x, wp, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
-  p.y = y;
-  p.rgb_weight = rgb->weight; p.rgb_style = rgb->style; p.rgb_out = rgb->out; p.rgb_scale = rgb->scale;
-  const int64_t cap = rw_bound_slot_capacity((int64_t)batch * out_ch * h * w);
-  const char* e = getenv("RW_DCONV_WM");
-  int wm = out_ch % 128 == 0 ? 4 : (out_ch % 64 == 0 ? 2 : 1);
-  if (e && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4) && out_ch % (32 * atoi(e)) == 0) wm = atoi(e);
-  p.o_tiles = out_ch / (32 * wm);
-  p.tiles_y = h / (16 / wm);
-  const int64_t work = (int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles;
-  if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
-  if (dconv_specialised(in_ch, ep) && out_ch % 64 == 0 && h % 8 == 0 && w % 64 == 0) {      // as rw_dconv3x3_f32: a style on load
-    p.o_tiles = out_ch / 64; p.tiles_y = h / 8; p.tiles_x = w / 64;
-    const unsigned grid = dconv_ws_grid((int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles);
-    if (y_amax && 12LL * grid > cap) return RW_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dconv_ws_w2_rgbp_kernel, dim3(grid), dim3(768), 0, rw_s(stream), p);
-    return dconv_finish(y_amax, 12LL * grid, stream);
-  }
-  if (y_amax && 4 * work > cap) return RW_ERR_UNSUPPORTED;
-  if (wm == 4) hipLaunchKernelGGL(dconv_w4_rgbp_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  else if (wm == 2) hipLaunchKernelGGL(dconv_w2_rgbp_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  else hipLaunchKernelGGL(dconv_w1_rgbp_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  return dconv_finish(y_amax, 4 * work, stream);
+  RW_CHECK_ARG(rw_rgb_ok(rgb));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
+  return dconv3x3_launch(x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, u_inv, x_amax, y_amax, stream);
 }
 
 // ---- conv_transpose(stride 2) + blur + noise + bias + leaky ReLU in one pass (rw_conv_transpose3x3s2_blur_wino4_f32's operation)
@@ -1258,7 +1190,7 @@ extern "C" int rw_dconv_transpose3x3s2_blur_f32(const float* x, const float* wp,
                                                 const float* post_scale, float u_inv, const float* x_amax, float* y_amax,
                                                 rw_stream_t stream) {
   RW_CHECK_ARG(x && wp && y && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (!dconv_up_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   if ((int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return RW_ERR_UNSUPPORTED;
   DconvProblem p = {};
@@ -1274,11 +1206,11 @@ extern "C" int rw_dconv_transpose3x3s2_blur_f32(const float* x, const float* wp,
     const unsigned grid = dconv_ws_grid((int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles);
     if (y_amax && 12LL * grid > cap) return RW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(dconv_ws_up_kernel, dim3(grid), dim3(768), 0, rw_s(stream), p);
-    return dconv_finish(y_amax, 12LL * grid, stream);
+    return rw_finish_bound(y_amax, 12LL * grid, stream);
   }
   if (y_amax && 4 * work > cap) return RW_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(dconv_up_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  return dconv_finish(y_amax, 4 * work, stream);
+  return rw_finish_bound(y_amax, 4 * work, stream);
 }
 
 // ---- the last styled convolution with ToRGB in the epilogue (rw_conv3x3_wino4_to_rgb_f32's operation)
@@ -1288,14 +1220,13 @@ extern "C" int rw_dconv3x3_to_rgb_supported(int out_ch, int in_ch, int h, int w)
 extern "C" int rw_dconv3x3_to_rgb_f32(const float* x, const float* wp, int batch, int in_ch, int out_ch, int h, int w,
                                       float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, float u_inv,
                                       const float* x_amax, rw_stream_t stream) {
-  RW_CHECK_ARG(x && wp && rgb && rgb->weight && rgb->style && rgb->out && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(x && wp && rw_rgb_ok(rgb) && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0);
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (!rw_dconv3x3_to_rgb_supported(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   if ((int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return RW_ERR_UNSUPPORTED;
   DconvProblem p = {};
   dconv_fill(p, x, wp, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, nullptr);
-  p.rgb_weight = rgb->weight; p.rgb_style = rgb->style; p.rgb_bias = rgb->bias; p.rgb_skip = rgb->skip;
-  p.rgb_out = rgb->out; p.rgb_scale = rgb->scale;
+  rw_fill_rgb(p, rgb);
   p.o_tiles = 1;
   p.tiles_y = h / 16;
   const int64_t work = (int64_t)batch * p.tiles_y * p.tiles_x;
@@ -1303,8 +1234,7 @@ extern "C" int rw_dconv3x3_to_rgb_f32(const float* x, const float* wp, int batch
   // RW_DCONV_V=2 (opt-in: at layer 18's shape it takes 7.4 ms where the kernel below takes 6.7 and the F(4x4) kernel 5.8 --
   // four multiplying waves per CU issue half the matrix rate of eight, profiles/r06l), a style on load, maps 64 columns wide:
   // the persistent workgroup with specialised waves
-  const char* ve = getenv("RW_DCONV_V");
-  if (ve && ve[0] == '2' && dconv_specialised(in_ch, ep) && h % 8 == 0 && w % 64 == 0) {
+  if (rw_env_is("RW_DCONV_V", '2') && dconv_specialised(in_ch, ep) && h % 8 == 0 && w % 64 == 0) {
     p.tiles_y = h / 8; p.tiles_x = w / 64;
     const unsigned grid = dconv_ws_grid((int64_t)batch * p.tiles_y * p.tiles_x);
     hipLaunchKernelGGL(dconv_ws_rgb_kernel, dim3(grid), dim3(384), 0, rw_s(stream), p);

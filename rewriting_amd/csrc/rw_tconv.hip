@@ -39,12 +39,7 @@
 // horizontally (16 multiply-adds), and the last four filtered rows give an output row (16 more): 9.5 multiply-adds per
 // output where the direct 16-tap form spends 16, and a third of its LDS reads; any other FIR takes the 16-tap form.
 #include "rw_common.h"
-#include <stdlib.h>
 #include <stdio.h>
-typedef float tc_f32x4 __attribute__((ext_vector_type(4)));
-typedef float tc_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 tc_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 tc_f16x8 __attribute__((ext_vector_type(8)));
 
 struct TconvProblem {
   const float* x; const unsigned char* wp; float* y; const float* k4;
@@ -80,30 +75,11 @@ struct TconvProblem {
                           // arithmetic (z written, one row read per output row), 128 = three position blocks per wave only
 #endif
 
-__device__ __forceinline__ int tc_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
-__device__ __forceinline__ int tc_swz(int cc) { return (cc >> 1) & 3; }       // rw_dconv.hip's dc_swz
-__device__ __forceinline__ tc_f16x8 tc_expand(tc_f32x2 w) {
-  const tc_f32x4 d = {w[0], w[1], w[0], w[1]};
-  return __builtin_bit_cast(tc_f16x8, d);
-}
-__device__ __forceinline__ tc_f16x8 tc_pair(tc_f32x2 a, tc_f32x2 b) {
-  const tc_f32x4 d = {a[0], a[1], b[0], b[1]};
-  return __builtin_bit_cast(tc_f16x8, d);
-}
-// [a0 a1 a2 a3 b0 b1 b2 b3]: the Vh parts of two pixel words
-__device__ __forceinline__ tc_f16x8 tc_pair(tc_f16x8 a, tc_f16x8 b) {
-  return tc_f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 // [h0 h1 h2 h3 q0 q1 q2 q3]: a Vh half-word and the Vh part of a pixel word
-__device__ __forceinline__ tc_f16x8 tc_pair_hq(tc_f32x2 h, tc_f16x8 q) {
-  const tc_f32x4 qq = __builtin_bit_cast(tc_f32x4, q);
-  const tc_f32x4 d = {h[0], h[1], qq[0], qq[1]};
-  return __builtin_bit_cast(tc_f16x8, d);
+__device__ __forceinline__ rw_f16x8 tc_pair_hq(rw_f32x2 h, rw_f16x8 q) {
+  const rw_f32x4 qq = __builtin_bit_cast(rw_f32x4, q);
+  const rw_f32x4 d = {h[0], h[1], qq[0], qq[1]};
+  return __builtin_bit_cast(rw_f16x8, d);
 }
 #ifndef TC_PROF
 #define TC_PROF 0         // 1: workgroups 0 and 100 leave cycle counts of wave 0 (multiplying) and wave 4 (staging) in tc_prof
@@ -121,7 +97,6 @@ extern "C" int rw_tconv_prof(unsigned long long* out) {
 #define TP_NOW(t)
 #define TP_ADD(var, t)
 #endif
-template <int N> struct tc_int { static constexpr int value = N; };
 // a * b as ONE v_mul_f32: left to the vectoriser, products of values that sit in different 16-byte load results become
 // v_pk_mul_f32 on register pairs assembled with two v_mov_b32 each
 __device__ __forceinline__ float tc_mul(float a, float b) {
@@ -161,7 +136,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lk = lane >> 4, lt = lane & 15;
 
-  const int local = tc_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int ot = local % p.o_tiles;
   int pg = local / p.o_tiles;
   const int tx = pg % p.tiles_x; pg /= p.tiles_x;
@@ -235,59 +210,59 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     const bool ok = mine && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
     xoff[s] = ok ? (iy * p.w + ix) * 4 : 0x7ffffff0;
     const int cc0 = 4 * j - 2;                                      // window column of pixel 0
-    lofa[s] = (r * TC_WC + cc0) * 64 + ((g ^ tc_swz(cc0 & 0x7ffffffe)) << 4);          // pixels 0, 1 share a swizzle ((cc >> 1) & 3) ...
-    lofb[s] = (r * TC_WC + cc0 + 2) * 64 + ((g ^ tc_swz(cc0 + 2)) << 4);               // ... pixels 2, 3 the next one
+    lofa[s] = (r * TC_WC + cc0) * 64 + ((g ^ rw_swz(cc0 & 0x7ffffffe)) << 4);          // pixels 0, 1 share a swizzle ((cc >> 1) & 3) ...
+    lofb[s] = (r * TC_WC + cc0 + 2) * 64 + ((g ^ rw_swz(cc0 + 2)) << 4);               // ... pixels 2, 3 the next one
     int m = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) m |= (mine && cc0 + e >= 0 && cc0 + e < TC_WC) ? (1 << e) : 0;
     lok[s] = m;
   }
-  tc_f32x4 raw[SI][4];                              // [piece][channel]: four pixels
+  rw_f32x4 raw[SI][4];                              // [piece][channel]: four pixels
   // channels K0 .. K1 - 1 of piece s of chunk c requested
   auto stage_load_part = [&](int c, auto s_tag, auto k0_tag, auto k1_tag) __attribute__((always_inline)) {
     constexpr int s = decltype(s_tag)::value, K0 = decltype(k0_tag)::value, K1 = decltype(k1_tag)::value;
     const int s0 = (16 * c + 4 * g) * hw4;
 #pragma unroll
     for (int k = K0; k < K1; ++k) {
-      if (TC_ABL & 1) raw[s][k] = tc_f32x4{1.f, 1.f, 1.f, 1.f};
-      else raw[s][k] = __builtin_bit_cast(tc_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], s0 + k * hw4, 0));
+      if (TC_ABL & 1) raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
+      else raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], s0 + k * hw4, 0));
     }
   };
   // pixels E0 .. E1 - 1 of piece s converted (style, exact f16 pair split) and written
   auto stage_store_part = [&](int c, int buf, auto s_tag, auto e0_tag, auto e1_tag) __attribute__((always_inline)) {
     constexpr int s = decltype(s_tag)::value, E0 = decltype(e0_tag)::value, E1 = decltype(e1_tag)::value;
-    const tc_f32x4 sv = *reinterpret_cast<const tc_f32x4*>(&St[16 * c + 4 * g]);
+    const rw_f32x4 sv = *reinterpret_cast<const rw_f32x4*>(&St[16 * c + 4 * g]);
     unsigned char* dst = Ls + buf * BUFB;
 #pragma unroll
     for (int e = E0; e < E1; ++e) {
       const float v0 = tc_mul(raw[s][0][e], sv[0]), v1 = tc_mul(raw[s][1][e], sv[1]), v2 = tc_mul(raw[s][2][e], sv[2]),
                   v3 = tc_mul(raw[s][3][e], sv[3]);
-      const tc_f16x2 h01 = __builtin_convertvector(tc_f32x2{v0, v1}, tc_f16x2);
-      const tc_f16x2 h23 = __builtin_convertvector(tc_f32x2{v2, v3}, tc_f16x2);
+      const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+      const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
       float r0, r1, r2, r3;                        // v - (float)h, exact
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
       asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-      const tc_f16x2 l01 = __builtin_convertvector(tc_f32x2{r0, r1}, tc_f16x2);
-      const tc_f16x2 l23 = __builtin_convertvector(tc_f32x2{r2, r3}, tc_f16x2);
-      tc_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+      const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+      const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+      rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
       if (TC_ABL & 256)                            // (timing ablation: no conversion arithmetic; results wrong)
-        word = __builtin_bit_cast(tc_f16x8, tc_f32x4{raw[s][0][e], raw[s][1][e], raw[s][2][e], raw[s][3][e]});
+        word = __builtin_bit_cast(rw_f16x8, rw_f32x4{raw[s][0][e], raw[s][1][e], raw[s][2][e], raw[s][3][e]});
       if (TC_ABL & 512) { asm volatile("" :: "v"(word)); }            // (timing ablation: no LDS store of the window)
-      else if (lok[s] & (1 << e)) *reinterpret_cast<tc_f16x8*>(dst + (e < 2 ? lofa[s] : lofb[s]) + (e & 1) * 64) = word;
+      else if (lok[s] & (1 << e)) *reinterpret_cast<rw_f16x8*>(dst + (e < 2 ? lofa[s] : lofb[s]) + (e & 1) * 64) = word;
     }
   };
   // the chunk's weights of this workgroup's NT out-channel blocks: NT x 9216 contiguous bytes of the packed array -> LDS
   const unsigned char* wsrc = p.wp + (int64_t)(NT * ot) * T * 1024;
   constexpr int NPC = NT * (TC_WCH / 16), NWP = (NPC + THREADS - 1) / THREADS;      // 16-byte pieces, per thread
-  tc_f32x4 wraw[NWP];
+  rw_f32x4 wraw[NWP];
   auto wstage_load = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
     for (int k = 0; k < NWP; ++k) {                 // (no branch around a request: the threads past the end read the last piece again)
       const int pc = tid + k * THREADS < NPC ? tid + k * THREADS : NPC - 1;
       const int n = pc / (TC_WCH / 16), r = pc - n * (TC_WCH / 16);
-      wraw[k] = *reinterpret_cast<const tc_f32x4*>(wsrc + ((int64_t)n * T + 9 * c) * 1024 + r * 16);
+      wraw[k] = *reinterpret_cast<const rw_f32x4*>(wsrc + ((int64_t)n * T + 9 * c) * 1024 + r * 16);
     }
   };
   auto wstage_store = [&](int buf) __attribute__((always_inline)) {
@@ -295,7 +270,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
 #pragma unroll
     for (int k = 0; k < NWP; ++k)
       if ((k + 1) * THREADS <= NPC || tid + k * THREADS < NPC)
-        *reinterpret_cast<tc_f32x4*>(dst + (tid + k * THREADS) * 16) = wraw[k];
+        *reinterpret_cast<rw_f32x4*>(dst + (tid + k * THREADS) * 16) = wraw[k];
   };
 
   // ---- this wave's position blocks: operand addresses of the lane's position q = 16 blk + lt (clamped), pixel offsets
@@ -308,17 +283,17 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     int q = 16 * (wave + WAVES * b) + lt;
     q = q < NPOS ? q : NPOS - 1;
     const int r = q / TC_PC, c = q - r * TC_PC;
-    pb0[b] = (unsigned)((r * TC_WC + c + 1) * 64 + ((lk ^ tc_swz(c + 1)) << 4));
-    pb1[b] = (unsigned)((r * TC_WC + c) * 64 + ((lk ^ tc_swz(c)) << 4));
+    pb0[b] = (unsigned)((r * TC_WC + c + 1) * 64 + ((lk ^ rw_swz(c + 1)) << 4));
+    pb1[b] = (unsigned)((r * TC_WC + c) * 64 + ((lk ^ rw_swz(c)) << 4));
   }
 
-  tc_f32x4 acc[BPW][NT][4];
+  rw_f32x4 acc[BPW][NT][4];
 #pragma unroll
   for (int b = 0; b < BPW; ++b)
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
-      for (int ph = 0; ph < 4; ++ph) acc[b][n][ph] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int ph = 0; ph < 4; ++ph) acc[b][n][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
 
   // One chunk in THREE tap groups, so that at most five weight operands per out-channel block (20 NT registers) are live
   // beside the accumulators: G0 = the taps on x[i][j] alone, G1 = those that also need x[i][j-1], G2 = those on the row above.
@@ -326,14 +301,14 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   // Three piece products (rw_dconv.hip): Vh Uh + Vl Uh by [Vh | Vl] x [Uh | Uh]; the Vh Ul of two taps of one phase share an
   // instruction, [Vh(P) | Vh(Q)] x [Ul(tP) | Ul(tQ)]; tap (1, 1), alone in its phase, keeps all four ([Ul | Ul]).
 #define TB_MFMA(PH, A, B) acc[b][n][PH] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[b][n][PH], 0, 0, 0)
-#define TB_UH(T_) tc_expand(*reinterpret_cast<const tc_f32x2*>(wb + n * TC_WCH + (T_) * 1024))
-#define TB_UL(T_) (*reinterpret_cast<const tc_f32x2*>(wb + n * TC_WCH + (T_) * 1024 + 512))
-#define TC_PIX(OFF) (*reinterpret_cast<const tc_f16x8*>(lb + (OFF)))
-#define TC_VH(OFF) (*reinterpret_cast<const tc_f32x2*>(lb + (OFF)))
+#define TB_UH(T_) rw_expand(*reinterpret_cast<const rw_f32x2*>(wb + n * TC_WCH + (T_) * 1024))
+#define TB_UL(T_) (*reinterpret_cast<const rw_f32x2*>(wb + n * TC_WCH + (T_) * 1024 + 512))
+#define TC_PIX(OFF) (*reinterpret_cast<const rw_f16x8*>(lb + (OFF)))
+#define TC_VH(OFF) (*reinterpret_cast<const rw_f32x2*>(lb + (OFF)))
 // (the persistent kernels below: one out-channel block per workgroup)
 #define TC_MFMA(PH, A, B) acc[b][PH] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[b][PH], 0, 0, 0)
-#define TC_UH(T_) tc_expand(*reinterpret_cast<const tc_f32x2*>(wb + (T_) * 1024))
-#define TC_UL(T_) (*reinterpret_cast<const tc_f32x2*>(wb + (T_) * 1024 + 512))
+#define TC_UH(T_) rw_expand(*reinterpret_cast<const rw_f32x2*>(wb + (T_) * 1024))
+#define TC_UL(T_) (*reinterpret_cast<const rw_f32x2*>(wb + (T_) * 1024 + 512))
   TP_DECL(tp = 0, tp_all = 0, tp_g0 = 0, tp_s0 = 0, tp_g1 = 0, tp_g2 = 0, tp_s1 = 0, tp_bar = 0, tp_pro = 0);
   auto chunk = [&](int c, auto last_tag) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(last_tag)::value != 0;
@@ -356,13 +331,13 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
       if (b < 4) { if (grp == 0) { TP_ADD(tp_g0, tp); } else if (grp == 1) { TP_ADD(tp_g1, tp); } else { TP_ADD(tp_g2, tp); } }
 #endif
       if constexpr (grp < SI) {
-        if (b == 0 && st) stage_store_part(c + 1, buf ^ 1, tc_int<grp>(), tc_int<0>(), tc_int<2>());
-        if (b == 1 && st) stage_store_part(c + 1, buf ^ 1, tc_int<grp>(), tc_int<2>(), tc_int<4>());
+        if (b == 0 && st) stage_store_part(c + 1, buf ^ 1, rw_int<grp>(), rw_int<0>(), rw_int<2>());
+        if (b == 1 && st) stage_store_part(c + 1, buf ^ 1, rw_int<grp>(), rw_int<2>(), rw_int<4>());
         if constexpr (BPW >= 4) {
-          if (b == 2) stage_load_part(c2, tc_int<grp>(), tc_int<0>(), tc_int<2>());
-          if (b == 3) stage_load_part(c2, tc_int<grp>(), tc_int<2>(), tc_int<4>());
+          if (b == 2) stage_load_part(c2, rw_int<grp>(), rw_int<0>(), rw_int<2>());
+          if (b == 3) stage_load_part(c2, rw_int<grp>(), rw_int<2>(), rw_int<4>());
         } else {
-          if (b == 2) stage_load_part(c2, tc_int<grp>(), tc_int<0>(), tc_int<4>());
+          if (b == 2) stage_load_part(c2, rw_int<grp>(), rw_int<0>(), rw_int<4>());
         }
       } else if constexpr (grp == 2) {
         if (b == 0 && st) wstage_store(buf ^ 1);
@@ -377,15 +352,15 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     constexpr int LB = BPW - 1;
     const bool last_ok = wave + WAVES * LB < NBLK;  // wave-uniform
     {
-      tc_f16x8 u0[NT], u1[NT], u3[NT], u4[NT], l4[NT];
+      rw_f16x8 u0[NT], u1[NT], u3[NT], u4[NT], l4[NT];
 #pragma unroll
-      for (int n = 0; n < NT; ++n) { u0[n] = TB_UH(0); u1[n] = TB_UH(1); u3[n] = TB_UH(3); u4[n] = TB_UH(4); l4[n] = tc_expand(TB_UL(4)); }
+      for (int n = 0; n < NT; ++n) { u0[n] = TB_UH(0); u1[n] = TB_UH(1); u3[n] = TB_UH(3); u4[n] = TB_UH(4); l4[n] = rw_expand(TB_UL(4)); }
       // (TC_AHEAD blocks ahead: 1 = round 5; 2 = the pixel operands of block b + 2 requested before block b's MFMAs)
-      tc_f16x8 pc = TC_PIX(pb0[0] + TC_WC * 64), pd = pc;
+      rw_f16x8 pc = TC_PIX(pb0[0] + TC_WC * 64), pd = pc;
       if (TC_AHEAD == 2 && BPW > 1) pd = TC_PIX(pb0[1] + TC_WC * 64);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f16x8 pn = TC_AHEAD == 2 ? pd : pc;
+        rw_f16x8 pn = TC_AHEAD == 2 ? pd : pc;
         if (b + TC_AHEAD < BPW) pn = TC_PIX(pb0[b + TC_AHEAD] + TC_WC * 64);
         if (b < LB || last_ok) {
 #pragma unroll
@@ -397,7 +372,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
             }
           }
         }
-        hook(tc_int<0>(), b);
+        hook(rw_int<0>(), b);
         __builtin_amdgcn_sched_barrier(0);
         if (TC_AHEAD == 2) { pc = pd; pd = pn; } else pc = pn;
       }
@@ -405,19 +380,19 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     TP_ADD(tp_g0, tp);
     __builtin_amdgcn_sched_barrier(0);
     {
-      tc_f16x8 u2[NT], u5[NT], m02[NT], m35[NT];
+      rw_f16x8 u2[NT], u5[NT], m02[NT], m35[NT];
 #pragma unroll
-      for (int n = 0; n < NT; ++n) { u2[n] = TB_UH(2); u5[n] = TB_UH(5); m02[n] = tc_pair(TB_UL(0), TB_UL(2)); m35[n] = tc_pair(TB_UL(3), TB_UL(5)); }
-      tc_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;    // Vh of x[i][j]: the first half of its word
-      tc_f16x8 qc = TC_PIX(pb1[0] + TC_WC * 64), qd = qc;
+      for (int n = 0; n < NT; ++n) { u2[n] = TB_UH(2); u5[n] = TB_UH(5); m02[n] = rw_pair(TB_UL(0), TB_UL(2)); m35[n] = rw_pair(TB_UL(3), TB_UL(5)); }
+      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;    // Vh of x[i][j]: the first half of its word
+      rw_f16x8 qc = TC_PIX(pb1[0] + TC_WC * 64), qd = qc;
       if (TC_AHEAD == 2 && BPW > 1) { hd = TC_VH(pb0[1] + TC_WC * 64); qd = TC_PIX(pb1[1] + TC_WC * 64); }
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
-        tc_f16x8 qn = TC_AHEAD == 2 ? qd : qc;
+        rw_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
+        rw_f16x8 qn = TC_AHEAD == 2 ? qd : qc;
         if (b + TC_AHEAD < BPW) { hn = TC_VH(pb0[b + TC_AHEAD] + TC_WC * 64); qn = TC_PIX(pb1[b + TC_AHEAD] + TC_WC * 64); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M = tc_pair_hq(hc, qc);
+          const rw_f16x8 M = tc_pair_hq(hc, qc);
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
             if (TC_ABL & 2) { asm volatile("" :: "v"(hc), "v"(qc), "v"(u2[n]), "v"(u5[n]), "v"(m02[n]), "v"(m35[n])); }
@@ -427,29 +402,29 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
             }
           }
         }
-        hook(tc_int<1>(), b);
+        hook(rw_int<1>(), b);
         __builtin_amdgcn_sched_barrier(0);
         if (TC_AHEAD == 2) { hc = hd; qc = qd; hd = hn; qd = qn; } else { hc = hn; qc = qn; }
       }
     }
     TP_ADD(tp_g1, tp);
     {
-      tc_f16x8 u6[NT], u7[NT], u8[NT], m17[NT], m68[NT];
+      rw_f16x8 u6[NT], u7[NT], u8[NT], m17[NT], m68[NT];
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         u6[n] = TB_UH(6); u7[n] = TB_UH(7); u8[n] = TB_UH(8);
-        m17[n] = tc_pair(TB_UL(1), TB_UL(7)); m68[n] = tc_pair(TB_UL(6), TB_UL(8));
+        m17[n] = rw_pair(TB_UL(1), TB_UL(7)); m68[n] = rw_pair(TB_UL(6), TB_UL(8));
       }
-      tc_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;
-      tc_f16x8 qc = TC_PIX(pb0[0]), rc = TC_PIX(pb1[0]), qd = qc, rd = rc;
+      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;
+      rw_f16x8 qc = TC_PIX(pb0[0]), rc = TC_PIX(pb1[0]), qd = qc, rd = rc;
       if (TC_AHEAD == 2 && BPW > 1) { hd = TC_VH(pb0[1] + TC_WC * 64); qd = TC_PIX(pb0[1]); rd = TC_PIX(pb1[1]); }
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
-        tc_f16x8 qn = TC_AHEAD == 2 ? qd : qc, rn = TC_AHEAD == 2 ? rd : rc;
+        rw_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
+        rw_f16x8 qn = TC_AHEAD == 2 ? qd : qc, rn = TC_AHEAD == 2 ? rd : rc;
         if (b + TC_AHEAD < BPW) { hn = TC_VH(pb0[b + TC_AHEAD] + TC_WC * 64); qn = TC_PIX(pb0[b + TC_AHEAD]); rn = TC_PIX(pb1[b + TC_AHEAD]); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M02 = tc_pair_hq(hc, qc), M23 = tc_pair(qc, rc);
+          const rw_f16x8 M02 = tc_pair_hq(hc, qc), M23 = rw_pair(qc, rc);
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
             if (TC_ABL & 2) { asm volatile("" :: "v"(hc), "v"(qc), "v"(rc), "v"(u6[n]), "v"(u7[n]), "v"(u8[n]), "v"(m17[n]), "v"(m68[n])); }
@@ -460,7 +435,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
             }
           }
         }
-        hook(tc_int<2>(), b);
+        hook(rw_int<2>(), b);
         __builtin_amdgcn_sched_barrier(0);
         if (TC_AHEAD == 2) { hc = hd; qc = qd; rc = rd; hd = hn; qd = qn; rd = rn; } else { hc = hn; qc = qn; rc = rn; }
       }
@@ -484,19 +459,19 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   wstage_load(0);
 #pragma unroll
   for (int s = 0; s < SI; ++s) {
-    if (s == 0) stage_load_part(0, tc_int<0>(), tc_int<0>(), tc_int<4>());
-    else stage_load_part(0, tc_int<SI - 1>(), tc_int<0>(), tc_int<4>());
+    if (s == 0) stage_load_part(0, rw_int<0>(), rw_int<0>(), rw_int<4>());
+    else stage_load_part(0, rw_int<SI - 1>(), rw_int<0>(), rw_int<4>());
   }
-  stage_store_part(0, 0, tc_int<0>(), tc_int<0>(), tc_int<4>());
-  if constexpr (SI > 1) stage_store_part(0, 0, tc_int<SI - 1>(), tc_int<0>(), tc_int<4>());
+  stage_store_part(0, 0, rw_int<0>(), rw_int<0>(), rw_int<4>());
+  if constexpr (SI > 1) stage_store_part(0, 0, rw_int<SI - 1>(), rw_int<0>(), rw_int<4>());
   wstage_store(0);
   __syncthreads();
   {
     const int c1 = NC > 1 ? 1 : 0;
     __builtin_amdgcn_sched_barrier(0);
-    stage_load_part(c1, tc_int<0>(), tc_int<0>(), tc_int<4>());
+    stage_load_part(c1, rw_int<0>(), rw_int<0>(), rw_int<4>());
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SI > 1) stage_load_part(c1, tc_int<SI - 1>(), tc_int<0>(), tc_int<4>());
+    if constexpr (SI > 1) stage_load_part(c1, rw_int<SI - 1>(), rw_int<0>(), rw_int<4>());
     __builtin_amdgcn_sched_barrier(0);
     wstage_load(c1);
     __builtin_amdgcn_sched_barrier(0);
@@ -505,8 +480,8 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
 #if TC_PROF
   TP_NOW(tp); tp_pro = tp - tp_all;
 #endif
-  for (int c = 0; c + 1 < NC; ++c) chunk(c, tc_int<0>());
-  chunk(NC - 1, tc_int<1>());
+  for (int c = 0; c + 1 < NC; ++c) chunk(c, rw_int<0>());
+  chunk(NC - 1, rw_int<1>());
 #if TC_PROF
   const unsigned long long tp_loop_end = (unsigned long long)clock64();
 #endif
@@ -536,12 +511,12 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   const int strip = tid & 127, seg = tid >> 7;
   const int s_og = strip & 15, s_ch = strip >> 4, s_oy0 = SR * seg;
   const int64_t s_pix = (int64_t)(2 * I0 + s_oy0) * W2 + 2 * J0 + 4 * s_og;
-  tc_f32x4 nzr[SR];
+  rw_f32x4 nzr[SR];
 #pragma unroll
   for (int oy = 0; oy < SR; ++oy) {
-    nzr[oy] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+    nzr[oy] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     if (sep && p.noise && !(TC_ABL & 32))
-      nzr[oy] = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
+      nzr[oy] = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
   }
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
@@ -573,39 +548,39 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
       const int cl = 16 * n + 8 * pass + s_ch;      // channel within the workgroup's OC
       const float sc = Sc[cl], bs = Bs[cl], post = Po[cl];
       float* yb = p.y + ((int64_t)ib * p.out_ch + OC * ot + cl) * hw2 + s_pix;
-      tc_f32x4 hrow[4];                             // the last four horizontally filtered rows
-      tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb), hi = *reinterpret_cast<const tc_f32x4*>(zb + 4);
+      rw_f32x4 hrow[4];                             // the last four horizontally filtered rows
+      rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb), hi = *reinterpret_cast<const rw_f32x4*>(zb + 4);
 #pragma unroll
       for (int zr = 0; zr < SR + 3; ++zr) {
-        tc_f32x4 lon = lo, hin = hi;                // the next z row, requested before this one is filtered
+        rw_f32x4 lon = lo, hin = hi;                // the next z row, requested before this one is filtered
         if (zr + 1 < SR + 3) {
-          lon = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP);
-          hin = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
+          lon = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP);
+          hin = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
         }
-        tc_f32x4 hsum = lo * kf[0];
+        rw_f32x4 hsum = lo * kf[0];
         if (!(TC_ABL & 64)) {
-          hsum += tc_f32x4{lo[1], lo[2], lo[3], hi[0]} * kf[1];
-          hsum += tc_f32x4{lo[2], lo[3], hi[0], hi[1]} * kf[2];
-          hsum += tc_f32x4{lo[3], hi[0], hi[1], hi[2]} * kf[3];
+          hsum += rw_f32x4{lo[1], lo[2], lo[3], hi[0]} * kf[1];
+          hsum += rw_f32x4{lo[2], lo[3], hi[0], hi[1]} * kf[2];
+          hsum += rw_f32x4{lo[3], hi[0], hi[1], hi[2]} * kf[3];
         }
         hrow[zr & 3] = hsum;
         if (zr >= 3) {
           const int oy = zr - 3;                    // output row oy0 + oy: filtered rows zr - 3 .. zr
-          tc_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
+          rw_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
           if (!(TC_ABL & 64)) {
             res += hrow[(zr - 2) & 3] * kv[1];
             res += hrow[(zr - 1) & 3] * kv[2];
             res += hrow[zr & 3] * kv[3];
           }
-          const tc_f32x4 nz = nzr[oy] * noise_wg;
-          tc_f32x4 v;
+          const rw_f32x4 nz = nzr[oy] * noise_wg;
+          rw_f32x4 v;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float u = res[q] * sc + nz[q] + bs;
             v[q] = fmaxf(u, u * slope) * post;
             ymax = fmaxf(ymax, fabsf(v[q]));
           }
-          if (!(TC_ABL & 16)) *reinterpret_cast<tc_f32x4*>(yb + (int64_t)oy * W2) = v;
+          if (!(TC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(yb + (int64_t)oy * W2) = v;
         }
         __builtin_amdgcn_sched_barrier(0);
         lo = lon; hi = hin;
@@ -619,8 +594,8 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         float res[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-          const tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP);
-          const tc_f32x4 hi = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP + 4);
+          const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP);
+          const rw_f32x4 hi = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP + 4);
           const float rowv[7] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2]};
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -629,17 +604,17 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         }
         const int cl = 16 * n + 8 * pass + ch;
         const int64_t pix = (int64_t)(2 * I0 + oy) * W2 + 2 * J0 + 4 * og;
-        tc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-        if (p.noise) nz = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
+        rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
         const float sc = Sc[cl], bs = Bs[cl], post = Po[cl];
-        tc_f32x4 v;
+        rw_f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float u = res[q] * sc + nz[q] + bs;
           v[q] = fmaxf(u, u * slope) * post;
           ymax = fmaxf(ymax, fabsf(v[q]));
         }
-        *reinterpret_cast<tc_f32x4*>(p.y + ((int64_t)ib * p.out_ch + OC * ot + cl) * hw2 + pix) = v;
+        *reinterpret_cast<rw_f32x4*>(p.y + ((int64_t)ib * p.out_ch + OC * ot + cl) * hw2 + pix) = v;
       }
     }
     __syncthreads();
@@ -716,7 +691,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
 
   // this workgroup's run: tile k * grid + bx (ot fastest, then x, y, image); those running at the same time are neighbours
   const int64_t total = (int64_t)p.batch * p.tiles_y * p.tiles_x * p.o_tiles;
-  const int bx = tc_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int count = (int)((total - bx + gridDim.x - 1) / gridDim.x);
   if (count <= 0) {                                 // (every wave of the launch owns a slot of the bound: rw_common.h)
     if (p.y_amax) rw_bound_store_wave(p.y_amax, 0.f);
@@ -763,9 +738,9 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
   const int64_t hw2 = 4 * hw;
   const int strip = tid & 127, seg = tid >> 7;
   const int s_og = strip & 15, s_ch = strip >> 4, s_oy0 = SR * seg;
-  tc_f32x4 nzr[SR];
+  rw_f32x4 nzr[SR];
 #pragma unroll
-  for (int oy = 0; oy < SR; ++oy) nzr[oy] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int oy = 0; oy < SR; ++oy) nzr[oy] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;
   // is the FIR an outer product kv x kh?  (tconv_body; kh, kv and the answer live in LDS: every register counts beside the
   // multiplying waves' accumulators and operands.)  Thread 0 decides, before the first barrier.
@@ -789,7 +764,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       const int64_t s_pix = (int64_t)(2 * ty * TY + s_oy0) * W2 + 2 * tx * TC_TX + 4 * s_og;
 #pragma unroll
       for (int oy = 0; oy < SR; ++oy)
-        nzr[oy] = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
+        nzr[oy] = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
     }
   };
   auto blur = [&](int pass, int par, int ot, int tx, int ty, int ib) __attribute__((always_inline)) {
@@ -800,35 +775,35 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       const float* zb = Zs + s_ch * CHS + (s_oy0 + 1) * TC_ZP + 4 * s_og + 4;
       const float sc = Sc[par][cl], bs = Bs[par][cl], post = Po[par][cl];
       float* yb = p.y + ((int64_t)ib * p.out_ch + 16 * ot + cl) * hw2 + s_pix;
-      tc_f32x4 hrow[4];                             // the last four horizontally filtered rows
-      tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb), hi = *reinterpret_cast<const tc_f32x4*>(zb + 4);
+      rw_f32x4 hrow[4];                             // the last four horizontally filtered rows
+      rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb), hi = *reinterpret_cast<const rw_f32x4*>(zb + 4);
 #pragma unroll
       for (int zr = 0; zr < SR + 3; ++zr) {
-        tc_f32x4 lon = lo, hin = hi;                // the next z row, requested before this one is filtered
+        rw_f32x4 lon = lo, hin = hi;                // the next z row, requested before this one is filtered
         if (zr + 1 < SR + 3) {
-          lon = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP);
-          hin = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
+          lon = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP);
+          hin = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
         }
-        tc_f32x4 hsum = tc_f32x4{lo[1], lo[2], lo[3], hi[0]} * kh[0];
-        hsum += tc_f32x4{lo[2], lo[3], hi[0], hi[1]} * kh[1];
-        hsum += tc_f32x4{lo[3], hi[0], hi[1], hi[2]} * kh[2];
+        rw_f32x4 hsum = rw_f32x4{lo[1], lo[2], lo[3], hi[0]} * kh[0];
+        hsum += rw_f32x4{lo[2], lo[3], hi[0], hi[1]} * kh[1];
+        hsum += rw_f32x4{lo[3], hi[0], hi[1], hi[2]} * kh[2];
         hsum += hi * kh[3];
         hrow[zr & 3] = hsum;
         if (zr >= 3) {
           const int oy = zr - 3;                    // output row oy0 + oy: filtered rows zr - 3 .. zr
-          tc_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
+          rw_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
           res += hrow[(zr - 2) & 3] * kv[1];
           res += hrow[(zr - 1) & 3] * kv[2];
           res += hrow[zr & 3] * kv[3];
-          const tc_f32x4 nz = nzr[oy] * noise_wg;
-          tc_f32x4 v;
+          const rw_f32x4 nz = nzr[oy] * noise_wg;
+          rw_f32x4 v;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float u = res[q] * sc + nz[q] + bs;
             v[q] = fmaxf(u, u * slope) * post;
             ymax = fmaxf(ymax, fabsf(v[q]));
           }
-          *reinterpret_cast<tc_f32x4*>(yb + (int64_t)oy * W2) = v;
+          *reinterpret_cast<rw_f32x4*>(yb + (int64_t)oy * W2) = v;
         }
         __builtin_amdgcn_sched_barrier(0);
         lo = lon; hi = hin;
@@ -842,8 +817,8 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
         float res[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-          const tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP);
-          const tc_f32x4 hi = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP + 4);
+          const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP);
+          const rw_f32x4 hi = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP + 4);
           const float rowv[7] = {lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -852,17 +827,17 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
         }
         const int cg = 8 * pass + ch;
         const int64_t pix = (int64_t)(2 * ty * TY + oy) * W2 + 2 * tx * TC_TX + 4 * og;
-        tc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-        if (p.noise) nz = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
+        rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
         const float sc = Sc[par][cg], bs = Bs[par][cg], post = Po[par][cg];
-        tc_f32x4 v;
+        rw_f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float u = res[q] * sc + nz[q] + bs;
           v[q] = fmaxf(u, u * slope) * post;
           ymax = fmaxf(ymax, fabsf(v[q]));
         }
-        *reinterpret_cast<tc_f32x4*>(p.y + ((int64_t)ib * p.out_ch + 16 * ot + cg) * hw2 + pix) = v;
+        *reinterpret_cast<rw_f32x4*>(p.y + ((int64_t)ib * p.out_ch + 16 * ot + cg) * hw2 + pix) = v;
       }
     }
   };
@@ -885,7 +860,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     // scalars): chunk n + 3 is requested when chunk n + 1 has been written -- two intervals between a request and its use
     // (one left layer 17 waiting: 1.3 of 6.5 ms disappeared with the window loads, profiles/r05u)
     struct Flight {
-      tc_f32x4 raw[SI][4];                          // [piece][channel]: four pixels
+      rw_f32x4 raw[SI][4];                          // [piece][channel]: four pixels
       float psv[4];
       float demod, bias, post, oscale, iscale;
       bool first;
@@ -894,7 +869,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     Flight fl[2];
     // (the weights come from the L2 and stay ONE interval ahead: tap pieces g, g + 4 and (g == 0) 8 of the chunk after the
     // one being written; w_next = where the chunk requested last finds its weights)
-    tc_f32x4 wraw[3];
+    rw_f32x4 wraw[3];
     float sv[4];
     int l_s0 = 0;
     const unsigned char* l_wsrc = p.wp;
@@ -952,14 +927,14 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       // (the weights FIRST, all with piece 0: loads return in order -- the wait for them, an interval later, must not reach
       // past this interval's window requests)
       if (with_w && s == 0) {
-        wraw[0] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + g * 1024);
-        wraw[1] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + (g + 4) * 1024);
-        if (g == 0) wraw[2] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + 8 * 1024);
+        wraw[0] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + g * 1024);
+        wraw[1] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + (g + 4) * 1024);
+        if (g == 0) wraw[2] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + 8 * 1024);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (TC_ABL & 1) F.raw[s][k] = tc_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
-        else F.raw[s][k] = __builtin_bit_cast(tc_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
+        if (TC_ABL & 1) F.raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
+        else F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
       }
     };
     // what setup() requested beside the pixels -> registers / LDS (the first wait of an interval)
@@ -978,9 +953,9 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       unsigned char* dst = Ls + buf * BUFB;
       unsigned char* wdst = Wl + buf * TC_WCH + lane * 16;
       if (s == 0) {
-        *reinterpret_cast<tc_f32x4*>(wdst + g * 1024) = wraw[0];
-        *reinterpret_cast<tc_f32x4*>(wdst + (g + 4) * 1024) = wraw[1];
-        if (g == 0) *reinterpret_cast<tc_f32x4*>(wdst + 8 * 1024) = wraw[2];
+        *reinterpret_cast<rw_f32x4*>(wdst + g * 1024) = wraw[0];
+        *reinterpret_cast<rw_f32x4*>(wdst + (g + 4) * 1024) = wraw[1];
+        if (g == 0) *reinterpret_cast<rw_f32x4*>(wdst + 8 * 1024) = wraw[2];
       }
       const int it = 64 * s + lane;
       const int r = it / IPR, j = it - r * IPR;
@@ -988,36 +963,36 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       for (int e = 0; e < 4; ++e) {
         const float v0 = F.raw[s][0][e] * sv[0], v1 = F.raw[s][1][e] * sv[1], v2 = F.raw[s][2][e] * sv[2],
                     v3 = F.raw[s][3][e] * sv[3];
-        const tc_f16x2 h01 = __builtin_convertvector(tc_f32x2{v0, v1}, tc_f16x2);
-        const tc_f16x2 h23 = __builtin_convertvector(tc_f32x2{v2, v3}, tc_f16x2);
+        const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+        const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
         float r0, r1, r2, r3;                        // v - (float)h, exact
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-        const tc_f16x2 l01 = __builtin_convertvector(tc_f32x2{r0, r1}, tc_f16x2);
-        const tc_f16x2 l23 = __builtin_convertvector(tc_f32x2{r2, r3}, tc_f16x2);
-        const tc_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+        const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+        const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+        const rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
         const int cc = 4 * j - 2 + e;                // window column of this pixel
         if (it < NITEM && cc >= 0 && cc < TC_WC)
-          *reinterpret_cast<tc_f16x8*>(dst + (r * TC_WC + cc) * 64 + ((g ^ tc_swz(cc)) << 4)) = word;
+          *reinterpret_cast<rw_f16x8*>(dst + (r * TC_WC + cc) * 64 + ((g ^ rw_swz(cc)) << 4)) = word;
       }
     };
 
     // chunks 0 and 1 requested (chunk 0's weights with chunk 1's window); chunk 0 written; chunk 2 requested
-    setup(tc_int<0>());
+    setup(rw_int<0>());
 #pragma unroll
-    for (int s = 0; s < SI; ++s) request_s(tc_int<0>(), s, false);
-    setup(tc_int<1>());
+    for (int s = 0; s < SI; ++s) request_s(rw_int<0>(), s, false);
+    setup(rw_int<1>());
 #pragma unroll
-    for (int s = 0; s < SI; ++s) request_s(tc_int<1>(), s);
-    tables(tc_int<0>());
+    for (int s = 0; s < SI; ++s) request_s(rw_int<1>(), s);
+    tables(rw_int<0>());
     __builtin_amdgcn_sched_barrier(0);
-    setup(tc_int<0>());
+    setup(rw_int<0>());
 #pragma unroll
     for (int s = 0; s < SI; ++s) {
-      deliver_s(tc_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
-      request_s(tc_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
+      deliver_s(rw_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
+      request_s(rw_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
     }
     lds_barrier();
     int cn = 0, e_pos = 0;                          // the tile the multiplying waves are on (its epilogue is shared)
@@ -1061,8 +1036,8 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       }
     };
     int n = 0;
-    for (; n + 1 < N; n += 2) { interval(n, tc_int<1>()); interval(n + 1, tc_int<0>()); }
-    if (n < N) interval(n, tc_int<1>());
+    for (; n + 1 < N; n += 2) { interval(n, rw_int<1>()); interval(n + 1, rw_int<0>()); }
+    if (n < N) interval(n, rw_int<1>());
 #if TC_PROF
     if (wave == MW && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
       unsigned long long* o = tc_prof + (blockIdx.x == 0 ? 0 : 32);
@@ -1082,14 +1057,14 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     int q = 16 * (wave + MW * b) + lt;
     q = q < NPOS ? q : NPOS - 1;
     const int r = q / TC_PC, c = q - r * TC_PC;
-    pb0[b] = (unsigned)(((r + 1) * TC_WC + c + 1) * 64 + ((lk ^ tc_swz(c + 1)) << 4));
-    pb1[b] = (unsigned)(((r + 1) * TC_WC + c) * 64 + ((lk ^ tc_swz(c)) << 4));
+    pb0[b] = (unsigned)(((r + 1) * TC_WC + c + 1) * 64 + ((lk ^ rw_swz(c + 1)) << 4));
+    pb1[b] = (unsigned)(((r + 1) * TC_WC + c) * 64 + ((lk ^ rw_swz(c)) << 4));
   }
-  tc_f32x4 acc[BPW][4];
+  rw_f32x4 acc[BPW][4];
 #pragma unroll
   for (int b = 0; b < BPW; ++b)
 #pragma unroll
-    for (int ph = 0; ph < 4; ++ph) acc[b][ph] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int LB = BPW - 1;
   const bool last_ok = wave + MW * LB < NBLK;       // wave-uniform: only the last block of a wave can be missing
   // One chunk: the three tap groups of tconv_body's chunk() (at most five weight operands live), the pixel operands of a
@@ -1099,11 +1074,11 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
   // registers more than there are.)
   auto mma = [&](const unsigned char* lb, const unsigned char* wb) __attribute__((always_inline)) {
     {
-      const tc_f16x8 u0 = TC_UH(0), u1 = TC_UH(1), u3 = TC_UH(3), u4 = TC_UH(4), l4 = tc_expand(TC_UL(4));
-      tc_f16x8 pc = TC_PIX(pb0[0]), pd = TC_PIX(pb0[1]);
+      const rw_f16x8 u0 = TC_UH(0), u1 = TC_UH(1), u3 = TC_UH(3), u4 = TC_UH(4), l4 = rw_expand(TC_UL(4));
+      rw_f16x8 pc = TC_PIX(pb0[0]), pd = TC_PIX(pb0[1]);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f16x8 pn = pd;
+        rw_f16x8 pn = pd;
         if (b + 2 < BPW) pn = TC_PIX(pb0[b + 2]);
         if (b < LB || last_ok) {
           TC_MFMA(3, pc, u4); TC_MFMA(0, pc, u0); TC_MFMA(1, pc, u1); TC_MFMA(2, pc, u3);
@@ -1114,16 +1089,16 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       }
     }
     {
-      const tc_f16x8 u2 = TC_UH(2), u5 = TC_UH(5), m02 = tc_pair(TC_UL(0), TC_UL(2)), m35 = tc_pair(TC_UL(3), TC_UL(5));
-      tc_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
-      tc_f16x8 qc = TC_PIX(pb1[0]), qd = TC_PIX(pb1[1]);
+      const rw_f16x8 u2 = TC_UH(2), u5 = TC_UH(5), m02 = rw_pair(TC_UL(0), TC_UL(2)), m35 = rw_pair(TC_UL(3), TC_UL(5));
+      rw_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
+      rw_f16x8 qc = TC_PIX(pb1[0]), qd = TC_PIX(pb1[1]);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = hd;
-        tc_f16x8 qn = qd;
+        rw_f32x2 hn = hd;
+        rw_f16x8 qn = qd;
         if (b + 2 < BPW) { hn = TC_VH(pb0[b + 2]); qn = TC_PIX(pb1[b + 2]); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M = tc_pair_hq(hc, qc);
+          const rw_f16x8 M = tc_pair_hq(hc, qc);
           TC_MFMA(0, qc, u2); TC_MFMA(2, qc, u5);
           TC_MFMA(0, M, m02); TC_MFMA(2, M, m35);
         }
@@ -1132,18 +1107,18 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       }
     }
     {
-      const tc_f16x8 u6 = TC_UH(6), u7 = TC_UH(7), u8 = TC_UH(8), m17 = tc_pair(TC_UL(1), TC_UL(7)),
-                     m68 = tc_pair(TC_UL(6), TC_UL(8));
-      tc_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
-      tc_f16x8 qc = TC_PIX(pb0[0] - TC_WC * 64), rc = TC_PIX(pb1[0] - TC_WC * 64);
-      tc_f16x8 qd = TC_PIX(pb0[1] - TC_WC * 64), rd = TC_PIX(pb1[1] - TC_WC * 64);
+      const rw_f16x8 u6 = TC_UH(6), u7 = TC_UH(7), u8 = TC_UH(8), m17 = rw_pair(TC_UL(1), TC_UL(7)),
+                     m68 = rw_pair(TC_UL(6), TC_UL(8));
+      rw_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
+      rw_f16x8 qc = TC_PIX(pb0[0] - TC_WC * 64), rc = TC_PIX(pb1[0] - TC_WC * 64);
+      rw_f16x8 qd = TC_PIX(pb0[1] - TC_WC * 64), rd = TC_PIX(pb1[1] - TC_WC * 64);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = hd;
-        tc_f16x8 qn = qd, rn = rd;
+        rw_f32x2 hn = hd;
+        rw_f16x8 qn = qd, rn = rd;
         if (b + 2 < BPW) { hn = TC_VH(pb0[b + 2]); qn = TC_PIX(pb0[b + 2] - TC_WC * 64); rn = TC_PIX(pb1[b + 2] - TC_WC * 64); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M02 = tc_pair_hq(hc, qc), M23 = tc_pair(qc, rc);
+          const rw_f16x8 M02 = tc_pair_hq(hc, qc), M23 = rw_pair(qc, rc);
           TC_MFMA(0, qc, u6); TC_MFMA(1, qc, u7);
           TC_MFMA(0, rc, u8); TC_MFMA(1, M02, m17);
           TC_MFMA(0, M23, m68);
@@ -1216,7 +1191,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
 #pragma unroll
     for (int b = 0; b < BPW; ++b)
 #pragma unroll
-      for (int ph = 0; ph < 4; ++ph) acc[b][ph] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     ++pos;
     advance(ot, tx, ty, ib);
   }
@@ -1267,7 +1242,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
   const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
 
   const int64_t total = (int64_t)p.batch * p.tiles_y * p.tiles_x * p.o_tiles;
-  const int bx = tc_xcd_remap(blockIdx.x, gridDim.x);
+  const int bx = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int count = (int)((total - bx + gridDim.x - 1) / gridDim.x);
   if (count <= 0) {                                 // (every wave of the launch owns a slot of the bound: rw_common.h)
     if (p.y_amax) rw_bound_store_wave(p.y_amax, 0.f);
@@ -1324,16 +1299,16 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
   const int W2 = 2 * p.w;
   const int64_t hw2 = 4 * hw;
   const int s_og = lane & 15, s_chl = lane >> 4, s_oy0 = SR * bw;
-  tc_f32x4 nzr[SR];
+  rw_f32x4 nzr[SR];
 #pragma unroll
-  for (int oy = 0; oy < SR; ++oy) nzr[oy] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int oy = 0; oy < SR; ++oy) nzr[oy] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;
   auto noise_request = [&](int ty, int tx, int ib) __attribute__((always_inline)) {
     if (p.noise) {
       const int64_t s_pix = (int64_t)(2 * ty * TY + s_oy0) * W2 + 2 * tx * TC_TX + 4 * s_og;
 #pragma unroll
       for (int oy = 0; oy < SR; ++oy)
-        nzr[oy] = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
+        nzr[oy] = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
     }
   };
   auto blur = [&](int pass, int par, int ot, int tx, int ty, int ib) __attribute__((always_inline)) {
@@ -1344,35 +1319,35 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       const float* zb = Zs + cl * CHS + (s_oy0 + 1) * TC_ZP + 4 * s_og + 4;
       const float sc = Sc[par][cl], bs = Bs[par][cl], post = Po[par][cl];
       float* yb = p.y + ((int64_t)ib * p.out_ch + 16 * ot + cl) * hw2 + s_pix;
-      tc_f32x4 hrow[4];                           // the last four horizontally filtered rows
-      tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb), hi = *reinterpret_cast<const tc_f32x4*>(zb + 4);
+      rw_f32x4 hrow[4];                           // the last four horizontally filtered rows
+      rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb), hi = *reinterpret_cast<const rw_f32x4*>(zb + 4);
 #pragma unroll
       for (int zr = 0; zr < SR + 3; ++zr) {
-        tc_f32x4 lon = lo, hin = hi;              // the next z row, requested before this one is filtered
+        rw_f32x4 lon = lo, hin = hi;              // the next z row, requested before this one is filtered
         if (zr + 1 < SR + 3) {
-          lon = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP);
-          hin = *reinterpret_cast<const tc_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
+          lon = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP);
+          hin = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
         }
-        tc_f32x4 hsum = tc_f32x4{lo[1], lo[2], lo[3], hi[0]} * kh[0];
-        hsum += tc_f32x4{lo[2], lo[3], hi[0], hi[1]} * kh[1];
-        hsum += tc_f32x4{lo[3], hi[0], hi[1], hi[2]} * kh[2];
+        rw_f32x4 hsum = rw_f32x4{lo[1], lo[2], lo[3], hi[0]} * kh[0];
+        hsum += rw_f32x4{lo[2], lo[3], hi[0], hi[1]} * kh[1];
+        hsum += rw_f32x4{lo[3], hi[0], hi[1], hi[2]} * kh[2];
         hsum += hi * kh[3];
         hrow[zr & 3] = hsum;
         if (zr >= 3) {
           const int oy = zr - 3;                  // output row oy0 + oy: filtered rows zr - 3 .. zr
-          tc_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
+          rw_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
           res += hrow[(zr - 2) & 3] * kv[1];
           res += hrow[(zr - 1) & 3] * kv[2];
           res += hrow[zr & 3] * kv[3];
-          const tc_f32x4 nz = nzr[oy] * noise_wg;
-          tc_f32x4 v;
+          const rw_f32x4 nz = nzr[oy] * noise_wg;
+          rw_f32x4 v;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float u = res[q] * sc + nz[q] + bs;
             v[q] = fmaxf(u, u * slope) * post;
             ymax = fmaxf(ymax, fabsf(v[q]));
           }
-          *reinterpret_cast<tc_f32x4*>(yb + (int64_t)oy * W2) = v;
+          *reinterpret_cast<rw_f32x4*>(yb + (int64_t)oy * W2) = v;
         }
         __builtin_amdgcn_sched_barrier(0);
         lo = lon; hi = hin;
@@ -1387,8 +1362,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         float res[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-          const tc_f32x4 lo = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP);
-          const tc_f32x4 hi = *reinterpret_cast<const tc_f32x4*>(zb + a * TC_ZP + 4);
+          const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP);
+          const rw_f32x4 hi = *reinterpret_cast<const rw_f32x4*>(zb + a * TC_ZP + 4);
           const float rowv[7] = {lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -1396,17 +1371,17 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
             for (int cc = 0; cc < 4; ++cc) res[q] += rowv[q + cc] * Kf[a * 4 + cc];
         }
         const int64_t pix = (int64_t)(2 * ty * TY + oy) * W2 + 2 * tx * TC_TX + 4 * og;
-        tc_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
-        if (p.noise) nz = *reinterpret_cast<const tc_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
+        rw_f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if (p.noise) nz = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + pix) * noise_wg;
         const float sc = Sc[par][cg], bs = Bs[par][cg], post = Po[par][cg];
-        tc_f32x4 v;
+        rw_f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float u = res[q] * sc + nz[q] + bs;
           v[q] = fmaxf(u, u * slope) * post;
           ymax = fmaxf(ymax, fabsf(v[q]));
         }
-        *reinterpret_cast<tc_f32x4*>(p.y + ((int64_t)ib * p.out_ch + 16 * ot + cg) * hw2 + pix) = v;
+        *reinterpret_cast<rw_f32x4*>(p.y + ((int64_t)ib * p.out_ch + 16 * ot + cg) * hw2 + pix) = v;
       }
     }
   };
@@ -1433,19 +1408,19 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int cc = 4 * j - 2 + e;               // window column of this pixel
-        ldst[s][e] = (it < NITEM && cc >= 0 && cc < TC_WC) ? (r * TC_WC + cc) * 64 + ((g ^ tc_swz(cc)) << 4) : -1;
+        ldst[s][e] = (it < NITEM && cc >= 0 && cc < TC_WC) ? (r * TC_WC + cc) * 64 + ((g ^ rw_swz(cc)) << 4) : -1;
       }
     }
     __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0, 0x00020000);
     struct Flight {
-      tc_f32x4 raw[SI][4];                          // [piece][channel]: four pixels
+      rw_f32x4 raw[SI][4];                          // [piece][channel]: four pixels
       float psv[4];
       float demod, bias, post, oscale, iscale;
       bool first;
       int par;
     };
     Flight fl[2];
-    tc_f32x4 wraw[3];
+    rw_f32x4 wraw[3];
     float sv[4];
     int l_s0 = 0;
     const unsigned char* l_wsrc = p.wp;
@@ -1501,14 +1476,14 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     auto request_s = [&](auto tag, int s, bool with_w = true) __attribute__((always_inline)) {
       Flight& F = fl[decltype(tag)::value];
       if (with_w && s == 0) {                       // the weights FIRST (loads return in order)
-        wraw[0] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + g * 1024);
-        wraw[1] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + (g + 4) * 1024);
-        if (g == 0) wraw[2] = *reinterpret_cast<const tc_f32x4*>(l_wsrc + 8 * 1024);
+        wraw[0] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + g * 1024);
+        wraw[1] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + (g + 4) * 1024);
+        if (g == 0) wraw[2] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + 8 * 1024);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (TC_ABL & 1) F.raw[s][k] = tc_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
-        else F.raw[s][k] = __builtin_bit_cast(tc_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
+        if (TC_ABL & 1) F.raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
+        else F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
       }
     };
     auto tables = [&](auto tag) __attribute__((always_inline)) {
@@ -1526,45 +1501,45 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       unsigned char* dst = Ls + buf * BUFB;
       unsigned char* wdst = Wl + buf * TC_WCH + lane * 16;
       if (s == 0) {
-        *reinterpret_cast<tc_f32x4*>(wdst + g * 1024) = wraw[0];
-        *reinterpret_cast<tc_f32x4*>(wdst + (g + 4) * 1024) = wraw[1];
-        if (g == 0) *reinterpret_cast<tc_f32x4*>(wdst + 8 * 1024) = wraw[2];
+        *reinterpret_cast<rw_f32x4*>(wdst + g * 1024) = wraw[0];
+        *reinterpret_cast<rw_f32x4*>(wdst + (g + 4) * 1024) = wraw[1];
+        if (g == 0) *reinterpret_cast<rw_f32x4*>(wdst + 8 * 1024) = wraw[2];
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float v0 = F.raw[s][0][e] * sv[0], v1 = F.raw[s][1][e] * sv[1], v2 = F.raw[s][2][e] * sv[2],
                     v3 = F.raw[s][3][e] * sv[3];
-        const tc_f16x2 h01 = __builtin_convertvector(tc_f32x2{v0, v1}, tc_f16x2);
-        const tc_f16x2 h23 = __builtin_convertvector(tc_f32x2{v2, v3}, tc_f16x2);
+        const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+        const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
         float r0, r1, r2, r3;                        // v - (float)h, exact
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-        const tc_f16x2 l01 = __builtin_convertvector(tc_f32x2{r0, r1}, tc_f16x2);
-        const tc_f16x2 l23 = __builtin_convertvector(tc_f32x2{r2, r3}, tc_f16x2);
-        tc_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+        const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+        const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+        rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
         if (TC_ABL & 256)                            // (timing ablation: no conversion arithmetic; results wrong)
-          word = __builtin_bit_cast(tc_f16x8, tc_f32x4{F.raw[s][0][e], F.raw[s][1][e], F.raw[s][2][e], F.raw[s][3][e]});
-        if (!(TC_ABL & 512) && ldst[s][e] >= 0) *reinterpret_cast<tc_f16x8*>(dst + ldst[s][e]) = word;
+          word = __builtin_bit_cast(rw_f16x8, rw_f32x4{F.raw[s][0][e], F.raw[s][1][e], F.raw[s][2][e], F.raw[s][3][e]});
+        if (!(TC_ABL & 512) && ldst[s][e] >= 0) *reinterpret_cast<rw_f16x8*>(dst + ldst[s][e]) = word;
         if (TC_ABL & 512) asm volatile("" :: "v"(word));
       }
     };
 
     // chunks 0 and 1 requested (chunk 0's weights with chunk 1's window); chunk 0 written; chunk 2 requested
-    setup(tc_int<0>());
+    setup(rw_int<0>());
 #pragma unroll
-    for (int s = 0; s < SI; ++s) request_s(tc_int<0>(), s, false);
-    setup(tc_int<1>());
+    for (int s = 0; s < SI; ++s) request_s(rw_int<0>(), s, false);
+    setup(rw_int<1>());
 #pragma unroll
-    for (int s = 0; s < SI; ++s) request_s(tc_int<1>(), s);
-    tables(tc_int<0>());
+    for (int s = 0; s < SI; ++s) request_s(rw_int<1>(), s);
+    tables(rw_int<0>());
     __builtin_amdgcn_sched_barrier(0);
-    setup(tc_int<0>());
+    setup(rw_int<0>());
 #pragma unroll
     for (int s = 0; s < SI; ++s) {
-      deliver_s(tc_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
-      request_s(tc_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
+      deliver_s(rw_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
+      request_s(rw_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
     }
     lds_barrier();
     int cn = 0, e_pos = 0;                          // the tile the multiplying waves are on
@@ -1609,8 +1584,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       }
     };
     int n = 0;
-    for (; n + 1 < N; n += 2) { interval(n, tc_int<1>()); interval(n + 1, tc_int<0>()); }
-    if (n < N) interval(n, tc_int<1>());
+    for (; n + 1 < N; n += 2) { interval(n, rw_int<1>()); interval(n + 1, rw_int<0>()); }
+    if (n < N) interval(n, rw_int<1>());
     // the last tile's blur: nobody waits for it
 #pragma unroll 1
     for (int ps = TC_PP_MQ; ps < 4; ++ps) blur(ps, b_par, b_ot, b_tx, b_ty, b_ib);
@@ -1633,23 +1608,23 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     int q = 16 * (wave + MW * b) + lt;
     q = q < NPOS ? q : NPOS - 1;
     const int r = q / TC_PC, c = q - r * TC_PC;
-    pb0[b] = (unsigned)(((r + 1) * TC_WC + c + 1) * 64 + ((lk ^ tc_swz(c + 1)) << 4));
-    pb1[b] = (unsigned)(((r + 1) * TC_WC + c) * 64 + ((lk ^ tc_swz(c)) << 4));
+    pb0[b] = (unsigned)(((r + 1) * TC_WC + c + 1) * 64 + ((lk ^ rw_swz(c + 1)) << 4));
+    pb1[b] = (unsigned)(((r + 1) * TC_WC + c) * 64 + ((lk ^ rw_swz(c)) << 4));
   }
-  tc_f32x4 acc[BPW][4];
+  rw_f32x4 acc[BPW][4];
 #pragma unroll
   for (int b = 0; b < BPW; ++b)
 #pragma unroll
-    for (int ph = 0; ph < 4; ++ph) acc[b][ph] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int LB = BPW - 1;
   const bool last_ok = wave + MW * LB < NBLK;       // wave-uniform: only the last block of a wave can be missing
   auto mma = [&](const unsigned char* lb, const unsigned char* wb) __attribute__((always_inline)) {
     {
-      const tc_f16x8 u0 = TC_UH(0), u1 = TC_UH(1), u3 = TC_UH(3), u4 = TC_UH(4), l4 = tc_expand(TC_UL(4));
-      tc_f16x8 pc = TC_PIX(pb0[0]), pd = TC_PIX(pb0[1]);
+      const rw_f16x8 u0 = TC_UH(0), u1 = TC_UH(1), u3 = TC_UH(3), u4 = TC_UH(4), l4 = rw_expand(TC_UL(4));
+      rw_f16x8 pc = TC_PIX(pb0[0]), pd = TC_PIX(pb0[1]);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f16x8 pn = pd;
+        rw_f16x8 pn = pd;
         if (b + 2 < BPW) pn = TC_PIX(pb0[b + 2]);
         if (b < LB || last_ok) {
           TC_MFMA(3, pc, u4); TC_MFMA(0, pc, u0); TC_MFMA(1, pc, u1); TC_MFMA(2, pc, u3);
@@ -1660,16 +1635,16 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       }
     }
     {
-      const tc_f16x8 u2 = TC_UH(2), u5 = TC_UH(5), m02 = tc_pair(TC_UL(0), TC_UL(2)), m35 = tc_pair(TC_UL(3), TC_UL(5));
-      tc_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
-      tc_f16x8 qc = TC_PIX(pb1[0]), qd = TC_PIX(pb1[1]);
+      const rw_f16x8 u2 = TC_UH(2), u5 = TC_UH(5), m02 = rw_pair(TC_UL(0), TC_UL(2)), m35 = rw_pair(TC_UL(3), TC_UL(5));
+      rw_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
+      rw_f16x8 qc = TC_PIX(pb1[0]), qd = TC_PIX(pb1[1]);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = hd;
-        tc_f16x8 qn = qd;
+        rw_f32x2 hn = hd;
+        rw_f16x8 qn = qd;
         if (b + 2 < BPW) { hn = TC_VH(pb0[b + 2]); qn = TC_PIX(pb1[b + 2]); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M = tc_pair_hq(hc, qc);
+          const rw_f16x8 M = tc_pair_hq(hc, qc);
           TC_MFMA(0, qc, u2); TC_MFMA(2, qc, u5);
           TC_MFMA(0, M, m02); TC_MFMA(2, M, m35);
         }
@@ -1678,18 +1653,18 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       }
     }
     {
-      const tc_f16x8 u6 = TC_UH(6), u7 = TC_UH(7), u8 = TC_UH(8), m17 = tc_pair(TC_UL(1), TC_UL(7)),
-                     m68 = tc_pair(TC_UL(6), TC_UL(8));
-      tc_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
-      tc_f16x8 qc = TC_PIX(pb0[0] - TC_WC * 64), rc = TC_PIX(pb1[0] - TC_WC * 64);
-      tc_f16x8 qd = TC_PIX(pb0[1] - TC_WC * 64), rd = TC_PIX(pb1[1] - TC_WC * 64);
+      const rw_f16x8 u6 = TC_UH(6), u7 = TC_UH(7), u8 = TC_UH(8), m17 = rw_pair(TC_UL(1), TC_UL(7)),
+                     m68 = rw_pair(TC_UL(6), TC_UL(8));
+      rw_f32x2 hc = TC_VH(pb0[0]), hd = TC_VH(pb0[1]);
+      rw_f16x8 qc = TC_PIX(pb0[0] - TC_WC * 64), rc = TC_PIX(pb1[0] - TC_WC * 64);
+      rw_f16x8 qd = TC_PIX(pb0[1] - TC_WC * 64), rd = TC_PIX(pb1[1] - TC_WC * 64);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        tc_f32x2 hn = hd;
-        tc_f16x8 qn = qd, rn = rd;
+        rw_f32x2 hn = hd;
+        rw_f16x8 qn = qd, rn = rd;
         if (b + 2 < BPW) { hn = TC_VH(pb0[b + 2]); qn = TC_PIX(pb0[b + 2] - TC_WC * 64); rn = TC_PIX(pb1[b + 2] - TC_WC * 64); }
         if (b < LB || last_ok) {
-          const tc_f16x8 M02 = tc_pair_hq(hc, qc), M23 = tc_pair(qc, rc);
+          const rw_f16x8 M02 = tc_pair_hq(hc, qc), M23 = rw_pair(qc, rc);
           TC_MFMA(0, qc, u6); TC_MFMA(1, qc, u7);
           TC_MFMA(0, rc, u8); TC_MFMA(1, M02, m17);
           TC_MFMA(0, M23, m68);
@@ -1752,7 +1727,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
 #pragma unroll
     for (int b = 0; b < BPW; ++b)
 #pragma unroll
-      for (int ph = 0; ph < 4; ++ph) acc[b][ph] = tc_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #if TC_PROF
   if (wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
@@ -1774,45 +1749,39 @@ extern "C" int rw_tconv_blur_f32(const float* x, const float* wp, const float* k
                                  const float* post_scale, float u_inv, const float* x_amax, float* y_amax,
                                  rw_stream_t stream) {
   RW_CHECK_ARG(x && wp && k4 && y && x_amax && u_inv > 0.f && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (!tconv_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   if ((int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return RW_ERR_UNSUPPORTED;
   TconvProblem p = {};
   p.x = x; p.wp = reinterpret_cast<const unsigned char*>(wp); p.y = y; p.k4 = k4;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
+  rw_fill_epilogue(p, ep);
   p.post = post_scale;
   p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w; p.w_scale = w_scale; p.u_inv = u_inv;
   p.x_amax = x_amax; p.y_amax = y_amax;
   // the form: RW_TCONV_TY = 0 the specialised persistent kernel, 8 / 16 the two shapes of tconv_body; unset: by input channels -- the persistent kernel where a tile has few chunks (<= 128
   // channels: its staging waves run ahead through the epilogue), the one-workgroup-per-CU shape where the MFMAs dominate
   // (profiles/r05q: layer 17 6.4 against 7.1 ms, layer 15 4.6 / 4.9, layer 13 3.7 / 3.7, layer 11 3.3 / 3.2, layer 9 1.9 / 1.7)
-  const char* e = getenv("RW_TCONV_TY");
   // (RW_TCONV_PERSISTENT = 0 / 2: which of the two persistent kernels the automatic choice means)
-  const char* pe = getenv("RW_TCONV_PERSISTENT");
+  const int persistent = rw_env_int("RW_TCONV_PERSISTENT", 0) == 2 ? 2 : 0;
   // (RW_TCONV_N32 = "lo:hi": the input-channel range the automatic choice gives to the 32-out-channel form.  Default: none --
   // stand-alone it ties the persistent form on layer 15 (4.2 against 4.3 ms), inside the forward the persistent form is ahead:
   // 1526 - 1528 against 1507 - 1518 img/s, same box, interleaved, profiles/r06ak)
   int n32_lo = 1, n32_hi = 0;
   if (const char* ne = getenv("RW_TCONV_N32")) { if (sscanf(ne, "%d:%d", &n32_lo, &n32_hi) != 2) { n32_lo = 1; n32_hi = 0; } }
-  const int sel = e ? atoi(e)
-                    : (out_ch % 32 == 0 && in_ch >= n32_lo && in_ch <= n32_hi ? 32
-                       : (in_ch >= 32 && in_ch <= 128 ? (pe && atoi(pe) == 2 ? 2 : 0) : 16));
+  const int sel = rw_env_int("RW_TCONV_TY", out_ch % 32 == 0 && in_ch >= n32_lo && in_ch <= n32_hi ? 32
+                                           : (in_ch >= 32 && in_ch <= 128 ? persistent : 16));
   if ((sel == 0 || sel == 2 || sel == 12) && in_ch >= 32) {      // 0: the specialised persistent kernel (one workgroup of eight waves per CU); 2: its pipelined form; 12: twelve waves
     p.tiles_x = w / TC_TX; p.tiles_y = h / 8; p.o_tiles = out_ch / 16;
     const int64_t tiles = (int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles;
     if (tiles <= 0 || tiles > 0x7fffffff) return RW_ERR_UNSUPPORTED;
-    const char* ge = getenv("RW_TCONV_GRID");
-    int64_t grid = ge ? atoi(ge) : rw_cu_count();       // one persistent workgroup per compute unit
+    int64_t grid = rw_env_int("RW_TCONV_GRID", rw_cu_count());      // one persistent workgroup per compute unit
     grid = grid < 1 ? 1 : (grid > tiles ? tiles : grid);
     const int wv = sel == 12 ? 12 : 8;
     if (y_amax && wv * grid > rw_bound_slot_capacity((int64_t)batch * out_ch * 4 * h * w)) return RW_ERR_UNSUPPORTED;
     if (sel == 2) hipLaunchKernelGGL(tconv_blur_pp_kernel, dim3((unsigned)grid), dim3(512), 0, rw_s(stream), p);
     else if (sel == 12) hipLaunchKernelGGL(tconv_blur_ws12_kernel, dim3((unsigned)grid), dim3(768), 0, rw_s(stream), p);
     else hipLaunchKernelGGL(tconv_blur_ws_kernel, dim3((unsigned)grid), dim3(512), 0, rw_s(stream), p);
-    const int rc = RW_LAUNCH_RESULT();
-    if (rc || !y_amax) return rc;
-    return rw_bound_finish(y_amax, wv * grid, rw_s(stream));
+    return rw_finish_bound(y_amax, wv * grid, stream);
   }
   const bool n32 = sel == 32 && out_ch % 32 == 0;   // 32 out-channels per workgroup (8 x 32 tile, eight waves)
   const int ty = sel == 16 ? 16 : 8;
@@ -1824,7 +1793,5 @@ extern "C" int rw_tconv_blur_f32(const float* x, const float* wp, const float* k
   if (n32) hipLaunchKernelGGL(tconv_blur_n32_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
   else if (ty == 16) hipLaunchKernelGGL(tconv_blur_t16_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
   else hipLaunchKernelGGL(tconv_blur_t8_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  const int rc = RW_LAUNCH_RESULT();
-  if (rc || !y_amax) return rc;
-  return rw_bound_finish(y_amax, waves * work, rw_s(stream));
+  return rw_finish_bound(y_amax, waves * work, stream);
 }

@@ -42,14 +42,6 @@
 // caller's x_amax, eU at pack time (trailer, as in rw_wino4.hip).  Packed weights: the 25 points carry 16 distinct values
 // (9 of phase (0,0), 3 + 3 of the mixed phases, 1 of phase (1,1)): uf[o / 16][i / 8][wi = 0..15][lane][{0: Uh pair,
 // 1: Ul pair}] -- 16 KB per interval and workgroup where the fp32 packing streams 28.
-#include <stdlib.h>
-typedef float uw_f32x4 __attribute__((ext_vector_type(4)));
-typedef float uw_f32x2 __attribute__((ext_vector_type(2)));
-typedef int uw_i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uw_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned uw_u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 uw_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 uw_f16x8 __attribute__((ext_vector_type(8)));
 
 struct UpWinoProblem {
   const float* x; const float* uf; float* y;
@@ -69,21 +61,6 @@ struct UpWinoProblem {
 #define UW_NTS 0          // non-temporal stores of the (2H+1)^2 map (A/B builds)
 #endif
 #define UW_PITCH 36             // row pitch of a patch channel in LDS: 33 columns + 3
-
-__device__ __forceinline__ int uw_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
-__device__ __forceinline__ void uw_dma_buffer_b32(unsigned lds_addr, int voffset, uw_i32x4 rsrc, int soffset) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
-}
-__device__ __forceinline__ void uw_dma_global_b128_s(unsigned lds_addr, int voffset, const void* sbase) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_addr), "v"(voffset), "s"(sbase)
-               : "memory");
-}
 
 // NRW = 16: input maps 16 pixels wide (layer 7 of the generators: 16^2 -> 33^2, a fifth of a key-statistics sweep at
 // layer 8): a wave's 16 blocks are then TWO block rows of 8 -- block lt sits at block row 2 wn + (lt >> 3), column
@@ -119,7 +96,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
   const int wm = wave >> 1, wn = wave & 1;        // out-channel half / block row
   const int lk = lane >> 4, lt = lane & 15;       // channel of the k-quad / block column
 
-  const int local = uw_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int o_tiles = p.out_ch / 32;
   const int runs_x = p.groups_x / p.gpw;
   const int ot = local % o_tiles;
@@ -171,7 +148,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
   typedef __attribute__((address_space(3))) float* lds_f;
   const unsigned ps_base = (unsigned)(size_t)(lds_f)Ps, us_base = (unsigned)(size_t)(lds_f)Us;
   const unsigned long long xaddr = (unsigned long long)xb;
-  const uw_i32x4 xsrc = {(int)(unsigned)xaddr, (int)(unsigned)(xaddr >> 32), (int)((int64_t)nimg * p.in_ch * hw * 4),
+  const rw_i32x4 xsrc = {(int)(unsigned)xaddr, (int)(unsigned)(xaddr >> 32), (int)((int64_t)nimg * p.in_ch * hw * 4),
                          0x00020000};
   const int hw4 = (int)hw * 4;
   // patch pieces of this wave: channels 2 wave, 2 wave + 1 of the interval, three pieces each.  Patch row r = input
@@ -199,7 +176,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
   // piece s = 0 .. 2 UW_PIECES - 1: channel 2 wave + s / UW_PIECES, piece s % UW_PIECES
   auto pload_piece = [&](int s) __attribute__((always_inline)) {
     if (UW_ABL & 2) return;
-    uw_dma_buffer_b32(p_dst + 256 * s, xoff[s % UW_PIECES], xsrc, p_soff + (s / UW_PIECES) * hw4);
+    rw_dma_buffer_b32(p_dst + 256 * s, xoff[s % UW_PIECES], xsrc, p_soff + (s / UW_PIECES) * hw4);
   };
   // weights of an interval: 28 one-KB pieces [half 2][k-quad 2][7]; wave w copies pieces 7 w .. 7 w + 6
   const int kq_total = p.in_ch >> 2;
@@ -211,19 +188,19 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       const float* src = p.uf + ((int64_t)((o0 >> 4) + (wave >> 1)) * (p.in_ch >> 3) + fc) * (16 * 128) + (wave & 1) * 1024;
       const unsigned dst = us_base + (unsigned)((slot * USZ + wave * 1024) * 4);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) uw_dma_global_b128_s(dst + q * 1024, a_lane * 4, src + q * 256);
+      for (int q = 0; q < 4; ++q) rw_dma_global_b128_s(dst + q * 1024, a_lane * 4, src + q * 256);
       return;
     }
     const int hf = wave >> 1, kql = wave & 1;
     const float* src = p.uf + ((int64_t)((o0 >> 4) + hf) * kq_total + 2 * fc + kql) * (7 * 256);       // uniform
     const unsigned dst = us_base + (unsigned)((slot * USZ + (hf * 2 + kql) * (7 * 256)) * 4);
 #pragma unroll
-    for (int q = 0; q < 7; ++q) uw_dma_global_b128_s(dst + q * 1024, a_lane * 4, src + q * 256);
+    for (int q = 0; q < 7; ++q) rw_dma_global_b128_s(dst + q * 1024, a_lane * 4, src + q * 256);
   };
 
-  uw_f32x4 acc[25];
+  rw_f32x4 acc[25];
 #pragma unroll
-  for (int xi = 0; xi < 25; ++xi) acc[xi] = uw_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int xi = 0; xi < 25; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
 
   // this lane's window: patch rows 2 wn .. 2 wn + 2, columns 2 lt .. 2 lt + 2 of channel lk (+ 4 per k-quad)
   const int item_off = lk * (UW_PIECES * 64) + (IPW > 1 ? img_l * ISTRIDE : 0) + (2 * b_row) * PITCH + 2 * b_col;
@@ -235,7 +212,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       float d[3][3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const uw_f32x2 lo = *reinterpret_cast<const uw_f32x2*>(src + r * PITCH);
+        const rw_f32x2 lo = *reinterpret_cast<const rw_f32x2*>(src + r * PITCH);
         d[r][0] = lo[0] * sv; d[r][1] = lo[1] * sv; d[r][2] = src[r * PITCH + 2] * sv;
       }
       // T[v][h]: v, h in (d0-d1, d1, d2-d1, d2)
@@ -250,12 +227,12 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
         T[v][0] = t[v][0] - t[v][1]; T[v][1] = t[v][1]; T[v][2] = t[v][2] - t[v][1]; T[v][3] = t[v][2];
       }
       const float* ub = &Us[uslot * USZ + (wm * 2 + kql) * (7 * 256) + a_lane];
-      uw_f32x4 a4[3];
-      a4[0] = *reinterpret_cast<const uw_f32x4*>(ub);
-      a4[1] = *reinterpret_cast<const uw_f32x4*>(ub + 256);
+      rw_f32x4 a4[3];
+      a4[0] = *reinterpret_cast<const rw_f32x4*>(ub);
+      a4[1] = *reinterpret_cast<const rw_f32x4*>(ub + 256);
 #pragma unroll
       for (int q = 0; q < 7; ++q) {
-        if (q + 2 < 7) a4[(q + 2) % 3] = *reinterpret_cast<const uw_f32x4*>(ub + (q + 2) * 256);
+        if (q + 2 < 7) a4[(q + 2) % 3] = *reinterpret_cast<const rw_f32x4*>(ub + (q + 2) * 256);
         if (spread && q < UW_PIECES) pload_piece(UW_PIECES * kql + q);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -282,7 +259,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       float d[3][3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const uw_f32x2 lo = *reinterpret_cast<const uw_f32x2*>(src + r * PITCH);
+        const rw_f32x2 lo = *reinterpret_cast<const rw_f32x2*>(src + r * PITCH);
         d[r][0] = lo[0] * sv; d[r][1] = lo[1] * sv; d[r][2] = src[r * PITCH + 2] * sv;
       }
       float t[4][3];
@@ -296,22 +273,22 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       }
     }
     // the 16 operand quads (Th pair, Th pair, Tl pair, Tl pair)
-    uw_f16x8 B[4][4];
+    rw_f16x8 B[4][4];
 #pragma unroll
     for (int v = 0; v < 4; ++v)
 #pragma unroll
       for (int hc = 0; hc < 4; ++hc) {
         const float t0 = T[0][v][hc], t1 = T[1][v][hc];
         if (UW_ABL & 16) {
-          const uw_f16x2 h0 = __builtin_bit_cast(uw_f16x2, t0), h1 = __builtin_bit_cast(uw_f16x2, t1);
-          B[v][hc] = uw_f16x8{h0[0], h0[1], h1[0], h1[1], h0[0], h0[1], h1[0], h1[1]};
+          const rw_f16x2 h0 = __builtin_bit_cast(rw_f16x2, t0), h1 = __builtin_bit_cast(rw_f16x2, t1);
+          B[v][hc] = rw_f16x8{h0[0], h0[1], h1[0], h1[1], h0[0], h0[1], h1[0], h1[1]};
         } else {
-          const uw_f16x2 hh = __builtin_convertvector(uw_f32x2{t0, t1}, uw_f16x2);
+          const rw_f16x2 hh = __builtin_convertvector(rw_f32x2{t0, t1}, rw_f16x2);
           float r0, r1;
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hh), "v"(t0));
           asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hh), "v"(t1));
-          const uw_f16x2 ll = __builtin_convertvector(uw_f32x2{r0, r1}, uw_f16x2);
-          B[v][hc] = uw_f16x8{hh[0], hh[1], hh[0], hh[1], ll[0], ll[1], ll[0], ll[1]};
+          const rw_f16x2 ll = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+          B[v][hc] = rw_f16x8{hh[0], hh[1], hh[0], hh[1], ll[0], ll[1], ll[0], ll[1]};
         }
       }
     // weights: the 25 points carry 16 distinct values (E x O, O x E and O x O repeat theirs), (Uh pair, Ul pair) of
@@ -322,23 +299,23 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
     // address twice"), four values per batch, one batch ahead.  The compiler takes an asm's outputs for ready: the
     // operands reach the MFMAs only through the asm that waits (scripts/check_asm_loads.py checks the assembly).
     const unsigned ua = us_base + (unsigned)((uslot * USZ + wm * (16 * 128) + 2 * lane) * 4);
-    uw_u32x4 aq[2][4];
-    auto aload = [&](int wi, uw_u32x4& dst) __attribute__((always_inline)) {
+    rw_u32x4 aq[2][4];
+    auto aload = [&](int wi, rw_u32x4& dst) __attribute__((always_inline)) {
       // offsets of ds_read2_b64 count 8-byte units and stop at 255: one base per four values
-      if (UW_ABL & 64) { dst = uw_u32x4{ua, (unsigned)wi, ua, 1u}; return; }
+      if (UW_ABL & 64) { dst = rw_u32x4{ua, (unsigned)wi, ua, 1u}; return; }
       asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%2" : "=&v"(dst) : "v"(ua + (wi >> 2) * 2048), "n"((wi & 3) * 64));
     };
-    auto point = [&](int xi, const uw_u32x4& a) __attribute__((always_inline)) {
+    auto point = [&](int xi, const rw_u32x4& a) __attribute__((always_inline)) {
       const int vr = xi < 9 ? xi / 3 : (xi < 15 ? (xi - 9) / 2 : (xi < 21 ? 1 + 2 * ((xi - 15) / 3) : 1 + 2 * ((xi - 21) / 2)));
       const int hc = xi < 9 ? xi % 3 : (xi < 15 ? 1 + 2 * ((xi - 9) % 2) : (xi < 21 ? (xi - 15) % 3 : 1 + 2 * ((xi - 21) % 2)));
       if (UW_ABL & 32) asm volatile("" :: "v"(a), "v"(B[vr][hc]));
-      else acc[xi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(uw_f16x8, a), B[vr][hc], acc[xi], 0, 0, 0);
+      else acc[xi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rw_f16x8, a), B[vr][hc], acc[xi], 0, 0, 0);
     };
 #pragma unroll
     for (int e = 0; e < 4; ++e) aload(e, aq[0][e]);
 #pragma unroll
     for (int bt = 0; bt < 4; ++bt) {
-      uw_u32x4 (&cur)[4] = aq[bt & 1];
+      rw_u32x4 (&cur)[4] = aq[bt & 1];
       if (bt < 3) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) aload(4 * (bt + 1) + e, aq[(bt + 1) & 1][e]);
@@ -414,7 +391,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       }
     }
 #pragma unroll
-    for (int xi = 0; xi < 25; ++xi) acc[xi] = uw_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int xi = 0; xi < 25; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
 #define UW_WAIT(n) __builtin_amdgcn_s_waitcnt(((n) & 15) | (((n) >> 4) << 14) | 0x70)
@@ -502,7 +479,7 @@ __global__ void __launch_bounds__(256) pack_up_wino_kernel(const float* __restri
     float* dst = uf + ((int64_t)ob * kqn + kq) * (7 * 256) + lane * 4;
 #pragma unroll
     for (int q = 0; q < 7; ++q)
-      *reinterpret_cast<uw_f32x4*>(dst + q * 256) = uw_f32x4{u[4 * q], u[4 * q + 1], u[4 * q + 2], u[4 * q + 3]};
+      *reinterpret_cast<rw_f32x4*>(dst + q * 256) = rw_f32x4{u[4 * q], u[4 * q + 1], u[4 * q + 2], u[4 * q + 3]};
   }
 }
 
@@ -536,8 +513,8 @@ __global__ void __launch_bounds__(256) pack_up_winoh_kernel(const float* __restr
         const int xi = wi < 9 ? wi : (wi < 12 ? 9 + 2 * (wi - 9) : (wi < 15 ? 15 + (wi - 12) : 21));    // a point that carries it
         const float a = u0[xi] * su, b = u1[xi] * su;
         const _Float16 ah = (_Float16)a, bh = (_Float16)b;
-        *reinterpret_cast<uw_u32x2*>(dst + wi * 128) =
-            uw_u32x2{uw_f16_bits(a) | (uw_f16_bits(b) << 16), uw_f16_bits(a - (float)ah) | (uw_f16_bits(b - (float)bh) << 16)};
+        *reinterpret_cast<rw_u32x2*>(dst + wi * 128) =
+            rw_u32x2{uw_f16_bits(a) | (uw_f16_bits(b) << 16), uw_f16_bits(a - (float)ah) | (uw_f16_bits(b - (float)bh) << 16)};
       }
     }
   }
@@ -594,17 +571,8 @@ static int up_wino_launch(const float* x, const float* uf, float* y, int batch, 
   const int ipw = whole ? (w == 8 ? 2 : 8) : 1;        // images per workgroup
   const int wg_batch = (batch + ipw - 1) / ipw;
   const int o_tiles = out_ch / 32;
-  const char* e = getenv("RW_UPWINO_GPW");
-  int gpw = e ? atoi(e) : 4;
-  if (gpw < 1) gpw = 1;
-  if (gpw > p.groups_x) gpw = p.groups_x;
-  while (p.groups_x % gpw) --gpw;
-  while (gpw > 1 && (int64_t)wg_batch * p.groups_y * (p.groups_x / gpw) * o_tiles < 1024) {
-    --gpw;
-    while (p.groups_x % gpw) --gpw;
-  }
-  p.gpw = gpw;
-  const int64_t work = (int64_t)wg_batch * p.groups_y * (p.groups_x / gpw) * o_tiles;
+  p.gpw = rw_groups_per_wg(p.groups_x, (int64_t)wg_batch * p.groups_y * o_tiles, rw_env_int("RW_UPWINO_GPW", 4), 1024);
+  const int64_t work = (int64_t)wg_batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
   if (h16) hipLaunchKernelGGL(conv_up_winoh_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
   else if (whole && w == 8) hipLaunchKernelGGL(conv_up_wino_8x8_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
@@ -638,9 +606,7 @@ extern "C" int rw_conv_transpose_weight_winoh_absmax_f32(const float* w, int out
   const int grid = rw_stream_grid(total, 256);
   hipLaunchKernelGGL(pack_up_winoh_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, (float*)nullptr, out_ch, in_ch, 1.f,
                      bound);
-  const int rc = RW_LAUNCH_RESULT();
-  if (rc) return rc;
-  return rw_bound_finish(bound, grid, rw_s(stream));
+  return rw_finish_bound(bound, grid, stream);
 }
 
 extern "C" int rw_pack_conv_transpose_winoh_f32(const float* w, float* uf, int out_ch, int in_ch, float u_scale,

@@ -37,15 +37,6 @@ struct WinoProblem {
   float rgb_scale;
 };
 
-__device__ __forceinline__ int wn_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
-
-template <int N> struct wn_int { static constexpr int value = N; };
-
 // ---------------------------------------------------------------------------------------
 // The GEMMs run on v_mfma_f32_16x16x4_f32 (32 cycles per instruction, 64 FLOP/clk/SIMD: the rate of 32x32x2).  A
 // 16 x 16 accumulator tile is 4 registers, so ONE wave holds all sixteen transform points of 32 out-channels x 16
@@ -72,8 +63,6 @@ template <int N> struct wn_int { static constexpr int value = N; };
 //   weights: uf[o/32][i/4][xi/4][(o%32)/16][lane][xi%4], o = 32 (o/32) + 16 ((o%32)/16) + (lane & 15),
 //            i = 4 (i/4) + (lane >> 4)                                     (rw_pack_conv_weight_wino_f32)
 // ---------------------------------------------------------------------------------------
-typedef float wn_f32x4 __attribute__((ext_vector_type(4)));
-
 // NRW = 16: maps 16 pixels wide (the 16^2 layers: most of a key-statistics sweep at layer 8): a wave's "tile row" of 16
 // tiles is then TWO map tile rows of 8 tiles -- tile lt sits at map tile row 2 wn + (lt >> 3), column lt & 7 -- the
 // raw patch is (4 WGN + 2) rows x 18 columns, one group spans the map's width (groups_x = gpw = 1); everything else
@@ -123,7 +112,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
   const int wm = wave / WGN, wn = wave % WGN;
   const int lk = lane >> 4, lt = lane & 15;        // k within the quad / tile column (A: out-channel row)
 
-  const int local = wn_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int o_tiles = p.out_ch / (32 * WGM);
   const int runs_x = p.groups_x / p.gpw;
   const int ot = local % o_tiles;
@@ -273,23 +262,23 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
   const int kq_total = p.in_ch >> 2;
   const float* ufs = p.uf + ((int64_t)((o0 >> 5) + wm) * kq_total) * 2048;     // uniform; + kq * 2048
   const int a_lane = lane * 4;
-  wn_f32x4 areg[4][2];                              // [xi / 4][16-channel half] over xi % 4
+  rw_f32x4 areg[4][2];                              // [xi / 4][16-channel half] over xi % 4
   float breg[16];
   auto aload = [&](int xq, int kq) __attribute__((always_inline)) {
     const float* base = ufs + (int64_t)kq * 2048 + xq * 512;
-    areg[xq][0] = *reinterpret_cast<const wn_f32x4*>(base + a_lane);
-    areg[xq][1] = *reinterpret_cast<const wn_f32x4*>(base + 256 + a_lane);
+    areg[xq][0] = *reinterpret_cast<const rw_f32x4*>(base + a_lane);
+    areg[xq][1] = *reinterpret_cast<const rw_f32x4*>(base + 256 + a_lane);
   };
   const float* vsrc = &Vs[0][0][lk][wn * 16 + lt];
   auto bload = [&](int buf, int kq, int xi) __attribute__((always_inline)) {
     breg[xi] = vsrc[buf * 16 * IC * VP + xi * IC * VP + 4 * kq * VP];
   };
 
-  wn_f32x4 acc[16][2];
+  rw_f32x4 acc[16][2];
 #pragma unroll
   for (int xi = 0; xi < 16; ++xi)
 #pragma unroll
-    for (int h = 0; h < 2; ++h) acc[xi][h] = wn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int h = 0; h < 2; ++h) acc[xi][h] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- prologue: V[0] = chunk 0, Rs[1] = chunk 1, registers = chunk 2; operands of the first k-quad
   set_group(0);
@@ -389,16 +378,16 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
       if (yb) {
         const float g0 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(odd ? v[0] : v[2]), 0xB1, 0xf, 0xf, true));
         const float g1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(odd ? v[1] : v[3]), 0xB1, 0xf, 0xf, true));
-        wn_f32x4 o4;
+        rw_f32x4 o4;
         o4[0] = odd ? g0 : v[0]; o4[1] = odd ? g1 : v[1];
         o4[2] = odd ? v[2] : g0; o4[3] = odd ? v[3] : g1;
-        *reinterpret_cast<wn_f32x4*>(yb + (int64_t)(16 * half + j) * hw) = o4;
+        *reinterpret_cast<rw_f32x4*>(yb + (int64_t)(16 * half + j) * hw) = o4;
       }
     }
 #pragma unroll
     for (int xi = 0; xi < 16; ++xi)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) acc[xi][h] = wn_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int h = 0; h < 2; ++h) acc[xi][h] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     if (RGB) {
       // the four 16-lane groups of the wave hold the other out-channels of the same pixels
 #pragma unroll
@@ -485,9 +474,9 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
     if (++fc == NC) { fc = 0; ++fg; }
     ++v;
   };
-  for (; v + 2 < VT;) step(wn_int<2>());
-  if (v + 1 < VT) step(wn_int<1>());
-  step(wn_int<0>());
+  for (; v + 2 < VT;) step(rw_int<2>());
+  if (v + 1 < VT) step(rw_int<1>());
+  step(rw_int<0>());
 }
 
 __global__ void __launch_bounds__(256) pack_wino16_kernel(const float* __restrict__ w, float* __restrict__ uf,
@@ -515,8 +504,8 @@ __global__ void __launch_bounds__(256) pack_wino16_kernel(const float* __restric
     float* dst = uf + ((int64_t)ob * kqn + kq) * 2048 + half * 256 + lane * 4;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
-      *reinterpret_cast<wn_f32x4*>(dst + a * 512) =
-          wn_f32x4{gg[a][0], 0.5f * (gg[a][0] + gg[a][1] + gg[a][2]), 0.5f * (gg[a][0] - gg[a][1] + gg[a][2]), gg[a][2]};
+      *reinterpret_cast<rw_f32x4*>(dst + a * 512) =
+          rw_f32x4{gg[a][0], 0.5f * (gg[a][0] + gg[a][1] + gg[a][2]), 0.5f * (gg[a][0] - gg[a][1] + gg[a][2]), gg[a][2]};
   }
 }
 
@@ -537,9 +526,6 @@ extern "C" long long rw_packed_conv_weight_wino_elems(int out_ch, int in_ch) {
   return 16LL * out_ch * in_ch;
 }
 
-#include <stdlib.h>
-static int wn_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 extern "C" int rw_pack_conv_weight_wino_f32(const float* w, float* uf, int out_ch, int in_ch, rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0);
   if (out_ch % 32 || in_ch % 4) return RW_ERR_UNSUPPORTED;
@@ -555,7 +541,7 @@ static int launch_wino(WinoProblem& p, bool rgb, hipStream_t s) {
   // (<4,1>: 128 out-channels x 1 tile row halves the staging per MFMA but gives each of the four waves its own weight
   // stream: measured 195-222 vs 240 TFLOP/s effective -- the weight stream binds first; kept selectable for tuning)
   int bm = p.out_ch % 64 == 0 ? 64 : 32;
-  const int force = wn_env("RW_WINO_TILE", 0);
+  const int force = rw_env_int("RW_WINO_TILE", 0);
   if (force && p.out_ch % force == 0 && (force == 32 || force == 64 || force == 128)) bm = force;
   const bool narrow = wino_narrow(p.h, p.w), whole = wino_whole(p.h, p.w);
   if ((narrow || whole) && bm == 128) bm = 64;    // NRW exists for the <2,2> and <1,4> shapes
@@ -567,17 +553,9 @@ static int launch_wino(WinoProblem& p, bool rgb, hipStream_t s) {
   const int ipw = whole ? (p.w == 8 ? wgn : 4 * wgn) : 1;        // images per workgroup
   const int wg_batch = (p.batch + ipw - 1) / ipw;
   const int o_tiles = p.out_ch / bm;
-  int gpw = wn_env("RW_WINO_GPW", 8);
-  if (gpw < 1) gpw = 1;
-  if (gpw > p.groups_x) gpw = p.groups_x;
-  while (p.groups_x % gpw) --gpw;
   // short launches: keep at least ~4 workgroups per CU
-  while (gpw > 1 && (int64_t)wg_batch * p.groups_y * (p.groups_x / gpw) * o_tiles < 1024) {
-    --gpw;
-    while (p.groups_x % gpw) --gpw;
-  }
-  p.gpw = gpw;
-  const int64_t work = (int64_t)wg_batch * p.groups_y * (p.groups_x / gpw) * o_tiles;
+  p.gpw = rw_groups_per_wg(p.groups_x, (int64_t)wg_batch * p.groups_y * o_tiles, rw_env_int("RW_WINO_GPW", 8), 1024);
+  const int64_t work = (int64_t)wg_batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)work), block(256);
   if (rgb && bm != 32) return RW_ERR_UNSUPPORTED;
@@ -595,34 +573,30 @@ static int launch_wino(WinoProblem& p, bool rgb, hipStream_t s) {
 }
 
 static void wino_fill(WinoProblem& p, const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch,
-                      int h, int w, float w_scale, const rw_conv_epilogue* ep) {
+                      int h, int w, float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb) {
   p.x = x; p.uf = uf; p.y = y;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
+  rw_fill_epilogue(p, ep);
   p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w; p.w_scale = w_scale;
-  p.rgb_weight = nullptr; p.rgb_style = nullptr; p.rgb_bias = nullptr; p.rgb_skip = nullptr; p.rgb_out = nullptr;
-  p.rgb_scale = 0.f;
+  rw_fill_rgb(p, rgb);
 }
 
 extern "C" int rw_conv3x3_wino_f32(const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch, int h,
                                    int w, float w_scale, const rw_conv_epilogue* ep, rw_stream_t stream) {
   RW_CHECK_ARG(x && uf && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (!wino_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   WinoProblem p;
-  wino_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep);
+  wino_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep, nullptr);
   return launch_wino(p, false, rw_s(stream));
 }
 
 extern "C" int rw_conv3x3_wino_to_rgb_f32(const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch,
                                           int h, int w, float w_scale, const rw_conv_epilogue* ep,
                                           const rw_rgb_epilogue* rgb, rw_stream_t stream) {
-  RW_CHECK_ARG(x && uf && rgb && rgb->weight && rgb->style && rgb->out && batch > 0 && in_ch > 0 && out_ch > 0);
-  RW_CHECK_ARG(h > 0 && w > 0 && (!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias))));
+  RW_CHECK_ARG(x && uf && rw_rgb_ok(rgb) && batch > 0 && in_ch > 0 && out_ch > 0);
+  RW_CHECK_ARG(h > 0 && w > 0 && rw_epilogue_ok(ep));
   if (out_ch != 32 || !wino_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;   // one wave pair holds all channels
   WinoProblem p;
-  wino_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep);
-  p.rgb_weight = rgb->weight; p.rgb_style = rgb->style; p.rgb_bias = rgb->bias; p.rgb_skip = rgb->skip;
-  p.rgb_out = rgb->out; p.rgb_scale = rgb->scale;
+  wino_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep, rgb);
   return launch_wino(p, true, rw_s(stream));
 }

@@ -31,7 +31,6 @@
 // per interval.  Weights: uf[o / 16][i / 4][xi / 4][lane = 16 (i % 4) + o % 16][xi % 4], copied to LDS one interval
 // ahead by global_load_lds and read from there (one ds_read_b128 per four points).
 #include "rw_common.h"
-#include <stdlib.h>
 
 // Timing ablations (build a second library with -DW4_ABL=<bits>; results are WRONG when a bit is set): 1 = no input
 // transform arithmetic, 2 = no patch fetch / staging, 4 = no weight copies, 8 = no output transform / stores,
@@ -43,9 +42,6 @@
 #ifndef W4_SETPRIO
 #define W4_SETPRIO 0      // A/B builds: wave priority (1..3) while the 36 MFMAs of a k-quad are issued
 #endif
-
-typedef float w4_f32x4 __attribute__((ext_vector_type(4)));
-template <int N> struct w4_int { static constexpr int value = N; };
 
 // Order of the 36 transform points in the packed weights (position -> natural index xi = 6 row + column): rows 0, 1, 2
 // first, then the second half in the order the point-split kernels want it -- positions 20..35 = rows 5, 3, 4 as far as
@@ -75,13 +71,6 @@ struct Wino4Problem {
 #define W4_PC 66                // patch columns: 64 + 2
 #define W4_RS 72                // row pitch of the raw patch in LDS (floats)
 
-__device__ __forceinline__ int w4_xcd_remap(int id, int total) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = id & 7, slot = id >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + slot;
-}
-
 // 1-D input transform B^T (Lavin & Gray, points 0, +-1, +-2, inf), in place
 __device__ __forceinline__ void w4_bt(float& d0, float& d1, float& d2, float& d3, float& d4, float& d5) {
   const float t0 = 4.f * d0 - 5.f * d2 + d4;
@@ -93,17 +82,12 @@ __device__ __forceinline__ void w4_bt(float& d0, float& d1, float& d2, float& d3
 
 // the same on two columns at once (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32: adjacent columns of a patch row come out
 // of the LDS reads as adjacent registers)
-typedef float w4_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned w4_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned w4_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 w4_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 w4_f16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void w4_bt2(w4_f32x2& d0, w4_f32x2& d1, w4_f32x2& d2, w4_f32x2& d3, w4_f32x2& d4,
-                                       w4_f32x2& d5) {
-  const w4_f32x2 t0 = 4.f * d0 - 5.f * d2 + d4;
-  const w4_f32x2 p = d4 - 4.f * d2, q = d3 - 4.f * d1;
-  const w4_f32x2 r = d4 - d2, s = 2.f * (d3 - d1);
-  const w4_f32x2 t5 = 4.f * d1 - 5.f * d3 + d5;
+__device__ __forceinline__ void w4_bt2(rw_f32x2& d0, rw_f32x2& d1, rw_f32x2& d2, rw_f32x2& d3, rw_f32x2& d4,
+                                       rw_f32x2& d5) {
+  const rw_f32x2 t0 = 4.f * d0 - 5.f * d2 + d4;
+  const rw_f32x2 p = d4 - 4.f * d2, q = d3 - 4.f * d1;
+  const rw_f32x2 r = d4 - d2, s = 2.f * (d3 - d1);
+  const rw_f32x2 t5 = 4.f * d1 - 5.f * d3 + d5;
   d0 = t0; d1 = p + q; d2 = p - q; d3 = r + s; d4 = r - s; d5 = t5;
 }
 
@@ -112,13 +96,13 @@ __device__ __forceinline__ void w4_bt2(w4_f32x2& d0, w4_f32x2& d1, w4_f32x2& d2,
 // constants ride in register pairs:
 //   (t0,t5) = 4 P0 - 5 P1 + P2     (p,r) = e4 + (-4,-1) e2     (q,s) = e3 + (-4,-1) e1
 //   (t1,t2) = p + (q,-q)           (t3,t4) = r + (2,-2) s
-__device__ __forceinline__ void w4_bt_row(const w4_f32x2 P0, const w4_f32x2 P1, const w4_f32x2 P2, float (&t)[6]) {
-  const w4_f32x2 K1 = {-4.f, -1.f}, K2 = {2.f, -2.f}, K3 = {1.f, -1.f};
-  const w4_f32x2 t05 = 4.f * P0 + (P2 - 5.f * P1);
-  const w4_f32x2 pr = w4_f32x2{P2[0], P2[0]} + K1 * w4_f32x2{P1[0], P1[0]};
-  const w4_f32x2 qs = w4_f32x2{P1[1], P1[1]} + K1 * w4_f32x2{P0[1], P0[1]};
-  const w4_f32x2 t12 = w4_f32x2{pr[0], pr[0]} + K3 * w4_f32x2{qs[0], qs[0]};
-  const w4_f32x2 t34 = w4_f32x2{pr[1], pr[1]} + K2 * w4_f32x2{qs[1], qs[1]};
+__device__ __forceinline__ void w4_bt_row(const rw_f32x2 P0, const rw_f32x2 P1, const rw_f32x2 P2, float (&t)[6]) {
+  const rw_f32x2 K1 = {-4.f, -1.f}, K2 = {2.f, -2.f}, K3 = {1.f, -1.f};
+  const rw_f32x2 t05 = 4.f * P0 + (P2 - 5.f * P1);
+  const rw_f32x2 pr = rw_f32x2{P2[0], P2[0]} + K1 * rw_f32x2{P1[0], P1[0]};
+  const rw_f32x2 qs = rw_f32x2{P1[1], P1[1]} + K1 * rw_f32x2{P0[1], P0[1]};
+  const rw_f32x2 t12 = rw_f32x2{pr[0], pr[0]} + K3 * rw_f32x2{qs[0], qs[0]};
+  const rw_f32x2 t34 = rw_f32x2{pr[1], pr[1]} + K2 * rw_f32x2{qs[1], qs[1]};
   t[0] = t05[0]; t[1] = t12[0]; t[2] = t12[1]; t[3] = t34[0]; t[4] = t34[1]; t[5] = t05[1];
 }
 
@@ -138,7 +122,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   const int wm = wave / WGN, wn = wave % WGN;
   const int lk = lane >> 4, lt = lane & 15;       // channel of the k-quad / tile column (A: k / out-channel row)
 
-  const int local = w4_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int o_tiles = p.out_ch / (16 * WGM);
   const int runs_x = p.groups_x / p.gpw;
   const int ot = local % o_tiles;
@@ -222,9 +206,9 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   // this lane's item: channel lk of the k-quad, tile (row wn, column lt): patch rows 4 wn .., columns 4 lt ..
   const float* item = &Rs[0][lk][4 * wn][4 * lt];
 
-  w4_f32x4 acc[36];
+  rw_f32x4 acc[36];
 #pragma unroll
-  for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
 
   const float noise_w = p.noise ? p.noise_w[0] : 0.f;
 
@@ -232,14 +216,14 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   auto compute = [&](int buf, int ubuf) __attribute__((always_inline)) {
     const float* base = &Us[ubuf][wm][a_lane];
     // column pass on column pairs (packed), row pass scalar on the halves of the pairs: no register shuffles
-    w4_f32x2 c2[6][3];
+    rw_f32x2 c2[6][3];
     const float* src = item + buf * IC * PR * W4_RS;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const w4_f32x4 lo = *reinterpret_cast<const w4_f32x4*>(src + r * W4_RS);
-      c2[r][0] = w4_f32x2{lo[0], lo[1]};
-      c2[r][1] = w4_f32x2{lo[2], lo[3]};
-      c2[r][2] = *reinterpret_cast<const w4_f32x2*>(src + r * W4_RS + 4);
+      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(src + r * W4_RS);
+      c2[r][0] = rw_f32x2{lo[0], lo[1]};
+      c2[r][1] = rw_f32x2{lo[2], lo[3]};
+      c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4_RS + 4);
     }
     float d[6][6];
     if (!(W4_ABL & 1)) {
@@ -257,7 +241,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
     }
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-      const w4_f32x4 a = *reinterpret_cast<const w4_f32x4*>(base + q * 256);
+      const rw_f32x4 a = *reinterpret_cast<const rw_f32x4*>(base + q * 256);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int xi = w4_nat(4 * q + e);
@@ -270,13 +254,13 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   // o0 + 16 wm + 4 lk + j, tile (row wn, column lt) -> pixels (y0 + 4 wn .. +3, x0 + 4 lt .. +3)
   auto group_epilogue = [&](int g) __attribute__((always_inline)) {
     const int oy = y0 + 4 * wn, ox = (gx0 + g) * 64 + 4 * lt;
-    w4_f32x4 nz[4];
+    rw_f32x4 nz[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) nz[r] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < 4; ++r) nz[r] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     if (p.noise) {
       const float* np = p.noise + (int64_t)ib * hw + (int64_t)oy * p.w + ox;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) nz[r] = *reinterpret_cast<const w4_f32x4*>(np + (int64_t)r * p.w) * noise_w;
+      for (int r = 0; r < 4; ++r) nz[r] = *reinterpret_cast<const rw_f32x4*>(np + (int64_t)r * p.w) * noise_w;
     }
     const float* ct = &Ct[0][16 * wm + 4 * lk];
     float* yb = p.y + ((int64_t)ib * p.out_ch + o0 + 16 * wm + 4 * lk) * hw + (int64_t)oy * p.w + ox;
@@ -298,7 +282,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float s1 = t[r][1] + t[r][2], s2 = t[r][1] - t[r][2], s3 = t[r][3] + t[r][4], s4 = t[r][3] - t[r][4];
-        w4_f32x4 v = {t[r][0] + s1 + s3, s2 + 2.f * s4, s1 + 4.f * s3, s2 + 8.f * s4 + t[r][5]};
+        rw_f32x4 v = {t[r][0] + s1 + s3, s2 + 2.f * s4, s1 + 4.f * s3, s2 + 8.f * s4 + t[r][5]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float u = v[k] * scale + nz[r][k];
@@ -308,11 +292,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
           }
           v[k] = u;
         }
-        *reinterpret_cast<w4_f32x4*>(yb + (int64_t)j * hw + (int64_t)r * p.w) = v;
+        *reinterpret_cast<rw_f32x4*>(yb + (int64_t)j * hw + (int64_t)r * p.w) = v;
       }
     }
 #pragma unroll
-    for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
   // ---- prologue: Rs[0] = interval 0, registers = interval 1
@@ -380,31 +364,14 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 #define W4_NTS 0          // non-temporal stores of the output map (A/B builds)
 #endif
 #if W4_NTS
-#define W4_STORE(ptr, val) __builtin_nontemporal_store((val), reinterpret_cast<w4_f32x4*>(ptr))
+#define W4_STORE(ptr, val) __builtin_nontemporal_store((val), reinterpret_cast<rw_f32x4*>(ptr))
 #else
-#define W4_STORE(ptr, val) (*reinterpret_cast<w4_f32x4*>(ptr) = (val))
+#define W4_STORE(ptr, val) (*reinterpret_cast<rw_f32x4*>(ptr) = (val))
 #endif
 #ifndef W4C_PREFETCH
 #define W4C_PREFETCH 0        // raw window of the next interval read during the MFMAs (36 more live registers)
 #endif
-typedef int w4_i32x4 __attribute__((ext_vector_type(4)));
-// LDS-direct loads as inline assembly (see the note on the compiler above): M0 = LDS byte address of the wave's 64 x
-// size destination, lane L lands at + L * size.
-__device__ __forceinline__ void w4_dma_buffer_b32(unsigned lds_addr, int voffset, w4_i32x4 rsrc, int soffset) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
-}
-__device__ __forceinline__ void w4_dma_global_b128(unsigned lds_addr, const void* gptr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_addr), "v"(gptr) : "memory");
-}
-// the same with a scalar base and a 32-bit lane offset: no 64-bit vector address arithmetic per piece
-__device__ __forceinline__ void w4_dma_global_b128_s(unsigned lds_addr, int voffset, const void* sbase) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_addr), "v"(voffset), "s"(sbase)
-               : "memory");
-}
-__device__ __forceinline__ void w4_dma_global_b32(unsigned lds_addr, const void* gptr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" :: "s"(lds_addr), "v"(gptr) : "memory");
-}
+// (the LDS-direct loads are inline assembly -- see the note on the compiler above: rw_dma_* in rw_common.h)
 
 // WGN tile rows per workgroup (2 WGN waves); UDEPTH = slots of the weight ring.  <4, 3>: one 512-thread workgroup per CU,
 // everything two intervals ahead -- but its eight waves pass one barrier per interval, so the two waves of a SIMD run
@@ -444,11 +411,11 @@ __device__ __forceinline__ void w4_dma_global_b32(unsigned lds_addr, const void*
 // WM + 2, WM + 4 (the single row: 0 or 5), d1..d4 = patch rows 1..4 (the pair rows: 1, 2 or 3, 4) with the wave-uniform
 // coefficients (cA, cB, cC) = (4, 1, 4) or (1, 2, 2): the same values as w4_bt2 computes (scaling by 2 commutes with
 // rounding).  Local row order: (0, 1, 2) resp. (5, 3, 4) -- see w4_nat.
-__device__ __forceinline__ void w4_bt2_rows(const w4_f32x2 e0, const w4_f32x2 e2, const w4_f32x2 e4, const w4_f32x2 d1,
-                                            const w4_f32x2 d2, const w4_f32x2 d3, const w4_f32x2 d4, float cA, float cB,
-                                            float cC, w4_f32x2& o0, w4_f32x2& o1, w4_f32x2& o2) {
+__device__ __forceinline__ void w4_bt2_rows(const rw_f32x2 e0, const rw_f32x2 e2, const rw_f32x2 e4, const rw_f32x2 d1,
+                                            const rw_f32x2 d2, const rw_f32x2 d3, const rw_f32x2 d4, float cA, float cB,
+                                            float cC, rw_f32x2& o0, rw_f32x2& o1, rw_f32x2& o2) {
   o0 = 4.f * e0 - 5.f * e2 + e4;
-  const w4_f32x2 p = d4 - cA * d2, q = cB * d3 - cC * d1;
+  const rw_f32x2 p = d4 - cA * d2, q = cB * d3 - cC * d1;
   o1 = p + q; o2 = p - q;
 }
 // one row of (A^T M) A: six values -> four
@@ -485,16 +452,16 @@ __device__ __forceinline__ void w4_at_row(const float (&t)[6], float (&v)[4]) {
 // the K = 32 form needs 8-channel intervals whose rings do not fit two workgroups' LDS.
 // ---------------------------------------------------------------------------------------
 // (h, h) and (l, l) of v: h = f16(v), l = f16(v - h)
-__device__ __forceinline__ void w4_split16(float v, w4_f16x2& hh, w4_f16x2& ll) {
-  if (W4_ABL & 32) { hh = __builtin_bit_cast(w4_f16x2, v); ll = hh; return; }
-  hh = __builtin_convertvector(w4_f32x2{v, v}, w4_f16x2);
+__device__ __forceinline__ void w4_split16(float v, rw_f16x2& hh, rw_f16x2& ll) {
+  if (W4_ABL & 32) { hh = __builtin_bit_cast(rw_f16x2, v); ll = hh; return; }
+  hh = __builtin_convertvector(rw_f32x2{v, v}, rw_f16x2);
   float r;
   asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hh), "v"(v));     // v - (float)h, exact
-  ll = __builtin_convertvector(w4_f32x2{r, r}, w4_f16x2);
+  ll = __builtin_convertvector(rw_f32x2{r, r}, rw_f16x2);
 }
-__device__ __forceinline__ w4_f32x4 w4_mfma16(w4_u32x2 ww, w4_f16x2 hh, w4_f16x2 ll, w4_f32x4 acc) {
-  const w4_f16x4 a = __builtin_bit_cast(w4_f16x4, ww);         // (w, w): the word of (position, lane) twice
-  const w4_f16x4 b = {hh[0], hh[1], ll[0], ll[1]};
+__device__ __forceinline__ rw_f32x4 w4_mfma16(rw_u32x2 ww, rw_f16x2 hh, rw_f16x2 ll, rw_f32x4 acc) {
+  const rw_f16x4 a = __builtin_bit_cast(rw_f16x4, ww);         // (w, w): the word of (position, lane) twice
+  const rw_f16x4 b = {hh[0], hh[1], ll[0], ll[1]};
   if (W4_ABL & 64) {
     asm volatile("" :: "v"(a), "v"(b));
     return acc;
@@ -538,7 +505,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   const int wm = wave / WGN, wn = wave % WGN;
   const int lk = lane >> 4, lt = lane & 15;
 
-  const int local = w4_xcd_remap(blockIdx.x, gridDim.x);
+  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
   const int o_tiles = p.out_ch / (16 * WGM);
   const int runs_x = p.groups_x / p.gpw;
   const int ot = local % o_tiles;
@@ -590,7 +557,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   const unsigned ps_base = (unsigned)(size_t)(lds_f)Ps, us_base = (unsigned)(size_t)(lds_f)Us,
                  ns_base = (unsigned)(size_t)(lds_f)Ns;
   const unsigned long long xaddr = (unsigned long long)xb;
-  const w4_i32x4 xsrc = {(int)(unsigned)xaddr, (int)(unsigned)(xaddr >> 32), (int)((int64_t)p.in_ch * hw * 4),
+  const rw_i32x4 xsrc = {(int)(unsigned)xaddr, (int)(unsigned)(xaddr >> 32), (int)((int64_t)p.in_ch * hw * 4),
                          0x00020000};
   const int hw4 = (int)hw * 4;
   // patch pieces of this wave: flat pieces [wave * PPW, + PPW) of the 4 * PIECES of a k-quad (never across a channel)
@@ -618,7 +585,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     p_soff = (4 * fc + pch) * hw4;
     p_dst = ps_base + (unsigned)((ring * PSZ + pch * (PIECES * 64) + 64 * piece0) * 4);
   };
-  auto pload_piece = [&](int s) __attribute__((always_inline)) { w4_dma_buffer_b32(p_dst + 256 * s, xoff[s], xsrc, p_soff); };
+  auto pload_piece = [&](int s) __attribute__((always_inline)) { rw_dma_buffer_b32(p_dst + 256 * s, xoff[s], xsrc, p_soff); };
   auto pload = [&](int ring, int fg, int fc) __attribute__((always_inline)) {
     pload_begin(ring, fg, fc);
 #pragma unroll
@@ -633,7 +600,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       if (j < 9 * WGM) {
         const int ob = j / 9, q = j - 9 * ob;
         const float* src = p.uf + ((int64_t)((o0 >> 4) + ob) * kq_total + kq) * (9 * 256) + q * 256;     // uniform
-        w4_dma_global_b128_s(us_base + (unsigned)((ring * USZ + ob * (9 * 256) + q * 256) * 4), a_lane * 4, src);
+        rw_dma_global_b128_s(us_base + (unsigned)((ring * USZ + ob * (9 * 256) + q * 256) * 4), a_lane * 4, src);
       }
     }
   };
@@ -647,18 +614,18 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       const int vo = ((lane >> 5) * (2 * p.w) + 4 * (lane & 31)) * 4;   // bytes
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        w4_dma_global_b128_s(ns_base + (unsigned)((wn * 1024 + (4 * wm + 2 * j) * 128) * 4), vo,
+        rw_dma_global_b128_s(ns_base + (unsigned)((wn * 1024 + (4 * wm + 2 * j) * 128) * 4), vo,
                              sb + (int64_t)(2 * j) * (2 * p.w));
       return;
     }
     const float* np = p.noise + (int64_t)ib * hw + (int64_t)(y0 + 4 * wn) * p.w + (gx0 + g) * 64 + lane;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) w4_dma_global_b32(ns_base + (unsigned)((wave * NSZ + 64 * r) * 4), np + (int64_t)r * p.w);
+    for (int r = 0; r < 4; ++r) rw_dma_global_b32(ns_base + (unsigned)((wave * NSZ + 64 * r) * 4), np + (int64_t)r * p.w);
   };
 
-  w4_f32x4 acc[36];
+  rw_f32x4 acc[36];
 #pragma unroll
-  for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;                 // H16: max |result| of this lane -> p.y_amax
 
   const int item_off = lk * (PIECES * 64) + (4 * wn) * W4B_PITCH + 4 * lt;
@@ -667,22 +634,22 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     const float* base = &Us[uring * USZ + wm * (9 * 256) + a_lane];
     const float* src = &Ps[ring * PSZ + item_off];
     const float sv = St[4 * kq + lk];
-    w4_f32x4 a4[3];
-    a4[0] = *reinterpret_cast<const w4_f32x4*>(base);
-    a4[1] = *reinterpret_cast<const w4_f32x4*>(base + 256);
-    a4[2] = *reinterpret_cast<const w4_f32x4*>(base + 512);
-    w4_f32x2 c2[6][3];
+    rw_f32x4 a4[3];
+    a4[0] = *reinterpret_cast<const rw_f32x4*>(base);
+    a4[1] = *reinterpret_cast<const rw_f32x4*>(base + 256);
+    a4[2] = *reinterpret_cast<const rw_f32x4*>(base + 512);
+    rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const w4_f32x4 lo = *reinterpret_cast<const w4_f32x4*>(src + r * W4B_PITCH);
+      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(src + r * W4B_PITCH);
       if (STYLE) {
-        c2[r][0] = w4_f32x2{lo[0], lo[1]} * sv;
-        c2[r][1] = w4_f32x2{lo[2], lo[3]} * sv;
-        c2[r][2] = *reinterpret_cast<const w4_f32x2*>(src + r * W4B_PITCH + 4) * sv;
+        c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
+        c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
+        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4) * sv;
       } else {
-        c2[r][0] = w4_f32x2{lo[0], lo[1]};
-        c2[r][1] = w4_f32x2{lo[2], lo[3]};
-        c2[r][2] = *reinterpret_cast<const w4_f32x2*>(src + r * W4B_PITCH + 4);
+        c2[r][0] = rw_f32x2{lo[0], lo[1]};
+        c2[r][1] = rw_f32x2{lo[2], lo[3]};
+        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4);
       }
     }
     float d[6][6];
@@ -705,8 +672,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #endif
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-      const w4_f32x4 a = a4[q % 3];
-      if (q + 3 < 9) a4[q % 3] = *reinterpret_cast<const w4_f32x4*>(base + (q + 3) * 256);
+      const rw_f32x4 a = a4[q % 3];
+      if (q + 3 < 9) a4[q % 3] = *reinterpret_cast<const rw_f32x4*>(base + (q + 3) * 256);
       if (SPREAD && !(W4_ABL & 2)) {
         if (2 * q < PPW) pload_piece(2 * q);
         if (2 * q + 1 < PPW) pload_piece(2 * q + 1);
@@ -727,9 +694,9 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   // (w4_nat): a row of B^T d B is finished right before its first point, every value is split where it is used.  The
   // weight words come in batches of six, one batch ahead: ds_read2st64_b32 with both offsets equal puts the word of
   // (position, lane) into both registers of the operand.
-  auto aread = [&](unsigned addr, auto pos_tag, w4_u32x2& dst) __attribute__((always_inline)) {
+  auto aread = [&](unsigned addr, auto pos_tag, rw_u32x2& dst) __attribute__((always_inline)) {
     constexpr int POS = decltype(pos_tag)::value;
-    if (W4_ABL & 128) { dst = w4_u32x2{addr, (unsigned)POS}; return; }
+    if (W4_ABL & 128) { dst = rw_u32x2{addr, (unsigned)POS}; return; }
     asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%2" : "=&v"(dst) : "v"(addr), "n"(POS));
   };
   auto compute16 = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
@@ -737,29 +704,29 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     const unsigned ua = us_base + (unsigned)((uring * USZ + wm * (9 * 256) + lane) * 4);
     const float* src = &Ps[ring * PSZ + item_off];
     const float sv = St[4 * kq + lk];
-    w4_f32x2 c2[6][3];
+    rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const w4_f32x4 lo = *reinterpret_cast<const w4_f32x4*>(src + r * W4B_PITCH);
-      c2[r][0] = w4_f32x2{lo[0], lo[1]} * sv;
-      c2[r][1] = w4_f32x2{lo[2], lo[3]} * sv;
-      c2[r][2] = *reinterpret_cast<const w4_f32x2*>(src + r * W4B_PITCH + 4) * sv;
+      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(src + r * W4B_PITCH);
+      c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
+      c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
+      c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4) * sv;
     }
-    w4_u32x2 aq[2][6];
-    aread(ua, w4_int<0>(), aq[0][0]); aread(ua, w4_int<1>(), aq[0][1]); aread(ua, w4_int<2>(), aq[0][2]);
-    aread(ua, w4_int<3>(), aq[0][3]); aread(ua, w4_int<4>(), aq[0][4]); aread(ua, w4_int<5>(), aq[0][5]);
+    rw_u32x2 aq[2][6];
+    aread(ua, rw_int<0>(), aq[0][0]); aread(ua, rw_int<1>(), aq[0][1]); aread(ua, rw_int<2>(), aq[0][2]);
+    aread(ua, rw_int<3>(), aq[0][3]); aread(ua, rw_int<4>(), aq[0][4]); aread(ua, rw_int<5>(), aq[0][5]);
 #pragma unroll
     for (int cp = 0; cp < 3; ++cp)
       if (!(W4_ABL & 1)) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
     float d[6][6];
     auto batch = [&](auto bt_tag) __attribute__((always_inline)) {
       constexpr int BT = decltype(bt_tag)::value;
-      w4_u32x2 (&cur)[6] = aq[BT & 1];
+      rw_u32x2 (&cur)[6] = aq[BT & 1];
       if (BT < 5) {
-        w4_u32x2 (&nxt)[6] = aq[(BT + 1) & 1];
-        aread(ua, w4_int<6 * BT + 6>(), nxt[0]); aread(ua, w4_int<6 * BT + 7>(), nxt[1]);
-        aread(ua, w4_int<6 * BT + 8>(), nxt[2]); aread(ua, w4_int<6 * BT + 9>(), nxt[3]);
-        aread(ua, w4_int<6 * BT + 10>(), nxt[4]); aread(ua, w4_int<6 * BT + 11>(), nxt[5]);
+        rw_u32x2 (&nxt)[6] = aq[(BT + 1) & 1];
+        aread(ua, rw_int<6 * BT + 6>(), nxt[0]); aread(ua, rw_int<6 * BT + 7>(), nxt[1]);
+        aread(ua, rw_int<6 * BT + 8>(), nxt[2]); aread(ua, rw_int<6 * BT + 9>(), nxt[3]);
+        aread(ua, rw_int<6 * BT + 10>(), nxt[4]); aread(ua, rw_int<6 * BT + 11>(), nxt[5]);
         // this batch's reads are older than the six just issued
         if (!(W4_ABL & 128))
           asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
@@ -785,12 +752,12 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
             d[ra][4] = c2[ra][2][0]; d[ra][5] = c2[ra][2][1];
           }
         }
-        w4_f16x2 hh, ll;
+        rw_f16x2 hh, ll;
         w4_split16(d[ra][xi % 6], hh, ll);
         acc[xi] = w4_mfma16(cur[e], hh, ll, acc[xi]);
       }
     };
-    batch(w4_int<0>()); batch(w4_int<1>()); batch(w4_int<2>()); batch(w4_int<3>()); batch(w4_int<4>()); batch(w4_int<5>());
+    batch(rw_int<0>()); batch(rw_int<1>()); batch(rw_int<2>()); batch(rw_int<3>()); batch(rw_int<4>()); batch(rw_int<5>());
     static_assert(2 * 6 >= PPW, "two patch pieces per batch cover the wave's share");
   };
 
@@ -804,26 +771,26 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     const float* base = &Us[uring * USZ + a_lane];                        // block 1: + 9 * 256
     const float* src = &Ps[ring * PSZ + item_off];
     const float sv = St[4 * kq + lk];
-    w4_f32x4 a4[2][2];
-    a4[0][0] = *reinterpret_cast<const w4_f32x4*>(base + ps_quad);
-    a4[0][1] = *reinterpret_cast<const w4_f32x4*>(base + 9 * 256 + ps_quad);
+    rw_f32x4 a4[2][2];
+    a4[0][0] = *reinterpret_cast<const rw_f32x4*>(base + ps_quad);
+    a4[0][1] = *reinterpret_cast<const rw_f32x4*>(base + 9 * 256 + ps_quad);
     // rows: [0..2] = patch rows wm, wm + 2, wm + 4; [3..6] = patch rows 1..4
-    w4_f32x2 c2[7][3];
+    rw_f32x2 c2[7][3];
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
       const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      const w4_f32x4 lo = *reinterpret_cast<const w4_f32x4*>(rp);
+      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(rp);
       if (STYLE) {
-        c2[r][0] = w4_f32x2{lo[0], lo[1]} * sv;
-        c2[r][1] = w4_f32x2{lo[2], lo[3]} * sv;
-        c2[r][2] = *reinterpret_cast<const w4_f32x2*>(rp + 4) * sv;
+        c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
+        c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
+        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4) * sv;
       } else {
-        c2[r][0] = w4_f32x2{lo[0], lo[1]};
-        c2[r][1] = w4_f32x2{lo[2], lo[3]};
-        c2[r][2] = *reinterpret_cast<const w4_f32x2*>(rp + 4);
+        c2[r][0] = rw_f32x2{lo[0], lo[1]};
+        c2[r][1] = rw_f32x2{lo[2], lo[3]};
+        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4);
       }
     }
-    w4_f32x2 hrow[3][3];
+    rw_f32x2 hrow[3][3];
 #pragma unroll
     for (int cp = 0; cp < 3; ++cp)
       w4_bt2_rows(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp], c2[6][cp], ps_cA, ps_cB, ps_cC,
@@ -834,15 +801,15 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     // four whole quads (local points 0..15), then the half quad (16, 17); weights one quad ahead
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
-      const w4_f32x4 a0 = a4[q & 1][0], a1 = a4[q & 1][1];
+      const rw_f32x4 a0 = a4[q & 1][0], a1 = a4[q & 1][1];
       if (q + 1 < 4) {
-        a4[(q + 1) & 1][0] = *reinterpret_cast<const w4_f32x4*>(base + ps_quad + (q + 1) * 256);
-        a4[(q + 1) & 1][1] = *reinterpret_cast<const w4_f32x4*>(base + 9 * 256 + ps_quad + (q + 1) * 256);
+        a4[(q + 1) & 1][0] = *reinterpret_cast<const rw_f32x4*>(base + ps_quad + (q + 1) * 256);
+        a4[(q + 1) & 1][1] = *reinterpret_cast<const rw_f32x4*>(base + 9 * 256 + ps_quad + (q + 1) * 256);
       } else if (q + 1 == 4) {
-        const w4_f32x2 h0 = *reinterpret_cast<const w4_f32x2*>(base + ps_half);
-        const w4_f32x2 h1 = *reinterpret_cast<const w4_f32x2*>(base + 9 * 256 + ps_half);
-        a4[0][0] = w4_f32x4{h0[0], h0[1], 0.f, 0.f};
-        a4[0][1] = w4_f32x4{h1[0], h1[1], 0.f, 0.f};
+        const rw_f32x2 h0 = *reinterpret_cast<const rw_f32x2*>(base + ps_half);
+        const rw_f32x2 h1 = *reinterpret_cast<const rw_f32x2*>(base + 9 * 256 + ps_half);
+        a4[0][0] = rw_f32x4{h0[0], h0[1], 0.f, 0.f};
+        a4[0][1] = rw_f32x4{h1[0], h1[1], 0.f, 0.f};
       }
       if (SPREAD && !(W4_ABL & 2)) {
 #pragma unroll
@@ -868,19 +835,19 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     const unsigned ub = us_base + (unsigned)((uring * USZ + lane) * 4) + (unsigned)(wm * 2 * 256);
     const float* src = &Ps[ring * PSZ + item_off];
     const float sv = St[4 * kq + lk];
-    w4_u32x2 aq[2][6];                              // three points x two blocks per batch
-    aread(ua, w4_int<0>(), aq[0][0]); aread(ua, w4_int<36>(), aq[0][1]); aread(ua, w4_int<1>(), aq[0][2]);
-    aread(ua, w4_int<37>(), aq[0][3]); aread(ua, w4_int<2>(), aq[0][4]); aread(ua, w4_int<38>(), aq[0][5]);
-    w4_f32x2 c2[7][3];
+    rw_u32x2 aq[2][6];                              // three points x two blocks per batch
+    aread(ua, rw_int<0>(), aq[0][0]); aread(ua, rw_int<36>(), aq[0][1]); aread(ua, rw_int<1>(), aq[0][2]);
+    aread(ua, rw_int<37>(), aq[0][3]); aread(ua, rw_int<2>(), aq[0][4]); aread(ua, rw_int<38>(), aq[0][5]);
+    rw_f32x2 c2[7][3];
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
       const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      const w4_f32x4 lo = *reinterpret_cast<const w4_f32x4*>(rp);
-      c2[r][0] = w4_f32x2{lo[0], lo[1]} * sv;
-      c2[r][1] = w4_f32x2{lo[2], lo[3]} * sv;
-      c2[r][2] = *reinterpret_cast<const w4_f32x2*>(rp + 4) * sv;
+      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(rp);
+      c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
+      c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
+      c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4) * sv;
     }
-    w4_f32x2 hrow[3][3];
+    rw_f32x2 hrow[3][3];
 #pragma unroll
     for (int cp = 0; cp < 3; ++cp)
       w4_bt2_rows(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp], c2[6][cp], ps_cA, ps_cB, ps_cC,
@@ -888,13 +855,13 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     float d[3][6];
     auto batch = [&](auto bt_tag) __attribute__((always_inline)) {
       constexpr int BT = decltype(bt_tag)::value;
-      w4_u32x2 (&cur)[6] = aq[BT & 1];
+      rw_u32x2 (&cur)[6] = aq[BT & 1];
       if (BT < 5) {
-        w4_u32x2 (&nxt)[6] = aq[(BT + 1) & 1];
+        rw_u32x2 (&nxt)[6] = aq[(BT + 1) & 1];
         constexpr int L0 = 3 * BT + 3, L1 = 3 * BT + 4, L2 = 3 * BT + 5;      // the next batch's local points
-        aread(L0 < 16 ? ua : ub, w4_int<L0>(), nxt[0]); aread(L0 < 16 ? ua : ub, w4_int<L0 + 36>(), nxt[1]);
-        aread(L1 < 16 ? ua : ub, w4_int<L1>(), nxt[2]); aread(L1 < 16 ? ua : ub, w4_int<L1 + 36>(), nxt[3]);
-        aread(L2 < 16 ? ua : ub, w4_int<L2>(), nxt[4]); aread(L2 < 16 ? ua : ub, w4_int<L2 + 36>(), nxt[5]);
+        aread(L0 < 16 ? ua : ub, rw_int<L0>(), nxt[0]); aread(L0 < 16 ? ua : ub, rw_int<L0 + 36>(), nxt[1]);
+        aread(L1 < 16 ? ua : ub, rw_int<L1>(), nxt[2]); aread(L1 < 16 ? ua : ub, rw_int<L1 + 36>(), nxt[3]);
+        aread(L2 < 16 ? ua : ub, rw_int<L2>(), nxt[4]); aread(L2 < 16 ? ua : ub, rw_int<L2 + 36>(), nxt[5]);
         if (!(W4_ABL & 128))
           asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
       } else if (!(W4_ABL & 128)) {
@@ -909,13 +876,13 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       for (int e = 0; e < 3; ++e) {
         const int le = 3 * BT + e;
         if (le % 6 == 0) w4_bt_row(hrow[le / 6][0], hrow[le / 6][1], hrow[le / 6][2], d[le / 6]);
-        w4_f16x2 hh, ll;
+        rw_f16x2 hh, ll;
         w4_split16(d[le / 6][le % 6], hh, ll);
         acc[le] = w4_mfma16(cur[2 * e], hh, ll, acc[le]);
         acc[18 + le] = w4_mfma16(cur[2 * e + 1], hh, ll, acc[18 + le]);
       }
     };
-    batch(w4_int<0>()); batch(w4_int<1>()); batch(w4_int<2>()); batch(w4_int<3>()); batch(w4_int<4>()); batch(w4_int<5>());
+    batch(rw_int<0>()); batch(rw_int<1>()); batch(rw_int<2>()); batch(rw_int<3>()); batch(rw_int<4>()); batch(rw_int<5>());
   };
 
   // ---- the output transform of one accumulator component j: Y[r][k] = (A^T M A)[r][k] of this wave's out-channel block
@@ -974,15 +941,15 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     lds_barrier();                                  // nobody reads what the slot held (weights / the previous round)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      w4_f32x4 o4;
+      rw_f32x4 o4;
 #pragma unroll
       for (int k = 0; k < 4; ++k) { o4[k] = wm ? y0[r][k] : y1[r][k]; Y[r][k] = wm ? y1[r][k] : y0[r][k]; }
-      *reinterpret_cast<w4_f32x4*>(xw + r * 256) = o4;
+      *reinterpret_cast<rw_f32x4*>(xw + r * 256) = o4;
     }
     lds_barrier();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const w4_f32x4 o4 = *reinterpret_cast<const w4_f32x4*>(xr + r * 256);
+      const rw_f32x4 o4 = *reinterpret_cast<const rw_f32x4*>(xr + r * 256);
 #pragma unroll
       for (int k = 0; k < 4; ++k) Y[r][k] += o4[k];
     }
@@ -1012,13 +979,13 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t off = (int64_t)(2 * r + py) * W2;
-        w4_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
+        rw_f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
         if (p.noise) {
-          n0 = *reinterpret_cast<const w4_f32x4*>(nb + (2 * r + py) * 128) * nwg;
-          n1 = *reinterpret_cast<const w4_f32x4*>(nb + (2 * r + py) * 128 + 4) * nwg;
+          n0 = *reinterpret_cast<const rw_f32x4*>(nb + (2 * r + py) * 128) * nwg;
+          n1 = *reinterpret_cast<const rw_f32x4*>(nb + (2 * r + py) * 128 + 4) * nwg;
         }
-        w4_f32x4 q0 = {v[0][r][0], v[1][r][0], v[0][r][1], v[1][r][1]};
-        w4_f32x4 q1 = {v[0][r][2], v[1][r][2], v[0][r][3], v[1][r][3]};
+        rw_f32x4 q0 = {v[0][r][0], v[1][r][0], v[0][r][1], v[1][r][1]};
+        rw_f32x4 q1 = {v[0][r][2], v[1][r][2], v[0][r][3], v[1][r][3]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float u0 = q0[k] * scale + n0[k] + bias, u1 = q1[k] * scale + n1[k] + bias;
@@ -1030,17 +997,17 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       }
     }
 #pragma unroll
-    for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
   auto rgb_epilogue = [&](int g, int xs) __attribute__((always_inline)) {
     const int oy = y0 + 4 * wn, ox = (gx0 + g) * 64 + 4 * lt;
     const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
-    w4_f32x4 nz[4];
+    rw_f32x4 nz[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      nz[r] = p.noise ? *reinterpret_cast<const w4_f32x4*>(&Ns[wave * NSZ + 64 * r + 4 * lt]) * (noise_w * gain)
-                      : w4_f32x4{0.f, 0.f, 0.f, 0.f};
+      nz[r] = p.noise ? *reinterpret_cast<const rw_f32x4*>(&Ns[wave * NSZ + 64 * r + 4 * lt]) * (noise_w * gain)
+                      : rw_f32x4{0.f, 0.f, 0.f, 0.f};
     float rp[4][4][3];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1066,13 +1033,12 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       }
     }
 #pragma unroll
-    for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     // sum over the wave's 16 channels = over its four 16-lane groups, as a reduce-scatter: lane (lk, lt) ends with
     // row lk of the tile
     // (gfx950's v_permlane32_swap / v_permlane16_swap exchange the halves / the odd and even rows of TWO registers in
     // one instruction: A' + B' is then "what I keep" + "what my partner sent" for both sides at once -- 36 swaps and adds
     // where ds_bpermute needed 36 LDS round trips and 72 selects)
-    typedef unsigned w4_u32x2 __attribute__((ext_vector_type(2)));
     float q[2][4][3];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -1081,17 +1047,17 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc) {
           // lanes 0..31 (lk 0, 1) keep row a, lanes 32..63 keep row a + 2
-          const w4_u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(rp[a][k][cc]),
+          const rw_u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(rp[a][k][cc]),
                                                               __float_as_uint(rp[a + 2][k][cc]), false, false);
           q[a][k][cc] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
         }
-    w4_f32x4 sum[3];
+    rw_f32x4 sum[3];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) {
         // even 16-lane rows (lk 0, 2) keep q[0], odd rows keep q[1]
-        const w4_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0][k][cc]), __float_as_uint(q[1][k][cc]),
+        const rw_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0][k][cc]), __float_as_uint(q[1][k][cc]),
                                                             false, false);
         sum[cc][k] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
       }
@@ -1102,7 +1068,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     asm volatile("" ::: "memory");
     if (!mine) {
 #pragma unroll
-      for (int cc = 0; cc < 3; ++cc) *reinterpret_cast<w4_f32x4*>(&Ns[wave * NSZ + cc * 128 + slot]) = sum[cc];
+      for (int cc = 0; cc < 3; ++cc) *reinterpret_cast<rw_f32x4*>(&Ns[wave * NSZ + cc * 128 + slot]) = sum[cc];
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
@@ -1111,11 +1077,11 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       const int64_t pix = (int64_t)(oy + lk) * p.w + ox;
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) {
-        const w4_f32x4 other = *reinterpret_cast<const w4_f32x4*>(&Ns[(wave ^ WGN) * NSZ + cc * 128 + slot]);
+        const rw_f32x4 other = *reinterpret_cast<const rw_f32x4*>(&Ns[(wave ^ WGN) * NSZ + cc * 128 + slot]);
         const int64_t off = ((int64_t)ib * 3 + cc) * hw + pix;
-        w4_f32x4 o4 = sum[cc] + other + (p.rgb_bias ? p.rgb_bias[cc] : 0.f);
-        if (p.rgb_skip) o4 += *reinterpret_cast<const w4_f32x4*>(p.rgb_skip + off);
-        *reinterpret_cast<w4_f32x4*>(p.rgb_out + off) = o4;
+        rw_f32x4 o4 = sum[cc] + other + (p.rgb_bias ? p.rgb_bias[cc] : 0.f);
+        if (p.rgb_skip) o4 += *reinterpret_cast<const rw_f32x4*>(p.rgb_skip + off);
+        *reinterpret_cast<rw_f32x4*>(p.rgb_out + off) = o4;
       }
     }
   };
@@ -1125,11 +1091,11 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     if (RGB) { rgb_epilogue(g, xs); return; }
     const int oy = y0 + 4 * wn, ox = (gx0 + g) * 64 + 4 * lt;
     const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
-    w4_f32x4 nz[4];
+    rw_f32x4 nz[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      nz[r] = p.noise ? *reinterpret_cast<const w4_f32x4*>(&Ns[wave * NSZ + 64 * r + 4 * lt]) * (noise_w * gain)
-                      : w4_f32x4{0.f, 0.f, 0.f, 0.f};
+      nz[r] = p.noise ? *reinterpret_cast<const rw_f32x4*>(&Ns[wave * NSZ + 64 * r + 4 * lt]) * (noise_w * gain)
+                      : rw_f32x4{0.f, 0.f, 0.f, 0.f};
     const float* ct = &Ct[0][16 * wm + 4 * lk];
     float* yb = p.y + ((int64_t)ib * p.out_ch + o0 + 16 * wm + 4 * lk) * hw + (int64_t)oy * p.w + ox;
 #pragma unroll
@@ -1139,7 +1105,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       tile(j, xs, Y);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        w4_f32x4 v = {Y[r][0], Y[r][1], Y[r][2], Y[r][3]};
+        rw_f32x4 v = {Y[r][0], Y[r][1], Y[r][2], Y[r][3]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float u = v[k] * scale + nz[r][k] + bias;
@@ -1150,7 +1116,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       }
     }
 #pragma unroll
-    for (int xi = 0; xi < 36; ++xi) acc[xi] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
   // s_waitcnt immediates (gfx9): vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14; expcnt 7 = no wait
@@ -1195,15 +1161,15 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       if (!(W4_ABL & 4)) uload((v + 1) & 1, c + 1 < NC ? c + 1 : 0);      // weights of interval v + 1
       pload_begin(ring2, fg, fc);                   // past the run: legal addresses, never read
       // ... issues the patch pieces of v + 2 between its MFMAs
-      if (H16 && PS) compute16_ps(ring, v & 1, c, w4_int<1>());
-      else if (H16) compute16(ring, v & 1, c, w4_int<1>());
-      else if (!PS) compute(ring, v & 1, c, w4_int<1>());
-      else compute_ps(ring, v & 1, c, w4_int<1>());
+      if (H16 && PS) compute16_ps(ring, v & 1, c, rw_int<1>());
+      else if (H16) compute16(ring, v & 1, c, rw_int<1>());
+      else if (!PS) compute(ring, v & 1, c, rw_int<1>());
+      else compute_ps(ring, v & 1, c, rw_int<1>());
     } else {
       if (!(W4_ABL & 2)) pload(ring2, fg, fc);
       if (!(W4_ABL & 4)) uload(ring2, fc);
-      if (H16) compute16(ring, ring, c, w4_int<0>());
-      else compute(ring, ring, c, w4_int<0>());
+      if (H16) compute16(ring, ring, c, rw_int<0>());
+      else compute(ring, ring, c, rw_int<0>());
     }
     const bool last = c == NC - 1;
     if (last) {
@@ -1254,8 +1220,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino36h_rgb_ps_kernel(const Wino4
 __global__ void __launch_bounds__(512, 1) conv_wino36h_wg8_kernel(const Wino4Problem p) { conv_wino36b_body<4, 3, 0, true, false, true>(p); }
 // point split: 0 = never, 1 = always, default = where in_ch >= 64 (RW_W4H_PS overrides)
 static bool w4h_point_split(int in_ch) {
-  const char* e = getenv("RW_W4H_PS");
-  const int mode = e ? atoi(e) : -1;
+  const int mode = rw_env_int("RW_W4H_PS", -1);
   return mode < 0 ? in_ch >= 64 : mode != 0;
 }
 
@@ -1278,7 +1243,7 @@ __global__ void __launch_bounds__(256, 2) conv_up_wino36_ns_ps_kernel(const Wino
 __global__ void __launch_bounds__(256, 2) conv_wino36_rgb_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 2, true, true>(p); }
 __global__ void __launch_bounds__(256, 2) conv_wino36_rgb_ns_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 2, false, true>(p); }
 static bool w4_point_split() {
-  static const bool on = [] { const char* e = getenv("RW_W4_PSPLIT"); return e && e[0] == '1'; }();
+  static const bool on = rw_env_is("RW_W4_PSPLIT", '1');
   return on;
 }
 #endif
@@ -1324,8 +1289,8 @@ __device__ __forceinline__ float w4_pack_store(const float* g, float* dst, float
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
       if (PASS == 0) {
-        *reinterpret_cast<w4_f32x4*>(dst + q * 256) =
-            w4_f32x4{u[w4_nat(4 * q)], u[w4_nat(4 * q + 1)], u[w4_nat(4 * q + 2)], u[w4_nat(4 * q + 3)]};
+        *reinterpret_cast<rw_f32x4*>(dst + q * 256) =
+            rw_f32x4{u[w4_nat(4 * q)], u[w4_nat(4 * q + 1)], u[w4_nat(4 * q + 2)], u[w4_nat(4 * q + 3)]};
       } else {
         // H16: one word per (position, lane), positions 256 bytes apart -- the kernels read a word into both halves of
         // an operand pair with ds_read2st64_b32 (dst = the lane's column of the block: + lane instead of + 4 lane)
@@ -1430,84 +1395,59 @@ extern "C" int rw_pack_conv_weight_wino4_f32(const float* w, float* uf, int out_
   return RW_LAUNCH_RESULT();
 }
 
+// whole rows where the launch still has >= 1024 workgroups: +1.5 % over 4
 static int wino4_gpw(const Wino4Problem& p, int batch, int o_tiles) {
-  const char* e = getenv("RW_WINO4_GPW");
-  int gpw = e ? atoi(e) : 16;         // whole rows where the launch still has >= 1024 workgroups: +1.5 % over 4
-  if (gpw < 1) gpw = 1;
-  if (gpw > p.groups_x) gpw = p.groups_x;
-  while (p.groups_x % gpw) --gpw;
-  while (gpw > 1 && (int64_t)batch * p.groups_y * (p.groups_x / gpw) * o_tiles < 1024) {
-    --gpw;
-    while (p.groups_x % gpw) --gpw;
-  }
-  return gpw;
+  return rw_groups_per_wg(p.groups_x, (int64_t)batch * p.groups_y * o_tiles, rw_env_int("RW_WINO4_GPW", 16), 1024);
 }
 
-// after an H16 launch whose waves stored their maxima: the bound of the result
-static int w4h_finish(float* y_amax, int64_t nslots, rw_stream_t stream) {
-  const int rc = RW_LAUNCH_RESULT();
-  if (rc || !y_amax) return rc;
-  return rw_bound_finish(y_amax, nslots, rw_s(stream));
+// what the three launchers share: the operands, the epilogue, the shape and the 8 x 64 pixel tile groups (32 out-channels
+// x 2 tile rows per workgroup)
+static void wino4_fill(Wino4Problem& p, const float* x, const float* uf, float* y, int batch, int in_ch, int vch, int h,
+                       int w, float w_scale, const rw_conv_epilogue* ep, float u_inv, const float* x_amax, float* y_amax) {
+  p.x = x; p.uf = uf; p.y = y;
+  rw_fill_epilogue(p, ep);
+  p.batch = batch; p.in_ch = in_ch; p.out_ch = vch; p.h = h; p.w = w; p.w_scale = w_scale;
+  p.x_amax = x_amax; p.y_amax = y_amax; p.u_inv = u_inv;
+  p.groups_x = w / 64;
+  p.groups_y = h / 8;
 }
 
 static int conv3x3_wino4_launch(const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch, int h,
                                 int w, float w_scale, const rw_conv_epilogue* ep, bool h16, float u_inv,
                                 const float* x_amax, float* y_amax, rw_stream_t stream) {
   RW_CHECK_ARG(x && uf && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
   if (!wino4_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
-  p.x = x; p.uf = uf; p.y = y;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
-  p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w; p.w_scale = w_scale;
-  p.x_amax = x_amax; p.y_amax = y_amax; p.u_inv = u_inv;
-  // 32 out-channels x 2 tile rows (8 x 64 pixels) per workgroup
-  p.groups_x = w / 64;
-  p.groups_y = h / 8;
+  wino4_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
   const int o_tiles = out_ch / 32;
-  const int gpw = wino4_gpw(p, batch, o_tiles);
-  p.gpw = gpw;
-  const int64_t work = (int64_t)batch * p.groups_y * (p.groups_x / gpw) * o_tiles;
+  p.gpw = wino4_gpw(p, batch, o_tiles);
+  const int64_t work = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
   if (h16) {
     if (in_ch > 512) return RW_ERR_UNSUPPORTED;
     const int64_t n_out = (int64_t)batch * out_ch * h * w;
-    const char* wg8 = getenv("RW_W4H_WG8");
-    if (wg8 && wg8[0] == '1' && h % 16 == 0) {
+    if (rw_env_is("RW_W4H_WG8", '1') && h % 16 == 0) {
       p.groups_y = h / 16;
-      int g8 = 4;
-      if (g8 > p.groups_x) g8 = p.groups_x;
-      while (p.groups_x % g8) --g8;
-      p.gpw = g8;
-      const int64_t work8 = (int64_t)batch * p.groups_y * (p.groups_x / g8) * o_tiles;
+      p.gpw = rw_groups_per_wg(p.groups_x, 0, 4, 0);
+      const int64_t work8 = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
       if (y_amax && 8 * work8 > rw_bound_slot_capacity(n_out)) return RW_ERR_UNSUPPORTED;
       hipLaunchKernelGGL(conv_wino36h_wg8_kernel, dim3((unsigned)work8), dim3(512), 0, rw_s(stream), p);
-      return w4h_finish(y_amax, 8 * work8, stream);
+      return rw_finish_bound(y_amax, 8 * work8, stream);
     }
     if (y_amax && 4 * work > rw_bound_slot_capacity(n_out)) return RW_ERR_UNSUPPORTED;
     if (w4h_point_split(in_ch)) hipLaunchKernelGGL(conv_wino36h_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     else hipLaunchKernelGGL(conv_wino36h_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-    return w4h_finish(y_amax, 4 * work, stream);
+    return rw_finish_bound(y_amax, 4 * work, stream);
   }
   // versions: 1 = registers / compiler-scheduled loads (256 threads); 2 = <4,3> 512-thread workgroups;
   // 3 (default) = <2,2> two 256-thread workgroups per CU.  RW_WINO4_V overrides for comparison.
-  const char* ver = getenv("RW_WINO4_V");
-  const int version = ver ? atoi(ver) : 3;
+  const int version = rw_env_int("RW_WINO4_V", 3);
   if (version == 2 && h % 16 == 0 && in_ch <= 512) {
-    const char* e = getenv("RW_WINO4_GPW");
     p.groups_y = h / 16;
-    int gpw2 = e ? atoi(e) : 4;
-    if (gpw2 < 1) gpw2 = 1;
-    if (gpw2 > p.groups_x) gpw2 = p.groups_x;
-    while (p.groups_x % gpw2) --gpw2;
-    while (gpw2 > 1 && (int64_t)batch * p.groups_y * (p.groups_x / gpw2) * o_tiles < 512) {
-      --gpw2;
-      while (p.groups_x % gpw2) --gpw2;
-    }
-    p.gpw = gpw2;
-    const int64_t work2 = (int64_t)batch * p.groups_y * (p.groups_x / gpw2) * o_tiles;
+    p.gpw = rw_groups_per_wg(p.groups_x, (int64_t)batch * p.groups_y * o_tiles, rw_env_int("RW_WINO4_GPW", 4), 512);
+    const int64_t work2 = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
     if (work2 <= 0 || work2 > 0x7fffffff) return RW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((conv_wino36b_kernel<4, 3>), dim3((unsigned)work2), dim3(512), 0, rw_s(stream), p);
     return RW_LAUNCH_RESULT();
@@ -1545,7 +1485,7 @@ extern "C" int rw_conv_weight_wino4h_absmax_f32(const float* w, int out_ch, int 
   const int grid = rw_stream_grid(total, 256);
   hipLaunchKernelGGL(pack_wino36_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, (float*)nullptr, out_ch, in_ch, 1.f,
                      bound);
-  return w4h_finish(bound, grid, stream);
+  return rw_finish_bound(bound, grid, stream);
 }
 
 extern "C" int rw_pack_conv_weight_wino4h_f32(const float* w, float* uf, int out_ch, int in_ch, float u_scale,
@@ -1596,18 +1536,12 @@ static int up_wino4_launch(const float* x, const float* uf, float* y, int batch,
                            float w_scale, const rw_conv_epilogue* ep, const float* post_scale, bool h16, float u_inv,
                            const float* x_amax, float* y_amax, rw_stream_t stream) {
   RW_CHECK_ARG(x && uf && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
   if (!up_wino4_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
-  p.x = x; p.uf = uf; p.y = y;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
+  wino4_fill(p, x, uf, y, batch, in_ch, 4 * out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
   p.post = post_scale;
-  p.batch = batch; p.in_ch = in_ch; p.out_ch = 4 * out_ch; p.h = h; p.w = w; p.w_scale = w_scale;
-  p.x_amax = x_amax; p.y_amax = y_amax; p.u_inv = u_inv;
-  p.groups_x = w / 64;
-  p.groups_y = h / 8;
   const int o_tiles = p.out_ch / 32;
   p.gpw = wino4_gpw(p, batch, o_tiles);
   const int64_t work = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw) * o_tiles;
@@ -1616,7 +1550,7 @@ static int up_wino4_launch(const float* x, const float* uf, float* y, int batch,
     if (y_amax && 4 * work > rw_bound_slot_capacity((int64_t)batch * out_ch * 4 * h * w)) return RW_ERR_UNSUPPORTED;
     if (w4h_point_split(in_ch)) hipLaunchKernelGGL(conv_up_wino36h_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     else hipLaunchKernelGGL(conv_up_wino36h_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-    return w4h_finish(y_amax, 4 * work, stream);
+    return rw_finish_bound(y_amax, 4 * work, stream);
   }
 #if W4_PSPLIT
   if (w4_point_split()) {
@@ -1649,7 +1583,7 @@ extern "C" int rw_conv_transpose_blur_weight_wino4h_absmax_f32(const float* w, c
   const int grid = rw_stream_grid(total, 256);
   hipLaunchKernelGGL(pack_up_wino36_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, k4, (float*)nullptr, out_ch, in_ch,
                      1.f, bound);
-  return w4h_finish(bound, grid, stream);
+  return rw_finish_bound(bound, grid, stream);
 }
 
 extern "C" int rw_pack_conv_transpose_blur_weight_wino4h_f32(const float* w, const float* k4, float* uf, int out_ch,
@@ -1680,20 +1614,13 @@ extern "C" int rw_conv3x3_wino4_to_rgb_supported(int out_ch, int in_ch, int h, i
 static int wino4_to_rgb_launch(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h, int w,
                                float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, bool h16,
                                float u_inv, const float* x_amax, rw_stream_t stream) {
-  RW_CHECK_ARG(x && uf && rgb && rgb->weight && rgb->style && rgb->out && batch > 0 && in_ch > 0 && out_ch > 0);
-  RW_CHECK_ARG(!ep || ((!ep->noise || ep->noise_w) && (!ep->act || ep->bias)));
+  RW_CHECK_ARG(x && uf && rw_rgb_ok(rgb) && batch > 0 && in_ch > 0 && out_ch > 0);
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
   if (!rw_conv3x3_wino4_to_rgb_supported(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
-  p.x = x; p.uf = uf; p.y = nullptr;
-  p.style = ep ? ep->style : nullptr; p.demod = ep ? ep->demod : nullptr; p.noise = ep ? ep->noise : nullptr;
-  p.noise_w = ep ? ep->noise_w : nullptr; p.bias = ep ? ep->bias : nullptr; p.act = ep ? ep->act : 0;
-  p.rgb_weight = rgb->weight; p.rgb_style = rgb->style; p.rgb_bias = rgb->bias; p.rgb_skip = rgb->skip;
-  p.rgb_out = rgb->out; p.rgb_scale = rgb->scale;
-  p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w; p.w_scale = w_scale;
-  p.x_amax = x_amax; p.u_inv = u_inv;
-  p.groups_x = w / 64;
-  p.groups_y = h / 8;
+  wino4_fill(p, x, uf, nullptr, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, nullptr);
+  rw_fill_rgb(p, rgb);
   p.gpw = wino4_gpw(p, batch, 1);
   const int64_t work = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw);
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;

@@ -7,13 +7,11 @@ must be float32 tensors on a HIP device (the _f16 / _f64 forms of the three L1 o
 float64); anything else raises (no CPU path).
 """
 import ctypes
-import os
-import math
 
 import torch
 
 from . import _lib
-from ._lib import ConvEpilogue, SolveProblem, check
+from ._lib import ConvEpilogue, RgbEpilogue, SolveProblem, check
 
 SQRT2 = 2 ** 0.5
 
@@ -237,10 +235,58 @@ def _epilogue(style=None, demod=None, noise=None, noise_w=None, bias=None, act=F
     return ep, keep
 
 
+def _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, out, x, out_ch):
+    """The ToRGB block of a convolution of x to out_ch channels that writes `out`: (RgbEpilogue, the tensors it
+    points at)."""
+    keep = [_dev(rgb_weight, 'rgb weight'), _dev(rgb_style, 'rgb style'), _opt(rgb_bias, 'rgb bias'),
+            _opt(rgb_skip, 'rgb skip'), out]
+    b, _, h, w = x.shape
+    if tuple(keep[0].shape) != (3, out_ch) or tuple(keep[1].shape) != (b, out_ch):
+        raise ValueError('rgb weight / style shapes')
+    if keep[3] is not None and tuple(keep[3].shape) != (b, 3, h, w):
+        raise ValueError('rgb skip shape')
+    return RgbEpilogue(*[_p(t).value for t in keep], float(rgb_scale)), keep
+
+
+def _packed(t, out_ch, in_ch, what, plain=None, split=None):
+    """(the packed weight t on the device, 1 / u_scale of a split -- f16 pair -- packing or None for the plain one): the
+    two are told apart by their size, `plain` / `split` being the rw_packed_*_elems entries of the two forms (None: there
+    is no such form) and `what` the pack function t must come from.  The scale of a split packing rides on the caller's
+    tensor (_u_inv), which is why it is read here, before t is replaced by its contiguous self."""
+    wp = _dev(t, 'packed weight')
+    if plain is not None and wp.numel() == plain(out_ch, in_ch):
+        return wp, None
+    if split is not None and wp.numel() == split(out_ch, in_ch):
+        return wp, _u_inv(t)
+    raise ValueError('packed weight does not come from %s(%d x %d)' % (what, out_ch, in_ch))
+
+
+def _k4(k4):
+    k4 = _dev(k4, 'blur kernel')
+    if tuple(k4.shape) != (4, 4):
+        raise ValueError('the blur kernel must be 4 x 4')
+    return k4
+
+
+def _post_scale(post_scale, batch, channels, named='out_ch'):
+    post_scale = _opt(post_scale, 'post scale')
+    if post_scale is not None and tuple(post_scale.shape) != (batch, channels):
+        raise ValueError('post_scale must be batch x %s' % named)
+    return post_scale
+
+
+def _supported(entry, doc):
+    """A shape predicate over the library's own rw_*_supported entry."""
+    def supported(out_ch, in_ch, height, width):
+        return bool(getattr(lib(), entry)(int(out_ch), int(in_ch), int(height), int(width)))
+    supported.__doc__ = '%s (%s).' % (doc, entry)
+    return supported
+
+
 def conv3x3(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None,
             act=False, impl=0):
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
+    wp = _dev(wp, 'packed weight')
     b, i, h, w = x.shape
     y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
@@ -259,31 +305,19 @@ def conv3x3_to_rgb(x, wp, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_
                    demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
     """The styled convolution with ToRGB fused into its epilogue: returns (fmap or None, rgb image)."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
-    rgb_weight = _dev(rgb_weight, 'rgb weight').contiguous()
-    rgb_style = _dev(rgb_style, 'rgb style').contiguous()
-    rgb_bias = _opt(rgb_bias, 'rgb bias')
-    rgb_skip = _opt(rgb_skip, 'rgb skip')
+    wp = _dev(wp, 'packed weight')
     b, i, h, w = x.shape
-    if tuple(rgb_weight.shape) != (3, out_ch) or tuple(rgb_style.shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    if rgb_skip is not None and tuple(rgb_skip.shape) != (b, 3, h, w):
-        raise ValueError('rgb skip shape')
+    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
+    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
     _check_packed(wp, out_ch, i, 0)
     y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype) if store_fmap else None
-    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    from ._lib import RgbEpilogue
-    re = RgbEpilogue(_p(rgb_weight).value, _p(rgb_style).value, _p(rgb_bias).value, _p(rgb_skip).value,
-                     _p(rgb).value, float(rgb_scale))
     check(lib().rw_conv3x3_to_rgb_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
                                       ctypes.byref(ep), ctypes.byref(re), _stream()))
     return y, rgb
 
 
-def wino_supported(out_ch, in_ch, height, width):
-    """Shapes the Winograd F(2x2,3x3) stride-1 convolution takes (rw_conv3x3_wino_supported)."""
-    return bool(lib().rw_conv3x3_wino_supported(int(out_ch), int(in_ch), int(height), int(width)))
+wino_supported = _supported('rw_conv3x3_wino_supported', 'Shapes the Winograd F(2x2,3x3) stride-1 convolution takes')
 
 
 def pack_conv_weight_wino(weight):
@@ -300,10 +334,8 @@ def pack_conv_weight_wino(weight):
 def conv3x3_wino(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False):
     """Stride-1 3x3 convolution by Winograd F(2x2,3x3) in fp32; same arguments and epilogue as conv3x3."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
     b, i, h, w = x.shape
-    if uf.numel() != lib().rw_packed_conv_weight_wino_elems(out_ch, i):
-        raise ValueError('packed weight does not come from pack_conv_weight_wino(%d x %d)' % (out_ch, i))
+    uf, _ = _packed(uf, out_ch, i, 'pack_conv_weight_wino', lib().rw_packed_conv_weight_wino_elems)
     y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     if style is not None and h == w and w in (4, 8):
         # whole 8^2 / 4^2 images per wave (several images per workgroup): the library takes exactly these maps already
@@ -316,9 +348,7 @@ def conv3x3_wino(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noi
     return y
 
 
-def wino4_supported(out_ch, in_ch, height, width):
-    """Shapes the Winograd F(4x4,3x3) stride-1 convolution takes (rw_conv3x3_wino4_supported)."""
-    return bool(lib().rw_conv3x3_wino4_supported(int(out_ch), int(in_ch), int(height), int(width)))
+wino4_supported = _supported('rw_conv3x3_wino4_supported', 'Shapes the Winograd F(4x4,3x3) stride-1 convolution takes')
 
 
 BOUND_LANES = 64                # RW_BOUND_LANES of include/rewriting_hip.h
@@ -410,15 +440,6 @@ def pack_conv_weight_wino4(weight, split=False):
     return uf
 
 
-def _wino4_split(uf, out_ch, in_ch, what='pack_conv_weight_wino4'):
-    """Is uf the split (f16 pair) packing?  Raises when it is neither packing of this shape."""
-    if uf.numel() == lib().rw_packed_conv_weight_wino4_elems(out_ch, in_ch):
-        return False
-    if uf.numel() == lib().rw_packed_conv_weight_wino4h_elems(out_ch, in_ch):
-        return True
-    raise ValueError('packed weight does not come from %s(%d x %d)' % (what, out_ch, in_ch))
-
-
 def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                   x_amax=None, y_amax=None):
     """Stride-1 3x3 convolution by Winograd F(4x4,3x3) (~1e-5 relative error per layer: the default of the
@@ -427,15 +448,15 @@ def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, no
     matrix pipe (exact f16 operand split, fp32 accumulation): x_amax = the bound of x (hip.absmax(x), or the y_amax its
     producer filled; measured here when None), y_amax = hip.new_bound(y.numel(), device), which receives the bound of y."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
     b, i, h, w = x.shape
-    split = _wino4_split(uf, out_ch, i)
+    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_weight_wino4', lib().rw_packed_conv_weight_wino4_elems,
+                        lib().rw_packed_conv_weight_wino4h_elems)
     y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    if split:
+    if u_inv is not None:
         x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
         check(lib().rw_conv3x3_wino4h_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                          _u_inv(packed), _p(x_amax), _p(y_amax), _stream()))
+                                          u_inv, _p(x_amax), _p(y_amax), _stream()))
         return y
     check(lib().rw_conv3x3_wino4_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
                                      _stream()))
@@ -446,32 +467,18 @@ def conv3x3_wino_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias,
                         demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
     """conv3x3_wino with ToRGB in the epilogue (out_ch == 32): returns (fmap or None, rgb image)."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
-    rgb_weight = _dev(rgb_weight, 'rgb weight').contiguous()
-    rgb_style = _dev(rgb_style, 'rgb style').contiguous()
-    rgb_bias = _opt(rgb_bias, 'rgb bias')
-    rgb_skip = _opt(rgb_skip, 'rgb skip')
     b, i, h, w = x.shape
-    if tuple(rgb_weight.shape) != (3, out_ch) or tuple(rgb_style.shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    if rgb_skip is not None and tuple(rgb_skip.shape) != (b, 3, h, w):
-        raise ValueError('rgb skip shape')
-    if uf.numel() != lib().rw_packed_conv_weight_wino_elems(out_ch, i):
-        raise ValueError('packed weight does not come from pack_conv_weight_wino(%d x %d)' % (out_ch, i))
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype) if store_fmap else None
     rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
+    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
+    uf, _ = _packed(uf, out_ch, i, 'pack_conv_weight_wino', lib().rw_packed_conv_weight_wino_elems)
+    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype) if store_fmap else None
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    from ._lib import RgbEpilogue
-    re = RgbEpilogue(_p(rgb_weight).value, _p(rgb_style).value, _p(rgb_bias).value, _p(rgb_skip).value,
-                     _p(rgb).value, float(rgb_scale))
     check(lib().rw_conv3x3_wino_to_rgb_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
                                            ctypes.byref(ep), ctypes.byref(re), _stream()))
     return y, rgb
 
 
-def wino4_to_rgb_supported(out_ch, in_ch, height, width):
-    """Shapes conv3x3_wino4_to_rgb takes (rw_conv3x3_wino4_to_rgb_supported: out_ch == 32)."""
-    return bool(lib().rw_conv3x3_wino4_to_rgb_supported(int(out_ch), int(in_ch), int(height), int(width)))
+wino4_to_rgb_supported = _supported('rw_conv3x3_wino4_to_rgb_supported', 'Shapes conv3x3_wino4_to_rgb takes: out_ch == 32')
 
 
 def conv3x3_wino4_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
@@ -479,26 +486,16 @@ def conv3x3_wino4_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias
     """conv3x3_wino4 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image); the feature map is not
     written.  Split weights and x_amax as in conv3x3_wino4."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
-    rgb_weight = _dev(rgb_weight, 'rgb weight').contiguous()
-    rgb_style = _dev(rgb_style, 'rgb style').contiguous()
-    rgb_bias = _opt(rgb_bias, 'rgb bias')
-    rgb_skip = _opt(rgb_skip, 'rgb skip')
     b, i, h, w = x.shape
-    if tuple(rgb_weight.shape) != (3, out_ch) or tuple(rgb_style.shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    if rgb_skip is not None and tuple(rgb_skip.shape) != (b, 3, h, w):
-        raise ValueError('rgb skip shape')
-    split = _wino4_split(uf, out_ch, i)
     rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
+    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
+    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_weight_wino4', lib().rw_packed_conv_weight_wino4_elems,
+                        lib().rw_packed_conv_weight_wino4h_elems)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    from ._lib import RgbEpilogue
-    re = RgbEpilogue(_p(rgb_weight).value, _p(rgb_style).value, _p(rgb_bias).value, _p(rgb_skip).value,
-                     _p(rgb).value, float(rgb_scale))
-    if split:
+    if u_inv is not None:
         x_amax = _amax_in(x, x_amax)
         check(lib().rw_conv3x3_wino4h_to_rgb_f32(_p(x), _p(uf), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                                 ctypes.byref(re), _u_inv(packed), _p(x_amax), _stream()))
+                                                 ctypes.byref(re), u_inv, _p(x_amax), _stream()))
         return None, rgb
     check(lib().rw_conv3x3_wino4_to_rgb_f32(_p(x), _p(uf), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
                                             ctypes.byref(re), _stream()))
@@ -550,7 +547,7 @@ def up_strips_applicable(out_ch, in_ch):
 
 def conv_transpose3x3s2(x, wp, out_ch, w_scale, style=None, demod=None, impl=0, out=None):
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
+    wp = _dev(wp, 'packed weight')
     b, i, h, w = x.shape
     y = out if out is not None else torch.empty(b, out_ch, 2 * h + 1, 2 * w + 1, device=x.device, dtype=x.dtype)
     if tuple(y.shape) != (b, out_ch, 2 * h + 1, 2 * w + 1) or not y.is_contiguous():
@@ -562,14 +559,10 @@ def conv_transpose3x3s2(x, wp, out_ch, w_scale, style=None, demod=None, impl=0, 
     return y
 
 
-def conv_transpose_wino_supported(out_ch, in_ch, height, width):
-    """Shapes the F(2,2) transposed convolution takes (rw_conv_transpose3x3s2_wino_supported)."""
-    return bool(lib().rw_conv_transpose3x3s2_wino_supported(int(out_ch), int(in_ch), int(height), int(width)))
+conv_transpose_wino_supported = _supported('rw_conv_transpose3x3s2_wino_supported', 'Shapes the F(2,2) transposed convolution takes')
 
 
-def conv_transpose_wino_split_supported(out_ch, in_ch, height, width):
-    """Shapes the split-operand (16-bit matrix pipe) form of conv_transpose3x3s2_wino takes."""
-    return bool(lib().rw_conv_transpose3x3s2_winoh_supported(int(out_ch), int(in_ch), int(height), int(width)))
+conv_transpose_wino_split_supported = _supported('rw_conv_transpose3x3s2_winoh_supported', 'Shapes the split-operand (16-bit matrix pipe) form of conv_transpose3x3s2_wino takes')
 
 
 def pack_conv_transpose_weight_wino(weight, split=False):
@@ -595,23 +588,19 @@ def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out
     pack_conv_transpose_weight_wino(split=True) the products run on the 16-bit matrix pipe (exact f16 operand split,
     fp32 accumulation; x_amax = the bound of x as in conv3x3_wino4, measured here when None)."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
     b, i, h, w = x.shape
-    if uf.numel() == lib().rw_packed_conv_transpose_wino_elems(out_ch, i):
-        split = False
-    elif uf.numel() == lib().rw_packed_conv_transpose_winoh_elems(out_ch, i):
-        split = True
-    else:
-        raise ValueError('packed weight does not come from pack_conv_transpose_weight_wino(%d x %d)' % (out_ch, i))
+    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_transpose_weight_wino',
+                        lib().rw_packed_conv_transpose_wino_elems,
+                        lib().rw_packed_conv_transpose_winoh_elems)
     y = out if out is not None else torch.empty(b, out_ch, 2 * h + 1, 2 * w + 1, device=x.device, dtype=x.dtype)
     if tuple(y.shape) != (b, out_ch, 2 * h + 1, 2 * w + 1) or not y.is_contiguous():
         raise ValueError('out has the wrong shape')
     style = _opt(style, 'style')
     demod = _opt(demod, 'demod')
-    if split:
+    if u_inv is not None:
         x_amax = _amax_in(x, x_amax)
         check(lib().rw_conv_transpose3x3s2_winoh_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                     _p(style), _p(demod), _u_inv(packed), _p(x_amax), _stream()))
+                                                     _p(style), _p(demod), u_inv, _p(x_amax), _stream()))
         return y
     if style is not None and h == w and w in (4, 8):
         # whole 8^2 / 4^2 images per wave (several images per workgroup): the library takes exactly these maps already
@@ -622,18 +611,14 @@ def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out
     return y
 
 
-def conv_transpose_blur_wino4_supported(out_ch, in_ch, height, width):
-    """Shapes the one-pass upsampling StyledConv takes (rw_conv_transpose_blur_wino4_supported)."""
-    return bool(lib().rw_conv_transpose_blur_wino4_supported(int(out_ch), int(in_ch), int(height), int(width)))
+conv_transpose_blur_wino4_supported = _supported('rw_conv_transpose_blur_wino4_supported', 'Shapes the one-pass upsampling StyledConv takes')
 
 
 def pack_conv_transpose_blur_weight_wino4(weight, k4, split=False):
     """F(4x4,3x3) weights of the four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4;
     split=True: as f16 pairs (pack_conv_weight_wino4)."""
     weight = _dev(weight, 'weight')
-    k4 = _dev(k4, 'blur kernel').contiguous()
-    if tuple(k4.shape) != (4, 4):
-        raise ValueError('the blur kernel must be 4 x 4')
+    k4 = _k4(k4)
     o, i = weight.shape[-4], weight.shape[-3]
     n = (lib().rw_packed_conv_transpose_blur_wino4h_elems if split
          else lib().rw_packed_conv_transpose_blur_wino4_elems)(o, i)
@@ -654,24 +639,17 @@ def conv_transpose3x3s2_blur_wino4(x, uf, out_ch, w_scale, style=None, demod=Non
     the four output-parity phases as virtual channels of the F(4x4,3x3) kernel (its error class: image generation).
     Split weights, x_amax and y_amax (max |y|, post_scale included) as in conv3x3_wino4."""
     x = _dev(x, 'fmap')
-    packed, uf = uf, _dev(uf, 'packed weight')      # (the scale of a split packing rides on the caller's tensor)
     b, i, h, w = x.shape
-    if uf.numel() == lib().rw_packed_conv_transpose_blur_wino4_elems(out_ch, i):
-        split = False
-    elif uf.numel() == lib().rw_packed_conv_transpose_blur_wino4h_elems(out_ch, i):
-        split = True
-    else:
-        raise ValueError('packed weight does not come from pack_conv_transpose_blur_weight_wino4(%d x %d)'
-                         % (out_ch, i))
+    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_transpose_blur_weight_wino4',
+                        lib().rw_packed_conv_transpose_blur_wino4_elems,
+                        lib().rw_packed_conv_transpose_blur_wino4h_elems)
     y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _opt(post_scale, 'post scale')
-    if post_scale is not None and tuple(post_scale.shape) != (b, out_ch):
-        raise ValueError('post_scale must be batch x out_ch')
-    if split:
+    post_scale = _post_scale(post_scale, b, out_ch)
+    if u_inv is not None:
         x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
         check(lib().rw_conv_transpose3x3s2_blur_wino4h_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                           ctypes.byref(ep), _p(post_scale), _u_inv(packed), _p(x_amax),
+                                                           ctypes.byref(ep), _p(post_scale), u_inv, _p(x_amax),
                                                            _p(y_amax), _stream()))
         return y
     check(lib().rw_conv_transpose3x3s2_blur_wino4_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
@@ -679,17 +657,13 @@ def conv_transpose3x3s2_blur_wino4(x, uf, out_ch, w_scale, style=None, demod=Non
     return y
 
 
-def dconv_supported(out_ch, in_ch, height, width):
-    """Shapes conv3x3_direct16 takes (rw_dconv3x3_supported)."""
-    return bool(lib().rw_dconv3x3_supported(int(out_ch), int(in_ch), int(height), int(width)))
+dconv_supported = _supported('rw_dconv3x3_supported', 'Shapes conv3x3_direct16 takes')
 
 
-def dconv_to_rgb_supported(out_ch, in_ch, height, width):
-    return bool(lib().rw_dconv3x3_to_rgb_supported(int(out_ch), int(in_ch), int(height), int(width)))
+dconv_to_rgb_supported = _supported('rw_dconv3x3_to_rgb_supported', 'Shapes conv3x3_direct16_to_rgb takes')
 
 
-def dconv_transpose_blur_supported(out_ch, in_ch, height, width):
-    return bool(lib().rw_dconv_transpose_blur_supported(int(out_ch), int(in_ch), int(height), int(width)))
+dconv_transpose_blur_supported = _supported('rw_dconv_transpose_blur_supported', 'Shapes conv_transpose3x3s2_blur_direct16 takes')
 
 
 def pack_conv_weight_direct16(weight):
@@ -706,24 +680,18 @@ def pack_conv_weight_direct16(weight):
     return wp
 
 
-def _direct16_check(wp, n, what):
-    if wp.numel() != n:
-        raise ValueError('packed weight does not come from %s' % what)
-
-
 def conv3x3_direct16(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                      x_amax=None, y_amax=None):
     """Stride-1 3x3 convolution as a direct sum on the 16-bit matrix pipe (exact f16 operand split, fp32 accumulation:
     rw_dconv3x3_f32); arguments, epilogue, x_amax and y_amax as conv3x3_wino4 with split weights."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
     b, i, h, w = x.shape
-    _direct16_check(wp, lib().rw_packed_dconv_weight_elems(out_ch, i), 'pack_conv_weight_direct16(%d x %d)' % (out_ch, i))
+    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
     y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
     x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
     check(lib().rw_dconv3x3_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                _u_inv(packed), _p(x_amax), _p(y_amax), _stream()))
+                                u_inv, _p(x_amax), _p(y_amax), _stream()))
     return y
 
 
@@ -732,24 +700,18 @@ def conv3x3_direct16_rgb_partial(x, wp, out_ch, w_scale, rgb_weight, rgb_style, 
     """conv3x3_direct16 that also leaves the channel sums of the ToRGB which reads its result (rw_dconv3x3_rgb_partial_f32):
     returns (feature map, partial images (out_ch / 32, B, 3, H, W)); rgb_combine() turns the partials into the image."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
-    rgb_weight = _dev(rgb_weight, 'rgb weight').contiguous()
-    rgb_style = _dev(rgb_style, 'rgb style').contiguous()
     b, i, h, w = x.shape
-    if tuple(rgb_weight.shape) != (3, out_ch) or tuple(rgb_style.shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    _direct16_check(wp, lib().rw_packed_dconv_weight_elems(out_ch, i), 'pack_conv_weight_direct16(%d x %d)' % (out_ch, i))
     n_part = lib().rw_dconv3x3_rgb_partials(out_ch)
     if n_part <= 0:
         raise ValueError('no ToRGB partial sums for %d out-channels' % out_ch)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     part = torch.empty(n_part, b, 3, h, w, device=x.device, dtype=x.dtype)
+    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, None, None, rgb_scale, part, x, out_ch)
+    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
+    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    from ._lib import RgbEpilogue
-    re = RgbEpilogue(_p(rgb_weight).value, _p(rgb_style).value, None, None, _p(part).value, float(rgb_scale))
     x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
     check(lib().rw_dconv3x3_rgb_partial_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                            ctypes.byref(re), _u_inv(packed), _p(x_amax), _p(y_amax), _stream()))
+                                            ctypes.byref(re), u_inv, _p(x_amax), _p(y_amax), _stream()))
     return y, part
 
 
@@ -770,25 +732,14 @@ def conv3x3_direct16_to_rgb(x, wp, out_ch, w_scale, rgb_weight, rgb_style, rgb_b
                             demod=None, noise=None, noise_w=None, bias=None, act=False, x_amax=None):
     """conv3x3_direct16 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image)."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
-    rgb_weight = _dev(rgb_weight, 'rgb weight').contiguous()
-    rgb_style = _dev(rgb_style, 'rgb style').contiguous()
-    rgb_bias = _opt(rgb_bias, 'rgb bias')
-    rgb_skip = _opt(rgb_skip, 'rgb skip')
     b, i, h, w = x.shape
-    if tuple(rgb_weight.shape) != (3, out_ch) or tuple(rgb_style.shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    if rgb_skip is not None and tuple(rgb_skip.shape) != (b, 3, h, w):
-        raise ValueError('rgb skip shape')
-    _direct16_check(wp, lib().rw_packed_dconv_weight_elems(out_ch, i), 'pack_conv_weight_direct16(%d x %d)' % (out_ch, i))
     rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
+    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
+    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    from ._lib import RgbEpilogue
-    re = RgbEpilogue(_p(rgb_weight).value, _p(rgb_style).value, _p(rgb_bias).value, _p(rgb_skip).value,
-                     _p(rgb).value, float(rgb_scale))
     x_amax = _amax_in(x, x_amax)
     check(lib().rw_dconv3x3_to_rgb_f32(_p(x), _p(wp), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                       ctypes.byref(re), _u_inv(packed), _p(x_amax), _stream()))
+                                       ctypes.byref(re), u_inv, _p(x_amax), _stream()))
     return None, rgb
 
 
@@ -796,9 +747,7 @@ def pack_conv_transpose_blur_weight_direct16(weight, k4):
     """The four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4, as f16 pairs in the operand
     order of the direct kernel (rw_pack_dconv_transpose_blur_weight_f32)."""
     weight = _dev(weight, 'weight')
-    k4 = _dev(k4, 'blur kernel').contiguous()
-    if tuple(k4.shape) != (4, 4):
-        raise ValueError('the blur kernel must be 4 x 4')
+    k4 = _k4(k4)
     o, i = weight.shape[-4], weight.shape[-3]
     n = lib().rw_packed_dconv_transpose_blur_weight_elems(o, i)
     if n <= 0:
@@ -814,25 +763,20 @@ def conv_transpose3x3s2_blur_direct16(x, wp, out_ch, w_scale, style=None, demod=
     """conv_transpose3x3s2 -> blur(pad 1,1) -> noise -> bias + leaky ReLU in one pass as a direct sum on the 16-bit matrix
     pipe: (B,Cin,H,W) -> (B,Cout,2H,2W); arguments as conv_transpose3x3s2_blur_wino4 with split weights."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
     b, i, h, w = x.shape
-    _direct16_check(wp, lib().rw_packed_dconv_transpose_blur_weight_elems(out_ch, i),
-                    'pack_conv_transpose_blur_weight_direct16(%d x %d)' % (out_ch, i))
+    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_transpose_blur_weight_direct16',
+                        split=lib().rw_packed_dconv_transpose_blur_weight_elems)
     y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _opt(post_scale, 'post scale')
-    if post_scale is not None and tuple(post_scale.shape) != (b, out_ch):
-        raise ValueError('post_scale must be batch x out_ch')
+    post_scale = _post_scale(post_scale, b, out_ch)
     x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
     check(lib().rw_dconv_transpose3x3s2_blur_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                 ctypes.byref(ep), _p(post_scale), _u_inv(packed), _p(x_amax), _p(y_amax),
+                                                 ctypes.byref(ep), _p(post_scale), u_inv, _p(x_amax), _p(y_amax),
                                                  _stream()))
     return y
 
 
-def tconv_blur_supported(out_ch, in_ch, height, width):
-    """Shapes conv_transpose3x3s2_blur_fused takes (rw_tconv_blur_supported)."""
-    return bool(lib().rw_tconv_blur_supported(int(out_ch), int(in_ch), int(height), int(width)))
+tconv_blur_supported = _supported('rw_tconv_blur_supported', 'Shapes conv_transpose3x3s2_blur_fused takes')
 
 
 def conv_transpose3x3s2_blur_fused(x, wp, k4, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None,
@@ -843,20 +787,15 @@ def conv_transpose3x3s2_blur_fused(x, wp, k4, out_ch, w_scale, style=None, demod
     the layer's weight (the plain packing: nothing is composed with the blur), k4 the 4x4 FIR; the other arguments as
     conv_transpose3x3s2_blur_direct16."""
     x = _dev(x, 'fmap')
-    packed, wp = wp, _dev(wp, 'packed weight')
-    k4 = _dev(k4, 'blur kernel').contiguous()
-    if tuple(k4.shape) != (4, 4):
-        raise ValueError('the blur kernel must be 4 x 4')
+    k4 = _k4(k4)
     b, i, h, w = x.shape
-    _direct16_check(wp, lib().rw_packed_dconv_weight_elems(out_ch, i), 'pack_conv_weight_direct16(%d x %d)' % (out_ch, i))
+    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
     y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
     ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _opt(post_scale, 'post scale')
-    if post_scale is not None and tuple(post_scale.shape) != (b, out_ch):
-        raise ValueError('post_scale must be batch x out_ch')
+    post_scale = _post_scale(post_scale, b, out_ch)
     x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
     check(lib().rw_tconv_blur_f32(_p(x), _p(wp), _p(k4), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                  _p(post_scale), _u_inv(packed), _p(x_amax), _p(y_amax), _stream()))
+                                  _p(post_scale), u_inv, _p(x_amax), _p(y_amax), _stream()))
     return y
 
 
@@ -881,9 +820,7 @@ def blur_noise_act(x, k4, noise, noise_w, bias, post_scale=None, y_amax=None):
     bias = _opt(bias, 'bias')
     b, c, ih, iw = x.shape
     y = torch.empty(b, c, ih - 1, iw - 1, device=x.device, dtype=x.dtype)
-    post_scale = _opt(post_scale, 'post scale')
-    if post_scale is not None and tuple(post_scale.shape) != (b, c):
-        raise ValueError('post_scale must be batch x channels')
+    post_scale = _post_scale(post_scale, b, c, 'channels')
     y_amax = _amax_out(y_amax, y.numel())
     check(lib().rw_blur_noise_act_amax_f32(_p(x), _p(k4), _p(noise), _p(noise_w), _p(bias), _p(post_scale), _p(y),
                                            b, c, ih - 1, iw - 1, _p(y_amax), _stream()))
