@@ -32,7 +32,10 @@ typedef void* rw_stream_t; /* hipStream_t */
 #define RW_ERR_BAD_ARGUMENT 10001
 #define RW_ERR_UNSUPPORTED  10002
 
-/* 7 since round 5: the split-operand ("H16") entry points take their bounds as RW_BOUND_LANES-float vectors written
+/* 10: the _f64 forward entries (rw_pixel_norm_f64 ... rw_conv_transpose3x3s2_f64, the last section of this header): a
+ * library without them is refused by the loader as stale, not at the first missing symbol.  9: rw_dconv3x3_rgb_partial_f32 /
+ * rw_rgb_combine_f32; 8: rw_tconv_blur_*.  7 since round 5: the split-operand ("H16") entry points take their bounds as
+ * RW_BOUND_LANES-float vectors written
  * by plain stores (no memset, no atomic, no device scalar that one launch raises and the next reads) and their weight
  * scale BY VALUE (rw_split_weight_scale); rw_publish_scalar_f32 is gone.  (3: rw_solve_run_*, the whole-image 8x8 / 4x4
  * shapes, the point order of the packed F(4x4,3x3) weights; 4: rw_*_wino4h_*; 5: rw_dconv*; 6: rw_publish_scalar_f32.)
@@ -54,12 +57,17 @@ const char* rw_error_string(int code);
  *     order, and is rounded to half ONCE, at the store: an _f16 result equals the _f32 entry run on the widened inputs,
  *     then rounded (round to nearest even).  bias_grad sums in float, as torch.sum does for half.  This differs from
  *     the reference's half path, which rounds after every operation and rounds alpha and scale to half.
+ * The generator's forward has a float64 form as well: the _f64 entries of the last section of this header (pixel norm,
+ * equalised linear, latent adjustment, style multiply, demodulation factors, the two 3x3 convolutions, noise, ToRGB)
+ * take `double` buffers and `double` scalars and compute and accumulate in double, so that a model cast with .double()
+ * runs its whole forward on the device, module by module.  That form is forward only: no fused epilogues, no packed
+ * weights, no gradients, no solver.
  * Every other entry of this library is fp32 ONLY: it takes `float` pointers -- the path it accelerates runs in fp32 end
- * to end (BASELINE.json: "images within 1e-3 L-inf fp32").  A model cast with .double() or .half() does not reach those
- * entries: the Python wrappers (rewriting_amd/hip.py) refuse any other dtype with an error that names this limit (the
- * status of the refusal is RW_ERR_UNSUPPORTED: nothing was launched), they never convert silently.  The ctypes stub
- * of INTEGRATION.md dispatches on the input's dtype to the three forms above and refuses any other dtype, or an
- * operand of another dtype, before anything is launched.
+ * to end (BASELINE.json: "images within 1e-3 L-inf fp32").  A .half() model does not reach those entries, and neither
+ * does a double tensor handed to an fp32 wrapper: the Python wrappers (rewriting_amd/hip.py) refuse any other dtype with
+ * an error that names this limit (the status of the refusal is RW_ERR_UNSUPPORTED: nothing was launched), they never
+ * convert silently.  The ctypes stub of INTEGRATION.md dispatches on the input's dtype to the three forms above and
+ * refuses any other dtype, or an operand of another dtype, before anything is launched.
  * ------------------------------------------------------------------------------------- */
 
 /* fused_bias_act(input, bias, refer, act, grad, alpha, scale)
@@ -603,6 +611,62 @@ int rw_conv_wgrad_f32(const float* g, const float* x, const float* gscale, const
                       rw_stream_t stream);
 /* out[r] = sum_j a[r][j] * b[r][j] for `rows` rows of length n (per-(image, channel) sums over a feature map) */
 int rw_rowdot_f32(const float* a, const float* b, float* out, long long rows, long long n, rw_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Generator forward in float64 -- the reference's generator runs after .double(): its two native ops dispatch double
+ * (above) and everything else is torch.  These entries are the double forms of that torch arithmetic: every pointer is a
+ * DEVICE pointer to contiguous float64, every scalar a double, every product and accumulation is in double.  The _f64
+ * twins take the arguments of their _f32 entries.  Forward only, one module per launch.
+ * ------------------------------------------------------------------------------------- */
+
+/* PixelNormL: y = x * rsqrt(mean(x^2, dim=1) + eps)      (models.py:609-614) */
+int rw_pixel_norm_f64(const double* x, double* y, int batch, int dim, double eps, rw_stream_t stream);
+
+/* EqualLinear.forward (models.py:503-511), as rw_equal_linear_f32; any in_dim. */
+int rw_equal_linear_f64(const double* x, const double* w, const double* bias, double* y,
+                        int batch, int in_dim, int out_dim, int64_t x_stride,
+                        double w_scale, double b_scale, int act, double alpha, double act_scale,
+                        rw_stream_t stream);
+
+/* AdjustLatent (models.py:570-583), as rw_adjust_latent_f32; avg nullable. */
+int rw_adjust_latent_f64(const double* w, const double* avg, double* out, int batch, int n_latent,
+                         int dim, double psi, rw_stream_t stream);
+
+/* ApplyStyle (models.py:616-620): y[b][c][p] = style[b][c] * x[b][c][p]. */
+int rw_style_mul_f64(const double* x, const double* style, double* y, int batch, int channels,
+                     int64_t hw, rw_stream_t stream);
+
+/* wsq[o][i] = sum_{ky,kx} (w_scale * W[o][i][ky][kx])^2 and demod[b][o] = rsqrt(sum_i style[b][i]^2 * wsq[o][i] + eps)
+ * -- the demodulation factor of DemodulatedConv2dF.forward (models.py:320-328). */
+int rw_weight_sqsum_f64(const double* w, double* wsq, int out_ch, int in_ch, int taps, double w_scale,
+                        rw_stream_t stream);
+int rw_demod_f64(const double* wsq, const double* style, double* demod, int batch, int out_ch,
+                 int in_ch, double eps, rw_stream_t stream);
+
+/* F.conv2d(x * style, w_scale * W, padding=1) * demod                    (models.py:318-319,328)
+ * F.conv_transpose2d(x * style, w_scale * W^T, stride=2) * demod         (models.py:315-316,328)
+ * x (B,Cin,H,W) -> y (B,Cout,H,W) / (B,Cout,2H+1,2W+1).  w is the parameter AS STORED, (out_ch, in_ch, 3, 3): nothing is
+ * packed.  style (B,Cin) nullable: multiplied into x while it is loaded (ApplyStyle, models.py:616-620); demod (B,Cout)
+ * nullable.  No noise / bias / activation epilogue and no impl argument: the double path runs module by module.
+ * Every shape is taken: in_ch % 4 == 0 and out_ch % 16 == 0 run as an implicit GEMM on v_mfma_f64_16x16x4_f64 (the input
+ * window staged in LDS, edges masked), any other shape as one thread per output element.  RW_ERR_UNSUPPORTED where one
+ * image's input or output maps, or the weight, have 2^31 elements or more. */
+int rw_conv3x3_f64(const double* x, const double* w, double* y, int batch, int in_ch, int out_ch,
+                   int h, int w_in, double w_scale, const double* style, const double* demod,
+                   rw_stream_t stream);
+int rw_conv_transpose3x3s2_f64(const double* x, const double* w, double* y, int batch, int in_ch,
+                               int out_ch, int h, int w_in, double w_scale, const double* style,
+                               const double* demod, rw_stream_t stream);
+
+/* NoiseInjectionF (models.py:535-546): y[b][c][p] = x[b][c][p] + noise_w[0] * noise[b][p]; the reference's float32 noise
+ * rows are widened by the caller (torch's promotion, models.py:539-546). */
+int rw_noise_add_f64(const double* x, const double* noise, const double* noise_w, double* y,
+                     int batch, int channels, int64_t hw, rw_stream_t stream);
+
+/* ToRGBF (models.py:628-655), as rw_to_rgb_f32; in_ch <= 2048. */
+int rw_to_rgb_f64(const double* x, const double* w, const double* style, const double* bias,
+                  const double* skip, double* y, int batch, int in_ch, int64_t hw, double w_scale,
+                  rw_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RW_HIP_LIB') or os.path.join(_HERE, 'librewriting_hip.so')    # RW_HIP_LIB: tuning builds
 
-ABI_VERSION = 9        # 9: rw_dconv3x3_rgb_partial_f32 / rw_rgb_combine_f32 (ToRGB sums left by the producing convolution); 8: rw_tconv_blur_* (fused transposed conv + blur); 7: bounds as RW_BOUND_LANES-float vectors written by plain stores, weight scales by value (rw_split_weight_scale, rw_*_absmax_f32), no rw_publish_scalar_f32; 6: rw_publish_scalar_f32; 5: rw_dconv* (direct sums on the 16-bit pipe); 4: rw_*_wino4h_* (operands split into f16 pairs), rw_absmax_f32; 3: rw_solve_run_*, the 8x8 / 4x4 shapes (style == NULL), packed F(4x4,3x3) point order w4_nat; 2: rw_solve_supported 1/0, sizes[6]
+ABI_VERSION = 10       # 10: the _f64 forward entries (rw_pixel_norm_f64 ... rw_conv_transpose3x3s2_f64); 9: rw_dconv3x3_rgb_partial_f32 / rw_rgb_combine_f32 (ToRGB sums left by the producing convolution); 8: rw_tconv_blur_* (fused transposed conv + blur); 7: bounds as RW_BOUND_LANES-float vectors written by plain stores, weight scales by value (rw_split_weight_scale, rw_*_absmax_f32), no rw_publish_scalar_f32; 6: rw_publish_scalar_f32; 5: rw_dconv* (direct sums on the 16-bit pipe); 4: rw_*_wino4h_* (operands split into f16 pairs), rw_absmax_f32; 3: rw_solve_run_*, the 8x8 / 4x4 shapes (style == NULL), packed F(4x4,3x3) point order w4_nat; 2: rw_solve_supported 1/0, sizes[6]
 
 
 class ConvEpilogue(Structure):
@@ -180,6 +180,23 @@ SIGNATURES = {
     'rw_conv_wgrad_ksplit': (c_int, [c_int] * 6),
     'rw_conv_wgrad_f32': (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float, c_void_p]),
     'rw_rowdot_f32': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
+    # the float64 forward: the _f32 twin's arguments, double buffers and double scalars
+    'rw_pixel_norm_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
+    'rw_equal_linear_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int64, c_double, c_double, c_int, c_double, c_double, c_void_p]),
+    'rw_adjust_latent_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                     c_void_p]),
+    'rw_style_mul_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    'rw_weight_sqsum_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p]),
+    'rw_demod_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p]),
+    'rw_conv3x3_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double,
+                               c_void_p, c_void_p, c_void_p]),
+    'rw_conv_transpose3x3s2_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                           c_double, c_void_p, c_void_p, c_void_p]),
+    'rw_noise_add_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
+                                 c_void_p]),
+    'rw_to_rgb_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                              c_int, c_int64, c_double, c_void_p]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ PyTorch is used here for device memory and streams only: every wrapper allocates
 with torch, passes ``data_ptr()`` and ``torch.cuda.current_stream().cuda_stream`` to the
 library and returns the torch tensor -- the ownership rule of SURVEY.md section 8b.  Inputs
 must be float32 tensors on a HIP device (the _f16 / _f64 forms of the three L1 ops: float16 /
-float64); anything else raises (no CPU path).
+float64; the _f64 wrappers of the generator's forward at the end of this file: float64); anything
+else raises (no CPU path).
 """
 import ctypes
 
@@ -978,3 +979,144 @@ def rowdot(a, b):
 
 
 __all__ = [n for n in dir() if not n.startswith('_')] + ['SolveProblem', 'ConvEpilogue']
+
+
+# ------------------------------------------------------------------ the float64 forward
+# The generator's forward in double (include/rewriting_hip.h, last section): the same pieces as above on float64
+# tensors, module by module -- no packed weights, no epilogues, no routes.  Every tensor operand must be float64
+# (nothing is converted); the fp32 wrappers above keep refusing it.
+_F64 = torch.float64
+
+
+def _d64(t, name):
+    return _dev(t, name, _F64)
+
+
+def _opt64(t, name):
+    return None if t is None else _dev(t, name, _F64)
+
+
+def pixel_norm_f64(x, eps=1e-8):
+    x = _d64(x, 'latent')
+    y = torch.empty_like(x)
+    check(lib().rw_pixel_norm_f64(_p(x), _p(y), x.shape[0], x.shape[1], float(eps), _stream()))
+    return y
+
+
+def equal_linear_f64(x, weight, bias, w_scale, b_scale, act=False, alpha=0.2, act_scale=SQRT2):
+    """x may be a strided row view (latent[:, index]): last dim contiguous."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != _F64:
+        _d64(x, 'input')
+    x = x.detach()
+    if x.ndim != 2 or x.stride(1) != 1:
+        x = x.reshape(x.shape[0], -1).contiguous()
+    weight = _d64(weight, 'weight')
+    bias = _opt64(bias, 'bias')
+    batch, in_dim = x.shape
+    out_dim = weight.shape[0]
+    if weight.shape[1] != in_dim:
+        raise ValueError('weight is %s, the input has %d features' % (tuple(weight.shape), in_dim))
+    y = torch.empty(batch, out_dim, device=x.device, dtype=_F64)
+    x_stride = x.stride(0) if batch > 1 else in_dim
+    check(lib().rw_equal_linear_f64(_p(x), _p(weight), _p(bias), _p(y), batch, in_dim, out_dim,
+                                    max(x_stride, in_dim), float(w_scale), float(b_scale), int(bool(act)),
+                                    float(alpha), float(act_scale), _stream()))
+    return y
+
+
+def adjust_latent_f64(w, avg, n_latent, psi):
+    w = _d64(w, 'latent')
+    avg = _opt64(avg, 'latent_avg')
+    out = torch.empty(w.shape[0], n_latent, w.shape[1], device=w.device, dtype=_F64)
+    check(lib().rw_adjust_latent_f64(_p(w), _p(avg), _p(out), w.shape[0], n_latent, w.shape[1], float(psi), _stream()))
+    return out
+
+
+def style_mul_f64(x, style):
+    x = _d64(x, 'fmap')
+    style = _d64(style, 'style')
+    b, c, h, w = x.shape
+    if tuple(style.shape) != (b, c):
+        raise ValueError('style must be batch x channels')
+    y = torch.empty_like(x)
+    check(lib().rw_style_mul_f64(_p(x), _p(style), _p(y), b, c, h * w, _stream()))
+    return y
+
+
+def weight_sqsum_f64(weight, w_scale):
+    weight = _d64(weight, 'weight')
+    o, i = weight.shape[-4], weight.shape[-3]
+    taps = weight.shape[-1] * weight.shape[-2]
+    wsq = torch.empty(o, i, device=weight.device, dtype=_F64)
+    check(lib().rw_weight_sqsum_f64(_p(weight), _p(wsq), o, i, taps, float(w_scale), _stream()))
+    return wsq
+
+
+def demod_f64(wsq, style, eps=1e-8):
+    wsq = _d64(wsq, 'wsq')
+    style = _d64(style, 'style')
+    b = style.shape[0]
+    o, i = wsq.shape
+    if style.shape[1] != i:
+        raise ValueError('style must be batch x in_ch')
+    out = torch.empty(b, o, device=wsq.device, dtype=_F64)
+    check(lib().rw_demod_f64(_p(wsq), _p(style), _p(out), b, o, i, float(eps), _stream()))
+    return out
+
+
+def _conv_f64(entry, up, x, weight, w_scale, style, demod):
+    x = _d64(x, 'fmap')
+    weight = _d64(weight, 'weight')
+    style = _opt64(style, 'style')
+    demod = _opt64(demod, 'demod')
+    b, i, h, w = x.shape
+    o = weight.shape[-4]
+    if tuple(weight.shape[-4:]) != (o, i, 3, 3) or weight.numel() != o * i * 9:
+        raise ValueError('weight must be (out_ch, %d, 3, 3) as stored, it is %s' % (i, tuple(weight.shape)))
+    if style is not None and tuple(style.shape) != (b, i):
+        raise ValueError('style must be batch x in_ch')
+    if demod is not None and tuple(demod.shape) != (b, o):
+        raise ValueError('demod must be batch x out_ch')
+    y = torch.empty((b, o, 2 * h + 1, 2 * w + 1) if up else (b, o, h, w), device=x.device, dtype=_F64)
+    check(getattr(lib(), entry)(_p(x), _p(weight), _p(y), b, i, o, h, w, float(w_scale), _p(style), _p(demod),
+                                _stream()))
+    return y
+
+
+def conv3x3_f64(x, weight, w_scale, style=None, demod=None):
+    """F.conv2d(x * style, w_scale * weight, padding=1) * demod in double; weight (out_ch, in_ch, 3, 3) as stored."""
+    return _conv_f64('rw_conv3x3_f64', False, x, weight, w_scale, style, demod)
+
+
+def conv_transpose3x3s2_f64(x, weight, w_scale, style=None, demod=None):
+    """F.conv_transpose2d(x * style, w_scale * weight^T, stride=2) * demod in double, to (2H+1) x (2W+1)."""
+    return _conv_f64('rw_conv_transpose3x3s2_f64', True, x, weight, w_scale, style, demod)
+
+
+def noise_add_f64(x, noise, noise_w):
+    x = _d64(x, 'fmap')
+    noise = _d64(noise, 'noise')
+    noise_w = _d64(noise_w, 'noise weight')
+    b, c, h, w = x.shape
+    if noise.numel() != b * h * w:
+        raise ValueError('noise must be batch x (height * width)')
+    y = torch.empty_like(x)
+    check(lib().rw_noise_add_f64(_p(x), _p(noise), _p(noise_w), _p(y), b, c, h * w, _stream()))
+    return y
+
+
+def to_rgb_f64(x, weight, style, bias, skip, w_scale):
+    x = _d64(x, 'fmap')
+    weight = _d64(weight, 'rgb weight')
+    style = _d64(style, 'style')
+    bias = _opt64(bias, 'bias')
+    skip = _opt64(skip, 'skip')
+    b, c, h, w = x.shape
+    if weight.numel() != 3 * c or tuple(style.shape) != (b, c):
+        raise ValueError('rgb weight / style shapes')
+    if skip is not None and tuple(skip.shape) != (b, 3, h, w):
+        raise ValueError('skip shape')
+    y = torch.empty(b, 3, h, w, device=x.device, dtype=_F64)
+    check(lib().rw_to_rgb_f64(_p(x), _p(weight), _p(style), _p(bias), _p(skip), _p(y), b, c, h * w, float(w_scale),
+                              _stream()))
+    return y

@@ -43,6 +43,10 @@ class ProgressiveGanRewriter(object):
                  tight_paste=True,           # optimise over the pasted crop, not the whole map
                  alpha_area=True,            # composite with the painted area, not its bounding box
                  key_method='zca'):          # or 'svd', 'mean', 'gandissect'
+        if next(model.parameters()).dtype == torch.float64:
+            raise RuntimeError('rewriting_amd: the rewriters (key statistics, solver, adjoints) are float32 only and the model '
+                               'is torch.float64 -- the double path is the generator\'s forward alone; rewrite a .float() '
+                               'copy of the model (nothing is converted)')
         self.firstlayer, self.lastlayer = self.maplayers(layernum)
         self.cachedir = cachedir
         self.tight_paste = tight_paste

@@ -10,6 +10,11 @@ What differs is underneath: every leaf calls a hand-written gfx950 kernel throug
 runs as ONE fused block (style multiply folded into the implicit-GEMM gather; demodulation,
 noise, bias and leaky-ReLU in its epilogue) -- invisible at the module boundaries the
 rewriter observes, because any hook or split turns the fusion off for that block.
+
+A model cast with ``.double()`` runs its forward on the float64 kernels (``hip.*_f64``): every module dispatches on the
+dtype of the tensor it is given, before any routing or fusion logic.  float32 takes the path described above; float64
+runs module by module (no fusion, no side streams, no packed weights), forward only: under grad mode a double layer
+that would have to record a graph raises, and the rewriters refuse a double model.
 """
 import contextlib
 import math
@@ -58,35 +63,39 @@ class _DerivedWeights:
 _noise_streams = {}
 
 
-def reference_noise(batch, hw, device):
+def reference_noise(batch, hw, device, double=False):
     """The reference regenerates ``np.random.RandomState(0).randn(batch, H*W)`` on the host for
     every noise layer of every call (utils/stylegan2/models.py:542-545; quirk Q1).  That is a
-    fixed stream prefix, so it is generated once and kept on the device."""
+    fixed stream prefix, so it is generated once and kept on the device.  double: the same float32
+    rows widened to float64, as torch's promotion widens them when the feature map is double
+    (models.py:539-546) -- a stream of its own, widened on the host."""
     need = batch * hw
-    key = str(device)
+    key = (str(device), 'f64') if double else str(device)
     stream = _noise_streams.get(key)
     if stream is None or stream.numel() < need:
         n = max(need, 1 << 16)
         host = np.random.RandomState(0).randn(n).astype('float32')
+        if double:
+            host = host.astype('float64')
         stream = torch.from_numpy(host).to(device)
         _noise_streams[key] = stream
     period = _noise_period[0]
     if period == 1 and batch > 1:
-        return reference_noise_row0(hw, device).expand(batch, hw)
+        return reference_noise_row0(hw, device, double).expand(batch, hw)
     if period and batch > period:
         # Several reference-sized batches run as one launch: image j takes the noise row it would have
         # had in its own batch of `period` (row j mod period), see noise_batch_period().
         if batch % period:
             raise ValueError('batch %d is not a multiple of the noise period %d' % (batch, period))
-        rows = reference_noise(period, hw, device)
+        rows = reference_noise(period, hw, device, double)
         return rows.repeat(batch // period, 1)
     return stream[:need].view(batch, hw)
 
 
-def reference_noise_row0(hw, device):
+def reference_noise_row0(hw, device, double=False):
     _noise_period[0], saved = 0, _noise_period[0]
     try:
-        return reference_noise(1, hw, device)
+        return reference_noise(1, hw, device, double)
     finally:
         _noise_period[0] = saved
 
@@ -117,6 +126,32 @@ def make_kernel(k):
     if k.ndim == 1:
         k = torch.outer(k, k)
     return k / k.sum()
+
+
+_F64 = torch.float64
+
+
+def _double(what, x, **operands):
+    """The dtype dispatch of a module: True when it runs on the float64 kernels (hip.*_f64), False for today's float32
+    path (which also refuses every other dtype, in rewriting_amd.hip).  `x` is the incoming tensor, `operands` the
+    module's own tensors (None = absent): if any of them is float64 all must be -- otherwise RuntimeError, naming
+    both dtypes, before anything is launched."""
+    if x.dtype is not _F64 and all(t is None or t.dtype is not _F64 for t in operands.values()):
+        return False
+    for name, t in operands.items():
+        if t is not None and t.dtype != x.dtype:
+            raise RuntimeError('rewriting_amd: %s: the input is %s and the %s %s -- cast the model and its input to one '
+                               'dtype, .float() or .double() (nothing is converted)' % (what, x.dtype, name, t.dtype))
+    return True
+
+
+def _forward_only_f64(what, *tensors):
+    """The float64 path is forward only (grad.py, the adjoints of the styled convolution, is float32): a double layer
+    that would have to record a graph raises instead of returning a result without one."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError('rewriting_amd: %s: the float64 path is forward only -- no graph is recorded for double '
+                                  'tensors (the adjoints in utils/stylegan2/grad.py are float32); run it under '
+                                  'torch.no_grad(), or differentiate a .float() model' % what)
 
 
 def _unhooked(*modules):
@@ -280,6 +315,8 @@ class ReturnOutput(nn.Module):
 
 class PixelNormL(nn.Module):
     def forward(self, d):
+        if d.latent.dtype is _F64:
+            return DataBag(d, latent=hip.pixel_norm_f64(d.latent))
         return DataBag(d, latent=hip.pixel_norm(d.latent))
 
 
@@ -299,6 +336,9 @@ class EqualLinear(nn.Linear):
             nn.init.constant_(self.bias, self.bias_init)
 
     def forward(self, input):
+        if _double('EqualLinear', input, weight=self.weight, bias=self.bias):
+            return hip.equal_linear_f64(input, self.weight, self.bias, self.scale, self.lr_mul,
+                                        act=bool(self.activation))
         return hip.equal_linear(input, self.weight, self.bias, self.scale, self.lr_mul,
                                 act=bool(self.activation))
 
@@ -329,8 +369,11 @@ class AdjustLatent(nn.Module):
 
     def forward(self, d):
         truncate = self.truncation != 1.0 and self.latent_avg.ndim > 0
-        lat = hip.adjust_latent(d.latent, self.latent_avg if truncate else None, self.n_latent,
-                                self.truncation)
+        adjust = hip.adjust_latent
+        if _double('AdjustLatent', d.latent, latent_avg=self.latent_avg if truncate else None):
+            adjust = hip.adjust_latent_f64
+        lat = adjust(d.latent, self.latent_avg if truncate else None, self.n_latent,
+                     self.truncation)
         return DataBag(d, latent=lat)
 
 
@@ -385,6 +428,9 @@ class ApplyStyle(nn.Module):
     """fmap * style -- its output is the rewriter's key (rewrite/ganrewrite.py:662-665)."""
 
     def forward(self, d):
+        if _double('ApplyStyle', d.fmap, style=d.style):
+            _forward_only_f64('ApplyStyle', d.fmap, d.style)
+            return DataBag(d, fmap=hip.style_mul_f64(d.fmap, d.style))
         return DataBag(d, fmap=grad.StyleMul.apply(d.fmap, d.style))
 
 
@@ -531,7 +577,20 @@ class DemodulatedConv2dF(nn.Module):
             main.wait_stream(aux)      # queued while fmap / style / demod / out are still referenced
         return out
 
+    def squared_sums_f64(self):
+        """The one derived tensor of the double path (none of the packed weights applies): cached per weight version."""
+        return self._derived.get('wsq_f64', self.weight, lambda: hip.weight_sqsum_f64(self.weight, self.scale))
+
+    def run_f64(self, fmap, style, style_on_load):
+        """The double form of run(): the convolution on the weight as stored, then the demodulation factor."""
+        demod = hip.demod_f64(self.squared_sums_f64(), style) if self.demodulate else None
+        conv = hip.conv_transpose3x3s2_f64 if self.upsample else hip.conv3x3_f64
+        return conv(fmap, self.weight[0], self.scale, style=style if style_on_load else None, demod=demod)
+
     def forward(self, d):
+        if _double('DemodulatedConv2dF', d.fmap, weight=self.weight, style=d.style):
+            _forward_only_f64('DemodulatedConv2dF', d.fmap, self.weight, d.style)
+            return DataBag(d, fmap=self.run_f64(d.fmap, d.style, style_on_load=False))
         # through torch.autograd (grad.DemodConv: backward to the input map, the weight -- both terms, quirk Q3 --
         # and the style); without a graph this is run() and nothing else
         return DataBag(d, fmap=grad.DemodConv.apply(d.fmap, self.weight, d.style, self))
@@ -589,18 +648,22 @@ class NoiseInjectionF(nn.Module):
         super().__init__()
         self.weight = nn.Parameter(torch.zeros(1))
 
-    def noise_for(self, d, batch, height, width, device):
+    def noise_for(self, d, batch, height, width, device, double=False):
         noise = d.get('noise', None)
         if noise is None:
             rows = d.get('batch_rows', None)
             if rows is not None:        # a slice [start, start + batch) of a launch of `total` images keeps its rows
                 start, total = rows
-                return reference_noise(total, height * width, device)[start:start + batch]
-            return reference_noise(batch, height * width, device)
+                return reference_noise(total, height * width, device, double)[start:start + batch]
+            return reference_noise(batch, height * width, device, double)
         return noise.reshape(batch, height * width)
 
     def forward(self, d):
         b, _, h, w = d.fmap.shape
+        if _double('NoiseInjectionF', d.fmap, weight=self.weight, noise=d.get('noise', None)):
+            _forward_only_f64('NoiseInjectionF', d.fmap, self.weight)
+            noise = self.noise_for(d, b, h, w, d.fmap.device, double=True)
+            return DataBag(d, fmap=hip.noise_add_f64(d.fmap, noise, self.weight))
         return DataBag(d, fmap=grad.NoiseAdd.apply(d.fmap, self.noise_for(d, b, h, w, d.fmap.device), self.weight))
 
 
@@ -645,13 +708,24 @@ class ModulatedConv2d(nn.Module):
             type(self).__name__, self.in_channel, self.out_channel, self.kernel_size, self.upsample)
 
     def forward(self, input, style):
+        double = _double('ModulatedConv2d', input, weight=self.weight, style=style)
         style = self.modulation(style)
         if self.kernel_size == 1:
             if self.demodulate or self.upsample or self.out_channel != 3:
                 raise NotImplementedError('1x1 modulated conv is implemented for ToRGB only')
-            return hip.to_rgb(input, self.weight.view(3, self.in_channel), style, None, None, self.scale)
+            to_rgb = hip.to_rgb_f64 if double else hip.to_rgb
+            return to_rgb(input, self.weight.view(3, self.in_channel), style, None, None, self.scale)
         if self.kernel_size != 3:
             raise NotImplementedError('kernel_size %d' % self.kernel_size)
+        if double:
+            # the weight as stored, the style on load: only wsq is cached per weight version
+            demod = None
+            if self.demodulate:
+                wsq = self._derived.get('wsq_f64', self.weight, lambda: hip.weight_sqsum_f64(self.weight, self.scale))
+                demod = hip.demod_f64(wsq, style)
+            if self.upsample:
+                return self.blur(hip.conv_transpose3x3s2_f64(input, self.weight[0], self.scale, style=style, demod=demod))
+            return hip.conv3x3_f64(input, self.weight[0], self.scale, style=style, demod=demod)
         wp = self._derived.get('packed', self.weight,
                                lambda: hip.pack_conv_weight(self.weight, 1 if self.upsample else 0))
         demod = None
@@ -685,6 +759,9 @@ class ToRGBF(nn.Module):
     def forward(self, d):
         if d.get('fused_rgb') is not None:          # already computed in the epilogue of the last styled conv
             return DataBag(d, output=d.fused_rgb, fused_rgb=None)
+        if _double('ToRGBF', d.fmap, weight=self.conv.weight, bias=self.bias, style=d.style,
+                   skip=d.get('output') if self.skip else None):
+            return self._forward_f64(d)
         skip = d.output if self.skip else None
         if skip is not None and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
             up = self.upsample if hasattr(self, 'upsample') else Upsample([1, 3, 3, 1]).to(skip.device)
@@ -721,6 +798,19 @@ class ToRGBF(nn.Module):
         # (Tensor.record_stream would do, but it defers the allocator's reuse of multi-GB blocks
         # unpredictably and shows up as intermittent hipMalloc stalls at large batch).
         _rgb_branch.keep.append((d.fmap, d.style))
+        return DataBag(d, output=out)
+
+
+    def _forward_f64(self, d):
+        """The double form: the running image (upsampled here if it is smaller), the style, ToRGB -- on the caller's
+        stream."""
+        conv = self.conv
+        skip = d.output if self.skip else None
+        if skip is not None and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
+            up = self.upsample if hasattr(self, 'upsample') else Upsample([1, 3, 3, 1]).to(skip.device).double()
+            skip = up(skip)
+        style = conv.modulation(d.style)
+        out = hip.to_rgb_f64(d.fmap, conv.weight.view(3, conv.in_channel), style, self.bias.view(3), skip, conv.scale)
         return DataBag(d, output=out)
 
 
@@ -771,6 +861,8 @@ class StyledConvSeq(nn.Sequential):
     def _fusable(self, d=None):
         if not fusion_enabled() or set(self._modules) != {'mconv', 'noise', 'activate'}:
             return False
+        if d is not None and torch.is_tensor(d.get('fmap')) and d.fmap.dtype is _F64:
+            return False            # the double path runs module by module (the fused kernels are float32)
         if torch.is_grad_enabled() and (
                 any(p.requires_grad for p in self.mconv.dconv.parameters())
                 or (d is not None and any(torch.is_tensor(t) and t.requires_grad for t in (d.get('fmap'), d.get('style'),
@@ -1006,7 +1098,27 @@ class SeqStyleGAN2(nn.Sequential):
             steps.append(('output', ReturnOutput()))
         super().__init__(OrderedDict(steps))
 
+    def _checked_f64(self, input):
+        """True when this forward runs in double.  A float64 input into a float32 model, or the other way round, raises
+        here -- before anything is launched -- and so does a double forward that would have to record a graph."""
+        t = input if torch.is_tensor(input) else input.get('latent') if isinstance(input, dict) else None
+        own = next(self.parameters(), None)
+        if not torch.is_tensor(t) or own is None or (t.dtype is not _F64 and own.dtype is not _F64):
+            return False
+        if t.dtype != own.dtype:
+            raise RuntimeError('rewriting_amd: SeqStyleGAN2: the input is %s and the model\'s parameters are %s -- cast the '
+                               'model and its input to one dtype, .float() or .double() (nothing is converted)'
+                               % (t.dtype, own.dtype))
+        if isinstance(input, dict) and torch.is_tensor(input.get('noise')) and input['noise'].dtype != own.dtype:
+            raise RuntimeError('rewriting_amd: SeqStyleGAN2: the noise handed in is %s and the model\'s parameters are %s '
+                               '(nothing is converted)' % (input['noise'].dtype, own.dtype))
+        graph = [m.weight for m in self.modules() if isinstance(m, (DemodulatedConv2dF, NoiseInjectionF))]
+        _forward_only_f64('SeqStyleGAN2', t, *graph)
+        return True
+
     def forward(self, input):
+        if self._checked_f64(input):
+            return super().forward(input)       # module by module: no side stream, no micro-batching
         saved, _rgb_branch.switches = _rgb_branch.switches, switches()     # ONE reading of the RW_* switches per forward
         try:
             whole = (fusion_enabled() and torch.is_tensor(input) and not self.bag_output and not self.bag_input
