@@ -78,6 +78,19 @@ extern "C" int rw_dconv_prof(unsigned long long* out) {
 #ifndef DC_PRODUCTS
 #define DC_PRODUCTS 3
 #endif
+// ---- The taps (2, 0) and (2, 1) as partners of each other (round 9).  Tap ky = 2 has no partner in its COLUMN, but the
+// same output block meets tap (2, 0) and tap (2, 1) at the same window row: [Vh(column 0) | Vh(column 1)] x [Ul(2,0) | Ul(2,1)]
+// is both taps' third product.  Column 0's Ul pass then issues only its row pairs, column 1's reads the Vh half of column
+// 0's operand word again (8 bytes per lane) beside its own, column 2 keeps [Vh | Vl] x [Ul | Ul]: 14 MFMAs per three
+// columns and output block where 15 were issued, 224 per 16-channel chunk instead of 240.  The packed weights are the
+// same -- the pair is built from pieces the kernels load anyway (the one-role kernel keeps column 0's Ul(2,0) in registers
+// into column 1, the specialised one reads it again from the chunk's weights in LDS).  DC_TAP2_PAIR=0 keeps the 15-MFMA form.
+// Measured (profiles/r09*, same box, interleaved): dconv_ws_w2_rgbp_kernel 3.24 -> 3.04 ms per launch inside the forward,
+// dconv_w4_kernel 0.737 -> 0.711, the 1024 forward at batch 64 1564 -> 1592 img/s.
+#ifndef DC_TAP2_PAIR
+#define DC_TAP2_PAIR 1
+#endif
+#define DC_T2P (DC_PRODUCTS == 3 && DC_TAP2_PAIR)
 
 // sum over the 16 lanes of a DPP row (every lane ends with the sum)
 __device__ __forceinline__ float dc_row_sum(float v) {
@@ -206,6 +219,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   const unsigned char* wbase = p.wp + (int64_t)vb0 * T * 1024 + lane * 8;
   rw_f16x8 W[3][2][2];
   rw_f32x2 Wc[3][2][2];
+  rw_f32x2 Wk[2] = {};                             // DC_T2P: Ul of tap (2, 0), kept for column 1
   auto wload = [&](int ky, int t) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob)
@@ -216,12 +230,15 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
       }
   };
   // W[ky][ob][0] = [Uh | Uh] of tap ky; DC_PRODUCTS == 3: W[0][ob][1] = [Ul(ky 0) | Ul(ky 1)], W[2][ob][1] = [Ul | Ul] of
-  // tap 2 (W[1][ob][1] unused); == 4: W[ky][ob][1] = [Ul | Ul] of tap ky
-  auto wexpand = [&](int ky) __attribute__((always_inline)) {
+  // tap 2 (W[1][ob][1] unused); == 4: W[ky][ob][1] = [Ul | Ul] of tap ky.  DC_T2P: W[2][ob][1] is unused in column 0 and
+  // [Ul(2,0) | Ul(2,1)] in column 1
+  auto wexpand = [&](int ky, int kx) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob) {
       W[ky][ob][0] = rw_expand(Wc[ky][ob][0]);
-      if (DC_PRODUCTS == 4 || ky == 2) W[ky][ob][1] = rw_expand(Wc[ky][ob][1]);
+      if (DC_T2P && ky == 2 && kx == 0) Wk[ob] = Wc[2][ob][1];
+      else if (DC_T2P && ky == 2 && kx == 1) W[2][ob][1] = rw_pair(Wk[ob], Wc[2][ob][1]);
+      else if (DC_PRODUCTS == 4 || ky == 2) W[ky][ob][1] = rw_expand(Wc[ky][ob][1]);
       else if (ky == 1) W[0][ob][1] = rw_pair(Wc[0][ob][1], Wc[1][ob][1]);       // first used in row 1
     }
   };
@@ -243,6 +260,10 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   auto bread = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
     return *reinterpret_cast<const rw_f16x8*>(lb + bbase[kx] + ((idx >> 1) * DC_PW + 16 * (idx & 1)) * 64);
   };
+  // the Vh half of the same word: its first 8 bytes
+  auto bread_h = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
+    return *reinterpret_cast<const rw_f32x2*>(lb + bbase[kx] + ((idx >> 1) * DC_PW + 16 * (idx & 1)) * 64);
+  };
 
   // One chunk.  Kernel column kx: rows r = 0..5, halves 0 / 1 (idx = 2 r + half); the operand of idx + 1 is read before
   // the MFMAs of idx.  The weights of the NEXT column (or the next chunk's first) replace a tap's registers right after its
@@ -261,10 +282,12 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 #pragma unroll
       for (int idx = 0; idx < 12; ++idx) {
         const int r = idx >> 1, half = idx & 1;
-        if (half == 0 && r < 3) wexpand(r);         // tap ky = r is first used in row r
+        if (half == 0 && r < 3) wexpand(r, kx);     // tap ky = r is first used in row r
         rw_f16x8 bnext = bcur;
         if (idx + 1 < 12) bnext = bread(lb, kx, idx + 1);
         else if (kx < 2) bnext = bread(lb, kx + 1, 0);
+        rw_f32x2 bh0 = {};                          // DC_T2P, column 1: Vh of column 0's operand of this idx
+        if (DC_T2P && kx == 1 && r >= 2 && !(DC_ABL & 2)) bh0 = bread_h(lb, 0, idx);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
           const int pr = r - ky;
@@ -273,10 +296,17 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
           if (DC_ABL & 2) { asm volatile("" :: "v"(bcur), "v"(W[ky][0][0]), "v"(W[ky][0][1]), "v"(W[ky][1][0]), "v"(W[ky][1][1])); continue; }
           acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][0][0], acc[0][pb], 0, 0, 0);
           acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][1][0], acc[1][pb], 0, 0, 0);
+          if (DC_T2P && ky == 2 && kx < 2) continue;          // the Vh Ul of the taps (2, 0) and (2, 1): below, in column 1
           if (DC_PRODUCTS == 4 || ky == 2) {
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][0][1], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][1][1], acc[1][pb], 0, 0, 0);
           }
+        }
+        if (DC_T2P && kx == 1 && r >= 2 && !(DC_ABL & 2)) {
+          const int pb = 2 * (r - 2) + half;
+          const rw_f16x8 hh = rw_pair(rw_expand(bh0), bcur);
+          acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[2][0][1], acc[0][pb], 0, 0, 0);
+          acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[2][1][1], acc[1][pb], 0, 0, 0);
         }
         if (DC_PRODUCTS == 3 && r >= 1 && r <= 4 && !(DC_ABL & 2)) {      // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
           const int pb = 2 * (r - 1) + half;
@@ -442,6 +472,9 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 // 302 M MFMAs x 20.5 / 1024 SIMDs = 3.6 ms + the tiles' epilogues = 4.2 ms, where the 2.5 PFLOP/s the pipe is priced at
 // (16 cycles, 2.4 GHz) would be 2.0.  That is the same 4.2 - 4.4 ms the split F(4x4,3x3) kernel takes with a quarter of
 // the multiplies; the direct sums stay an opt-in (closer to the fp32 sum: 4e-7 against 1.1e-6).
+// (Round 9: 224 MFMAs per chunk where these figures had 240 -- DC_TAP2_PAIR above; column 1's Ul pass reads its pixel operand
+// as two 8-byte halves, [Vh(column 1) | Vh(column 0)], and the epilogue derives its lane values per tile: carried through
+// the chunks they were what the allocator spilled -- 4 VGPRs and 20 B / lane of scratch in the rgbp kernel, none now.)
 // ---------------------------------------------------------------------------------------
 // MW multiplying waves (wave < MW) = WM pairs of out-channel blocks x (MW / WM) strips of 4 rows x 32 columns, WC of them side
 // by side (a tile is 4 MW / (WM WC) rows x 32 WC columns: the wider, the fewer 128-byte lines its window touches per
@@ -717,6 +750,15 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   auto bread = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
     return *reinterpret_cast<const rw_f16x8*>(lb + bbase[kx] + ((idx >> 1) * PW + 16 * (idx & 1)) * 64);
   };
+  // DC_T2P: column 1's Ul pass (half-step 3) needs no Vl at all -- its operand is [Vh(column 1) | Vh(column 0)], the first
+  // 8 bytes of the two columns' words side by side: the row pairs take its first half as before, tap 2's instruction all of it
+  constexpr bool T2P1 = DC_T2P && !(DC_ABL & 2);
+  auto bread_hs = [&](const unsigned char* lb, int hs, int idx) __attribute__((always_inline)) {
+    const unsigned off = ((idx >> 1) * PW + 16 * (idx & 1)) * 64;
+    if (T2P1 && hs == 3)
+      return rw_pair(*reinterpret_cast<const rw_f32x2*>(lb + bbase[1] + off), *reinterpret_cast<const rw_f32x2*>(lb + bbase[0] + off));
+    return bread(lb, hs >> 1, idx);
+  };
   // weights.  A chunk is six HALF-steps (kernel column kx, piece Uh / Ul): 48 MFMAs on 48 different accumulators with the
   // six operands [ky][ob] of that piece -- 24 registers where a whole column's twelve take 48, which is what lets three waves
   // share a SIMD (168 registers; the pixel operands are then read once per half-step: 72 reads per chunk).  They come from
@@ -724,11 +766,13 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   // 288 loads per chunk and CU -- three quarters of everything the CU's memory path carried, and it was full (r04q).
   rw_f16x8 W[3][2];
   rw_f32x2 Wc[3][2];
+  rw_f32x2 Wk[2] = {};                             // DC_T2P: Ul of tap (2, 0), read again in column 1's Ul pass
   auto wread = [&](const unsigned char* wb, int kx, int part) __attribute__((always_inline)) {
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int ob = 0; ob < 2; ++ob) {
+        if (DC_T2P && part == 1 && ky == 2 && kx == 0) continue;       // column 0's Ul pass: row pairs only
         if (DC_ABL & 4) Wc[ky][ob] = rw_f32x2{1.f, 1.f};
         else Wc[ky][ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 3 * ky + kx) * 1024 + part * 512 + lane * 8);
       }
@@ -780,7 +824,9 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
           for (int ky = 0; ky < 3; ++ky) W[ky][ob] = rw_expand(Wc[ky][ob]);
         } else {
           W[0][ob] = rw_pair(Wc[0][ob], Wc[1][ob]);
-          W[2][ob] = rw_expand(Wc[2][ob]);
+          // DC_T2P: nothing in column 0; column 1: [Ul(2,1) | Ul(2,0)] (meets [Vh(column 1) | Vh(column 0)])
+          if (DC_T2P && kx == 1) W[2][ob] = rw_pair(Wc[2][ob], Wk[ob]);
+          else if (!(DC_T2P && kx == 0)) W[2][ob] = rw_expand(Wc[2][ob]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -790,8 +836,17 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
       for (int idx = 0; idx < 12; ++idx) {
         const int r = idx >> 1, half = idx & 1;
         const rw_f16x8 b = bq[idx % 3];
-        if (idx + 2 < 12) bq[(idx + 2) % 3] = bread(lb, kx, idx + 2);
-        else if (hs < 5) bq[(idx + 2) % 3] = bread(lb, (hs + 1) >> 1, idx + 2 - 12);
+        if (idx + 2 < 12) bq[(idx + 2) % 3] = bread_hs(lb, hs, idx + 2);
+        else if (hs < 5) bq[(idx + 2) % 3] = bread_hs(lb, hs + 1, idx + 2 - 12);
+        // Ul of tap (2, 0) again, for the next half-step: in its last row a Uh pass uses tap 2 only -- the registers of the
+        // other two taps' operands are free
+        if (T2P1 && hs == 2 && idx == 10) {
+#pragma unroll
+          for (int ob = 0; ob < 2; ++ob) {
+            if (DC_ABL & 4) Wk[ob] = rw_f32x2{1.f, 1.f};
+            else Wk[ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 6) * 1024 + 512 + lane * 8);
+          }
+        }
         if (DC_PRODUCTS == 4 || part == 0) {
 #pragma unroll
           for (int ky = 0; ky < 3; ++ky) {
@@ -803,7 +858,8 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[ky][1], acc[1][pb], 0, 0, 0);
           }
         } else if (DC_ABL & 2) {
-          asm volatile("" :: "v"(b), "v"(W[0][0]), "v"(W[0][1]), "v"(W[2][0]), "v"(W[2][1]));
+          if (DC_T2P && kx == 0) asm volatile("" :: "v"(b), "v"(W[0][0]), "v"(W[0][1]));
+          else asm volatile("" :: "v"(b), "v"(W[0][0]), "v"(W[0][1]), "v"(W[2][0]), "v"(W[2][1]));
         } else {
           if (r >= 1 && r <= 4) {                   // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
             const int pb = 2 * (r - 1) + half;
@@ -811,7 +867,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][1], acc[1][pb], 0, 0, 0);
           }
-          if (r >= 2) {                             // tap (2, kx): all four products
+          if (r >= 2 && !(DC_T2P && kx == 0)) {     // tap (2, kx): all four products; DC_T2P, column 1: Vh Ul of (2, 1) and (2, 0)
             const int pb = 2 * (r - 2) + half;
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[2][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[2][1], acc[1][pb], 0, 0, 0);
@@ -836,6 +892,11 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     const int par = (tile - t0) & 1;
     const int y0 = ty * TR, x0 = tx * TC;
     if (!(DC_ABL & 8)) {
+      // what the epilogue derives from the lane (channel, pixel offsets, plane addresses) is derived HERE, once per tile:
+      // carried through the chunks' MFMAs these values were the registers the allocator spilled
+      int lane_e = lane;
+      asm volatile("" : "+v"(lane_e));
+      const int lk = lane_e >> 4, lt = lane_e & 15;
       if (PLAIN) {
         const int oc = 16 * (2 * wm) + lt;          // + 16 ob
         const float sc[2] = {Ct[par][0][oc], Ct[par][0][oc + 16]}, bs[2] = {Ct[par][1][oc], Ct[par][1][oc + 16]};
