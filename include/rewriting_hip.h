@@ -612,6 +612,23 @@ int rw_conv_wgrad_f32(const float* g, const float* x, const float* gscale, const
 /* out[r] = sum_j a[r][j] * b[r][j] for `rows` rows of length n (per-(image, channel) sums over a feature map) */
 int rw_rowdot_f32(const float* a, const float* b, float* out, long long rows, long long n, rw_stream_t stream);
 
+/* ---- gradients of ToRGB (a loss on the IMAGE: rewrite/ganrewrite.py:300-331 through utils/stylegan2/models.py:394-425,
+ * 639-655 -- the 1x1 modulated convolution without demodulation, y[b][c][p] = sum_i w_scale w[c][i] style[b][i] x[b][i][p]
+ * + bias[c] + skip[b][c][p]).  g (batch, 3, hw) is the gradient w.r.t. y; d bias is rw_bias_grad_f32, d skip is g itself.
+ *
+ * rw_to_rgb_input_grad_f32: gx[b][i][p] = w_scale * style[b][i] * sum_{c < 3} w[c][i] * g[b][c][p]; gx (batch, in_ch, hw) is
+ *   overwritten.  16-byte accesses where hw % 4 == 0, a scalar form otherwise (as rw_to_rgb_f32).
+ * rw_to_rgb_weight_sums_f32: t[b][c][i] = sum_p g[b][c][p] * x[b][i][p], t (batch, 3, in_ch) overwritten -- from it
+ *   d w[c][i] = w_scale sum_b t[b][c][i] style[b][i] and d style[b][i] = w_scale sum_c t[b][c][i] w[c][i] (host side).
+ *   One pass over x (batch, in_ch, hw); scratch holds rw_to_rgb_weight_sums_scratch_elems(batch, in_ch, hw) floats of
+ *   per-workgroup partial sums that a second launch adds in a fixed order: no atomics, nothing to zero, two runs agree
+ *   bit for bit (as rw_conv_wgrad_f32).  batch <= 65535. */
+int rw_to_rgb_input_grad_f32(const float* g, const float* w, const float* style, float* gx, int batch, int in_ch,
+                             int64_t hw, float w_scale, rw_stream_t stream);
+long long rw_to_rgb_weight_sums_scratch_elems(int batch, int in_ch, int64_t hw);
+int rw_to_rgb_weight_sums_f32(const float* g, const float* x, float* scratch, float* t, int batch, int in_ch, int64_t hw,
+                              rw_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Generator forward in float64 -- the reference's generator runs after .double(): its two native ops dispatch double
  * (above) and everything else is torch.  These entries are the double forms of that torch arithmetic: every pointer is a

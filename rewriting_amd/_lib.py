@@ -180,6 +180,10 @@ SIGNATURES = {
     'rw_conv_wgrad_ksplit': (c_int, [c_int] * 6),
     'rw_conv_wgrad_f32': (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float, c_void_p]),
     'rw_rowdot_f32': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
+    'rw_to_rgb_input_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float,
+                                         c_void_p]),
+    'rw_to_rgb_weight_sums_scratch_elems': (ctypes.c_longlong, [c_int, c_int, c_int64]),
+    'rw_to_rgb_weight_sums_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     # the float64 forward: the _f32 twin's arguments, double buffers and double scalars
     'rw_pixel_norm_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
     'rw_equal_linear_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -11,6 +11,10 @@
 // solver's K3 (rw_solve.hip) without its Adam epilogue, generalised to a batch and to maps of any size: M = out
 // channels, N = (in channel, tap) columns, K = batch x conv-output positions, fp32 MFMA, split-K over workgroups
 // with the partial sums reduced in a fixed order (no atomics: the result is deterministic).
+//
+// At the end of the file: the two adjoints of ToRGB (models.py:394-425, 639-655) that a loss on the IMAGE needs -- the
+// gradient to the feature map (streaming: 3 planes in, in_ch planes out) and the per-image sums  g . x  over the pixels
+// from which the host forms the gradients of the ToRGB weight and of its style (utils/stylegan2/grad.py: ToRGB).
 #include "rw_common.h"
 
 #define WG_KC 16        // K chunk: conv-output positions per staging step
@@ -193,5 +197,155 @@ extern "C" int rw_rowdot_f32(const float* a, const float* b, float* out, long lo
                              rw_stream_t stream) {
   RW_CHECK_ARG(a && b && out && rows > 0 && n > 0 && rows < (1LL << 31));
   hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)rows), dim3(256), 0, rw_s(stream), a, b, out, (int64_t)n);
+  return RW_LAUNCH_RESULT();
+}
+
+// ---------------------------------------------------------------------------------------
+// ToRGB backward (models.py:394-425 with demodulate=False, kernel 1; :639-655): y[b][c][p] = sum_i s W[c][i] style[b][i] x[b][i][p].
+//
+// d x: gx[b][i][p] = s style[b][i] sum_c W[c][i] g[b][c][p].  Streaming, the mirror of to_rgb_kernel (rw_ops.hip): a thread
+// owns 4 consecutive pixels (16-byte accesses along W), reads the three gradient planes once and writes RGI_CG channel
+// planes; the 3 x RGI_CG modulated weights of (image, channel group) sit in LDS.  Channel groups are a grid dimension so
+// that the 4x4 .. 32x32 maps with 512 channels still fill the chip (g is re-read once per group: 3 planes against 64).
+// ---------------------------------------------------------------------------------------
+#define RGI_CG 64
+
+template <bool V4>
+__global__ void __launch_bounds__(256) to_rgb_input_grad_kernel(const float* __restrict__ g, const float* __restrict__ w,
+                                                                const float* __restrict__ style, float* __restrict__ gx,
+                                                                int in_ch, int64_t hw, float w_scale) {
+  __shared__ float wm[3][RGI_CG];
+  const int b = blockIdx.y, i0 = blockIdx.z * RGI_CG;
+  const int ni = min(RGI_CG, in_ch - i0);
+  for (int t = threadIdx.x; t < 3 * RGI_CG; t += 256) {
+    const int c = t / RGI_CG, ii = t - c * RGI_CG;
+    wm[c][ii] = ii < ni ? w_scale * w[c * in_ch + i0 + ii] * style[(int64_t)b * in_ch + i0 + ii] : 0.f;
+  }
+  __syncthreads();
+  const float* gb = g + (int64_t)b * 3 * hw;
+  float* xb = gx + ((int64_t)b * in_ch + i0) * hw;
+  if (V4) {
+    const int64_t hw4 = hw >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < hw4; q += (int64_t)gridDim.x * 256) {
+      const float4 g0 = reinterpret_cast<const float4*>(gb)[q];
+      const float4 g1 = reinterpret_cast<const float4*>(gb + hw)[q];
+      const float4 g2 = reinterpret_cast<const float4*>(gb + 2 * hw)[q];
+#pragma unroll 4
+      for (int ii = 0; ii < ni; ++ii) {
+        const float w0 = wm[0][ii], w1 = wm[1][ii], w2 = wm[2][ii];
+        float4 o;
+        o.x = w0 * g0.x + w1 * g1.x + w2 * g2.x;
+        o.y = w0 * g0.y + w1 * g1.y + w2 * g2.y;
+        o.z = w0 * g0.z + w1 * g1.z + w2 * g2.z;
+        o.w = w0 * g0.w + w1 * g1.w + w2 * g2.w;
+        reinterpret_cast<float4*>(xb + (int64_t)ii * hw)[q] = o;
+      }
+    }
+  } else {
+    // maps whose pixel count is no multiple of four (cropped goal maps: rows of 5 x 7, ...): one pixel per thread
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < hw; q += (int64_t)gridDim.x * 256) {
+      const float g0 = gb[q], g1 = gb[hw + q], g2 = gb[2 * hw + q];
+      for (int ii = 0; ii < ni; ++ii) xb[(int64_t)ii * hw + q] = wm[0][ii] * g0 + wm[1][ii] * g1 + wm[2][ii] * g2;
+    }
+  }
+}
+
+extern "C" int rw_to_rgb_input_grad_f32(const float* g, const float* w, const float* style, float* gx, int batch,
+                                        int in_ch, int64_t hw, float w_scale, rw_stream_t stream) {
+  RW_CHECK_ARG(g && w && style && gx && batch > 0 && batch <= 65535 && in_ch > 0 && hw > 0);
+  const int groups = (int)rw_cdiv(in_ch, RGI_CG);
+  RW_CHECK_ARG(groups <= 65535);
+  const bool v4 = hw % 4 == 0;
+  int64_t gxn = rw_cdiv(v4 ? hw / 4 : hw, 256);
+  const int64_t cap = rw_cdiv(256 * 8, (int64_t)batch * groups);
+  if (gxn > cap) gxn = cap;
+  if (gxn < 1) gxn = 1;
+  const dim3 grid((unsigned)gxn, (unsigned)batch, (unsigned)groups);
+  if (v4)
+    hipLaunchKernelGGL(to_rgb_input_grad_kernel<true>, grid, dim3(256), 0, rw_s(stream), g, w, style, gx, in_ch, hw, w_scale);
+  else
+    hipLaunchKernelGGL(to_rgb_input_grad_kernel<false>, grid, dim3(256), 0, rw_s(stream), g, w, style, gx, in_ch, hw, w_scale);
+  return RW_LAUNCH_RESULT();
+}
+
+// ---------------------------------------------------------------------------------------
+// t[b][c][i] = sum_p g[b][c][p] x[b][i][p]: what d W and d style of ToRGB are made of.  ONE pass over x: a workgroup takes
+// (a chunk of RGS_CHUNK pixels, a group of RGS_CG channels, an image), keeps its 3 x 16 gradient values per thread in
+// registers and walks the group's channel planes; per channel three sums over the thread's 16 products, a 64-lane
+// butterfly, then the four waves' results through LDS -- summed in wave order -- to scratch[chunk][b][c][i].  A second
+// small launch adds the chunks in order.  No atomics, nothing zeroed beforehand: two runs are bit-identical.
+// ---------------------------------------------------------------------------------------
+#define RGS_CG 32
+#define RGS_PER_THREAD 16
+#define RGS_CHUNK (256 * RGS_PER_THREAD)
+
+template <bool V4>
+__device__ __forceinline__ void rgs_load(float (&v)[RGS_PER_THREAD], const float* __restrict__ plane, int64_t p0, int64_t hw) {
+  if (V4) {           // hw % 4 == 0 and p0 % 4 == 0: whole float4s are inside the plane or outside it
+#pragma unroll
+    for (int r = 0; r < RGS_PER_THREAD / 4; ++r) {
+      const int64_t p = p0 + 4 * ((int64_t)threadIdx.x + 256 * r);
+      float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (p < hw) f = *reinterpret_cast<const float4*>(plane + p);
+      v[4 * r] = f.x; v[4 * r + 1] = f.y; v[4 * r + 2] = f.z; v[4 * r + 3] = f.w;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < RGS_PER_THREAD; ++r) {
+      const int64_t p = p0 + threadIdx.x + 256 * r;
+      v[r] = p < hw ? plane[p] : 0.f;
+    }
+  }
+}
+
+template <bool V4>
+__global__ void __launch_bounds__(256) to_rgb_weight_sums_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                                 float* __restrict__ part, int batch, int in_ch, int64_t hw) {
+  __shared__ float red[4][3][RGS_CG];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t chunk = blockIdx.x, p0 = chunk * RGS_CHUNK;
+  const int i0 = blockIdx.y * RGS_CG, b = blockIdx.z;
+  const int ni = min(RGS_CG, in_ch - i0);
+  float gr[3][RGS_PER_THREAD];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) rgs_load<V4>(gr[c], g + ((int64_t)b * 3 + c) * hw, p0, hw);
+  for (int ii = 0; ii < ni; ++ii) {
+    float xv[RGS_PER_THREAD];
+    rgs_load<V4>(xv, x + ((int64_t)b * in_ch + i0 + ii) * hw, p0, hw);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < RGS_PER_THREAD; ++e) {
+      a0 += gr[0][e] * xv[e]; a1 += gr[1][e] * xv[e]; a2 += gr[2][e] * xv[e];
+    }
+    a0 = rw_wave_sum(a0); a1 = rw_wave_sum(a1); a2 = rw_wave_sum(a2);
+    if (lane == 0) { red[wave][0][ii] = a0; red[wave][1][ii] = a1; red[wave][2][ii] = a2; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * RGS_CG) {
+    const int c = threadIdx.x / RGS_CG, ii = threadIdx.x - c * RGS_CG;
+    if (ii < ni)
+      part[((chunk * batch + b) * 3 + c) * in_ch + i0 + ii] = red[0][c][ii] + red[1][c][ii] + red[2][c][ii] + red[3][c][ii];
+  }
+}
+
+extern "C" long long rw_to_rgb_weight_sums_scratch_elems(int batch, int in_ch, int64_t hw) {
+  if (batch <= 0 || in_ch <= 0 || hw <= 0) return 0;
+  return (long long)(rw_cdiv(hw, RGS_CHUNK) * batch * 3 * in_ch);
+}
+
+extern "C" int rw_to_rgb_weight_sums_f32(const float* g, const float* x, float* scratch, float* t, int batch, int in_ch,
+                                         int64_t hw, rw_stream_t stream) {
+  RW_CHECK_ARG(g && x && scratch && t && batch > 0 && batch <= 65535 && in_ch > 0 && hw > 0);
+  const int64_t chunks = rw_cdiv(hw, RGS_CHUNK), groups = rw_cdiv(in_ch, RGS_CG);
+  RW_CHECK_ARG(chunks < (1LL << 31) && groups <= 65535);
+  hipStream_t s = rw_s(stream);
+  const dim3 grid((unsigned)chunks, (unsigned)groups, (unsigned)batch);
+  if (hw % 4 == 0)
+    hipLaunchKernelGGL(to_rgb_weight_sums_kernel<true>, grid, dim3(256), 0, s, g, x, scratch, batch, in_ch, hw);
+  else
+    hipLaunchKernelGGL(to_rgb_weight_sums_kernel<false>, grid, dim3(256), 0, s, g, x, scratch, batch, in_ch, hw);
+  const int64_t n = (int64_t)batch * 3 * in_ch;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rw_stream_grid(n, 256)), dim3(256), 0, s, (const float*)scratch, t, n,
+                     (int)chunks, 1.f);
   return RW_LAUNCH_RESULT();
 }

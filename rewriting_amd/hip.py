@@ -978,6 +978,37 @@ def rowdot(a, b):
     return out.view(lead)
 
 
+# ------------------------------------------------------------------ gradients of ToRGB (a loss on the image)
+def to_rgb_input_grad(g, weight, style, w_scale):
+    """d fmap (B, C, H, W) of to_rgb given g = dL/d image (B, 3, H, W): w_scale * style[b, i] * sum_c weight[c, i] g[b, c]
+    -- rw_to_rgb_input_grad_f32."""
+    g = _dev(g, 'image gradient')
+    weight = _dev(weight, 'rgb weight')
+    style = _dev(style, 'style')
+    b, three, h, w = g.shape
+    c = style.shape[1]
+    if three != 3 or tuple(weight.shape) != (3, c) or style.shape[0] != b:
+        raise ValueError('image gradient / rgb weight / style shapes')
+    gx = torch.empty(b, c, h, w, device=g.device, dtype=torch.float32)
+    check(lib().rw_to_rgb_input_grad_f32(_p(g), _p(weight), _p(style), _p(gx), b, c, h * w, float(w_scale), _stream()))
+    return gx
+
+
+def to_rgb_weight_sums(g, x):
+    """(B, 3, C) sums over the pixels of g[b, c] * x[b, i] for g = dL/d image (B, 3, H, W) and the feature map x
+    (B, C, H, W) that to_rgb read: what d weight and d style are made of -- rw_to_rgb_weight_sums_f32 (deterministic)."""
+    g = _dev(g, 'image gradient')
+    x = _dev(x, 'fmap')
+    b, c, h, w = x.shape
+    if tuple(g.shape) != (b, 3, h, w):
+        raise ValueError('image gradient %s does not belong to a feature map %s' % (tuple(g.shape), tuple(x.shape)))
+    n = lib().rw_to_rgb_weight_sums_scratch_elems(b, c, h * w)
+    scratch = torch.empty(n, device=x.device, dtype=torch.float32)
+    t = torch.empty(b, 3, c, device=x.device, dtype=torch.float32)
+    check(lib().rw_to_rgb_weight_sums_f32(_p(g), _p(x), _p(scratch), _p(t), b, c, h * w, _stream()))
+    return t
+
+
 __all__ = [n for n in dir() if not n.startswith('_')] + ['SolveProblem', 'ConvEpilogue']
 
 

@@ -243,11 +243,16 @@ class ProgressiveGanRewriter(object):
         self.insert(goal_in, goal_out, mkey, update_callback=update_callback,
                     niter=niter, piter=piter, lr=lr)
 
-    def apply_overfit(self, request, niter=20001, lr=0.01, update_callback=None):
-        raise NotImplementedError(
-            'apply_overfit trains every weight against a VGG16 perceptual loss '
-            '(rewrite/ganrewrite.py:171-181,300-331); torchvision weights are unavailable and the '
-            'path is outside the rule-editing hot path (SURVEY.md section 8a row d5)')
+    def apply_overfit(self, request, niter=20001, lr=0.01, update_callback=None, feature_net=None):
+        """The overfit baseline (rewrite/ganrewrite.py:171-181): paste the selected object into the image itself and
+        train every weight toward it (all_weights_insert).  feature_net: see there."""
+        _need_feature_net(feature_net)
+        o_imgnum, o_mask = request['object']
+        p_imgnum, p_mask = request['paste']
+        rgb_clip, _, obj_area, _ = self.rgb_from_selection(o_imgnum, o_mask)
+        host_z, changed_rgb, bounds = self.rgbpaste_from_selection(p_imgnum, p_mask, rgb_clip, obj_area)
+        self.all_weights_insert(changed_rgb, host_z, bounds=bounds, update_callback=update_callback, niter=niter, lr=lr,
+                                feature_net=feature_net)
 
     def zero(self, context, amount=0.0):
         """W <- W - P(W) + amount * P(1)   (:190-195)"""
@@ -359,8 +364,37 @@ class ProgressiveGanRewriter(object):
             sync()
             return (time.time() - started) * 1000
 
-    def all_weights_insert(self, *args, **kwargs):
-        raise NotImplementedError('see apply_overfit')
+    def all_weights_insert(self, x, z, bounds=None, update_callback=None, niter=20001, lr=0.01, feature_net=None):
+        """Adam over EVERY parameter of the generator toward the image x for the latent z (rewrite/ganrewrite.py:300-331):
+        L1 on the image (cropped to bounds = (top, left, bottom, right) if given) plus 1e-2 of the mean squared
+        difference of feature_net's responses.  The gradient reaches the parameters through the adjoints of
+        utils/stylegan2/grad.py.  feature_net (VF of the reference: torchvision's VGG16 features[:21], whose weights have
+        to be downloaded) is the caller's: any module or function from images to feature tensors."""
+        _need_feature_net(feature_net)
+        x, z = self.detach(x), self.detach(z)
+
+        def compute_loss():
+            out = self.model(z)
+            if bounds is None:
+                gt, pred = x, out
+            else:
+                t, l, b, r = bounds
+                gt, pred = x[:, :, t:b, l:r], out[:, :, t:b, l:r]
+            return torch.nn.functional.l1_loss(gt, pred) + (
+                1e-2 * torch.nn.functional.mse_loss(feature_net(gt), feature_net(pred)))
+        nethook.set_requires_grad(False, self.model)
+        params = list(self.model.parameters())
+        nethook.set_requires_grad(True, *params)
+        optimizer = torch.optim.Adam(params, lr=lr)
+        for it in range(niter):
+            with torch.enable_grad():
+                loss = compute_loss()
+                optimizer.zero_grad()
+                loss.backward()
+                optimizer.step()
+                if update_callback is not None:
+                    update_callback(it, loss)
+        _weights_changed()
 
     # ---- context direction ----------------------------------------------------------------
     def _key_observations(self, imgnum_mask_pairs):
@@ -779,6 +813,16 @@ class SeqPreStyleGanRewriter(SeqStyleGanRewriter):
 # ------------------------------------------------------------------------------------------
 # utilities
 # ------------------------------------------------------------------------------------------
+
+def _need_feature_net(feature_net):
+    if feature_net is None:
+        raise NotImplementedError(
+            'apply_overfit trains every weight against a VGG16 perceptual loss '
+            '(rewrite/ganrewrite.py:171-181,300-331); torchvision weights are unavailable and the '
+            'path is outside the rule-editing hot path (SURVEY.md section 8a row d5) -- pass the perceptual network '
+            'yourself as feature_net= (a module from images to feature maps, e.g. a VGG16 features[:21] with its '
+            'weights loaded); without one neither apply_overfit nor all_weights_insert runs')
+
 
 def _weights_changed():
     from ..utils.stylegan2 import models as sg

@@ -317,6 +317,8 @@ class PixelNormL(nn.Module):
     def forward(self, d):
         if d.latent.dtype is _F64:
             return DataBag(d, latent=hip.pixel_norm_f64(d.latent))
+        if grad.records(d.latent):
+            return DataBag(d, latent=grad.PixelNorm.apply(d.latent, 1e-8))
         return DataBag(d, latent=hip.pixel_norm(d.latent))
 
 
@@ -339,6 +341,8 @@ class EqualLinear(nn.Linear):
         if _double('EqualLinear', input, weight=self.weight, bias=self.bias):
             return hip.equal_linear_f64(input, self.weight, self.bias, self.scale, self.lr_mul,
                                         act=bool(self.activation))
+        if grad.records(input, self.weight, self.bias):
+            return grad.EqualLinear.apply(input, self.weight, self.bias, self)
         return hip.equal_linear(input, self.weight, self.bias, self.scale, self.lr_mul,
                                 act=bool(self.activation))
 
@@ -372,6 +376,8 @@ class AdjustLatent(nn.Module):
         adjust = hip.adjust_latent
         if _double('AdjustLatent', d.latent, latent_avg=self.latent_avg if truncate else None):
             adjust = hip.adjust_latent_f64
+        elif grad.records(d.latent):
+            adjust = grad.AdjustLatent.apply
         lat = adjust(d.latent, self.latent_avg if truncate else None, self.n_latent,
                      self.truncation)
         return DataBag(d, latent=lat)
@@ -421,6 +427,8 @@ class ConstantInputF(nn.Module):
         self.input = nn.Parameter(torch.randn(1, channel, size, size))
 
     def forward(self, d):
+        if grad.records(self.input) and self.input.dtype is not _F64:
+            return DataBag(d, fmap=self.input.repeat(d.latent.shape[0], 1, 1, 1))      # the constant is trained too
         return DataBag(d, fmap=self.input.detach().repeat(d.latent.shape[0], 1, 1, 1))
 
 
@@ -785,8 +793,11 @@ class ToRGBF(nn.Module):
             return nd
         if side is None:
             style = conv.modulation(d.style)
-            out = hip.to_rgb(d.fmap, conv.weight.view(3, conv.in_channel), style, self.bias.view(3), skip,
-                             conv.scale)
+            weight, bias = conv.weight.view(3, conv.in_channel), self.bias.view(3)
+            if grad.records(d.fmap, weight, style, bias, skip):
+                out = grad.ToRGB.apply(d.fmap, weight, style, bias, skip, conv.scale)
+            else:
+                out = hip.to_rgb(d.fmap, weight, style, bias, skip, conv.scale)
             return DataBag(d, output=out)
         ahead = _prefetched(self)
         side.wait_stream(torch.cuda.current_stream())      # the feature map and the latent come from the trunk
@@ -864,7 +875,7 @@ class StyledConvSeq(nn.Sequential):
         if d is not None and torch.is_tensor(d.get('fmap')) and d.fmap.dtype is _F64:
             return False            # the double path runs module by module (the fused kernels are float32)
         if torch.is_grad_enabled() and (
-                any(p.requires_grad for p in self.mconv.dconv.parameters())
+                any(p.requires_grad for p in self.parameters())     # dconv weight, modulation, noise strength, act bias
                 or (d is not None and any(torch.is_tensor(t) and t.requires_grad for t in (d.get('fmap'), d.get('style'),
                                                                                            d.get('latent'))))):
             # somebody may differentiate through this layer (an `insert` whose target spans it, rewrite/ganrewrite.py:
@@ -1116,9 +1127,38 @@ class SeqStyleGAN2(nn.Sequential):
         _forward_only_f64('SeqStyleGAN2', t, *graph)
         return True
 
+    def _records_graph(self, input):
+        """True when this forward has to leave a graph from the image back to the latent, the mapping network, a
+        modulation, a ToRGB or the constant input: the adjoints that exist for a loss on the image (grad.py, second
+        half).  Nothing else changes the way the generator runs: under torch.no_grad() this is False at once, and a model
+        in which only parameters of the styled convolutions proper (dconv weight, noise strength, activation bias)
+        require a gradient keeps the forward it had -- the layers concerned already run module by module
+        (StyledConvSeq._fusable), and the image carries no graph."""
+        if not torch.is_grad_enabled():
+            return False
+        t = input if torch.is_tensor(input) else input.get('latent') if isinstance(input, dict) else None
+        if torch.is_tensor(t) and t.requires_grad:
+            return True
+        for m in self.modules():
+            own = isinstance(m, (EqualLinear, ConstantInputF, ToRGBF)) or \
+                (isinstance(m, ModulatedConv2d) and m.kernel_size == 1)
+            if own and any(p.requires_grad for p in m.parameters(recurse=False)):
+                return True
+        return False
+
     def forward(self, input):
         if self._checked_f64(input):
             return super().forward(input)       # module by module: no side stream, no micro-batching
+        if self._records_graph(input):
+            # module by module on the caller's stream: no RGB side stream, no style prefetch, no micro-batches, no
+            # ToRGB sums left by a convolution -- every step is then a Function of grad.py / op/ (or a fused block none
+            # of whose own parameters and inputs requires a gradient: StyledConvSeq._fusable), and autograd replays them
+            # on this one stream
+            saved, _rgb_branch.switches = _rgb_branch.switches, switches()
+            try:
+                return super().forward(input)
+            finally:
+                _rgb_branch.switches = saved
         saved, _rgb_branch.switches = _rgb_branch.switches, switches()     # ONE reading of the RW_* switches per forward
         try:
             whole = (fusion_enabled() and torch.is_tensor(input) and not self.bag_output and not self.bag_input
