@@ -444,7 +444,7 @@ def pack_conv_weight_wino4(weight, split=False):
 def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                   x_amax=None, y_amax=None):
     """Stride-1 3x3 convolution by Winograd F(4x4,3x3) (~1e-5 relative error per layer: the default of the
-    un-hooked whole-generator forward, never used by a hooked or sliced model -- models.conv_algo); same arguments
+    un-hooked whole-generator forward, never used by a hooked or sliced model -- routing.conv_algo); same arguments
     and epilogue as conv3x3.  With weights from pack_conv_weight_wino4(split=True) the products run on the 16-bit
     matrix pipe (exact f16 operand split, fp32 accumulation): x_amax = the bound of x (hip.absmax(x), or the y_amax its
     producer filled; measured here when None), y_amax = hip.new_bound(y.numel(), device), which receives the bound of y."""

@@ -21,7 +21,7 @@ import math
 import re
 import threading
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -165,49 +165,93 @@ def _unhooked(*modules):
 # issued on a second HIP stream so that it overlaps the next styled convolutions, and is joined
 # before the image is returned.  Hooked / sliced models (nethook) never see this: the mode is on only
 # inside that forward.
-class _RgbBranch(threading.local):      # per thread: two threads may run generators concurrently
+def _idle():
+    """The record of the running forward while none runs: every field, and its default, is stated here."""
+    return dict(
+        stream=None,        # the RGB branch's stream and ...
+        aux=None,           # ... the auxiliary one (border strips, prefetch) of the running side-stream forward
+        keep=[],            # trunk tensors the side streams still read: referenced until the join (_side_streams_joined)
+        final=None,         # (last StyledConvSeq, its ToRGBF, latent index of the ToRGB) of the running forward
+        image_path=False,   # inside the un-hooked forward of a whole generator (see routing.conv_algo)
+        switches=None,      # routing.switches() of the running generator forward
+        neighbours={},      # id(StyledConvSeq) -> _Neighbours of the running un-hooked forward (SeqStyleGAN2._topology)
+        pre={},             # id(StyledConvSeq) -> (style, demod factors), id(ToRGBF) -> style: computed up front
+        pre_join=None)      # the stream they were computed on, until the trunk has waited for it
+
+
+class _RunningForward(threading.local):     # per thread: two threads may run generators concurrently
     def __init__(self):
-        self.stream = None
-        self.aux = None
-        self.keep = []
-        self.final = None        # (last StyledConvSeq, its ToRGBF, latent index of the ToRGB) of the running forward
-        self.image_path = False  # inside the un-hooked forward of a whole generator (see routing.conv_algo)
-        self.switches = None     # routing.switches() of the running generator forward
-        self.successor = {}      # id(upsampling StyledConvSeq) -> (the StyledConvSeq that reads its result, latent index)
-        self.reader = {}         # id(StyledConvSeq) -> the StyledConvSeq that reads its feature map (any kind), if any
-        self.torgb = {}          # id(StyledConvSeq) -> (the ToRGBF that reads its feature map, its latent index), if any
-        self.pre = {}            # id(StyledConvSeq) -> (style, demod factors), id(ToRGBF) -> style: computed up front
-        self.pre_join = None     # the stream they were computed on, until the trunk has waited for it
+        vars(self).update(_idle())
 
 
-_rgb_branch = _RgbBranch()
-_rgb_side_streams = {}          # one per device, module-level: models are deep-copied by the rewriters
+_running = _RunningForward()
+_side_streams = {}              # (device, 'rgb' / 'aux') -> stream; module-level: models are deep-copied by the rewriters
+# who reads a StyledConvSeq's result: `reader` the next StyledConvSeq (any kind); `successor` (the stride-1 StyledConvSeq
+# directly behind this upsampling one, its latent index); `torgb` (the ToRGBF directly behind, its latent index); or None
+_Neighbours = namedtuple('_Neighbours', 'reader successor torgb')
+_NO_NEIGHBOURS = _Neighbours(None, None, None)
 
 
-def _side_stream(device):
-    """A stream for the work beside the trunk (RGB branch, border strips, prefetch).  RW_SIDE_PRIORITY (default 0): the
-    priority torch gives it (positive = below the trunk's stream; clamped to the device's range)."""
-    return torch.cuda.Stream(device=device, priority=_switches().side_priority)
+class _scope:
+    """with _scope(field=value, ...): the only place that assigns fields of the running forward's record.  The values
+    they had return on exit, whether or not the body raised."""
+
+    def __init__(self, **fields):
+        self.fields = fields
+
+    def __enter__(self):
+        record = vars(_running)
+        self.saved = {name: record[name] for name in self.fields}
+        record.update(self.fields)
+
+    def __exit__(self, *exc):
+        vars(_running).update(self.saved)
+
+
+def _side_stream(device, which):
+    """The device's stream `which` ('rgb' / 'aux') for the work beside the trunk (RGB branch, border strips, prefetch),
+    made at its first use.  RW_SIDE_PRIORITY (default 0): the priority torch gives it (positive = below the trunk's
+    stream; clamped to the device's range)."""
+    stream = _side_streams.get((device, which))
+    if stream is None:
+        stream = _side_streams[device, which] = torch.cuda.Stream(device=device, priority=_switches().side_priority)
+    return stream
+
+
+@contextlib.contextmanager
+def _side_streams_joined(device):
+    """The side-stream scope of one generator forward: the device's two streams are installed; on the way out, raised or
+    not, the caller's stream (which is yielded) first waits for the RGB branch -- the image is then complete on it --
+    and only THEN are the tensors of `keep` released, to the trunk's pool.  The branch reads trunk tensors from another
+    stream, so they stay referenced until that join (Tensor.record_stream would do, but it defers the allocator's reuse
+    of multi-GB blocks unpredictably and shows up as intermittent hipMalloc stalls at large batch)."""
+    main, side = torch.cuda.current_stream(), _side_stream(device, 'rgb')
+    try:
+        with _scope(stream=side, aux=_side_stream(device, 'aux')):
+            yield main
+    finally:
+        main.wait_stream(side)      # the join is queued first ...
+        del _running.keep[:]        # ... then the kept tensors go, to the trunk's pool
 
 
 def _rgb_stream():
-    return _rgb_branch.stream
+    return _running.stream
 
 
 def _prefetched(module):
     """(style, demod) of a StyledConvSeq / the style of a ToRGBF computed at the start of the un-hooked forward
     (SeqStyleGAN2._prefetch_modulations), or None.  The first reader makes the trunk wait for the stream they
     were computed on."""
-    entry = _rgb_branch.pre.get(id(module))
-    if entry is not None and _rgb_branch.pre_join is not None:
-        torch.cuda.current_stream().wait_stream(_rgb_branch.pre_join)
-        _rgb_branch.pre_join = None
+    entry = _running.pre.get(id(module))
+    if entry is not None and _running.pre_join is not None:
+        torch.cuda.current_stream().wait_stream(_running.pre_join)
+        _running.pre_join = None        # consumed once (the one assignment outside _scope, which restores it anyway)
     return entry
 
 
 def _switches():
     """The snapshot of the RW_* switches that the running generator forward took at its start, else a fresh one."""
-    return _rgb_branch.switches or switches()
+    return _running.switches or switches()
 
 
 def fusion_enabled():
@@ -217,26 +261,6 @@ def fusion_enabled():
 def conv_impl():
     """rw_conv3x3_f32's impl for the 3x3 convolutions (RW_CONV_IMPL, see routing.Switches)."""
     return _switches().conv_impl
-
-
-def conv_precision():
-    """'f32' (default: exact fp32 MFMA) or 'bf16x6' (RW_CONV_PRECISION=bf16x6, opt-in)."""
-    return _switches().conv_precision
-
-
-def conv_algo():
-    """routing.conv_algo for the way the modules are being run right now."""
-    return routing.conv_algo(_switches(), _rgb_branch.image_path)
-
-
-def up_conv_algo():
-    """Algorithm of the stride-2 transposed convolutions (RW_UP_ALGO, see routing.Switches)."""
-    return _switches().up_algo
-
-
-def matrix_mode(kind=None):
-    """routing.matrix_mode for the way the modules are being run right now."""
-    return routing.matrix_mode(_switches(), _rgb_branch.image_path, kind)
 
 
 def matrix_mode_of_image_path():
@@ -252,8 +276,8 @@ def micro_batch():
 def _context(tensor, weight_changes=False):
     """routing.Context of a layer that is about to run on `tensor`'s device."""
     on_device = tensor.is_cuda
-    return routing.Context(_rgb_branch.image_path, on_device, on_device and torch.cuda.is_current_stream_capturing(),
-                           _rgb_branch.stream is not None, _rgb_branch.aux is not None, weight_changes)
+    return routing.Context(_running.image_path, on_device, on_device and torch.cuda.is_current_stream_capturing(),
+                           _running.stream is not None, _running.aux is not None, weight_changes)
 
 
 def _amax_of(fmap):
@@ -262,7 +286,7 @@ def _amax_of(fmap):
     the map themselves (hip.absmax).  It travels with the tensor object, not with an address or a bag key: a slice, a
     copy or a map that was edited in place since (hooks) carries no usable bound.  Trusted only inside the un-hooked
     forward of a whole generator, where producer and consumer are both ours."""
-    if fmap is None or not _rgb_branch.image_path:
+    if fmap is None or not _running.image_path:
         return None
     entry = getattr(fmap, 'rw_amax', None)
     if entry is not None and entry[1] == fmap._version:
@@ -562,9 +586,7 @@ class DemodulatedConv2dF(nn.Module):
         b, _, h, w = fmap.shape
         aux = None
         if route.side_strips:
-            aux = _rgb_branch.aux if _rgb_branch.aux is not None else _rgb_side_streams.get((fmap.device, 'aux'))
-            if aux is None:
-                aux = _rgb_side_streams[(fmap.device, 'aux')] = _side_stream(fmap.device)
+            aux = _running.aux if _running.aux is not None else _side_stream(fmap.device, 'aux')
         out = torch.empty(b, self.out_channel, 2 * h + 1, 2 * w + 1, device=fmap.device, dtype=fmap.dtype)
         wp = self.packed_weight()      # (re)packed on the trunk's stream BEFORE the fork
         f22 = route.kernel == 'f22_strips'
@@ -787,7 +809,7 @@ class ToRGBF(nn.Module):
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 out = hip.rgb_combine(partials, self.bias.view(3), skip)
-            _rgb_branch.keep.append((partials,))
+            _running.keep.append((partials,))
             nd = DataBag(d, output=out)
             nd.pop('rgb_partials', None)        # bags that callers see never carry the key
             return nd
@@ -805,10 +827,7 @@ class ToRGBF(nn.Module):
             style = ahead if ahead is not None else conv.modulation(d.style)
             out = hip.to_rgb(d.fmap, conv.weight.view(3, conv.in_channel), style, self.bias.view(3), skip,
                              conv.scale)
-        # The branch reads trunk tensors from another stream: they stay referenced until the join
-        # (Tensor.record_stream would do, but it defers the allocator's reuse of multi-GB blocks
-        # unpredictably and shows up as intermittent hipMalloc stalls at large batch).
-        _rgb_branch.keep.append((d.fmap, d.style))
+        _running.keep.append((d.fmap, d.style))         # read on the side stream: referenced until the join
         return DataBag(d, output=out)
 
 
@@ -908,11 +927,8 @@ class StyledConvSeq(nn.Sequential):
 
     def forward(self, d):
         # ONE reading of the RW_* switches per layer where no generator forward took one (a sliced model: the sweeps)
-        saved, _rgb_branch.switches = _rgb_branch.switches, _switches()
-        try:
+        with _scope(switches=_switches()):
             return self._forward(d)
-        finally:
-            _rgb_branch.switches = saved
 
     def _forward(self, d):
         pre = d.get('prescaled')
@@ -939,7 +955,8 @@ class StyledConvSeq(nn.Sequential):
             d.pop('prescaled', None)
         # ... and this layer's bound for the layer that reads its result, inside the un-hooked forward only (a hooked
         # model under RW_MM=split lets the kernels measure their inputs)
-        reader = _rgb_branch.reader.get(id(self)) if ctx.image_path else None
+        near = _running.neighbours.get(id(self), _NO_NEIGHBOURS)
+        reader = near.reader
         want_amax = reader is not None and routing.matrix_mode(sw, True) == 'split'
 
         def y_bound(height, width):
@@ -957,7 +974,7 @@ class StyledConvSeq(nn.Sequential):
             # inside the un-hooked whole-generator forward the result is read by exactly one consumer, the next
             # styled convolution: where that one runs F(4x4,3x3) -- whose loop is bound by vector instructions beside
             # the MFMAs -- its style multiply (18 packed multiplies per 6x6 item) moves into this layer's epilogue
-            nxt = _rgb_branch.successor.get(id(self)) if ctx.image_path else None
+            nxt = near.successor
             if (nxt is not None and nxt[0]._fusable() and nxt[0]._standard_activation()
                     and not nxt[0].mconv.upsample and nxt[0]._route(ctx, h, w).prescaled):
                 nxt_ahead = _prefetched(nxt[0])
@@ -967,8 +984,8 @@ class StyledConvSeq(nn.Sequential):
             y_amax = y_bound(h, w)
             bound = dict(y_amax=y_amax) if y_amax is not None else {}
             if route.kernel == 'fused':
-                if sw.up_fused2_join and _rgb_branch.stream is not None:
-                    torch.cuda.current_stream().wait_stream(_rgb_branch.stream)
+                if sw.up_fused2_join and _running.stream is not None:
+                    torch.cuda.current_stream().wait_stream(_running.stream)
                 out = hip.conv_transpose3x3s2_blur_fused(
                     fmap, dconv.direct16_weight(), mconv.blur.kernel, dconv.out_channel, dconv.scale,
                     style=style, demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
@@ -992,7 +1009,7 @@ class StyledConvSeq(nn.Sequential):
         else:
             h, w = fmap.shape[2:]
             noise = self.noise.noise_for(d, b, h, w, fmap.device)
-            fin = _rgb_branch.final
+            fin = _running.final
             final = None
             if fin is not None and fin[0] is self:
                 final = routing.final_rgb_route(sw, ctx, dconv.in_channel, dconv.out_channel, h, w)
@@ -1004,8 +1021,8 @@ class StyledConvSeq(nn.Sequential):
                 if skip is not None and tuple(skip.shape[2:]) != (h, w):
                     return self._unfused_final(d_in)
                 main = torch.cuda.current_stream()
-                if _rgb_branch.stream is not None:
-                    main.wait_stream(_rgb_branch.stream)           # the running image comes from the RGB stream
+                if _running.stream is not None:
+                    main.wait_stream(_running.stream)           # the running image comes from the RGB stream
                 rgb_ahead = _prefetched(torgb)
                 rgb_style = rgb_ahead if rgb_ahead is not None else torgb.conv.modulation(d.latent[:, idx])
                 if final == 'direct16':
@@ -1027,7 +1044,7 @@ class StyledConvSeq(nn.Sequential):
             y_amax = y_bound(h, w) if route.reports_bound else None
             # the ToRGB that reads this layer's result (to_rgbK follows layer 2K): its channel sums are left by the
             # convolution itself where the direct-sum kernel runs
-            tr = _rgb_branch.torgb.get(id(self)) if route.rgb_partials else None
+            tr = near.torgb if route.rgb_partials else None
             rgb = None
             if tr is not None:
                 rgb_ahead = _prefetched(tr[0])
@@ -1048,11 +1065,8 @@ class StyledConvSeq(nn.Sequential):
         return DataBag(d, style=style, fmap=out, **extra)
 
     def _unfused_final(self, d):
-        saved, _rgb_branch.final = _rgb_branch.final, None
-        try:
+        with _scope(final=None):
             return self.forward(d)
-        finally:
-            _rgb_branch.final = saved
 
 
 class SeqStyleGAN2(nn.Sequential):
@@ -1149,78 +1163,48 @@ class SeqStyleGAN2(nn.Sequential):
     def forward(self, input):
         if self._checked_f64(input):
             return super().forward(input)       # module by module: no side stream, no micro-batching
-        if self._records_graph(input):
-            # module by module on the caller's stream: no RGB side stream, no style prefetch, no micro-batches, no
-            # ToRGB sums left by a convolution -- every step is then a Function of grad.py / op/ (or a fused block none
-            # of whose own parameters and inputs requires a gradient: StyledConvSeq._fusable), and autograd replays them
-            # on this one stream
-            saved, _rgb_branch.switches = _rgb_branch.switches, switches()
-            try:
+        with _scope(switches=switches()):       # ONE reading of the RW_* switches per forward
+            if self._records_graph(input):
+                # module by module on the caller's stream: no RGB side stream, no style prefetch, no micro-batches, no
+                # ToRGB sums left by a convolution -- every step is then a Function of grad.py / op/ (or a fused block
+                # none of whose own parameters and inputs requires a gradient: StyledConvSeq._fusable), and autograd
+                # replays them on this one stream
                 return super().forward(input)
-            finally:
-                _rgb_branch.switches = saved
-        saved, _rgb_branch.switches = _rgb_branch.switches, switches()     # ONE reading of the RW_* switches per forward
-        try:
             whole = (fusion_enabled() and torch.is_tensor(input) and not self.bag_output and not self.bag_input
-                     and not _rgb_branch.image_path and _unhooked(*self.modules()))
-            return self._forward_whole(input) if whole else self._forward(input)
-        finally:
-            _rgb_branch.switches = saved
+                     and not _running.image_path and _unhooked(*self.modules()))
+            if not whole:
+                return self._forward(input)
+            topology = self._topology()
+            with _scope(image_path=True, neighbours=topology[0]):
+                return self._forward(input, topology)
 
-    def _forward_whole(self, input):
-        _rgb_branch.image_path = True
-        _rgb_branch.successor = self._successors()
-        _rgb_branch.reader = self._readers()
-        _rgb_branch.torgb = self._torgbs()
-        try:
-            return self._forward(input)
-        finally:
-            _rgb_branch.image_path = False
-            _rgb_branch.successor = {}
-            _rgb_branch.reader = {}
-            _rgb_branch.torgb = {}
-
-    def _forward(self, input):
+    def _forward(self, input, topology=None):
         mb, from_res = micro_batch()
-        if (mb and fusion_enabled() and torch.is_tensor(input) and not self.bag_output
-                and not self.bag_input and input.shape[0] > mb and 'up_rgb%d' % (int(math.log2(from_res)) - 2)
-                in self._modules and _rgb_branch.stream is None and _unhooked(*self.modules())):
-            return self._forward_micro(input, mb, from_res)
-        side_ok = (fusion_enabled() and _switches().rgb_stream and torch.is_tensor(input)
-                   and input.is_cuda and not self.bag_output and _rgb_branch.stream is None
+        micro = (mb and fusion_enabled() and torch.is_tensor(input) and not self.bag_output
+                 and not self.bag_input and input.shape[0] > mb and 'up_rgb%d' % (int(math.log2(from_res)) - 2)
+                 in self._modules and _running.stream is None and _unhooked(*self.modules()))
+        side_ok = (not micro and fusion_enabled() and _switches().rgb_stream and torch.is_tensor(input)
+                   and input.is_cuda and not self.bag_output and _running.stream is None
                    and not torch.cuda.is_current_stream_capturing()
                    and _unhooked(*self.modules()))
-        if not side_ok:
+        if not micro and not side_ok:
             return super().forward(input)
-        main = torch.cuda.current_stream()
-        side = _rgb_side_streams.get(input.device)
-        if side is None:
-            side = _rgb_side_streams[input.device] = _side_stream(input.device)
-        aux = _rgb_side_streams.get((input.device, 'aux'))
-        if aux is None:
-            aux = _rgb_side_streams[(input.device, 'aux')] = _side_stream(input.device)
-        _rgb_branch.stream = side
-        _rgb_branch.aux = aux
-        _rgb_branch.final = self._final_pair()
-        try:
+        final = (topology or self._topology())[1] if _switches().fuse_final_rgb else None
+        if micro:
+            return self._forward_micro(input, mb, from_res, final)
+        with contextlib.ExitStack() as scopes:
+            main = scopes.enter_context(_side_streams_joined(input.device))
+            scopes.enter_context(_scope(final=final))
             out = input
             for name, module in self._modules.items():
                 out = module(out)
-                if name == 'latents' and _rgb_branch.image_path and _switches().prefetch_styles:
-                    self._prefetch_modulations(out, aux)
-        finally:
-            _rgb_branch.stream = None
-            _rgb_branch.aux = None
-            _rgb_branch.final = None
-            _rgb_branch.pre = {}
-            _rgb_branch.pre_join = None
-            main.wait_stream(side)                          # join: the image is complete on the caller's stream
-            del _rgb_branch.keep[:]                      # freed to the trunk's pool AFTER the join is queued
+                if name == 'latents' and _running.image_path and _switches().prefetch_styles:
+                    scopes.enter_context(_scope(**self._prefetch_modulations(out, _running.aux)))
         if torch.is_tensor(out):
             out.record_stream(main)
         return out
 
-    def _forward_micro(self, z, mb, from_res):
+    def _forward_micro(self, z, mb, from_res, final):
         """The un-hooked generator on a large batch: the low-resolution steps on the whole batch (their launches
         need it to fill 256 CUs), the steps from resolution `from_res` up on `mb` images at a time, so that the
         feature maps handed from one kernel to the next (134 MB per image at 1024^2) are still in the 256 MB
@@ -1234,8 +1218,7 @@ class SeqStyleGAN2(nn.Sequential):
             d = m(d)
         total = d.latent.shape[0]
         out = None
-        _rgb_branch.final = self._final_pair()
-        try:
+        with _scope(final=final):
             for s in range(0, total, mb):
                 e = min(s + mb, total)
                 part = DataBag({key: (v[s:e] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == total else v)
@@ -1247,8 +1230,6 @@ class SeqStyleGAN2(nn.Sequential):
                     out = part.new_empty((total,) + tuple(part.shape[1:]))
                 out[s:e] = part
                 del part
-        finally:
-            _rgb_branch.final = None
         return out
 
     def _prefetch_modulations(self, d, aux):
@@ -1259,7 +1240,7 @@ class SeqStyleGAN2(nn.Sequential):
         the trunk and two of them (in front of layers 15 / 17) sat 0.3 - 0.6 ms behind the grid-stride workgroups of
         the RGB branch waiting for a wave slot (rocprofv3 trace of round 2).  The first layer's are computed inline
         (it needs them at once); the trunk waits for the rest at its first use (_prefetched).  Values are those of
-        the per-layer path: same kernels, same inputs."""
+        the per-layer path: same kernels, same inputs.  Returns the fields to install for the rest of the forward."""
         pre = {}
         todo = []
         for name, mod in self._modules.items():
@@ -1273,7 +1254,7 @@ class SeqStyleGAN2(nn.Sequential):
             elif isinstance(kids[1], ToRGBF):
                 todo.append((kids[0].index, kids[1]))
         if len(todo) < 3:
-            return
+            return {}
         main = torch.cuda.current_stream()
         aux.wait_stream(main)                       # the latents come from the trunk
         with torch.cuda.stream(aux):
@@ -1284,70 +1265,42 @@ class SeqStyleGAN2(nn.Sequential):
                 else:
                     style = mod.mconv.modulation(DataBag(style=lat)).style
                     pre[id(mod)] = (style, mod.mconv.dconv.demod_factors(style))
-        _rgb_branch.pre = pre
-        _rgb_branch.pre_join = aux
+        return dict(pre=pre, pre_join=aux)
 
-    def _successors(self):
-        """{id(upsampling StyledConvSeq): (next StyledConvSeq, its latent index)} for the layer pairs
-        'layer(2j+1)' (upsample) -> 'layer(2j+2)' that follow each other directly in this sequence."""
-        out = {}
-        names = list(self._modules)
-        for a, b in zip(names, names[1:]):
-            ma, mb = self._modules[a], self._modules[b]
-            sa, sb = getattr(ma, 'sconv', None), getattr(mb, 'sconv', None)
-            if not (isinstance(sa, StyledConvSeq) and isinstance(sb, StyledConvSeq)):
+    def _topology(self):
+        """({id(StyledConvSeq): _Neighbours}, final) of this sequence as it stands now, from one walk of its steps (the
+        rewriters edit sequences between forwards).  `final`: (last styled conv 'layer{num_layers+1}', the ToRGBF of
+        the step 'to_rgb{log_size-1}' directly behind it, that step's latent index), or None.  A step's styled conv is
+        its child 'sconv' ('layer2': 'conv', which only a reader or a ToRGB may follow); the step behind hands its
+        latent index over where it has a single PickLatent -- as its first child for a successor, and as the first of
+        exactly two, in front of the ToRGBF, for a ToRGB (models.py:126-131)."""
+        near, final, prev = {}, None, None
+        last = ('layer%d' % (self.num_layers + 1), 'to_rgb%d' % (self.log_size - 1))
+        steps = list(self._modules.items())
+        for (name, step), (nname, nstep) in zip(steps, steps[1:] + [(None, None)]):
+            sconv = getattr(step, 'sconv', None)
+            conv = sconv or getattr(step, 'conv', None)
+            if not isinstance(conv, StyledConvSeq):
                 continue
-            if not getattr(sa.mconv, 'upsample', False) or getattr(sb.mconv, 'upsample', False):
-                continue
-            picks = [m for m in mb.children() if isinstance(m, PickLatent)]
-            if len(picks) == 1 and list(mb.children())[0] is picks[0]:
-                out[id(sa)] = (sb, picks[0].index)
-        return out
-
-    def _readers(self):
-        """{id(StyledConvSeq): the next StyledConvSeq of this sequence} -- the layer that reads its feature map (the ToRGB
-        / up_rgb steps in between pass it on untouched)."""
-        out, prev = {}, None
-        for mod in self._modules.values():
-            conv = getattr(mod, 'sconv', None) or getattr(mod, 'conv', None)
-            if isinstance(conv, StyledConvSeq):
-                if prev is not None:
-                    out[id(prev)] = conv
-                prev = conv
-        return out
-
-    def _torgbs(self):
-        """{id(StyledConvSeq): (ToRGBF, latent index)} for every 'layerN' directly followed by a 'to_rgbK' step whose first
-        child picks the latent and whose second is the ToRGB (models.py:126-131)."""
-        out = {}
-        names = list(self._modules)
-        for a, b in zip(names, names[1:]):
-            sconv = getattr(self._modules[a], 'sconv', None) or getattr(self._modules[a], 'conv', None)
-            rgbseq = self._modules[b]
-            torgb = getattr(rgbseq, 'rgb', None)
-            if not isinstance(sconv, StyledConvSeq) or not isinstance(torgb, ToRGBF):
-                continue
-            kids = list(rgbseq.children())
-            if len(kids) == 2 and isinstance(kids[0], PickLatent) and kids[1] is torgb:
-                out[id(sconv)] = (torgb, kids[0].index)
-        return out
-
-    def _final_pair(self):
-        """(last StyledConvSeq, the ToRGBF that consumes it, latent index of that ToRGB) or None."""
-        if not _switches().fuse_final_rgb:
-            return None
-        names = list(self._modules)
-        last_rgb = 'to_rgb%d' % (self.log_size - 1)
-        last_layer = 'layer%d' % (self.num_layers + 1)
-        if last_rgb not in names or last_layer not in names or names.index(last_rgb) != names.index(last_layer) + 1:
-            return None
-        layer, rgbseq = self._modules[last_layer], self._modules[last_rgb]
-        sconv = getattr(layer, 'sconv', None)
-        torgb = getattr(rgbseq, 'rgb', None)
-        picks = [m for m in rgbseq.children() if isinstance(m, PickLatent)]
-        if not isinstance(sconv, StyledConvSeq) or not isinstance(torgb, ToRGBF) or len(picks) != 1:
-            return None
-        return sconv, torgb, picks[0].index
+            if prev is not None:        # the ToRGB / up_rgb steps in between pass the feature map on untouched
+                near[id(prev)] = near[id(prev)]._replace(reader=conv)
+            prev = conv
+            kids = list(nstep.children()) if nstep is not None else []
+            picks = [m for m in kids if isinstance(m, PickLatent)]
+            index = picks[0].index if len(picks) == 1 else None
+            leads = index is not None and kids[0] is picks[0]
+            nconv, rgb = getattr(nstep, 'sconv', None), getattr(nstep, 'rgb', None)
+            successor = torgb = None
+            if (conv is sconv and leads and isinstance(nconv, StyledConvSeq)
+                    and getattr(conv.mconv, 'upsample', False) and not getattr(nconv.mconv, 'upsample', False)):
+                successor = (nconv, index)
+            if isinstance(rgb, ToRGBF):
+                if leads and len(kids) == 2 and kids[1] is rgb:
+                    torgb = (rgb, index)
+                if conv is sconv and index is not None and (name, nname) == last:
+                    final = (conv, rgb, index)
+            near[id(conv)] = _Neighbours(None, successor, torgb)
+        return near, final
 
     def bag_from_z(self, z):
         return InputLatent()(z)

@@ -67,15 +67,13 @@ def test_a_bound_travels_on_its_tensor_and_only_inside_the_unhooked_forward():
     bound = torch.ones(64)
     t.rw_amax = (bound, t._version)
     assert models._amax_of(t) is None                       # not inside SeqStyleGAN2.forward
-    models._rgb_branch.image_path = True
-    try:
+    with models._scope(image_path=True):
         assert models._amax_of(t) is bound
         assert models._amax_of(t[:1]) is None               # a slice is another tensor
         assert models._amax_of(None) is None
         t.add_(1.0)                                         # edited in place (a hook): the bound no longer describes it
         assert models._amax_of(t) is None
-    finally:
-        models._rgb_branch.image_path = False
+    assert vars(models._running) == models._idle()
 
 
 @pytest.mark.skipif(shutil.which('hipcc') is None and not os.path.exists('/opt/rocm/bin/hipcc'), reason='no hipcc')

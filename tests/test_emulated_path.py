@@ -366,13 +366,13 @@ def test_style_handed_over_premultiplied_changes_nothing(emulated_hip, monkeypat
 
 
 def test_successor_pairs_and_hand_over_guards(emulated_hip):
-    """SeqStyleGAN2._successors pairs every upsampling layer with the styled convolution that follows it directly,
+    """The `successor` field of SeqStyleGAN2._topology pairs every upsampling layer with the styled convolution that follows it directly,
     and a pre-scaled map can only be consumed by a fused stride-1 layer: anything else refuses it loudly."""
     from rewriting_amd.utils.stylegan2 import models
     g = load_golden('gen_s64_cm1')
     meta = golden_meta(g)
     model = build_stylegan(meta['size'], meta['truncation'], meta['channel_multiplier'])
-    succ = model._successors()
+    succ = {key: near.successor for key, near in model._topology()[0].items() if near.successor is not None}
     ups = [m.sconv for n, m in model.named_children() if n.startswith('layer') and getattr(m, 'sconv', None) is not None
            and m.sconv.mconv.upsample]
     assert len(ups) == 4 and set(succ) == {id(u) for u in ups}
@@ -458,7 +458,7 @@ def test_bounds_are_produced_only_where_the_next_layer_reads_them(emulated_hip, 
     real_new, real_abs = hip.new_bound, hip.absmax
     monkeypatch.setattr(hip, 'new_bound', lambda n, dev: (made.append(n), real_new(n, dev))[1])
     monkeypatch.setattr(hip, 'absmax', lambda x: (measured.append(tuple(x.shape)), real_abs(x))[1])
-    readers = model._readers()
+    readers = {key: near.reader for key, near in model._topology()[0].items() if near.reader is not None}
     names = {id(getattr(m, 'sconv', None) or getattr(m, 'conv', None)): n for n, m in model.named_children()}
     chain = [(names[k], names[id(v)]) for k, v in readers.items()]
     assert chain[0] == ('layer2', 'layer3') and chain[-1] == ('layer9', 'layer10') and len(chain) == 8
@@ -516,7 +516,87 @@ def test_bounds_are_produced_only_where_the_next_layer_reads_them(emulated_hip, 
         with torch.no_grad():
             inst(z)
     assert not made and not measured
-    assert not models._rgb_branch.reader and not models._rgb_branch.image_path
+    assert vars(models._running) == models._idle()         # the record of the running forward is idle
+
+
+def test_topology_of_an_edited_sequence(emulated_hip):
+    """SeqStyleGAN2._topology describes the sequence as it stands when a forward starts (the rewriters edit sequences
+    between forwards): a ToRGB step taken out leaves the layer in front of it without one and every other record as it
+    was; without the last ToRGB step there is no `final`, and the forward still runs."""
+    g = load_golden('gen_s64_cm1')
+    meta = golden_meta(g)
+    model = build_stylegan(meta['size'], meta['truncation'], meta['channel_multiplier'])
+    z = torch.from_numpy(g['z'])[:2]
+    fmaps = []
+    hook = model.layer10.register_forward_hook(lambda m, i, o: fmaps.append(o.fmap))
+    with torch.no_grad():
+        model(z)
+    near, final = model._topology()
+    assert len(near) == 9 and final == (model.layer10.sconv, model.to_rgb5.rgb, 9)
+    assert near[id(model.layer6.sconv)].torgb == (model.to_rgb3.rgb, 5)
+    steps = dict(model._modules)
+    del model._modules['to_rgb3']
+    edited, edited_final = model._topology()
+    assert edited_final == final and set(edited) == set(near)
+    assert edited[id(model.layer6.sconv)] == near[id(model.layer6.sconv)]._replace(torgb=None)
+    assert all(edited[key] == near[key] for key in near if key != id(model.layer6.sconv))
+    model._modules.clear()
+    model._modules.update(steps)
+    assert model._topology() == (near, final)
+    del model._modules['to_rgb5']
+    edited, edited_final = model._topology()
+    assert edited_final is None
+    assert edited[id(model.layer10.sconv)] == near[id(model.layer10.sconv)]._replace(torgb=None)
+    assert all(edited[key] == near[key] for key in near if key != id(model.layer10.sconv))
+    with torch.no_grad():
+        model(z)
+    hook.remove()
+    assert len(fmaps) == 2 and torch.equal(fmaps[0], fmaps[1])          # same steps, same inputs, up to the last layer
+
+
+class _Stop(Exception):
+    pass
+
+
+@pytest.mark.parametrize('mode', ['unhooked', 'hooked', 'unfused', 'micro'])
+def test_a_forward_that_raises_leaves_nothing_behind(emulated_hip, monkeypatch, mode):
+    """An exception in the middle of a generator forward -- un-hooked, inside nethook.InstrumentedModel, RW_FUSE=0, in
+    the slice loop of RW_MICRO_BATCH -- leaves every field of the running forward's record at its idle default, and the
+    next forward gives the image from before."""
+    import contextlib
+    from rewriting_amd.utils import nethook
+    from rewriting_amd.utils.stylegan2 import models
+    if mode == 'unfused':
+        monkeypatch.setenv('RW_FUSE', '0')
+    if mode == 'micro':
+        monkeypatch.setenv('RW_MICRO_BATCH', '1:32')            # layer7 (16^2 -> 32^2) runs in the slices
+    g = load_golden('gen_s64_cm1')
+    meta = golden_meta(g)
+    model = build_stylegan(meta['size'], meta['truncation'], meta['channel_multiplier'])
+    z = torch.from_numpy(g['z'])[:2]
+    seen = []
+
+    def stop(module, args, output):
+        seen.append({name: value for name, value in vars(models._running).items() if not value == models._idle()[name]})
+        raise _Stop()
+    with contextlib.ExitStack() as stack, torch.no_grad():
+        run = model
+        if mode == 'hooked':
+            run = stack.enter_context(nethook.InstrumentedModel(model))
+            run.retain_layer('layer7.sconv.mconv.adain', detach=False)        # layer7 then runs module by module
+        before = run(z)
+        assert vars(models._running) == models._idle()
+        handle = (model.layer7.sconv.activate if mode == 'hooked' else model.layer7).register_forward_hook(stop)
+        with pytest.raises(_Stop):
+            run(z)
+        handle.remove()
+        assert vars(models._running) == models._idle()
+        assert torch.equal(run(z), before)
+    # the forward was inside its scopes when it raised (not vacuous): a snapshot of the switches in every mode (the
+    # hooked model's is its layer7's own), the image path and the neighbours in the whole un-hooked forwards, the fused last layer in the slices
+    installed = {'unhooked': {'switches', 'image_path', 'neighbours'}, 'hooked': {'switches'}, 'unfused': {'switches'},
+                 'micro': {'switches', 'image_path', 'neighbours', 'final'}}[mode]
+    assert len(seen) == 1 and set(seen[0]) == installed, seen
 
 
 def test_fused_transposed_conv_and_blur_layer_stays_inside_the_image_tolerance(emulated_hip, monkeypatch):

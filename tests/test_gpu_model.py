@@ -493,6 +493,46 @@ def test_micro_batched_forward_equals_one_launch(monkeypatch):
         assert (got_p - want_p).abs().max().item() < 5e-5, spec
 
 
+@pytest.mark.parametrize('micro, layer', [(None, 'layer9'), ('1:128', 'layer13')])
+def test_a_forward_that_raises_leaves_streams_and_record_as_they_were(monkeypatch, micro, layer):
+    """A Python exception in the middle of the un-hooked forward -- on the side streams with the modulations
+    prefetched (layer9), or inside the slice loop of RW_MICRO_BATCH (layer13, 256^2) -- in the smallest generator whose
+    last layer runs ToRGB in its epilogue: the record of the running forward is idle afterwards, the caller's stream
+    is current, and the next forward gives the image from before, bit for bit (the join with the RGB stream was
+    queued before the kept tensors were released)."""
+    from rewriting_amd.utils.stylegan2 import models, routing
+    if micro:
+        monkeypatch.setenv('RW_MICRO_BATCH', micro)
+    model = build_stylegan(256, 0.7, 1, device=DEV)
+    last = model.layer14.sconv.mconv.dconv
+    ctx = routing.Context(True, True, False, micro is None, micro is None, False)
+    assert routing.final_rgb_route(routing.switches(), ctx, last.in_channel, last.out_channel, 256, 256) is not None
+    assert 'up_rgb5' in model._modules and model._topology()[1][0] is model.layer14.sconv
+    z = torch.randn(2, 512, generator=torch.Generator().manual_seed(11)).to(DEV)
+    seen = []
+
+    def stop(module, args, output):
+        seen.append({name for name, value in vars(models._running).items() if not value == models._idle()[name]})
+        raise KeyError('stop')
+    with torch.no_grad():
+        stream = torch.cuda.current_stream()
+        before = model(z)
+        torch.cuda.synchronize()
+        handle = getattr(model, layer).register_forward_hook(stop)
+        with pytest.raises(KeyError, match='stop'):
+            model(z)
+        handle.remove()
+        torch.cuda.synchronize()
+        assert vars(models._running) == models._idle()
+        assert torch.cuda.current_stream() == stream
+        after = model(z)
+        torch.cuda.synchronize()
+    assert torch.equal(after, before)
+    # not vacuous: the forward that raised was on its side streams / in its slices, with the last layer's ToRGB fused
+    engaged = {'final'} | ({'stream', 'aux', 'keep', 'pre'} if micro is None else set())
+    assert len(seen) == 1 and engaged <= seen[0], seen
+
+
 def test_premultiplied_style_and_one_pass_layers_on_the_image_path(monkeypatch):
     """The un-hooked forward's extra fusions against the same forward without them: the next layer's style multiplied
     into an upsampling layer's result (RW_PRESCALE: the same products, up to the FMA contraction of the in-loop

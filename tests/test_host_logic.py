@@ -332,10 +332,10 @@ def test_sweep_batch_never_starves_a_rank(monkeypatch):
 
 
 def test_final_pair_identifies_last_styled_conv_and_its_to_rgb():
-    """SeqStyleGAN2._final_pair: the layer whose ToRGB is fused into its epilogue in the un-hooked forward."""
+    """`final` of SeqStyleGAN2._topology: the layer whose ToRGB is fused into its epilogue in the un-hooked forward."""
     from rewriting_amd.utils.stylegan2 import models as sg
     g = sg.SeqStyleGAN2(64, 512, 2, mconv='seq')
-    sconv, torgb, idx = g._final_pair()
+    sconv, torgb, idx = g._topology()[1]
     assert sconv is g.layer10.sconv and torgb is g.to_rgb5.rgb
     assert idx == g.n_latent - 1 == 9                      # ToRGB of the last resolution takes the last latent
     assert torgb.skip and torgb.conv.in_channel == sconv.mconv.dconv.out_channel
