@@ -249,6 +249,16 @@ def _prefetched(module):
     return entry
 
 
+def _style_of(module, ahead, latent, index=None):
+    """The style of a StyledConvSeq / ToRGBF for the row latent[:, index] (`latent` itself without an index): `ahead`, what
+    _prefetched(module) gave the caller (whose stream then waits for it), else computed now on the current stream."""
+    styled = isinstance(module, StyledConvSeq)
+    if ahead is not None:
+        return ahead[0] if styled else ahead
+    row = latent if index is None else latent[:, index]
+    return module.mconv.modulation(DataBag(style=row)).style if styled else module.conv.modulation(row)
+
+
 def _switches():
     """The snapshot of the RW_* switches that the running generator forward took at its start, else a fresh one."""
     return _running.switches or switches()
@@ -520,6 +530,9 @@ class DemodulatedConv2dF(nn.Module):
         return self._derived.get('wino4_split' if split else 'wino4', self.weight,
                                  lambda: hip.pack_conv_weight_wino4(self.weight, split=split))
 
+    def bf16x6_weight(self):
+        return self._derived.get('packed_bf16x3', self.weight, lambda: hip.pack_conv_weight_bf16x3(self.weight))
+
     def route(self, ctx, h, w, blur=None):
         """THE routing decision for a map of h x w.  blur: the layer's BlurF where the caller runs the whole StyledConv."""
         if not self.upsample:
@@ -535,49 +548,72 @@ class DemodulatedConv2dF(nn.Module):
     def squared_sums(self):
         return self._derived.get('wsq', self.weight, lambda: hip.weight_sqsum(self.weight, self.scale))
 
-    def demod_factors(self, style):
+    def demod_factors(self, style, ahead=None):
+        """The demodulation factors: `ahead` where the running forward computed them up front, else computed now."""
+        if ahead is not None:
+            return ahead
         return hip.demod(self.squared_sums(), style) if self.demodulate else None
 
-    def run(self, fmap, style, style_on_load, demod=None, x_amax=None, y_amax=None, rgb=None, weight_changes=False,
-            route=None, **epilogue):
+    # route kernel (routing.STRIDE1_KERNELS, the whole-layer UP_KERNELS) -> (stem of its wrapper in `hip`, looked up there at
+    # call time, the weight packed for it); stem + '_to_rgb': ToRGB in the epilogue, stem + '_rgb_partial': its partial sums
+    KERNELS = {
+        'direct16': ('conv3x3_direct16', lambda m, route, fir: m.direct16_weight()),
+        'wino4_split': ('conv3x3_wino4', lambda m, route, fir: m.wino4_weight(True)),
+        'wino4': ('conv3x3_wino4', lambda m, route, fir: m.wino4_weight(False)),
+        'wino': ('conv3x3_wino', lambda m, route, fir: m.wino_weight()),
+        'bf16x6': ('conv3x3_bf16x6', lambda m, route, fir: m.bf16x6_weight()),
+        'gemm': ('conv3x3', lambda m, route, fir: m.packed_weight()),          # the one that takes impl=conv_impl()
+        'fused': ('conv_transpose3x3s2_blur_fused', lambda m, route, fir: m.direct16_weight()),    # and the FIR itself
+        'one_pass_direct16': ('conv_transpose3x3s2_blur_direct16', lambda m, route, fir: m.up_blur_direct16_weight(fir)),
+        'one_pass_wino4': ('conv_transpose3x3s2_blur_wino4', lambda m, route, fir: m.up_blur_wino4_weight(fir, route.split)),
+    }
+
+    def run(self, fmap, style, style_on_load, demod=None, x_amax=None, y_amax=None, rgb=None, to_rgb=None,
+            weight_changes=False, route=None, **epilogue):
         """Dispatches on `route` (self.route(...) of the map; computed here if the caller has not).  x_amax: the bound of
-        |fmap| if the producer of fmap left one (hip.new_bound; the kernels of route.reads_bound take it and measure the
-        map themselves otherwise); y_amax: a hip.new_bound buffer that receives the bound of the result where
-        route.reports_bound; rgb: (ToRGB weight (3, out), its style (B, out), its scale), only where route.rgb_partials --
-        the result is then (map, partial images); weight_changes: the caller differentiates with respect to the weight."""
+        |fmap| if its producer left one (hip.new_bound; the kernels of route.reads_bound take it and measure the map
+        themselves otherwise); y_amax: a hip.new_bound buffer that receives the result's bound where route.reports_bound;
+        rgb: (ToRGB weight (3, out), its style (B, out), its scale), only where route.rgb_partials -- the result is then
+        (map, partial images); to_rgb: (ToRGB weight, its style, bias, running image, scale) with a routing.FinalRgbRoute
+        -- the result is then (None, image); weight_changes: the caller differentiates with respect to the weight."""
         if route is None:
             route = self.route(_context(fmap, weight_changes), fmap.shape[-2], fmap.shape[-1])
         if rgb is not None and (self.upsample or not route.rgb_partials):
             raise RuntimeError('run(rgb=...) on a layer that does not leave ToRGB partial sums')
-        if demod is None:
-            demod = self.demod_factors(style)
-        args = dict(style=style if style_on_load else None, demod=demod)
+        args = dict(style=style if style_on_load else None, demod=self.demod_factors(style, demod))
         if self.upsample:
             return self._run_two_pass(fmap, route, x_amax, args)
+        stem, packed = self.KERNELS[route.kernel]
         args.update(epilogue)
         if route.reads_bound:
             args['x_amax'] = x_amax
+        head = (fmap, packed(self, route, None), self.out_channel, self.scale)
+        if to_rgb is not None:
+            return getattr(hip, stem + '_to_rgb')(*head, *to_rgb, **args)
         if route.reports_bound:
             args['y_amax'] = y_amax
-        kernel = route.kernel
-        if kernel == 'direct16' and rgb is not None:
-            return hip.conv3x3_direct16_rgb_partial(fmap, self.direct16_weight(), self.out_channel, self.scale,
-                                                    rgb[0], rgb[1], rgb[2], **args)
-        if kernel == 'direct16':
-            return hip.conv3x3_direct16(fmap, self.direct16_weight(), self.out_channel, self.scale, **args)
-        if kernel in ('wino4_split', 'wino4'):
-            return hip.conv3x3_wino4(fmap, self.wino4_weight(kernel == 'wino4_split'), self.out_channel, self.scale, **args)
-        if kernel == 'wino':
-            return hip.conv3x3_wino(fmap, self.wino_weight(), self.out_channel, self.scale, **args)
-        if kernel == 'bf16x6':
-            wb = self._derived.get('packed_bf16x3', self.weight, lambda: hip.pack_conv_weight_bf16x3(self.weight))
-            return hip.conv3x3_bf16x6(fmap, wb, self.out_channel, self.scale, **args)
-        return hip.conv3x3(fmap, self.packed_weight(), self.out_channel, self.scale, impl=conv_impl(), **args)
+        if rgb is not None:
+            return getattr(hip, stem + '_rgb_partial')(*head, *rgb, **args)
+        if route.kernel == 'gemm':
+            args['impl'] = conv_impl()
+        return getattr(hip, stem)(*head, **args)
+
+    def run_whole_layer(self, fmap, style, route, fir, demod=None, **rest):
+        """The upsampling layer in one launch (route.runs_layer): transposed convolution, blur by `fir`, then what `rest`
+        names -- noise, the epilogue, post_scale and the bounds, as the kernel's wrapper takes them.  Under
+        RW_UP_FUSED2_JOIN the current stream first waits for the running forward's RGB stream, in front of the fused kernel."""
+        stem, packed = self.KERNELS[route.kernel]
+        fused = route.kernel == 'fused'
+        if fused and _switches().up_fused2_join and _running.stream is not None:
+            torch.cuda.current_stream().wait_stream(_running.stream)
+        return getattr(hip, stem)(fmap, packed(self, route, fir), *((fir,) if fused else ()), self.out_channel, self.scale,
+                                  style=style, demod=self.demod_factors(style, demod), **rest)
 
     def _run_two_pass(self, fmap, route, x_amax, args):
         """The transposed convolution alone, to the (2H+1) x (2W+1) map (its blur is the caller's)."""
         if route.kernel == 'plain':
             return hip.conv_transpose3x3s2(fmap, self.packed_weight(), self.out_channel, self.scale, impl=conv_impl(), **args)
+        f22 = {'f22_strips': True, 'halo_strips': False}[route.kernel]        # no other name: KeyError
         # quad tiles (F(2,2) where it applies, else the direct halo kernel) and the border row / column strips write
         # disjoint elements of the same map.  The strips (latency-bound, 2 % of the step) go to an auxiliary stream beside
         # the tiles: the one of the running whole-generator forward, else (a sliced or hooked model: the statistics
@@ -589,7 +625,6 @@ class DemodulatedConv2dF(nn.Module):
             aux = _running.aux if _running.aux is not None else _side_stream(fmap.device, 'aux')
         out = torch.empty(b, self.out_channel, 2 * h + 1, 2 * w + 1, device=fmap.device, dtype=fmap.dtype)
         wp = self.packed_weight()      # (re)packed on the trunk's stream BEFORE the fork
-        f22 = route.kernel == 'f22_strips'
         uf = self.up_wino_weight(route.split) if f22 else None
         if f22 and route.split and x_amax is None:
             x_amax = hip.absmax(fmap)
@@ -824,12 +859,10 @@ class ToRGBF(nn.Module):
         ahead = _prefetched(self)
         side.wait_stream(torch.cuda.current_stream())      # the feature map and the latent come from the trunk
         with torch.cuda.stream(side):
-            style = ahead if ahead is not None else conv.modulation(d.style)
-            out = hip.to_rgb(d.fmap, conv.weight.view(3, conv.in_channel), style, self.bias.view(3), skip,
-                             conv.scale)
+            out = hip.to_rgb(d.fmap, conv.weight.view(3, conv.in_channel), _style_of(self, ahead, d.style),
+                             self.bias.view(3), skip, conv.scale)
         _running.keep.append((d.fmap, d.style))         # read on the side stream: referenced until the join
         return DataBag(d, output=out)
-
 
     def _forward_f64(self, d):
         """The double form: the running image (upsampled here if it is smaller), the style, ToRGB -- on the caller's
@@ -931,142 +964,108 @@ class StyledConvSeq(nn.Sequential):
             return self._forward(d)
 
     def _forward(self, d):
+        received = d                # with the hand-over key, if any: what a re-entry must see
         pre = d.get('prescaled')
         if not self._fusable(d):
             return self._module_by_module(d)
-        mconv, act = self.mconv, self.activate
         # `pre`: the layer in front already multiplied this layer's style into fmap (and computed it)
         ahead = _prefetched(self)
-        style = pre if pre is not None else ahead[0] if ahead is not None else \
-            mconv.modulation(DataBag(style=d.style)).style
-        demod = ahead[1] if ahead is not None else None        # else: computed where it is used
-        fmap = d.fmap
-        b = fmap.shape[0]
-        dconv = mconv.dconv
+        style = pre if pre is not None else _style_of(self, ahead, d.style)
+        demod = ahead[1] if ahead is not None else None        # else: computed in front of the launch (dconv.demod_factors)
         if not self._standard_activation():
             return self._module_by_module(d)
-        sw = _switches()
-        ctx = _context(fmap)
-        d_in = d                    # as received (with the hand-over key, if any): what a re-entry must see
-        # the producer's bound on |fmap| (for the kernels that read one), else None
-        x_amax = None if sw.mm_no_handover else _amax_of(fmap)
-        if pre is not None:
+        fmap, dconv = d.fmap, self.mconv.dconv
+        sw, ctx = _switches(), _context(fmap)
+        x_amax = None if sw.mm_no_handover else _amax_of(fmap)      # the producer's bound on |fmap|, if it left one
+        if pre is not None:         # bags that callers see never carry the key
             d = DataBag(d)
             d.pop('prescaled', None)
-        # ... and this layer's bound for the layer that reads its result, inside the un-hooked forward only (a hooked
-        # model under RW_MM=split lets the kernels measure their inputs)
-        near = _running.neighbours.get(id(self), _NO_NEIGHBOURS)
-        reader = near.reader
-        want_amax = reader is not None and routing.matrix_mode(sw, True) == 'split'
-
-        def y_bound(height, width):
-            if not want_amax or not reader._fusable() or not reader._route(ctx, height, width).reads_bound:
-                return None
-            return hip.new_bound(b * dconv.out_channel * height * width, fmap.device)
-        post = None
-        rgb_partials = None
-        epilogue = dict(noise_w=self.noise.weight, bias=act.bias, act=True)
-        if mconv.upsample:
+        if self.mconv.upsample:
             if pre is not None:
                 raise RuntimeError('a pre-scaled feature map reached an upsampling layer')
-            route = self._route(ctx, fmap.shape[2], fmap.shape[3])
-            h, w = 2 * fmap.shape[2], 2 * fmap.shape[3]
-            # inside the un-hooked whole-generator forward the result is read by exactly one consumer, the next
-            # styled convolution: where that one runs F(4x4,3x3) -- whose loop is bound by vector instructions beside
-            # the MFMAs -- its style multiply (18 packed multiplies per 6x6 item) moves into this layer's epilogue
-            nxt = near.successor
-            if (nxt is not None and nxt[0]._fusable() and nxt[0]._standard_activation()
-                    and not nxt[0].mconv.upsample and nxt[0]._route(ctx, h, w).prescaled):
-                nxt_ahead = _prefetched(nxt[0])
-                post = nxt_ahead[0] if nxt_ahead is not None else \
-                    nxt[0].mconv.modulation(DataBag(style=d.latent[:, nxt[1]])).style
-            noise = self.noise.noise_for(d, b, h, w, fmap.device)
-            y_amax = y_bound(h, w)
-            bound = dict(y_amax=y_amax) if y_amax is not None else {}
-            if route.kernel == 'fused':
-                if sw.up_fused2_join and _running.stream is not None:
-                    torch.cuda.current_stream().wait_stream(_running.stream)
-                out = hip.conv_transpose3x3s2_blur_fused(
-                    fmap, dconv.direct16_weight(), mconv.blur.kernel, dconv.out_channel, dconv.scale,
-                    style=style, demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
-                    post_scale=post, x_amax=x_amax, **bound, **epilogue)
-            elif route.kernel in ('one_pass_direct16', 'one_pass_wino4'):
-                if route.kernel == 'one_pass_direct16':
-                    one_pass, packed = hip.conv_transpose3x3s2_blur_direct16, dconv.up_blur_direct16_weight(mconv.blur.kernel)
-                else:
-                    one_pass, packed = hip.conv_transpose3x3s2_blur_wino4, dconv.up_blur_wino4_weight(mconv.blur.kernel, route.split)
-                if not route.split:
-                    y_amax = None           # the fp32 phase kernel neither reads nor reports a bound
-                mm = dict(x_amax=x_amax, y_amax=y_amax) if route.split else {}
-                out = one_pass(
-                    fmap, packed, dconv.out_channel, dconv.scale,
-                    style=style, demod=demod if demod is not None else dconv.demod_factors(style), noise=noise,
-                    post_scale=post, **mm, **epilogue)
-            else:
-                wide = dconv.run(fmap, style, style_on_load=True, demod=demod, x_amax=x_amax, route=route)
-                out = hip.blur_noise_act(wide, mconv.blur.kernel, noise, self.noise.weight, act.bias, post_scale=post,
-                                         **bound)
-        else:
-            h, w = fmap.shape[2:]
-            noise = self.noise.noise_for(d, b, h, w, fmap.device)
-            fin = _running.final
-            final = None
-            if fin is not None and fin[0] is self:
-                final = routing.final_rgb_route(sw, ctx, dconv.in_channel, dconv.out_channel, h, w)
+            return self._run_upsampling(d, style, demod, ctx, x_amax)
+        b, _, h, w = fmap.shape
+        epilogue = dict(noise=self.noise.noise_for(d, b, h, w, fmap.device), noise_w=self.noise.weight, bias=self.activate.bias,
+                        act=True)
+        fin = _running.final
+        if fin is not None and fin[0] is self:
+            final = routing.final_rgb_route(sw, ctx, dconv.in_channel, dconv.out_channel, h, w)
             if final is not None:
-                # last styled conv of the un-hooked generator: ToRGB runs in its epilogue and the feature
-                # map, which nothing else reads, is never written (models.py:639-655 fused)
-                torgb, idx = fin[1], fin[2]
-                skip = d.output if torgb.skip else None
-                if skip is not None and tuple(skip.shape[2:]) != (h, w):
-                    return self._unfused_final(d_in)
-                main = torch.cuda.current_stream()
-                if _running.stream is not None:
-                    main.wait_stream(_running.stream)           # the running image comes from the RGB stream
-                rgb_ahead = _prefetched(torgb)
-                rgb_style = rgb_ahead if rgb_ahead is not None else torgb.conv.modulation(d.latent[:, idx])
-                if final == 'direct16':
-                    fused, packed = hip.conv3x3_direct16_to_rgb, dconv.direct16_weight()
-                elif final in ('wino4_split', 'wino4'):
-                    fused, packed = hip.conv3x3_wino4_to_rgb, dconv.wino4_weight(final == 'wino4_split')
-                elif final == 'wino':
-                    fused, packed = hip.conv3x3_wino_to_rgb, dconv.wino_weight()
-                else:
-                    fused, packed = hip.conv3x3_to_rgb, dconv.packed_weight()
-                mm = dict(x_amax=x_amax) if final in ('direct16', 'wino4_split') else {}
-                _, rgb = fused(
-                    fmap, packed, dconv.out_channel, dconv.scale,
-                    torgb.conv.weight.view(3, torgb.conv.in_channel), rgb_style, torgb.bias.view(3), skip,
-                    torgb.conv.scale, style=style if pre is None else None,
-                    demod=demod if demod is not None else dconv.demod_factors(style), noise=noise, **mm, **epilogue)
-                return DataBag(d, style=style, fmap=None, fused_rgb=rgb)
-            route = self._route(ctx, h, w)
-            y_amax = y_bound(h, w) if route.reports_bound else None
-            # the ToRGB that reads this layer's result (to_rgbK follows layer 2K): its channel sums are left by the
-            # convolution itself where the direct-sum kernel runs
-            tr = near.torgb if route.rgb_partials else None
-            rgb = None
-            if tr is not None:
-                rgb_ahead = _prefetched(tr[0])
-                rgb_style = rgb_ahead if rgb_ahead is not None else tr[0].conv.modulation(d.latent[:, tr[1]])
-                rgb = (tr[0].conv.weight.view(3, tr[0].conv.in_channel), rgb_style, tr[0].conv.scale)
-            out = dconv.run(fmap, style, style_on_load=pre is None, demod=demod, x_amax=x_amax, y_amax=y_amax, rgb=rgb,
-                            route=route, noise=noise, **epilogue)
-            if rgb is not None:
-                out, rgb_partials = out
-        # hand-overs, only inside the un-hooked forward: the bound rides on the tensor itself (_amax_of)
-        extra = {}
-        if rgb_partials is not None:
-            extra['rgb_partials'] = rgb_partials
+                return self._run_final(d, style, demod, x_amax, pre is None, epilogue, final, received)
+        return self._run_stride1(d, style, demod, ctx, x_amax, pre is None, epilogue)
+
+    def _result_bound(self, ctx, fmap, height, width):
+        """A buffer for the bound of the result where its reader takes one (inside the un-hooked forward only), else None."""
+        reader = _running.neighbours.get(id(self), _NO_NEIGHBOURS).reader
+        if (reader is None or routing.matrix_mode(_switches(), True) != 'split' or not reader._fusable()
+                or not reader._route(ctx, height, width).reads_bound):
+            return None
+        return hip.new_bound(fmap.shape[0] * self.mconv.dconv.out_channel * height * width, fmap.device)
+
+    def _run_upsampling(self, d, style, demod, ctx, x_amax):
+        """One launch where route.runs_layer, else two passes.  Hands over the result's bound (on the tensor) and `prescaled`."""
+        fmap, dconv, fir = d.fmap, self.mconv.dconv, self.mconv.blur.kernel
+        route = self._route(ctx, fmap.shape[2], fmap.shape[3])
+        h, w = 2 * fmap.shape[2], 2 * fmap.shape[3]
+        # inside the un-hooked forward the result has one reader, the next styled convolution: where that one runs F(4x4,3x3)
+        # (vector-bound beside its MFMAs) its style multiply, 18 packed multiplies per 6x6 item, moves into this epilogue
+        post = None
+        nxt = _running.neighbours.get(id(self), _NO_NEIGHBOURS).successor
+        if (nxt is not None and nxt[0]._fusable() and nxt[0]._standard_activation()
+                and not nxt[0].mconv.upsample and nxt[0]._route(ctx, h, w).prescaled):
+            post = _style_of(nxt[0], _prefetched(nxt[0]), d.latent, nxt[1])
+        noise = self.noise.noise_for(d, fmap.shape[0], h, w, fmap.device)
+        y_amax = self._result_bound(ctx, fmap, h, w)
+        if route.runs_layer and not route.split:
+            y_amax = None               # allocated and dropped: the fp32 phase kernel neither reads nor reports a bound
+        bound = dict(y_amax=y_amax) if y_amax is not None else {}
+        if route.runs_layer:
+            bound.update(dict(x_amax=x_amax) if route.split else {})
+            out = dconv.run_whole_layer(fmap, style, route, fir, demod, noise=noise, post_scale=post, **bound,
+                                        noise_w=self.noise.weight, bias=self.activate.bias, act=True)
+        else:
+            wide = dconv.run(fmap, style, style_on_load=True, demod=demod, x_amax=x_amax, route=route)
+            out = hip.blur_noise_act(wide, fir, noise, self.noise.weight, self.activate.bias, post_scale=post, **bound)
         if y_amax is not None:
             out.rw_amax = (y_amax, out._version)
-        if post is not None:        # bags that callers see never carry the key
-            extra['prescaled'] = post
-        return DataBag(d, style=style, fmap=out, **extra)
+        return DataBag(d, style=style, fmap=out, **({} if post is None else dict(prescaled=post)))
 
-    def _unfused_final(self, d):
-        with _scope(final=None):
-            return self.forward(d)
+    def _run_final(self, d, style, demod, x_amax, style_on_load, epilogue, route, received):
+        """The last layer of the un-hooked generator, ToRGB in its epilogue: the map is never written.  Hands over `fused_rgb`."""
+        _, torgb, idx = _running.final
+        skip = d.output if torgb.skip else None
+        if skip is not None and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
+            with _scope(final=None):        # not fused after all: as the bag came, before anything was launched
+                return self.forward(received)
+        main = torch.cuda.current_stream()          # this form needs a device: without one it raises here, nothing launched
+        if _running.stream is not None:
+            main.wait_stream(_running.stream)       # the running image comes from the RGB stream
+        rgb_style = _style_of(torgb, _prefetched(torgb), d.latent, idx)
+        to_rgb = (torgb.conv.weight.view(3, torgb.conv.in_channel), rgb_style, torgb.bias.view(3), skip, torgb.conv.scale)
+        _, rgb = self.mconv.dconv.run(d.fmap, style, style_on_load, demod=demod, x_amax=x_amax, to_rgb=to_rgb, route=route,
+                                      **epilogue)
+        return DataBag(d, style=style, fmap=None, fused_rgb=rgb)
+
+    def _run_stride1(self, d, style, demod, ctx, x_amax, style_on_load, epilogue):
+        """The stride-1 layer in one launch.  Hands over the bound of its result (on the tensor) and `rgb_partials`."""
+        fmap, (h, w) = d.fmap, d.fmap.shape[2:]
+        route = self._route(ctx, h, w)
+        y_amax = self._result_bound(ctx, fmap, h, w) if route.reports_bound else None
+        # the ToRGB that reads the result (to_rgbK follows layer 2K): the direct-sum kernel leaves its channel sums itself
+        tr = _running.neighbours.get(id(self), _NO_NEIGHBOURS).torgb if route.rgb_partials else None
+        rgb = None
+        if tr is not None:
+            torgb, idx = tr
+            rgb_style = _style_of(torgb, _prefetched(torgb), d.latent, idx)
+            rgb = (torgb.conv.weight.view(3, torgb.conv.in_channel), rgb_style, torgb.conv.scale)
+        out = self.mconv.dconv.run(fmap, style, style_on_load, demod=demod, x_amax=x_amax, y_amax=y_amax, rgb=rgb,
+                                   route=route, **epilogue)
+        extra = {}
+        if rgb is not None:
+            out, extra['rgb_partials'] = out
+        if y_amax is not None:
+            out.rw_amax = (y_amax, out._version)
+        return DataBag(d, style=style, fmap=out, **extra)
 
 
 class SeqStyleGAN2(nn.Sequential):

@@ -1,8 +1,9 @@
 """Which kernel runs a styled convolution: the RW_* switches, read in ONE place, and one pure decision function per kind
 of layer (snapshot of the switches, calling context, shape -> a record; only the ``hip.*_supported`` / ``*_applicable``
 helpers are consulted).  models.py dispatches on the record and decides nothing itself: a new route is one branch here
-and one case in ``DemodulatedConv2dF.run`` / ``StyledConvSeq.forward``; tests/test_routes.py holds every context and
-switch setting to the launches recorded under tests/golden/."""
+and one row of ``DemodulatedConv2dF.KERNELS`` (the names are STRIDE1_KERNELS / UP_KERNELS below); ``StyledConvSeq`` reads
+the records' flags only.  tests/test_routes.py holds every context and switch setting to the launches recorded under
+tests/golden/."""
 import os
 from collections import namedtuple
 
@@ -89,16 +90,43 @@ def switches():
 # forward has its RGB / auxiliary side stream; weight_changes: the caller differentiates with respect to the weight.
 Context = namedtuple('Context', 'image_path on_device capturing rgb_stream aux_stream weight_changes')
 
-# kernel: 'direct16' | 'wino4_split' | 'wino4' | 'wino' | 'bf16x6' | 'gemm'; specialised: the twelve-wave direct sum that
-# needs its style on load; rgb_partials: it also leaves the ToRGB channel sums; reads_bound / reports_bound: it takes a
-# bound of |input| (measuring the map itself without one) / writes the bound of its result; prescaled: the layer in front
-# may hand it a map already multiplied by its style.
+STRIDE1_KERNELS = ('direct16', 'wino4_split', 'wino4', 'wino', 'bf16x6', 'gemm')
+# these run the layer's blur, noise and activation too; the other upsampling kernels leave the (2H+1) x (2W+1) map
+WHOLE_LAYER_KERNELS = ('fused', 'one_pass_direct16', 'one_pass_wino4')
+UP_KERNELS = WHOLE_LAYER_KERNELS + ('f22_strips', 'halo_strips', 'plain')
+
+# kernel: one of STRIDE1_KERNELS; specialised: the twelve-wave direct sum that needs its style on load; rgb_partials: it
+# also leaves the ToRGB channel sums; reads_bound / reports_bound: it takes a bound of |input| (measuring the map itself
+# without one) / writes the bound of its result; prescaled: the layer in front may hand it a map already multiplied by
+# its style.
 Stride1Route = namedtuple('Stride1Route', 'kernel specialised rgb_partials reads_bound reports_bound prescaled')
 
-# kernel: 'fused' | 'one_pass_direct16' | 'one_pass_wino4' | 'f22_strips' | 'halo_strips' | 'plain'; split: the F(2,2) /
-# phase kernel runs in the split form; side_strips: the border strips go to the auxiliary stream beside the tiles;
-# reads_bound: ADVICE to the layer in front, inside the un-hooked forward, to leave a bound on its result (see there).
-UpRoute = namedtuple('UpRoute', 'kernel split side_strips reads_bound')
+# kernel: one of UP_KERNELS; split: the F(2,2) / phase kernel runs in the split form; side_strips: the border strips go
+# to the auxiliary stream beside the tiles; reads_bound: ADVICE to the layer in front, inside the un-hooked forward, to
+# leave a bound on its result (see there); runs_layer: the kernel is one of WHOLE_LAYER_KERNELS.
+UpRoute = namedtuple('UpRoute', 'kernel split side_strips reads_bound runs_layer')
+
+# kernel: one of STRIDE1_KERNELS, in its form with ToRGB in the epilogue; reads_bound: as Stride1Route's.  Nothing reads
+# the result but ToRGB, so none of them reports a bound.
+FinalRgbRoute = namedtuple('FinalRgbRoute', 'kernel reads_bound')
+
+
+def _stride1(kernel, *flags):
+    if kernel not in STRIDE1_KERNELS:
+        raise ValueError(kernel)
+    return Stride1Route(kernel, *flags)
+
+
+def _up(kernel, *flags):
+    if kernel not in UP_KERNELS:
+        raise ValueError(kernel)
+    return UpRoute(kernel, *flags, kernel in WHOLE_LAYER_KERNELS)
+
+
+def _final_rgb(kernel, reads_bound):
+    if kernel not in STRIDE1_KERNELS:
+        raise ValueError(kernel)
+    return FinalRgbRoute(kernel, reads_bound)
 
 
 def conv_algo(sw, image_path):
@@ -173,14 +201,14 @@ def stride1_route(sw, ctx, in_ch, out_ch, h, w):
             # the RGB stream then adds a few small images instead of re-reading the feature map (4.3 GB for layer 16 at
             # batch 64); without them ToRGB re-reads the map on the RGB stream
             partials = ctx.image_path and ctx.rgb_stream and sw.rgb_partial and out_ch % 32 == 0
-            return Stride1Route('direct16', specialised, partials, True, True, sw.prescale and not specialised)
-        return Stride1Route('wino4_split' if split else 'wino4', False, False, split, split, sw.prescale)
+            return _stride1('direct16', specialised, partials, True, True, sw.prescale and not specialised)
+        return _stride1('wino4_split' if split else 'wino4', False, False, split, split, sw.prescale)
     if (ctx.image_path and split and sw.direct16_small and algo == 'winograd4' and plain and min(h, w) >= 32
             and _direct16(sw, 'conv', in_ch, out_ch, h, w)):
         # the 32^2 layer, too narrow for F(4x4,3x3): 0.8 against 1.4 ms on the fp32 F(2x2,3x3) kernel at batch 64, the
         # forward +1.7 % (same box, interleaved: profiles/r06aq).  The layer in front runs an fp32 kernel, so its blur
         # pass reports the bound
-        return Stride1Route('direct16', False, False, True, True, False)
+        return _stride1('direct16', False, False, True, True, False)
     if (not ctx.image_path and not ctx.weight_changes and not ctx.capturing and sw.direct16_hooked
             and sw.conv_algo is None and matrix_mode(sw, False, 'up') == 'split' and plain
             and _direct16(sw, 'conv', in_ch, out_ch, h, w)):
@@ -190,12 +218,12 @@ def stride1_route(sw, ctx, in_ch, out_ch, h, w):
         # outside the un-hooked forward.  Not where the weight is being optimised (every re-packing reads the weights'
         # maximum back to the host, hip._split_scale: two launches and a sync per layer and iteration) and not while
         # the stream is captured (the read-back would fail)
-        return Stride1Route('direct16', False, False, True, False, False)
+        return _stride1('direct16', False, False, True, False, False)
     if algo in ('winograd', 'winograd4') and plain and hip.wino_supported(out_ch, in_ch, h, w):
-        return Stride1Route('wino', False, False, False, False, False)
+        return _stride1('wino', False, False, False, False, False)
     if sw.conv_precision == 'bf16x6' and sw.conv_impl == 0 and hip.bf16x6_supported(out_ch, in_ch, w):
-        return Stride1Route('bf16x6', False, False, False, False, False)
-    return Stride1Route('gemm', False, False, False, False, False)
+        return _stride1('bf16x6', False, False, False, False, False)
+    return _stride1('gemm', False, False, False, False, False)
 
 
 def upsample_route(sw, ctx, in_ch, out_ch, h, w, whole_layer):
@@ -213,7 +241,7 @@ def upsample_route(sw, ctx, in_ch, out_ch, h, w, whole_layer):
     if (one_pass and sw.up_fused2 and in_ch <= sw.up_fused2_max_in
             and (_split_part(sw, True, 'up1') if ctx.image_path else _split_part(sw, False, 'up') and sw.up_fused2_hooked)
             and hip.tconv_blur_supported(out_ch, in_ch, h, w)):
-        return UpRoute('fused', True, False, advice)
+        return _up('fused', True, False, advice)
     split = _split_part(sw, ctx.image_path, 'up')
     f22 = (sw.up_algo == 'winograd' and sw.conv_impl == 0 and hip.up_strips_applicable(out_ch, in_ch)
            and hip.conv_transpose_wino_supported(out_ch, in_ch, h, w))
@@ -225,31 +253,31 @@ def upsample_route(sw, ctx, in_ch, out_ch, h, w, whole_layer):
             and (sw.up_algo == 'winograd4' or conv_algo(sw, ctx.image_path) == 'winograd4' and in_ch <= ONE_PASS_UP_MAX_IN)):
         split1 = _split_part(sw, ctx.image_path, 'up1')
         if split1 and _direct16(sw, 'up', in_ch, out_ch, h, w):
-            return UpRoute('one_pass_direct16', True, False, advice)
+            return _up('one_pass_direct16', True, False, advice)
         # reads_bound stays the approximate predicate it was: with RW_MM_PARTS=up (not up1) the fp32 phase kernel
         # runs and ignores the bound that this advice makes the layer in front leave (one reduction launch)
-        return UpRoute('one_pass_wino4', split1, False, advice and (split1 or f22_split))
+        return _up('one_pass_wino4', split1, False, advice and (split1 or f22_split))
     # 3. two passes: quad tiles -- F(2,2) on the four phases (25 instead of 36 multiplies per 2x2 block of quads) or
     # the direct halo kernel -- beside the border row / column strips, then the blur pass
     side = ctx.aux_stream or (ctx.on_device and sw.strip_stream and not ctx.capturing)
     if f22:
         # reads_bound, approximate again: under RW_CONV_PRECISION=bf16x6 the split F(2,2) kernel runs and measures
         # its input itself (hip.absmax), because the advice is given in plain fp32 mode only
-        return UpRoute('f22_strips', f22_split, side, advice and f22_split)
+        return _up('f22_strips', f22_split, side, advice and f22_split)
     if sw.conv_impl == 0 and side and hip.up_halo_applicable(out_ch, in_ch, w):
-        return UpRoute('halo_strips', False, True, False)
-    return UpRoute('plain', False, False, False)
+        return _up('halo_strips', False, True, False)
+    return _up('plain', False, False, False)
 
 
 def final_rgb_route(sw, ctx, in_ch, out_ch, h, w):
-    """The last styled convolution of the un-hooked generator with ToRGB in its epilogue: Stride1Route's kernel, or None."""
+    """The last styled convolution of the un-hooked generator with ToRGB in its epilogue: a FinalRgbRoute, or None."""
     if not (_plain(sw) and hip.to_rgb_fusable(out_ch, in_ch, w)):
         return None
     algo = conv_algo(sw, ctx.image_path)
     if algo == 'winograd4' and sw.rgb_f4 and hip.wino4_to_rgb_supported(out_ch, in_ch, h, w):
         if not _split_part(sw, ctx.image_path, 'w4'):
-            return 'wino4'
-        return 'direct16' if _direct16(sw, 'rgb', in_ch, out_ch, h, w) else 'wino4_split'
+            return _final_rgb('wino4', False)
+        return _final_rgb('direct16' if _direct16(sw, 'rgb', in_ch, out_ch, h, w) else 'wino4_split', True)
     if algo in ('winograd', 'winograd4') and out_ch == 32 and hip.wino_supported(out_ch, in_ch, h, w):
-        return 'wino'
-    return 'gemm'
+        return _final_rgb('wino', False)
+    return _final_rgb('gemm', False)

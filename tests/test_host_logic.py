@@ -555,3 +555,60 @@ def test_hooked_models_leave_a_layer_whose_weight_requires_grad_on_the_fp32_kern
         assert (got.detach() - want).abs().max().item() < 1e-4     # the fp32 kernel's result: the image barely moves
     finally:
         layer.weight.requires_grad_(False)
+
+
+def test_the_kernel_table_names_every_route_kernel_and_only_wrappers_that_exist(monkeypatch):
+    """DemodulatedConv2dF.KERNELS has one row per stride-1 kernel name and per whole-layer upsampling kernel name of
+    routing.py, and every wrapper name that a row can produce -- the stem, stem + '_to_rgb' for every kernel that
+    final_rgb_route returns over the switch settings of tests/route_spy.py, the partial-sum form of the kernels that leave
+    partial sums -- is a callable of rewriting_amd.hip."""
+    from rewriting_amd import hip
+    from rewriting_amd.utils.stylegan2 import models, routing
+    from tests import route_spy
+    from tests.conftest import build_stylegan
+    table = models.DemodulatedConv2dF.KERNELS
+    assert sorted(table) == sorted(routing.STRIDE1_KERNELS + routing.WHOLE_LAYER_KERNELS)
+    assert len(set(routing.STRIDE1_KERNELS + routing.UP_KERNELS)) == len(routing.STRIDE1_KERNELS + routing.UP_KERNELS)
+    assert set(routing.WHOLE_LAYER_KERNELS) < set(routing.UP_KERNELS)
+    for name in [n for n in os.environ if n.startswith('RW_')]:
+        monkeypatch.delenv(name)
+    ctx = routing.Context(True, True, False, True, True, False)
+    final, partial = set(), set()
+    for size in (256, 1024):
+        model = build_stylegan(size, 0.7, device='cpu')
+        last = [m for m in model.modules() if isinstance(m, models.DemodulatedConv2dF)][-1]
+        assert not last.upsample
+        for env in route_spy.SETTINGS:
+            with monkeypatch.context() as mp:
+                for name, value in env.items():
+                    mp.setenv(name, value)
+                sw = routing.switches()
+                route = routing.final_rgb_route(sw, ctx, last.in_channel, last.out_channel, size, size)
+                if route is not None:
+                    assert route.kernel in routing.STRIDE1_KERNELS
+                    final.add(route.kernel)
+                route = routing.stride1_route(sw, ctx, last.in_channel, last.out_channel, size, size)
+                if route.rgb_partials:
+                    partial.add(route.kernel)
+    assert len(final) >= 4 and partial, (final, partial)       # both forms are reached (not vacuous)
+    names = ([stem for stem, _ in table.values()] + [table[k][0] + '_to_rgb' for k in final]
+             + [table[k][0] + '_rgb_partial' for k in partial])
+    for name in names:
+        assert callable(getattr(hip, name, None)), name
+
+
+def test_a_route_whose_kernel_has_no_row_raises_and_names_it(emulated_hip):
+    """No fallback: a misspelt or new kernel name never runs another kernel in its place (it used to run the implicit GEMM)."""
+    import torch
+    from rewriting_amd.utils.stylegan2 import models
+    dconv = models.DemodulatedConv2dF(16, 16, 3)
+    fmap, style = torch.randn(1, 16, 8, 8), 1 + 0.3 * torch.randn(1, 16)
+    route = dconv.route(models._context(fmap), 8, 8)
+    with torch.no_grad():
+        assert dconv.run(fmap, style, True, route=route).shape == (1, 16, 8, 8)
+        with pytest.raises((KeyError, RuntimeError), match='no_such'):
+            dconv.run(fmap, style, True, route=route._replace(kernel='no_such'))
+    up = models.DemodulatedConv2dF(16, 16, 3, upsample=True)
+    route = up.route(models._context(fmap), 8, 8)
+    with torch.no_grad(), pytest.raises((KeyError, RuntimeError), match='no_such'):
+        up.run(fmap, style, True, route=route._replace(kernel='no_such'))
