@@ -508,6 +508,17 @@ int rw_second_moment_f32(const float* a, float* mom2, int64_t rows, int channels
 int rw_channel_sums_f32(const float* a, float* sums, int64_t rows, int channels, int64_t hw,
                         int layout, int square_input, rw_stream_t stream);
 
+/* Search (rewrite/ganrewrite.py:582-594, :610-650): the response of every pixel of a key map to K query keys,
+ *   heat[b][k][p] = sum_c keys[k][c] * a[b][c][p],     peak[b][k] = max_p heat[b][k][p]
+ * a (images, C, hw) NCHW as the generator left it, keys (K, C), heat (images, K, hw), peak (images, K) nullable.
+ * a is read once for all K keys.  The sum of a pixel runs over the channels in order, one fused multiply-add each: a
+ * row of heat is bit-identical whatever images, K, the key's slot or the alignment of the pointers, and peak is the
+ * plain maximum of the heat row.  RW_ERR_BAD_ARGUMENT (nothing launched) for a null a / keys / heat, images, channels
+ * or hw < 1, K outside 1 .. RW_KEY_RESPONSE_MAX_KEYS, or C * hw / K * hw / K * C / images past 31 bits. */
+#define RW_KEY_RESPONSE_MAX_KEYS 8
+int rw_key_response_f32(const float* a, const float* keys, float* heat, float* peak,
+                        int64_t images, int channels, int64_t hw, int n_keys, rw_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * The rank-constrained solve -- replaces the body of ProgressiveGanRewriter.insert
  * (rewrite/ganrewrite.py:254-298) and of linear_insert (:201-252) for a SeqStyleGAN2 layer

@@ -888,6 +888,39 @@ def channel_sums(a, nchw=False, square_input=False):
     return sums
 
 
+KEY_RESPONSE_MAX_KEYS = 8       # RW_KEY_RESPONSE_MAX_KEYS of include/rewriting_hip.h
+
+
+def key_response(acts, keys, want_peak=True):
+    """heat (B, K, H, W) = sum_c keys[k][c] * acts[b][c], peak (B, K) = heat's maximum over the pixels (None unless
+    want_peak).  acts (B, C, H, W) is read as it lies -- a view that is not contiguous is refused, not copied: it may be
+    the resident key maps of rewrite/search.py; keys (K, C) or (C,).  More than KEY_RESPONSE_MAX_KEYS keys run in
+    groups of that many; a key's rows do not depend on its group (see the header)."""
+    if isinstance(acts, torch.Tensor) and not acts.is_contiguous():
+        raise RuntimeError('rewriting_amd: the key map must be contiguous (B, C, H, W); it is read in place')
+    acts = _dev(acts, 'key map')
+    keys = _dev(keys, 'keys')
+    if keys.dim() == 1:
+        keys = keys[None]
+    if acts.dim() != 4 or keys.dim() != 2 or keys.shape[1] != acts.shape[1] or keys.device != acts.device:
+        raise RuntimeError('rewriting_amd: key map %s on %s does not go with keys %s on %s'
+                           % (tuple(acts.shape), acts.device, tuple(keys.shape), keys.device))
+    b, c, h, w = acts.shape
+    heats, peaks = [], []
+    for k0 in range(0, keys.shape[0], KEY_RESPONSE_MAX_KEYS):
+        group = keys[k0:k0 + KEY_RESPONSE_MAX_KEYS]
+        heat = torch.empty(b, group.shape[0], h, w, device=acts.device, dtype=acts.dtype)
+        peak = torch.empty(b, group.shape[0], device=acts.device, dtype=acts.dtype) if want_peak else None
+        if heat.numel():
+            check(lib().rw_key_response_f32(_p(acts), _p(group), _p(heat), _p(peak), b, c, h * w, group.shape[0],
+                                            _stream()))
+        heats.append(heat)
+        peaks.append(peak)
+    if len(heats) == 1:
+        return heats[0], peaks[0]
+    return torch.cat(heats, dim=1), (torch.cat(peaks, dim=1) if want_peak else None)
+
+
 # ------------------------------------------------------------------ solve
 def project_weight(w, context, base=None, out=None):
     """out = base + P(w), P = projected_conv (rewrite/ganrewrite.py:806-813).  w (..., O, I, kh, kw)."""

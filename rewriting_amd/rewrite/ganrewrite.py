@@ -30,6 +30,7 @@ import torch
 
 from ..utils import nethook, pbar, renormalize, tally
 from .. import hip, parallel
+from . import search
 
 # Debug globals the reference's notebooks peek at (rewrite/ganrewrite.py:13-14); kept assigned.
 (all_obs, all_weight, all_CinvK, all_kCinvK, e_val, e_vec, kbasis, row_dirs, q) = (None,) * 9
@@ -42,7 +43,8 @@ class ProgressiveGanRewriter(object):
                  use_linear_insert=False,    # optimise Lambda with W = W0 + Lambda D
                  tight_paste=True,           # optimise over the pasted crop, not the whole map
                  alpha_area=True,            # composite with the painted area, not its bounding box
-                 key_method='zca'):          # or 'svd', 'mean', 'gandissect'
+                 key_method='zca',           # or 'svd', 'mean', 'gandissect'
+                 device_search=False):       # ranking_for_key answers through search() (rewrite/search.py)
         if next(model.parameters()).dtype == torch.float64:
             raise RuntimeError('rewriting_amd: the rewriters (key statistics, solver, adjoints) are float32 only and the model '
                                'is torch.float64 -- the double path is the generator\'s forward alone; rewrite a .float() '
@@ -58,6 +60,8 @@ class ProgressiveGanRewriter(object):
         self.low_rank_insert = low_rank_insert
         self.low_rank_gradient = low_rank_gradient
         self.use_linear_insert = use_linear_insert
+        self.device_search = device_search
+        self.search_index = None
         self.device = next(model.parameters()).device
         self.zds = zds
         self.model = copy.deepcopy(model)
@@ -597,6 +601,9 @@ class ProgressiveGanRewriter(object):
     def ranking_for_key(self, key, k=12):
         """Seeds whose key map responds most to ``key`` + the quantile statistics of the response
         (the UI's "Search"; rewrite/ganrewrite.py:582-594)."""
+        if self.device_search:
+            numbers, _, rq = self.search(key, k)
+            return numbers, rq
         tensorkey = key.to(self.device)[None, :, None, None]
 
         def image_max_sel(zbatch):
@@ -605,6 +612,21 @@ class ProgressiveGanRewriter(object):
             return heatmap.reshape(heatmap.shape[0], -1).max(1)[0], heatmap.reshape(-1)[:, None]
         topk, rq = self._sweep(tally.tally_topk_and_quantile, image_max_sel, self.zds, k=k)
         return topk.result()[1], rq
+
+    def search(self, keys, k=12):
+        """ranking_for_key for keys (K, C) or (C,) on the key-response kernel: per key the top-k seeds by descending
+        peak, their peaks, and the RunningQuantile of every response; one pass over the resident key maps when
+        build_search_index() was called, a sweep otherwise -- the same numbers either way (rewrite/search.py)."""
+        return search.search(self, keys, k)
+
+    def build_search_index(self, max_bytes=None):
+        """Computes the key map of every seed once and keeps it on the device (len(zds) x C x H x W float32; ValueError
+        and nothing allocated if that is more than max_bytes).  It survives edits of the target layer; a change of the
+        context model drops it at the next search."""
+        return search.build_index(self, max_bytes)
+
+    def drop_search_index(self):
+        self.search_index = None
 
     def _overlay(self):
         """utils.imgviz (heat-map / mask overlays, outside the hot path): this package's own if it has one,
