@@ -499,14 +499,29 @@ int rw_to_rgb_f32(const float* x, const float* w, const float* style, const floa
  *             (rewrite/ganrewrite.py:90-93);
  *   layout 1: a is (batch, C, hw) NCHW, rows = batch*hw -- the key map as the generator
  *             produced it (no permute copy).
- * workspace: >= rw_second_moment_workspace_bytes(C, rows) bytes of device scratch. */
+ * workspace: >= rw_second_moment_workspace_bytes(C, rows) bytes of device scratch = ksplit * C * C * 4, one C x C slab
+ *   per row slice: with tiles of 128 channels (64 when C < 128), pairs = tiles (tiles + 1) / 2 and chunks of 16 rows,
+ *   ksplit = min(512 / pairs, max(chunks / 8, 1)), at least 1 (integer divisions).
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null a / mom2 / workspace, rows or C < 1, a layout outside {0, 1}.
+ * RW_ERR_UNSUPPORTED (nothing launched): layout 0 with C % 4 != 0; layout 1 with hw % 16 != 0 or rows % hw != 0. */
 int64_t rw_second_moment_workspace_bytes(int channels, int64_t rows);
 int rw_second_moment_f32(const float* a, float* mom2, int64_t rows, int channels, int64_t hw,
                          int layout, void* workspace, rw_stream_t stream);
 
-/* per-channel sum and sum of squares over rows (same layouts); sums (2,C) are OVERWRITTEN. */
+/* per-channel sum and sum of squares over rows (same layouts, any C and hw); sums (2,C) are OVERWRITTEN.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null a / sums, rows or C < 1, layout 1 with rows % hw != 0. */
 int rw_channel_sums_f32(const float* a, float* sums, int64_t rows, int channels, int64_t hw,
                         int layout, int square_input, rw_stream_t stream);
+
+/* The same reductions about a pivot, for a centred sum of squares that does not cancel against mean^2
+ * (RunningVariance.add, utils/runningstats.py:770-777: (a - batch_mean).pow(2).sum(0)).  v is the sample, squared when
+ * square_input; the pivot p_c is the mean of the first v of channel c (layout 1: min(hw, 256) pixels of image 0; layout
+ * 0: min(rows, 16) rows).  moments (3,C) are OVERWRITTEN:
+ *   moments[0][c] = p_c,   moments[1][c] = sum (v - p_c),   moments[2][c] = sum (v - p_c)^2
+ * so that mean = p + S1 / n and sum (v - mean)^2 = S2 - S1^2 / n.  The map is read once.  Same layouts, same refusals as
+ * rw_channel_sums_f32. */
+int rw_channel_moments_f32(const float* a, float* moments, int64_t rows, int channels, int64_t hw,
+                           int layout, int square_input, rw_stream_t stream);
 
 /* Search (rewrite/ganrewrite.py:582-594, :610-650): the response of every pixel of a key map to K query keys,
  *   heat[b][k][p] = sum_c keys[k][c] * a[b][c][p],     peak[b][k] = max_p heat[b][k][p]

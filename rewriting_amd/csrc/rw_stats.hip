@@ -199,66 +199,112 @@ extern "C" int rw_second_moment_f32(const float* a, float* mom2, int64_t rows, i
 // ---------------------------------------------------------------------------------------
 // per-channel sum / sum of squares
 // ---------------------------------------------------------------------------------------
+// PIVOT = false: the raw sums of v and v^2 (rw_channel_sums_f32, out (2,C)).
+// PIVOT = true:  the same sums of v - p_c (rw_channel_moments_f32, out (3,C) = p, S1, S2), p_c the mean of the channel's
+// first samples (NCHW: up to 256 pixels of image 0; rows: up to 16 rows): the centred sum of squares S2 - S1^2 / n then
+// cancels against n (mean - p)^2, a fraction of the variance, not against n mean^2.  Every workgroup of a channel
+// forms the same p, from the same samples in the same order.  v is the sample, squared when square_input.
+#define ST_PIVOT_ROWS 16
+
 // NCHW: one workgroup per channel, deterministic.
+template <bool PIVOT>
 __global__ void __launch_bounds__(256) channel_sums_nchw_kernel(const float* __restrict__ a,
-                                                                float* __restrict__ sums,
+                                                                float* __restrict__ out,
                                                                 int64_t batch, int channels,
                                                                 int64_t hw, int square_input) {
   __shared__ float red[4];
   const int c = blockIdx.x;
+  float p = 0.f;
+  if (PIVOT) {
+    const int m = hw < 256 ? (int)hw : 256;
+    float v = 0.f;
+    if ((int)threadIdx.x < m) {
+      v = a[(int64_t)c * hw + threadIdx.x];
+      if (square_input) v = v * v;
+    }
+    p = rw_block_sum_256(v, red) / (float)m;
+  }
   float s1 = 0.f, s2 = 0.f;
   for (int64_t b = 0; b < batch; ++b) {
     const float* row = a + (b * channels + c) * hw;
     for (int64_t i = threadIdx.x; i < hw; i += 256) {
       float v = row[i];
       if (square_input) v = v * v;
+      if (PIVOT) v -= p;
       s1 += v; s2 += v * v;
     }
   }
   s1 = rw_block_sum_256(s1, red);
   s2 = rw_block_sum_256(s2, red);
-  if (threadIdx.x == 0) { sums[c] = s1; sums[channels + c] = s2; }
+  if (threadIdx.x == 0) {
+    if (PIVOT) { out[c] = p; out[channels + c] = s1; out[2 * channels + c] = s2; }
+    else { out[c] = s1; out[channels + c] = s2; }
+  }
 }
 
 // (rows, C): 64 channels x 4 row lanes per workgroup, row-split over blockIdx.y, fp32 atomics.
+template <bool PIVOT>
 __global__ void __launch_bounds__(256) channel_sums_rows_kernel(const float* __restrict__ a,
-                                                                float* __restrict__ sums,
+                                                                float* __restrict__ out,
                                                                 int64_t rows, int channels,
                                                                 int square_input) {
   __shared__ float l1[4][64], l2[4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f, s2 = 0.f, p = 0.f;
   if (c < channels) {
+    if (PIVOT) {
+      const int m = rows < ST_PIVOT_ROWS ? (int)rows : ST_PIVOT_ROWS;
+      for (int r = 0; r < m; ++r) {
+        float v = a[(int64_t)r * channels + c];
+        if (square_input) v = v * v;
+        p += v;
+      }
+      p /= (float)m;
+    }
     for (int64_t r = (int64_t)blockIdx.y * 4 + rl; r < rows; r += (int64_t)gridDim.y * 4) {
       float v = a[r * channels + c];
       if (square_input) v = v * v;
+      if (PIVOT) v -= p;
       s1 += v; s2 += v * v;
     }
   }
   l1[rl][cl] = s1; l2[rl][cl] = s2;
   __syncthreads();
   if (rl == 0 && c < channels) {
+    float* sums = PIVOT ? out + channels : out;
+    if (PIVOT && blockIdx.y == 0) out[c] = p;        // a plain store: row 0 takes no atomics
     atomicAdd(&sums[c], l1[0][cl] + l1[1][cl] + l1[2][cl] + l1[3][cl]);
     atomicAdd(&sums[channels + c], l2[0][cl] + l2[1][cl] + l2[2][cl] + l2[3][cl]);
   }
 }
 
-extern "C" int rw_channel_sums_f32(const float* a, float* sums, int64_t rows, int channels,
-                                   int64_t hw, int layout, int square_input, rw_stream_t stream) {
-  RW_CHECK_ARG(a && sums && rows > 0 && channels > 0 && (layout == 0 || layout == 1));
+template <bool PIVOT>
+static int channel_sums_launch(const float* a, float* out, int64_t rows, int channels, int64_t hw, int layout,
+                               int square_input, rw_stream_t stream) {
+  RW_CHECK_ARG(a && out && rows > 0 && channels > 0 && (layout == 0 || layout == 1));
   hipStream_t s = rw_s(stream);
   if (layout == 1) {
     RW_CHECK_ARG(hw > 0 && rows % hw == 0);
-    hipLaunchKernelGGL(channel_sums_nchw_kernel, dim3(channels), dim3(256), 0, s, a, sums, rows / hw,
+    hipLaunchKernelGGL((channel_sums_nchw_kernel<PIVOT>), dim3(channels), dim3(256), 0, s, a, out, rows / hw,
                        channels, hw, square_input);
     return RW_LAUNCH_RESULT();
   }
-  hipError_t e = hipMemsetAsync(sums, 0, 2 * (size_t)channels * sizeof(float), s);
+  hipError_t e = hipMemsetAsync(out, 0, (PIVOT ? 3 : 2) * (size_t)channels * sizeof(float), s);
   if (e != hipSuccess) return (int)e;
   int64_t gy = rw_cdiv(rows, 4 * 64);
   if (gy > 512) gy = 512;
-  hipLaunchKernelGGL(channel_sums_rows_kernel, dim3((unsigned)rw_cdiv(channels, 64), (unsigned)gy),
-                     dim3(256), 0, s, a, sums, rows, channels, square_input);
+  hipLaunchKernelGGL((channel_sums_rows_kernel<PIVOT>), dim3((unsigned)rw_cdiv(channels, 64), (unsigned)gy),
+                     dim3(256), 0, s, a, out, rows, channels, square_input);
   return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_channel_sums_f32(const float* a, float* sums, int64_t rows, int channels,
+                                   int64_t hw, int layout, int square_input, rw_stream_t stream) {
+  return channel_sums_launch<false>(a, sums, rows, channels, hw, layout, square_input, stream);
+}
+
+extern "C" int rw_channel_moments_f32(const float* a, float* moments, int64_t rows, int channels,
+                                      int64_t hw, int layout, int square_input, rw_stream_t stream) {
+  return channel_sums_launch<true>(a, moments, rows, channels, hw, layout, square_input, stream);
 }

@@ -846,7 +846,9 @@ _workspaces = {}
 
 
 def _workspace(nbytes, device):
-    key = (device.index, 'ws')
+    """The split-K scratch of the current stream: one per (device, stream), because a launch on a second stream may run
+    while the reduction of the first still reads its slabs."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
@@ -855,7 +857,10 @@ def _workspace(nbytes, device):
 
 
 def second_moment_accumulate(mom2, a, nchw=False):
-    """mom2 (C,C) += a^T a.  a: (rows, C) row-major, or (B, C, H, W) when nchw."""
+    """mom2 (C,C) += a^T a.  a: (rows, C) row-major, or (B, C, H, W) when nchw.  Any C: the NCHW kernel takes every channel
+    count as it lies when H * W is a multiple of 16; other maps are copied to rows, and rows whose C is no multiple of 4
+    (the kernel reads float4 along the channels) are zero-padded to the next one and accumulated through a padded scratch,
+    whose C x C corner is added to mom2."""
     a = _dev(a, 'sample')
     if not (mom2.is_cuda and mom2.dtype == torch.float32 and mom2.is_contiguous()):
         raise RuntimeError('mom2 must be a contiguous float32 GPU tensor')
@@ -868,13 +873,21 @@ def second_moment_accumulate(mom2, a, nchw=False):
     else:
         rows, c = a.shape
         hw, layout = 0, 0
-    nbytes = lib().rw_second_moment_workspace_bytes(c, rows)
+    if mom2.shape != (c, c):
+        raise RuntimeError('mom2 is %s, the sample has %d channels' % (tuple(mom2.shape), c))
+    out = mom2
+    if layout == 0 and c % 4:
+        a = torch.nn.functional.pad(a, (0, 4 - c % 4))
+        out = torch.zeros(a.shape[1], a.shape[1], dtype=torch.float32, device=a.device)
+    nbytes = lib().rw_second_moment_workspace_bytes(out.shape[0], rows)
     ws = _workspace(nbytes, a.device)
-    check(lib().rw_second_moment_f32(_p(a), _p(mom2), rows, c, hw, layout, _p(ws), _stream()))
+    check(lib().rw_second_moment_f32(_p(a), _p(out), rows, out.shape[0], hw, layout, _p(ws), _stream()))
+    if out is not mom2:
+        mom2 += out[:c, :c]
     return mom2
 
 
-def channel_sums(a, nchw=False, square_input=False):
+def _channel_reduction(entry, out_rows, a, nchw, square_input):
     a = _dev(a, 'sample')
     if nchw:
         b, c, h, w = a.shape
@@ -882,10 +895,19 @@ def channel_sums(a, nchw=False, square_input=False):
     else:
         rows, c = a.shape
         hw, layout = 0, 0
-    sums = torch.empty(2, c, device=a.device, dtype=a.dtype)
-    check(lib().rw_channel_sums_f32(_p(a), _p(sums), rows, c, hw, layout, int(bool(square_input)),
-                                    _stream()))
-    return sums
+    out = torch.empty(out_rows, c, device=a.device, dtype=a.dtype)
+    check(entry(_p(a), _p(out), rows, c, hw, layout, int(bool(square_input)), _stream()))
+    return out
+
+
+def channel_sums(a, nchw=False, square_input=False):
+    """(2, C): the sum and the sum of squares of every channel (of the squared sample when square_input)"""
+    return _channel_reduction(lib().rw_channel_sums_f32, 2, a, nchw, square_input)
+
+
+def channel_moments(a, nchw=False, square_input=False):
+    """(3, C): p, sum (v - p), sum (v - p)^2 with p the mean of the channel's first samples -- see rw_channel_moments_f32"""
+    return _channel_reduction(lib().rw_channel_moments_f32, 3, a, nchw, square_input)
 
 
 KEY_RESPONSE_MAX_KEYS = 8       # RW_KEY_RESPONSE_MAX_KEYS of include/rewriting_hip.h

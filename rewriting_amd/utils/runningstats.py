@@ -6,7 +6,8 @@
   ``rw_second_moment_f32``, and ``add_nchw`` consumes the key map in the layout the generator
   produced it (no permute copy).
 * ``RunningVariance`` -- per-unit mean/variance with Chan's parallel merge
-  (reference: :748-819); the per-batch reductions run in ``rw_channel_sums_f32``.
+  (reference: :748-819); the per-batch reductions run in ``rw_channel_moments_f32``, which delivers the
+  reference's centred sum of squares from one pass over the map.
 
 ``state_dict`` / ``set_state_dict`` keep the reference's npz schema (keys ``constructor``,
 ``count``, ``mom2`` / ``batchcount``, ``mean``, ``cmom2``) so caches written by either
@@ -109,10 +110,11 @@ class RunningVariance:
     def _batch_stats(a, nchw, square_input):
         """(n, batch mean, batch centred sum of squares) per unit."""
         if hip.on_device(a):
-            sums = hip.channel_sums(a, nchw=nchw, square_input=square_input)
-            n = a.numel() // sums.shape[1]
-            mean = sums[0] / n
-            return n, mean, (sums[1] - n * mean * mean).clamp_(min=0)
+            # one pass about a pivot (the mean of the channel's first samples): S2 - S1^2 / n cancels against a term of the order
+            # of the variance, where raw sums cancel against n mean^2 and lose (mean / std)^2 of float32's precision
+            pivot, s1, s2 = hip.channel_moments(a, nchw=nchw, square_input=square_input)
+            n = a.numel() // pivot.shape[0]
+            return n, pivot + s1 / n, (s2 - s1 * s1 / n).clamp_(min=0)
         if nchw:
             a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
         if square_input:

@@ -288,6 +288,19 @@ def channel_sums(a, nchw=False, square_input=False):
     return torch.stack([a.sum(0), (a * a).sum(0)])
 
 
+def channel_moments(a, nchw=False, square_input=False):
+    a = a.detach()
+    first = 16
+    if nchw:
+        first = min(a.shape[2] * a.shape[3], 256)
+        a = a.permute(0, 2, 3, 1).reshape(-1, a.shape[1])
+    if square_input:
+        a = a * a
+    pivot = a[:first].mean(0)
+    d = a - pivot
+    return torch.stack([pivot, d.sum(0), (d * d).sum(0)])
+
+
 def project_weight(w, context, base=None, out=None):
     res = R.projected_conv(w.detach(), context.detach())
     if base is not None:
@@ -623,7 +636,7 @@ def install(monkeypatch):
              'pack_conv_weight_direct16', 'conv3x3_direct16', 'conv3x3_direct16_to_rgb',
              'pack_conv_transpose_blur_weight_direct16', 'conv_transpose3x3s2_blur_direct16',
              'conv_transpose_wino_split_supported', 'tconv_blur_supported', 'conv_transpose3x3s2_blur_fused',
-             'second_moment_accumulate', 'channel_sums', 'project_weight', 'solve_ksplit',
+             'second_moment_accumulate', 'channel_sums', 'channel_moments', 'project_weight', 'solve_ksplit',
              'solve_step', 'solve_run', 'conv_wgrad', 'rowdot']
     for n in names:
         monkeypatch.setattr(hip, n, globals()[n])

@@ -39,7 +39,7 @@ def test_the_limit_of_the_header_is_the_limit_of_the_wrapper():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = open(os.path.join(root, 'include', 'rewriting_hip.h')).read()
     assert int(re.search(r'#define RW_KEY_RESPONSE_MAX_KEYS (\d+)', text).group(1)) == hip.KEY_RESPONSE_MAX_KEYS == 8
-    assert _lib.ABI_VERSION == 10 and 'rw_key_response_f32' in _lib.SIGNATURES
+    assert _lib.ABI_VERSION == 11 and 'rw_key_response_f32' in _lib.SIGNATURES
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
