@@ -534,6 +534,30 @@ int rw_channel_moments_f32(const float* a, float* moments, int64_t rows, int cha
 int rw_key_response_f32(const float* a, const float* keys, float* heat, float* peak,
                         int64_t images, int channels, int64_t hw, int n_keys, rw_stream_t stream);
 
+/* Overlays: the bytes of ImageVisualizer.masked_image (utils/imgviz.py:56-122, border_from_mask :309-330, the centred
+ * bilinear grid of utils/upsample.py:124-156) and of renormalize.as_image (utils/renormalize.py:15-19) for a batch, in
+ * one launch.  image (images, 3, H, W) float32 in the generator's range, out (images, H, W, 3) uint8.
+ *   bytes:   s = trunc(clamp(x * 127.5f + 127.5f, 0, 255)), product and sum rounded separately (no fused multiply-add).
+ *   inside:  mode 0: no selector, every pixel shows s.
+ *            mode 2: selector = bytes (images, H, W), non-zero = inside (sel_height, sel_width must be H, W).
+ *            mode 1: selector = float32 heat maps (images, h, w), inside = up(y, x) > level (NaN compares false) with
+ *                    up bilinear, zeros outside the map: fy = (y + 1/2) h / H - 1/2, rows floor(fy) and floor(fy) + 1
+ *                    weighted 1 - (fy - floor(fy)) and fy - floor(fy); the same along x.
+ *   outline: border = not inside, and some pixel of the image within Chebyshev distance `thickness` is inside
+ *            (= border_from_mask(mask, thickness, outside=True)); thickness 0: none.
+ *   blend:   border pixels show border_rgb, inside pixels s (or inside_rgb when it is >= 0), every other pixel
+ *            trunc(clamp(outside_bright * s, 0, 255)), one float32 product.  Colours: r | g << 8 | b << 16.
+ * The inside bit of a pixel depends on (y, x), the sizes, the selector and level alone: an image's bytes are the same
+ * alone or in a batch and whatever the alignment of the pointers.  Every byte of out is written exactly once.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null image / out, images, H or W < 1, 3 * H * W past 31 bits, a mode outside
+ * 0 .. 2, mode != 0 with a null selector, mode 2 with a selector that is not H x W, thickness outside
+ * 0 .. RW_RENDER_MAX_THICKNESS, a non-finite outside_bright, mode 1 with h * w, (2 H + 1) h or (2 W + 1) w past 31 bits.
+ * RW_ERR_UNSUPPORTED (nothing launched): mode 1 with h < 2 or w < 2 (the host grid degenerates to a constant). */
+#define RW_RENDER_MAX_THICKNESS 8
+int rw_render_bytes_f32(const float* image, const void* selector, uint8_t* out, int64_t images, int height, int width,
+                        int mode, int sel_height, int sel_width, float level, int thickness, uint32_t border_rgb,
+                        int32_t inside_rgb, float outside_bright, rw_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * The rank-constrained solve -- replaces the body of ProgressiveGanRewriter.insert
  * (rewrite/ganrewrite.py:254-298) and of linear_insert (:201-252) for a SeqStyleGAN2 layer

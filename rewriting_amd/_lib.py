@@ -96,6 +96,8 @@ SIGNATURES = {
                                        c_void_p]),
     'rw_key_response_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int,
                                     c_void_p]),
+    'rw_render_bytes_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_int, c_uint, c_int32, c_float, c_void_p]),
     'rw_conv3x3_wino_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rw_packed_conv_weight_wino_elems': (ctypes.c_longlong, [c_int, c_int]),
     'rw_pack_conv_weight_wino_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

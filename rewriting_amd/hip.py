@@ -943,6 +943,69 @@ def key_response(acts, keys, want_peak=True):
     return torch.cat(heats, dim=1), (torch.cat(peaks, dim=1) if want_peak else None)
 
 
+RENDER_MAX_THICKNESS = 8        # RW_RENDER_MAX_THICKNESS of include/rewriting_hip.h
+
+
+def _rgb(color):
+    """Three colour values as .clamp(0, 255).byte() leaves them, packed r | g << 8 | b << 16."""
+    values = [float(v) for v in color]
+    if len(values) != 3:
+        raise RuntimeError('rewriting_amd: a colour has three components, not %d' % len(values))
+    r, g, b = (int(min(max(v, 0.0), 255.0)) if v == v else 0 for v in values)
+    return r | g << 8 | b << 16
+
+
+def _in_place(t, name, dtype=torch.float32, device=None):
+    """_dev for an operand that is read where it lies: a view that is not contiguous is refused, not copied, and so is a
+    tensor on another device than `device`."""
+    if isinstance(t, torch.Tensor) and not t.is_contiguous():
+        raise RuntimeError('rewriting_amd: %s must be contiguous; it is read in place' % name)
+    t = _dev(t, name, dtype)
+    if device is not None and t.device != device:
+        raise RuntimeError('rewriting_amd: %s is on %s, the images on %s' % (name, t.device, device))
+    return t
+
+
+def render_bytes(images, activations=None, mask=None, level=None, thickness=1, border_color=None, outside_bright=0.5,
+                 inside_color=None):
+    """(B, H, W, 3) uint8 on the device: what ImageVisualizer.pytorch_masked_image (utils/imgviz.py) shows for every image
+    of images (B, 3, H, W) -- or renormalize.as_image's bytes when neither activations nor mask is given -- in one launch
+    of rw_render_bytes_f32.  activations (B, h, w) float32 with a level: inside = bilinear up-sampling > level;
+    mask (B, H, W) bool or uint8: inside = non-zero.  The defaults are pytorch_masked_image's (yellow border).  Inputs
+    are read in place: a view that is not contiguous, a wrong dtype or device is refused, never copied.  The percentile
+    level (activations without level) stays on the host."""
+    images = _in_place(images, 'images')
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError('rewriting_amd: images are (B, 3, H, W), not %s' % (tuple(images.shape),))
+    b, _, h, w = images.shape
+    if activations is not None and mask is not None:
+        raise RuntimeError('rewriting_amd: render_bytes takes activations or a mask, not both')
+    mode, sel, sh, sw, lvl = 0, None, 0, 0, 0.0
+    if activations is not None:
+        if level is None:
+            raise RuntimeError('rewriting_amd: render_bytes needs a level with activations (the percentile level of '
+                               'ImageVisualizer.level_for stays on the host)')
+        sel = _in_place(activations, 'activations', device=images.device)
+        if sel.dim() != 3 or sel.shape[0] != b:
+            raise RuntimeError('rewriting_amd: activations %s do not go with images %s'
+                               % (tuple(sel.shape), tuple(images.shape)))
+        mode, sh, sw, lvl = 1, sel.shape[1], sel.shape[2], float(level)
+    elif mask is not None:
+        sel = _in_place(mask, 'mask', torch.bool if getattr(mask, 'dtype', None) == torch.bool else torch.uint8,
+                        images.device)
+        if tuple(sel.shape) != (b, h, w):
+            raise RuntimeError('rewriting_amd: mask %s does not go with images %s'
+                               % (tuple(sel.shape), tuple(images.shape)))
+        mode, sh, sw = 2, h, w
+    border = _rgb([255, 255, 0] if border_color is None else border_color)
+    inside = -1 if inside_color is None else _rgb(inside_color)
+    out = torch.empty(b, h, w, 3, device=images.device, dtype=torch.uint8)
+    if out.numel():
+        check(lib().rw_render_bytes_f32(_p(images), _p(sel), _p(out), b, h, w, mode, sh, sw, lvl, int(thickness), border,
+                                        inside, float(outside_bright), _stream()))
+    return out
+
+
 # ------------------------------------------------------------------ solve
 def project_weight(w, context, base=None, out=None):
     """out = base + P(w), P = projected_conv (rewrite/ganrewrite.py:806-813).  w (..., O, I, kh, kw)."""

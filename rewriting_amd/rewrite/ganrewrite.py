@@ -44,7 +44,8 @@ class ProgressiveGanRewriter(object):
                  tight_paste=True,           # optimise over the pasted crop, not the whole map
                  alpha_area=True,            # composite with the painted area, not its bounding box
                  key_method='zca',           # or 'svd', 'mean', 'gandissect'
-                 device_search=False):       # ranking_for_key answers through search() (rewrite/search.py)
+                 device_search=False,        # ranking_for_key answers through search() (rewrite/search.py)
+                 device_render=False):       # render_image* / render_object build their bytes with hip.render_bytes
         if next(model.parameters()).dtype == torch.float64:
             raise RuntimeError('rewriting_amd: the rewriters (key statistics, solver, adjoints) are float32 only and the model '
                                'is torch.float64 -- the double path is the generator\'s forward alone; rewrite a .float() '
@@ -61,6 +62,7 @@ class ProgressiveGanRewriter(object):
         self.low_rank_gradient = low_rank_gradient
         self.use_linear_insert = use_linear_insert
         self.device_search = device_search
+        self.device_render = device_render
         self.search_index = None
         self.device = next(model.parameters()).device
         self.zds = zds
@@ -641,17 +643,42 @@ class ProgressiveGanRewriter(object):
                                   'path; install_reference_aliases(reference_root=...) provides the '
                                   "reference's); plain rendering works")
 
+    # what ImageVisualizer.masked_image takes beyond the image and its selector, and hip.render_bytes as well
+    _OVERLAY_KWARGS = ('thickness', 'border_color', 'outside_bright', 'inside_color')
+
+    def _device_overlay(self, kwargs=None, heat_shape=None):
+        """True when hip.render_bytes builds the picture: device_render is set, the model is on the device, and the
+        overlay is one the kernel takes (thickness <= hip.RENDER_MAX_THICKNESS, a heat map at least two wide, no
+        percentile level).  Everything else stays on the host route."""
+        kwargs = kwargs or {}
+        thickness = kwargs.get('thickness', 1)
+        return bool(self.device_render and self._kernels() and all(k in self._OVERLAY_KWARGS for k in kwargs)
+                    and isinstance(thickness, int) and 0 <= thickness <= hip.RENDER_MAX_THICKNESS
+                    and (heat_shape is None or min(heat_shape) >= 2))
+
+    @staticmethod
+    def _as_images(tiles):
+        """(B, H, W, 3) bytes on the device -> PIL images, through ONE device-to-host copy."""
+        import PIL.Image
+        return [PIL.Image.fromarray(tile) for tile in tiles.cpu().numpy()]
+
     def render_object(self, target_output, obj_area=None, box=None):
         with torch.no_grad():
             imgdata = self.rendered_image(self.rendering_model(target_output))
         if box is None:
+            if self._device_overlay():
+                return self._as_images(hip.render_bytes(imgdata[:1].contiguous()))[0]
             return renormalize.as_image(imgdata[0])
         t, l, b, r = box
+        overlay = dict(level=0.0, border_color=[255, 0, 0], thickness=3)
+        if self._device_overlay(dict(thickness=3), self.v_shape[2:]):
+            lowres = torch.zeros((1,) + tuple(self.v_shape[2:]), device=imgdata.device)
+            lowres[0, t:b, l:r] = 1
+            return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), activations=lowres, **overlay))[0]
         lowres = torch.zeros(self.v_shape[2:])
         lowres[t:b, l:r] = 1
         iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
-        return iv.masked_image(imgdata, activations=lowres, level=0.0, border_color=[255, 0, 0],
-                               thickness=3)
+        return iv.masked_image(imgdata, activations=lowres, **overlay)
 
     def render_image(self, imgnum, key=None, level=None, mask=None, **kwargs):
         with torch.no_grad():
@@ -660,30 +687,48 @@ class ProgressiveGanRewriter(object):
         if key is not None and level is not None:
             with torch.no_grad():
                 acts = self.context_acts(self.context_model(z))
-            heatmap = (acts * key.to(self.device)[None, :, None, None]).sum(dim=1)[0]
+            heatmap = (acts * key.to(self.device)[None, :, None, None]).sum(dim=1)
+            if self._device_overlay(kwargs, heatmap.shape[1:]):
+                return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), activations=heatmap[:1].contiguous(),
+                                                        level=level, **kwargs))[0]
             iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
-            return iv.masked_image(imgdata, heatmap, level=level, **kwargs)
+            return iv.masked_image(imgdata, heatmap[0], level=level, **kwargs)
         if mask is not None:
+            if self._device_overlay(kwargs):
+                inside = (torch.as_tensor(mask).to(imgdata.device) != 0)[None].contiguous()
+                return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), mask=inside, **kwargs))[0]
             iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
             return iv.masked_image(imgdata, mask=mask, **kwargs)
+        if self._device_overlay():
+            return self._as_images(hip.render_bytes(imgdata[:1].contiguous()))[0]
         return renormalize.as_image(imgdata[0])
 
     def render_image_batch(self, imgnums, key=None, level=None, **kwargs):
         """Batches of three, as the reference renders them (rewrite/ganrewrite.py:626-650): an image's noise row is
-        its position in its batch of three (quirk Q1), for the picture and for the heat map alike."""
-        results = []
+        its position in its batch of three (quirk Q1), for the picture and for the heat map alike.  With device_render
+        the bytes of every batch are built on the device (one launch each) and come to the host in one copy."""
+        results, tiles = [], []
+        overlay = key is not None and level is not None
         for i in range(0, len(imgnums), 3):
             with torch.no_grad():
                 zb = torch.cat([self.get_z(n) for n in imgnums[i:i + 3]])
                 batch = self.rendered_image(self.sample_image_from_latent(zb))
-                if key is not None and level is not None:
+                if overlay:
                     acts = self.context_acts(self.context_model(zb))
                     heatmap = (acts * key.to(self.device)[None, :, None, None]).sum(dim=1)
-            if key is not None and level is not None:
+            if self._device_overlay(kwargs if overlay else None, heatmap.shape[1:] if overlay else None):
+                if overlay:
+                    tiles.append(hip.render_bytes(batch.contiguous(), activations=heatmap.contiguous(), level=level,
+                                                  **kwargs))
+                else:
+                    tiles.append(hip.render_bytes(batch.contiguous()))
+            elif overlay:
                 iv = self._overlay().ImageVisualizer(batch.shape[2:])
                 results.extend(iv.masked_image(img, heatmap[j], level=level, **kwargs) for j, img in enumerate(batch))
             else:
                 results.extend(renormalize.as_image(img) for img in batch)
+        if tiles:
+            results = self._as_images(torch.cat(tiles))
         return results
 
 
