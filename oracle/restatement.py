@@ -53,9 +53,56 @@ def fused_bias_act(x, b=None, ref=None, act=3, grad=0, alpha=0.2, scale=SQRT2):
     return y * scale
 
 
-def fused_leaky_relu(x, bias, negative_slope=0.2, scale=SQRT2):
-    """op/fused_act.py:51-86 forward."""
-    return fused_bias_act(x, bias, None, 3, 0, negative_slope, scale)
+def fused_leaky_relu(x, bias, negative_slope=0.2, scale=SQRT2, decisions=None):
+    """op/fused_act.py:51-86 forward.  decisions (a Decisions, see there): the branch of every element is the next
+    pinned one instead of the sign of the biased input."""
+    if decisions is None:
+        return fused_bias_act(x, bias, None, 3, 0, negative_slope, scale)
+    if bias is not None and bias.numel():
+        x = x + bias.view(*([1, -1] + [1] * (x.ndim - 2)))
+    return torch.where(decisions.take(x), x, x * negative_slope) * scale
+
+
+class RecordDecisions(list):
+    """Given as ``decisions=``, it RECEIVES the run's own branches (input > 0, one tensor per leaky ReLU in call order)
+    instead of pinning them."""
+
+
+class Decisions:
+    """The leaky ReLUs' branches of one generator forward, pinned: a sequence of boolean tensors, one per leaky ReLU in
+    call order -- the eight mapping layers, then layer2.conv, layer3.sconv, ... -- each of the shape of that
+    activation's input.  The activation then computes where(decision, v, 0.2 v) sqrt(2) on the biased input v in place
+    of where(v > 0, ...): the piecewise-linear function that another run (a device, another precision) evaluated,
+    differentiated exactly.  A shape mismatch raises where it is met, a decision nobody consumed in ``finish``."""
+
+    def __init__(self, given):
+        self.record = given if isinstance(given, RecordDecisions) else None
+        self.given = None if self.record is not None else list(given)
+        self.used = 0
+
+    @classmethod
+    def of(cls, given):
+        """(a Decisions or None, whether this call made it and so has to ``finish`` it)"""
+        if given is None or isinstance(given, cls):
+            return given, False
+        return cls(given), True
+
+    def take(self, v):
+        if self.record is not None:
+            self.record.append(v.detach() > 0)
+            return self.record[-1]
+        if self.used >= len(self.given):
+            raise ValueError('leaky ReLU %d has no pinned decision: %d were given' % (self.used, len(self.given)))
+        d = self.given[self.used]
+        if d.dtype is not torch.bool or tuple(d.shape) != tuple(v.shape):
+            raise ValueError('decision %d is %s %s, the activation\'s input is %s'
+                             % (self.used, d.dtype, tuple(d.shape), tuple(v.shape)))
+        self.used += 1
+        return d
+
+    def finish(self):
+        if self.record is None and self.used != len(self.given):
+            raise ValueError('%d decisions given, %d consumed' % (len(self.given), self.used))
 
 
 def fused_leaky_relu_backward(grad_out, out, negative_slope=0.2, scale=SQRT2):
@@ -137,20 +184,28 @@ def noise_rows(batch, hw):
     return torch.from_numpy(numpy.random.RandomState(0).randn(batch, hw).astype('float32'))
 
 
-def equal_linear(x, w, b, lr_mul=1.0, activation=False):
-    """models.py:487-511."""
+def equal_linear(x, w, b, lr_mul=1.0, activation=False, decisions=None):
+    """models.py:487-511.  decisions: see Decisions (consumed by the activation only)."""
     scale = (1 / math.sqrt(w.shape[1])) * lr_mul
+    decisions, mine = Decisions.of(decisions)
     if activation:
-        return fused_leaky_relu(F.linear(x, w * scale), b * lr_mul)
-    return F.linear(x, w * scale, bias=b * lr_mul)
+        out = fused_leaky_relu(F.linear(x, w * scale), b * lr_mul, decisions=decisions)
+    else:
+        out = F.linear(x, w * scale, bias=b * lr_mul)
+    if mine:
+        decisions.finish()
+    return out
 
 
-def mapping(sd, z, n_mlp=8, lr_mlp=0.01):
-    """PixelNormL (models.py:609-614) + n_mlp EqualLinearL with fused lrelu (:59-65)."""
+def mapping(sd, z, n_mlp=8, lr_mlp=0.01, decisions=None):
+    """PixelNormL (models.py:609-614) + n_mlp EqualLinearL with fused lrelu (:59-65).  decisions: see Decisions."""
+    decisions, mine = Decisions.of(decisions)
     x = z * torch.rsqrt(torch.mean(z ** 2, dim=1, keepdim=True) + 1e-8)
     for i in range(1, n_mlp + 1):
         x = equal_linear(x, sd['style.%d.weight' % i], sd['style.%d.bias' % i],
-                         lr_mul=lr_mlp, activation=True)
+                         lr_mul=lr_mlp, activation=True, decisions=decisions)
+    if mine:
+        decisions.finish()
     return x
 
 
@@ -176,9 +231,10 @@ def demod_conv(x, style, weight, upsample):
     return out * demod[:, :, None, None]
 
 
-def styled_conv(sd, prefix, fmap, latent_row, upsample, taps=None):
+def styled_conv(sd, prefix, fmap, latent_row, upsample, taps=None, decisions=None):
     """StyledConvSeq = modulation -> adain -> dconv -> [blur] -> noise -> activate
-    (models.py:232-289).  ``prefix`` e.g. 'layer8.sconv'.  Returns dict of stage outputs."""
+    (models.py:232-289).  ``prefix`` e.g. 'layer8.sconv'.  Returns dict of stage outputs.  decisions: see Decisions."""
+    decisions, mine = Decisions.of(decisions)
     style = equal_linear(latent_row, sd[prefix + '.mconv.modulation.weight'],
                          sd[prefix + '.mconv.modulation.bias'])
     key = style[:, :, None, None] * fmap                       # ApplyStyle :616-620
@@ -190,8 +246,10 @@ def styled_conv(sd, prefix, fmap, latent_row, upsample, taps=None):
     b, _, h, w = out.shape
     out = out + sd[prefix + '.noise.weight'] * noise_rows(b, h * w).view(b, 1, h, w)
     stages['noise'] = out
-    out = fused_leaky_relu(out, sd[prefix + '.activate.bias'])
+    out = fused_leaky_relu(out, sd[prefix + '.activate.bias'], decisions=decisions)
     stages['activate'] = out
+    if mine:
+        decisions.finish()
     return out, stages
 
 
@@ -211,12 +269,14 @@ def to_rgb(sd, prefix, fmap, latent_row, skip):
     return out
 
 
-def generator_forward(sd, z, size, truncation=1.0, n_mlp=8, collect=None):
+def generator_forward(sd, z, size, truncation=1.0, n_mlp=8, collect=None, decisions=None):
     """SeqStyleGAN2.forward with mconv='seq' (models.py:92-141).  ``collect`` (a dict)
-    receives every named stage output, keyed like nethook names."""
+    receives every named stage output, keyed like nethook names.  ``decisions``: the branch of every leaky ReLU, pinned
+    (see Decisions); without it nothing changes."""
     log_size = int(math.log(size, 2))
     n_latent = log_size * 2 - 2
-    w = mapping(sd, z, n_mlp)
+    decisions, mine = Decisions.of(decisions)
+    w = mapping(sd, z, n_mlp, decisions=decisions)
     lat = adjust_latent(sd, w, n_latent, truncation)
     b = z.shape[0]
     fmap = sd['input.input'].repeat(b, 1, 1, 1)
@@ -227,7 +287,7 @@ def generator_forward(sd, z, size, truncation=1.0, n_mlp=8, collect=None):
 
     rec('style', w)
     rec('latents', lat)
-    fmap, st = styled_conv(sd, 'layer2.conv', fmap, lat[:, 0], False)
+    fmap, st = styled_conv(sd, 'layer2.conv', fmap, lat[:, 0], False, decisions=decisions)
     for k, v in st.items():
         rec('layer2.conv.' + k, v)
     out = to_rgb(sd, 'to_rgb1', fmap, lat[:, 1], None)
@@ -237,12 +297,14 @@ def generator_forward(sd, z, size, truncation=1.0, n_mlp=8, collect=None):
         out = upfirdn2d(out, sd['up_rgb%d.kernel' % (i - 2)], up=2, pad=(2, 1))  # UpsampleO :435-447
         rec('up_rgb%d' % (i - 2), out)
         for j, ups in ((lat_i + 2, True), (lat_i + 3, False)):
-            fmap, st = styled_conv(sd, 'layer%d.sconv' % j, fmap, lat[:, j - 2], ups)
+            fmap, st = styled_conv(sd, 'layer%d.sconv' % j, fmap, lat[:, j - 2], ups, decisions=decisions)
             for k, v in st.items():
                 rec('layer%d.sconv.%s' % (j, k), v)
         out = to_rgb(sd, 'to_rgb%d' % (i - 1), fmap, lat[:, lat_i + 2], out)
         rec('to_rgb%d' % (i - 1), out)
         lat_i += 2
+    if mine:
+        decisions.finish()
     return out
 
 

@@ -44,14 +44,15 @@ def smooth_loss(out, target):
     return (out * target).mean() + 0.5 * out.pow(2).mean()
 
 
-def oracle_gradients(sd, param_names, z, target, size, truncation, dtype, loss_fn=smooth_loss):
+def oracle_gradients(sd, param_names, z, target, size, truncation, dtype, loss_fn=smooth_loss, decisions=None):
     """torch.autograd over the restatement on the host in `dtype`: (loss, image, {name: gradient} with 'z' for the
-    latent).  sd: the model's state dict on the host (float32), param_names: its parameters."""
+    latent).  sd: the model's state dict on the host (float32), param_names: its parameters; decisions: the branch of
+    every leaky ReLU, pinned (oracle.restatement.Decisions)."""
     sd = {k: (v.detach().to(dtype) if v.is_floating_point() else v.detach().clone()) for k, v in sd.items()}
     for name in param_names:
         sd[name].requires_grad_(True)
     z = z.detach().to(dtype).requires_grad_(True)
-    out = R.generator_forward(sd, z, size, truncation=truncation)
+    out = R.generator_forward(sd, z, size, truncation=truncation, decisions=decisions)
     loss = loss_fn(out, target.to(dtype))
     loss.backward()
     grads = {name: sd[name].grad for name in param_names}

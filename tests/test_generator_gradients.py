@@ -1,9 +1,12 @@
 """Gradients from the image, on the emulated path: the adjoints of ToRGB, EqualLinear, PixelNorm and AdjustLatent
 (utils/stylegan2/grad.py) make the whole generator differentiable, ``all_weights_insert`` runs the reference's overfit
 loop over them, and under ``torch.no_grad()`` nothing of it is entered."""
+import functools
+
 import pytest
 import torch
 
+from tests import generator_gradient_checks as C
 from tests import grad_emulation as G
 from tests.conftest import build_stylegan, oracle_state_dict
 
@@ -53,6 +56,116 @@ def test_latent_only(emulated):
     _, _, got = G.model_gradients(model, z, target)
     assert G.rel(got['z'], want['z']) <= BAR
     assert all(got[name] is None for name in names)
+
+
+# ---- the twin of the device's tests at 32^2 (tests/test_gpu_generator_gradients.py, scenarios A, B and D): the same checks
+# module on the emulated path, so that the checks themselves run wherever the suite does ------------------------------------
+WIDE = 32
+
+
+@functools.lru_cache(maxsize=None)
+def wide_model():
+    """(the 32^2 model, its state dict, its parameter names): built once, its parameters never stepped"""
+    model = build_stylegan(WIDE, TRUNCATION)
+    return model, oracle_state_dict(model), tuple(n for n, _ in model.named_parameters())
+
+
+@pytest.fixture
+def launches(emulated, monkeypatch):
+    from tests import route_spy
+    log = []
+    route_spy.install_spies(monkeypatch, log)
+    return log
+
+
+def test_pinned_decisions_at_32_every_tensor_at_the_bar(launches):
+    """Scenario A at size 32, seed 2 -- the seed at which the per-tensor ratio against float64's OWN branches reaches 290
+    on a noise strength and 8.01 on a multi-element tensor for honest float32 arithmetic.  With both oracles on the run's
+    branches every tensor is within 8 d_ref (measured: 1.18 on the worst multi-element tensor, 1.51 on a noise strength
+    against its own d_ref; one decision of 2.78 million differs from float64's own).  The record holds
+    conv3x3_wino on the 32^2 map, and in the backward conv_wgrad and conv3x3(impl=0) on the 33 x 33 gradient map of the
+    transposed convolution (65 x 65 belongs to size 64): launches the 8^2 and 16^2 models never make."""
+    model, sd, names = wide_model()
+    z, target = G.recipe(WIDE, 2)
+    run = C.recorded_run(model, z, target, launches)
+    figures, bad = C.check(run, sd, names + ('z',), z, target, WIDE, TRUNCATION)
+    print(C.describe('A size %d seed 2' % WIDE, figures))
+    assert not bad, bad
+    assert C.launched(run.launches, 'conv3x3_wino', (2, 512, 32, 32))
+    assert C.launched(run.launches, 'conv_wgrad', (2, 512, 33, 33), flags=('upsample', 'gscale'))
+    assert C.launched(run.launches, 'conv3x3', (2, 512, 33, 33), impl=0, flags=('style',))
+
+
+def test_pinned_decisions_at_32_latent_only(launches):
+    """Scenario B at size 32: every parameter frozen, z.grad at the bar, no parameter with a .grad; weight_changes is
+    false, so the stride-1 layer of the 32^2 map is the direct sum that measures its own bound."""
+    model, sd, names = wide_model()
+    z, target = G.recipe(WIDE, 0)
+    with C.only_trainable(model, ()):
+        run = C.recorded_run(model, z, target, launches)
+    figures, bad = C.check(run, sd, ('z',), z, target, WIDE, TRUNCATION)
+    print(C.describe('B size %d seed 0' % WIDE, figures))
+    assert not bad, bad
+    assert all(run.grads[name] is None for name in names)
+    assert all(p.requires_grad for p in model.parameters())
+    assert C.launched(run.launches, 'conv3x3_direct16', (2, 512, 32, 32))
+    assert C.launched(run.launches, 'absmax', (2, 512, 32, 32))
+    assert not C.launched(run.launches, 'conv3x3_wino', (2, 512, 32, 32))
+
+
+@pytest.mark.parametrize('size', [8, 16])
+def test_the_small_sizes_make_none_of_those_launches(launches, size):
+    """What the tests at 32^2 and 64^2 assert from the record is out of reach of the 8^2 and 16^2 models: no launch of
+    theirs, forward or backward, all parameters trainable or none, sees a map of 32 rows or more, and none is a direct sum,
+    a fused transposed convolution or a transposed convolution with a bound."""
+    model = build_stylegan(size, TRUNCATION)
+    z, target = G.recipe(size, 0)
+    seen = list(C.recorded_run(model, z, target, launches).launches)
+    with C.only_trainable(model, ()):
+        seen += C.recorded_run(model, z, target, launches).launches
+    assert any(call.startswith('conv_wgrad ') for call in seen) and any(call.startswith('conv3x3_wino ') for call in seen)
+    for call in seen:
+        name, shape, _, _, on = call.split(' ')
+        if not name.startswith('pack_'):
+            assert int(shape.split('x')[2]) < 32, call
+        assert name not in ('conv3x3_direct16', 'conv_transpose3x3s2_blur_fused', 'absmax'), call
+        assert 'x_amax' not in on.split(','), call
+
+
+def test_the_overfit_loop_teacher_forced_at_32(emulated, monkeypatch):
+    """Scenario D: every loss all_weights_insert reports equals the float64 restatement's at the state the loop was in
+    (1e-5 relative), and every iteration packs every trained convolution weight once in each form -- a pack that is not
+    renewed after optimizer.step() fails both at iteration 1."""
+    rows, bad, packs = C.teacher_forced_overfit(build_stylegan(WIDE, TRUNCATION), TRUNCATION, 'cpu', monkeypatch)
+    print('\n'.join('it %(it)d: loss %(loss).6f  oracle %(oracle).6f  rel %(rel).1e' % r for r in rows), packs)
+    assert not bad, bad
+    assert len(rows) == C.OVERFIT['niter']
+
+
+def test_the_decision_hooks_refuse_what_they_cannot_pin(emulated):
+    """The oracle's side of the pinning: a decision of another shape, one too few and one too many raise; recorded
+    decisions given back reproduce the unpinned run bit for bit."""
+    from oracle import restatement as R
+    model = build_stylegan(SIZE, TRUNCATION)
+    sd = oracle_state_dict(model)
+    z, _ = G.recipe(SIZE, 0)
+    own = R.RecordDecisions()
+    plain = R.generator_forward(sd, z, SIZE, truncation=TRUNCATION)
+    assert torch.equal(R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=own), plain)
+    assert [tuple(d.shape) for d in own] == [(2, 512)] * 8 + [(2, 512, 4, 4), (2, 512, 8, 8), (2, 512, 8, 8)]
+    assert torch.equal(R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=list(own)), plain)
+    flipped = [~d for d in own]
+    assert not torch.equal(R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=flipped), plain)
+    with pytest.raises(ValueError, match='consumed'):
+        R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=list(own) + [own[-1]])
+    with pytest.raises(ValueError, match='no pinned decision'):
+        R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=list(own)[:-1])
+    with pytest.raises(ValueError, match='activation'):
+        R.generator_forward(sd, z, SIZE, truncation=TRUNCATION, decisions=list(own)[:-1] + [own[-1][:, :, :4]])
+    with C.decisions_of(model) as seen, torch.enable_grad():
+        model(z.clone().requires_grad_(True))
+    assert [name for name, _ in seen] == ['style.%d' % i for i in range(1, 9)] + ['layer2.conv', 'layer3.sconv', 'layer4.sconv']
+    assert not any(m._forward_hooks for m in model.modules())
 
 
 def test_all_weights_insert_runs_the_reference_loop(emulated):

@@ -9,6 +9,7 @@ import os
 import pytest
 import torch
 
+from tests import generator_gradient_checks as C
 from tests import grad_emulation as G
 from tests.conftest import build_stylegan, oracle_state_dict
 
@@ -178,3 +179,114 @@ def test_all_weights_insert_at_16():
     assert len(losses) == niter
     assert abs(losses[0] - want[0]) <= 1e-5 * abs(want[0]), (losses[0], want[0])
     assert losses[19] < losses[0], losses
+
+
+# ---------------------------------------------------------------------------------- 32^2 and 64^2: pinned decisions
+# From the 32^2 map up the forward and the backward take routes that the 8^2 and 16^2 models never reach: the general
+# tile form of conv3x3_wino, the split f16-pair form of conv_transpose3x3s2_wino with its strips on the auxiliary stream,
+# conv3x3_direct16 measuring its own bound, the fused blocks in front of a partly frozen model, and in the backward
+# conv3x3(impl=0) / conv_wgrad / rowdot on maps of up to 65 x 65.  The measure, its bars and where they come from:
+# tests/generator_gradient_checks.py.  Every test below records its launches (tests/route_spy.py), asserts the ones that
+# make it worth running, and asserts that planting the decision hooks changed none (C.recorded_run).  Figures:
+# DESIGN.md section 8.1.
+
+@pytest.fixture
+def launches(monkeypatch):
+    from tests import route_spy
+    log = []
+    route_spy.install_spies(monkeypatch, log)
+    return log
+
+
+def held(section, tag, run, names, z, target, size):
+    """C.check of one run; the figures into the report and the output BEFORE anything is asserted"""
+    _, sd, _ = generator(size)
+    figures, bad = C.check(run, sd, names, z, target, size, TRUNCATION)
+    report(section, figures)
+    print(C.describe(tag, figures))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize('size,seed', [(32, 0), (32, 2), (64, 1), (64, 2)])
+def test_pinned_every_parameter_and_the_latent(launches, size, seed):
+    """Scenario A: everything trainable and z.  Every tensor receives a gradient and is within 8 d_ref of the float64
+    oracle on the run's own branches (one-element tensors: 8 times the largest d_ref among them), no seed exempted.
+    What ran, from the record: conv3x3_wino on the 32^2 map (and the 64^2 one at size 64); at size 64 the transposed
+    convolution of the 32^2 map in the split form -- conv_transpose3x3s2_wino with a bound, measured by absmax, beside the
+    strip launch (impl 8); in the backward conv_wgrad with the stride-2 gather and conv3x3(impl=0) with demod as its
+    on-load factor on the (size + 1)^2 gradient map of the last transposed convolution: 65 x 65 at size 64, 33 x 33 at 32.
+    Measured on one MI355X: the largest ratio on a multi-element tensor is 2.55 / 4.33 / 2.63 / 3.36 in the order of the
+    cases (to_rgb2.rgb.bias on three of them); a noise strength reaches 9.77 times its OWN d_ref (layer7, size 64, seed 2)
+    and half of the one-element bar at most."""
+    model, _, names = generator(size)
+    z, target = G.recipe(size, seed)
+    run = C.recorded_run(model, z, target, launches)
+    held('pinned_all_size%d_seed%d' % (size, seed), 'A size %d seed %d' % (size, seed), run, names + ('z',), z, target, size)
+    wide = (2, 512, size + 1, size + 1)
+    for side in sorted({32, size}):
+        assert C.launched(run.launches, 'conv3x3_wino', (2, 512, side, side)), run.launches
+    assert C.launched(run.launches, 'conv_wgrad', wide, flags=('upsample', 'gscale')), run.launches
+    assert C.launched(run.launches, 'conv3x3', wide, impl=0, flags=('style',)), run.launches
+    if size == 64:
+        assert C.launched(run.launches, 'conv_transpose3x3s2_wino', (2, 512, 32, 32), flags=('x_amax',)), run.launches
+        assert C.launched(run.launches, 'conv_transpose3x3s2', (2, 512, 32, 32), impl=8), run.launches
+        assert not C.launched(run.launches, 'conv_transpose3x3s2_wino', (2, 512, 16, 16), flags=('x_amax',))
+
+
+@pytest.mark.parametrize('size,seed', [(32, 0), (64, 1)])
+def test_pinned_latent_only(launches, size, seed):
+    """Scenario B: every parameter frozen, z.grad at the bar (one multi-element tensor), no parameter with a .grad.
+    weight_changes is false: the stride-1 layers from the 32^2 map up are conv3x3_direct16, measuring their own bound.
+    Measured on one MI355X: ratio 1.26 at size 32, 1.56 at size 64."""
+    model, _, names = generator(size)
+    z, target = G.recipe(size, seed)
+    with C.only_trainable(model, ()):
+        run = C.recorded_run(model, z, target, launches)
+    held('pinned_latent_only_size%d' % size, 'B size %d seed %d' % (size, seed), run, ('z',), z, target, size)
+    assert all(run.grads[name] is None for name in names)
+    assert all(p.requires_grad for p in model.parameters())
+    for side in sorted({32, size}):
+        assert C.launched(run.launches, 'conv3x3_direct16', (2, 512, side, side)), run.launches
+        assert C.launched(run.launches, 'absmax', (2, 512, side, side)), run.launches
+        assert not C.launched(run.launches, 'conv3x3_wino', (2, 512, side, side))
+
+
+def test_pinned_partly_frozen_model(launches):
+    """Scenario C at size 64: only the parameters of layer10 and to_rgb5 trainable, z without a gradient.  Every
+    trainable tensor at the bar, nothing else with a .grad.  The hand-over, from the record: the layers in front run as
+    fused blocks -- conv3x3_direct16 with its activation and conv_transpose3x3s2_blur_fused, both on the 32^2 map -- and
+    layer10 behind them module by module: style_mul on the 64^2 map, then conv3x3_wino on it, then in the backward
+    conv_wgrad on the 64^2 map.  Measured on one MI355X: ratio at most 2.38 (to_rgb5.rgb.bias); the one noise strength
+    1.70 times its own d_ref."""
+    size, seed = 64, 1
+    model, _, names = generator(size)
+    trainable = tuple(C.partly_frozen_names(model))
+    assert len(trainable) == 9
+    z, target = G.recipe(size, seed)
+    with C.only_trainable(model, trainable):
+        run = C.recorded_run(model, z, target, launches, z_grad=False)
+    held('pinned_partly_frozen_size%d' % size, 'C size %d seed %d' % (size, seed), run, trainable, z, target, size)
+    assert run.grads['z'] is None and all(run.grads[n] is None for n in names if n not in trainable)
+    assert all(p.requires_grad for p in model.parameters())
+    log = run.launches
+    direct = C.index_of(log, 'conv3x3_direct16', (2, 512, 32, 32), flags=('act', 'noise', 'bias'))
+    fused = C.index_of(log, 'conv_transpose3x3s2_blur_fused', (2, 512, 32, 32), flags=('act', 'noise', 'bias'))
+    mul = C.index_of(log, 'style_mul', (2, 512, 64, 64))
+    wino = C.index_of(log, 'conv3x3_wino', (2, 512, 64, 64))
+    wgrad = C.index_of(log, 'conv_wgrad', (2, 512, 64, 64))
+    assert direct < fused < mul < wino < wgrad, log
+    assert not C.launched(log, 'style_mul', (2, 512, 32, 32)), log          # nothing in front ran module by module
+
+
+def test_all_weights_insert_teacher_forced_at_32(monkeypatch):
+    """Scenario D: all_weights_insert at size 32, 6 iterations, crop (8, 8, 24, 24), lr 0.01, the convolution-free
+    perceptual network.  The loss reported at every iteration is the float64 restatement's at the state the loop was in
+    (the initial one, then the snapshot taken after the optimizer.step() before), 1e-5 relative, no decision pinned; and
+    every iteration packs every trained convolution weight in the forms iteration 0 packed it, each once.  A packed weight
+    that outlives a step fails at iteration 1, which the first loss and `loss[19] < loss[0]` of the size-16 test do not see."""
+    model = build_stylegan(C.OVERFIT['size'], TRUNCATION, device=DEV)
+    rows, bad, packs = C.teacher_forced_overfit(model, TRUNCATION, DEV, monkeypatch)
+    report('all_weights_insert_teacher_forced_size%d' % C.OVERFIT['size'], dict(rows=rows, packs_per_iteration=packs))
+    print('\n'.join('it %(it)d: loss %(loss).6f  oracle %(oracle).6f  rel %(rel).1e' % r for r in rows))
+    assert not bad, bad
+    assert len(rows) == C.OVERFIT['niter']
