@@ -29,6 +29,7 @@ from collections import OrderedDict
 import torch
 
 from ..utils import nethook, pbar, renormalize, tally
+from ..utils.stylegan2.models import noise_batch_period
 from .. import hip, parallel
 from . import search
 
@@ -129,28 +130,40 @@ class ProgressiveGanRewriter(object):
         """True when this rewriter's tensors live on a HIP device (kernels mandatory)."""
         return hip.on_device(next(self.model.parameters()))
 
+    # ---- key maps -------------------------------------------------------------------------
+    def _key_map(self, zbatch):
+        """The key map (B, C, h, w) of a batch of seeds."""
+        return self.context_acts(self.context_model(zbatch.to(self.device))).detach()
+
+    @staticmethod
+    def _rows(acts):
+        """A key map as rows (B*h*w, C), one key per pixel."""
+        return acts.permute(0, 2, 3, 1).reshape(-1, acts.shape[1])
+
+    def _key_rows(self, zbatch):
+        return self._rows(self._key_map(zbatch))
+
+    @staticmethod
+    def _response(acts, key):
+        """The response (B, h, w) of every pixel of a key map to a key (C,)."""
+        return (acts * key[None, :, None, None]).sum(dim=1)
+
     # ---- key statistics -------------------------------------------------------------------
+    def _sweep(self, fn, *args, **kwargs):
+        """Runs a tally over self.zds.  On the GPU with a periodic dataset: in launches of _sweep_batch() seeds, many
+        reference batches of 10 each, with the noise rows repeating every 10 so that each seed keeps its reference row;
+        otherwise in the tally's own batches of 10."""
+        with pbar.quiet(), torch.no_grad():
+            if self._kernels() and self._noise_periodic():
+                with noise_batch_period(10):
+                    return fn(*args, batch_size=self._sweep_batch(), **kwargs)
+            return fn(*args, **kwargs)
+
     def collect_2nd_moment(self):
         """Uncentred second moment C of the keys over the seed sweep (cached in r2m.npz)."""
-        with torch.no_grad(), pbar.quiet():
-            on_gpu = self._kernels()
-
-            def key_rows(zbatch):
-                acts = self.context_acts(self.context_model(zbatch.to(self.device)))
-                if on_gpu:
-                    return acts          # NCHW straight into the MFMA kernel
-                return acts.permute(0, 2, 3, 1).reshape(-1, acts.shape[1])
-            if on_gpu and self._noise_periodic():
-                # many reference batches of 10 per launch; each seed keeps its reference noise row
-                from ..utils.stylegan2.models import noise_batch_period
-                with noise_batch_period(10):
-                    r2m = tally.tally_second_moment(key_rows, self.zds, batch_size=self._sweep_batch(),
-                                                    cachefile=self.rf('r2m.npz'),
-                                                    shard=parallel.shard(), nchw=True)
-            else:
-                r2m = tally.tally_second_moment(key_rows, self.zds, cachefile=self.rf('r2m.npz'),
-                                                shard=parallel.shard(), nchw=on_gpu)
-            return r2m.moment()
+        on_gpu = self._kernels()      # NCHW straight into the MFMA kernel; rows on the host
+        return self._sweep(tally.tally_second_moment, self._key_map if on_gpu else self._key_rows, self.zds,
+                           cachefile=self.rf('r2m.npz'), shard=parallel.shard(), nchw=on_gpu).moment()
 
     # seeds per launch of the statistics sweeps on the GPU (a multiple of the reference's batch of 10), at most.  510 and
     # not 500: the kernels of the context forward launch 16 / 8 / 4 / 2 / 1 workgroups per image or pair of images, and
@@ -182,38 +195,15 @@ class ProgressiveGanRewriter(object):
 
     def square_scales_for_units(self):
         if self.unit_rs is None:
-            with pbar.quiet(), torch.no_grad():
-                on_gpu = self._kernels()
-
-                def squared_units(zbatch):
-                    acts = self.context_acts(self.context_model(zbatch.to(self.device))).detach()
-                    if on_gpu:
-                        return acts
-                    return acts.permute(0, 2, 3, 1).reshape(-1, acts.shape[1]).pow(2)
-                if on_gpu and self._noise_periodic():
-                    from ..utils.stylegan2.models import noise_batch_period
-                    with noise_batch_period(10):
-                        rv = tally.tally_mean(squared_units, self.zds, batch_size=self._sweep_batch(),
-                                              cachefile=self.rf('unit_rs.npz'), nchw=True, square_input=True,
-                                              shard=parallel.shard())
-                else:
-                    rv = tally.tally_mean(squared_units, self.zds, cachefile=self.rf('unit_rs.npz'),
-                                          nchw=on_gpu, square_input=on_gpu, shard=parallel.shard())
-                self.unit_rs = rv.mean()
+            on_gpu = self._kernels()      # the kernel squares the NCHW map as it reads it; squared rows on the host
+            self.unit_rs = self._sweep(tally.tally_mean, self._key_map if on_gpu else (lambda z: self._key_rows(z).pow(2)),
+                                       self.zds, cachefile=self.rf('unit_rs.npz'), nchw=on_gpu, square_input=on_gpu,
+                                       shard=parallel.shard()).mean()
         return self.unit_rs
 
     def covariance_adjusted_query_key(self, k):
-        """C^-1 k by least squares (the reference's torch.lstsq, :101-105), in float32 LAPACK on the
-        host like the reference's CPU configuration: C is ill-conditioned, so the precision of this
-        solve is part of the result -- and so is the driver: torch 1.x lstsq was gels (QR, no rank
-        truncation); torch.linalg.lstsq's default gelsy would drop the directions of C below
-        eps * 512 * lambda_max and return a different key."""
-        c = self.c_matrix.cpu()
-        rhs = (k[:, None] if k.dim() == 1 else k.permute(1, 0)).cpu()
-        with host_linalg_threads():
-            sol = torch.linalg.lstsq(c, rhs, driver='gels').solution
-        sol = sol.to(k.dtype).to(k.device)
-        return sol[:, 0] if k.dim() == 1 else sol.permute(1, 0)
+        """C^-1 k (the reference's torch.lstsq, :101-105); see least_squares_key."""
+        return least_squares_key(self.c_matrix, k)
 
     def covariance_adjusted_key(self, k, kout):
         return self.covariance_adjusted_query_key(k)
@@ -271,43 +261,64 @@ class ProgressiveGanRewriter(object):
         _weights_changed()
 
     # ---- the solve ------------------------------------------------------------------------
+    def _timed(self, return_timing, run):
+        """run(); with return_timing, its milliseconds on the wall clock with the device drained before and after."""
+        sync = torch.cuda.synchronize if self.device.type == 'cuda' else (lambda: None)
+        if return_timing:
+            sync()
+            started = time.time()
+        run()
+        if return_timing:
+            sync()
+            return (time.time() - started) * 1000
+
+    def _goal_loss(self, key, val):
+        goal = self.target_acts(val)
+        return lambda: torch.nn.functional.l1_loss(goal, self.target_acts(self.target_model(key)))
+
+    @staticmethod
+    def _adam(params, lr, niter, compute_loss, update_callback, project_gradient=None, project_weight=None):
+        """The reference's loop (rewrite/ganrewrite.py:282-292) through torch autograd.  The order is part of the result
+        (quirk Q9): the callback sees the stepped, not yet projected weight."""
+        optimizer = torch.optim.Adam(params, lr=lr)
+        for it in range(niter):
+            with torch.enable_grad():
+                loss = compute_loss()
+                optimizer.zero_grad()
+                loss.backward()
+                if project_gradient is not None:
+                    project_gradient()
+                optimizer.step()
+                if update_callback is not None:
+                    update_callback(it, loss)
+            if project_weight is not None:
+                project_weight(it)
+
     def insert(self, key, val, context=None, update_callback=None, niter=2001, piter=10, lr=0.05,
                return_timing=False):
         if self.use_linear_insert:
             return self.linear_insert(key, val, context, update_callback=update_callback,
                                       niter=niter, lr=lr, return_timing=return_timing)
-        sync = (lambda: torch.cuda.synchronize()) if self.device.type == 'cuda' else (lambda: None)
-        if return_timing:
-            sync()
-            started = time.time()
-        key, val = self.detach(key), self.detach(val)
-        self._run_insert(key, val, context, update_callback, niter, piter, lr)
-        if return_timing:
-            sync()
-            return (time.time() - started) * 1000
+        return self._timed(return_timing, lambda: self._run_insert(
+            self.detach(key), self.detach(val), context, update_callback, niter, piter, lr))
 
     def _run_insert(self, key, val, context, update_callback, niter, piter, lr):
         """Projected-gradient Adam through torch autograd (targets made of torch ops)."""
         weight = self.target_weights()
-        constrained = self.low_rank_insert or self.low_rank_gradient
-        if constrained:
+        if self.low_rank_insert or self.low_rank_gradient:
             with torch.no_grad():
                 ortho = weight - projected_conv(weight, context)
-        optimizer = torch.optim.Adam([weight], lr=lr)
-        goal = self.target_acts(val)
-        for it in range(niter):
-            with torch.enable_grad():
-                loss = torch.nn.functional.l1_loss(goal, self.target_acts(self.target_model(key)))
-                optimizer.zero_grad()
-                loss.backward()
-                if self.low_rank_gradient:
-                    weight.grad[...] = projected_conv(weight.grad, context)
-                optimizer.step()
-                if update_callback is not None:
-                    update_callback(it, loss)
-                if self.low_rank_insert and (it % piter == 0 or it == niter - 1):
-                    with torch.no_grad():
-                        weight[...] = ortho + projected_conv(weight, context)
+
+        def project_gradient():
+            weight.grad[...] = projected_conv(weight.grad, context)
+
+        def project_weight(it):
+            if it % piter == 0 or it == niter - 1:
+                with torch.no_grad():
+                    weight[...] = ortho + projected_conv(weight, context)
+        self._adam([weight], lr, niter, self._goal_loss(key, val), update_callback,
+                   project_gradient if self.low_rank_gradient else None,
+                   project_weight if self.low_rank_insert else None)
         _weights_changed()
 
     def linear_insert(self, key, val, context=None, update_callback=None, niter=2001, lr=0.05,
@@ -320,12 +331,11 @@ class ProgressiveGanRewriter(object):
         The reference sizes Lambda as (ws[0], ws[1], rank, ws[3], ws[4]) and therefore raises IndexError on
         ProgGAN's 4-d nn.Conv2d weight (use_linear_insert=True never worked on its config 1); here a 4-d weight
         (O, I, ky, kx) gets Lambda (O, rank, ky, kx), a 5-d one (1, O, I, ky, kx) the reference's shape."""
-        sync = (lambda: torch.cuda.synchronize()) if self.device.type == 'cuda' else (lambda: None)
-        if return_timing:
-            sync()
-            started = time.time()
+        return self._timed(return_timing, lambda: self._run_linear_insert(
+            self.detach(key), self.detach(val), context, update_callback, niter, lr))
+
+    def _run_linear_insert(self, key, val, context, update_callback, niter, lr):
         nethook.set_requires_grad(False, self.model)
-        key, val = self.detach(key), self.detach(val)
         weight = self.target_weights()
         owner = [m for m in self.target_model.modules() if getattr(m, 'weight', None) is weight][0]
         five = weight.dim() == 5
@@ -345,16 +355,7 @@ class ProgressiveGanRewriter(object):
             return plain_forward(*args, **kwargs)
         owner.forward = forward_with_lambda
         try:
-            optimizer = torch.optim.Adam([lam], lr=lr)
-            goal = self.target_acts(val)
-            for it in range(niter):
-                with torch.enable_grad():
-                    loss = torch.nn.functional.l1_loss(goal, self.target_acts(self.target_model(key)))
-                    optimizer.zero_grad()
-                    loss.backward()
-                    optimizer.step()
-                    if update_callback is not None:
-                        update_callback(it, loss)
+            self._adam([lam], lr, niter, self._goal_loss(key, val), update_callback)
         finally:
             with torch.no_grad():
                 weight[...] = weight + torch.einsum(rule, lam.detach(), context)
@@ -366,9 +367,6 @@ class ProgressiveGanRewriter(object):
             else:
                 del owner.forward         # the instance attribute; the class's forward is back
         _weights_changed()
-        if return_timing:
-            sync()
-            return (time.time() - started) * 1000
 
     def all_weights_insert(self, x, z, bounds=None, update_callback=None, niter=20001, lr=0.01, feature_net=None):
         """Adam over EVERY parameter of the generator toward the image x for the latent z (rewrite/ganrewrite.py:300-331):
@@ -391,15 +389,7 @@ class ProgressiveGanRewriter(object):
         nethook.set_requires_grad(False, self.model)
         params = list(self.model.parameters())
         nethook.set_requires_grad(True, *params)
-        optimizer = torch.optim.Adam(params, lr=lr)
-        for it in range(niter):
-            with torch.enable_grad():
-                loss = compute_loss()
-                optimizer.zero_grad()
-                loss.backward()
-                optimizer.step()
-                if update_callback is not None:
-                    update_callback(it, loss)
+        self._adam(params, lr, niter, compute_loss, update_callback)
         _weights_changed()
 
     # ---- context direction ----------------------------------------------------------------
@@ -409,9 +399,8 @@ class ProgressiveGanRewriter(object):
         for imgnum, mask in imgnum_mask_pairs:
             k_outs = self.context_model(self.get_z(imgnum))
             k_acts = self.context_acts(k_outs)
-            area = renormalize.from_url(mask, target='pt', size=self.k_shape[2:])[0]
-            observed.append((k_acts.permute(0, 2, 3, 1).reshape(-1, k_acts.shape[1]), k_outs,
-                             area.reshape(-1)[:, None].to(k_acts.device)))
+            area = self._mask_on(mask, self.k_shape)
+            observed.append((self._rows(k_acts), k_outs, area.reshape(-1)[:, None].to(k_acts.device)))
         return observed
 
     def multi_key_from_selection(self, imgnum_mask_pairs, rank=1, key_method=None):
@@ -458,15 +447,10 @@ class ProgressiveGanRewriter(object):
                 result[torch.arange(rank), top] = 1.0
                 return result
             assert key_method in ['svd', 'mean']
-            gathered = []
-            for imgnum, mask in imgnum_mask_pairs:
-                k_outs = self.context_model(self.get_z(imgnum))
-                k_acts = self.context_acts(k_outs)
-                area = renormalize.from_url(mask, target='pt', size=self.k_shape[2:])[0]
-                weighted = (k_acts[0] * area[None].to(self.device)).permute(1, 2, 0).reshape(
-                    -1, k_acts.shape[1])
-                gathered.append((weighted[weighted.norm(2, dim=1) > 0], k_outs))
-            all_k = torch.cat([self.covariance_adjusted_key(nk, ko) for nk, ko in gathered])
+            # every key times its mask weight -- the products of (k_acts[0] * area[None]).permute(1, 2, 0).reshape(-1, C),
+            # row by row -- and of those the rows that are not zero (a zero key under the mask goes too, unlike 'zca')
+            gathered = [(obs * w, k_outs) for obs, k_outs, w in self._key_observations(imgnum_mask_pairs)]
+            all_k = torch.cat([self.covariance_adjusted_key(nk[nk.norm(2, dim=1) > 0], ko) for nk, ko in gathered])
             just_avg = all_k.mean(0)
             if key_method == 'mean':
                 assert rank == 1
@@ -480,9 +464,9 @@ class ProgressiveGanRewriter(object):
             return u.permute(1, 0)[:rank].contiguous()
 
     def query_key_from_selection(self, imgnum, mask):
-        area = renormalize.from_url(mask, target='pt', size=self.k_shape[2:])[0]
+        area = self._mask_on(mask, self.k_shape)
         with torch.no_grad():
-            k_acts = self.context_acts(self.context_model(self.get_z(imgnum)))
+            k_acts = self._key_map(self.get_z(imgnum))
             mean = (k_acts[0] * area[None].to(self.device)).sum(2).sum(1) / (1e-10 + area.sum())
         k = self.covariance_adjusted_query_key(mean)
         return k / (1e-10 + k.norm(2))
@@ -569,33 +553,17 @@ class ProgressiveGanRewriter(object):
         return z, changed, bounds
 
     # ---- UI conveniences ------------------------------------------------------------------
-    def _flat_units(self, zbatch):
-        acts = self.context_acts(self.context_model(zbatch.to(self.device))).detach()
-        return acts.permute(0, 2, 3, 1).reshape(-1, acts.shape[1])
-
-    def _sweep(self, fn, *args, **kwargs):
-        """Runs a tally over self.zds; on the GPU in launches of sweep_batch seeds with the reference's
-        batch-of-10 noise rows (see collect_2nd_moment)."""
-        with pbar.quiet(), torch.no_grad():
-            if self._kernels() and self._noise_periodic():
-                from ..utils.stylegan2.models import noise_batch_period
-                with noise_batch_period(10):
-                    return fn(*args, batch_size=self._sweep_batch(), **kwargs)
-            return fn(*args, **kwargs)
-
     def quantiles_for_units(self):
         if self.unit_rq is None:
-            self.unit_rq = self._sweep(tally.tally_quantile, self._flat_units, self.zds,
+            self.unit_rq = self._sweep(tally.tally_quantile, self._key_rows, self.zds,
                                        cachefile=self.rf('unit_rq.npz'))
         return self.unit_rq
 
     def quantiles_for_covariance_adjusted_directions(self):
         if self.cad_rq is None:
             def adjusted(zbatch):
-                outs = self.context_model(zbatch.to(self.device))
-                acts = self.context_acts(outs)
-                flat = acts.permute(0, 2, 3, 1).reshape(-1, acts.shape[1])
-                return self.covariance_adjusted_key(flat, outs)
+                outs = self.context_model(zbatch.to(self.device))     # the whole output: a key may be adjusted by its style
+                return self.covariance_adjusted_key(self._rows(self.context_acts(outs)), outs)
             self.cad_rq = self._sweep(tally.tally_quantile, adjusted, self.zds,
                                       cachefile=self.rf('unit_cad.npz'))
         return self.cad_rq
@@ -606,11 +574,10 @@ class ProgressiveGanRewriter(object):
         if self.device_search:
             numbers, _, rq = self.search(key, k)
             return numbers, rq
-        tensorkey = key.to(self.device)[None, :, None, None]
+        key = key.to(self.device)
 
         def image_max_sel(zbatch):
-            acts = self.context_acts(self.context_model(zbatch.to(self.device)))
-            heatmap = (acts * tensorkey).sum(dim=1)
+            heatmap = self._response(self._key_map(zbatch), key)
             return heatmap.reshape(heatmap.shape[0], -1).max(1)[0], heatmap.reshape(-1)[:, None]
         topk, rq = self._sweep(tally.tally_topk_and_quantile, image_max_sel, self.zds, k=k)
         return topk.result()[1], rq
@@ -662,74 +629,70 @@ class ProgressiveGanRewriter(object):
         import PIL.Image
         return [PIL.Image.fromarray(tile) for tile in tiles.cpu().numpy()]
 
+    def _pictures(self, imgdata, activations=None, level=None, mask=None, box=None, as_bytes=False, **kwargs):
+        """One PIL picture per image of imgdata (B, 3, H, W): plain, or under ONE selector -- where activations (B, h, w)
+        exceed `level`, inside a `mask` (H, W; B = 1), or inside a `box` (t, l, b, r) of the target layer's map, drawn
+        as a map of ones above `level` (B = 1) -- with the overlay's kwargs (_OVERLAY_KWARGS; a plain picture has none).
+        The only place that chooses between hip.render_bytes (one launch for the batch, one copy to the host; with
+        as_bytes the bytes stay on the device, for the caller to join) and ImageVisualizer / as_image on the host."""
+        if activations is None and mask is None and box is None:
+            kwargs = {}
+        heat_shape = self.v_shape[2:] if box is not None else (None if activations is None else activations.shape[1:])
+        on_device = self._device_overlay(kwargs, heat_shape)
+        if box is not None:
+            t, l, b, r = box
+            activations = torch.zeros((1,) + tuple(heat_shape), device=imgdata.device if on_device else None)
+            activations[0, t:b, l:r] = 1
+        if on_device:
+            if activations is not None:
+                activations = activations.contiguous()
+            elif mask is not None:
+                mask = (torch.as_tensor(mask).to(imgdata.device) != 0)[None].contiguous()
+            tiles = hip.render_bytes(imgdata.contiguous(), activations=activations, mask=mask, level=level, **kwargs)
+            return tiles if as_bytes else self._as_images(tiles)
+        if activations is None and mask is None:
+            return [renormalize.as_image(img) for img in imgdata]
+        iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
+        if mask is not None:
+            return [iv.masked_image(img, mask=mask, **kwargs) for img in imgdata]
+        return [iv.masked_image(img, activations[j], level=level, **kwargs) for j, img in enumerate(imgdata)]
+
     def render_object(self, target_output, obj_area=None, box=None):
         with torch.no_grad():
             imgdata = self.rendered_image(self.rendering_model(target_output))
         if box is None:
-            if self._device_overlay():
-                return self._as_images(hip.render_bytes(imgdata[:1].contiguous()))[0]
-            return renormalize.as_image(imgdata[0])
-        t, l, b, r = box
-        overlay = dict(level=0.0, border_color=[255, 0, 0], thickness=3)
-        if self._device_overlay(dict(thickness=3), self.v_shape[2:]):
-            lowres = torch.zeros((1,) + tuple(self.v_shape[2:]), device=imgdata.device)
-            lowres[0, t:b, l:r] = 1
-            return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), activations=lowres, **overlay))[0]
-        lowres = torch.zeros(self.v_shape[2:])
-        lowres[t:b, l:r] = 1
-        iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
-        return iv.masked_image(imgdata, activations=lowres, **overlay)
+            return self._pictures(imgdata[:1])[0]
+        return self._pictures(imgdata[:1], box=box, level=0.0, border_color=[255, 0, 0], thickness=3)[0]
+
+    def _heat(self, z, key, level):
+        """The response of the key maps of z to the key if there is a key and a level to draw it at, else None."""
+        if key is None or level is None:
+            return None
+        with torch.no_grad():
+            return self._response(self._key_map(z), key.to(self.device))
 
     def render_image(self, imgnum, key=None, level=None, mask=None, **kwargs):
         with torch.no_grad():
             z = self.get_z(imgnum)
             imgdata = self.rendered_image(self.sample_image_from_latent(z))
-        if key is not None and level is not None:
-            with torch.no_grad():
-                acts = self.context_acts(self.context_model(z))
-            heatmap = (acts * key.to(self.device)[None, :, None, None]).sum(dim=1)
-            if self._device_overlay(kwargs, heatmap.shape[1:]):
-                return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), activations=heatmap[:1].contiguous(),
-                                                        level=level, **kwargs))[0]
-            iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
-            return iv.masked_image(imgdata, heatmap[0], level=level, **kwargs)
-        if mask is not None:
-            if self._device_overlay(kwargs):
-                inside = (torch.as_tensor(mask).to(imgdata.device) != 0)[None].contiguous()
-                return self._as_images(hip.render_bytes(imgdata[:1].contiguous(), mask=inside, **kwargs))[0]
-            iv = self._overlay().ImageVisualizer(imgdata.shape[2:])
-            return iv.masked_image(imgdata, mask=mask, **kwargs)
-        if self._device_overlay():
-            return self._as_images(hip.render_bytes(imgdata[:1].contiguous()))[0]
-        return renormalize.as_image(imgdata[0])
+        heatmap = self._heat(z, key, level)
+        if heatmap is not None:
+            return self._pictures(imgdata, heatmap, level, **kwargs)[0]
+        return self._pictures(imgdata, mask=mask, **kwargs)[0]
 
     def render_image_batch(self, imgnums, key=None, level=None, **kwargs):
         """Batches of three, as the reference renders them (rewrite/ganrewrite.py:626-650): an image's noise row is
         its position in its batch of three (quirk Q1), for the picture and for the heat map alike.  With device_render
         the bytes of every batch are built on the device (one launch each) and come to the host in one copy."""
-        results, tiles = [], []
-        overlay = key is not None and level is not None
+        parts = []
         for i in range(0, len(imgnums), 3):
             with torch.no_grad():
                 zb = torch.cat([self.get_z(n) for n in imgnums[i:i + 3]])
                 batch = self.rendered_image(self.sample_image_from_latent(zb))
-                if overlay:
-                    acts = self.context_acts(self.context_model(zb))
-                    heatmap = (acts * key.to(self.device)[None, :, None, None]).sum(dim=1)
-            if self._device_overlay(kwargs if overlay else None, heatmap.shape[1:] if overlay else None):
-                if overlay:
-                    tiles.append(hip.render_bytes(batch.contiguous(), activations=heatmap.contiguous(), level=level,
-                                                  **kwargs))
-                else:
-                    tiles.append(hip.render_bytes(batch.contiguous()))
-            elif overlay:
-                iv = self._overlay().ImageVisualizer(batch.shape[2:])
-                results.extend(iv.masked_image(img, heatmap[j], level=level, **kwargs) for j, img in enumerate(batch))
-            else:
-                results.extend(renormalize.as_image(img) for img in batch)
-        if tiles:
-            results = self._as_images(torch.cat(tiles))
-        return results
+            parts.append(self._pictures(batch, self._heat(zb, key, level), level, as_bytes=True, **kwargs))
+        if parts and torch.is_tensor(parts[0]):
+            return self._as_images(torch.cat(parts))
+        return [picture for part in parts for picture in part]
 
 
 class SeqStyleGanRewriter(ProgressiveGanRewriter):
@@ -826,8 +789,7 @@ class SeqStyleGanRewriter(ProgressiveGanRewriter):
             # (loss.backward() through the module chain + torch.optim.Adam), every module's forward and adjoint on
             # the HIP kernels (utils/stylegan2/grad.py)
             if linear:
-                return ProgressiveGanRewriter.linear_insert(self, key, val, context, update_callback=update_callback,
-                                                            niter=niter, lr=lr)
+                return self._run_linear_insert(key, val, context, update_callback, niter, lr)
             return super()._run_insert(key, val, context, update_callback, niter, piter, lr)
         from . import hipsolve
         adain, dconv, blur, noise, act = parts
@@ -846,14 +808,8 @@ class SeqStyleGanRewriter(ProgressiveGanRewriter):
                       return_timing=False):
         """Optimise Lambda with weight = W0 + Lambda . context (rewrite/ganrewrite.py:201-252): Adam on
         the (Cout, rank, 3, 3) coefficients only; the weight stays on the rank-r affine subspace."""
-        if return_timing:
-            torch.cuda.synchronize()
-            started = time.time()
-        key, val = self.detach(key), self.detach(val)
-        self._run_insert(key, val, context, update_callback, niter, 10, lr, linear=True)
-        if return_timing:
-            torch.cuda.synchronize()
-            return (time.time() - started) * 1000
+        return self._timed(return_timing, lambda: self._run_insert(
+            self.detach(key), self.detach(val), context, update_callback, niter, 10, lr, linear=True))
 
 
 class SeqTinyStyleGanRewriter(SeqStyleGanRewriter):
@@ -869,12 +825,7 @@ class SeqPreStyleGanRewriter(SeqStyleGanRewriter):
     def covariance_adjusted_key(self, k, kout):
         assert 'adain' in self.firstlayer
         assert kout.style.shape[0] == 1
-        cs = (self.c_matrix * kout.style[0][None, :]).cpu()
-        rhs = (k[:, None] if k.dim() == 1 else k.permute(1, 0)).cpu()
-        with host_linalg_threads():
-            sol = torch.linalg.lstsq(cs, rhs, driver='gels').solution
-        sol = sol.to(k.dtype).to(k.device)
-        return sol[:, 0] if k.dim() == 1 else sol.permute(1, 0)
+        return least_squares_key(self.c_matrix * kout.style[0][None, :], k)
 
 
 # ------------------------------------------------------------------------------------------
@@ -982,6 +933,18 @@ class host_linalg_threads:
     def __exit__(self, *exc):
         if torch.get_num_threads() != self.old:
             torch.set_num_threads(self.old)
+
+
+def least_squares_key(c, k):
+    """c^-1 k for a key (C,) or keys in rows (n, C) by least squares, in float32 LAPACK on the host like the
+    reference's CPU configuration: C is ill-conditioned, so the precision of this solve is part of the result -- and
+    so is the driver: torch 1.x lstsq was gels (QR, no rank truncation); torch.linalg.lstsq's default gelsy would drop
+    the directions of C below eps * 512 * lambda_max and return a different key."""
+    rhs = (k[:, None] if k.dim() == 1 else k.permute(1, 0)).cpu()
+    with host_linalg_threads():
+        sol = torch.linalg.lstsq(c.cpu(), rhs, driver='gels').solution
+    sol = sol.to(k.dtype).to(k.device)
+    return sol[:, 0] if k.dim() == 1 else sol.permute(1, 0)
 
 
 def zca_from_cov(cov):

@@ -27,10 +27,6 @@ def _each_launch(visit, dataset, batch_size=10):
         tally.call_compute(visit, batch)
 
 
-def _key_maps(gw, zbatch):
-    return gw.context_acts(gw.context_model(zbatch.to(gw.device))).detach()
-
-
 def _stamp(model):
     """What a change of the context model cannot leave alone: where each parameter and buffer lives and how often it
     was written in place."""
@@ -54,7 +50,7 @@ class KeyMapIndex:
         self.launches = []
 
         def keep(zbatch):
-            acts = _key_maps(gw, zbatch)
+            acts = gw._key_map(zbatch)
             first = self.launches[-1][0] + self.launches[-1][1] if self.launches else 0
             self.maps[first:first + acts.shape[0]].copy_(acts)
             self.launches.append((first, acts.shape[0]))
@@ -95,7 +91,7 @@ def _respond(gw, acts, keys):
     """heat (B, K, H, W), peak (B, K)"""
     if gw._kernels():
         return hip.key_response(acts.contiguous(), keys)
-    heat = torch.stack([(acts * key[None, :, None, None]).sum(dim=1) for key in keys], dim=1)
+    heat = torch.stack([gw._response(acts, key) for key in keys], dim=1)
     return heat, heat.reshape(heat.shape[0], heat.shape[1], -1).max(2)[0]
 
 
@@ -119,7 +115,7 @@ def search(gw, keys, k=12):
             for acts in index.pieces():
                 tally_piece(acts)
         else:
-            gw._sweep(_each_launch, lambda zbatch: tally_piece(_key_maps(gw, zbatch)), gw.zds)
+            gw._sweep(_each_launch, lambda zbatch: tally_piece(gw._key_map(zbatch)), gw.zds)
     rtk.to_('cpu')
     rq.compress_()
     rq.to_('cpu')
