@@ -437,8 +437,13 @@ __device__ __forceinline__ void w4_at_row(const float (&t)[6], float (&v)[4]) {
 // waits, epilogues).  The powers of two keep the operands inside f16's normal range: eU from max |U| at pack time (read
 // back by the host once per weight version and passed by value), eV from the bound x_amax >= max |x| that the producer of
 // the map left behind (or rw_absmax_f32), the style's largest factor and the transform's gain (<= 100): |V 2^eV| < 25600.  Both leave the result
-// through the epilogue's per-channel factor (exact).  Values more than 2^17 below the map's maximum lose low bits of Vl
-// (f16 denormals: absolute error <= 2^-25 2^-eV) -- no worse than what fp32 accumulation does to them beside the large terms.
+// through the epilogue's per-channel factor (exact).  e is read off bound * smax and clamped to [-100, 100]; the bound is
+// ONE number for the whole map and batch, smax the image's own largest |style|.  Values more than 2^17 below
+// bound * smax * gain lose low bits of Vl (f16 denormals: absolute error <= 2^-25 2^-eV).  Inside the footprint of a
+// large value that is what fp32 accumulation does to them beside the large terms anyway; AWAY from it -- an output
+// that sums no large term, or a whole image beside a 2^k-larger one in its batch -- it is not: the fp32 kernels
+// compute such an output to 2^-24 of its own size, these to 2^-25 2^-eV absolute (DESIGN.md section 4.1 "Range":
+// the measured table; tests/test_gpu_split_range.py).
 // Per-product error <= 2^-21.x of the product against 2^-24 for an fp32 multiply; measured against float64 the kernel's
 // total error is that of the fp32 F(4x4,3x3) kernel (the transforms' constants dominate both).
 // Packed weights: uf[o / 16][i / 4][position 0..35 (w4_nat)][lane] of 32-bit words Uh | Ul << 16 -- the size and the

@@ -132,15 +132,64 @@ class _Split:
 
 
 def _pow2_above(t):
-    """e with max |t| < 2^e (the kernels read it off the exponent field)"""
+    """e with max |t| < 2^e (the pack kernels read it off the exponent field of max |U|)"""
     m = float(t.abs().max())
     return 0 if m == 0 else math.frexp(m)[1]
 
 
-def _f16_pair(t, scale_exp):
-    ts = t * (2.0 ** scale_exp)
-    h = ts.half().float()
-    return (h + (ts - h).half().float()) * (2.0 ** -scale_exp)
+def _exp_above(am):
+    """e with am < 2^e as the convolution kernels read it off an fp32 number: ((bits >> 23) & 0xff) - 126, clamped to
+    +-100 (a zero or denormal am gives -126 -> -100); elementwise, as an int64 tensor"""
+    bits = am.detach().float().contiguous().view(torch.int32).to(torch.int64)
+    return (((bits >> 23) & 0xff) - 126).clamp(-100, 100)
+
+
+def _input_exp(x_amax, x, style, top):
+    """eV PER IMAGE, as every kernel's prologue computes it: top - e with bound * smax < 2^e, smax the largest |style|
+    of the image's own row (1 without a style) and the product taken in fp32"""
+    bound = _bound_of(x_amax, x).float()
+    smax = torch.ones(x.shape[0]) if style is None else style.detach().float().abs().amax(1)
+    return top - _exp_above(bound * smax)
+
+
+def _f16_pair(t, scale_exp, flush=False):
+    """t as the sum of the two f16 numbers of t 2^scale_exp, in t's own dtype; scale_exp an int, or one exponent per
+    image (the leading dimension of t).  flush: f16 denormals read as zero -- what the kernels do NOT do (split_model)"""
+    if torch.is_tensor(scale_exp):
+        scale_exp = scale_exp.view(-1, *[1] * (t.dim() - 1))
+    up, down = torch.ldexp(torch.ones((), dtype=t.dtype), torch.as_tensor(scale_exp)), \
+        torch.ldexp(torch.ones((), dtype=t.dtype), -torch.as_tensor(scale_exp))
+    ts = t * up
+
+    def f16(v):
+        h = v.half().to(t.dtype)
+        return torch.where(h.abs() < 2.0 ** -14, torch.zeros_like(h), h) if flush else h
+    h = f16(ts)
+    return (h + f16(ts - h)) * down
+
+
+def _phase_weights(w, k4):
+    """The four output-parity phases of conv_transpose(stride 2, w [o][i][3][3]) (*) blur(k4) as the 4 * o filters of a
+    3x3 convolution (virtual channel 4 o + 2 py + px), in w's dtype"""
+    o, i = w.shape[:2]
+    kf = torch.flip(k4.to(w.dtype), [0, 1])
+    g6 = torch.zeros(o, i, 6, 6, dtype=w.dtype)
+    for c in range(4):
+        for d in range(4):
+            # g6[t + 2] += k'[c] w[t - 1 + c]  ->  w[ky] lands at t = ky + 1 - c
+            g6[:, :, 3 - c:6 - c, 3 - d:6 - d] += kf[c, d] * w
+    wv = torch.zeros(4 * o, i, 3, 3, dtype=w.dtype)
+    for py in range(2):
+        for px in range(2):
+            for a in range(3):
+                for b in range(3):
+                    wv[2 * py + px::4, :, a, b] = g6[:, :, 4 - 2 * a + py, 4 - 2 * b + px]
+    return wv
+
+
+def _pixel_shuffle_phases(z, o):
+    n, _, h, wd = z.shape
+    return z.reshape(n, o, 2, 2, h, wd).permute(0, 1, 4, 2, 5, 3).reshape(n, o, 2 * h, 2 * wd)
 
 
 BOUND_LANES = 64
@@ -192,25 +241,12 @@ def pack_conv_transpose_weight_wino(weight, split=False):
     return _Split(h) if split else h
 
 
-def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out=None, x_amax=None):
-    """The arithmetic of rw_upwino.hip in torch fp32: per axis the even outputs by F(2,2) (points d0-d1, d1, d2-d1
-    against w2, w2+w0, w0), the odd ones by their single tap; 25 products per 2x2 block of quads.  Writes the
-    quads y < H, x < W of `out` only."""
-    x = x.detach()
-    split = isinstance(uf, _Split)
-    if split:
-        # |T| <= 4 max |x style| < 2^(e + 2): the kernel scales by 2^(12 - e); the weights by 2^(15 - eu), eu from the
-        # largest of the 25 points (at most 4 max |w|: the exact bound is taken here, one binade cannot matter)
-        smax = 1.0 if style is None else float(style.detach().abs().max())
-        ev = 12 - _pow2_above(_bound_of(x_amax, x) * smax)
-        uf = uf.handle
-    if style is not None:
-        x = x * style.detach()[:, :, None, None]
-    w = _unpack(uf, 1)                                   # [o][i][ky][kx]
-    if split:
-        eu = 15 - _pow2_above(w.abs().max().reshape(1) * 4)
+def _upwino_quads(x, w, y, ev=None, eu=None, flush=False, T=None):
+    """The F(2,2) sums of the styled map x against w [o][i][ky][kx] into the quads y < 2H, x < 2W of y, in x's dtype: per
+    axis the even outputs by F(2,2) (points d0-d1, d1, d2-d1 against w2, w2+w0, w0), the odd ones by their single tap;
+    25 products per 2x2 block of quads.  ev (per image) / eu: the operands rounded to f16 pairs.  T[v][h] (v, h over
+    d0-d1, d1, d2-d1, d2): the input points computed by the caller (split_model: in the kernel's own fp32 order)."""
     b, c, h, wd = x.shape
-    y = out if out is not None else torch.zeros(b, out_ch, 2 * h + 1, 2 * wd + 1)
     xp = F.pad(x, (1, 1, 1, 1))
     d = [[xp[:, :, r:r + h:2, cc:cc + wd:2] for cc in range(3)] for r in range(3)]      # windows of the 2x2 blocks
 
@@ -226,20 +262,44 @@ def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out
         for px, kh in ((0, 'E'), (1, 'O')):
             rows = [pts(kv, d[0][cc], d[1][cc], d[2][cc]) for cc in range(3)]            # rows[cc][a]
             V = [pts(kh, rows[0][a], rows[1][a], rows[2][a]) for a in range(len(rows[0]))]   # V[a][b]
+            if T is not None:
+                V = [[T[a][bb] for bb in ((0, 1, 2) if kh == 'E' else (1, 3))] for a in ((0, 1, 2) if kv == 'E' else (1, 3))]
             gv = wts(kv, w[:, :, 0], w[:, :, 1], w[:, :, 2])                              # [a] -> (o,i,kx)
             U = [wts(kh, g[:, :, 0], g[:, :, 1], g[:, :, 2]) for g in gv]                  # U[a][b] (o,i)
-            if split:
-                V = [[_f16_pair(v, ev) for v in row] for row in V]
+            if ev is not None:
+                V = [[_f16_pair(v, ev, flush) for v in row] for row in V]
                 U = [[_f16_pair(u, eu) for u in row] for row in U]
             M = [[torch.einsum('oi,nihw->nohw', U[a][bb], V[a][bb]) for bb in range(len(V[0]))] for a in range(len(V))]
             cols = [outs(kh, M[a]) for a in range(len(M))]
             for bq in range(2):
                 col = outs(kv, [cols[a][bq] for a in range(len(M))])
                 for aq in range(2):
-                    val = col[aq] * w_scale
-                    if demod is not None:
-                        val = val * demod[:, :, None, None]
-                    y[:, :, 2 * aq + py:2 * h:4, 2 * bq + px:2 * wd:4] = val
+                    y[:, :, 2 * aq + py:2 * h:4, 2 * bq + px:2 * wd:4] = col[aq]
+    return y
+
+
+def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out=None, x_amax=None):
+    """The arithmetic of rw_upwino.hip in torch fp32 (_upwino_quads).  Writes the quads y < H, x < W of `out` only."""
+    x = x.detach()
+    split = isinstance(uf, _Split)
+    ev = eu = None
+    if split:
+        # |T| <= 4 max |x style| < 2^(e + 2): the kernel scales by 2^(12 - e); the weights by 2^(15 - eu), eu from the
+        # largest of the 25 points (at most 4 max |w|: the exact bound is taken here, one binade cannot matter)
+        ev = _input_exp(x_amax, x, style, 12)
+        uf = uf.handle
+    if style is not None:
+        x = x * style.detach()[:, :, None, None]
+    w = _unpack(uf, 1)                                   # [o][i][ky][kx]
+    if split:
+        eu = 15 - _pow2_above(w.abs().max().reshape(1) * 4)
+    b, c, h, wd = x.shape
+    y = out if out is not None else torch.zeros(b, out_ch, 2 * h + 1, 2 * wd + 1)
+    _upwino_quads(x, w, y, ev, eu)
+    quads = y[:, :, :2 * h, :2 * wd]
+    quads *= w_scale
+    if demod is not None:
+        quads *= demod[:, :, None, None]
     return y
 
 
@@ -428,28 +488,36 @@ _W4BT = torch.tensor([[4., 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1,
 _W4AT = torch.tensor([[1., 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]])
 
 
+def _wino4_sums(x, wt, ev=None, flush=False, V=None):
+    """F(4x4,3x3) of the styled map x against wt [o][i][3][3] on 6x6 tiles of stride 4, in x's dtype; ev (per image): the
+    transformed operands rounded to pairs of f16 numbers as the kernels on the 16-bit matrix pipe do.  V: B^T d B computed
+    by the caller (split_model: in the kernel's own fp32 order)"""
+    b, i, h, w = x.shape
+    G, BT, AT = (m.to(x.dtype) for m in (_W4G, _W4BT, _W4AT))
+    U = torch.einsum('ab,oibc,dc->oiad', G, wt, G)
+    d = F.pad(x, (1, 1, 1, 1)).unfold(2, 6, 4).unfold(3, 6, 4)
+    if V is None:
+        V = torch.einsum('ab,nithbc,dc->nithad', BT, d, BT)
+    if ev is not None:
+        U, V = _f16_pair(U, 15 - _pow2_above(U)), _f16_pair(V, ev, flush)
+    M = torch.einsum('oiad,nithad->nothad', U, V)
+    Y = torch.einsum('ab,nothbc,dc->nothad', AT, M, AT)
+    return Y.permute(0, 1, 2, 4, 3, 5).reshape(b, wt.shape[0], h, w)
+
+
 def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                   x_amax=None, y_amax=None):
-    """The arithmetic of rw_wino4.hip in torch fp32: F(4x4,3x3) on 6x6 tiles of stride 4; with split weights the
-    transformed operands rounded to pairs of f16 numbers as the kernels on the 16-bit matrix pipe do."""
+    """The arithmetic of rw_wino4.hip in torch fp32 (_wino4_sums), split weights included."""
     x = x.detach()
     split = isinstance(uf, _Split)
+    ev = None
     if split:
-        smax = 1.0 if style is None else float(style.detach().abs().max())
-        ev = 8 - _pow2_above(_bound_of(x_amax, x) * smax)     # |B^T d B| <= 100 max < 2^(e + 7)
+        ev = _input_exp(x_amax, x, style, 8)              # |B^T d B| <= 100 max < 2^(e + 7)
         uf = uf.handle
     if style is not None:
         x = x * style.detach()[:, :, None, None]
-    wt = _unpack(uf, 0)
     b, i, h, w = x.shape
-    U = torch.einsum('ab,oibc,dc->oiad', _W4G, wt, _W4G)
-    d = F.pad(x, (1, 1, 1, 1)).unfold(2, 6, 4).unfold(3, 6, 4)
-    V = torch.einsum('ab,nithbc,dc->nithad', _W4BT, d, _W4BT)
-    if split:
-        U, V = _f16_pair(U, 15 - _pow2_above(U)), _f16_pair(V, ev)
-    M = torch.einsum('oiad,nithad->nothad', U, V)
-    Y = torch.einsum('ab,nothbc,dc->nothad', _W4AT, M, _W4AT)
-    y = Y.permute(0, 1, 2, 4, 3, 5).reshape(b, out_ch, h, w) * w_scale
+    y = _wino4_sums(x, _unpack(uf, 0), ev) * w_scale
     if demod is not None:
         y = y * demod[:, :, None, None]
     if noise is not None:
@@ -473,22 +541,11 @@ def conv_transpose3x3s2_blur_wino4(x, uf, out_ch, w_scale, style=None, demod=Non
     wp, k4 = uf.handle if split else uf
     w = _unpack(wp, 1)                                   # [o][i][3][3]
     o, i = w.shape[:2]
-    kf = torch.flip(k4, [0, 1])
-    g6 = torch.zeros(o, i, 6, 6)
-    for c in range(4):
-        for d in range(4):
-            # g6[t + 2] += k'[c] w[t - 1 + c]  ->  w[ky] lands at t = ky + 1 - c
-            g6[:, :, 3 - c:6 - c, 3 - d:6 - d] += kf[c, d] * w
-    wv = torch.zeros(4 * o, i, 3, 3)
-    for py in range(2):
-        for px in range(2):
-            for a in range(3):
-                for b in range(3):
-                    wv[2 * py + px::4, :, a, b] = g6[:, :, 4 - 2 * a + py, 4 - 2 * b + px]
+    wv = _phase_weights(w, k4)
     z = conv3x3_wino4(x, pack_conv_weight_wino4(wv.reshape(1, 4 * o, i, 3, 3), split), 4 * o, w_scale, style=style,
                       demod=None if demod is None else demod.repeat_interleave(4, dim=1), x_amax=x_amax)
     n, _, h, wd = z.shape
-    y = z.reshape(n, o, 2, 2, h, wd).permute(0, 1, 4, 2, 5, 3).reshape(n, o, 2 * h, 2 * wd)
+    y = _pixel_shuffle_phases(z, o)
     if noise is not None:
         y = y + noise_w.detach().reshape(1) * noise.reshape(n, 1, 2 * h, 2 * wd)
     if act:
@@ -510,16 +567,21 @@ def pack_conv_weight_direct16(weight):
     return _Direct16(pack_conv_weight(weight, 0))
 
 
+def _direct16_sums(x, wt, ev, transposed=False, flush=False):
+    """The direct sums of the styled map x against wt [o][i][3][3] (stride 1, or the stride-2 transposed convolution) with
+    both operands rounded to f16 pairs, in x's dtype"""
+    xr, wr = _f16_pair(x, ev, flush), _f16_pair(wt, 15 - _pow2_above(wt))
+    return F.conv_transpose2d(xr, wr.transpose(0, 1), stride=2) if transposed else F.conv2d(xr, wr, padding=1)
+
+
 def conv3x3_direct16(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                      x_amax=None, y_amax=None):
     x = x.detach()
-    smax = 1.0 if style is None else float(style.detach().abs().max())
-    ev = 14 - _pow2_above(_bound_of(x_amax, x) * smax)
+    ev = _input_exp(x_amax, x, style, 14)
     if style is not None:
         x = x * style.detach()[:, :, None, None]
-    wt = _unpack(wp.handle, 0)
     b, i, h, w = x.shape
-    y = F.conv2d(_f16_pair(x, ev), _f16_pair(wt, 15 - _pow2_above(wt)), padding=1) * w_scale
+    y = _direct16_sums(x, _unpack(wp.handle, 0), ev) * w_scale
     if demod is not None:
         y = y * demod[:, :, None, None]
     if noise is not None:
@@ -548,21 +610,11 @@ def conv_transpose3x3s2_blur_direct16(x, wp, out_ch, w_scale, style=None, demod=
     packed, k4 = wp.handle
     w = _unpack(packed, 1)                               # [o][i][3][3]
     o, i = w.shape[:2]
-    kf = torch.flip(k4, [0, 1])
-    g6 = torch.zeros(o, i, 6, 6)
-    for c in range(4):
-        for d in range(4):
-            g6[:, :, 3 - c:6 - c, 3 - d:6 - d] += kf[c, d] * w
-    wv = torch.zeros(4 * o, i, 3, 3)
-    for py in range(2):
-        for px in range(2):
-            for a in range(3):
-                for b in range(3):
-                    wv[2 * py + px::4, :, a, b] = g6[:, :, 4 - 2 * a + py, 4 - 2 * b + px]
+    wv = _phase_weights(w, k4)
     z = conv3x3_direct16(x, pack_conv_weight_direct16(wv.reshape(1, 4 * o, i, 3, 3)), 4 * o, w_scale, style=style,
                          demod=None if demod is None else demod.repeat_interleave(4, dim=1), x_amax=x_amax)
     n, _, h, wd = z.shape
-    y = z.reshape(n, o, 2, 2, h, wd).permute(0, 1, 4, 2, 5, 3).reshape(n, o, 2 * h, 2 * wd)
+    y = _pixel_shuffle_phases(z, o)
     if noise is not None:
         y = y + noise_w.detach().reshape(1) * noise.reshape(n, 1, 2 * h, 2 * wd)
     if act:
@@ -582,12 +634,10 @@ def conv_transpose3x3s2_blur_fused(x, wp, k4, out_ch, w_scale, style=None, demod
     """rw_tconv.hip: the transposed convolution itself as a direct sum with the operands rounded to f16 pairs, then the blur,
     noise, bias + leaky ReLU and the post scale."""
     x = x.detach()
-    smax = 1.0 if style is None else float(style.detach().abs().max())
-    ev = 14 - _pow2_above(_bound_of(x_amax, x) * smax)
+    ev = _input_exp(x_amax, x, style, 14)
     if style is not None:
         x = x * style.detach()[:, :, None, None]
-    wt = _unpack(wp.handle, 0)                           # [o][i][3][3]
-    z = F.conv_transpose2d(_f16_pair(x, ev), _f16_pair(wt, 15 - _pow2_above(wt)).transpose(0, 1), stride=2) * w_scale
+    z = _direct16_sums(x, _unpack(wp.handle, 0), ev, transposed=True) * w_scale
     if demod is not None:
         z = z * demod[:, :, None, None]
     y = R.upfirdn2d(z, k4.detach(), pad=(1, 1))
