@@ -79,6 +79,40 @@ __device__ __forceinline__ int rw_xcd_remap(int id, int total) {
   return base + slot;
 }
 
+// ---- tiles of the direct-sum kernels (rw_dconv.hip, rw_tconv.hip): tile id = ((ib * tiles_y + ty) * tiles_x + tx) * o_tiles + ot
+// -- ot fastest, so that the out-channel tiles of one window run back to back.  p = the kernel's problem struct; I = int or
+// unsigned, the division the body was written with.
+template <class I, class P>
+__device__ __forceinline__ void rw_tile_digits(const P& p, I tile, int& ot, int& tx, int& ty, int& ib) {
+  ot = (int)(tile % (I)p.o_tiles);
+  I pg = tile / (I)p.o_tiles;
+  tx = (int)(pg % (I)p.tiles_x); pg /= (I)p.tiles_x;
+  ty = (int)(pg % (I)p.tiles_y);
+  ib = (int)(pg / (I)p.tiles_y);
+}
+// The walk of a persistent workgroup, tile bx + k * grid for k = 0, 1, ...: the digits of tile bx once, then + the grid's
+// digits per step, with carries (64-bit divisions per tile cost the staging waves 1.7 k cycles per chunk on layer 17:
+// profiles/r05p)
+template <class P> struct rw_tile_walk {
+  const P& p;
+  int g_ot, g_tx, g_ty, g_ib;                       // the digits of the grid size
+  __device__ __forceinline__ explicit rw_tile_walk(const P& problem) : p(problem) {
+    rw_tile_digits(p, (unsigned)gridDim.x, g_ot, g_tx, g_ty, g_ib);
+  }
+  __device__ __forceinline__ void advance(int& ot, int& tx, int& ty, int& ib) const {
+    ot += g_ot;
+    int carry = ot >= p.o_tiles ? 1 : 0;
+    ot -= carry ? p.o_tiles : 0;
+    tx += g_tx + carry;
+    carry = tx >= p.tiles_x ? 1 : 0;
+    tx -= carry ? p.tiles_x : 0;
+    ty += g_ty + carry;
+    carry = ty >= p.tiles_y ? 1 : 0;
+    ty -= carry ? p.tiles_y : 0;
+    ib += g_ib + carry;
+  }
+};
+
 // ---- f16-pair operands of the direct-sum kernels (rw_dconv.hip, rw_tconv.hip)
 // position of channel quad g inside the 64 bytes of window column cc: g ^ rw_swz(cc).  ds_read_b128 is serviced in the
 // lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32): with this swizzle the 16 lanes of every group -- 16 pixels of
@@ -99,6 +133,21 @@ __device__ __forceinline__ rw_f16x8 rw_pair(rw_f32x2 a, rw_f32x2 b) {
   const rw_f32x4 d = {a[0], a[1], b[0], b[1]};
   return __builtin_bit_cast(rw_f16x8, d);
 }
+// the pixel operand [h0 h1 h2 h3 | l0 l1 l2 l3] of four values (four input channels of a pixel): the exact split v = h + l + an
+// error below 2^-22 |v|, h = f16(v), l = f16(v - h), both rounded to nearest; v - (float)h is exact in fp32 and costs one
+// v_fma_mix_f32 reading the half where the conversion left it
+__device__ __forceinline__ rw_f16x8 rw_split4(float v0, float v1, float v2, float v3) {
+  const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
+  const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
+  float r0, r1, r2, r3;                            // v - (float)h, exact
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
+  const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+  const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
+  return rw_f16x8{h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+}
 
 // ---- LDS-direct loads as inline assembly: M0 = LDS byte address of the wave's 64 x size destination, lane L lands at
 // + L * size
@@ -113,6 +162,22 @@ __device__ __forceinline__ void rw_dma_global_b32(unsigned lds_addr, const void*
 __device__ __forceinline__ void rw_dma_global_b128_s(unsigned lds_addr, int voffset, const void* sbase) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_addr), "v"(voffset), "s"(sbase)
                : "memory");
+}
+
+// ---- the barrier between the roles of a specialised workgroup: LDS traffic waited for (lgkmcnt(0)), nothing else --
+// vector loads and stores stay in flight across the barrier
+__device__ __forceinline__ void rw_lds_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// ---- buffer descriptor of the feature maps of image ib: in_ch planes of hw floats, range checked -- a lane offset past the
+// end reads 0, which is the convolutions' zero padding
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rw_image_rsrc(const float* x, int ib, int in_ch, int64_t hw) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (int64_t)ib * in_ch * hw), 0,
+                                           (int)((int64_t)in_ch * hw * 4), 0x00020000);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -152,15 +217,50 @@ __device__ __forceinline__ void rw_bound_store_block_256(float* __restrict__ bou
   if (threadIdx.x == 0) bound[RW_BOUND_LANES + blockIdx.x] = fmaxf(fmaxf(lds4[0], lds4[1]), fmaxf(lds4[2], lds4[3]));
 }
 
-// u_scale = 2^(15 - e), max |U| < 2^e  (rw_split_weight_scale in the header; one definition for host and tests)
+// ---- max |style| of image ib, the factor that turns the bound on x into one on x style (no style: 1); p = the kernel's problem
+// struct (its style and in_ch are read where they are used, as the bodies read them).  Thread `first` of STRIDE takes the
+// channels first, first + STRIDE, ..., then the wave reduces: with the default every lane ends with the maximum, with
+// <64 * WAVES>(p, ib, tid) with its wave's share of it -- rw_block_max() is the rest.
+template <int STRIDE = 64, class P> __device__ __forceinline__ float rw_style_absmax_wave(const P& p, int ib, int first) {
+  float smax = p.style ? 0.f : 1.f;
+  if (p.style)
+    for (int i = first; i < p.in_ch; i += STRIDE) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
+  return rw_wave_max(smax);
+}
+// The maximum over a workgroup of WAVES waves of v, a value every wave has reduced already; every thread ends with it
+// (red: in LDS; one barrier).  lane and wave are the caller's own: its wave index is wave-uniform by readfirstlane, one
+// derived here would not be.  (Called beside rw_style_absmax_wave, not from inside a helper that does both: nested, the
+// compiler orders the bodies' instructions differently.)
+template <int WAVES> __device__ __forceinline__ float rw_block_max(float v, int lane, int wave, float (&red)[WAVES]) {
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  v = red[0];
+#pragma unroll
+  for (int k = 1; k < WAVES; ++k) v = fmaxf(v, red[k]);
+  return v;
+}
+
+// ---- the scale rule of the split-operand kernels, stated once for the host and every kernel body.
+// e with x < 2^e, from the exponent field alone and clamped to +-100, so that 2^(+-(HEAD - e)) is a normal float whatever
+// x is: zero and the denormals give -100, infinity and NaN 100.
+__host__ __device__ __forceinline__ int rw_exp_above(float x) {
+  const int e = (int)((__builtin_bit_cast(unsigned, x) >> 23) & 0xff) - 126;      // x < 2^e
+  return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+// am >= max |x style| (a bound on x times the largest |style|), am < 2^e: in_scale = 2^(HEAD - e) rides in the style table,
+// so that |V| = |x style in_scale| < 2^HEAD -- HEAD = 14 where V itself is split, less by the gain of the transform where
+// one comes between (each site says which); out_scale = 2^(e - HEAD) / u_scale takes both scales off the result.
+template <int HEAD>
+__host__ __device__ __forceinline__ void rw_split_scales(float am, float u_inv, float& in_scale, float& out_scale) {
+  const int e = rw_exp_above(am);
+  in_scale = __builtin_bit_cast(float, (unsigned)(127 + HEAD - e) << 23);
+  out_scale = __builtin_bit_cast(float, (unsigned)(127 + e - HEAD) << 23) * u_inv;
+}
+// u_scale = 2^(15 - e), max |U| < 2^e; 1 for all-zero weights  (rw_split_weight_scale in the header; one definition for
+// host and tests)
 static inline float rw_weight_scale_of(float u_absmax) {
-  union { float f; unsigned u; } b;
-  b.f = u_absmax;
-  int eu = (int)((b.u >> 23) & 0xff) - 126;
-  if ((b.u & 0x7fffffffu) == 0u) eu = 15;
-  eu = eu < -100 ? -100 : (eu > 100 ? 100 : eu);
-  b.u = (unsigned)(127 + 15 - eu) << 23;
-  return b.f;
+  const int eu = u_absmax == 0.f ? 15 : rw_exp_above(u_absmax);
+  return __builtin_bit_cast(float, (unsigned)(127 + 15 - eu) << 23);
 }
 
 // ---------------------------------------------------------------------------------------

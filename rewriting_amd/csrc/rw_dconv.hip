@@ -9,7 +9,8 @@
 // the multiplies they save -- the layers with few channels and large maps -- the direct sum wins.
 //
 // The operand split is rw_wino4.hip's (V 2^eV = Vh + Vl, U 2^eU = Uh + Ul, f16 round-to-nearest twice, all four products
-// accumulated in fp32), arranged so that neither operand needs a shuffle: a lane's eight k values of
+// accumulated in fp32; the scale rule is rw_split_scales, the split of a pixel's four channels rw_split4: rw_common.h),
+// arranged so that neither operand needs a shuffle: a lane's eight k values of
 // v_mfma_f32_16x16x32_f16 are FOUR input channels,
 //     pixel operand   [Vh c0..c3, Vl c0..c3]                       (what staging writes: 16 bytes per pixel and channel quad)
 //     weight operand  [Uh c0..c3, Uh c0..c3]  then  [Ul c0..c3, Ul c0..c3]    (two MFMAs on the same pixel operand)
@@ -122,32 +123,22 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   const int wm = wave / WN, wn = wave % WN;
   const int lk = lane >> 4, lt = lane & 15;
 
-  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
-  const int ot = local % p.o_tiles;
-  int pg = local / p.o_tiles;
-  const int tx = pg % p.tiles_x; pg /= p.tiles_x;
-  const int ty = pg % p.tiles_y;
-  const int ib = pg / p.tiles_y;
+  int ot, tx, ty, ib;
+  rw_tile_digits(p, rw_xcd_remap(blockIdx.x, gridDim.x), ot, tx, ty, ib);
   const int y0 = ty * TR, x0 = tx * 32;
   const int64_t hw = (int64_t)p.h * p.w;
   const int NC = p.in_ch >> 4, T = 9 * NC;
   const int real_ch = UP ? p.out_ch >> 2 : p.out_ch;
 
-  // ---- scales (see rw_wino4.hip H16): |x style| <= am < 2^e  ->  |V| = |x style 2^(14 - e)| < 2^14
+  // ---- scales (rw_split_scales, rw_common.h); headroom 14: V itself is split
   float in_scale, out_scale;
   {
-    float smax = p.style ? 0.f : 1.f;
-    if (p.style)
-      for (int i = tid; i < p.in_ch; i += 256) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
-    smax = rw_wave_max(smax);
+    float smax = rw_style_absmax_wave<256>(p, ib, tid);
+    // (written out, not rw_block_max: the pairwise maximum below is what this kernel's code was generated from)
     if (lane == 0) Red[wave] = smax;
     __syncthreads();
     smax = fmaxf(fmaxf(Red[0], Red[1]), fmaxf(Red[2], Red[3]));
-    const float am = rw_bound_load(p.x_amax) * smax;
-    int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    in_scale = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-    out_scale = __uint_as_float((unsigned)(127 + e - 14) << 23) * p.u_inv;
+    rw_split_scales<14>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
   }
   const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
   for (int i = tid; i < p.in_ch; i += 256) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
@@ -165,8 +156,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   __syncthreads();                                  // St / Ct / Cr are read by other threads than their writers
 
   // ---- staging: wave g = channel quad g of the chunk; lane = pixel 64 s + lane of the flattened window
-  const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.x + (int64_t)ib * p.in_ch * hw), 0, (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xsrc = rw_image_rsrc(p.x, ib, p.in_ch, hw);
   const int hw4 = (int)hw * 4;
   int xoff[SI], loff[SI];
 #pragma unroll
@@ -199,6 +189,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
     for (int s = S0; s < S1; ++s) {
       const float (&rw)[4] = raw[s - S0];
       const float v0 = rw[0] * sv[0], v1 = rw[1] * sv[1], v2 = rw[2] * sv[2], v3 = rw[3] * sv[3];
+      // rw_split4 written out: through the helper the compiler orders this kernel's conversions and LDS stores differently
       const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
       const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
       float r0, r1, r2, r3;                        // v - (float)h, exact
@@ -523,18 +514,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   const int N = (t1 - t0) * NC;                    // chunks of the run
   const int t_mul = p.strided ? gridDim.x : 1, t_add = p.strided ? bx : 0;            // tile id of run position k
   auto decode = [&](int pos, int& ot, int& tx, int& ty, int& ib) __attribute__((always_inline)) {
-    const int tile = pos * t_mul + t_add;
-    ot = tile % p.o_tiles;
-    int pg = tile / p.o_tiles;
-    tx = pg % p.tiles_x; pg /= p.tiles_x;
-    ty = pg % p.tiles_y;
-    ib = pg / p.tiles_y;
-  };
-  auto lds_barrier = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0): vector loads stay in flight across the barrier
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    rw_tile_digits(p, pos * t_mul + t_add, ot, tx, ty, ib);
   };
 
   if (wave >= MW) {
@@ -583,16 +563,11 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         l_y0 = ty * TR; l_x0 = tx * TC;
         if (ib != l_ib) {
           l_ib = ib;
-          float smax = 0.f;
+          float smax = 0.f;                         // (not rw_style_absmax_wave: this body always has a style, no test for one)
           for (int i = lane; i < p.in_ch; i += 64) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
           smax = rw_wave_max(smax);
-          const float am = xam * smax;
-          int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-          e = e < -100 ? -100 : (e > 100 ? 100 : e);
-          in_scale = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-          out_scale = __uint_as_float((unsigned)(127 + e - 14) << 23) * p.u_inv;
-          xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)ib * p.in_ch * hw), 0,
-                                                   (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+          rw_split_scales<14>(xam * smax, p.u_inv, in_scale, out_scale);      // headroom 14: V itself is split
+          xsrc = rw_image_rsrc(p.x, ib, p.in_ch, hw);
         }
 #pragma unroll
         for (int s = 0; s < SI; ++s) {
@@ -677,16 +652,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         for (int e = 0; e < 4; ++e) {
           const float v0 = raw[q][s][0][e] * sv[q][0], v1 = raw[q][s][1][e] * sv[q][1], v2 = raw[q][s][2][e] * sv[q][2],
                       v3 = raw[q][s][3][e] * sv[q][3];
-          const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
-          const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
-          float r0, r1, r2, r3;                      // v - (float)h, exact
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-          const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
-          const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
-          const rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+          const rw_f16x8 word = rw_split4(v0, v1, v2, v3);
           const int cc = 4 * j - 3 + e;              // window column of this pixel
           if (it < NITEM && cc >= 0 && cc < PW)
             *reinterpret_cast<rw_f16x8*>(dst + loff[s] + e * 64 + (((g2 + q) ^ rw_swz(cc)) << 4)) = word;
@@ -702,7 +668,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     setup();
 #pragma unroll
     for (int s = 0; s < SI; ++s) { deliver_s(0, s); __builtin_amdgcn_sched_barrier(0); request_s(s); __builtin_amdgcn_sched_barrier(0); }
-    lds_barrier();
+    rw_lds_barrier();
 #if DC_PROF
     unsigned long long pt_del = 0, pt_req = 0, pt_bar = 0, pt_all = DC_T();
 #endif
@@ -722,7 +688,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #if DC_PROF
       const unsigned long long tc = DC_T();
 #endif
-      lds_barrier();
+      rw_lds_barrier();
 #if DC_PROF
       const unsigned long long td = DC_T();
       pt_del += tb - ta; pt_req += tc - tb; pt_bar += td - tc;
@@ -791,7 +757,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   int tile = t0, c = 0;
   int ot, tx, ty, ib;
   decode(tile, ot, tx, ty, ib);
-  lds_barrier();                                    // chunk 0 is in LDS
+  rw_lds_barrier();                                 // chunk 0 is in LDS
 
 #if DC_PROF
   unsigned long long pt_mm = 0, pt_bar = 0, pt_epi = 0, pt_all = DC_T();
@@ -880,7 +846,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #if DC_PROF
     const unsigned long long tb = DC_T();
 #endif
-    lds_barrier();
+    rw_lds_barrier();
 #if DC_PROF
     const unsigned long long tc = DC_T();
     pt_mm += tb - ta; pt_bar += tc - tb;

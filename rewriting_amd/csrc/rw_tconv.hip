@@ -18,7 +18,8 @@
 // are the M side of v_mfma_f32_16x16x32_f16 (16 consecutive positions of the flattened (TY + 2) x (TX + 2) position window:
 // a shift in the flattened index is the same for every lane, so the four pixel operands are four LDS reads at fixed
 // offsets), 16 out-channels the N side, a 16-channel chunk the K side with the exact f16 operand split of rw_dconv.hip
-// ([Vh c0..3 | Vl c0..3] pixel words against [Uh | Uh] and [Ul | Ul]: 18 MFMAs per block and chunk; the packed weights ARE
+// ([Vh c0..3 | Vl c0..3] pixel words -- rw_split4, scaled by rw_split_scales<14>, both in rw_common.h -- against [Uh | Uh]
+// and [Ul | Ul]: 18 MFMAs per block and chunk; the packed weights ARE
 // rw_pack_dconv_weight_f32's -- the plain 3x3 kernel, no composition).  The blur needs z one row above and two below its
 // output rows (one column left, two right): a workgroup computes the positions (TY + 2) x (TX + 2) around its TY x TX
 // tile (halo factor 1.2 at 16 x 32) from an x window of (TY + 3) x (TX + 3) pixels staged as in rw_dconv.hip.
@@ -136,33 +137,17 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lk = lane >> 4, lt = lane & 15;
 
-  const int local = rw_xcd_remap(blockIdx.x, gridDim.x);
-  const int ot = local % p.o_tiles;
-  int pg = local / p.o_tiles;
-  const int tx = pg % p.tiles_x; pg /= p.tiles_x;
-  const int ty = pg % p.tiles_y;
-  const int ib = pg / p.tiles_y;
+  int ot, tx, ty, ib;
+  rw_tile_digits(p, rw_xcd_remap(blockIdx.x, gridDim.x), ot, tx, ty, ib);
   const int I0 = ty * TY, J0 = tx * TC_TX;
   const int64_t hw = (int64_t)p.h * p.w;
   const int NC = p.in_ch >> 4, T = 9 * NC;
 
-  // ---- scales (rw_dconv.hip): |x style| <= am < 2^e  ->  |V| = |x style 2^(14 - e)| < 2^14
+  // ---- scales (rw_split_scales, rw_common.h); headroom 14: V itself is split
   float in_scale, out_scale;
   {
-    float smax = p.style ? 0.f : 1.f;
-    if (p.style)
-      for (int i = tid; i < p.in_ch; i += THREADS) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
-    smax = rw_wave_max(smax);
-    if (lane == 0) Red[wave] = smax;
-    __syncthreads();
-    smax = Red[0];
-#pragma unroll
-    for (int v = 1; v < WAVES; ++v) smax = fmaxf(smax, Red[v]);
-    const float am = rw_bound_load(p.x_amax) * smax;
-    int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    in_scale = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-    out_scale = __uint_as_float((unsigned)(127 + e - 14) << 23) * p.u_inv;
+    const float smax = rw_block_max<WAVES>(rw_style_absmax_wave<64 * WAVES>(p, ib, tid), lane, wave, Red);
+    rw_split_scales<14>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
   }
   const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
   for (int i = tid; i < p.in_ch; i += THREADS) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
@@ -191,8 +176,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   // waits for the OLDER requests assume it absent (the software pipeline below keeps up to eleven in flight).
   constexpr int NSL = WAVES / 4;
   const int g = wave & 3, hsel = wave >> 2;
-  const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.x + (int64_t)ib * p.in_ch * hw), 0, (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xsrc = rw_image_rsrc(p.x, ib, p.in_ch, hw);
   const int hw4 = (int)hw * 4;
   constexpr int IPR = TC_TX / 4 + 2, NITEM = WR * IPR;
   constexpr int SI = (NITEM + 64 * NSL - 1) / (64 * NSL), LPP = ((NITEM + SI * NSL - 1) / (SI * NSL) + 3) & ~3;
@@ -237,16 +221,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     for (int e = E0; e < E1; ++e) {
       const float v0 = tc_mul(raw[s][0][e], sv[0]), v1 = tc_mul(raw[s][1][e], sv[1]), v2 = tc_mul(raw[s][2][e], sv[2]),
                   v3 = tc_mul(raw[s][3][e], sv[3]);
-      const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
-      const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
-      float r0, r1, r2, r3;                        // v - (float)h, exact
-      asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
-      asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
-      asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
-      asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-      const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
-      const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
-      rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+      rw_f16x8 word = rw_split4(v0, v1, v2, v3);
       if (TC_ABL & 256)                            // (timing ablation: no conversion arithmetic; results wrong)
         word = __builtin_bit_cast(rw_f16x8, rw_f32x4{raw[s][0][e], raw[s][1][e], raw[s][2][e], raw[s][3][e]});
       if (TC_ABL & 512) { asm volatile("" :: "v"(word)); }            // (timing ablation: no LDS store of the window)
@@ -698,35 +673,8 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     return;
   }
   const int N = count * NC;                         // chunks of the run
-  // tile coordinates: (ot, tx, ty, ib) of tile bx once, then + the grid's digits per step (64-bit divisions per tile cost the
-  // staging waves 1.7 k cycles per chunk on layer 17: profiles/r05p)
-  auto digits = [&](unsigned tile, int& ot, int& tx, int& ty, int& ib) __attribute__((always_inline)) {
-    ot = (int)(tile % (unsigned)p.o_tiles);
-    unsigned pg = tile / (unsigned)p.o_tiles;
-    tx = (int)(pg % (unsigned)p.tiles_x); pg /= (unsigned)p.tiles_x;
-    ty = (int)(pg % (unsigned)p.tiles_y);
-    ib = (int)(pg / (unsigned)p.tiles_y);
-  };
-  int g_ot, g_tx, g_ty, g_ib;
-  digits(gridDim.x, g_ot, g_tx, g_ty, g_ib);
-  auto advance = [&](int& ot, int& tx, int& ty, int& ib) __attribute__((always_inline)) {
-    ot += g_ot;
-    int carry = ot >= p.o_tiles ? 1 : 0;
-    ot -= carry ? p.o_tiles : 0;
-    tx += g_tx + carry;
-    carry = tx >= p.tiles_x ? 1 : 0;
-    tx -= carry ? p.tiles_x : 0;
-    ty += g_ty + carry;
-    carry = ty >= p.tiles_y ? 1 : 0;
-    ty -= carry ? p.tiles_y : 0;
-    ib += g_ib + carry;
-  };
-  auto lds_barrier = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0): vector loads and stores stay in flight across the barrier
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
+  // tile coordinates: (ot, tx, ty, ib) of tile bx once, then + the grid's digits per step (rw_tile_walk, rw_common.h)
+  const rw_tile_walk<TconvProblem> walk(p);
   if (tid < 16) {
     const int a = tid >> 2, c = tid & 3;
     Kf[tid] = p.k4[(3 - a) * 4 + (3 - c)];          // flipped, as upfirdn2d applies it (read after the first barrier)
@@ -852,7 +800,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     const int hw4 = (int)hw * 4;
     int l_pos = 0, l_c = 0, l_ib = -1, l_ot, l_tx, l_ty, l_ibn;       // (l_ot, l_tx, l_ty, l_ibn): the tile being requested
     bool l_past = false;
-    digits((unsigned)bx, l_ot, l_tx, l_ty, l_ibn);
+    rw_tile_digits(p, (unsigned)bx, l_ot, l_tx, l_ty, l_ibn);
     float in_scale = 1.f, out_scale = 1.f;
     int xoff[SI];
     __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0, 0x00020000);
@@ -882,17 +830,9 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
         const int i0 = l_ty * TY, j0 = l_tx * TC_TX;
         if (ib != l_ib) {
           l_ib = ib;
-          float smax = p.style ? 0.f : 1.f;
-          if (p.style)
-            for (int i = lane; i < p.in_ch; i += 64) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
-          smax = rw_wave_max(smax);
-          const float am = xam * smax;
-          int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-          e = e < -100 ? -100 : (e > 100 ? 100 : e);
-          in_scale = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-          out_scale = __uint_as_float((unsigned)(127 + e - 14) << 23) * p.u_inv;
-          xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)ib * p.in_ch * hw), 0,
-                                                   (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+          const float smax = rw_style_absmax_wave(p, ib, lane);
+          rw_split_scales<14>(xam * smax, p.u_inv, in_scale, out_scale);      // headroom 14: V itself is split
+          xsrc = rw_image_rsrc(p.x, ib, p.in_ch, hw);
         }
 #pragma unroll
         for (int s = 0; s < SI; ++s) {
@@ -918,7 +858,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       l_wsrc = w_next;                              // the weights of the chunk set up ONE call ago
       w_next = p.wp + ((int64_t)l_ot * T + 9 * l_c) * 1024 + lane * 16;
       if (++l_c == NC) {
-        if (l_pos + 1 < count) { l_c = 0; ++l_pos; advance(l_ot, l_tx, l_ty, l_ibn); }
+        if (l_pos + 1 < count) { l_c = 0; ++l_pos; walk.advance(l_ot, l_tx, l_ty, l_ibn); }
         else { l_c = NC - 1; l_past = true; }
       }
     };
@@ -963,16 +903,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       for (int e = 0; e < 4; ++e) {
         const float v0 = F.raw[s][0][e] * sv[0], v1 = F.raw[s][1][e] * sv[1], v2 = F.raw[s][2][e] * sv[2],
                     v3 = F.raw[s][3][e] * sv[3];
-        const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
-        const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
-        float r0, r1, r2, r3;                        // v - (float)h, exact
-        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "v"(v0));
-        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "v"(v1));
-        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "v"(v2));
-        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "v"(v3));
-        const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
-        const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
-        const rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+        const rw_f16x8 word = rw_split4(v0, v1, v2, v3);
         const int cc = 4 * j - 2 + e;                // window column of this pixel
         if (it < NITEM && cc >= 0 && cc < TC_WC)
           *reinterpret_cast<rw_f16x8*>(dst + (r * TC_WC + cc) * 64 + ((g ^ rw_swz(cc)) << 4)) = word;
@@ -994,10 +925,10 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
       deliver_s(rw_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
       request_s(rw_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
     }
-    lds_barrier();
+    rw_lds_barrier();
     int cn = 0, e_pos = 0;                          // the tile the multiplying waves are on (its epilogue is shared)
     int e_ot, e_tx, e_ty, e_ib;
-    digits((unsigned)bx, e_ot, e_tx, e_ty, e_ib);
+    rw_tile_digits(p, (unsigned)bx, e_ot, e_tx, e_ty, e_ib);
     TP_DECL(tp = 0, tp_all = 0, tp_setup = 0, tp_del = 0, tp_bar = 0, tp_blur = 0, tp_ebar = 0, tp_tab = 0);
     TP_NOW(tp); TP_NOW(tp_all);
     // interval n: chunk n + 1 (slot (n + 1) & 1, in flight for two intervals; its weights for one) -> LDS piece by piece, the
@@ -1019,20 +950,20 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
         request_s(tag, s); __builtin_amdgcn_sched_barrier(0);
       }
       TP_ADD(tp_del, tp);
-      lds_barrier();
+      rw_lds_barrier();
       TP_ADD(tp_bar, tp);
       if (++cn == NC) {                             // the tile's epilogue (the loads stay in flight)
         cn = 0;
         const int par = e_pos & 1;
         if (STAGERS_BLUR) blur(0, par, e_ot, e_tx, e_ty, e_ib);
         TP_ADD(tp_blur, tp);
-        lds_barrier();                              // z is free: the multiplying waves write the other eight channels
-        lds_barrier();
+        rw_lds_barrier();                           // z is free: the multiplying waves write the other eight channels
+        rw_lds_barrier();
         TP_ADD(tp_ebar, tp);
         if (STAGERS_BLUR) blur(1, par, e_ot, e_tx, e_ty, e_ib);
         TP_ADD(tp_blur, tp);
         ++e_pos;
-        advance(e_ot, e_tx, e_ty, e_ib);
+        walk.advance(e_ot, e_tx, e_ty, e_ib);
       }
     };
     int n = 0;
@@ -1160,8 +1091,8 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
 
   int pos = 0, c = 0;
   int ot, tx, ty, ib;
-  digits((unsigned)bx, ot, tx, ty, ib);
-  lds_barrier();                                    // chunk 0 and the FIR are in LDS
+  rw_tile_digits(p, (unsigned)bx, ot, tx, ty, ib);
+  rw_lds_barrier();                                 // chunk 0 and the FIR are in LDS
   TP_DECL(tp = 0, tp_all = 0, tp_mma = 0, tp_bar = 0, tp_zw = 0, tp_blur = 0, tp_ebar = 0);
   TP_NOW(tp); TP_NOW(tp_all);
   for (int n = 0; n < N; ++n) {
@@ -1169,22 +1100,22 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     const unsigned char* wb = Wl + (n & 1) * TC_WCH + lane * 8;
     mma(lb, wb);
     TP_ADD(tp_mma, tp);
-    if (c + 1 < NC) { ++c; lds_barrier(); TP_ADD(tp_bar, tp); continue; }
+    if (c + 1 < NC) { ++c; rw_lds_barrier(); TP_ADD(tp_bar, tp); continue; }
     // ---- epilogue of the tile, eight channels at a time
     c = 0;
     const int par = pos & 1;
     noise_request(ty, tx, ib);                      // (behind the MFMAs: sixteen registers they need; the z write and a barrier cover it)
     zwrite(0);
     TP_ADD(tp_zw, tp);
-    lds_barrier();                                  // (the barrier of the tile's last chunk)
+    rw_lds_barrier();                               // (the barrier of the tile's last chunk)
     TP_ADD(tp_bar, tp);
     blur(0, par, ot, tx, ty, ib);
     TP_ADD(tp_blur, tp);
-    lds_barrier();                                  // every strip of the first eight channels is read: z is free again
+    rw_lds_barrier();                               // every strip of the first eight channels is read: z is free again
     TP_ADD(tp_ebar, tp);
     zwrite(1);
     TP_ADD(tp_zw, tp);
-    lds_barrier();
+    rw_lds_barrier();
     TP_ADD(tp_ebar, tp);
     blur(1, par, ot, tx, ty, ib);
     TP_ADD(tp_blur, tp);
@@ -1193,7 +1124,7 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
 #pragma unroll
       for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     ++pos;
-    advance(ot, tx, ty, ib);
+    walk.advance(ot, tx, ty, ib);
   }
 #if TC_PROF
   if (wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
@@ -1249,33 +1180,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     return;
   }
   const int N = count * NC;                         // chunks of the run
-  auto digits = [&](unsigned tile, int& ot, int& tx, int& ty, int& ib) __attribute__((always_inline)) {
-    ot = (int)(tile % (unsigned)p.o_tiles);
-    unsigned pg = tile / (unsigned)p.o_tiles;
-    tx = (int)(pg % (unsigned)p.tiles_x); pg /= (unsigned)p.tiles_x;
-    ty = (int)(pg % (unsigned)p.tiles_y);
-    ib = (int)(pg / (unsigned)p.tiles_y);
-  };
-  int g_ot, g_tx, g_ty, g_ib;
-  digits(gridDim.x, g_ot, g_tx, g_ty, g_ib);
-  auto advance = [&](int& ot, int& tx, int& ty, int& ib) __attribute__((always_inline)) {
-    ot += g_ot;
-    int carry = ot >= p.o_tiles ? 1 : 0;
-    ot -= carry ? p.o_tiles : 0;
-    tx += g_tx + carry;
-    carry = tx >= p.tiles_x ? 1 : 0;
-    tx -= carry ? p.tiles_x : 0;
-    ty += g_ty + carry;
-    carry = ty >= p.tiles_y ? 1 : 0;
-    ty -= carry ? p.tiles_y : 0;
-    ib += g_ib + carry;
-  };
-  auto lds_barrier = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0): vector loads and stores stay in flight across the barrier
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
+  const rw_tile_walk<TconvProblem> walk(p);
   if (tid < 16) {
     const int a = tid >> 2, c = tid & 3;
     Kf[tid] = p.k4[(3 - a) * 4 + (3 - c)];          // flipped, as upfirdn2d applies it (read after the first barrier)
@@ -1396,7 +1301,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     const int hw4 = (int)hw * 4;
     int l_pos = 0, l_c = 0, l_ib = -1, l_ot, l_tx, l_ty, l_ibn;       // (l_ot, l_tx, l_ty, l_ibn): the tile being requested
     bool l_past = false;
-    digits((unsigned)bx, l_ot, l_tx, l_ty, l_ibn);
+    rw_tile_digits(p, (unsigned)bx, l_ot, l_tx, l_ty, l_ibn);
     float in_scale = 1.f, out_scale = 1.f;
     int xoff[SI];
     // where a lane's pixels go in a window buffer: the same for every chunk and tile (-1: outside the window)
@@ -1433,17 +1338,9 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         const int i0 = (TC_ABL & 1024) ? 0 : l_ty * TY, j0 = (TC_ABL & 1024) ? 0 : l_tx * TC_TX;
         if (ib != l_ib) {
           l_ib = ib;
-          float smax = p.style ? 0.f : 1.f;
-          if (p.style)
-            for (int i = lane; i < p.in_ch; i += 64) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
-          smax = rw_wave_max(smax);
-          const float am = xam * smax;
-          int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-          e = e < -100 ? -100 : (e > 100 ? 100 : e);
-          in_scale = __uint_as_float((unsigned)(127 + 14 - e) << 23);
-          out_scale = __uint_as_float((unsigned)(127 + e - 14) << 23) * p.u_inv;
-          xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)ib * p.in_ch * hw), 0,
-                                                   (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+          const float smax = rw_style_absmax_wave(p, ib, lane);
+          rw_split_scales<14>(xam * smax, p.u_inv, in_scale, out_scale);      // headroom 14: V itself is split
+          xsrc = rw_image_rsrc(p.x, ib, p.in_ch, hw);
         }
 #pragma unroll
         for (int s = 0; s < SI; ++s) {
@@ -1469,7 +1366,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       l_wsrc = w_next;                              // the weights of the chunk set up ONE call ago
       w_next = p.wp + ((int64_t)l_ot * T + 9 * l_c) * 1024 + lane * 16;
       if (++l_c == NC) {
-        if (l_pos + 1 < count) { l_c = 0; ++l_pos; advance(l_ot, l_tx, l_ty, l_ibn); }
+        if (l_pos + 1 < count) { l_c = 0; ++l_pos; walk.advance(l_ot, l_tx, l_ty, l_ibn); }
         else { l_c = NC - 1; l_past = true; }
       }
     };
@@ -1509,6 +1406,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       for (int e = 0; e < 4; ++e) {
         const float v0 = F.raw[s][0][e] * sv[0], v1 = F.raw[s][1][e] * sv[1], v2 = F.raw[s][2][e] * sv[2],
                     v3 = F.raw[s][3][e] * sv[3];
+        // rw_split4 written out: through the helper the compiler orders this kernel's address additions differently
         const rw_f16x2 h01 = __builtin_convertvector(rw_f32x2{v0, v1}, rw_f16x2);
         const rw_f16x2 h23 = __builtin_convertvector(rw_f32x2{v2, v3}, rw_f16x2);
         float r0, r1, r2, r3;                        // v - (float)h, exact
@@ -1541,10 +1439,10 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       deliver_s(rw_int<0>(), 0, s); __builtin_amdgcn_sched_barrier(0);
       request_s(rw_int<0>(), s); __builtin_amdgcn_sched_barrier(0);
     }
-    lds_barrier();
+    rw_lds_barrier();
     int cn = 0, e_pos = 0;                          // the tile the multiplying waves are on
     int e_ot, e_tx, e_ty, e_ib;
-    digits((unsigned)bx, e_ot, e_tx, e_ty, e_ib);
+    rw_tile_digits(p, (unsigned)bx, e_ot, e_tx, e_ty, e_ib);
     bool have_prev = false;                         // the tile whose z tile is in LDS, waiting to be blurred
     int b_ot = 0, b_tx = 0, b_ty = 0, b_ib = 0, b_par = 0;
     TP_DECL(tp = 0, tp_all = 0, tp_setup = 0, tp_del = 0, tp_bar = 0, tp_blur = 0, tp_zbar = 0);
@@ -1570,7 +1468,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         for (int ps = p_lo; ps < p_hi; ++ps) blur(ps, b_par, b_ot, b_tx, b_ty, b_ib);
       }
       TP_ADD(tp_blur, tp);
-      lds_barrier();
+      rw_lds_barrier();
       TP_ADD(tp_bar, tp);
       if (++cn == NC) {                             // the multiplying waves write the z tile of THEIR tile now
         cn = 0;
@@ -1578,8 +1476,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         have_prev = true;
         if (TC_PP_MQ < 4) noise_request(b_ty, b_tx, b_ib);       // (ahead of the next interval's window requests: loads return in order)
         ++e_pos;
-        advance(e_ot, e_tx, e_ty, e_ib);
-        lds_barrier();                              // z is ready
+        walk.advance(e_ot, e_tx, e_ty, e_ib);
+        rw_lds_barrier();                           // z is ready
         TP_ADD(tp_zbar, tp);
       }
     };
@@ -1699,8 +1597,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
 
   int c = 0, pos = 0;
   int ot, tx, ty, ib;
-  digits((unsigned)bx, ot, tx, ty, ib);
-  lds_barrier();                                    // chunk 0 and the FIR are in LDS
+  rw_tile_digits(p, (unsigned)bx, ot, tx, ty, ib);
+  rw_lds_barrier();                                 // chunk 0 and the FIR are in LDS
   TP_DECL(tp = 0, tp_all = 0, tp_mma = 0, tp_bar = 0, tp_zw = 0, tp_zbar = 0, tp_blur = 0);
   TP_NOW(tp); TP_NOW(tp_all);
   for (int n = 0; n < N; ++n) {
@@ -1708,14 +1606,14 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     const unsigned char* wb = Wl + (n & 1) * TC_WCH + lane * 8;
     mma(lb, wb);
     TP_ADD(tp_mma, tp);
-    lds_barrier();                                  // the chunk is consumed; at a tile's last chunk also: the previous tile is blurred, z is free
+    rw_lds_barrier();                               // the chunk is consumed; at a tile's last chunk also: the previous tile is blurred, z is free
     TP_ADD(tp_bar, tp);
     if (c + 1 < NC) { ++c; continue; }
     c = 0;
     if (TC_PP_MQ > 0) noise_request(ty, tx, ib);    // (the z write and a barrier cover it)
     zwrite();
     TP_ADD(tp_zw, tp);
-    lds_barrier();                                  // z is ready
+    rw_lds_barrier();                               // z is ready
     TP_ADD(tp_zbar, tp);
     // this role's share of the tile's blur (passes 0 .. TC_PP_MQ - 1), before the next tile's multiplies; the staging
     // waves take the rest beside them
@@ -1723,7 +1621,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     for (int ps = 0; ps < TC_PP_MQ; ++ps) blur(ps, pos & 3, ot, tx, ty, ib);
     TP_ADD(tp_blur, tp);
     ++pos;
-    advance(ot, tx, ty, ib);
+    walk.advance(ot, tx, ty, ib);
 #pragma unroll
     for (int b = 0; b < BPW; ++b)
 #pragma unroll

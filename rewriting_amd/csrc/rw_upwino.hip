@@ -39,7 +39,7 @@
 //   B = [Th0, Th1, Th0, Th1, Tl0, Tl1, Tl0, Tl1]    (v_cvt_pk_f16_f32 converts the pair of channels at once)
 // -- 25 MFMAs of ~17 cycles per 8 channels instead of 50 of 32, the 16 distinct transformed inputs split once per
 // interval (4 VALU per pair) and kept as operand quads.  |T| <= 4 max |x style| and |U| <= 4 max |w|: eV from the
-// caller's x_amax, eU at pack time (trailer, as in rw_wino4.hip).  Packed weights: the 25 points carry 16 distinct values
+// caller's x_amax by rw_split_scales<12> (rw_common.h), eU at pack time (trailer, as in rw_wino4.hip).  Packed weights: the 25 points carry 16 distinct values
 // (9 of phase (0,0), 3 + 3 of the mixed phases, 1 of phase (1,1)): uf[o / 16][i / 8][wi = 0..15][lane][{0: Uh pair,
 // 1: Ul pair}] -- 16 KB per interval and workgroup where the fp32 packing streams 28.
 
@@ -121,6 +121,8 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
     float in_scale = 1.f, out_scale = 1.f;       // H16: 2^eV on the input (style table), 2^-(eU + eV) on the result
     if (H16) {
       __shared__ float Red[4];
+      // (written out, not rw_style_absmax_wave / rw_block_max: with rw_wave_max in place of this shuffle loop the compiler
+      // orders the kernel's prologue differently)
       float smax = p.style ? 0.f : 1.f;
       if (p.style)
         for (int i = tid; i < p.in_ch; i += 256) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
@@ -129,11 +131,8 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
       if (lane == 0) Red[wave] = smax;
       __syncthreads();
       smax = fmaxf(fmaxf(Red[0], Red[1]), fmaxf(Red[2], Red[3]));
-      const float am = rw_bound_load(p.x_amax) * smax;            // |T| <= 4 am < 2^(e + 2)
-      int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;    // am < 2^e
-      e = e < -100 ? -100 : (e > 100 ? 100 : e);
-      in_scale = __uint_as_float((unsigned)(127 + 12 - e) << 23);
-      out_scale = __uint_as_float((unsigned)(127 + e - 12) << 23) * p.u_inv;
+      // headroom 12: |T| <= 4 am < 2^(e + 2)
+      rw_split_scales<12>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
     }
     for (int i = tid; i < p.in_ch; i += 256) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
     if (tid < 32) Sc[tid] = (p.demod ? p.demod[(int64_t)ib * p.out_ch + o0 + tid] * p.w_scale : p.w_scale) * out_scale;

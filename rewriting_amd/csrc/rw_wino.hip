@@ -163,6 +163,8 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
   // (descriptor = this image's feature maps, scalar channel offset, 32-bit lane offset): positions outside the
   // image get an out-of-range offset and the hardware returns 0 -- the zero padding costs no instruction, and
   // there is no 64-bit address arithmetic.  Lane offsets are recomputed when the fetch cursor enters a new group.
+  // (written out, not rw_image_rsrc: the range spans the workgroup's nimg images, and the helper with an image count
+  // changed the code of the NRW = 4 / 8 kernels)
   const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(xb), 0, (int)((int64_t)nimg * p.in_ch * hw * 4), 0x00020000);
   int xoff[PSLOT], xlds[PSLOT];

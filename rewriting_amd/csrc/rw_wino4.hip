@@ -145,8 +145,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   }
 
   // ---- raw patch: buffer loads (out-of-image positions read 0), style applied on the way into LDS
-  const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(xb), 0, (int)((int64_t)p.in_ch * hw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xsrc = rw_image_rsrc(xb, 0, p.in_ch, hw);
   int xoff[PSLOT], xlds[PSLOT];
 #pragma unroll
   for (int sl = 0; sl < PSLOT; ++sl) {
@@ -437,7 +436,8 @@ __device__ __forceinline__ void w4_at_row(const float (&t)[6], float (&v)[4]) {
 // waits, epilogues).  The powers of two keep the operands inside f16's normal range: eU from max |U| at pack time (read
 // back by the host once per weight version and passed by value), eV from the bound x_amax >= max |x| that the producer of
 // the map left behind (or rw_absmax_f32), the style's largest factor and the transform's gain (<= 100): |V 2^eV| < 25600.  Both leave the result
-// through the epilogue's per-channel factor (exact).  e is read off bound * smax and clamped to [-100, 100]; the bound is
+// through the epilogue's per-channel factor (exact).  e is read off bound * smax and clamped to [-100, 100] -- the rule is
+// written once, rw_split_scales<headroom> in rw_common.h, for these kernels, rw_upwino.hip and the direct sums; the bound is
 // ONE number for the whole map and batch, smax the image's own largest |style|.  Values more than 2^17 below
 // bound * smax * gain lose low bits of Vl (f16 denormals: absolute error <= 2^-25 2^-eV).  Inside the footprint of a
 // large value that is what fp32 accumulation does to them beside the large terms anyway; AWAY from it -- an output
@@ -528,21 +528,16 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   // H16: 2^eV rides in the style table (the transform multiplies by it), 2^-(eU + eV) in the per-channel factor
   float in_scale = 1.f, out_scale = 1.f;
   if (H16) {
+    // (the loop and the shuffles written out, not rw_style_absmax_wave: with rw_wave_max in their place the compiler orders
+    // these kernels' prologues differently)
     float smax = p.style ? 0.f : 1.f;
     if (p.style)
       for (int i = tid; i < p.in_ch; i += THREADS) smax = fmaxf(smax, fabsf(p.style[(int64_t)ib * p.in_ch + i]));
 #pragma unroll
     for (int off = 32; off; off >>= 1) smax = fmaxf(smax, __shfl_xor(smax, off));
-    if (lane == 0) Red[wave] = smax;
-    __syncthreads();
-    smax = Red[0];
-#pragma unroll
-    for (int wv = 1; wv < WAVES; ++wv) smax = fmaxf(smax, Red[wv]);
-    const float am = rw_bound_load(p.x_amax) * smax;              // >= max |x style|; |B^T d B| <= 100 am < 2^(e + 7)
-    int e = (int)((__float_as_uint(am) >> 23) & 0xff) - 126;      // am < 2^e
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    in_scale = __uint_as_float((unsigned)(127 + 8 - e) << 23);
-    out_scale = __uint_as_float((unsigned)(127 + e - 8) << 23) * p.u_inv;
+    smax = rw_block_max<WAVES>(smax, lane, wave, Red);
+    // headroom 8: |B^T d B| <= 100 am < 2^(e + 7)
+    rw_split_scales<8>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
   }
   for (int i = tid; i < p.in_ch; i += THREADS) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
   if (tid < 16 * WGM) {
@@ -892,12 +887,6 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 
   // ---- the output transform of one accumulator component j: Y[r][k] = (A^T M A)[r][k] of this wave's out-channel block
   // (16 wm + 4 lk + j) on its tile.  PS: see the note above the body; `xs` = the weight slot just consumed.
-  auto lds_barrier = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0): LDS-direct loads stay in flight
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
   // partial tile of block ob from the three rows this wave holds: L0, L1, L2 = rows (0, 1, 2) resp. (5, 3, 4).  With
   // S = L1 + L2, D = L1 - L2 and R(.) the row pass:  wave 0: Y = (R(L0) + R(S), R(D), R(S), R(D));
   // wave 1: Y = (R(S), 2 R(D), 4 R(S), 8 R(D) + R(L0)) -- one stream, scalar coefficients (1 and 0 are exact).
@@ -943,7 +932,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     partial_rows(j, 18, y1);
     float* xw = &Us[xs * USZ + wave * 1024 + lane * 4];
     const float* xr = &Us[xs * USZ + (wave ^ WGN) * 1024 + lane * 4];
-    lds_barrier();                                  // nobody reads what the slot held (weights / the previous round)
+    rw_lds_barrier();                               // nobody reads what the slot held (weights / the previous round)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       rw_f32x4 o4;
@@ -951,7 +940,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
       for (int k = 0; k < 4; ++k) { o4[k] = wm ? y0[r][k] : y1[r][k]; Y[r][k] = wm ? y1[r][k] : y0[r][k]; }
       *reinterpret_cast<rw_f32x4*>(xw + r * 256) = o4;
     }
-    lds_barrier();
+    rw_lds_barrier();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const rw_f32x4 o4 = *reinterpret_cast<const rw_f32x4*>(xr + r * 256);

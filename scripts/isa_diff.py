@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Does the working tree generate the device code that <rev> generated?
+
+    scripts/isa_diff.py [--keep DIR] <rev> [rewriting_amd/csrc/rw_x.hip ...]      (default: every .hip of rewriting_amd/csrc)
+
+The sources of <rev> (git show <rev>:path) go into a temporary directory; both sides are compiled to gfx950 assembly
+with the library's own flags (csrc/build.sh, the file's "// hipcc-flags:" line, + --cuda-device-only -S), at most 16
+compilations at a time.  The listings are split at the function symbols and compared as text, kernel by kernel: the
+instruction text and the .amdhsa_* resource block (registers, scratch, LDS).  The lines that name the compilation
+unit's __hip_cuid_ symbol are dropped -- they differ between two builds of unchanged code.  Per kernel one line,
+"same", or "differs" with both instruction counts and both resource blocks; exit status 1 if anything differs.
+Needs hipcc and git, no GPU.  A full run compiles every file twice and takes minutes.
+"""
+import argparse
+import concurrent.futures
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = "rewriting_amd/csrc"
+HEADERS = [CSRC + "/rw_common.h", "include/rewriting_hip.h"]
+FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result".split()
+NOPK = "-Xclang -target-feature -Xclang -packed-fp32-ops".split()
+
+
+def compile_asm(tree, rel, out):
+    src = os.path.join(tree, rel)
+    with open(src) as f:
+        head = f.read(4096)
+    extra = re.search(r"^// hipcc-flags: (.*)$", head, re.M)
+    keep_pk = re.search(r"^// hipcc-keep-packed-fp32", head, re.M)
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + ([] if keep_pk else NOPK)
+    cmd += (extra.group(1).split() if extra else []) + ["--cuda-device-only", "-S", src, "-o", out]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode:
+        raise RuntimeError("%s\n%s" % (" ".join(cmd), r.stdout))
+    return out
+
+
+def split_listing(path):
+    """{symbol: [lines]} for every function, {kernel: [.amdhsa_ lines]}, and the lines outside both."""
+    funcs, res, rest = {}, {}, []
+    cur = kern = None
+    with open(path) as f:
+        for line in f:
+            line = line.rstrip()
+            if "__hip_cuid_" in line:
+                continue
+            m = re.match(r"\s*\.type\s+(\S+),@function", line)
+            if m:
+                cur = m.group(1)
+                funcs[cur] = []
+                continue
+            m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+            if m:
+                kern = m.group(1)
+                res[kern] = []
+                continue
+            if kern is not None:
+                if line.strip() == ".end_amdhsa_kernel":
+                    kern = None
+                else:
+                    res[kern].append(line.strip())
+                continue
+            if cur is not None:
+                if re.match(r"\s*\.size\s+%s," % re.escape(cur), line):
+                    cur = None
+                else:
+                    funcs[cur].append(line)
+                continue
+            rest.append(line)
+    return funcs, res, rest
+
+
+def n_instructions(lines):
+    n = 0
+    for line in lines:
+        s = line.strip()
+        if s and not s.startswith((".", ";")) and not s.split(";")[0].rstrip().endswith(":"):
+            n += 1
+    return n
+
+
+def show_resources(tag, block):
+    keep = [l for l in block if re.search(r"vgpr|sgpr|private_segment_fixed|group_segment_fixed|accum_offset", l)]
+    print("      %s: %s" % (tag, "  ".join(l.replace(".amdhsa_", "") for l in keep)))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("rev")
+    ap.add_argument("files", nargs="*")
+    ap.add_argument("--keep", metavar="DIR", help="keep both listings of every file in DIR (<file>.old.s, <file>.new.s)")
+    args = ap.parse_args()
+    files = [os.path.relpath(os.path.abspath(f), ROOT) for f in args.files]
+    if not files:
+        files = sorted(CSRC + "/" + f for f in os.listdir(os.path.join(ROOT, CSRC)) if f.endswith(".hip"))
+
+    differing = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        lst = tmp
+        if args.keep:
+            lst = os.path.abspath(args.keep)
+            os.makedirs(lst, exist_ok=True)
+        for rel in files + HEADERS:
+            dst = os.path.join(tmp, "old", rel)
+            os.makedirs(os.path.dirname(dst), exist_ok=True)
+            with open(dst, "wb") as f:
+                f.write(subprocess.check_output(["git", "show", "%s:%s" % (args.rev, rel)], cwd=ROOT))
+        jobs = {}
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            for rel in files:
+                base = os.path.basename(rel)
+                jobs[rel] = (pool.submit(compile_asm, os.path.join(tmp, "old"), rel, os.path.join(lst, base + ".old.s")),
+                             pool.submit(compile_asm, ROOT, rel, os.path.join(lst, base + ".new.s")))
+            for rel in files:
+                old_f, old_r, old_x = split_listing(jobs[rel][0].result())
+                new_f, new_r, new_x = split_listing(jobs[rel][1].result())
+                print("%s  (%d lines of assembly at %s, %d now)" % (
+                    rel, sum(map(len, old_f.values())) + len(old_x), args.rev, sum(map(len, new_f.values())) + len(new_x)))
+                for name in sorted(set(old_f) | set(new_f)):
+                    a, b = old_f.get(name), new_f.get(name)
+                    ra, rb = old_r.get(name, []), new_r.get(name, [])
+                    if a == b and ra == rb:
+                        print("  same     %s" % name)
+                        continue
+                    differing += 1
+                    if a is None or b is None:
+                        print("  differs  %s  (only %s)" % (name, "in the working tree" if a is None else "at " + args.rev))
+                        continue
+                    print("  differs  %s  instructions %d -> %d, resource block %s" % (
+                        name, n_instructions(a), n_instructions(b), "equal" if ra == rb else "DIFFERENT"))
+                    show_resources(args.rev, ra)
+                    show_resources("now", rb)
+                if old_x != new_x:
+                    differing += 1
+                    print("  differs  (the listing outside the functions: data, metadata)")
+    print("%d differ" % differing if differing else "all same")
+    return 1 if differing else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -3,8 +3,8 @@ rw_upwino.hip) evaluated in float64, and the inputs, refe
 (test_split_model.py on the host, test_gpu_split_range.py on the device).
 
 The model is hip_emulation.py's statement of these kernels with ONE thing kept from the device: the rounding of the scaled
-operands to pairs of f16 numbers, with the kernels' exponent rule (((bits >> 23) & 0xff) - 126 of bound * smax in fp32,
-clamped to +-100, smax per image).  The style product is the kernels' fp32 product and so is what else precedes the
+operands to pairs of f16 numbers, with the kernels' exponent rule (rw_exp_above / rw_split_scales in csrc/rw_common.h:
+((bits >> 23) & 0xff) - 126 of bound * smax in fp32, clamped to +-100, smax per image).  The style product is the kernels' fp32 product and so is what else precedes the
 rounding -- the input transform of the F(4x4,3x3) and F(2,2) kernels, in their own operation order; every sum after the
 rounding is float64, so what separates a kernel from the model is its fp32 accumulation -- nothing that depends on the
 range of the data.  The code is hip_emulation's own (its functions take any dtype).
@@ -28,17 +28,18 @@ BARS = {'direct': (3e-6, 2e-5), 'dconv_up': (3e-6, 2e-5), 'tconv': (3e-6, 2e-5),
         'wino4': (2e-5, 1e-4), 'wino4_up': (3e-5, 1e-4)}
 KS = (0, 12, 16, 20)
 
-# (name, kind, (batch, in, out, h, w), environment).  Which value reaches which kernel body, and with it which of the
-# sites that read the exponent off bound * smax:
-#   rw_dconv.hip   dconv_body (:147)       -- RW_DCONV_V=1 always; the upsampling mode below 32 input channels under both
-#                  dconv_ws_body (:590)    -- RW_DCONV_V=2 with in >= 32, out % 64 == 0, w % 64 == 0
-#   rw_tconv.hip   tconv_body (:162)       -- RW_TCONV_TY=8 / 16; unset outside 32 <= in <= 128; ANY value below 32 channels
-#                  tconv_ws_body (:890)    -- RW_TCONV_TY=0 and unset with 32 <= in <= 128: needs in >= 32
-#                  tconv_blur_pp (:1441)   -- RW_TCONV_TY=2, in >= 32
-#   rw_wino4.hip   (:537)                  -- one body for stride 1 and the upsampling phases; RW_W4H_PS=0 / 1 its two
+# (name, kind, (batch, in, out, h, w), environment).  The exponent rule is written once, rw_exp_above() in rw_common.h:
+# every kernel body reaches it through rw_split_scales<headroom>(bound * smax, ...), the host through rw_weight_scale_of().
+# Which value reaches which body, each with its own bound * smax and headroom:
+#   rw_dconv.hip   dconv_body              -- RW_DCONV_V=1 always; the upsampling mode below 32 input channels under both
+#                  dconv_ws_body           -- RW_DCONV_V=2 with in >= 32, out % 64 == 0, w % 64 == 0
+#   rw_tconv.hip   tconv_body              -- RW_TCONV_TY=8 / 16; unset outside 32 <= in <= 128; ANY value below 32 channels
+#                  tconv_ws_body           -- RW_TCONV_TY=0 and unset with 32 <= in <= 128: needs in >= 32
+#                  tconv_blur_pp_kernel    -- RW_TCONV_TY=2, in >= 32
+#   rw_wino4.hip   conv_wino36b_body       -- one body for stride 1 and the upsampling phases; RW_W4H_PS=0 / 1 its two
 #                                             ways of dealing the 36 points to the waves
-#   rw_upwino.hip  (:133)
-#   rw_common.h    rw_weight_scale_of (:159) -- every pack_* call (the zero-weight case reads it off a zero)
+#   rw_upwino.hip  conv_up_wino_body
+#   rw_common.h    rw_weight_scale_of      -- every pack_* call (the zero-weight case reads it off a zero)
 # The fused upsampling kernel's persistent bodies do not take 16 input channels, so they run at (2, 32, 16, 16, 32), the
 # smallest shape they take.
 FORMS = [
