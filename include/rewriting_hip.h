@@ -558,6 +558,47 @@ int rw_render_bytes_f32(const float* image, const void* selector, uint8_t* out, 
                         int mode, int sel_height, int sel_width, float level, int thickness, uint32_t border_rgb,
                         int32_t inside_rgb, float outside_bright, rw_stream_t stream);
 
+/* PNG encoding of bytes that are on the device: the per-byte work of renormalize.as_url's img.save(format='png')
+ * (utils/renormalize.py:22-32) and of SaveImageWorker.work (utils/imgsave.py:58-66), for image (images, H, W, 3) uint8 --
+ * what rw_render_bytes_f32 writes.  The PNG is 8-bit truecolour, not interlaced: signature, IHDR, one IDAT, IEND.
+ *   stream:   H rows of a filter type byte and 3 W residuals.  The type of a row is libpng's heuristic: the smallest, over
+ *             types 0 .. 4, sum of |residual as a signed byte|, ties to the lowest type; the prior row of row 0 is zero.
+ *   segments: the stream is cut into segments of S = rw_png_segment_bytes() bytes, nseg = ceil(H (1 + 3 W) / S).
+ *   IDAT:     a zlib stream: 78 01; per segment one deflate block with dynamic Huffman codes and LITERALS ONLY (HDIST = 0,
+ *             one distance code of length 0: RFC 1951 3.2.7), its end-of-block, and an empty stored block (000, pad to the
+ *             byte, 00 00 FF FF), so that every segment is a whole number of bytes and stands alone; then 01 00 00 FF FF
+ *             and the Adler-32.  No LZ77 matches: flat images cost at least one bit per byte.
+ * The host does the O(256)-per-image work between the calls: from hist it builds one complete prefix code per image
+ * (lengths <= 15, symbol 256 counted once per segment), the complete code-length code (<= 7) and the bits of the block
+ * header; it frames the chunks (CRC-32) and folds the segments' Adler sums.
+ *   rw_png_filter_u8   row_type (images, H) bytes; stream (images, nseg S) bytes, 16-byte aligned -- of every 16-byte
+ *                      piece that starts inside an image's stream all 16 bytes are written, zeros past its end;
+ *                      hist_part (images, nseg, 256) and hist (images, 256) counts of the stream's bytes;
+ *                      adler (images, nseg, 2): s1 = sum d_k and s2 = sum (n - k) d_k mod 65521 over the n bytes d_0 ..
+ *                      of a segment (a, b) -> (a + s1, b + n a + s2) folds a segment into a running Adler-32.
+ *   rw_png_encode_u8   table (images, rw_png_table_words()) uint32: [0] the bits of the block header (at most 2048),
+ *                      [1 + s] for s = 0 .. 256 the code of symbol s, bit-reversed (as it lies in the stream), | its length
+ *                      << 16, [258 ..] the header's bits, first bit in bit 0.  coded (images, nseg, C) bytes with
+ *                      C = rw_png_segment_capacity(), 16-byte aligned: a segment's bytes from the start of its slot;
+ *                      lengths (images, nseg) their number.
+ *   rw_png_compact_u8  offsets (segments) uint64 scratch; head (segments, 3) uint32 = length, s1, s2; bytes: the
+ *                      segments back to back, in order.  A segment that would end past `capacity` bytes is left out (its
+ *                      length is still reported).  The host sizes `bytes` from hist and its code lengths.
+ * Histograms and sums follow the rule of the bounds: LDS atomics inside a workgroup, plain stores of per-workgroup
+ * partials, a small launch that adds them in order; no global atomics, nothing zeroed first, one writer per byte.  All of
+ * it is integer work: an image's PNG is the same on every run, alone or in a batch.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null pointer, images < 1, a grid past 31 bits, a stream / coded pointer that
+ * is not 16-byte aligned.  RW_ERR_UNSUPPORTED (nothing launched): H or W < 1, a stream of 2^31 bytes or more. */
+int64_t rw_png_segment_bytes(void);
+int64_t rw_png_segment_capacity(void);
+int64_t rw_png_table_words(void);
+int rw_png_filter_u8(const uint8_t* image, uint8_t* row_type, uint8_t* stream, uint32_t* hist_part, uint32_t* hist,
+                     uint32_t* adler, int64_t images, int height, int width, rw_stream_t stream_);
+int rw_png_encode_u8(const uint8_t* stream, const uint32_t* table, uint8_t* coded, uint32_t* lengths, int64_t images,
+                     int height, int width, rw_stream_t stream_);
+int rw_png_compact_u8(const uint8_t* coded, const uint32_t* lengths, const uint32_t* adler, uint64_t* offsets,
+                      uint32_t* head, uint8_t* bytes, int64_t capacity, int64_t segments, rw_stream_t stream_);
+
 /* ---------------------------------------------------------------------------------------
  * The rank-constrained solve -- replaces the body of ProgressiveGanRewriter.insert
  * (rewrite/ganrewrite.py:254-298) and of linear_insert (:201-252) for a SeqStyleGAN2 layer

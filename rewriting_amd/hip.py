@@ -1006,6 +1006,93 @@ def render_bytes(images, activations=None, mask=None, level=None, thickness=1, b
     return out
 
 
+def png_segment_bytes():
+    """Stream bytes per deflate block of png_encode (rw_png_segment_bytes)"""
+    return int(lib().rw_png_segment_bytes())
+
+
+def png_encode(bytes_bhwc, timings=None, deferred=False):
+    """One PNG file (bytes) per image of bytes_bhwc (B, H, W, 3) uint8 on the device -- what render_bytes returns --
+    lossless, 8-bit truecolour: the filters, the histogram, the Huffman coding and the compaction run in rw_png_filter_u8 /
+    rw_png_encode_u8 / rw_png_compact_u8, the host builds one code table per image from 256 counts (pngcode) and frames
+    the chunks.  Two copies to the host (the counts; the coded bytes with their lengths and Adler sums) and one to the
+    device (the tables).  Literals only, no LZ77 matches: photographic content codes like PIL's default, flat images
+    cost at least one bit per byte.  The input is read in place: a view that is not contiguous, a wrong dtype or device
+    is refused, never copied.  An empty batch gives [].  deferred: return one callable per image that frames its file
+    (CRC-32, Adler fold, chunks) when called -- for a pool of writer threads (pngwriter.save_image_set).  timings: a dict
+    that receives milliseconds of the stages (filter, host, encode, compact, copy) from HIP events -- it synchronises; for
+    benchmarks."""
+    import numpy
+    from . import pngcode
+    x = _in_place(bytes_bhwc, 'bytes', torch.uint8)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('rewriting_amd: png_encode takes bytes (B, H, W, 3), not %s' % (tuple(x.shape),))
+    b, h, w, _ = x.shape
+    if b == 0:
+        return []
+    stream_len = h * (1 + 3 * w)
+    if h < 1 or w < 1 or stream_len >= 2 ** 31:
+        raise RuntimeError('rewriting_amd: png_encode takes images of at least 1 x 1 whose filtered stream H (1 + 3 W) is '
+                           'below 2^31 bytes (RW_ERR_UNSUPPORTED, include/rewriting_hip.h), not %d x %d' % (h, w))
+    seg, cap, words = png_segment_bytes(), int(lib().rw_png_segment_capacity()), int(lib().rw_png_table_words())
+    assert words == pngcode.TABLE_WORDS
+    nseg = -(-stream_len // seg)
+    dev = x.device
+    marks = []
+
+    def mark(name):
+        if timings is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            marks.append((name, event))
+
+    def new(*shape, dtype=torch.int32):
+        return torch.empty(*shape, device=dev, dtype=dtype)
+
+    mark('start')
+    row_type, stream = new(b, h, dtype=torch.uint8), new(b, nseg * seg, dtype=torch.uint8)
+    hist_part, hist, adler = new(b, nseg, 256), new(b, 256), new(b, nseg, 2)
+    check(lib().rw_png_filter_u8(_p(x), _p(row_type), _p(stream), _p(hist_part), _p(hist), _p(adler), b, h, w, _stream()))
+    mark('filter')
+    counts = hist.cpu().numpy().astype(numpy.int64)
+    table = numpy.empty((b, words), dtype=numpy.uint32)
+    bound = 0
+    for i in range(b):
+        table[i], lengths = pngcode.code_table(counts[i], nseg)
+        bound += pngcode.coded_bytes_bound(counts[i], lengths, int(table[i, 0]), nseg)
+    table_dev = torch.from_numpy(table.view(numpy.int32)).to(dev)
+    mark('host')
+    coded, seg_len = new(b, nseg, cap, dtype=torch.uint8), new(b, nseg)
+    check(lib().rw_png_encode_u8(_p(stream), _p(table_dev), _p(coded), _p(seg_len), b, h, w, _stream()))
+    mark('encode')
+    n = b * nseg
+    head_bytes = -(-12 * n // 16) * 16
+    packed, offsets = new(head_bytes + bound, dtype=torch.uint8), new(n, dtype=torch.int64)
+    check(lib().rw_png_compact_u8(_p(coded), _p(seg_len), _p(adler), _p(offsets), _p(packed),
+                                  ctypes.c_void_p(packed.data_ptr() + head_bytes), bound, n, _stream()))
+    mark('compact')
+    host = packed.cpu().numpy()
+    mark('copy')
+    if timings is not None:
+        torch.cuda.synchronize(dev)
+        for (_, before), (name, after) in zip(marks, marks[1:]):
+            timings[name] = timings.get(name, 0.0) + before.elapsed_time(after)
+    head = host[:12 * n].view('<u4').reshape(b, nseg, 3).astype(numpy.int64)
+    if int(head[:, :, 0].sum()) > bound:
+        raise RuntimeError('rewriting_amd: png_encode coded %d bytes, the host expected at most %d'
+                           % (int(head[:, :, 0].sum()), bound))
+    body = memoryview(host)[head_bytes:]
+    sizes = [min(seg, stream_len - s * seg) for s in range(nseg)]
+    ends = numpy.cumsum(head[:, :, 0].sum(axis=1)).tolist()          # an image's segments lie back to back
+
+    def framer(i):
+        parts = list(zip(sizes, head[i, :, 1].tolist(), head[i, :, 2].tolist()))
+        middle = body[ends[i - 1] if i else 0:ends[i]]
+        return lambda: pngcode.frame(w, h, [middle], pngcode.adler_fold(parts))
+    framers = [framer(i) for i in range(b)]
+    return framers if deferred else [make() for make in framers]
+
+
 # ------------------------------------------------------------------ solve
 def project_weight(w, context, base=None, out=None):
     """out = base + P(w), P = projected_conv (rewrite/ganrewrite.py:806-813).  w (..., O, I, kh, kw)."""

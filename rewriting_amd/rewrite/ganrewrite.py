@@ -684,15 +684,36 @@ class ProgressiveGanRewriter(object):
         """Batches of three, as the reference renders them (rewrite/ganrewrite.py:626-650): an image's noise row is
         its position in its batch of three (quirk Q1), for the picture and for the heat map alike.  With device_render
         the bytes of every batch are built on the device (one launch each) and come to the host in one copy."""
+        parts = self._picture_batches(imgnums, key, level, **kwargs)
+        if parts and torch.is_tensor(parts[0]):
+            return self._as_images(torch.cat(parts))
+        return [picture for part in parts for picture in part]
+
+    def _picture_batches(self, imgnums, key=None, level=None, **kwargs):
+        """render_image_batch's pictures per batch of three: bytes on the device where hip.render_bytes builds them, PIL
+        pictures otherwise"""
         parts = []
         for i in range(0, len(imgnums), 3):
             with torch.no_grad():
                 zb = torch.cat([self.get_z(n) for n in imgnums[i:i + 3]])
                 batch = self.rendered_image(self.sample_image_from_latent(zb))
             parts.append(self._pictures(batch, self._heat(zb, key, level), level, as_bytes=True, **kwargs))
-        if parts and torch.is_tensor(parts[0]):
-            return self._as_images(torch.cat(parts))
-        return [picture for part in parts for picture in part]
+        return parts
+
+    def render_urls(self, imgnums, key=None, level=None, **kwargs):
+        """The data URLs (``renormalize.as_url``) of the pictures render_image_batch shows, with the bytes AND the PNG
+        files built on the device (hip.render_bytes, hip.png_encode): one coded buffer comes to the host instead of
+        twelve pictures for twelve PIL saves.  Needs the device overlay route (device_render=True, the model on the
+        device, an overlay the kernel takes); there is no host fall-back -- render_image_batch + as_url is that."""
+        from .. import pngwriter
+        parts = self._picture_batches(imgnums, key, level, **kwargs)
+        if not parts:
+            return []
+        if not torch.is_tensor(parts[0]):
+            raise RuntimeError('rewriting_amd: render_urls needs the device overlay route (device_render=True, the model '
+                               'on a HIP device, an overlay hip.render_bytes takes); use render_image_batch and '
+                               'renormalize.as_url on the host')
+        return [pngwriter.as_url(png) for png in hip.png_encode(torch.cat(parts))]
 
 
 class SeqStyleGanRewriter(ProgressiveGanRewriter):
