@@ -67,6 +67,34 @@ typedef _Float16 rw_f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 rw_f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 rw_f16x8 __attribute__((ext_vector_type(8)));
 
+// Row of the 32x32 C/D tile of v_mfma_f32_32x32x* that accumulator register r (0 .. 15) of a lane holds; frow = lane >> 5,
+// the column is lane & 31.
+__host__ __device__ __forceinline__ constexpr int rw_mfma32_row(int r, int frow = 0) {
+  return 4 * frow + (r & 3) + 8 * (r >> 2);
+}
+
+// ---- the 3x3 convolution as a GEMM over gathered columns (the solver's K1 / K3 in rw_solve.hip, conv_wgrad_kernel in
+// rw_grad.hip).  Extent, along one axis of n input samples, of the map the convolution writes: n for the stride-1 layer,
+// 2n + 1 -- the pre-blur map -- for an upsampling layer (conv_transpose2d stride 2, utils/stylegan2/models.py:315-316).
+__host__ __device__ static inline int rw_conv_extent(int upsample, int n) { return upsample ? 2 * n + 1 : n; }
+// xcol[k = (i, tap)][position]: the sample of the h x w plane of channel i that weight tap (ky, kx) multiplies at
+// conv-output position (Y, X); zero outside the plane (zero padding, pad 1; the solver's crop: quirk Q2) and, for the
+// transposed convolution, where the parity of (Y - ky, X - kx) does not land on an input sample.
+// p = the kernel's problem struct (its upsample, h, w).
+template <class P> __device__ __forceinline__ float rw_conv_gather(const P& p, const float* plane, int tap, int Y, int X) {
+  const int ky = tap / 3, kx = tap - 3 * ky;
+  int iy, ix;
+  if (p.upsample) {
+    const int ty = Y - ky, tx = X - kx;
+    if ((ty | tx) < 0 || ((ty | tx) & 1)) return 0.f;
+    iy = ty >> 1; ix = tx >> 1;
+  } else {
+    iy = Y + ky - 1; ix = X + kx - 1;
+  }
+  if (iy < 0 || iy >= p.h || ix < 0 || ix >= p.w) return 0.f;
+  return plane[iy * p.w + ix];
+}
+
 // a compile-time integer as a function argument (generic lambdas unrolled by hand)
 template <int N> struct rw_int { static constexpr int value = N; };
 

@@ -10,7 +10,9 @@
 // (Q3: the demodulation factor is differentiable).  The weight gradient is the GEMM of the
 // solver's K3 (rw_solve.hip) without its Adam epilogue, generalised to a batch and to maps of any size: M = out
 // channels, N = (in channel, tap) columns, K = batch x conv-output positions, fp32 MFMA, split-K over workgroups
-// with the partial sums reduced in a fixed order (no atomics: the result is deterministic).
+// with the partial sums reduced in a fixed order (no atomics: the result is deterministic).  The gathered column, the
+// extent of the convolution's map and the MFMA row map are rw_common.h's (rw_conv_gather, rw_conv_extent, rw_mfma32_row),
+// shared with the solver; the K loop with its operand ring is written out as in K1 / K3 (rw_solve.hip says why).
 //
 // At the end of the file: the two adjoints of ToRGB (models.py:394-425, 639-655) that a loss on the IMAGE needs -- the
 // gradient to the feature map (streaming: 3 planes in, in_ch planes out) and the per-image sums  g . x  over the pixels
@@ -31,26 +33,6 @@ struct WgradProblem {
   int batch, in_ch, out_ch, h, w, upsample, ksplit;
 };
 
-__host__ __device__ static inline int wg_conv_w(const WgradProblem& p) { return p.upsample ? 2 * p.w + 1 : p.w; }
-__host__ __device__ static inline int wg_conv_h(const WgradProblem& p) { return p.upsample ? 2 * p.h + 1 : p.h; }
-
-// the input sample that weight tap (ky, kx) of one channel multiplies at conv-output position (Y, X): zero padding
-// for the stride-1 convolution (pad 1); for the stride-2 transposed convolution only where the parity of
-// (Y - ky, X - kx) lands on an input sample (F.conv_transpose2d, models.py:315-316)
-__device__ __forceinline__ float wg_gather(const WgradProblem& p, const float* xi, int tap, int Y, int X) {
-  const int ky = tap / 3, kx = tap - 3 * ky;
-  int iy, ix;
-  if (p.upsample) {
-    const int ty = Y - ky, tx = X - kx;
-    if ((ty | tx) < 0 || ((ty | tx) & 1)) return 0.f;
-    iy = ty >> 1; ix = tx >> 1;
-  } else {
-    iy = Y + ky - 1; ix = X + kx - 1;
-  }
-  if (iy < 0 || iy >= p.h || ix < 0 || ix >= p.w) return 0.f;
-  return xi[iy * p.w + ix];
-}
-
 __global__ void __launch_bounds__(256) conv_wgrad_kernel(const WgradProblem p) {
   __shared__ float As[2][WG_KC][WG_BM + 4];
   __shared__ float Bs[2][WG_KC][WG_BN];
@@ -58,7 +40,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(const WgradProblem p) {
   const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;      // wave tile: 32 out channels x 32 columns
   const int frow = lane >> 5, fcol = lane & 31;
   const int o0 = blockIdx.x * WG_BM, k0 = blockIdx.y * WG_BN, ks = blockIdx.z;
-  const int CW = wg_conv_w(p), P = wg_conv_h(p) * CW;
+  const int CW = rw_conv_extent(p.upsample, p.w), P = rw_conv_extent(p.upsample, p.h) * CW;
   const int K = 9 * p.in_ch;
   const int cpb = (P + WG_KC - 1) / WG_KC;                     // chunks per batch item (none straddles two items)
   const int chunks = cpb * p.batch;
@@ -93,7 +75,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(const WgradProblem p) {
       float v = 0.f;
       if (n < P && col_ok) {
         const int y = n / CW;
-        v = wg_gather(p, xi, ctap, y, n - y * CW) * xs;
+        v = rw_conv_gather(p, xi, ctap, y, n - y * CW) * xs;
       }
       breg[slot][j] = v;
     }
@@ -135,7 +117,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(const WgradProblem p) {
   const int k = k0 + wn0 + fcol;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int o = o0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * frow;
+    const int o = o0 + wm0 + rw_mfma32_row(r, frow);
     if (o < p.out_ch && k < K) out[(int64_t)o * K + k] = acc[r];
   }
 }
@@ -152,7 +134,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 
 extern "C" int rw_conv_wgrad_ksplit(int batch, int in_ch, int out_ch, int h, int w, int upsample) {
   if (batch <= 0 || in_ch <= 0 || out_ch <= 0 || h <= 0 || w <= 0) return 0;
-  const int CH = upsample ? 2 * h + 1 : h, CW = upsample ? 2 * w + 1 : w;
+  const int CH = rw_conv_extent(upsample, h), CW = rw_conv_extent(upsample, w);
   const int64_t blocks = rw_cdiv(out_ch, WG_BM) * rw_cdiv(9 * (int64_t)in_ch, WG_BN);
   const int64_t chunks = rw_cdiv((int64_t)CH * CW, WG_KC) * batch;
   int64_t ks = rw_cdiv(1024, blocks);                 // ~4 workgroups per CU

@@ -518,7 +518,6 @@ __global__ void __launch_bounds__(256) equal_linear_kernel(
 // component j to MFMA j of the block (k = 16 c + 4 q + j on both operands: every k exactly once).  The butterfly
 // kernel above is one memory latency + six shuffle rounds per four batch rows (18 us at batch 64, 51 us at 250 --
 // 7 % of a key-statistics sweep); this one is 128 MFMAs behind 8-deep load batches.
-typedef float rw_lin_f32x4 __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(64) equal_linear_mfma_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ y, int batch, int in_dim, int out_dim, int64_t x_stride, float w_scale,
@@ -528,21 +527,21 @@ __global__ void __launch_bounds__(64) equal_linear_mfma_kernel(
   const int brow = min(b0 + mn, batch - 1);                 // rows past the batch: a legal row, results dropped
   const float* xp = x + (int64_t)brow * x_stride + 4 * q;
   const float* wp = w + (int64_t)(o0 + mn) * in_dim + 4 * q;
-  rw_lin_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  rw_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const int blocks = in_dim >> 4;
   constexpr int DEPTH = 8;
   for (int c0 = 0; c0 < blocks; c0 += DEPTH) {
-    rw_lin_f32x4 a[DEPTH], b[DEPTH];
+    rw_f32x4 a[DEPTH], b[DEPTH];
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       const int c = min(c0 + d, blocks - 1);
-      a[d] = *reinterpret_cast<const rw_lin_f32x4*>(xp + 16 * c);
-      b[d] = *reinterpret_cast<const rw_lin_f32x4*>(wp + 16 * c);
+      a[d] = *reinterpret_cast<const rw_f32x4*>(xp + 16 * c);
+      b[d] = *reinterpret_cast<const rw_f32x4*>(wp + 16 * c);
     }
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       if (c0 + d < blocks) {
-        const rw_lin_f32x4 bs = b[d] * w_scale;            // the reference scales the weight before F.linear
+        const rw_f32x4 bs = b[d] * w_scale;            // the reference scales the weight before F.linear
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[d][j], bs[j], acc, 0, 0, 0);
       }
@@ -718,16 +717,16 @@ __global__ void __launch_bounds__(64) demod_mfma_kernel(const float* __restrict_
   const int brow = min(b0 + mn, batch - 1);
   const float* sp = style + (int64_t)brow * in_ch + 4 * q;
   const float* wp = wsq + (int64_t)(o0 + mn) * in_ch + 4 * q;
-  rw_lin_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  rw_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const int blocks = in_ch >> 4;
   constexpr int DEPTH = 8;
   for (int c0 = 0; c0 < blocks; c0 += DEPTH) {
-    rw_lin_f32x4 a[DEPTH], b[DEPTH];
+    rw_f32x4 a[DEPTH], b[DEPTH];
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       const int c = min(c0 + d, blocks - 1);
-      a[d] = *reinterpret_cast<const rw_lin_f32x4*>(sp + 16 * c);
-      b[d] = *reinterpret_cast<const rw_lin_f32x4*>(wp + 16 * c);
+      a[d] = *reinterpret_cast<const rw_f32x4*>(sp + 16 * c);
+      b[d] = *reinterpret_cast<const rw_f32x4*>(wp + 16 * c);
     }
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {

@@ -19,6 +19,13 @@
 // The per-iteration scalars (lr/(1-b1^t), sqrt(1-b2^t)) come from device tables indexed by a
 // device-side step counter, so ten iterations can be captured in one HIP graph and replayed
 // with no host synchronisation; losses are written to a device array.
+//
+// Steps that several kernels take are stated once: the gathered column of the GEMMs and the extent of the map the
+// convolution writes (rw_conv_gather, rw_conv_extent) and the C/D row map of the 32x32 MFMA (rw_mfma32_row) in rw_common.h,
+// shared with rw_grad.hip; the loss at one element (sv_lrelu, sv_l1_grad, sv_l1_step) for K2 in both forms and for the
+// one-launch kernels; and, for the two one-launch kernels at the end of the file, phase B, the rank-r projection, the tap
+// blocks and the LDS prologue (svp_phase_b, svp_reduce_rows / svp_project_rows, svp_fwd_taps / svp_grad_taps,
+// svp_fill_maps) over one svp_ctx.  What stayed written out says so where it stands.
 #include "rw_common.h"
 #include <stdlib.h>
 
@@ -33,30 +40,6 @@
 #define SV_DEPTH 4      // chunks of operands in flight per workgroup (K1, K3)
 
 static inline int sv_pp(int p) { return (int)rw_cdiv(p, 64) * 64; }
-
-// Number of positions of the map the convolution writes: h*w for the stride-1 layer, the
-// (2h+1) x (2w+1) pre-blur map for an upsampling layer (conv_transpose2d stride 2,
-// utils/stylegan2/models.py:315-316).
-__host__ __device__ static inline int sv_conv_w(const rw_solve_problem& p) { return p.upsample ? 2 * p.w + 1 : p.w; }
-__host__ __device__ static inline int sv_conv_h(const rw_solve_problem& p) { return p.upsample ? 2 * p.h + 1 : p.h; }
-
-// xcol[k = (i, tap)][position]: the input sample that weight tap (ky,kx) of channel i multiplies
-// at conv-output position (Y, X); zero outside the crop (quirk Q2) and, for the transposed conv,
-// where the parity of (Y-ky, X-kx) does not land on an input sample.
-__device__ __forceinline__ float sv_gather(const rw_solve_problem& p, const float* key_i, int tap,
-                                           int Y, int X) {
-  const int ky = tap / 3, kx = tap - 3 * ky;
-  int iy, ix;
-  if (p.upsample) {
-    const int ty = Y - ky, tx = X - kx;
-    if ((ty | tx) < 0 || ((ty | tx) & 1)) return 0.f;
-    iy = ty >> 1; ix = tx >> 1;
-  } else {
-    iy = Y + ky - 1; ix = X + kx - 1;
-  }
-  if (iy < 0 || iy >= p.h || ix < 0 || ix >= p.w) return 0.f;
-  return key_i[iy * p.w + ix];
-}
 
 extern "C" int rw_solve_ksplit(int out_ch, int in_ch, int h, int w) {
   const int blocks = (out_ch / SV_BM) * (int)rw_cdiv((int64_t)h * w, SV_BN);
@@ -80,8 +63,8 @@ __global__ void __launch_bounds__(256) solve_fwd_kernel(const rw_solve_problem p
   const int o0 = blockIdx.x * SV_BM;
   const int n0 = blockIdx.y * SV_BN;
   const int ks = blockIdx.z;
-  const int CW = sv_conv_w(p);
-  const int P = sv_conv_h(p) * CW;
+  const int CW = rw_conv_extent(p.upsample, p.w);
+  const int P = rw_conv_extent(p.upsample, p.h) * CW;
   const int K = 9 * p.in_ch;
   const int chunks = K / SV_KC;
   const int cbeg = (int)((int64_t)chunks * ks / p.ksplit), cend = (int)((int64_t)chunks * (ks + 1) / p.ksplit);
@@ -95,6 +78,9 @@ __global__ void __launch_bounds__(256) solve_fwd_kernel(const rw_solve_problem p
   const bool pix_ok = pix < P;
   const int py = pix_ok ? pix / CW : 0, px = pix_ok ? pix - py * CW : 0;
 
+  // (The ring and its K loop are written out here, in K3 and in conv_wgrad_kernel of rw_grad.hip: as one template over
+  // fetch / stash / mma callables the three kernels came out with other address arithmetic and other register counts --
+  // as they do with this very loop wrapped, verbatim, in one more inlined lambda.)
   // Operands are fetched SV_DEPTH chunks ahead through a ring of register sets: the K range of a workgroup is
   // only 9 - 18 chunks of 8 MFMAs, and with a one-ahead prefetch every chunk cost a full memory latency (13 us
   // for 1.2 GFLOP).  Nothing touches a fetched value before its stash, SV_DEPTH - 1 chunks later.
@@ -111,7 +97,7 @@ __global__ void __launch_bounds__(256) solve_fwd_kernel(const rw_solve_problem p
     for (int j = 0; j < 4; ++j) {
       const int k = k0 + bk0 + 4 * j;
       const int i = k / 9, tap = k - 9 * i;
-      breg[slot][j] = pix_ok ? sv_gather(p, p.key + (int64_t)i * p.h * p.w, tap, py, px) : 0.f;
+      breg[slot][j] = pix_ok ? rw_conv_gather(p, p.key + (int64_t)i * p.h * p.w, tap, py, px) : 0.f;
     }
   };
   auto stash = [&](int buf, int slot) __attribute__((always_inline)) {
@@ -156,7 +142,7 @@ __global__ void __launch_bounds__(256) solve_fwd_kernel(const rw_solve_problem p
   float* cpart = p.conv + (int64_t)ks * p.out_ch * pp;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int o = o0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * frow;
+    const int o = o0 + wm0 + rw_mfma32_row(r, frow);
     const int n = n0 + wn0 + fcol;
     cpart[(int64_t)o * pp + n] = acc[r];
   }
@@ -181,6 +167,40 @@ __device__ __forceinline__ float sv_sum_partials(const float* base, int64_t stri
 }
 
 // ---------------------------------------------------------------------------------------
+// The loss at one element of the target, stated once for K2 (both forms) and phase B of the one-launch kernels.
+// ---------------------------------------------------------------------------------------
+// FusedLeakyReLU's activation: leaky ReLU (slope 0.2) x sqrt 2
+__device__ __forceinline__ float sv_lrelu(float pre) { return 1.4142135623730951f * ((pre > 0.f) ? pre : 0.2f * pre); }
+// The L1 half: |out - target|, and in g_pre dL/dpre of the mean-reduced l1_loss through the activation (plain: there is
+// none).  (plain by reference: the caller's flag, read where the written-out code read it -- passed by value, K2 comes out
+// with one select fewer.)
+__device__ __forceinline__ float sv_l1_grad(float pre, float out, float target, float inv_numel, const bool& plain,
+                                            float& g_pre) {
+  const float diff = out - target;
+  const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
+  const float g_out = sgn * inv_numel;                      // l1_loss backward, mean reduction
+  g_pre = plain ? g_out : ((pre > 0.f) ? g_out : g_out * 0.2f) * 1.4142135623730951f;  // kernel case 31
+  return fabsf(diff);
+}
+// The whole step from the scaled convolution sum: demodulate, add noise_term() (= noise_w * noise) and the bias, activate,
+// then the L1 half.  plain (bias == NULL): the target is the demodulated convolution alone (SeqTinyStyleGanRewriter,
+// rewrite/ganrewrite.py:731-738): no noise, no bias, no activation between it and the loss -- noise_term is a callable
+// so that such a target reads none.
+template <class Noise>
+__device__ __forceinline__ float sv_l1_step(float conv, float demod, const Noise& noise_term, float bias, float target,
+                                            float inv_numel, const bool& plain, float& g_pre) {
+  float out, pre;
+  if (plain) {
+    pre = conv * demod;
+    out = pre;
+  } else {
+    pre = conv * demod + noise_term() + bias;
+    out = sv_lrelu(pre);
+  }
+  return sv_l1_grad(pre, out, target, inv_numel, plain, g_pre);
+}
+
+// ---------------------------------------------------------------------------------------
 // K2: one workgroup per out channel
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) solve_mid_kernel(const rw_solve_problem p, int pp, float* lpart) {
@@ -189,12 +209,10 @@ __global__ void __launch_bounds__(256) solve_mid_kernel(const rw_solve_problem p
   const int lane = threadIdx.x & 63;
   const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (o >= p.out_ch) return;
-  const int P = sv_conv_h(p) * sv_conv_w(p);
+  const int P = rw_conv_extent(p.upsample, p.h) * rw_conv_extent(p.upsample, p.w);
   const float wsq = sv_sum_partials(p.wsq + o, p.out_ch, p.ksplit);
   const float demod = rsqrtf(wsq + 1e-8f);
-  // bias == NULL: the target is the demodulated convolution alone (SeqTinyStyleGanRewriter,
-  // rewrite/ganrewrite.py:731-738): no noise, no bias, no activation between it and the loss
-  const bool plain = p.bias == nullptr;
+  const bool plain = p.bias == nullptr;        // sv_l1_step
   const float nw = plain ? 0.f : p.noise_w[0], bv = plain ? 0.f : p.bias[o];
   const float inv_numel = 1.0f / ((float)p.out_ch * (float)P);
   float lsum = 0.f, tsum = 0.f;
@@ -203,20 +221,8 @@ __global__ void __launch_bounds__(256) solve_mid_kernel(const rw_solve_problem p
     if (n < P) {
       float conv = sv_sum_partials(p.conv + (int64_t)o * pp + n, (int64_t)p.out_ch * pp, p.ksplit);
       conv *= p.w_scale;
-      float out, pre;
-      if (plain) {
-        pre = conv * demod;
-        out = pre;
-      } else {
-        pre = conv * demod + nw * p.noise[n] + bv;
-        out = 1.4142135623730951f * ((pre > 0.f) ? pre : 0.2f * pre);
-      }
-      const float diff = out - p.val[(int64_t)o * P + n];
-      lsum += fabsf(diff);
-      const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-      const float g_out = sgn * inv_numel;                      // l1_loss backward, mean reduction
-      const float g_pre = plain ? g_out
-                                : ((pre > 0.f) ? g_out : g_out * 0.2f) * 1.4142135623730951f;  // kernel case 31
+      float g_pre;
+      lsum += sv_l1_step(conv, demod, [&] { return nw * p.noise[n]; }, bv, p.val[(int64_t)o * P + n], inv_numel, plain, g_pre);
       gdv = g_pre * demod;
       tsum += g_pre * conv;
     }
@@ -269,12 +275,7 @@ __global__ void __launch_bounds__(256) solve_mid_up_kernel(const rw_solve_proble
       }
     }
     const float pre = b + nw * p.noise[n] + bv;
-    const float out = 1.4142135623730951f * ((pre > 0.f) ? pre : 0.2f * pre);
-    const float diff = out - p.val[(int64_t)o * PO + n];
-    lsum += fabsf(diff);
-    const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-    const float g_out = sgn * inv_numel;
-    gpre[n] = ((pre > 0.f) ? g_out : g_out * 0.2f) * 1.4142135623730951f;
+    lsum += sv_l1_grad(pre, sv_lrelu(pre), p.val[(int64_t)o * PO + n], inv_numel, false, gpre[n]);
   }
   __syncthreads();
   float tsum = 0.f;
@@ -332,8 +333,8 @@ __global__ void __launch_bounds__(256) solve_bwd_adam_kernel(const rw_solve_prob
   const int frow = lane >> 5, fcol = lane & 31;
   const int o0 = blockIdx.x * SV_BM;
   const int k0 = blockIdx.y * SV_BNK;
-  const int CW = sv_conv_w(p);
-  const int P = sv_conv_h(p) * CW;
+  const int CW = rw_conv_extent(p.upsample, p.w);
+  const int P = rw_conv_extent(p.upsample, p.h) * CW;
   const int K = 9 * p.in_ch;
   const int it = p.step_counter[0];
 
@@ -363,7 +364,7 @@ __global__ void __launch_bounds__(256) solve_bwd_adam_kernel(const rw_solve_prob
       float v = 0.f;
       if (n < P && col_ok) {
         const int y = n / CW;
-        v = sv_gather(p, kch, ctap, y, n - y * CW);
+        v = rw_conv_gather(p, kch, ctap, y, n - y * CW);
       }
       breg[slot][j] = v;
     }
@@ -415,7 +416,7 @@ __global__ void __launch_bounds__(256) solve_bwd_adam_kernel(const rw_solve_prob
   const float step_size = p.step_size[it], bc2s = p.bc2_sqrt[it];
   float c2v[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) c2v[r] = p.c2[o0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * frow];
+  for (int r = 0; r < 16; ++r) c2v[r] = p.c2[o0 + wm0 + rw_mfma32_row(r, frow)];
 #pragma unroll
   for (int b = 0; b < SV_NB; ++b) {
     const int k = k0 + wn0 + 32 * b + fcol;
@@ -427,26 +428,26 @@ __global__ void __launch_bounds__(256) solve_bwd_adam_kernel(const rw_solve_prob
     float wv[16], mv[16], vv[16];
     const bool adam = !(p.low_rank_gradient || p.linear_insert);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) wv[r] = p.weight[base + (int64_t)((r & 3) + 8 * (r >> 2)) * K];
+    for (int r = 0; r < 16; ++r) wv[r] = p.weight[base + (int64_t)rw_mfma32_row(r) * K];
     if (adam) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) mv[r] = p.exp_avg[base + (int64_t)((r & 3) + 8 * (r >> 2)) * K];
+      for (int r = 0; r < 16; ++r) mv[r] = p.exp_avg[base + (int64_t)rw_mfma32_row(r) * K];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) vv[r] = p.exp_avg_sq[base + (int64_t)((r & 3) + 8 * (r >> 2)) * K];
+      for (int r = 0; r < 16; ++r) vv[r] = p.exp_avg_sq[base + (int64_t)rw_mfma32_row(r) * K];
     }
     float g[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) g[r] = p.w_scale * acc[b][r] - c2v[r] * wv[r] * sig2;
     if (!adam) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) p.grad[base + (int64_t)((r & 3) + 8 * (r >> 2)) * K] = g[r];
+      for (int r = 0; r < 16; ++r) p.grad[base + (int64_t)rw_mfma32_row(r) * K] = g[r];
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         adam_update(g[r], wv[r], mv[r], vv[r], p.one_minus_beta1, p.beta2, p.one_minus_beta2, p.eps, step_size, bc2s);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t idx = base + (int64_t)((r & 3) + 8 * (r >> 2)) * K;
+        const int64_t idx = base + (int64_t)rw_mfma32_row(r) * K;
         p.weight[idx] = wv[r]; p.exp_avg[idx] = mv[r]; p.exp_avg_sq[idx] = vv[r];
       }
     }
@@ -483,7 +484,6 @@ __global__ void __launch_bounds__(256) project_kernel(const float* __restrict__ 
   for (int r = 0; r < rank; ++r) {
     const float* d = ctx + (int64_t)r * in_ch;
     float part[SV_MAX_TAPS];
-    float lam_new = 0.f;
 #pragma unroll
     for (int t = 0; t < SV_MAX_TAPS; ++t) part[t] = 0.f;
     for (int i = tid; i < in_ch; i += 256) {
@@ -512,7 +512,6 @@ __global__ void __launch_bounds__(256) project_kernel(const float* __restrict__ 
       }
       __syncthreads();
     }
-    (void)lam_new;
     for (int i = tid; i < in_ch; i += 256) {
       const float dv = d[i];
       for (int t = 0; t < taps; ++t) prow[i * taps + t] += cosv[t] * dv;
@@ -579,9 +578,6 @@ extern "C" int rw_project_weight_f32(const float* w, const float* context, const
 // takes rw_solve_step_f32.
 // ---------------------------------------------------------------------------------------
 #define SVP_RMAX 8
-typedef float svp_f2 __attribute__((ext_vector_type(2)));
-typedef float svp_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned svp_u2 __attribute__((ext_vector_type(2)));
 
 template <int CTRL>
 __device__ __forceinline__ float svp_dpp(float v) {        // the DPP-selected lane's v (controls that read valid lanes)
@@ -604,14 +600,14 @@ __device__ __forceinline__ float svp_wave_sum63(float v) {
 }
 // v[l] + v[l ^ 16] and then + [l ^ 32]: the rows of 16 and the halves of the wave exchanged by the gfx950 swaps
 __device__ __forceinline__ float svp_rows_sum(float v) {
-  svp_u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  rw_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 // Four values per lane (a: position n, b: position n+1; [0], [1]: the two out-channels) summed over the wave; every
 // lane l returns the total of value (l & 3), numbered 2 * position + channel.
-__device__ __forceinline__ float svp_wave_sum4(svp_f2 a, svp_f2 b, bool odd, bool hi) {
+__device__ __forceinline__ float svp_wave_sum4(rw_f32x2 a, rw_f32x2 b, bool odd, bool hi) {
   const float k01 = odd ? a[1] : a[0], s01 = odd ? a[0] : a[1];
   const float k23 = odd ? b[1] : b[0], s23 = odd ? b[0] : b[1];
   const float v01 = k01 + svp_dpp<0xB1>(s01);              // quad_perm [1,0,3,2]: even lanes hold channel 0, odd 1
@@ -629,6 +625,123 @@ __host__ __device__ static inline int svp_pair_row(int h, int w) { return (2 * s
 __host__ __device__ static inline int svp_part_floats(int nw, int h, int w) {
   const int a = nw * svp_pair_row(h, w), b = nw * 18 * SVP_RMAX;     // wave partials; aliased by the projection's
   return a > b ? a : b;
+}
+
+// The LDS prologue behind the zeroing of gds, vals and nz (whose pad positions stay 0) and a barrier: nmap, the targets of
+// out-channels o0, o0 + 1 and the noise term at the crop's positions
+__device__ __forceinline__ void svp_fill_maps(const rw_solve_problem& p, int o0, int* nmap, float* vals, float* nz,
+                                              bool plain, int tid, int nth) {
+  const int P = p.h * p.w, WP = p.w + 1;
+  for (int q = tid; q < P; q += nth) {
+    const int y = q / p.w, n = y * WP + (q - y * p.w);
+    nmap[q] = n;
+    vals[2 * n] = p.val[(int64_t)o0 * P + q];
+    vals[2 * n + 1] = p.val[(int64_t)(o0 + 1) * P + q];
+    if (!plain) nz[n] = p.noise_w[0] * p.noise[q];
+  }
+}
+
+// What the helpers of the two one-launch kernels work on: the LDS arrays both lay out (behind the resident kernel's key
+// crops) and the scalars of the shape, gathered once per kernel.
+struct svp_ctx {
+  float* part;      // [NW][PA]      per-wave conv sums (n, o); the projection's scratch
+  float* gds;       // [PA]          g_pre * demod at (n, o); 0 at pad positions
+  float* vals;      // [PA]          the target values at (n, o)
+  float* nz;        // [PA]          noise_w * noise at n
+  float* wq;        // [NW][2]       demodulation partials
+  float* chn;       // [2][4]        c2 per out-channel
+  int* nmap;        // [P]           position index n of crop element q
+  float* red;       // = part
+  int P, PA;        // crop elements; floats per (position, channel)-interleaved row
+  int NW;           // waves = in_ch / 64
+  int lane, wave;
+  float s, inv_numel, bias0, bias1;
+  bool plain;
+};
+
+// ---- B: wave o finishes out-channel o0 + o (a 64-channel layer has one wave: it takes both): demodulation factor from the
+// waves' partials, the loss step at every crop element, gd -> LDS, c2 and the channel's part of the loss of iteration it
+__device__ __forceinline__ void svp_phase_b(const svp_ctx& c, int out_ch, int o0, int it, float* lpart_all) {
+  for (int o = c.wave; o < 2; o += c.NW) {
+    float wsq = 0.f;
+    for (int w2 = 0; w2 < c.NW; ++w2) wsq += c.wq[w2 * 2 + o];
+    const float demod = rsqrtf(wsq + 1e-8f);
+    const float bv = o ? c.bias1 : c.bias0;
+    float lsum = 0.f, tsum = 0.f;
+    for (int q = c.lane; q < c.P; q += 64) {
+      const int n2 = 2 * c.nmap[q] + o;
+      float conv = 0.f;
+      for (int w2 = 0; w2 < c.NW; ++w2) conv += c.part[w2 * c.PA + n2];
+      conv *= c.s;
+      float g_pre;
+      lsum += sv_l1_step(conv, demod, [&] { return c.nz[n2 >> 1]; }, bv, c.vals[n2], c.inv_numel, c.plain, g_pre);
+      c.gds[n2] = g_pre * demod;
+      tsum += g_pre * conv;
+    }
+    lsum = svp_wave_sum63(lsum);
+    tsum = svp_wave_sum63(tsum);
+    if (c.lane == 63) {
+      c.chn[o * 4] = c.s * c.s * demod * demod * demod * tsum;
+      lpart_all[(int64_t)it * out_ch + o0 + o] = lsum * c.inv_numel;
+    }
+  }
+}
+
+// sums over the workgroup's channels of x[t][o] d_r (weighted: of x[t][o] sig2 d_r), d_r = dctx[r] of this thread's channel:
+// red[(wave * RMAX + r) * 18 + 2 t + o]; one barrier to publish
+__device__ __forceinline__ void svp_reduce_rows(const svp_ctx& c, const rw_solve_problem& p, const rw_f32x2 (&x)[9],
+                                                const float (&dctx)[SVP_RMAX], bool weighted, float sig2) {
+  for (int r = 0; r < p.rank; ++r) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int o = 0; o < 2; ++o) {
+        const float sum = svp_wave_sum63(x[t][o] * (weighted ? dctx[r] * sig2 : dctx[r]));
+        if (c.lane == 63) c.red[(c.wave * SVP_RMAX + r) * 18 + 2 * t + o] = sum;
+      }
+  }
+  __syncthreads();
+}
+// x[t][o] <- sum_r (sum_i x[t][o][i] d[r][i]) d[r][i] over the workgroup's channels; two barriers
+__device__ __forceinline__ void svp_project_rows(const svp_ctx& c, const rw_solve_problem& p, rw_f32x2 (&x)[9],
+                                                 const float (&dctx)[SVP_RMAX]) {
+  svp_reduce_rows(c, p, x, dctx, false, 0.f);
+  rw_f32x2 out[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) out[t] = rw_f32x2{0.f, 0.f};
+  for (int r = 0; r < p.rank; ++r) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      rw_f32x2 sum = {0.f, 0.f};
+      for (int w2 = 0; w2 < c.NW; ++w2) sum += *reinterpret_cast<const rw_f32x2*>(c.red + (w2 * SVP_RMAX + r) * 18 + 2 * t);
+      out[t] += sum * dctx[r];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 9; ++t) x[t] = out[t];
+  __syncthreads();
+}
+
+// One kernel row ky of a position pair: the two positions share their key reads -- four adjacent values k0 .. k3 of the
+// padded row feed six packed FMAs (v_pk_fma_f32: both out-channels in one instruction).  Forward: a, b = the sums at
+// positions n, n + 1; gradient: ga, gb = gd at the two positions, G[tap] = the weight gradient.
+__device__ __forceinline__ void svp_fwd_taps(const rw_f32x2 (&W)[9], int ky, float k0, float k1, float k2, float k3,
+                                             rw_f32x2& a, rw_f32x2& b) {
+  a = __builtin_elementwise_fma(W[3 * ky], rw_f32x2{k0, k0}, a);
+  b = __builtin_elementwise_fma(W[3 * ky], rw_f32x2{k1, k1}, b);
+  a = __builtin_elementwise_fma(W[3 * ky + 1], rw_f32x2{k1, k1}, a);
+  b = __builtin_elementwise_fma(W[3 * ky + 1], rw_f32x2{k2, k2}, b);
+  a = __builtin_elementwise_fma(W[3 * ky + 2], rw_f32x2{k2, k2}, a);
+  b = __builtin_elementwise_fma(W[3 * ky + 2], rw_f32x2{k3, k3}, b);
+}
+__device__ __forceinline__ void svp_grad_taps(rw_f32x2 (&G)[9], int ky, float k0, float k1, float k2, float k3,
+                                              rw_f32x2 ga, rw_f32x2 gb) {
+  G[3 * ky] = __builtin_elementwise_fma(ga, rw_f32x2{k0, k0}, G[3 * ky]);
+  G[3 * ky] = __builtin_elementwise_fma(gb, rw_f32x2{k1, k1}, G[3 * ky]);
+  G[3 * ky + 1] = __builtin_elementwise_fma(ga, rw_f32x2{k1, k1}, G[3 * ky + 1]);
+  G[3 * ky + 1] = __builtin_elementwise_fma(gb, rw_f32x2{k2, k2}, G[3 * ky + 1]);
+  G[3 * ky + 2] = __builtin_elementwise_fma(ga, rw_f32x2{k2, k2}, G[3 * ky + 2]);
+  G[3 * ky + 2] = __builtin_elementwise_fma(gb, rw_f32x2{k3, k3}, G[3 * ky + 2]);
 }
 
 __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_problem p, int it0, int it1, int niter,
@@ -662,14 +775,8 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
     const int c = e / P, q = e - c * P, y = q / p.w, x = q - y * p.w;
     Ks[c * PS + (y + 1) * WP + x + 1] = p.key[e];
   }
-  for (int q = tid; q < P; q += nth) {
-    const int y = q / p.w, n = y * WP + (q - y * p.w);
-    nmap[q] = n;
-    vals[2 * n] = p.val[(int64_t)o0 * P + q];
-    vals[2 * n + 1] = p.val[(int64_t)(o0 + 1) * P + q];
-    if (!plain) nz[n] = p.noise_w[0] * p.noise[q];
-  }
-  svp_f2 W[9], M[9], V[9], Or[9];                   // [tap]{out-channel o0, o0 + 1}
+  svp_fill_maps(p, o0, nmap, vals, nz, plain, tid, nth);
+  rw_f32x2 W[9], M[9], V[9], Or[9];                   // [tap]{out-channel o0, o0 + 1}
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -685,35 +792,8 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
   const float inv_numel = 1.0f / ((float)p.out_ch * (float)P);
   const float* kb = Ks + i * PS;
   const float bias0 = plain ? 0.f : p.bias[o0], bias1 = plain ? 0.f : p.bias[o0 + 1];
+  const svp_ctx c = {part, gds, vals, nz, wq, chn, nmap, red, P, PA, NW, lane, wave, s, inv_numel, bias0, bias1, plain};
   __syncthreads();
-
-  // x[t][o] <- sum_r (sum_i x[t][o][i] d[r][i]) d[r][i] over the workgroup's channels; two barriers
-  auto project_rows = [&](svp_f2 (&x)[9]) __attribute__((always_inline)) {
-    for (int r = 0; r < p.rank; ++r) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-          const float sum = svp_wave_sum63(x[t][o] * dctx[r]);
-          if (lane == 63) red[(wave * SVP_RMAX + r) * 18 + 2 * t + o] = sum;
-        }
-    }
-    __syncthreads();
-    svp_f2 out[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) out[t] = svp_f2{0.f, 0.f};
-    for (int r = 0; r < p.rank; ++r) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        svp_f2 c = {0.f, 0.f};
-        for (int w2 = 0; w2 < NW; ++w2) c += *reinterpret_cast<const svp_f2*>(red + (w2 * SVP_RMAX + r) * 18 + 2 * t);
-        out[t] += c * dctx[r];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) x[t] = out[t];
-    __syncthreads();
-  };
 
   float ss_next = p.step_size[it0 < it1 ? it0 : 0], bc_next = p.bc2_sqrt[it0 < it1 ? it0 : 0];
   for (int it = it0; it < it1; ++it) {
@@ -722,16 +802,16 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
     if (it + 1 < it1) { ss_next = p.step_size[it + 1]; bc_next = p.bc2_sqrt[it + 1]; }
     // ---- A: partial convolution of my channel, the demodulation partial
     {
-      svp_f2 wq2 = {0.f, 0.f};
+      rw_f32x2 wq2 = {0.f, 0.f};
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
-        const svp_f2 a = (s * W[t]) * sg;
+        const rw_f32x2 a = (s * W[t]) * sg;
         wq2 += a * a;
       }
       const float wq0 = svp_wave_sum63(wq2[0]), wq1 = svp_wave_sum63(wq2[1]);
       if (lane == 63) { wq[wave * 2] = wq0; wq[wave * 2 + 1] = wq1; }
       for (int n = 0; n < NP; n += 2) {
-        svp_f2 a = {0.f, 0.f}, b = {0.f, 0.f};
+        rw_f32x2 a = {0.f, 0.f}, b = {0.f, 0.f};
         float kk[3][4];                                       // all twelve reads in flight before the first FMA
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -740,62 +820,22 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
           for (int c = 0; c < 4; ++c) kk[ky][c] = r[c];
         }
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const float k0 = kk[ky][0], k1 = kk[ky][1], k2 = kk[ky][2], k3 = kk[ky][3];
-          a = __builtin_elementwise_fma(W[3 * ky], svp_f2{k0, k0}, a);
-          b = __builtin_elementwise_fma(W[3 * ky], svp_f2{k1, k1}, b);
-          a = __builtin_elementwise_fma(W[3 * ky + 1], svp_f2{k1, k1}, a);
-          b = __builtin_elementwise_fma(W[3 * ky + 1], svp_f2{k2, k2}, b);
-          a = __builtin_elementwise_fma(W[3 * ky + 2], svp_f2{k2, k2}, a);
-          b = __builtin_elementwise_fma(W[3 * ky + 2], svp_f2{k3, k3}, b);
-        }
+        for (int ky = 0; ky < 3; ++ky) svp_fwd_taps(W, ky, kk[ky][0], kk[ky][1], kk[ky][2], kk[ky][3], a, b);
         const float v = svp_wave_sum4(a, b, odd, hi);
         if (lane < 4) part[wave * PA + 2 * n + lane] = v;
       }
     }
     __syncthreads();
-    // ---- B: wave o finishes out-channel o0 + o
-    for (int o = wave; o < 2; o += NW) {            // (a 64-channel layer has one wave: it takes both)
-      float wsq = 0.f;
-      for (int w2 = 0; w2 < NW; ++w2) wsq += wq[w2 * 2 + o];
-      const float demod = rsqrtf(wsq + 1e-8f);
-      const float bv = o ? bias1 : bias0;
-      float lsum = 0.f, tsum = 0.f;
-      for (int q = lane; q < P; q += 64) {
-        const int n2 = 2 * nmap[q] + o;
-        float conv = 0.f;
-        for (int w2 = 0; w2 < NW; ++w2) conv += part[w2 * PA + n2];
-        conv *= s;
-        float out, pre;
-        if (plain) { pre = conv * demod; out = pre; }
-        else {
-          pre = conv * demod + nz[n2 >> 1] + bv;
-          out = 1.4142135623730951f * ((pre > 0.f) ? pre : 0.2f * pre);
-        }
-        const float diff = out - vals[n2];
-        lsum += fabsf(diff);
-        const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-        const float g_out = sgn * inv_numel;
-        const float g_pre = plain ? g_out : ((pre > 0.f) ? g_out : g_out * 0.2f) * 1.4142135623730951f;
-        gds[n2] = g_pre * demod;
-        tsum += g_pre * conv;
-      }
-      lsum = svp_wave_sum63(lsum);
-      tsum = svp_wave_sum63(tsum);
-      if (lane == 63) {
-        chn[o * 4] = s * s * demod * demod * demod * tsum;
-        lpart_all[(int64_t)it * p.out_ch + o0 + o] = lsum * inv_numel;
-      }
-    }
+    svp_phase_b(c, p.out_ch, o0, it, lpart_all);
     __syncthreads();
     // ---- C: gradient of my 18 weights, Adam, projections
     {
-      svp_f2 G[9];
+      rw_f32x2 G[9];
 #pragma unroll
-      for (int t = 0; t < 9; ++t) G[t] = svp_f2{0.f, 0.f};
+      for (int t = 0; t < 9; ++t) G[t] = rw_f32x2{0.f, 0.f};
       for (int n = 0; n < NP; n += 2) {
-        const svp_f4 gq = *reinterpret_cast<const svp_f4*>(gds + 2 * n);      // (n, o0) (n, o1) (n+1, o0) (n+1, o1)
-        const svp_f2 ga = {gq[0], gq[1]}, gb = {gq[2], gq[3]};
+        const rw_f32x4 gq = *reinterpret_cast<const rw_f32x4*>(gds + 2 * n);      // (n, o0) (n, o1) (n+1, o0) (n+1, o1)
+        const rw_f32x2 ga = {gq[0], gq[1]}, gb = {gq[2], gq[3]};
         float kk[3][4];
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -804,20 +844,12 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
           for (int c = 0; c < 4; ++c) kk[ky][c] = r[c];
         }
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const float k0 = kk[ky][0], k1 = kk[ky][1], k2 = kk[ky][2], k3 = kk[ky][3];
-          G[3 * ky] = __builtin_elementwise_fma(ga, svp_f2{k0, k0}, G[3 * ky]);
-          G[3 * ky] = __builtin_elementwise_fma(gb, svp_f2{k1, k1}, G[3 * ky]);
-          G[3 * ky + 1] = __builtin_elementwise_fma(ga, svp_f2{k1, k1}, G[3 * ky + 1]);
-          G[3 * ky + 1] = __builtin_elementwise_fma(gb, svp_f2{k2, k2}, G[3 * ky + 1]);
-          G[3 * ky + 2] = __builtin_elementwise_fma(ga, svp_f2{k2, k2}, G[3 * ky + 2]);
-          G[3 * ky + 2] = __builtin_elementwise_fma(gb, svp_f2{k3, k3}, G[3 * ky + 2]);
-        }
+        for (int ky = 0; ky < 3; ++ky) svp_grad_taps(G, ky, kk[ky][0], kk[ky][1], kk[ky][2], kk[ky][3], ga, gb);
       }
-      const svp_f2 c2 = {chn[0], chn[4]};
+      const rw_f32x2 c2 = {chn[0], chn[4]};
 #pragma unroll
       for (int t = 0; t < 9; ++t) G[t] = s * G[t] - c2 * W[t] * sig2;
-      if (p.low_rank_gradient) project_rows(G);
+      if (p.low_rank_gradient) svp_project_rows(c, p, G, dctx);
 #pragma unroll
       for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -827,10 +859,10 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
           W[t][o] = wv; M[t][o] = mv; V[t][o] = vv;
         }
       if (low_rank_insert && (it % piter == 0 || it == niter - 1)) {
-        svp_f2 pw[9];
+        rw_f32x2 pw[9];
 #pragma unroll
         for (int t = 0; t < 9; ++t) pw[t] = W[t];
-        project_rows(pw);
+        svp_project_rows(c, p, pw, dctx);
 #pragma unroll
         for (int t = 0; t < 9; ++t) W[t] = Or[t] + pw[t];
       }
@@ -858,7 +890,11 @@ __global__ void __launch_bounds__(512) solve_persistent_kernel(const rw_solve_pr
 //   P(dW)[o][i][t] = sum_r (s sum_n g[o][n] kd_r[n + t] - c2[o] sum_j W[o][j][t] sig2[j] d_r[j]) d_r[i],
 //   kd_r[e] = sum_i d_r[i] key[i][e]   (a one-channel map per context row, computed once per launch),
 // i.e. 18 correlations of 256 positions per context row instead of 2.4 M multiply-adds per out-channel pair.
-// Everything else -- phase B, Adam, the projections, the per-channel loss parts -- is the resident kernel's.
+// Everything else -- phase B, the projections, the tap blocks, the LDS prologue -- is the resident kernel's, through the
+// svp_* helpers above it.  (Written out in both kernels, because a shared form changed their code generation: the
+// demodulation partial and the Adam sweep with the write-back -- with either, the resident kernel compiles to 3911
+// instructions instead of 4012, on other registers; the four-row rotation below, twice -- as one for_each_row(row_fn) this
+// kernel takes 236 vector registers instead of 243.)
 // Limits: as solve_persistent_kernel but w <= 16 and the (small) LDS footprint below instead of the crop's.
 // ---------------------------------------------------------------------------------------
 #define SVS_WP_MAX 17
@@ -906,29 +942,23 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
 
   for (int e = tid; e < 3 * PA; e += nth) gds[e] = 0.f;       // gds, vals, nz
   __syncthreads();
-  for (int q = tid; q < P; q += nth) {
-    const int y = q / p.w, n = y * WP + (q - y * p.w);
-    nmap[q] = n;
-    vals[2 * n] = p.val[(int64_t)o0 * P + q];
-    vals[2 * n + 1] = p.val[(int64_t)(o0 + 1) * P + q];
-    if (!plain) nz[n] = p.noise_w[0] * p.noise[q];
-  }
+  svp_fill_maps(p, o0, nmap, vals, nz, plain, tid, nth);
   if (lrg) {
     // kd_r[e] = sum_j d_r[j] key[j][e]: thread e walks the channels of its position (consecutive floats of keyT)
     for (int e = tid; e < PS; e += nth) {
-      const svp_f4* row = reinterpret_cast<const svp_f4*>(keyT + (int64_t)e * p.in_ch);
+      const rw_f32x4* row = reinterpret_cast<const rw_f32x4*>(keyT + (int64_t)e * p.in_ch);
       for (int r = 0; r < p.rank; ++r) {
-        const svp_f4* d4 = reinterpret_cast<const svp_f4*>(p.context + (int64_t)r * p.in_ch);
+        const rw_f32x4* d4 = reinterpret_cast<const rw_f32x4*>(p.context + (int64_t)r * p.in_ch);
         float acc = 0.f;
         for (int j = 0; j < p.in_ch / 4; ++j) {
-          const svp_f4 kv = row[j], dv = d4[j];
+          const rw_f32x4 kv = row[j], dv = d4[j];
           acc += kv[0] * dv[0] + kv[1] * dv[1] + kv[2] * dv[2] + kv[3] * dv[3];
         }
         kd[r * PS + e] = acc;
       }
     }
   }
-  svp_f2 W[9];
+  rw_f32x2 W[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -944,38 +974,9 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
   const float sg = p.style[i], sig2 = sg * sg, s = p.w_scale;
   const float inv_numel = 1.0f / ((float)p.out_ch * (float)P);
   const float bias0 = plain ? 0.f : p.bias[o0], bias1 = plain ? 0.f : p.bias[o0 + 1];
+  const svp_ctx c = {part, gds, vals, nz, wq, chn, nmap, red, P, PA, NW, lane, wave, s, inv_numel, bias0, bias1, plain};
   __syncthreads();
 
-  // sums over the workgroup's channels of x[t][o] d_r: red[(wave * RMAX + r) * 18 + 2 t + o] (one barrier to publish)
-  auto reduce_rows = [&](const svp_f2 (&x)[9], bool weighted) __attribute__((always_inline)) {
-    for (int r = 0; r < p.rank; ++r) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-          const float sum = svp_wave_sum63(x[t][o] * (weighted ? dctx[r] * sig2 : dctx[r]));
-          if (lane == 63) red[(wave * SVP_RMAX + r) * 18 + 2 * t + o] = sum;
-        }
-    }
-    __syncthreads();
-  };
-  auto project_rows = [&](svp_f2 (&x)[9]) __attribute__((always_inline)) {
-    reduce_rows(x, false);
-    svp_f2 out[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) out[t] = svp_f2{0.f, 0.f};
-    for (int r = 0; r < p.rank; ++r) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        svp_f2 c = {0.f, 0.f};
-        for (int w2 = 0; w2 < NW; ++w2) c += *reinterpret_cast<const svp_f2*>(red + (w2 * SVP_RMAX + r) * 18 + 2 * t);
-        out[t] += c * dctx[r];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) x[t] = out[t];
-    __syncthreads();
-  };
   // padded row r of this thread's channel -> registers (entries beyond the row / the crop's padded extent are 0)
   // (buffer loads: one vector register of lane offsets and a scalar offset per element -- twenty 64-bit vector
   // addresses per row spilled the kernel --, and an element past the copy's end reads 0 by the range check)
@@ -995,10 +996,10 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
     if (it + 1 < it1) { ss_next = p.step_size[it + 1]; bc_next = p.bc2_sqrt[it + 1]; }
     // ---- A: partial convolution of my channel (rows streamed), the demodulation partial
     {
-      svp_f2 wq2 = {0.f, 0.f};
+      rw_f32x2 wq2 = {0.f, 0.f};
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
-        const svp_f2 a = (s * W[t]) * sg;
+        const rw_f32x2 a = (s * W[t]) * sg;
         wq2 += a * a;
       }
       const float wq0 = svp_wave_sum63(wq2[0]), wq1 = svp_wave_sum63(wq2[1]);
@@ -1008,17 +1009,11 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
 #pragma unroll
         for (int x = 0; x < SVS_WP_MAX; x += 2) {
           if (x < WP) {
-            svp_f2 a = {0.f, 0.f}, b = {0.f, 0.f};
+            rw_f32x2 a = {0.f, 0.f}, b = {0.f, 0.f};
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
               const float (&R)[SVS_ROW] = ky == 0 ? R0 : (ky == 1 ? R1 : R2);
-              const float k0 = R[x], k1 = R[x + 1], k2 = R[x + 2], k3 = R[x + 3];
-              a = __builtin_elementwise_fma(W[3 * ky], svp_f2{k0, k0}, a);
-              b = __builtin_elementwise_fma(W[3 * ky], svp_f2{k1, k1}, b);
-              a = __builtin_elementwise_fma(W[3 * ky + 1], svp_f2{k1, k1}, a);
-              b = __builtin_elementwise_fma(W[3 * ky + 1], svp_f2{k2, k2}, b);
-              a = __builtin_elementwise_fma(W[3 * ky + 2], svp_f2{k2, k2}, a);
-              b = __builtin_elementwise_fma(W[3 * ky + 2], svp_f2{k3, k3}, b);
+              svp_fwd_taps(W, ky, R[x], R[x + 1], R[x + 2], R[x + 3], a, b);
             }
             const float v = svp_wave_sum4(a, b, odd, hi);
             const int n2 = 2 * (y * WP + x) + lane;
@@ -1037,89 +1032,51 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
       }
     }
     __syncthreads();
-    // ---- B: wave o finishes out-channel o0 + o
-    for (int o = wave; o < 2; o += NW) {
-      float wsq = 0.f;
-      for (int w2 = 0; w2 < NW; ++w2) wsq += wq[w2 * 2 + o];
-      const float demod = rsqrtf(wsq + 1e-8f);
-      const float bv = o ? bias1 : bias0;
-      float lsum = 0.f, tsum = 0.f;
-      for (int q = lane; q < P; q += 64) {
-        const int n2 = 2 * nmap[q] + o;
-        float conv = 0.f;
-        for (int w2 = 0; w2 < NW; ++w2) conv += part[w2 * PA + n2];
-        conv *= s;
-        float out, pre;
-        if (plain) { pre = conv * demod; out = pre; }
-        else {
-          pre = conv * demod + nz[n2 >> 1] + bv;
-          out = 1.4142135623730951f * ((pre > 0.f) ? pre : 0.2f * pre);
-        }
-        const float diff = out - vals[n2];
-        lsum += fabsf(diff);
-        const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-        const float g_out = sgn * inv_numel;
-        const float g_pre = plain ? g_out : ((pre > 0.f) ? g_out : g_out * 0.2f) * 1.4142135623730951f;
-        gds[n2] = g_pre * demod;
-        tsum += g_pre * conv;
-      }
-      lsum = svp_wave_sum63(lsum);
-      tsum = svp_wave_sum63(tsum);
-      if (lane == 63) {
-        chn[o * 4] = s * s * demod * demod * demod * tsum;
-        lpart_all[(int64_t)it * p.out_ch + o0 + o] = lsum * inv_numel;
-      }
-    }
+    svp_phase_b(c, p.out_ch, o0, it, lpart_all);
     __syncthreads();
     // ---- C: gradient of my 18 weights, Adam, projections
     {
-      svp_f2 G[9];
-      const svp_f2 c2 = {chn[0], chn[4]};
+      rw_f32x2 G[9];
+      const rw_f32x2 c2 = {chn[0], chn[4]};
       if (lrg) {
         // s * sum_n g[n][o] kd_r[n + tap]: wave w takes the (context row, tap) pairs w, w + NW, ...
         for (int idx = wave; idx < p.rank * 9; idx += NW) {
           const int r = idx / 9, t = idx - 9 * r;
           const float* kr = kd + r * PS + (t / 3) * WP + (t % 3);
-          svp_f2 acc = {0.f, 0.f};
-          for (int n = lane; n < NP; n += 64) acc += *reinterpret_cast<const svp_f2*>(gds + 2 * n) * kr[n];
+          rw_f32x2 acc = {0.f, 0.f};
+          for (int n = lane; n < NP; n += 64) acc += *reinterpret_cast<const rw_f32x2*>(gds + 2 * n) * kr[n];
           const float a0 = svp_wave_sum63(acc[0]), a1 = svp_wave_sum63(acc[1]);
           if (lane == 63) { cgs[r * 18 + 2 * t] = s * a0; cgs[r * 18 + 2 * t + 1] = s * a1; }
         }
-        reduce_rows(W, true);                       // sum_j W[t][o][j] sig2[j] d_r[j] (publishes cgs too)
+        svp_reduce_rows(c, p, W, dctx, true, sig2);       // sum_j W[t][o][j] sig2[j] d_r[j] (publishes cgs too)
 #pragma unroll
-        for (int t = 0; t < 9; ++t) G[t] = svp_f2{0.f, 0.f};
+        for (int t = 0; t < 9; ++t) G[t] = rw_f32x2{0.f, 0.f};
         for (int r = 0; r < p.rank; ++r) {
 #pragma unroll
           for (int t = 0; t < 9; ++t) {
-            svp_f2 wsd = {0.f, 0.f};
-            for (int w2 = 0; w2 < NW; ++w2) wsd += *reinterpret_cast<const svp_f2*>(red + (w2 * SVP_RMAX + r) * 18 + 2 * t);
-            const svp_f2 cg = *reinterpret_cast<const svp_f2*>(cgs + r * 18 + 2 * t);
+            rw_f32x2 wsd = {0.f, 0.f};
+            for (int w2 = 0; w2 < NW; ++w2) wsd += *reinterpret_cast<const rw_f32x2*>(red + (w2 * SVP_RMAX + r) * 18 + 2 * t);
+            const rw_f32x2 cg = *reinterpret_cast<const rw_f32x2*>(cgs + r * 18 + 2 * t);
             G[t] += (cg - c2 * wsd) * dctx[r];
           }
         }
         __syncthreads();                            // red (= part) and cgs are free again
       } else {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) G[t] = svp_f2{0.f, 0.f};
+        for (int t = 0; t < 9; ++t) G[t] = rw_f32x2{0.f, 0.f};
         auto grad_row = [&](int y, const float (&R0)[SVS_ROW], const float (&R1)[SVS_ROW], const float (&R2)[SVS_ROW])
             __attribute__((always_inline)) {
 #pragma unroll
           for (int x = 0; x < SVS_WP_MAX; x += 2) {
             if (x < WP) {
               const int n = y * WP + x;
-              const svp_f2 ga = *reinterpret_cast<const svp_f2*>(gds + 2 * n);
+              const rw_f32x2 ga = *reinterpret_cast<const rw_f32x2*>(gds + 2 * n);
               // the second position of a row's last pair belongs to the next row (its first pair counts it)
-              const svp_f2 gb = (x + 1 < WP && n + 1 < NP) ? *reinterpret_cast<const svp_f2*>(gds + 2 * n + 2) : svp_f2{0.f, 0.f};
+              const rw_f32x2 gb = (x + 1 < WP && n + 1 < NP) ? *reinterpret_cast<const rw_f32x2*>(gds + 2 * n + 2) : rw_f32x2{0.f, 0.f};
 #pragma unroll
               for (int ky = 0; ky < 3; ++ky) {
                 const float (&R)[SVS_ROW] = ky == 0 ? R0 : (ky == 1 ? R1 : R2);
-                const float k0 = R[x], k1 = R[x + 1], k2 = R[x + 2], k3 = R[x + 3];
-                G[3 * ky] = __builtin_elementwise_fma(ga, svp_f2{k0, k0}, G[3 * ky]);
-                G[3 * ky] = __builtin_elementwise_fma(gb, svp_f2{k1, k1}, G[3 * ky]);
-                G[3 * ky + 1] = __builtin_elementwise_fma(ga, svp_f2{k1, k1}, G[3 * ky + 1]);
-                G[3 * ky + 1] = __builtin_elementwise_fma(gb, svp_f2{k2, k2}, G[3 * ky + 1]);
-                G[3 * ky + 2] = __builtin_elementwise_fma(ga, svp_f2{k2, k2}, G[3 * ky + 2]);
-                G[3 * ky + 2] = __builtin_elementwise_fma(gb, svp_f2{k3, k3}, G[3 * ky + 2]);
+                svp_grad_taps(G, ky, R[x], R[x + 1], R[x + 2], R[x + 3], ga, gb);
               }
             }
           }
@@ -1135,7 +1092,7 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
         }
 #pragma unroll
         for (int t = 0; t < 9; ++t) G[t] = s * G[t] - c2 * W[t] * sig2;
-        if (p.low_rank_gradient) project_rows(G);
+        if (p.low_rank_gradient) svp_project_rows(c, p, G, dctx);
       }
 #pragma unroll
       for (int t = 0; t < 9; ++t)
@@ -1146,13 +1103,13 @@ __global__ void __launch_bounds__(512) solve_stream_kernel(const rw_solve_proble
           W[t][o] = wv; mv[(2 * t + o) * nth] = mm; mv[(18 + 2 * t + o) * nth] = vv;
         }
       if (low_rank_insert && (it % piter == 0 || it == niter - 1)) {
-        svp_f2 pw[9];
+        rw_f32x2 pw[9];
 #pragma unroll
         for (int t = 0; t < 9; ++t) pw[t] = W[t];
-        project_rows(pw);
+        svp_project_rows(c, p, pw, dctx);
 #pragma unroll
         for (int t = 0; t < 9; ++t)          // ortho part: read where it is used (every piter-th iteration)
-          W[t] = svp_f2{p.ortho[(int64_t)o0 * K + i * 9 + t], p.ortho[(int64_t)(o0 + 1) * K + i * 9 + t]} + pw[t];
+          W[t] = rw_f32x2{p.ortho[(int64_t)o0 * K + i * 9 + t], p.ortho[(int64_t)(o0 + 1) * K + i * 9 + t]} + pw[t];
       }
     }
   }
@@ -1285,7 +1242,7 @@ extern "C" int rw_solve_supported(int out_ch, int in_ch, int h, int w, int upsam
 // convolution writes (h*w, or (2h+1)(2w+1) for an upsampling target); c2 carries the per-channel loss behind it.
 extern "C" int rw_solve_scratch_elems(int out_ch, int in_ch, int h, int w, int upsample, long long* sizes) {
   if (!sizes || out_ch <= 0 || in_ch <= 0 || h <= 0 || w <= 0) return RW_ERR_BAD_ARGUMENT;
-  const int ch = upsample ? 2 * h + 1 : h, cw = upsample ? 2 * w + 1 : w;
+  const int ch = rw_conv_extent(upsample, h), cw = rw_conv_extent(upsample, w);
   const long long pp = sv_pp(ch * cw);
   const long long ks = rw_solve_ksplit(out_ch, in_ch, ch, cw);
   sizes[0] = ks * out_ch * pp;
@@ -1317,7 +1274,7 @@ extern "C" int rw_solve_step_f32(const rw_solve_problem* pr, int project, rw_str
     if (rc) return rc;
   }
   hipStream_t s = rw_s(stream);
-  const int P = sv_conv_h(p) * sv_conv_w(p);
+  const int P = rw_conv_extent(p.upsample, p.h) * rw_conv_extent(p.upsample, p.w);
   const int pp = sv_pp(P);
   float* lpart = p.c2 + p.out_ch;   // c2 is allocated with 2*out_ch floats: [c2 | per-channel loss]
   hipLaunchKernelGGL(solve_fwd_kernel, dim3(p.out_ch / SV_BM, pp / SV_BN, p.ksplit), dim3(256), 0, s, p, pp);

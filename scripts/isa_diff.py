@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Does the working tree generate the device code that <rev> generated?
 
-    scripts/isa_diff.py [--keep DIR] <rev> [rewriting_amd/csrc/rw_x.hip ...]      (default: every .hip of rewriting_amd/csrc)
+    scripts/isa_diff.py [--keep DIR] [--ops] <rev> [rewriting_amd/csrc/rw_x.hip ...]      (default: every .hip of rewriting_amd/csrc)
 
 The sources of <rev> (git show <rev>:path) go into a temporary directory; both sides are compiled to gfx950 assembly
 with the library's own flags (csrc/build.sh, the file's "// hipcc-flags:" line, + --cuda-device-only -S), at most 16
@@ -9,6 +9,9 @@ compilations at a time.  The listings are split at the function symbols and comp
 instruction text and the .amdhsa_* resource block (registers, scratch, LDS).  The lines that name the compilation
 unit's __hip_cuid_ symbol are dropped -- they differ between two builds of unchanged code.  Per kernel one line,
 "same", or "differs" with both instruction counts and both resource blocks; exit status 1 if anything differs.
+--ops adds, per differing kernel, the arithmetic mnemonics whose counts changed (ARITH below: floating-point VALU
+operations, conversions, selects, MFMAs, lane permutes -- integer address arithmetic, moves, waits and nops are not
+counted) or "arithmetic instructions: equal multiset": the same operations on other registers or in another order.
 Needs hipcc and git, no GPU.  A full run compiles every file twice and takes minutes.
 """
 import argparse
@@ -24,6 +27,9 @@ CSRC = "rewriting_amd/csrc"
 HEADERS = [CSRC + "/rw_common.h", "include/rewriting_hip.h"]
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result".split()
 NOPK = "-Xclang -target-feature -Xclang -packed-fp32-ops".split()
+# --ops: floating-point arithmetic (the _dpp forms included), conversions and selects; matrix instructions; lane permutes
+ARITH = re.compile(r"v_(pk_)?(add|sub|mul|fma|fmac|mac|mad|max|min|rsq|sqrt|rcp|div\w*)_\w*(f16|f32|f64)\w*$"
+                   r"|v_(cvt\w*|cndmask)\w*$|v_\w*mfma\w*$|v_permlane\w*$")
 
 
 def compile_asm(tree, rel, out):
@@ -84,6 +90,18 @@ def n_instructions(lines):
     return n
 
 
+def arith_counts(lines):
+    """{mnemonic: count} of the instructions ARITH matches"""
+    counts = {}
+    for line in lines:
+        s = line.split(";")[0].strip()
+        if s and not s.startswith(".") and not s.endswith(":"):
+            m = s.split()[0]
+            if ARITH.match(m):
+                counts[m] = counts.get(m, 0) + 1
+    return counts
+
+
 def show_resources(tag, block):
     keep = [l for l in block if re.search(r"vgpr|sgpr|private_segment_fixed|group_segment_fixed|accum_offset", l)]
     print("      %s: %s" % (tag, "  ".join(l.replace(".amdhsa_", "") for l in keep)))
@@ -93,6 +111,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("rev")
     ap.add_argument("files", nargs="*")
+    ap.add_argument("--ops", action="store_true", help="per differing kernel: the arithmetic mnemonics whose counts changed")
     ap.add_argument("--keep", metavar="DIR", help="keep both listings of every file in DIR (<file>.old.s, <file>.new.s)")
     args = ap.parse_args()
     files = [os.path.relpath(os.path.abspath(f), ROOT) for f in args.files]
@@ -135,6 +154,11 @@ def main():
                         name, n_instructions(a), n_instructions(b), "equal" if ra == rb else "DIFFERENT"))
                     show_resources(args.rev, ra)
                     show_resources("now", rb)
+                    if args.ops:
+                        ca, cb = arith_counts(a), arith_counts(b)
+                        changed = ["%s %d -> %d" % (m, ca.get(m, 0), cb.get(m, 0))
+                                   for m in sorted(set(ca) | set(cb)) if ca.get(m, 0) != cb.get(m, 0)]
+                        print("      arithmetic instructions: %s" % ("  ".join(changed) if changed else "equal multiset"))
                 if old_x != new_x:
                     differing += 1
                     print("  differs  (the listing outside the functions: data, metadata)")
