@@ -73,6 +73,24 @@ __host__ __device__ __forceinline__ constexpr int rw_mfma32_row(int r, int frow 
   return 4 * frow + (r & 3) + 8 * (r >> 2);
 }
 
+// leaky ReLU (slope 0.2) times sqrt 2: the activation behind every styled convolution's bias
+__device__ __forceinline__ float rw_lrelu_sqrt2(float v) { return ((v > 0.f) ? v : v * 0.2f) * 1.4142135623730951f; }
+
+// ---- halo staging of the direct fp32 convolutions (rw_conv.hip).  The XH x XUSED patch of input rows y0 - 1 .., columns
+// x0 - 1 .. lies in LDS at row pitch XW > XUSED; thread tid of 256 stages the positions pos = tid + 256 k, and the rule is
+// branch-free: a position outside the h x w image loads a legal address (offset 0) and multiplies by mask 0, a slot past
+// the patch does the same and writes the padding column XW - 1 of row 0, which no tap reads.
+__host__ __device__ __forceinline__ void rw_halo_slot_of(int pos, int y0, int x0, int h, int w, int XH, int XW, int XUSED,
+                                                         int& goff, float& mask, int& lds) {
+  const int NPOS = XH * XUSED;
+  const int r = pos / XUSED, c = pos - r * XUSED;
+  const int iy = y0 - 1 + r, ix = x0 - 1 + c;
+  const bool ok = pos < NPOS && iy >= 0 && iy < h && ix >= 0 && ix < w;
+  goff = ok ? iy * w + ix : 0;
+  mask = ok ? 1.0f : 0.0f;
+  lds = pos < NPOS ? r * XW + c : XW - 1;
+}
+
 // ---- the 3x3 convolution as a GEMM over gathered columns (the solver's K1 / K3 in rw_solve.hip, conv_wgrad_kernel in
 // rw_grad.hip).  Extent, along one axis of n input samples, of the map the convolution writes: n for the stride-1 layer,
 // 2n + 1 -- the pre-blur map -- for an upsampling layer (conv_transpose2d stride 2, utils/stylegan2/models.py:315-316).

@@ -16,6 +16,12 @@
 // The epilogue applies, in registers, the weight scale, the demodulation factor and -- for
 // stride-1 layers -- noise, bias and leaky-ReLU, so a styled-conv block reads its input once
 // and writes its output once.
+//
+// Steps more than one kernel takes are stated once: the work-item decodes (rw_batch_slot, rw_conv_pos; rw_tile_digits
+// over HaloTiles for the halo kernels), the halo staging (rw_halo_slot_of in rw_common.h, rw_halo_fetch), the noise batch
+// of the epilogues (rw_noise_batch), the C/D row map and the activation (rw_mfma32_row, rw_lrelu_sqrt2 in rw_common.h);
+// on the host the stride-1 problem, the tile choice and the HaloProblem fill (stride1_problem, halo_tile, fill_halo).
+// Where a site is still written out, a note there says what sharing it did to the kernel's registers.
 #include "rw_common.h"
 #include <string.h>
 
@@ -47,10 +53,46 @@ struct ConvBatch {
   ConvProblem p[4];
 };
 
+// Work item of a batched launch -> its problem (returned) and the item within that problem (work).
+__device__ __forceinline__ int rw_batch_slot(const ConvBatch& cb, int& work) {
+  int q = 0;
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (j < cb.n && work >= cb.work0[j]) q = j;
+  work -= cb.work0[q];
+  return q;
+}
+
+// Position r0 of an image's ph x pw position grid: its coordinates and the output pixel it writes.
+struct ConvPos { int yy, xx; int64_t pix; };
+__device__ __forceinline__ ConvPos rw_conv_pos(const ConvProblem& p, int r0) {
+  const int yq = r0 / p.pw;
+  const int yy = yq + p.yoff, xx = r0 - yq * p.pw + p.xoff;
+  return {yy, xx, (int64_t)(p.sy * yy + p.oy0) * p.ow + (p.sx * xx + p.ox0)};
+}
+
+// ---- the epilogues' fetches, each a batch behind ONE uniform branch: a load per store, each behind its own `if`, costs
+// an L2 round trip plus the drain of the previous store (vmcnt counts both) per element -- as long as the whole K loop
+// on the 32/64-channel layers.
+// The noise of TN_ positions, nz[b] = noise_w * noise[off(b)] (no noise: 0).  P = ConvProblem or HaloProblem.
+// (The factors of a lane's 16 accumulator rows -- demod x w_scale, or w_scale; the bias, or 0 -- stay written out in
+// rw_tile_epilogue and rw_halo_epilogue: filled by a shared function, the bias batch takes two conv_mfma_kernel forms
+// from 180 to 176 VGPRs and the scale batch changes the registers of both bf16x6 kernels; with the factors passed by
+// value every kernel changes.)
+template <int TN_, class P, class F> __device__ __forceinline__ void rw_noise_batch(const P& p, float (&nz)[TN_], F off) {
+#pragma unroll
+  for (int b = 0; b < TN_; ++b) nz[b] = 0.f;
+  if (p.noise) {
+    const float nw = p.noise_w[0];
+#pragma unroll
+    for (int b = 0; b < TN_; ++b) nz[b] = p.noise[off(b)];
+#pragma unroll
+    for (int b = 0; b < TN_; ++b) nz[b] *= nw;
+  }
+}
+
 // Epilogue of the im2col kernels for a wave's TM x TN accumulator tiles (C/D layout: col = lane&31
-// is the position n, row r of a tile is out-channel o_first + 32a + (r&3) + 8(r>>2)).  Every value
-// it reads is fetched in batches behind ONE uniform branch each: a load per store, each behind its
-// own `if`, costs an L2 round trip plus the drain of the previous store (vmcnt counts both).
+// is the position n, row r of a tile is out-channel o_first + 32a + rw_mfma32_row(r)).
 template <int TM_, int TN_>
 __device__ __forceinline__ void rw_tile_epilogue(const ConvProblem& p, const rw_f32x16 (&acc)[TM_][TN_],
                                                  int o_first, int64_t n_first, int ppi, int64_t n_total) {
@@ -65,26 +107,16 @@ __device__ __forceinline__ void rw_tile_epilogue(const ConvProblem& p, const rw_
     live[b] = n < n_total;
     const int64_t nn = live[b] ? n : 0;
     ib[b] = (int)(nn / ppi);
-    const int r0 = (int)(nn - (int64_t)ib[b] * ppi);
-    const int yq = r0 / p.pw;
-    const int yy = yq + p.yoff, xx = r0 - yq * p.pw + p.xoff;
-    pix[b] = (int64_t)(p.sy * yy + p.oy0) * p.ow + (p.sx * xx + p.ox0);
-    nz[b] = 0.f;
+    pix[b] = rw_conv_pos(p, (int)(nn - (int64_t)ib[b] * ppi)).pix;
   }
-  if (p.noise) {
-    const float nw = p.noise_w[0];
-#pragma unroll
-    for (int b = 0; b < TN_; ++b) nz[b] = p.noise[(int64_t)ib[b] * ohw + pix[b]];
-#pragma unroll
-    for (int b = 0; b < TN_; ++b) nz[b] *= nw;
-  }
+  rw_noise_batch<TN_>(p, nz, [&](int b) { return (int64_t)ib[b] * ohw + pix[b]; });
 #pragma unroll
   for (int a = 0; a < TM_; ++a) {
     const int ob = o_first + 32 * a;
     float bias[16];
     if (p.act) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bias[r] = p.bias[ob + (r & 3) + 8 * (r >> 2)];
+      for (int r = 0; r < 16; ++r) bias[r] = p.bias[ob + rw_mfma32_row(r)];
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) bias[r] = 0.f;
@@ -95,7 +127,7 @@ __device__ __forceinline__ void rw_tile_epilogue(const ConvProblem& p, const rw_
       if (p.demod) {
         const float* dm = p.demod + (int64_t)ib[b] * p.out_ch + ob;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) scale[r] = dm[(r & 3) + 8 * (r >> 2)];
+        for (int r = 0; r < 16; ++r) scale[r] = dm[rw_mfma32_row(r)];
 #pragma unroll
         for (int r = 0; r < 16; ++r) scale[r] *= p.w_scale;
       } else {
@@ -106,13 +138,11 @@ __device__ __forceinline__ void rw_tile_epilogue(const ConvProblem& p, const rw_
       float* yo = p.y + ((int64_t)ib[b] * p.out_ch + ob) * ohw + pix[b];
       if (p.act) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float v = acc[a][b][r] * scale[r] + nz[b] + bias[r];
-          yo[((r & 3) + 8 * (r >> 2)) * ohw] = ((v > 0.f) ? v : v * 0.2f) * 1.4142135623730951f;
-        }
+        for (int r = 0; r < 16; ++r)
+          yo[rw_mfma32_row(r) * ohw] = rw_lrelu_sqrt2(acc[a][b][r] * scale[r] + nz[b] + bias[r]);
       } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) yo[((r & 3) + 8 * (r >> 2)) * ohw] = acc[a][b][r] * scale[r] + nz[b];
+        for (int r = 0; r < 16; ++r) yo[rw_mfma32_row(r) * ohw] = acc[a][b][r] * scale[r] + nz[b];
       }
     }
   }
@@ -137,30 +167,23 @@ __global__ void __launch_bounds__(256) conv_mfma_kernel(const ConvBatch cb) {
   const int wn0 = (wave % WGN) * 32 * TN;
 
   int work = rw_xcd_remap(blockIdx.x, gridDim.x);
-  int q = 0;
-#pragma unroll
-  for (int j = 1; j < 4; ++j)
-    if (j < cb.n && work >= cb.work0[j]) q = j;
-  work -= cb.work0[q];
-  const ConvProblem& p = cb.p[q];
+  const ConvProblem& p = cb.p[rw_batch_slot(cb, work)];
   const int o_tiles = p.out_ch / BM;
   const int ppi = p.ph * p.pw;
   const int64_t n_total = (int64_t)p.batch * ppi;
   const int o0 = (work % o_tiles) * BM;
   const int64_t n0 = (int64_t)(work / o_tiles) * BN;
 
-  // ---- this thread's gather column
-  const int nl = tid % BN;
-  const int kk0 = tid / BN;
+  // this thread's gather column (written out in both im2col kernels: as one function returning (ok, gb, gy, gx) the
+  // 64x64 split-K kernel gains 48 v_mov_b64 at equal registers)
+  const int nl = tid % BN, kk0 = tid / BN;
   const int64_t n_mine = n0 + nl;
   const bool n_ok = n_mine < n_total;
   int gb = 0, gy = 0, gx = 0;
   if (n_ok) {
     gb = (int)(n_mine / ppi);
-    const int r = (int)(n_mine - (int64_t)gb * ppi);
-    gy = r / p.pw;
-    gx = r - gy * p.pw + p.xoff;
-    gy += p.yoff;
+    const ConvPos g = rw_conv_pos(p, (int)(n_mine - (int64_t)gb * ppi));
+    gy = g.yy; gx = g.xx;
   }
   const int64_t hw = (int64_t)p.h * p.w;
   const float* xb = p.x + (int64_t)gb * p.in_ch * hw;
@@ -282,29 +305,23 @@ __global__ void __launch_bounds__(256) conv_mfma_ksplit_kernel(const ConvBatch c
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int work = rw_xcd_remap(blockIdx.x, gridDim.x);
-  int q = 0;
-#pragma unroll
-  for (int j = 1; j < 4; ++j)
-    if (j < cb.n && work >= cb.work0[j]) q = j;
-  work -= cb.work0[q];
-  const ConvProblem& p = cb.p[q];
+  const ConvProblem& p = cb.p[rw_batch_slot(cb, work)];
   const int o_tiles = p.out_ch / BM;
   const int ppi = p.ph * p.pw;
   const int64_t n_total = (int64_t)p.batch * ppi;
   const int o0 = (work % o_tiles) * BM;
   const int64_t n0 = (int64_t)(work / o_tiles) * BN;
 
-  const int nl = tid % BN;
-  const int kk0 = tid / BN;
+  // this thread's gather column (written out in both im2col kernels: as one function returning (ok, gb, gy, gx) the
+  // 64x64 split-K kernel gains 48 v_mov_b64 at equal registers)
+  const int nl = tid % BN, kk0 = tid / BN;
   const int64_t n_mine = n0 + nl;
   const bool n_ok = n_mine < n_total;
   int gb = 0, gy = 0, gx = 0;
   if (n_ok) {
     gb = (int)(n_mine / ppi);
-    const int r = (int)(n_mine - (int64_t)gb * ppi);
-    gy = r / p.pw;
-    gx = r - gy * p.pw + p.xoff;
-    gy += p.yoff;
+    const ConvPos g = rw_conv_pos(p, (int)(n_mine - (int64_t)gb * ppi));
+    gy = g.yy; gx = g.xx;
   }
   const int64_t hw = (int64_t)p.h * p.w;
   const float* xb = p.x + (int64_t)gb * p.in_ch * hw;
@@ -387,9 +404,7 @@ __global__ void __launch_bounds__(256) conv_mfma_ksplit_kernel(const ConvBatch c
               acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf[b], acc[a][b], 0, 0, 0);
         }
         if (c + 1 < n_chunks) stash(buf ^ 1, bring[(d + 1) % DEPTH], aring[(d + 1) % DEPTH]);
-        // LDS writes complete + barrier; NOT __syncthreads(), whose vmcnt(0) would drain the ring every chunk
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
+        rw_lds_barrier();      // NOT __syncthreads(), whose vmcnt(0) would drain the ring every chunk
       }
     }
   }
@@ -458,6 +473,9 @@ static int rw_abl_env() { return rw_env_int("RW_CONV_ABL", 0); }
 static int rw_abl_env() { return 0; }
 #endif
 
+// the tile counts of a halo launch as rw_tile_digits reads them: work item -> (out-channel tile, tx, ty, image)
+struct HaloTiles { int o_tiles, tiles_x, tiles_y; };
+
 struct PhaseDesc {
   int ntaps;
   unsigned dy_bits, dx_bits;
@@ -496,16 +514,8 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
     const int yy = y_first + b * RPT;
     live[b] = yy < d.ph && xx < d.pw;
     pix[b] = live[b] ? (int64_t)(p.sy * yy + d.oy0) * p.ow + (p.sx * xx + d.ox0) : 0;
-    nz[b] = 0.f;
   }
-  if (p.noise) {
-    const float nw = p.noise_w[0];
-    const float* np = p.noise + (int64_t)ib * ohw;
-#pragma unroll
-    for (int b = 0; b < TN; ++b) nz[b] = np[pix[b]];
-#pragma unroll
-    for (int b = 0; b < TN; ++b) nz[b] *= nw;
-  }
+  rw_noise_batch<TN>(p, nz, [&](int b) { return (int64_t)ib * ohw + pix[b]; });
   // Fused ToRGB (models.py:639-655): rgb[c] = sum_o (s W[c][o] style[b][o]) * out[o] + bias[c] + skip.  The
   // workgroup holds every out-channel of its pixels: a lane sums its 16 * TM channels, the partner lane
   // (other half of the wave, same pixel) the rest.
@@ -520,7 +530,7 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
     if (p.demod) {
       const float* dm = p.demod + (int64_t)ib * p.out_ch + ob;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) scale[r] = dm[(r & 3) + 8 * (r >> 2)];
+      for (int r = 0; r < 16; ++r) scale[r] = dm[rw_mfma32_row(r)];
 #pragma unroll
       for (int r = 0; r < 16; ++r) scale[r] *= p.w_scale;
     } else {
@@ -529,7 +539,7 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
     }
     if (p.act) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bias[r] = p.bias[ob + (r & 3) + 8 * (r >> 2)];
+      for (int r = 0; r < 16; ++r) bias[r] = p.bias[ob + rw_mfma32_row(r)];
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) bias[r] = 0.f;
@@ -538,11 +548,11 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
     if (rgb) {
       float sr[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sr[r] = p.rgb_style[(int64_t)ib * p.out_ch + ob + (r & 3) + 8 * (r >> 2)];
+      for (int r = 0; r < 16; ++r) sr[r] = p.rgb_style[(int64_t)ib * p.out_ch + ob + rw_mfma32_row(r)];
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wr[c][r] = p.rgb_weight[c * p.out_ch + ob + (r & 3) + 8 * (r >> 2)];
+        for (int r = 0; r < 16; ++r) wr[c][r] = p.rgb_weight[c * p.out_ch + ob + rw_mfma32_row(r)];
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -556,11 +566,8 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float v = acc[a][b][r] * scale[r] + nz[b];
-        if (p.act) {
-          v += bias[r];
-          v = ((v > 0.f) ? v : v * 0.2f) * 1.4142135623730951f;
-        }
-        if (yo) yo[((r & 3) + 8 * (r >> 2)) * ohw] = v;
+        if (p.act) v = rw_lrelu_sqrt2(v + bias[r]);
+        if (yo) yo[rw_mfma32_row(r) * ohw] = v;
         if (rgb) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) part[b][c] += v * wr[c][r];
@@ -599,6 +606,32 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
   }
 }
 
+// Halo staging of the three halo kernels.  Thread tid of 256 owns up to PSLOT fixed positions of the XH x XUSED input
+// patch around tile (y0, x0) and walks the IC channels of a chunk for each: one 32-bit offset per slot, channel stride
+// uniform.  The rule for a slot is rw_halo_slot_of (rw_common.h), branch-free: outside the image a legal address times 0,
+// past the patch the padding column.  Each kernel keeps the tables as local arrays, fills them in its own loop and keeps
+// its own stash step: with the tables filled by a function over the arrays the <1, 4, 16, *> forms of conv_up_halo_kernel
+// spill (242 -> 256 VGPRs + 20 bytes of scratch), with tables, fetch and stash step as one struct <1, 4, 16, 32> takes
+// 244 VGPRs.
+// The fetch of one chunk: channels i0 .. i0 + IC of the thread's positions (offsets xoff inside a plane of hw floats; xb =
+// the image's planes) into xreg, the chunk's style into sty (st = the image's style row, uniform: scalar loads; none: 1.0).
+template <int IC, int PSLOT>
+__device__ __forceinline__ void rw_halo_fetch(const float* xb, const float* st, int64_t hw, int i0, const int (&xoff)[PSLOT],
+                                              float (&xreg)[PSLOT][IC], float (&sty)[IC]) {
+  const float* xc = xb + (int64_t)i0 * hw;               // uniform
+#pragma unroll
+  for (int ic = 0; ic < IC; ++ic)
+#pragma unroll
+    for (int sl = 0; sl < PSLOT; ++sl) xreg[sl][ic] = xc[(int64_t)ic * hw + xoff[sl]];
+  if (st) {
+#pragma unroll
+    for (int ic = 0; ic < IC; ++ic) sty[ic] = st[i0 + ic];
+  } else {
+#pragma unroll
+    for (int ic = 0; ic < IC; ++ic) sty[ic] = 1.0f;
+  }
+}
+
 // TW = 32: an MFMA column tile is 32 consecutive pixels of one row; TW = 16 (maps 9..16 wide): two
 // rows of 16; TW = 8 (maps 5..8 wide): four rows of 8 -- the low-resolution layers keep every lane of
 // the tile busy.
@@ -624,53 +657,25 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HaloProblem p) 
   for (int q = 1; q < 4; ++q)
     if (q < p.nphase && work >= p.phase[q].work0) phase = q;
   const PhaseDesc d = p.phase[phase];
-  int local = work - d.work0;
-  const int o_tiles = p.out_ch / BM;
-  const int o0 = (local % o_tiles) * BM; local /= o_tiles;
-  const int tx = local % d.tiles_x; local /= d.tiles_x;
-  const int ty = local % d.tiles_y;
-  const int ib = local / d.tiles_y;
-  const int y0 = ty * TH, x0 = tx * TW;
+  int ot, tx, ty, ib;
+  rw_tile_digits(HaloTiles{p.out_ch / BM, d.tiles_x, d.tiles_y}, work - d.work0, ot, tx, ty, ib);
+  const int o0 = ot * BM, y0 = ty * TH, x0 = tx * TW;
   const int64_t hw = (int64_t)p.h * p.w;
   const float* xb = p.x + (int64_t)ib * p.in_ch * hw;
   const float* st = p.style ? p.style + (int64_t)ib * p.in_ch : nullptr;     // uniform: scalar loads
   const float* wph = p.wp + d.wp_off + o0;            // wave-uniform
   const int a_lane = frow * p.out_ch + wm0 + fcol;    // this lane's offset inside a k-pair of rows
 
-  // Halo staging: this thread owns up to PSLOT fixed positions (r, c) of the (TH+2) x 34 patch and
-  // walks the IC channels of a chunk for each: one 32-bit offset per slot, channel stride uniform.
-  // Positions outside the image are loaded from a legal address and multiplied by 0, slots past the
-  // patch are written to a padding column nobody reads, so the staging is branch-free.
-  constexpr int NPOS = XH * XUSED;
-  constexpr int PSLOT = (NPOS + 255) / 256;
+  // Halo staging (see rw_halo_fetch) of the (TH+2) x (TW+2) patch
+  constexpr int PSLOT = (XH * XUSED + 255) / 256;
   int xoff[PSLOT], xlds[PSLOT];
   float xmask[PSLOT];
 #pragma unroll
-  for (int sl = 0; sl < PSLOT; ++sl) {
-    const int pos = tid + 256 * sl;
-    const int r = pos / XUSED, c = pos - r * XUSED;
-    const int iy = y0 - 1 + r, ix = x0 - 1 + c;
-    const bool ok = pos < NPOS && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
-    xoff[sl] = ok ? iy * p.w + ix : 0;            // invalid -> any legal address, value masked to 0
-    xmask[sl] = ok ? 1.0f : 0.0f;
-    xlds[sl] = pos < NPOS ? r * XW + c : XW - 1;
-  }
+  for (int sl = 0; sl < PSLOT; ++sl)
+    rw_halo_slot_of(tid + 256 * sl, y0, x0, p.h, p.w, XH, XW, XUSED, xoff[sl], xmask[sl], xlds[sl]);
   float xreg[PSLOT][IC];
   float sty[IC];                            // style of the chunk held in xreg (SGPRs; 1.0 when not fused)
-  auto xfetch = [&](int i0) {
-    const float* xc = xb + (int64_t)i0 * hw;               // uniform
-#pragma unroll
-    for (int ic = 0; ic < IC; ++ic)
-#pragma unroll
-      for (int sl = 0; sl < PSLOT; ++sl) xreg[sl][ic] = xc[(int64_t)ic * hw + xoff[sl]];
-    if (st) {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = st[i0 + ic];
-    } else {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = 1.0f;
-    }
-  };
+  auto xfetch = [&](int i0) { rw_halo_fetch(xb, st, hw, i0, xoff, xreg, sty); };
   // One element of the staging (mask + style applied on the way into LDS).  In the stride-1 kernel
   // the steps ride between the MFMAs of the last two taps of a chunk, so there is no VALU/LDS-only
   // phase in front of the barrier.
@@ -816,8 +821,7 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   constexpr int RPT = 32 / TW;                // quad rows per 32-lane column tile (TW = 16: two, narrow maps)
   constexpr int TH = TN * WGN * RPT;
   constexpr int XH = TH + 1, XW = TW == 32 ? 36 : (TW == 16 ? 20 : 12), XUSED = TW + 1;
-  constexpr int NPOS = XH * XUSED;
-  constexpr int PSLOT = (NPOS + 255) / 256;
+  constexpr int PSLOT = (XH * XUSED + 255) / 256;
   constexpr int KP = IC / 2;
   static_assert(WGM * WGN == 4, "4 waves per workgroup");
   __shared__ float Xs[2][IC][XH][XW];
@@ -829,13 +833,9 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   const int frow = lane >> 5, fcol = lane & 31;
   const int lc = fcol & (TW - 1), lr = fcol / TW;
 
-  int local = rw_xcd_remap(blockIdx.x, gridDim.x);
-  const int o_tiles = p.out_ch / BM;
-  const int o0 = (local % o_tiles) * BM; local /= o_tiles;
-  const int tx = local % p.tiles_x; local /= p.tiles_x;
-  const int ty = local % p.tiles_y;
-  const int ib = local / p.tiles_y;
-  const int y0 = ty * TH, x0 = tx * TW;
+  int ot, tx, ty, ib;
+  rw_tile_digits(HaloTiles{p.out_ch / BM, p.tiles_x, p.tiles_y}, rw_xcd_remap(blockIdx.x, gridDim.x), ot, tx, ty, ib);
+  const int o0 = ot * BM, y0 = ty * TH, x0 = tx * TW;
   const int64_t hw = (int64_t)p.h * p.w;
   const float* xb = p.x + (int64_t)ib * p.in_ch * hw;
   const float* st = p.style ? p.style + (int64_t)ib * p.in_ch : nullptr;     // uniform: scalar loads
@@ -846,37 +846,15 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   // a memory latency per workgroup: the per-channel factors go to LDS up front (visible after the first barrier).
   if (tid < BM) Sc[tid] = p.demod ? p.demod[(int64_t)ib * p.out_ch + o0 + tid] * p.w_scale : p.w_scale;
 
-  // Halo staging: this thread owns up to PSLOT fixed positions of the (TH+1) x 33 patch; positions
-  // outside the image are loaded from a legal address and multiplied by 0, slots past the patch
-  // are written to a padding column nobody reads, so the staging is branch-free.
+  // Halo staging (see rw_halo_fetch) of the (TH+1) x (TW+1) patch
   int xoff[PSLOT], xlds[PSLOT];
   float xmask[PSLOT];
 #pragma unroll
-  for (int sl = 0; sl < PSLOT; ++sl) {
-    const int pos = tid + 256 * sl;
-    const int r = pos / XUSED, c = pos - r * XUSED;
-    const int iy = y0 - 1 + r, ix = x0 - 1 + c;
-    const bool ok = pos < NPOS && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
-    xoff[sl] = ok ? iy * p.w + ix : 0;
-    xmask[sl] = ok ? 1.0f : 0.0f;
-    xlds[sl] = pos < NPOS ? r * XW + c : XW - 1;
-  }
+  for (int sl = 0; sl < PSLOT; ++sl)
+    rw_halo_slot_of(tid + 256 * sl, y0, x0, p.h, p.w, XH, XW, XUSED, xoff[sl], xmask[sl], xlds[sl]);
   float xreg[PSLOT][IC];
   float sty[IC];                            // style of the chunk held in xreg (SGPRs)
-  auto xfetch = [&](int i0) {
-    const float* xc = xb + (int64_t)i0 * hw;
-#pragma unroll
-    for (int ic = 0; ic < IC; ++ic)
-#pragma unroll
-      for (int sl = 0; sl < PSLOT; ++sl) xreg[sl][ic] = xc[(int64_t)ic * hw + xoff[sl]];
-    if (st) {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = st[i0 + ic];
-    } else {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = 1.0f;
-    }
-  };
+  auto xfetch = [&](int i0) { rw_halo_fetch(xb, st, hw, i0, xoff, xreg, sty); };
   // one element of the staging (style and the zero padding applied on the way into LDS); the steps
   // are spread between the MFMAs of the last k-pairs of a chunk instead of forming a VALU/LDS-only
   // phase in front of the barrier
@@ -989,7 +967,7 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   const bool pair_ok = (xx | 1) < p.w;        // both quads of the lane pair are inside the tiled area
   float scale[16];                            // w_scale * demod of this lane's 16 out-channels (LDS table)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) scale[r] = Sc[wm0 + 4 * frow + (r & 3) + 8 * (r >> 2)];
+  for (int r = 0; r < 16; ++r) scale[r] = Sc[wm0 + 4 * frow + rw_mfma32_row(r)];
 #pragma unroll
   for (int b = 0; b < TN; ++b) {
     const int yy = y0 + wrow0 + b * RPT + lr;
@@ -1012,13 +990,13 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
         f32x4_u v;
         v[0] = odd_lane ? g0 : v00; v[1] = odd_lane ? g1 : v01;
         v[2] = odd_lane ? v10 : g0; v[3] = odd_lane ? v11 : g1;
-        *reinterpret_cast<f32x4_u*>(yv + (int64_t)((r & 3) + 8 * (r >> 2)) * ohw) = v;
+        *reinterpret_cast<f32x4_u*>(yv + (int64_t)rw_mfma32_row(r) * ohw) = v;
       }
     } else if (xx < p.w) {                      // odd W: last quad column of the tiled area
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float sc = scale[r];
-        float* yo = yb + (int64_t)((r & 3) + 8 * (r >> 2)) * ohw;
+        float* yo = yb + (int64_t)rw_mfma32_row(r) * ohw;
         f32x2_u e = {acc[0][b][r] * sc, acc[1][b][r] * sc}, d = {acc[2][b][r] * sc, acc[3][b][r] * sc};
         *reinterpret_cast<f32x2_u*>(yo) = e;
         *reinterpret_cast<f32x2_u*>(yo + ow) = d;
@@ -1171,30 +1149,34 @@ static int launch_up_strips(const ConvProblem& c, const float* wp_all, hipStream
   return RW_LAUNCH_RESULT();
 }
 
+// The tile of a halo kernel for a map `width` positions wide: tw columns (a 32-lane column tile is 32 / tw image rows: 2 on
+// maps 9..16 wide, 4 on maps 5..8 wide), th rows and bm out-channels per workgroup.  Stride 1: 128 x 4, 64 x 8 or 32 x 16
+// rows of 32; the quad tiles of the transposed convolution (up): 64 x 4 or 32 x 8; 8-wide tiles: 128 out-channels x 8 rows.
+struct HaloTile { int tw, th, bm; };
+static HaloTile halo_tile(int width, int out_ch, bool up) {
+  HaloTile t;
+  t.tw = width > 16 ? 32 : (width > 8 ? 16 : 8);
+  t.bm = out_ch % 128 == 0 && !up ? 128 : (out_ch % 64 == 0 ? 64 : 32);
+  t.th = (up ? 256 : 512) / t.bm * (32 / t.tw);
+  if (t.tw == 8) { t.th = 8; t.bm = 128; }
+  return t;
+}
+
 static int launch_up_halo(const ConvProblem* ps, const float* wp_all, int part, hipStream_t s) {
   const ConvProblem& c = ps[0];
   UpProblem u;
   u.x = c.x; u.wfrag = wp_all + (int64_t)9 * c.in_ch * c.out_ch; u.y = c.y; u.style = c.style; u.demod = c.demod;
   u.batch = c.batch; u.in_ch = c.in_ch; u.out_ch = c.out_ch; u.h = c.h; u.w = c.w; u.w_scale = c.w_scale;
   u.abl = rw_abl_env();
-  const int tw = c.w > 16 ? 32 : (c.w > 8 ? 16 : 8), rpt = 32 / tw;
-  u.tiles_x = (int)rw_cdiv(c.w, tw);
+  const HaloTile t = halo_tile(c.w, c.out_ch, true);
+  u.tiles_x = (int)rw_cdiv(c.w, t.tw); u.tiles_y = (int)rw_cdiv(c.h, t.th);
+  const dim3 grid(c.batch * u.tiles_x * u.tiles_y * (c.out_ch / t.bm)), block(256);
   if (part == 2) {
-  } else if (tw == 8) {                            // 128 out-channels x (8 x 8 quads)
-    u.tiles_y = (int)rw_cdiv(c.h, 8);
-    const int work = c.batch * u.tiles_x * u.tiles_y * (c.out_ch / 128);
-    hipLaunchKernelGGL((conv_up_halo_kernel<4, 1, 16, 8>), dim3(work), dim3(256), 0, s, u);
-  } else if (c.out_ch % 64 == 0) {
-    u.tiles_y = (int)rw_cdiv(c.h, 4 * rpt);
-    const int work = c.batch * u.tiles_x * u.tiles_y * (c.out_ch / 64);
-    if (tw == 16) hipLaunchKernelGGL((conv_up_halo_kernel<2, 2, 16, 16>), dim3(work), dim3(256), 0, s, u);
-    else hipLaunchKernelGGL((conv_up_halo_kernel<2, 2, 16, 32>), dim3(work), dim3(256), 0, s, u);
-  } else {
-    u.tiles_y = (int)rw_cdiv(c.h, 8 * rpt);
-    const int work = c.batch * u.tiles_x * u.tiles_y * (c.out_ch / 32);
-    if (tw == 16) hipLaunchKernelGGL((conv_up_halo_kernel<1, 4, 16, 16>), dim3(work), dim3(256), 0, s, u);
-    else hipLaunchKernelGGL((conv_up_halo_kernel<1, 4, 16, 32>), dim3(work), dim3(256), 0, s, u);
-  }
+  } else if (t.tw == 8) hipLaunchKernelGGL((conv_up_halo_kernel<4, 1, 16, 8>), grid, block, 0, s, u);
+  else if (t.bm == 64 && t.tw == 16) hipLaunchKernelGGL((conv_up_halo_kernel<2, 2, 16, 16>), grid, block, 0, s, u);
+  else if (t.bm == 64) hipLaunchKernelGGL((conv_up_halo_kernel<2, 2, 16, 32>), grid, block, 0, s, u);
+  else if (t.tw == 16) hipLaunchKernelGGL((conv_up_halo_kernel<1, 4, 16, 16>), grid, block, 0, s, u);
+  else hipLaunchKernelGGL((conv_up_halo_kernel<1, 4, 16, 32>), grid, block, 0, s, u);
   if (part == 1) return RW_LAUNCH_RESULT();
   // Output row 2H and column 2W: quads y' = H (phases (0,0),(0,1)) and x' = W, y' < H (phases (0,0),(1,0)): the strip
   // kernel above; RW_UP_STRIPS=im2col keeps the four strip problems of one batched im2col launch (A/B, cross-check)
@@ -1223,56 +1205,51 @@ static bool halo_applicable(const ConvProblem* ps, int n) {
 }
 
 template <int TW>
-static void launch_halo_frag(int bm, int work, const HaloProblem& h, hipStream_t s) {
-  if (bm == 128)
-    hipLaunchKernelGGL((conv_halo_kernel<2, 2, 2, 2, 16, true, TW>), dim3(work), dim3(256), 0, s, h);
-  else if (bm == 64)
-    hipLaunchKernelGGL((conv_halo_kernel<2, 2, 1, 4, 16, true, TW>), dim3(work), dim3(256), 0, s, h);
-  else
-    hipLaunchKernelGGL((conv_halo_kernel<1, 4, 1, 4, 8, true, TW>), dim3(work), dim3(256), 0, s, h);
+static void launch_halo_frag(int bm, dim3 grid, const HaloProblem& h, hipStream_t s) {
+  if (bm == 128) hipLaunchKernelGGL((conv_halo_kernel<2, 2, 2, 2, 16, true, TW>), grid, dim3(256), 0, s, h);
+  else if (bm == 64) hipLaunchKernelGGL((conv_halo_kernel<2, 2, 1, 4, 16, true, TW>), grid, dim3(256), 0, s, h);
+  else hipLaunchKernelGGL((conv_halo_kernel<1, 4, 1, 4, 8, true, TW>), grid, dim3(256), 0, s, h);
 }
 
-// ps: 1 (stride-1 conv) or 4 (transposed-conv phases) problems sharing x / y / epilogue.
-static int launch_halo(const ConvProblem* ps, int n, const float* wfrag, hipStream_t s, const rw_rgb_epilogue* rgb = nullptr) {
+// ps: 1 (stride-1 conv) or 4 (transposed-conv phases) problems sharing x / y / epilogue -> the problem of a halo kernel
+// on tiles t.  Returns the launch's workgroups.
+static int64_t fill_halo(HaloProblem& h, const ConvProblem* ps, int n, const float* wfrag, const rw_rgb_epilogue* rgb,
+                         const HaloTile& t) {
   const ConvProblem& c = ps[0];
-  HaloProblem h;
   rw_fill_rgb(h, rgb);
   h.x = c.x; h.wp = ps[0].wp; h.wfrag = wfrag; h.y = c.y; h.style = c.style; h.demod = c.demod; h.noise = c.noise;
   h.noise_w = c.noise_w; h.bias = c.bias; h.batch = c.batch; h.in_ch = c.in_ch; h.out_ch = c.out_ch;
   h.h = c.h; h.w = c.w; h.oh = c.oh; h.ow = c.ow; h.sy = c.sy; h.sx = c.sx; h.w_scale = c.w_scale;
   h.act = c.act; h.nphase = n; h.abl = rw_abl_env();
-  // 2 (4) image rows per column tile on maps 9..16 (5..8) wide
-  const int tw = !wfrag || c.pw > 16 ? 32 : (c.pw > 8 ? 16 : 8);
-  int th, bm;
-  if (c.out_ch % 128 == 0) { th = 4; bm = 128; }
-  else if (c.out_ch % 64 == 0) { th = 8; bm = 64; }
-  else { th = 16; bm = 32; }
-  th *= 32 / tw;
-  if (tw == 8) { th = 8; bm = 128; }                   // one variant: 128 out-channels x (8 rows x 8 columns)
-  int work = 0;
+  int64_t work = 0;
   for (int q = 0; q < 4; ++q) {
     PhaseDesc& d = h.phase[q];
     const ConvProblem& pq = ps[q < n ? q : 0];
     d.ntaps = pq.ntaps; d.dy_bits = pq.dy_bits; d.dx_bits = pq.dx_bits; d.ph = pq.ph; d.pw = pq.pw;
     d.oy0 = pq.oy0; d.ox0 = pq.ox0;
-    d.tiles_x = (int)rw_cdiv(pq.pw, tw); d.tiles_y = (int)rw_cdiv(pq.ph, th);
-    d.work0 = work; d.wp_off = (long long)(pq.wp - ps[0].wp);
-    if (q < n) work += c.batch * d.tiles_x * d.tiles_y * (c.out_ch / bm);
+    d.tiles_x = (int)rw_cdiv(pq.pw, t.tw); d.tiles_y = (int)rw_cdiv(pq.ph, t.th);
+    d.work0 = (int)work; d.wp_off = (long long)(pq.wp - ps[0].wp);
+    if (q < n) work += (int64_t)c.batch * d.tiles_x * d.tiles_y * (c.out_ch / t.bm);
   }
+  return work;
+}
+
+// wfrag: the weights in fragment order (stride-1 convolution); nullptr: the per-phase form of the transposed convolution,
+// which reads wp[tap][i][o] and has 32-pixel column tiles only
+static int launch_halo(const ConvProblem* ps, int n, const float* wfrag, hipStream_t s, const rw_rgb_epilogue* rgb = nullptr) {
+  const HaloTile t = halo_tile(wfrag ? ps[0].pw : 32, ps[0].out_ch, false);
+  HaloProblem h;
+  const int64_t work = fill_halo(h, ps, n, wfrag, rgb, t);
   if (work == 0) return 0;
-  if (wfrag) {        // stride-1 convolution, weights in fragment order
-    if (tw == 8)
-      hipLaunchKernelGGL((conv_halo_kernel<2, 1, 2, 2, 16, true, 8>), dim3(work), dim3(256), 0, s, h);
-    else if (tw == 16) launch_halo_frag<16>(bm, work, h, s);
-    else launch_halo_frag<32>(bm, work, h, s);
-  } else {
-    if (bm == 128)
-      hipLaunchKernelGGL((conv_halo_kernel<2, 2, 2, 2, 16, false, 32>), dim3(work), dim3(256), 0, s, h);
-    else if (bm == 64)
-      hipLaunchKernelGGL((conv_halo_kernel<2, 2, 1, 4, 16, false, 32>), dim3(work), dim3(256), 0, s, h);
-    else
-      hipLaunchKernelGGL((conv_halo_kernel<1, 4, 1, 4, 8, false, 32>), dim3(work), dim3(256), 0, s, h);
-  }
+  if (work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)work), block(256);
+  if (!wfrag) {
+    if (t.bm == 128) hipLaunchKernelGGL((conv_halo_kernel<2, 2, 2, 2, 16, false, 32>), grid, block, 0, s, h);
+    else if (t.bm == 64) hipLaunchKernelGGL((conv_halo_kernel<2, 2, 1, 4, 16, false, 32>), grid, block, 0, s, h);
+    else hipLaunchKernelGGL((conv_halo_kernel<1, 4, 1, 4, 8, false, 32>), grid, block, 0, s, h);
+  } else if (t.tw == 8) hipLaunchKernelGGL((conv_halo_kernel<2, 1, 2, 2, 16, true, 8>), grid, block, 0, s, h);
+  else if (t.tw == 16) launch_halo_frag<16>(t.bm, grid, h, s);
+  else launch_halo_frag<32>(t.bm, grid, h, s);
   return RW_LAUNCH_RESULT();
 }
 
@@ -1289,7 +1266,7 @@ __global__ void __launch_bounds__(256) conv_direct_kernel(const ConvProblem p) {
     const int r0 = (int)(idx % ppi);
     const int o = (int)((idx / ppi) % p.out_ch);
     const int ib = (int)(idx / ((int64_t)ppi * p.out_ch));
-    const int yq = r0 / p.pw;
+    const int yq = r0 / p.pw;       // written out: through rw_conv_pos the kernel takes 85 SGPRs instead of 84
     const int yy = yq + p.yoff, xx = r0 - yq * p.pw + p.xoff;
     float acc = 0.f;
     for (int t = 0; t < p.ntaps; ++t) {
@@ -1307,10 +1284,7 @@ __global__ void __launch_bounds__(256) conv_direct_kernel(const ConvProblem p) {
     float v = acc * p.w_scale;
     if (p.demod) v *= p.demod[(int64_t)ib * p.out_ch + o];
     if (p.noise) v += nw * p.noise[(int64_t)ib * ohw + pix];
-    if (p.act) {
-      v += p.bias[o];
-      v = ((v > 0.f) ? v : v * 0.2f) * 1.4142135623730951f;
-    }
+    if (p.act) v = rw_lrelu_sqrt2(v + p.bias[o]);
     p.y[((int64_t)ib * p.out_ch + o) * ohw + pix] = v;
   }
 }
@@ -1391,16 +1365,23 @@ static void set_tap(ConvProblem& p, int t, int dy, int dx) {
   p.dx_bits |= (unsigned)(dx + 1) << (2 * t);
 }
 
-extern "C" int rw_conv3x3_f32(const float* x, const float* wp, float* y, int batch, int in_ch,
-                              int out_ch, int h, int w, float w_scale, const rw_conv_epilogue* ep,
-                              int impl, rw_stream_t stream) {
-  RW_CHECK_ARG(x && wp && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
-  RW_CHECK_ARG(rw_epilogue_ok(ep));
+// the stride-1 convolution: one position per pixel, nine taps (dy, dx) = (t / 3 - 1, t % 3 - 1)
+static ConvProblem stride1_problem(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch, int h, int w,
+                                   float w_scale, const rw_conv_epilogue* ep) {
   ConvProblem p;
   fill_common(p, x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep);
   p.ph = h; p.pw = w; p.oh = h; p.ow = w; p.sy = 1; p.sx = 1; p.oy0 = 0; p.ox0 = 0;
   p.ntaps = 9;
   for (int t = 0; t < 9; ++t) set_tap(p, t, t / 3 - 1, t % 3 - 1);
+  return p;
+}
+
+extern "C" int rw_conv3x3_f32(const float* x, const float* wp, float* y, int batch, int in_ch,
+                              int out_ch, int h, int w, float w_scale, const rw_conv_epilogue* ep,
+                              int impl, rw_stream_t stream) {
+  RW_CHECK_ARG(x && wp && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
+  RW_CHECK_ARG(rw_epilogue_ok(ep));
+  const ConvProblem p = stride1_problem(x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep);
   if (impl == 3 && !halo_applicable(&p, 1)) return RW_ERR_UNSUPPORTED;
   if (impl == 3 || (impl == 0 && halo_applicable(&p, 1)))
     return launch_halo(&p, 1, wp + (int64_t)9 * in_ch * out_ch, rw_s(stream));
@@ -1415,11 +1396,7 @@ extern "C" int rw_conv3x3_to_rgb_f32(const float* x, const float* wp, float* y, 
   // ONE WAVE must hold every out-channel of its pixels (the 32- and 64-channel tile shapes), 32-pixel column tiles
   if (!(out_ch == 32 || out_ch == 64) || w < 24 || in_ch % 16 || in_ch > 1024)
     return RW_ERR_UNSUPPORTED;
-  ConvProblem p;
-  fill_common(p, x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep);
-  p.ph = h; p.pw = w; p.oh = h; p.ow = w; p.sy = 1; p.sx = 1; p.oy0 = 0; p.ox0 = 0;
-  p.ntaps = 9;
-  for (int t = 0; t < 9; ++t) set_tap(p, t, t / 3 - 1, t % 3 - 1);
+  const ConvProblem p = stride1_problem(x, wp, y, batch, in_ch, out_ch, h, w, w_scale, ep);
   return launch_halo(&p, 1, wp + (int64_t)9 * in_ch * out_ch, rw_s(stream), rgb);
 }
 
@@ -1519,47 +1496,22 @@ __global__ void __launch_bounds__(256, 2) conv_halo_bf16x6_kernel(const HaloProb
   const int frow = lane >> 5, fcol = lane & 31;
 
   const PhaseDesc d = p.phase[0];
-  int local = rw_xcd_remap(blockIdx.x, gridDim.x);
-  const int o_tiles = p.out_ch / BM;
-  const int o0 = (local % o_tiles) * BM; local /= o_tiles;
-  const int tx = local % d.tiles_x; local /= d.tiles_x;
-  const int ty = local % d.tiles_y;
-  const int ib = local / d.tiles_y;
-  const int y0 = ty * TH, x0 = tx * 32;
+  int ot, tx, ty, ib;
+  rw_tile_digits(HaloTiles{p.out_ch / BM, d.tiles_x, d.tiles_y}, rw_xcd_remap(blockIdx.x, gridDim.x), ot, tx, ty, ib);
+  const int o0 = ot * BM, y0 = ty * TH, x0 = tx * 32;
   const int64_t hw = (int64_t)p.h * p.w;
   const float* xb = p.x + (int64_t)ib * p.in_ch * hw;
   const float* st = p.style ? p.style + (int64_t)ib * p.in_ch : nullptr;
 
-  constexpr int NPOS = XH * XUSED;
-  constexpr int PSLOT = (NPOS + 255) / 256;
+  constexpr int PSLOT = (XH * XUSED + 255) / 256;
   int xoff[PSLOT], xlds[PSLOT];
   float xmask[PSLOT];
 #pragma unroll
-  for (int sl = 0; sl < PSLOT; ++sl) {
-    const int pos = tid + 256 * sl;
-    const int r = pos / XUSED, c = pos - r * XUSED;
-    const int iy = y0 - 1 + r, ix = x0 - 1 + c;
-    const bool ok = pos < NPOS && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
-    xoff[sl] = ok ? iy * p.w + ix : 0;
-    xmask[sl] = ok ? 1.0f : 0.0f;
-    xlds[sl] = pos < NPOS ? r * XW + c : XW - 1;
-  }
+  for (int sl = 0; sl < PSLOT; ++sl)
+    rw_halo_slot_of(tid + 256 * sl, y0, x0, p.h, p.w, XH, XW, XUSED, xoff[sl], xmask[sl], xlds[sl]);
   float xreg[PSLOT][IC];
   float sty[IC];
-  auto xfetch = [&](int i0) {
-    const float* xc = xb + (int64_t)i0 * hw;
-#pragma unroll
-    for (int ic = 0; ic < IC; ++ic)
-#pragma unroll
-      for (int sl = 0; sl < PSLOT; ++sl) xreg[sl][ic] = xc[(int64_t)ic * hw + xoff[sl]];
-    if (st) {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = st[i0 + ic];
-    } else {
-#pragma unroll
-      for (int ic = 0; ic < IC; ++ic) sty[ic] = 1.0f;
-    }
-  };
+  auto xfetch = [&](int i0) { rw_halo_fetch(xb, st, hw, i0, xoff, xreg, sty); };
   // style and zero padding in fp32, then the exact three-way split, 8 channels per 16-byte LDS cell;
   // one unit = the 8 channels (sl, g) of one staged position
   constexpr int NU = 2 * PSLOT;
@@ -1673,26 +1625,13 @@ extern "C" int rw_conv3x3_bf16x6_f32(const float* x, const void* wb, float* y, i
   RW_CHECK_ARG(x && wb && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
   RW_CHECK_ARG(rw_epilogue_ok(ep));
   if (w < 24 || in_ch % 16 || in_ch > 1024 || out_ch % 64) return RW_ERR_UNSUPPORTED;
+  // the weights ride in wfrag (there is no wp[tap][i][o] form of them); the kernels have 32-pixel tiles of 128 or 64 channels
+  const ConvProblem p = stride1_problem(x, nullptr, y, batch, in_ch, out_ch, h, w, w_scale, ep);
+  const HaloTile t = halo_tile(w, out_ch, false);
   HaloProblem hp;
-  hp.x = x; hp.wp = nullptr; hp.wfrag = reinterpret_cast<const float*>(wb); hp.y = y;
-  rw_fill_epilogue(hp, ep);
-  hp.batch = batch; hp.in_ch = in_ch; hp.out_ch = out_ch; hp.h = h; hp.w = w; hp.oh = h; hp.ow = w;
-  hp.sy = 1; hp.sx = 1; hp.w_scale = w_scale; hp.nphase = 1; hp.abl = rw_abl_env();
-  hp.rgb_weight = nullptr; hp.rgb_style = nullptr; hp.rgb_bias = nullptr; hp.rgb_skip = nullptr; hp.rgb_out = nullptr;
-  hp.rgb_scale = 0.f;
-  const int bm = out_ch % 128 == 0 ? 128 : 64, th = bm == 128 ? 4 : 8;
-  PhaseDesc& d = hp.phase[0];
-  d.ntaps = 9; d.dy_bits = 0; d.dx_bits = 0;
-  for (int t = 0; t < 9; ++t) {
-    d.dy_bits |= (unsigned)(t / 3) << (2 * t);          // (dy + 1), (dx + 1)
-    d.dx_bits |= (unsigned)(t % 3) << (2 * t);
-  }
-  d.ph = h; d.pw = w; d.oy0 = 0; d.ox0 = 0;
-  d.tiles_x = (int)rw_cdiv(w, 32); d.tiles_y = (int)rw_cdiv(h, th); d.work0 = 0; d.wp_off = 0;
-  for (int q = 1; q < 4; ++q) hp.phase[q] = d;
-  const int64_t work = (int64_t)batch * d.tiles_x * d.tiles_y * (out_ch / bm);
+  const int64_t work = fill_halo(hp, &p, 1, reinterpret_cast<const float*>(wb), nullptr, t);
   if (work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
-  if (bm == 128)
+  if (t.bm == 128)
     hipLaunchKernelGGL((conv_halo_bf16x6_kernel<2, 2, 2, 2>), dim3((unsigned)work), dim3(256), 0, rw_s(stream), hp);
   else
     hipLaunchKernelGGL((conv_halo_bf16x6_kernel<2, 2, 1, 4>), dim3((unsigned)work), dim3(256), 0, rw_s(stream), hp);

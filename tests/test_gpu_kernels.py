@@ -159,7 +159,7 @@ CONV_CASES = [  # (batch, cin, cout, h, w)
     (2, 512, 512, 4, 4), (3, 512, 512, 8, 8), (1, 512, 512, 32, 32), (2, 512, 256, 16, 16),
     (1, 256, 128, 8, 12), (2, 128, 64, 16, 16), (1, 64, 32, 32, 32), (1, 32, 32, 20, 36),
     (2, 128, 64, 40, 64), (5, 16, 32, 3, 5), (1, 48, 96, 7, 9), (2, 64, 128, 13, 29), (1, 32, 64, 70, 33),
-    (1, 64, 64, 8, 8), (3, 128, 32, 4, 6), (16, 512, 512, 4, 4),
+    (1, 64, 64, 8, 8), (3, 128, 32, 4, 6), (16, 512, 512, 4, 4), (1, 32, 96, 9, 13),
 ]
 
 
