@@ -201,6 +201,11 @@ __device__ __forceinline__ void rw_dma_buffer_b32(unsigned lds_addr, int voffset
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
                :: "s"(lds_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
 }
+// 16 bytes per lane; voffset + soffset and lds_addr are multiples of 16, an out-of-range lane writes four zeros
+__device__ __forceinline__ void rw_dma_buffer_b128(unsigned lds_addr, int voffset, rw_i32x4 rsrc, int soffset) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+               :: "s"(lds_addr), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
+}
 __device__ __forceinline__ void rw_dma_global_b32(unsigned lds_addr, const void* gptr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" :: "s"(lds_addr), "v"(gptr) : "memory");
 }

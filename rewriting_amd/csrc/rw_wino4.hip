@@ -344,10 +344,38 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 // loads write behind ALL of them (vmcnt(0) in front of the first read of an interval), and with one array per ring
 // slot it serialises the loads themselves.  So the loads are issued from inline assembly -- the compiler does not
 // know they exist -- and every vmcnt wait in the loop is written by hand.  The loop has no ordinary vector load:
-//   * patch: `buffer_load_dword ... lds` (out-of-image lanes write 0: the zero padding), the (4 WGN + 2) x 66 window
-//     of a channel as a flat image of pitch 68, 20 one-wave pieces per channel; wave w copies channel w / 2, pieces
-//     10 (w % 2) .. + 9.  The style factor is applied in the transform (packed multiplies of the 18 input pairs)
-//     from a table in LDS;
+//   * patch: `buffer_load_dwordx4 ... lds` (rw_dma_buffer_b128), 16 bytes per lane from 16-byte aligned addresses.  The
+//     window of a channel is rows y0 - 1 .. y0 + PR - 2 (PR = 4 WGN + 2) x columns x0 - 4 .. x0 + 67: 72 floats = 18 items
+//     per row, row pitch 72, PR x 18 = 180 (324) items = 720 (1296) floats per channel slot, item i at byte 16 i.  x0 and
+//     the width are multiples of 64, so an item lies wholly inside the image or wholly outside it; an outside item has the
+//     lane offset 0x7fffffff and the load writes four zeros: the zero padding, per item.  A channel is copied by
+//     ceil(items / 64) = 3 (6) one-wave pieces of 1 KB (eleven 256-byte pieces before: pitch 68, one float per lane); the
+//     last piece starts at item items - 64, overlaps its predecessor and writes those bytes twice (the same values), so
+//     no lane lands outside the slot -- no exec mask, no pad.  Wave w copies channel w (<4, 3>: channel w / 2, pieces
+//     3 (w % 2) .. + 2): three pieces and three offset registers per wave and interval.  The style factor is applied in
+//     the transform (multiplies of the 18 input pairs) from a table in LDS;
+//     read side (w4_row_read): tile lt's six columns x0 + 4 lt - 1 .. + 4 are floats 4 lt + 3 .. 4 lt + 8 of the row:
+//     one ds_read_b128 at + 4 (aligned) and one ds_read2_b32 at + 3 and + 8 -- two instructions per row as before.
+//     Banks (MI355X: ds_read_b128 by 16-byte slot mod 16 within four 16-lane groups such as lanes {0-3, 12-15, 20-27};
+//     ds_read2_b32 as two 4-byte accesses by dword mod 32 within the 32-lane halves):
+//       - b128: lane (lk, lt) reads slot 180 lk + 18 row + lt + 1.  A group holds eight tiles of channel lk and the
+//         other eight of channel lk + 1, 180 = 4 (mod 16) slots further: {0-3, 12-15} meets {4-11} + 4 = {8-15} in four
+//         slots -- 2-way, 8 LDS cycles per read instead of 4 (1296 floats = 324 slots = 4 (mod 16): the same).  Pitch
+//         68's channels were 704 floats = 0 (mod 16) slots apart and conflict-free.  That needs the two channels of a
+//         16-lane pair 0 (mod 64) floats apart: a 768-float slot, or channels (0, 1) and (2, 3) at distance 1472 with
+//         32 floats of pad per ring slot -- 2304 resp. 384 bytes that the upsampling forms do not have (they end at
+//         81 920 bytes exactly, see the static_assert);
+//       - read2: a 4-byte access at a lane stride of 16 bytes puts the 16 tiles of a channel on 8 of the 32 banks, and
+//         the half's second channel (720 = 16 (mod 32)) on the same 8: 4-way, 8 cycles per dword, 16 per instruction,
+//         whatever the pitch (the 8-byte read it replaces was 2-way by the same rule: 4 cycles).
+//       Per wave and interval 6 x (8 + 16) = 144 LDS cycles where pitch 68 took 6 x (4 + 4) = 48, in an interval of
+//       ~6500 cycles.  Measured on layer 18 + ToRGB (batch 64, same box and session, medians of five processes): this
+//       form 5.32 - 5.40 ms against the parent's 5.56 - 5.62; the outer columns as two 8-byte reads (-DW4_ROW3=1: 96
+//       cycles, three instructions per row) 5.38; from the neighbour lanes by DPP and one 4-byte read of the row's end
+//       columns (-DW4_ROW3=2: 60 cycles, twelve more vector instructions) 5.41; the padded pairs (-DW4_PAIRPAD=1, the
+//       forms with room: 120 cycles) 5.31 against 5.33 -- none outside the spread (0.1), so the two-instruction read and
+//       the unpadded slot stay.  Without any patch fetch (-DW4_ABL=2) the kernel takes 4.58 ms where the parent took
+//       4.26: 0.32 ms of the fetch's former 1.36 ms moved to the read side, 0.75 ms is still the fetch;
 //   * weights: `global_load_lds_dwordx4`, 18 one-KB pieces per interval dealt to the eight waves;
 //   * noise of a group: four dword pieces per wave into a wave-private strip, issued FIRST in the group's second-to-last
 //     interval, so the counted wait at the end of that interval retires them.
@@ -358,7 +386,33 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 // One workgroup of 512 threads per CU (117 KB of LDS): WGM = 2 out-channel blocks of 16 x WGN = 4 tile rows -- the
 // weights of an interval serve four waves, the patch halo is 2 rows in 18.
 // ---------------------------------------------------------------------------------------
-#define W4B_PITCH 68
+#define W4B_PITCH 72          // window columns x0 - 4 .. x0 + 67: 18 aligned 16-byte items per row
+#ifndef W4_PAIRPAD
+#define W4_PAIRPAD 0      // A/B builds: conflict-free 16-byte window reads in the forms whose LDS has room (CPAD in the body)
+#endif
+#ifndef W4_ROW3
+#define W4_ROW3 0         // A/B builds: the row's outer columns by 1 = two 8-byte reads, 2 = DPP from the neighbour lanes
+#endif
+// (both measured on layer 18 + ToRGB and left off: profiles/INDEX.md, r10b)
+// The six window columns of one tile in one row, as the three column pairs of the transform: rp = float 4 lt of the row,
+// the tile's columns are floats 3 .. 8.  One aligned 16-byte read of floats 4 .. 7 and one two-address read of 3 and 8.
+__device__ __forceinline__ void w4_row_read(const float* rp, rw_f32x2 (&c)[3], int eoff = 0) {
+  const rw_f32x4 mid = *reinterpret_cast<const rw_f32x4*>(rp + 4);
+#if W4_ROW3 == 2
+  // A/B build: the outer columns from the neighbour tiles' lanes (a DPP row is the 16 tiles of a channel); the row's two
+  // end columns, which no lane holds, by one 4-byte read per row (eoff: float 68 for the last tile, float 3 otherwise)
+  const int edge = __float_as_int(rp[eoff]);
+  const float e0 = __int_as_float(__builtin_amdgcn_update_dpp(edge, __float_as_int(mid[3]), 0x111, 0xf, 0xf, false));
+  const float e5 = __int_as_float(__builtin_amdgcn_update_dpp(edge, __float_as_int(mid[0]), 0x101, 0xf, 0xf, false));
+#elif W4_ROW3
+  const float e0 = (*reinterpret_cast<const rw_f32x2*>(rp + 2))[1], e5 = (*reinterpret_cast<const rw_f32x2*>(rp + 8))[0];
+#else
+  const float e0 = rp[3], e5 = rp[8];
+#endif
+  c[0] = rw_f32x2{e0, mid[0]};
+  c[1] = rw_f32x2{mid[1], mid[2]};
+  c[2] = rw_f32x2{mid[3], e5};
+}
 #ifndef W4_NTS
 #define W4_NTS 0          // non-temporal stores of the output map (A/B builds)
 #endif
@@ -491,11 +545,19 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   constexpr int WGM = 2;
   constexpr int WAVES = WGM * WGN, THREADS = 64 * WAVES;
   constexpr int PR = 4 * WGN + 2;                 // patch rows
-  constexpr int PIECES = (PR * W4B_PITCH + 63) / 64;      // 64-float pieces per channel
+  constexpr int IPR = W4B_PITCH / 4;              // 16-byte items per window row
+  constexpr int ITEMS = PR * IPR;                 // ... per channel: 180 / 324
+  constexpr int PIECES = (ITEMS + 63) / 64;       // 64-item (1 KB) pieces per channel: 3 / 6, the last one overlapping
+  static_assert(ITEMS >= 64, "the last piece starts at item ITEMS - 64");
+  constexpr int CSZ = PR * W4B_PITCH;             // floats per channel slot
   constexpr int PPW = 4 * PIECES / WAVES;         // patch pieces per wave and interval
   static_assert(4 * PIECES % WAVES == 0, "patch pieces divide among the waves");
   constexpr int UPW = (9 * WGM + WAVES - 1) / WAVES;      // weight pieces per wave and interval (at most)
-  constexpr int PSZ = 4 * PIECES * 64;            // floats per patch ring slot
+  // channels (0, 1) and (2, 3) of a ring slot a multiple of 64 floats apart (slot order 0, 2, pad, 1, 3), where the LDS has
+  // the 384 bytes: see the bank notes above the body
+  constexpr int CPAD = W4_PAIRPAD && !UP ? 64 - 2 * CSZ % 64 : 0;
+  constexpr int PSZ = 4 * CSZ + CPAD;             // floats per patch ring slot
+  auto chan_off = [](int c) __attribute__((always_inline)) { return CPAD ? (c & 1) * (2 * CSZ + CPAD) + (c >> 1) * CSZ : c * CSZ; };
   constexpr int USZ = WGM * 9 * 256;              // floats per weight ring slot
   __shared__ __attribute__((aligned(16))) float Ps[3 * PSZ];
   __shared__ __attribute__((aligned(16))) float Us[UDEPTH * USZ];
@@ -503,7 +565,12 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   __shared__ float St[512];
   __shared__ float Ct[2][16 * WGM];
   __shared__ float Cr[3][16 * WGM];
-  __shared__ float Red[WAVES];
+  // the workgroup reduction of the prologue borrows the noise strips, which nothing touches before the loop (the H16 upsampling
+  // form has not 16 bytes to spare)
+  float (&Red)[WAVES] = *reinterpret_cast<float (*)[WAVES]>(&Ns[0]);
+  // two 256-thread workgroups per CU: 80 KB each (Cr exists in the ToRGB forms only)
+  static_assert(THREADS != 256 || (3 * PSZ + UDEPTH * USZ + WAVES * NSZ + 512 + 2 * 16 * WGM + (RGB ? 3 * 16 * WGM : 0)) * 4 <= 81920,
+                "LDS of a 256-thread workgroup: two must stay resident per CU");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -563,29 +630,37 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   // patch pieces of this wave: flat pieces [wave * PPW, + PPW) of the 4 * PIECES of a k-quad (never across a channel)
   static_assert(PIECES % PPW == 0, "a wave's pieces lie in one channel");
   const int pch = (wave * PPW) / PIECES, piece0 = (wave * PPW) % PIECES;
+  // first item of this wave's piece s: 64 (piece0 + s), the channel's last piece pulled back to end with the window
+  auto piece_item0 = [&](int s) __attribute__((always_inline)) {
+    const int i0 = 64 * (piece0 + s);
+    return i0 < ITEMS - 64 ? i0 : ITEMS - 64;
+  };
   int xoff[PPW];
   auto set_group = [&](int g) __attribute__((always_inline)) {
     const int x0 = (gx0 + g) * 64;
 #pragma unroll
     for (int s = 0; s < PPW; ++s) {
-      const int f = 64 * (piece0 + s) + lane;
-      const int r = f / W4B_PITCH, c = f - r * W4B_PITCH;
-      const int iy = y0 - 1 + r, ix = x0 - 1 + c;
-      const bool ok = r < PR && c < W4_PC && iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
+      const int it = piece_item0(s) + lane;         // < ITEMS: a row of the window
+      const int r = it / IPR, ci = it - r * IPR;
+      const int iy = y0 - 1 + r, ix = x0 - 4 + 4 * ci;
+      // x0 and p.w are multiples of 64: an item lies wholly inside the image or wholly outside it
+      const bool ok = iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
       xoff[s] = ok ? (iy * p.w + ix) * 4 : 0x7fffffff;
     }
   };
   // the pieces of interval (group fg, k-quad fc) -> ring slot: all at once (prologue), or piece by piece from
-  // inside the MFMA loop -- a wave that issues its eleven loads in one burst sits in the issue stage while the
+  // inside the MFMA loop -- a wave that issues its loads in one burst sits in the issue stage while the
   // address unit works them off, with its MFMAs waiting behind
   int p_soff = 0;
   unsigned p_dst = 0;
   auto pload_begin = [&](int ring, int fg, int fc) __attribute__((always_inline)) {
     if (fc == 0) set_group(fg);
     p_soff = (4 * fc + pch) * hw4;
-    p_dst = ps_base + (unsigned)((ring * PSZ + pch * (PIECES * 64) + 64 * piece0) * 4);
+    p_dst = ps_base + (unsigned)((ring * PSZ + chan_off(pch)) * 4);
   };
-  auto pload_piece = [&](int s) __attribute__((always_inline)) { rw_dma_buffer_b32(p_dst + 256 * s, xoff[s], xsrc, p_soff); };
+  auto pload_piece = [&](int s) __attribute__((always_inline)) {
+    rw_dma_buffer_b128(p_dst + 16 * piece_item0(s), xoff[s], xsrc, p_soff);
+  };
   auto pload = [&](int ring, int fg, int fc) __attribute__((always_inline)) {
     pload_begin(ring, fg, fc);
 #pragma unroll
@@ -628,7 +703,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;                 // H16: max |result| of this lane -> p.y_amax
 
-  const int item_off = lk * (PIECES * 64) + (4 * wn) * W4B_PITCH + 4 * lt;
+  const int item_off = chan_off(lk) + (4 * wn) * W4B_PITCH + 4 * lt;
+  const int edge_off = lt == 15 ? 8 : 3 - 4 * lt;   // W4_ROW3 == 2 only (w4_row_read)
   auto compute = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
     constexpr bool SPREAD = decltype(spread_tag)::value != 0;
     const float* base = &Us[uring * USZ + wm * (9 * 256) + a_lane];
@@ -641,16 +717,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(src + r * W4B_PITCH);
-      if (STYLE) {
-        c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
-        c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
-        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4) * sv;
-      } else {
-        c2[r][0] = rw_f32x2{lo[0], lo[1]};
-        c2[r][1] = rw_f32x2{lo[2], lo[3]};
-        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4);
-      }
+      w4_row_read(src + r * W4B_PITCH, c2[r], edge_off);
+      if (STYLE) { c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv; }
     }
     float d[6][6];
 #pragma unroll
@@ -707,10 +775,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(src + r * W4B_PITCH);
-      c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
-      c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
-      c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4B_PITCH + 4) * sv;
+      w4_row_read(src + r * W4B_PITCH, c2[r], edge_off);
+      c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv;
     }
     rw_u32x2 aq[2][6];
     aread(ua, rw_int<0>(), aq[0][0]); aread(ua, rw_int<1>(), aq[0][1]); aread(ua, rw_int<2>(), aq[0][2]);
@@ -779,16 +845,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
       const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(rp);
-      if (STYLE) {
-        c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
-        c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
-        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4) * sv;
-      } else {
-        c2[r][0] = rw_f32x2{lo[0], lo[1]};
-        c2[r][1] = rw_f32x2{lo[2], lo[3]};
-        c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4);
-      }
+      w4_row_read(rp, c2[r], edge_off);
+      if (STYLE) { c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv; }
     }
     rw_f32x2 hrow[3][3];
 #pragma unroll
@@ -842,10 +900,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
       const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      const rw_f32x4 lo = *reinterpret_cast<const rw_f32x4*>(rp);
-      c2[r][0] = rw_f32x2{lo[0], lo[1]} * sv;
-      c2[r][1] = rw_f32x2{lo[2], lo[3]} * sv;
-      c2[r][2] = *reinterpret_cast<const rw_f32x2*>(rp + 4) * sv;
+      w4_row_read(rp, c2[r], edge_off);
+      c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv;
     }
     rw_f32x2 hrow[3][3];
 #pragma unroll
@@ -1371,6 +1427,9 @@ static bool wino4_shape_ok(int out_ch, int in_ch, int h, int w) {
   return out_ch > 0 && in_ch > 0 && out_ch % 32 == 0 && in_ch % 8 == 0 && w % 64 == 0 && h % 8 == 0;
 }
 
+// the window arrives in 16-byte items (conv_wino36b_body): with w % 64 == 0 every image and row starts where the map does
+static bool w4_window_aligned(const float* x) { return ((uintptr_t)x & 15) == 0; }
+
 extern "C" int rw_conv3x3_wino4_supported(int out_ch, int in_ch, int h, int w) {
   return wino4_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
@@ -1412,7 +1471,7 @@ static int conv3x3_wino4_launch(const float* x, const float* uf, float* y, int b
   RW_CHECK_ARG(x && uf && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
   RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
-  if (!wino4_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
+  if (!wino4_shape_ok(out_ch, in_ch, h, w) || !w4_window_aligned(x)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
   wino4_fill(p, x, uf, y, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
   const int o_tiles = out_ch / 32;
@@ -1532,7 +1591,7 @@ static int up_wino4_launch(const float* x, const float* uf, float* y, int batch,
   RW_CHECK_ARG(x && uf && y && batch > 0 && in_ch > 0 && out_ch > 0 && h > 0 && w > 0);
   RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
-  if (!up_wino4_shape_ok(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
+  if (!up_wino4_shape_ok(out_ch, in_ch, h, w) || !w4_window_aligned(x)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
   wino4_fill(p, x, uf, y, batch, in_ch, 4 * out_ch, h, w, w_scale, ep, u_inv, x_amax, y_amax);
   p.post = post_scale;
@@ -1611,7 +1670,7 @@ static int wino4_to_rgb_launch(const float* x, const float* uf, int batch, int i
   RW_CHECK_ARG(x && uf && rw_rgb_ok(rgb) && batch > 0 && in_ch > 0 && out_ch > 0);
   RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
-  if (!rw_conv3x3_wino4_to_rgb_supported(out_ch, in_ch, h, w)) return RW_ERR_UNSUPPORTED;
+  if (!rw_conv3x3_wino4_to_rgb_supported(out_ch, in_ch, h, w) || !w4_window_aligned(x)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
   wino4_fill(p, x, uf, nullptr, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, nullptr);
   rw_fill_rgb(p, rgb);
