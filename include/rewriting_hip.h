@@ -39,7 +39,9 @@ typedef void* rw_stream_t; /* hipStream_t */
  * by plain stores (no memset, no atomic, no device scalar that one launch raises and the next reads) and their weight
  * scale BY VALUE (rw_split_weight_scale); rw_publish_scalar_f32 is gone.  (3: rw_solve_run_*, the whole-image 8x8 / 4x4
  * shapes, the point order of the packed F(4x4,3x3) weights; 4: rw_*_wino4h_*; 5: rw_dconv*; 6: rw_publish_scalar_f32.)
- * Buffers packed by an older library do not fit this one: repack, as the Python side does per weight version. */
+ * Buffers packed by an older library do not fit this one: repack, as the Python side does per weight version.
+ * rw_resize_bilinear_u8 joins at 11, as rw_render_bytes_f32 and rw_png_* did: an entry that is only ADDED changes no
+ * existing call, and the loader names the missing symbol of a library built before it ("stale ... no symbol"). */
 int rw_abi_version(void);
 const char* rw_error_string(int code);
 
@@ -598,6 +600,39 @@ int rw_png_encode_u8(const uint8_t* stream, const uint32_t* table, uint8_t* code
                      int height, int width, rw_stream_t stream_);
 int rw_png_compact_u8(const uint8_t* coded, const uint32_t* lengths, const uint32_t* adler, uint64_t* offsets,
                       uint32_t* head, uint8_t* bytes, int64_t capacity, int64_t segments, rw_stream_t stream_);
+
+/* Tiles at the UI's size: the PIL.Image.resize(size, resample=BILINEAR) of renormalize.as_url(img, size=...)
+ * (utils/renormalize.py:22-32), byte for byte, for image (images, H, W, 3) uint8 -- what rw_render_bytes_f32 writes --
+ * into out (images, OH, OW, 3) uint8, which rw_png_filter_u8 reads.  Pillow's 8-bit resampler is integer arithmetic over
+ * fixed-point coefficients that the host computes in double (precompute_coeffs + normalize_coeffs_8bpc, bilinear filter,
+ * support 1).  For one axis of length n resized to m:
+ *   scale = n / m;  fs = max(scale, 1.0);  support = fs;  K = 2 * ceil(support) + 1
+ *   for o in 0 .. m - 1:
+ *     center = (o + 0.5) * scale
+ *     first  = max(int(center - support + 0.5), 0)
+ *     count  = min(int(center + support + 0.5), n) - first
+ *     w[j]   = tri((j + first - center + 0.5) * (1.0 / fs))  for j < count;   tri(v) = 1 - |v| if |v| < 1 else 0
+ *     w[j]  /= sum(w)                                         (if the sum is not 0)
+ *     k[j]   = int(0.5 + w[j] * 2^22)   (int(-0.5 + ...) for a negative w[j]);   k[j] = 0 for count <= j < K
+ *   out[o] = clamp((2^21 + sum_j k[j] * in[first + j]) >> 22, 0, 255)          (int32, arithmetic shift)
+ * All but the last line is IEEE double in this operation order, int() truncates toward zero, and it is the HOST's work
+ * (rewriting_amd/resample.py): the entry takes the tables, kx (OW, kx_width) / ky (OH, ky_width) int32 and bounds_x
+ * (OW, 2) / bounds_y (OH, 2) int32 = first, count, and applies the last line.  A picture is resized along x first, into
+ * scratch (images, H, OW, 3) uint8, rounded to bytes there, then along y into out: the rounding between the passes is
+ * part of the result.  An axis that keeps its length is not touched: its pass is skipped and its tables are not read
+ * (they and, unless both axes change, scratch may be NULL).  The three channels are independent.  The sum fits int32:
+ * 255 (2^22 + K / 2) + 2^21 < 2^31.  Two plain launches at most; no allocation, memset, atomic or stream drain; every
+ * byte of out has one writer, and a picture's bytes are the same alone or in a batch.
+ * The tables are signed and the shift is arithmetic (Pillow's other separable filters would go through unchanged), and
+ * the kernels never read outside the picture whatever the tables hold: count is clamped to 0 .. K, first and first + j
+ * to the axis, the sum wraps.  A wrong table gives a wrong picture, never a fault.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null image / out, a null table of an axis that changes or its width < 1, a
+ * null scratch when both axes change, images < 1, OH == H and OW == W (nothing to compute: the picture is the caller's),
+ * a grid past 31 bits.  RW_ERR_UNSUPPORTED (nothing launched): any extent < 1; a picture, resized picture or scratch
+ * picture of 2^31 bytes or more. */
+int rw_resize_bilinear_u8(const uint8_t* image, const int32_t* kx, const int32_t* bounds_x, const int32_t* ky,
+                          const int32_t* bounds_y, uint8_t* scratch, uint8_t* out, int64_t images, int height, int width,
+                          int out_height, int out_width, int kx_width, int ky_width, rw_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * The rank-constrained solve -- replaces the body of ProgressiveGanRewriter.insert

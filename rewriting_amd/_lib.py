@@ -104,6 +104,7 @@ SIGNATURES = {
     'rw_png_filter_u8': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_void_p]),
     'rw_png_encode_u8': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_void_p]),
     'rw_png_compact_u8': (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_void_p]),
+    'rw_resize_bilinear_u8': (c_int, [c_void_p] * 7 + [c_int64] + [c_int] * 6 + [c_void_p]),
     'rw_conv3x3_wino_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rw_packed_conv_weight_wino_elems': (ctypes.c_longlong, [c_int, c_int]),
     'rw_pack_conv_weight_wino_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

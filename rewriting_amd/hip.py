@@ -1006,6 +1006,50 @@ def render_bytes(images, activations=None, mask=None, level=None, thickness=1, b
     return out
 
 
+def _size(size):
+    """(width, height) of a `size` as PIL.Image.resize reads it: two positive integers"""
+    import operator
+    try:
+        width, height = (operator.index(v) for v in size if not isinstance(v, bool))
+    except (TypeError, ValueError):              # not a pair, not integers
+        width = height = 0
+    if width < 1 or height < 1:
+        raise RuntimeError('rewriting_amd: size is (width, height), two positive integers as PIL.Image.resize takes '
+                           'them, not %r' % (size,))
+    return width, height
+
+
+def resize_bytes(bytes_bhwc, size):
+    """(B, size[1], size[0], 3) uint8 on the device: ``PIL.Image.resize(size, resample=BILINEAR)`` of every picture of
+    bytes_bhwc (B, H, W, 3) uint8 -- what render_bytes returns, what png_encode takes -- byte for byte, on the current
+    stream (rw_resize_bilinear_u8 applies the tables of resample.coefficients: along x, rounded to bytes, then along y).
+    `size` is renormalize.as_url's: PIL reads it as (width, height).  size == (W, H) returns the input itself (PIL
+    copies; nothing is launched).  The input is read in place: a view that is not contiguous, a wrong dtype or device
+    is refused, never copied, and so is a size that is not two positive integers -- all before the library is touched."""
+    from . import resample
+    ow, oh = _size(size)
+    x = _in_place(bytes_bhwc, 'bytes', torch.uint8)
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise RuntimeError('rewriting_amd: resize_bytes takes bytes (B, H, W, 3), not %s' % (tuple(x.shape),))
+    b, h, w, _ = x.shape
+    if h < 1 or w < 1 or 3 * max(h * w, h * ow, oh * ow) >= 2 ** 31:
+        raise RuntimeError('rewriting_amd: resize_bytes takes pictures of at least 1 x 1 and below 2^31 bytes, before '
+                           'and after (RW_ERR_UNSUPPORTED, include/rewriting_hip.h), not %d x %d -> %d x %d'
+                           % (h, w, oh, ow))
+    if (ow, oh) == (w, h):
+        return bytes_bhwc
+    out = torch.empty(b, oh, ow, 3, device=x.device, dtype=torch.uint8)
+    if b == 0:
+        return out
+    kx, bounds_x = resample.device_coefficients(w, ow, x.device) if ow != w else (None, None)
+    ky, bounds_y = resample.device_coefficients(h, oh, x.device) if oh != h else (None, None)
+    scratch = torch.empty(b, h, ow, 3, device=x.device, dtype=torch.uint8) if ow != w and oh != h else None
+    check(lib().rw_resize_bilinear_u8(_p(x), _p(kx), _p(bounds_x), _p(ky), _p(bounds_y), _p(scratch), _p(out), b, h, w,
+                                      oh, ow, 0 if kx is None else kx.shape[1], 0 if ky is None else ky.shape[1],
+                                      _stream()))
+    return out
+
+
 def png_segment_bytes():
     """Stream bytes per deflate block of png_encode (rw_png_segment_bytes)"""
     return int(lib().rw_png_segment_bytes())

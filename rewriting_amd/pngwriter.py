@@ -7,7 +7,8 @@ metrics/make_watermark_images.py:99-131 -- goes through ``hip.render_bytes`` and
 the filters and the Huffman coding run in kernels, the host frames the chunks and writes the files.  The files are
 lossless and decode to exactly ``renormalize.as_image``'s pixels; they are coded with literals only (no LZ77 matches),
 so photographic pictures come out about the size of PIL's default and flat pictures larger.
-``as_url(size=...)``'s PIL resize has no counterpart here: resize first.
+``as_url(size=...)``'s PIL resize (BILINEAR) is ``hip.resize_bytes`` between the two, byte for byte: ``size`` below is
+that ``size``, (width, height) as PIL reads it; the coder then works on the resized bytes.
 """
 import base64
 import collections
@@ -19,19 +20,21 @@ from . import hip, samples
 MAX_WRITERS = 16          # file-writing threads; never sized from os.cpu_count() (a shared machine shows all its CPUs)
 
 
-def encode(images, **overlay_kwargs):
+def encode(images, size=None, **overlay_kwargs):
     """One PNG file (bytes) per image of images (B, 3, H, W) float32 on the device, in the generator's range; the
-    overlay_kwargs are hip.render_bytes's (activations / mask, level, thickness, colours)."""
-    return hip.png_encode(hip.render_bytes(images, **overlay_kwargs))
+    overlay_kwargs are hip.render_bytes's (activations / mask, level, thickness, colours).  size (width, height):
+    the pictures are resized as PIL.Image.resize(size, BILINEAR) does, on the device, before they are coded."""
+    tiles = hip.render_bytes(images, **overlay_kwargs)
+    return hip.png_encode(tiles if size is None else hip.resize_bytes(tiles, size))
 
 
 def as_url(png):
     return 'data:image/png;base64,%s' % base64.b64encode(png).decode('utf-8')
 
 
-def as_urls(images, **overlay_kwargs):
-    """``[renormalize.as_url(img) for img in images]`` for a batch on the device (no ``size``: resize first)"""
-    return [as_url(png) for png in encode(images, **overlay_kwargs)]
+def as_urls(images, size=None, **overlay_kwargs):
+    """``[renormalize.as_url(img, size=size) for img in images]`` for a batch on the device"""
+    return [as_url(png) for png in encode(images, size=size, **overlay_kwargs)]
 
 
 def _write(path, make):

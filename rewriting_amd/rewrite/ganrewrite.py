@@ -671,14 +671,19 @@ class ProgressiveGanRewriter(object):
         with torch.no_grad():
             return self._response(self._key_map(z), key.to(self.device))
 
-    def render_image(self, imgnum, key=None, level=None, mask=None, **kwargs):
+    def _picture_of(self, imgnum, key, level, mask, **kwargs):
+        """_pictures of the one image render_image shows: under the key's heat map where there is a key and a level,
+        else inside `mask`, else plain"""
         with torch.no_grad():
             z = self.get_z(imgnum)
             imgdata = self.rendered_image(self.sample_image_from_latent(z))
         heatmap = self._heat(z, key, level)
         if heatmap is not None:
-            return self._pictures(imgdata, heatmap, level, **kwargs)[0]
-        return self._pictures(imgdata, mask=mask, **kwargs)[0]
+            return self._pictures(imgdata, heatmap, level, **kwargs)
+        return self._pictures(imgdata, mask=mask, **kwargs)
+
+    def render_image(self, imgnum, key=None, level=None, mask=None, **kwargs):
+        return self._picture_of(imgnum, key, level, mask, **kwargs)[0]
 
     def render_image_batch(self, imgnums, key=None, level=None, **kwargs):
         """Batches of three, as the reference renders them (rewrite/ganrewrite.py:626-650): an image's noise row is
@@ -700,20 +705,34 @@ class ProgressiveGanRewriter(object):
             parts.append(self._pictures(batch, self._heat(zb, key, level), level, as_bytes=True, **kwargs))
         return parts
 
-    def render_urls(self, imgnums, key=None, level=None, **kwargs):
-        """The data URLs (``renormalize.as_url``) of the pictures render_image_batch shows, with the bytes AND the PNG
-        files built on the device (hip.render_bytes, hip.png_encode): one coded buffer comes to the host instead of
-        twelve pictures for twelve PIL saves.  Needs the device overlay route (device_render=True, the model on the
-        device, an overlay the kernel takes); there is no host fall-back -- render_image_batch + as_url is that."""
+    def _urls(self, parts, size, caller):
+        """The data URLs of bytes on the device (a list of (B, H, W, 3) tensors): hip.resize_bytes where a size is asked
+        for, then hip.png_encode.  PIL pictures -- the host route built them -- are refused."""
         from .. import pngwriter
-        parts = self._picture_batches(imgnums, key, level, **kwargs)
         if not parts:
             return []
         if not torch.is_tensor(parts[0]):
-            raise RuntimeError('rewriting_amd: render_urls needs the device overlay route (device_render=True, the model '
+            raise RuntimeError('rewriting_amd: %s needs the device overlay route (device_render=True, the model '
                                'on a HIP device, an overlay hip.render_bytes takes); use render_image_batch and '
-                               'renormalize.as_url on the host')
-        return [pngwriter.as_url(png) for png in hip.png_encode(torch.cat(parts))]
+                               'renormalize.as_url on the host' % caller)
+        tiles = torch.cat(parts)
+        if size is not None:
+            tiles = hip.resize_bytes(tiles, size)
+        return [pngwriter.as_url(png) for png in hip.png_encode(tiles)]
+
+    def render_urls(self, imgnums, key=None, level=None, size=None, **kwargs):
+        """The data URLs (``renormalize.as_url``) of the pictures render_image_batch shows, with the bytes AND the PNG
+        files built on the device (hip.render_bytes, hip.png_encode): one coded buffer comes to the host instead of
+        twelve pictures for twelve PIL saves.  size: as_url's ``size`` -- (width, height) as PIL reads it; the app passes
+        (canvas.height, canvas.width) -- resizes the pictures as PIL.Image.resize(size, BILINEAR) does, on the device
+        (hip.resize_bytes), before they are coded.  Needs the device overlay route (device_render=True, the model on the
+        device, an overlay the kernel takes); there is no host fall-back -- render_image_batch + as_url is that."""
+        return self._urls(self._picture_batches(imgnums, key, level, **kwargs), size, 'render_urls')
+
+    def render_url(self, imgnum, key=None, level=None, mask=None, size=None, **kwargs):
+        """render_urls for the one picture render_image shows (the copy, paste and key-tray canvases), with
+        render_image's arguments.  The same route, the same error."""
+        return self._urls([self._picture_of(imgnum, key, level, mask, as_bytes=True, **kwargs)], size, 'render_url')[0]
 
 
 class SeqStyleGanRewriter(ProgressiveGanRewriter):
