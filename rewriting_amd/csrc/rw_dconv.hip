@@ -1082,8 +1082,11 @@ static bool dconv_shape_ok(int out_ch, int in_ch, int h, int w) {
 
 extern "C" int rw_dconv3x3_supported(int out_ch, int in_ch, int h, int w) { return dconv_shape_ok(out_ch, in_ch, h, w) ? 1 : 0; }
 
+// the channel counts both packings (the plain one and the four phases of the transposed convolution) exist for
+static bool dconv_packs(int out_ch, int in_ch) { return out_ch % 16 == 0 && in_ch % 16 == 0; }
+
 extern "C" long long rw_packed_dconv_weight_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 16) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !dconv_packs(out_ch, in_ch)) return -1;
   return 9LL * out_ch * in_ch + 4;
 }
 
@@ -1108,13 +1111,13 @@ static int dconv_pack(const float* w, const float* k4, float* wp, int vch, int i
 
 extern "C" int rw_dconv_weight_absmax_f32(const float* w, int out_ch, int in_ch, float* bound, rw_stream_t stream) {
   RW_CHECK_ARG(w && bound && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 16) return RW_ERR_UNSUPPORTED;
+  if (!dconv_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   return dconv_absmax<false>(w, nullptr, out_ch, in_ch, bound, stream);
 }
 
 extern "C" int rw_pack_dconv_weight_f32(const float* w, float* wp, int out_ch, int in_ch, float u_scale, rw_stream_t stream) {
   RW_CHECK_ARG(w && wp && out_ch > 0 && in_ch > 0 && u_scale > 0.f);
-  if (out_ch % 16 || in_ch % 16) return RW_ERR_UNSUPPORTED;
+  if (!dconv_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   return dconv_pack<false>(w, nullptr, wp, out_ch, in_ch, u_scale, stream);
 }
 
@@ -1197,19 +1200,19 @@ extern "C" int rw_dconv_transpose_blur_supported(int out_ch, int in_ch, int h, i
   return dconv_up_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
 extern "C" long long rw_packed_dconv_transpose_blur_weight_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 16) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !dconv_packs(out_ch, in_ch)) return -1;
   return 36LL * out_ch * in_ch + 4;
 }
 extern "C" int rw_dconv_transpose_blur_weight_absmax_f32(const float* w, const float* k4, int out_ch, int in_ch,
                                                          float* bound, rw_stream_t stream) {
   RW_CHECK_ARG(w && k4 && bound && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 16) return RW_ERR_UNSUPPORTED;
+  if (!dconv_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   return dconv_absmax<true>(w, k4, 4 * out_ch, in_ch, bound, stream);
 }
 extern "C" int rw_pack_dconv_transpose_blur_weight_f32(const float* w, const float* k4, float* wp, int out_ch, int in_ch,
                                                        float u_scale, rw_stream_t stream) {
   RW_CHECK_ARG(w && k4 && wp && out_ch > 0 && in_ch > 0 && u_scale > 0.f);
-  if (out_ch % 16 || in_ch % 16) return RW_ERR_UNSUPPORTED;
+  if (!dconv_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   return dconv_pack<true>(w, k4, wp, 4 * out_ch, in_ch, u_scale, stream);
 }
 extern "C" int rw_dconv_transpose3x3s2_blur_f32(const float* x, const float* wp, float* y, int batch, int in_ch, int out_ch,

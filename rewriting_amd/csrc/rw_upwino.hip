@@ -535,14 +535,17 @@ extern "C" int rw_conv_transpose3x3s2_wino_supported(int out_ch, int in_ch, int 
   return up_wino_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
 
+// the channel counts the fp32 packing exists for
+static bool up_wino_packs(int out_ch, int in_ch) { return out_ch % 16 == 0 && in_ch % 4 == 0; }
+
 extern "C" long long rw_packed_conv_transpose_wino_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 4) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !up_wino_packs(out_ch, in_ch)) return -1;
   return 28LL * out_ch * in_ch;
 }
 
 extern "C" int rw_pack_conv_transpose_wino_f32(const float* w, float* uf, int out_ch, int in_ch, rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 4) return RW_ERR_UNSUPPORTED;
+  if (!up_wino_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)out_ch * in_ch;
   hipLaunchKernelGGL(pack_up_wino_kernel, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, uf, out_ch,
                      in_ch);
@@ -592,30 +595,34 @@ extern "C" int rw_conv_transpose3x3s2_winoh_supported(int out_ch, int in_ch, int
   return up_wino_shape_ok(out_ch, in_ch, h, w) && w % 32 == 0 && h % 4 == 0 ? 1 : 0;
 }
 
+// the channel counts the H16 packing exists for: one thread packs a pair of in-channels of one out-channel
+static bool up_winoh_packs(int out_ch, int in_ch) { return out_ch % 16 == 0 && in_ch % 8 == 0; }
+
+// one pass of pack_up_winoh_kernel (PASS 1: max |U| into bound, which is then finished; PASS 2: the f16 pairs into uf)
+template <int PASS>
+static int up_winoh_pack(const float* w, float* uf, int out_ch, int in_ch, float su, float* bound, rw_stream_t stream) {
+  const int grid = rw_stream_grid((int64_t)out_ch * (in_ch >> 1), 256);
+  hipLaunchKernelGGL(pack_up_winoh_kernel<PASS>, dim3(grid), dim3(256), 0, rw_s(stream), w, uf, out_ch, in_ch, su, bound);
+  return rw_finish_bound(bound, grid, stream);
+}
+
 extern "C" long long rw_packed_conv_transpose_winoh_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 8) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !up_winoh_packs(out_ch, in_ch)) return -1;
   return 16LL * out_ch * in_ch + 4;
 }
 
 extern "C" int rw_conv_transpose_weight_winoh_absmax_f32(const float* w, int out_ch, int in_ch, float* bound,
                                                          rw_stream_t stream) {
   RW_CHECK_ARG(w && bound && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 8) return RW_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)out_ch * (in_ch >> 1);
-  const int grid = rw_stream_grid(total, 256);
-  hipLaunchKernelGGL(pack_up_winoh_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, (float*)nullptr, out_ch, in_ch, 1.f,
-                     bound);
-  return rw_finish_bound(bound, grid, stream);
+  if (!up_winoh_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return up_winoh_pack<1>(w, nullptr, out_ch, in_ch, 1.f, bound, stream);
 }
 
 extern "C" int rw_pack_conv_transpose_winoh_f32(const float* w, float* uf, int out_ch, int in_ch, float u_scale,
                                                 rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0 && u_scale > 0.f);
-  if (out_ch % 16 || in_ch % 8) return RW_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)out_ch * (in_ch >> 1);
-  hipLaunchKernelGGL(pack_up_winoh_kernel<2>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, uf,
-                     out_ch, in_ch, u_scale, (float*)nullptr);
-  return RW_LAUNCH_RESULT();
+  if (!up_winoh_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return up_winoh_pack<2>(w, uf, out_ch, in_ch, u_scale, nullptr, stream);
 }
 
 extern "C" int rw_conv_transpose3x3s2_winoh_f32(const float* x, const float* uf, float* y, int batch, int in_ch,

@@ -523,14 +523,17 @@ extern "C" int rw_conv3x3_wino_supported(int out_ch, int in_ch, int h, int w) {
   return wino_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
 
+// the channel counts the packing exists for: whole 32-out-channel tiles of whole in-channel quads (a lane's i = 4 (i/4) + lane / 16)
+static bool wino_packs(int out_ch, int in_ch) { return out_ch % 32 == 0 && in_ch % 4 == 0; }
+
 extern "C" long long rw_packed_conv_weight_wino_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 32 || in_ch % 2) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !wino_packs(out_ch, in_ch)) return -1;
   return 16LL * out_ch * in_ch;
 }
 
 extern "C" int rw_pack_conv_weight_wino_f32(const float* w, float* uf, int out_ch, int in_ch, rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0);
-  if (out_ch % 32 || in_ch % 4) return RW_ERR_UNSUPPORTED;
+  if (!wino_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)out_ch * in_ch;
   hipLaunchKernelGGL(pack_wino16_kernel, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, uf, out_ch,
                      in_ch);

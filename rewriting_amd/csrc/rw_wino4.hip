@@ -1434,18 +1434,26 @@ extern "C" int rw_conv3x3_wino4_supported(int out_ch, int in_ch, int h, int w) {
   return wino4_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
 
+// the channel counts the packing (fp32 and H16) exists for
+static bool wino4_packs(int out_ch, int in_ch) { return out_ch % 16 == 0 && in_ch % 4 == 0; }
+
+// one pass of pack_wino36_kernel over the out_ch x in_ch filters (PASS 1: then the bound is finished)
+template <int PASS>
+static int wino4_pack(const float* w, float* uf, int out_ch, int in_ch, float su, float* bound, rw_stream_t stream) {
+  const int grid = rw_stream_grid((int64_t)out_ch * in_ch, 256);
+  hipLaunchKernelGGL(pack_wino36_kernel<PASS>, dim3(grid), dim3(256), 0, rw_s(stream), w, uf, out_ch, in_ch, su, bound);
+  return rw_finish_bound(bound, grid, stream);
+}
+
 extern "C" long long rw_packed_conv_weight_wino4_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 4) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !wino4_packs(out_ch, in_ch)) return -1;
   return 36LL * out_ch * in_ch;
 }
 
 extern "C" int rw_pack_conv_weight_wino4_f32(const float* w, float* uf, int out_ch, int in_ch, rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)out_ch * in_ch;
-  hipLaunchKernelGGL(pack_wino36_kernel<0>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, uf, out_ch,
-                     in_ch, 1.f, (float*)nullptr);
-  return RW_LAUNCH_RESULT();
+  if (!wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return wino4_pack<0>(w, uf, out_ch, in_ch, 1.f, nullptr, stream);
 }
 
 // whole rows where the launch still has >= 1024 workgroups: +1.5 % over 4
@@ -1527,28 +1535,21 @@ extern "C" int rw_conv3x3_wino4_f32(const float* x, const float* uf, float* y, i
 
 // ---- H16: the same operations with the products on the 16-bit matrix pipe (exact operand split, fp32 accumulation)
 extern "C" long long rw_packed_conv_weight_wino4h_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 16 || in_ch % 4) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !wino4_packs(out_ch, in_ch)) return -1;
   return 36LL * out_ch * in_ch + 4;
 }
 
 extern "C" int rw_conv_weight_wino4h_absmax_f32(const float* w, int out_ch, int in_ch, float* bound, rw_stream_t stream) {
   RW_CHECK_ARG(w && bound && out_ch > 0 && in_ch > 0);
-  if (out_ch % 16 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)out_ch * in_ch;
-  const int grid = rw_stream_grid(total, 256);
-  hipLaunchKernelGGL(pack_wino36_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, (float*)nullptr, out_ch, in_ch, 1.f,
-                     bound);
-  return rw_finish_bound(bound, grid, stream);
+  if (!wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return wino4_pack<1>(w, nullptr, out_ch, in_ch, 1.f, bound, stream);
 }
 
 extern "C" int rw_pack_conv_weight_wino4h_f32(const float* w, float* uf, int out_ch, int in_ch, float u_scale,
                                               rw_stream_t stream) {
   RW_CHECK_ARG(w && uf && out_ch > 0 && in_ch > 0 && u_scale > 0.f);
-  if (out_ch % 16 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)out_ch * in_ch;
-  hipLaunchKernelGGL(pack_wino36_kernel<2>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, uf, out_ch,
-                     in_ch, u_scale, (float*)nullptr);
-  return RW_LAUNCH_RESULT();
+  if (!wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return wino4_pack<2>(w, uf, out_ch, in_ch, u_scale, nullptr, stream);
 }
 
 extern "C" int rw_conv3x3_wino4h_f32(const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch, int h,
@@ -1570,19 +1571,29 @@ extern "C" int rw_conv_transpose_blur_wino4_supported(int out_ch, int in_ch, int
   return up_wino4_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;
 }
 
+// the channel counts the phase packing (fp32 and H16) exists for
+static bool up_wino4_packs(int out_ch, int in_ch) { return out_ch % 4 == 0 && in_ch % 4 == 0; }
+
+// one pass of pack_up_wino36_kernel over the 4 out_ch x in_ch phase filters (PASS 1: then the bound is finished)
+template <int PASS>
+static int up_wino4_pack(const float* w, const float* k4, float* uf, int out_ch, int in_ch, float su, float* bound,
+                         rw_stream_t stream) {
+  const int grid = rw_stream_grid(4LL * out_ch * in_ch, 256);
+  hipLaunchKernelGGL(pack_up_wino36_kernel<PASS>, dim3(grid), dim3(256), 0, rw_s(stream), w, k4, uf, out_ch, in_ch, su,
+                     bound);
+  return rw_finish_bound(bound, grid, stream);
+}
+
 extern "C" long long rw_packed_conv_transpose_blur_wino4_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 4 || in_ch % 4) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !up_wino4_packs(out_ch, in_ch)) return -1;
   return 144LL * out_ch * in_ch;
 }
 
 extern "C" int rw_pack_conv_transpose_blur_weight_wino4_f32(const float* w, const float* k4, float* uf, int out_ch,
                                                             int in_ch, rw_stream_t stream) {
   RW_CHECK_ARG(w && k4 && uf && out_ch > 0 && in_ch > 0);
-  if (out_ch % 4 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = 4LL * out_ch * in_ch;
-  hipLaunchKernelGGL(pack_up_wino36_kernel<0>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, k4, uf,
-                     out_ch, in_ch, 1.f, (float*)nullptr);
-  return RW_LAUNCH_RESULT();
+  if (!up_wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return up_wino4_pack<0>(w, k4, uf, out_ch, in_ch, 1.f, nullptr, stream);
 }
 
 static int up_wino4_launch(const float* x, const float* uf, float* y, int batch, int in_ch, int out_ch, int h, int w,
@@ -1624,29 +1635,22 @@ extern "C" int rw_conv_transpose3x3s2_blur_wino4_f32(const float* x, const float
 }
 
 extern "C" long long rw_packed_conv_transpose_blur_wino4h_elems(int out_ch, int in_ch) {
-  if (out_ch <= 0 || in_ch <= 0 || out_ch % 4 || in_ch % 4) return -1;
+  if (out_ch <= 0 || in_ch <= 0 || !up_wino4_packs(out_ch, in_ch)) return -1;
   return 144LL * out_ch * in_ch + 4;
 }
 
 extern "C" int rw_conv_transpose_blur_weight_wino4h_absmax_f32(const float* w, const float* k4, int out_ch, int in_ch,
                                                                float* bound, rw_stream_t stream) {
   RW_CHECK_ARG(w && k4 && bound && out_ch > 0 && in_ch > 0);
-  if (out_ch % 4 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = 4LL * out_ch * in_ch;
-  const int grid = rw_stream_grid(total, 256);
-  hipLaunchKernelGGL(pack_up_wino36_kernel<1>, dim3(grid), dim3(256), 0, rw_s(stream), w, k4, (float*)nullptr, out_ch, in_ch,
-                     1.f, bound);
-  return rw_finish_bound(bound, grid, stream);
+  if (!up_wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return up_wino4_pack<1>(w, k4, nullptr, out_ch, in_ch, 1.f, bound, stream);
 }
 
 extern "C" int rw_pack_conv_transpose_blur_weight_wino4h_f32(const float* w, const float* k4, float* uf, int out_ch,
                                                              int in_ch, float u_scale, rw_stream_t stream) {
   RW_CHECK_ARG(w && k4 && uf && out_ch > 0 && in_ch > 0 && u_scale > 0.f);
-  if (out_ch % 4 || in_ch % 4) return RW_ERR_UNSUPPORTED;
-  const int64_t total = 4LL * out_ch * in_ch;
-  hipLaunchKernelGGL(pack_up_wino36_kernel<2>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, k4, uf,
-                     out_ch, in_ch, u_scale, (float*)nullptr);
-  return RW_LAUNCH_RESULT();
+  if (!up_wino4_packs(out_ch, in_ch)) return RW_ERR_UNSUPPORTED;
+  return up_wino4_pack<2>(w, k4, uf, out_ch, in_ch, u_scale, nullptr, stream);
 }
 
 extern "C" int rw_conv_transpose3x3s2_blur_wino4h_f32(const float* x, const float* uf, float* y, int batch, int in_ch,

@@ -8,6 +8,7 @@ float64; the _f64 wrappers of the generator's forward at the end of this file: f
 else raises (no CPU path).
 """
 import ctypes
+from collections import namedtuple as _namedtuple
 
 import torch
 
@@ -40,8 +41,8 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def _opt(t, name):
-    return None if t is None else _dev(t, name)
+def _opt(t, name, dtype=torch.float32):
+    return None if t is None else _dev(t, name, dtype)
 
 
 def lib():
@@ -148,210 +149,174 @@ def upfirdn2d_major_f64(x, k, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
 
 
 # ------------------------------------------------------------------ generator pieces
-def pixel_norm(x, eps=1e-8):
-    x = _dev(x, 'latent')
+# The glue ops run in float32 and in float64 (the _f64 names at the end of this file): one body per op takes the dtype,
+# which every tensor operand must have -- nothing is converted -- as the three L1 ops above do.
+def _entry(op, dtype):
+    return getattr(lib(), 'rw_%s_%s' % (op, _ABI_SUFFIX[dtype]))
+
+
+def _pixel_norm_as(dtype, x, eps):
+    x = _dev(x, 'latent', dtype)
     y = torch.empty_like(x)
-    check(lib().rw_pixel_norm_f32(_p(x), _p(y), x.shape[0], x.shape[1], eps, _stream()))
+    check(_entry('pixel_norm', dtype)(_p(x), _p(y), x.shape[0], x.shape[1], float(eps), _stream()))
     return y
+
+
+def _equal_linear_as(dtype, x, weight, bias, w_scale, b_scale, act, alpha, act_scale):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != dtype:
+        _dev(x, 'input', dtype)                 # raises
+    x = x.detach()
+    if x.ndim != 2 or x.stride(1) != 1:
+        x = x.reshape(x.shape[0], -1).contiguous()
+    weight = _dev(weight, 'weight', dtype)
+    bias = _opt(bias, 'bias', dtype)
+    batch, in_dim = x.shape
+    out_dim = weight.shape[0]
+    if weight.shape[1] != in_dim:
+        raise ValueError('weight is %s, the input has %d features' % (tuple(weight.shape), in_dim))
+    y = torch.empty(batch, out_dim, device=x.device, dtype=dtype)
+    x_stride = x.stride(0) if batch > 1 else in_dim
+    check(_entry('equal_linear', dtype)(_p(x), _p(weight), _p(bias), _p(y), batch, in_dim, out_dim,
+                                        max(x_stride, in_dim), float(w_scale), float(b_scale), int(bool(act)),
+                                        float(alpha), float(act_scale), _stream()))
+    return y
+
+
+def _adjust_latent_as(dtype, w, avg, n_latent, psi):
+    w = _dev(w, 'latent', dtype)
+    avg = _opt(avg, 'latent_avg', dtype)
+    out = torch.empty(w.shape[0], n_latent, w.shape[1], device=w.device, dtype=dtype)
+    check(_entry('adjust_latent', dtype)(_p(w), _p(avg), _p(out), w.shape[0], n_latent, w.shape[1], float(psi),
+                                         _stream()))
+    return out
+
+
+def _style_mul_as(dtype, x, style):
+    x = _dev(x, 'fmap', dtype)
+    style = _dev(style, 'style', dtype)
+    b, c, h, w = x.shape
+    if tuple(style.shape) != (b, c):
+        raise ValueError('style must be batch x channels')
+    y = torch.empty_like(x)
+    check(_entry('style_mul', dtype)(_p(x), _p(style), _p(y), b, c, h * w, _stream()))
+    return y
+
+
+def _weight_sqsum_as(dtype, weight, w_scale):
+    weight = _dev(weight, 'weight', dtype)
+    o, i = weight.shape[-4], weight.shape[-3]
+    taps = weight.shape[-1] * weight.shape[-2]
+    wsq = torch.empty(o, i, device=weight.device, dtype=dtype)
+    check(_entry('weight_sqsum', dtype)(_p(weight), _p(wsq), o, i, taps, float(w_scale), _stream()))
+    return wsq
+
+
+def _demod_as(dtype, wsq, style, eps):
+    wsq = _dev(wsq, 'wsq', dtype)
+    style = _dev(style, 'style', dtype)
+    b = style.shape[0]
+    o, i = wsq.shape
+    if style.shape[1] != i:
+        raise ValueError('style must be batch x in_ch')
+    out = torch.empty(b, o, device=wsq.device, dtype=dtype)
+    check(_entry('demod', dtype)(_p(wsq), _p(style), _p(out), b, o, i, float(eps), _stream()))
+    return out
+
+
+def _noise_add_as(dtype, x, noise, noise_w):
+    x = _dev(x, 'fmap', dtype)
+    noise = _dev(noise, 'noise', dtype)
+    noise_w = _dev(noise_w, 'noise weight', dtype)
+    b, c, h, w = x.shape
+    if noise.numel() != b * h * w:
+        raise ValueError('noise must be batch x (height * width)')
+    y = torch.empty_like(x)
+    check(_entry('noise_add', dtype)(_p(x), _p(noise), _p(noise_w), _p(y), b, c, h * w, _stream()))
+    return y
+
+
+def _to_rgb_as(dtype, x, weight, style, bias, skip, w_scale):
+    x = _dev(x, 'fmap', dtype)
+    weight = _dev(weight, 'rgb weight', dtype)
+    style = _dev(style, 'style', dtype)
+    bias = _opt(bias, 'bias', dtype)
+    skip = _opt(skip, 'skip', dtype)
+    b, c, h, w = x.shape
+    if weight.numel() != 3 * c or tuple(style.shape) != (b, c):
+        raise ValueError('rgb weight / style shapes')
+    if skip is not None and tuple(skip.shape) != (b, 3, h, w):
+        raise ValueError('skip shape')
+    y = torch.empty(b, 3, h, w, device=x.device, dtype=dtype)
+    check(_entry('to_rgb', dtype)(_p(x), _p(weight), _p(style), _p(bias), _p(skip), _p(y), b, c, h * w, float(w_scale),
+                                  _stream()))
+    return y
+
+
+def pixel_norm(x, eps=1e-8):
+    return _pixel_norm_as(torch.float32, x, eps)
 
 
 def equal_linear(x, weight, bias, w_scale, b_scale, act=False, alpha=0.2, act_scale=SQRT2):
     """x may be a strided row view (latent[:, index]): last dim contiguous."""
-    if not x.is_cuda:
-        _dev(x, 'input')
-    x = x.detach()
-    if x.dtype != torch.float32 or x.ndim != 2 or x.stride(1) != 1:
-        x = _dev(x.reshape(x.shape[0], -1), 'input')
-    weight = _dev(weight, 'weight')
-    bias = _opt(bias, 'bias')
-    batch, in_dim = x.shape
-    out_dim = weight.shape[0]
-    y = torch.empty(batch, out_dim, device=x.device, dtype=torch.float32)
-    x_stride = x.stride(0) if batch > 1 else in_dim
-    check(lib().rw_equal_linear_f32(_p(x), _p(weight), _p(bias), _p(y), batch, in_dim, out_dim,
-                                    max(x_stride, in_dim), float(w_scale), float(b_scale), int(bool(act)),
-                                    float(alpha), float(act_scale), _stream()))
-    return y
+    return _equal_linear_as(torch.float32, x, weight, bias, w_scale, b_scale, act, alpha, act_scale)
 
 
 def adjust_latent(w, avg, n_latent, psi):
-    w = _dev(w, 'latent')
-    avg = _opt(avg, 'latent_avg')
-    out = torch.empty(w.shape[0], n_latent, w.shape[1], device=w.device, dtype=w.dtype)
-    check(lib().rw_adjust_latent_f32(_p(w), _p(avg), _p(out), w.shape[0], n_latent, w.shape[1],
-                                     float(psi), _stream()))
-    return out
+    return _adjust_latent_as(torch.float32, w, avg, n_latent, psi)
 
 
 def style_mul(x, style):
-    x = _dev(x, 'fmap')
-    style = _dev(style, 'style')
-    b, c, h, w = x.shape
-    y = torch.empty_like(x)
-    check(lib().rw_style_mul_f32(_p(x), _p(style), _p(y), b, c, h * w, _stream()))
-    return y
+    return _style_mul_as(torch.float32, x, style)
 
 
 def weight_sqsum(weight, w_scale):
-    weight = _dev(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    taps = weight.shape[-1] * weight.shape[-2]
-    wsq = torch.empty(o, i, device=weight.device, dtype=weight.dtype)
-    check(lib().rw_weight_sqsum_f32(_p(weight), _p(wsq), o, i, taps, float(w_scale), _stream()))
-    return wsq
+    return _weight_sqsum_as(torch.float32, weight, w_scale)
 
 
 def demod(wsq, style, eps=1e-8):
-    wsq = _dev(wsq, 'wsq')
-    style = _dev(style, 'style')
-    b = style.shape[0]
-    o, i = wsq.shape
-    out = torch.empty(b, o, device=wsq.device, dtype=wsq.dtype)
-    check(lib().rw_demod_f32(_p(wsq), _p(style), _p(out), b, o, i, float(eps), _stream()))
-    return out
+    return _demod_as(torch.float32, wsq, style, eps)
 
 
-def pack_conv_weight(weight, mode):
-    weight = _dev(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = lib().rw_packed_conv_weight_elems(o, i, int(mode))
-    if n <= 0:
-        raise ValueError('bad weight shape / mode')
-    wp = torch.empty(n, device=weight.device, dtype=weight.dtype)   # slab order, then fragment order
-    check(lib().rw_pack_conv_weight_f32(_p(weight), _p(wp), o, i, int(mode), _stream()))
-    return wp
+def noise_add(x, noise, noise_w):
+    return _noise_add_as(torch.float32, x, noise, noise_w)
 
 
-def _check_packed(wp, out_ch, in_ch, mode):
-    if wp.numel() != lib().rw_packed_conv_weight_elems(out_ch, in_ch, mode):
-        raise ValueError('packed weight does not come from pack_conv_weight(%d x %d, mode %d)'
-                         % (out_ch, in_ch, mode))
+def to_rgb(x, weight, style, bias, skip, w_scale):
+    return _to_rgb_as(torch.float32, x, weight, style, bias, skip, w_scale)
 
 
-def _epilogue(style=None, demod=None, noise=None, noise_w=None, bias=None, act=False):
-    keep = [_opt(style, 'style'), _opt(demod, 'demod'), _opt(noise, 'noise'),
-            _opt(noise_w, 'noise weight'), _opt(bias, 'bias')]
-    ep = ConvEpilogue(_p(keep[0]).value, _p(keep[1]).value, _p(keep[2]).value,
-                      _p(keep[3]).value, _p(keep[4]).value, int(bool(act)))
-    return ep, keep
-
-
-def _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, out, x, out_ch):
-    """The ToRGB block of a convolution of x to out_ch channels that writes `out`: (RgbEpilogue, the tensors it
-    points at)."""
-    keep = [_dev(rgb_weight, 'rgb weight'), _dev(rgb_style, 'rgb style'), _opt(rgb_bias, 'rgb bias'),
-            _opt(rgb_skip, 'rgb skip'), out]
-    b, _, h, w = x.shape
-    if tuple(keep[0].shape) != (3, out_ch) or tuple(keep[1].shape) != (b, out_ch):
-        raise ValueError('rgb weight / style shapes')
-    if keep[3] is not None and tuple(keep[3].shape) != (b, 3, h, w):
-        raise ValueError('rgb skip shape')
-    return RgbEpilogue(*[_p(t).value for t in keep], float(rgb_scale)), keep
-
-
-def _packed(t, out_ch, in_ch, what, plain=None, split=None):
-    """(the packed weight t on the device, 1 / u_scale of a split -- f16 pair -- packing or None for the plain one): the
-    two are told apart by their size, `plain` / `split` being the rw_packed_*_elems entries of the two forms (None: there
-    is no such form) and `what` the pack function t must come from.  The scale of a split packing rides on the caller's
-    tensor (_u_inv), which is why it is read here, before t is replaced by its contiguous self."""
-    wp = _dev(t, 'packed weight')
-    if plain is not None and wp.numel() == plain(out_ch, in_ch):
-        return wp, None
-    if split is not None and wp.numel() == split(out_ch, in_ch):
-        return wp, _u_inv(t)
-    raise ValueError('packed weight does not come from %s(%d x %d)' % (what, out_ch, in_ch))
-
-
-def _k4(k4):
+def blur_noise_act(x, k4, noise, noise_w, bias, post_scale=None, y_amax=None):
+    """Blur(pad 1,1) + noise + bias + leaky ReLU of an upsampling layer in one pass; post_scale (B x C, optional):
+    a factor on the result -- the style of the convolution that consumes it; y_amax (hip.new_bound(result elements),
+    optional) receives the bound of the result."""
+    x = _dev(x, 'fmap')
     k4 = _dev(k4, 'blur kernel')
-    if tuple(k4.shape) != (4, 4):
-        raise ValueError('the blur kernel must be 4 x 4')
-    return k4
-
-
-def _post_scale(post_scale, batch, channels, named='out_ch'):
-    post_scale = _opt(post_scale, 'post scale')
-    if post_scale is not None and tuple(post_scale.shape) != (batch, channels):
-        raise ValueError('post_scale must be batch x %s' % named)
-    return post_scale
-
-
-def _supported(entry, doc):
-    """A shape predicate over the library's own rw_*_supported entry."""
-    def supported(out_ch, in_ch, height, width):
-        return bool(getattr(lib(), entry)(int(out_ch), int(in_ch), int(height), int(width)))
-    supported.__doc__ = '%s (%s).' % (doc, entry)
-    return supported
-
-
-def conv3x3(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None,
-            act=False, impl=0):
-    x = _dev(x, 'fmap')
-    wp = _dev(wp, 'packed weight')
-    b, i, h, w = x.shape
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    _check_packed(wp, out_ch, i, 0)
-    check(lib().rw_conv3x3_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
-                               ctypes.byref(ep), int(impl), _stream()))
+    noise = _opt(noise, 'noise')
+    noise_w = _opt(noise_w, 'noise weight')
+    bias = _opt(bias, 'bias')
+    b, c, ih, iw = x.shape
+    y = torch.empty(b, c, ih - 1, iw - 1, device=x.device, dtype=x.dtype)
+    post_scale = _post_scale(post_scale, b, c, 'channels')
+    y_amax = _amax_out(y_amax, y.numel())
+    check(lib().rw_blur_noise_act_amax_f32(_p(x), _p(k4), _p(noise), _p(noise_w), _p(bias), _p(post_scale), _p(y),
+                                           b, c, ih - 1, iw - 1, _p(y_amax), _stream()))
     return y
 
 
-def to_rgb_fusable(out_ch, in_ch, width):
-    """Shapes rw_conv3x3_to_rgb_f32 takes: one wave holds every out-channel of its pixels."""
-    return out_ch in (32, 64) and width >= 24 and in_ch % 16 == 0 and in_ch <= 1024
-
-
-def conv3x3_to_rgb(x, wp, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
-                   demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
-    """The styled convolution with ToRGB fused into its epilogue: returns (fmap or None, rgb image)."""
-    x = _dev(x, 'fmap')
-    wp = _dev(wp, 'packed weight')
-    b, i, h, w = x.shape
-    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
-    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
-    _check_packed(wp, out_ch, i, 0)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype) if store_fmap else None
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    check(lib().rw_conv3x3_to_rgb_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                      ctypes.byref(ep), ctypes.byref(re), _stream()))
-    return y, rgb
-
-
-wino_supported = _supported('rw_conv3x3_wino_supported', 'Shapes the Winograd F(2x2,3x3) stride-1 convolution takes')
-
-
-def pack_conv_weight_wino(weight):
-    weight = _dev(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = lib().rw_packed_conv_weight_wino_elems(o, i)
-    if n <= 0:
-        raise ValueError('no Winograd packing for a %d x %d weight' % (o, i))
-    uf = torch.empty(n, device=weight.device, dtype=torch.float32)
-    check(lib().rw_pack_conv_weight_wino_f32(_p(weight), _p(uf), o, i, _stream()))
-    return uf
-
-
-def conv3x3_wino(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False):
-    """Stride-1 3x3 convolution by Winograd F(2x2,3x3) in fp32; same arguments and epilogue as conv3x3."""
-    x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    uf, _ = _packed(uf, out_ch, i, 'pack_conv_weight_wino', lib().rw_packed_conv_weight_wino_elems)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    if style is not None and h == w and w in (4, 8):
-        # whole 8^2 / 4^2 images per wave (several images per workgroup): the library takes exactly these maps already
-        # multiplied by their style (style == NULL, see the header) -- the same product, rounded the same way, one tiny
-        # launch earlier
-        x, style = style_mul(x, _dev(style, 'style')), None
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    check(lib().rw_conv3x3_wino_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                    _stream()))
+def rgb_combine(partials, bias, skip):
+    """ToRGB from the partial sums a convolution left (conv3x3_direct16_rgb_partial): sum over partials + bias + skip."""
+    partials = _dev(partials, 'rgb partial sums')
+    bias = _opt(bias, 'rgb bias')
+    skip = _opt(skip, 'rgb skip')
+    n, b, c, h, w = partials.shape
+    if c != 3 or (skip is not None and tuple(skip.shape) != (b, 3, h, w)):
+        raise ValueError('rgb partial / skip shapes')
+    y = torch.empty(b, 3, h, w, device=partials.device, dtype=partials.dtype)
+    check(lib().rw_rgb_combine_f32(_p(partials), n, _p(bias), _p(skip), _p(y), b, h * w, _stream()))
     return y
 
 
-wino4_supported = _supported('rw_conv3x3_wino4_supported', 'Shapes the Winograd F(4x4,3x3) stride-1 convolution takes')
-
-
+# ------------------------------------------------------------------ bounds (the split-operand kernels)
 BOUND_LANES = 64                # RW_BOUND_LANES of include/rewriting_hip.h
 
 
@@ -402,110 +367,25 @@ def _amax_out(y_amax, n_elems):
     return y_amax
 
 
-def _split_scale(measure, *args):
-    """(u_scale, u_inv) of a split-operand packing: `measure` (a rw_*_absmax_f32 entry) leaves max |U| as a bound, the
-    host reads it -- ONE sync per weight version, never inside a forward whose weights are packed -- and
-    rw_split_weight_scale turns it into the power of two that the pack kernel and every convolution launch then get BY
-    VALUE."""
-    device = args[0].device
-    bound = new_bound(0, device)
-    check(measure(*[_p(a) if torch.is_tensor(a) else a for a in args], _p(bound), _stream()))
-    u_scale = float(lib().rw_split_weight_scale(bound_value(bound)))
-    return u_scale, 1.0 / u_scale
-
-
-def _u_inv(packed):
-    """1 / u_scale of a split-operand packing: it travels with the tensor the pack function returned."""
-    try:
-        return float(packed.rw_u_inv)
-    except AttributeError:
-        raise ValueError('split-operand packed weights must be the tensor a hip.pack_*(split=True) / pack_*_direct16 call '
-                         'returned (its scale travels as the attribute rw_u_inv; a copy does not carry it)') from None
-
-
-def pack_conv_weight_wino4(weight, split=False):
-    """G g G^T of every filter in the fragment order of the F(4x4,3x3) kernels; split=True: every value as the pair
-    of f16 numbers the kernels on the 16-bit matrix pipe multiply (rw_pack_conv_weight_wino4h_f32) -- the convolution
-    functions tell the two formats apart by their size."""
+# ------------------------------------------------------------------ packed weights
+def pack_conv_weight(weight, mode):
     weight = _dev(weight, 'weight')
     o, i = weight.shape[-4], weight.shape[-3]
-    n = (lib().rw_packed_conv_weight_wino4h_elems if split else lib().rw_packed_conv_weight_wino4_elems)(o, i)
+    n = lib().rw_packed_conv_weight_elems(o, i, int(mode))
     if n <= 0:
-        raise ValueError('no F(4x4,3x3) packing for a %d x %d weight' % (o, i))
-    uf = torch.empty(n, device=weight.device, dtype=torch.float32)
-    if split:
-        u_scale, uf.rw_u_inv = _split_scale(lib().rw_conv_weight_wino4h_absmax_f32, weight, o, i)
-        check(lib().rw_pack_conv_weight_wino4h_f32(_p(weight), _p(uf), o, i, u_scale, _stream()))
-    else:
-        check(lib().rw_pack_conv_weight_wino4_f32(_p(weight), _p(uf), o, i, _stream()))
-    return uf
+        raise ValueError('bad weight shape / mode')
+    wp = torch.empty(n, device=weight.device, dtype=weight.dtype)   # slab order, then fragment order
+    check(lib().rw_pack_conv_weight_f32(_p(weight), _p(wp), o, i, int(mode), _stream()))
+    return wp
 
 
-def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
-                  x_amax=None, y_amax=None):
-    """Stride-1 3x3 convolution by Winograd F(4x4,3x3) (~1e-5 relative error per layer: the default of the
-    un-hooked whole-generator forward, never used by a hooked or sliced model -- routing.conv_algo); same arguments
-    and epilogue as conv3x3.  With weights from pack_conv_weight_wino4(split=True) the products run on the 16-bit
-    matrix pipe (exact f16 operand split, fp32 accumulation): x_amax = the bound of x (hip.absmax(x), or the y_amax its
-    producer filled; measured here when None), y_amax = hip.new_bound(y.numel(), device), which receives the bound of y."""
-    x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_weight_wino4', lib().rw_packed_conv_weight_wino4_elems,
-                        lib().rw_packed_conv_weight_wino4h_elems)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    if u_inv is not None:
-        x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-        check(lib().rw_conv3x3_wino4h_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                          u_inv, _p(x_amax), _p(y_amax), _stream()))
-        return y
-    check(lib().rw_conv3x3_wino4_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                     _stream()))
-    return y
-
-
-def conv3x3_wino_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
-                        demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
-    """conv3x3_wino with ToRGB in the epilogue (out_ch == 32): returns (fmap or None, rgb image)."""
-    x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
-    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
-    uf, _ = _packed(uf, out_ch, i, 'pack_conv_weight_wino', lib().rw_packed_conv_weight_wino_elems)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype) if store_fmap else None
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    check(lib().rw_conv3x3_wino_to_rgb_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                           ctypes.byref(ep), ctypes.byref(re), _stream()))
-    return y, rgb
-
-
-wino4_to_rgb_supported = _supported('rw_conv3x3_wino4_to_rgb_supported', 'Shapes conv3x3_wino4_to_rgb takes: out_ch == 32')
-
-
-def conv3x3_wino4_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
-                         demod=None, noise=None, noise_w=None, bias=None, act=False, x_amax=None):
-    """conv3x3_wino4 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image); the feature map is not
-    written.  Split weights and x_amax as in conv3x3_wino4."""
-    x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
-    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
-    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_weight_wino4', lib().rw_packed_conv_weight_wino4_elems,
-                        lib().rw_packed_conv_weight_wino4h_elems)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    if u_inv is not None:
-        x_amax = _amax_in(x, x_amax)
-        check(lib().rw_conv3x3_wino4h_to_rgb_f32(_p(x), _p(uf), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                                 ctypes.byref(re), u_inv, _p(x_amax), _stream()))
-        return None, rgb
-    check(lib().rw_conv3x3_wino4_to_rgb_f32(_p(x), _p(uf), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                            ctypes.byref(re), _stream()))
-    return None, rgb
-
-
-def bf16x6_supported(out_ch, in_ch, width):
-    """Shapes the opt-in split-precision convolution takes (rw_conv3x3_bf16x6_f32)."""
-    return width >= 24 and in_ch % 16 == 0 and in_ch <= 1024 and out_ch % 64 == 0
+def _check_packed(wp, out_ch, in_ch, mode):
+    """(wp on the device, None): the one packing of pack_conv_weight, as _packed returns a form's."""
+    wp = _dev(wp, 'packed weight')
+    if wp.numel() != lib().rw_packed_conv_weight_elems(out_ch, in_ch, mode):
+        raise ValueError('packed weight does not come from pack_conv_weight(%d x %d, mode %d)'
+                         % (out_ch, in_ch, mode))
+    return wp, None
 
 
 def pack_conv_weight_bf16x3(weight):
@@ -519,19 +399,323 @@ def pack_conv_weight_bf16x3(weight):
     return wb
 
 
+class _Form(_namedtuple('_Form', 'pack_fn what plain split k4')):
+    """What a packed form is.  pack_fn: the public function that makes it; what: its name in "no <what> weight";
+    plain: the (rw_packed_*_elems, rw_pack_*) entries of the fp32 packing, split: the (rw_packed_*_elems, rw_*_absmax_f32,
+    rw_pack_*) entries of the one in f16 pairs (None: the form has no such packing); k4: the 4x4 FIR is an operand.
+    Entries are named, not resolved: they are looked up on lib() at each call."""
+
+
+_WINO = _Form('pack_conv_weight_wino', 'Winograd packing for a %d x %d',
+              ('rw_packed_conv_weight_wino_elems', 'rw_pack_conv_weight_wino_f32'), None, False)
+_WINO4 = _Form('pack_conv_weight_wino4', 'F(4x4,3x3) packing for a %d x %d',
+               ('rw_packed_conv_weight_wino4_elems', 'rw_pack_conv_weight_wino4_f32'),
+               ('rw_packed_conv_weight_wino4h_elems', 'rw_conv_weight_wino4h_absmax_f32', 'rw_pack_conv_weight_wino4h_f32'),
+               False)
+_UP_WINO = _Form('pack_conv_transpose_weight_wino', 'F(2,2) packing for a %d x %d transposed-conv',
+                 ('rw_packed_conv_transpose_wino_elems', 'rw_pack_conv_transpose_wino_f32'),
+                 ('rw_packed_conv_transpose_winoh_elems', 'rw_conv_transpose_weight_winoh_absmax_f32',
+                  'rw_pack_conv_transpose_winoh_f32'), False)
+_UP_BLUR_WINO4 = _Form('pack_conv_transpose_blur_weight_wino4', 'F(4x4,3x3) phase packing for a %d x %d transposed-conv',
+                       ('rw_packed_conv_transpose_blur_wino4_elems', 'rw_pack_conv_transpose_blur_weight_wino4_f32'),
+                       ('rw_packed_conv_transpose_blur_wino4h_elems', 'rw_conv_transpose_blur_weight_wino4h_absmax_f32',
+                        'rw_pack_conv_transpose_blur_weight_wino4h_f32'), True)
+_DIRECT16 = _Form('pack_conv_weight_direct16', 'direct-16 packing for a %d x %d', None,
+                  ('rw_packed_dconv_weight_elems', 'rw_dconv_weight_absmax_f32', 'rw_pack_dconv_weight_f32'), False)
+_UP_BLUR_DIRECT16 = _Form('pack_conv_transpose_blur_weight_direct16',
+                          'direct-16 phase packing for a %d x %d transposed-conv', None,
+                          ('rw_packed_dconv_transpose_blur_weight_elems', 'rw_dconv_transpose_blur_weight_absmax_f32',
+                           'rw_pack_dconv_transpose_blur_weight_f32'), True)
+
+
+def _k4(k4):
+    k4 = _dev(k4, 'blur kernel')
+    if tuple(k4.shape) != (4, 4):
+        raise ValueError('the blur kernel must be 4 x 4')
+    return k4
+
+
+def _split_scale(measure, *args):
+    """(u_scale, u_inv) of a split-operand packing: `measure` (a rw_*_absmax_f32 entry) leaves max |U| as a bound, the
+    host reads it -- ONE sync per weight version, never inside a forward whose weights are packed -- and
+    rw_split_weight_scale turns it into the power of two that the pack kernel and every convolution launch then get BY
+    VALUE."""
+    device = args[0].device
+    bound = new_bound(0, device)
+    check(measure(*[_p(a) if torch.is_tensor(a) else a for a in args], _p(bound), _stream()))
+    u_scale = float(lib().rw_split_weight_scale(bound_value(bound)))
+    return u_scale, 1.0 / u_scale
+
+
+def _pack(form, weight, k4=None, split=False):
+    """The plain or the split packing of `form` of weight (and k4, where the form takes it): a flat float32 tensor; the
+    scale of a split one rides on it as the attribute rw_u_inv."""
+    weight = _dev(weight, 'weight')
+    operands = (weight, _k4(k4)) if form.k4 else (weight,)
+    o, i = weight.shape[-4], weight.shape[-3]
+    entries = form.split if split else form.plain
+    n = getattr(lib(), entries[0])(o, i)
+    if n <= 0:
+        raise ValueError('no %s weight' % (form.what % (o, i)))
+    packed = torch.empty(n, device=weight.device, dtype=torch.float32)
+    scale = ()
+    if split:
+        u_scale, packed.rw_u_inv = _split_scale(getattr(lib(), entries[1]), *operands, o, i)
+        scale = (u_scale,)
+    check(getattr(lib(), entries[-1])(*[_p(t) for t in operands], _p(packed), o, i, *scale, _stream()))
+    return packed
+
+
+def _u_inv(packed):
+    """1 / u_scale of a split-operand packing: it travels with the tensor the pack function returned."""
+    try:
+        return float(packed.rw_u_inv)
+    except AttributeError:
+        raise ValueError('split-operand packed weights must be the tensor a hip.pack_*(split=True) / pack_*_direct16 call '
+                         'returned (its scale travels as the attribute rw_u_inv; a copy does not carry it)') from None
+
+
+def _packed(t, out_ch, in_ch, form):
+    """(the packed weight t on the device, 1 / u_scale of a split -- f16 pair -- packing or None for the plain one): the
+    two packings of `form` are told apart by their size.  The scale of a split packing rides on the caller's tensor
+    (_u_inv), which is why it is read here, before t is replaced by its contiguous self."""
+    wp = _dev(t, 'packed weight')
+    if form.plain is not None and wp.numel() == getattr(lib(), form.plain[0])(out_ch, in_ch):
+        return wp, None
+    if form.split is not None and wp.numel() == getattr(lib(), form.split[0])(out_ch, in_ch):
+        return wp, _u_inv(t)
+    raise ValueError('packed weight does not come from %s(%d x %d)' % (form.pack_fn, out_ch, in_ch))
+
+
+def pack_conv_weight_wino(weight):
+    return _pack(_WINO, weight)
+
+
+def pack_conv_weight_wino4(weight, split=False):
+    """G g G^T of every filter in the fragment order of the F(4x4,3x3) kernels; split=True: every value as the pair
+    of f16 numbers the kernels on the 16-bit matrix pipe multiply (rw_pack_conv_weight_wino4h_f32) -- the convolution
+    functions tell the two formats apart by their size."""
+    return _pack(_WINO4, weight, split=split)
+
+
+def pack_conv_transpose_weight_wino(weight, split=False):
+    """The 25 F(2,2) points of every filter in fragment order; split=True: as pairs of f16 numbers for the kernel on
+    the 16-bit matrix pipe (rw_pack_conv_transpose_winoh_f32) -- told apart by size."""
+    return _pack(_UP_WINO, weight, split=split)
+
+
+def pack_conv_transpose_blur_weight_wino4(weight, k4, split=False):
+    """F(4x4,3x3) weights of the four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4;
+    split=True: as f16 pairs (pack_conv_weight_wino4)."""
+    return _pack(_UP_BLUR_WINO4, weight, k4, split=split)
+
+
+def pack_conv_weight_direct16(weight):
+    """The weights as f16 pairs in the operand order of the direct kernels on the 16-bit matrix pipe
+    (rw_pack_dconv_weight_f32)."""
+    return _pack(_DIRECT16, weight, split=True)
+
+
+def pack_conv_transpose_blur_weight_direct16(weight, k4):
+    """The four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4, as f16 pairs in the operand
+    order of the direct kernel (rw_pack_dconv_transpose_blur_weight_f32)."""
+    return _pack(_UP_BLUR_DIRECT16, weight, k4, split=True)
+
+
+# ------------------------------------------------------------------ convolutions
+def _epilogue(style=None, demod=None, noise=None, noise_w=None, bias=None, act=False):
+    keep = [_opt(style, 'style'), _opt(demod, 'demod'), _opt(noise, 'noise'),
+            _opt(noise_w, 'noise weight'), _opt(bias, 'bias')]
+    ep = ConvEpilogue(_p(keep[0]).value, _p(keep[1]).value, _p(keep[2]).value,
+                      _p(keep[3]).value, _p(keep[4]).value, int(bool(act)))
+    return ep, keep
+
+
+def _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, out, x, out_ch):
+    """The ToRGB block of a convolution of x to out_ch channels that writes `out`: (RgbEpilogue, the tensors it
+    points at)."""
+    keep = [_dev(rgb_weight, 'rgb weight'), _dev(rgb_style, 'rgb style'), _opt(rgb_bias, 'rgb bias'),
+            _opt(rgb_skip, 'rgb skip'), out]
+    b, _, h, w = x.shape
+    if tuple(keep[0].shape) != (3, out_ch) or tuple(keep[1].shape) != (b, out_ch):
+        raise ValueError('rgb weight / style shapes')
+    if keep[3] is not None and tuple(keep[3].shape) != (b, 3, h, w):
+        raise ValueError('rgb skip shape')
+    return RgbEpilogue(*[_p(t).value for t in keep], float(rgb_scale)), keep
+
+
+def _post_scale(post_scale, batch, channels, named='out_ch'):
+    post_scale = _opt(post_scale, 'post scale')
+    if post_scale is not None and tuple(post_scale.shape) != (batch, channels):
+        raise ValueError('post_scale must be batch x %s' % named)
+    return post_scale
+
+
+def _supported(entry, doc):
+    """A shape predicate over the library's own rw_*_supported entry."""
+    def supported(out_ch, in_ch, height, width):
+        return bool(getattr(lib(), entry)(int(out_ch), int(in_ch), int(height), int(width)))
+    supported.__doc__ = '%s (%s).' % (doc, entry)
+    return supported
+
+
+def _conv(entries, x, packed, out_ch, w_scale, ep=None, style_demod=None, x_amax=None, **slots):
+    """Calls a convolution entry.  Every one takes its arguments in ONE order (include/rewriting_hip.h), the bracketed
+    ones only where it has them:
+
+        x, packed, [k4], [y], batch, in_ch, out_ch, h, w, w_scale, ep | (style, demod), [rgb], [impl], [post_scale],
+        [u_inv, x_amax], [y_amax], stream
+
+    entries: the entry's name, or (entry for a plain packing, entry for a split one) -- chosen here, once, by the scale
+    that `packed` = (tensor, u_inv or None) carries (_packed).  ep / rgb: what _epilogue / _rgb_epilogue returned;
+    style_demod: the two tensors of an entry without an epilogue block.  `slots`: the bracketed arguments this entry has
+    -- a slot that is given as None is a null pointer, one that is not given is not in the entry's list.  A split
+    packing adds u_inv, the bound of x (x_amax, measured here when None) and, where there is a y_amax slot, the buffer
+    that receives the bound of slots['y']; a plain one takes none of the three."""
+    wp, u_inv = packed
+    b, i, h, w = x.shape
+    args = [_p(x), _p(wp)] + [_p(slots[s]) for s in ('k4', 'y') if s in slots] + [b, i, out_ch, h, w, float(w_scale)]
+    if ep is not None:
+        args.append(ctypes.byref(ep[0]))
+    else:
+        style_demod = [_opt(style_demod[0], 'style'), _opt(style_demod[1], 'demod')]
+        args += [_p(t) for t in style_demod]
+    if 'rgb' in slots:
+        args.append(ctypes.byref(slots['rgb'][0]))
+    if 'impl' in slots:
+        args.append(int(slots['impl']))
+    if 'post_scale' in slots:
+        args.append(_p(slots['post_scale']))
+    if u_inv is not None:
+        x_amax = _amax_in(x, x_amax)
+        args += [u_inv, _p(x_amax)]
+        if 'y_amax' in slots:
+            y_amax = _amax_out(slots['y_amax'], slots['y'].numel())
+            args.append(_p(y_amax))
+    entry = entries if isinstance(entries, str) else entries[u_inv is not None]
+    check(getattr(lib(), entry)(*args, _stream()))
+
+
+def _out(x, out_ch, up=1):
+    """The (uninitialised) result of a convolution of x to out_ch channels at `up` times its size."""
+    b, _, h, w = x.shape
+    return torch.empty(b, out_ch, up * h, up * w, device=x.device, dtype=x.dtype)
+
+
+def _out_transposed(x, out_ch, out):
+    """The (2H+1) x (2W+1) map of a transposed convolution of x: the caller's `out`, or a new one."""
+    b, _, h, w = x.shape
+    y = out if out is not None else torch.empty(b, out_ch, 2 * h + 1, 2 * w + 1, device=x.device, dtype=x.dtype)
+    if tuple(y.shape) != (b, out_ch, 2 * h + 1, 2 * w + 1) or not y.is_contiguous():
+        raise ValueError('out has the wrong shape')
+    return y
+
+
+def _styled_whole_maps(x, style):
+    """(x, style) as the F(2x2) / F(2,2) fp32 kernels take them.  8^2 and 4^2 maps run as whole images per wave (several
+    images per workgroup), and the library takes exactly these already multiplied by their style (style == NULL, see the
+    header) -- the same product, rounded the same way, one tiny launch earlier."""
+    if style is not None and x.shape[2] == x.shape[3] and x.shape[3] in (4, 8):
+        return style_mul(x, _dev(style, 'style')), None
+    return x, style
+
+
+def conv3x3(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None,
+            act=False, impl=0):
+    x = _dev(x, 'fmap')
+    y = _out(x, out_ch)
+    _conv('rw_conv3x3_f32', x, _check_packed(wp, out_ch, x.shape[1], 0), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), y=y, impl=impl)
+    return y
+
+
+def to_rgb_fusable(out_ch, in_ch, width):
+    """Shapes rw_conv3x3_to_rgb_f32 takes: one wave holds every out-channel of its pixels."""
+    return out_ch in (32, 64) and width >= 24 and in_ch % 16 == 0 and in_ch <= 1024
+
+
+def conv3x3_to_rgb(x, wp, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
+                   demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
+    """The styled convolution with ToRGB fused into its epilogue: returns (fmap or None, rgb image)."""
+    x = _dev(x, 'fmap')
+    y, rgb = _out(x, out_ch) if store_fmap else None, _out(x, 3)
+    _conv('rw_conv3x3_to_rgb_f32', x, _check_packed(wp, out_ch, x.shape[1], 0), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), y=y,
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch))
+    return y, rgb
+
+
+wino_supported = _supported('rw_conv3x3_wino_supported', 'Shapes the Winograd F(2x2,3x3) stride-1 convolution takes')
+
+
+def conv3x3_wino(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False):
+    """Stride-1 3x3 convolution by Winograd F(2x2,3x3) in fp32; same arguments and epilogue as conv3x3."""
+    x = _dev(x, 'fmap')
+    uf = _packed(uf, out_ch, x.shape[1], _WINO)
+    y = _out(x, out_ch)
+    x, style = _styled_whole_maps(x, style)
+    _conv('rw_conv3x3_wino_f32', x, uf, out_ch, w_scale, _epilogue(style, demod, noise, noise_w, bias, act), y=y)
+    return y
+
+
+def conv3x3_wino_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
+                        demod=None, noise=None, noise_w=None, bias=None, act=False, store_fmap=False):
+    """conv3x3_wino with ToRGB in the epilogue (out_ch == 32): returns (fmap or None, rgb image)."""
+    x = _dev(x, 'fmap')
+    y, rgb = _out(x, out_ch) if store_fmap else None, _out(x, 3)
+    _conv('rw_conv3x3_wino_to_rgb_f32', x, _packed(uf, out_ch, x.shape[1], _WINO), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), y=y,
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch))
+    return y, rgb
+
+
+wino4_supported = _supported('rw_conv3x3_wino4_supported', 'Shapes the Winograd F(4x4,3x3) stride-1 convolution takes')
+
+
+def conv3x3_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
+                  x_amax=None, y_amax=None):
+    """Stride-1 3x3 convolution by Winograd F(4x4,3x3) (~1e-5 relative error per layer: the default of the
+    un-hooked whole-generator forward, never used by a hooked or sliced model -- routing.conv_algo); same arguments
+    and epilogue as conv3x3.  With weights from pack_conv_weight_wino4(split=True) the products run on the 16-bit
+    matrix pipe (exact f16 operand split, fp32 accumulation): x_amax = the bound of x (hip.absmax(x), or the y_amax its
+    producer filled; measured here when None), y_amax = hip.new_bound(y.numel(), device), which receives the bound of y."""
+    x = _dev(x, 'fmap')
+    y = _out(x, out_ch)
+    _conv(('rw_conv3x3_wino4_f32', 'rw_conv3x3_wino4h_f32'), x, _packed(uf, out_ch, x.shape[1], _WINO4), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, y=y, y_amax=y_amax)
+    return y
+
+
+wino4_to_rgb_supported = _supported('rw_conv3x3_wino4_to_rgb_supported', 'Shapes conv3x3_wino4_to_rgb takes: out_ch == 32')
+
+
+def conv3x3_wino4_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
+                         demod=None, noise=None, noise_w=None, bias=None, act=False, x_amax=None):
+    """conv3x3_wino4 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image); the feature map is not
+    written.  Split weights and x_amax as in conv3x3_wino4."""
+    x = _dev(x, 'fmap')
+    rgb = _out(x, 3)
+    _conv(('rw_conv3x3_wino4_to_rgb_f32', 'rw_conv3x3_wino4h_to_rgb_f32'), x, _packed(uf, out_ch, x.shape[1], _WINO4),
+          out_ch, w_scale, _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax,
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch))
+    return None, rgb
+
+
+def bf16x6_supported(out_ch, in_ch, width):
+    """Shapes the opt-in split-precision convolution takes (rw_conv3x3_bf16x6_f32)."""
+    return width >= 24 and in_ch % 16 == 0 and in_ch <= 1024 and out_ch % 64 == 0
+
+
 def conv3x3_bf16x6(x, wb, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None,
                    act=False):
     """Opt-in: the stride-1 convolution on the bf16 matrix pipe with exact three-way operand splits
     (six piece products, fp32 accumulation); same arguments and epilogue as conv3x3."""
     x = _dev(x, 'fmap')
     wb = _dev(wb, 'packed weight')
-    b, i, h, w = x.shape
-    if wb.numel() * 4 != lib().rw_packed_conv_weight_bf16x3_bytes(out_ch, i):
-        raise ValueError('packed weight does not come from pack_conv_weight_bf16x3(%d x %d)' % (out_ch, i))
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    check(lib().rw_conv3x3_bf16x6_f32(_p(x), _p(wb), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                      ctypes.byref(ep), _stream()))
+    if wb.numel() * 4 != lib().rw_packed_conv_weight_bf16x3_bytes(out_ch, x.shape[1]):
+        raise ValueError('packed weight does not come from pack_conv_weight_bf16x3(%d x %d)' % (out_ch, x.shape[1]))
+    y = _out(x, out_ch)
+    _conv('rw_conv3x3_bf16x6_f32', x, (wb, None), out_ch, w_scale, _epilogue(style, demod, noise, noise_w, bias, act), y=y)
     return y
 
 
@@ -548,15 +732,9 @@ def up_strips_applicable(out_ch, in_ch):
 
 def conv_transpose3x3s2(x, wp, out_ch, w_scale, style=None, demod=None, impl=0, out=None):
     x = _dev(x, 'fmap')
-    wp = _dev(wp, 'packed weight')
-    b, i, h, w = x.shape
-    y = out if out is not None else torch.empty(b, out_ch, 2 * h + 1, 2 * w + 1, device=x.device, dtype=x.dtype)
-    if tuple(y.shape) != (b, out_ch, 2 * h + 1, 2 * w + 1) or not y.is_contiguous():
-        raise ValueError('out has the wrong shape')
-    ep, keep = _epilogue(style, demod)
-    _check_packed(wp, out_ch, i, 1)
-    check(lib().rw_conv_transpose3x3s2_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                           ctypes.byref(ep), int(impl), _stream()))
+    y = _out_transposed(x, out_ch, out)
+    _conv('rw_conv_transpose3x3s2_f32', x, _check_packed(wp, out_ch, x.shape[1], 1), out_ch, w_scale,
+          _epilogue(style, demod), y=y, impl=impl)
     return y
 
 
@@ -566,72 +744,22 @@ conv_transpose_wino_supported = _supported('rw_conv_transpose3x3s2_wino_supporte
 conv_transpose_wino_split_supported = _supported('rw_conv_transpose3x3s2_winoh_supported', 'Shapes the split-operand (16-bit matrix pipe) form of conv_transpose3x3s2_wino takes')
 
 
-def pack_conv_transpose_weight_wino(weight, split=False):
-    """The 25 F(2,2) points of every filter in fragment order; split=True: as pairs of f16 numbers for the kernel on
-    the 16-bit matrix pipe (rw_pack_conv_transpose_winoh_f32) -- told apart by size."""
-    weight = _dev(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = (lib().rw_packed_conv_transpose_winoh_elems if split else lib().rw_packed_conv_transpose_wino_elems)(o, i)
-    if n <= 0:
-        raise ValueError('no F(2,2) packing for a %d x %d transposed-conv weight' % (o, i))
-    uf = torch.empty(n, device=weight.device, dtype=torch.float32)
-    if split:
-        u_scale, uf.rw_u_inv = _split_scale(lib().rw_conv_transpose_weight_winoh_absmax_f32, weight, o, i)
-        check(lib().rw_pack_conv_transpose_winoh_f32(_p(weight), _p(uf), o, i, u_scale, _stream()))
-    else:
-        check(lib().rw_pack_conv_transpose_wino_f32(_p(weight), _p(uf), o, i, _stream()))
-    return uf
-
-
 def conv_transpose3x3s2_wino(x, uf, out_ch, w_scale, style=None, demod=None, out=None, x_amax=None):
     """The quads y < H, x < W of conv_transpose3x3s2 by F(2,2) (25 instead of 36 multiplies per 2x2 block of quads);
     output row 2H and column 2W are left to conv_transpose3x3s2(..., impl=8, out=...).  With weights from
     pack_conv_transpose_weight_wino(split=True) the products run on the 16-bit matrix pipe (exact f16 operand split,
     fp32 accumulation; x_amax = the bound of x as in conv3x3_wino4, measured here when None)."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_transpose_weight_wino',
-                        lib().rw_packed_conv_transpose_wino_elems,
-                        lib().rw_packed_conv_transpose_winoh_elems)
-    y = out if out is not None else torch.empty(b, out_ch, 2 * h + 1, 2 * w + 1, device=x.device, dtype=x.dtype)
-    if tuple(y.shape) != (b, out_ch, 2 * h + 1, 2 * w + 1) or not y.is_contiguous():
-        raise ValueError('out has the wrong shape')
-    style = _opt(style, 'style')
-    demod = _opt(demod, 'demod')
-    if u_inv is not None:
-        x_amax = _amax_in(x, x_amax)
-        check(lib().rw_conv_transpose3x3s2_winoh_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                     _p(style), _p(demod), u_inv, _p(x_amax), _stream()))
-        return y
-    if style is not None and h == w and w in (4, 8):
-        # whole 8^2 / 4^2 images per wave (several images per workgroup): the library takes exactly these maps already
-        # multiplied by their style -- the same product, rounded the same way, one tiny launch earlier
-        x, style = style_mul(x, style), None
-    check(lib().rw_conv_transpose3x3s2_wino_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale), _p(style),
-                                                _p(demod), _stream()))
+    uf = _packed(uf, out_ch, x.shape[1], _UP_WINO)
+    y = _out_transposed(x, out_ch, out)
+    if uf[1] is None:                           # the split kernel takes no 8^2 / 4^2 maps
+        x, style = _styled_whole_maps(x, style)
+    _conv(('rw_conv_transpose3x3s2_wino_f32', 'rw_conv_transpose3x3s2_winoh_f32'), x, uf, out_ch, w_scale,
+          style_demod=(style, demod), x_amax=x_amax, y=y)
     return y
 
 
 conv_transpose_blur_wino4_supported = _supported('rw_conv_transpose_blur_wino4_supported', 'Shapes the one-pass upsampling StyledConv takes')
-
-
-def pack_conv_transpose_blur_weight_wino4(weight, k4, split=False):
-    """F(4x4,3x3) weights of the four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4;
-    split=True: as f16 pairs (pack_conv_weight_wino4)."""
-    weight = _dev(weight, 'weight')
-    k4 = _k4(k4)
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = (lib().rw_packed_conv_transpose_blur_wino4h_elems if split
-         else lib().rw_packed_conv_transpose_blur_wino4_elems)(o, i)
-    if n <= 0:
-        raise ValueError('no F(4x4,3x3) phase packing for a %d x %d transposed-conv weight' % (o, i))
-    uf = torch.empty(n, device=weight.device, dtype=torch.float32)
-    if split:
-        u_scale, uf.rw_u_inv = _split_scale(lib().rw_conv_transpose_blur_weight_wino4h_absmax_f32, weight, k4, o, i)
-        check(lib().rw_pack_conv_transpose_blur_weight_wino4h_f32(_p(weight), _p(k4), _p(uf), o, i, u_scale, _stream()))
-    else:
-        check(lib().rw_pack_conv_transpose_blur_weight_wino4_f32(_p(weight), _p(k4), _p(uf), o, i, _stream()))
-    return uf
 
 
 def conv_transpose3x3s2_blur_wino4(x, uf, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None,
@@ -640,21 +768,11 @@ def conv_transpose3x3s2_blur_wino4(x, uf, out_ch, w_scale, style=None, demod=Non
     the four output-parity phases as virtual channels of the F(4x4,3x3) kernel (its error class: image generation).
     Split weights, x_amax and y_amax (max |y|, post_scale included) as in conv3x3_wino4."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    uf, u_inv = _packed(uf, out_ch, i, 'pack_conv_transpose_blur_weight_wino4',
-                        lib().rw_packed_conv_transpose_blur_wino4_elems,
-                        lib().rw_packed_conv_transpose_blur_wino4h_elems)
-    y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _post_scale(post_scale, b, out_ch)
-    if u_inv is not None:
-        x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-        check(lib().rw_conv_transpose3x3s2_blur_wino4h_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                           ctypes.byref(ep), _p(post_scale), u_inv, _p(x_amax),
-                                                           _p(y_amax), _stream()))
-        return y
-    check(lib().rw_conv_transpose3x3s2_blur_wino4_f32(_p(x), _p(uf), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                      ctypes.byref(ep), _p(post_scale), _stream()))
+    y = _out(x, out_ch, up=2)
+    _conv(('rw_conv_transpose3x3s2_blur_wino4_f32', 'rw_conv_transpose3x3s2_blur_wino4h_f32'), x,
+          _packed(uf, out_ch, x.shape[1], _UP_BLUR_WINO4), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, y=y,
+          post_scale=_post_scale(post_scale, x.shape[0], out_ch), y_amax=y_amax)
     return y
 
 
@@ -667,32 +785,14 @@ dconv_to_rgb_supported = _supported('rw_dconv3x3_to_rgb_supported', 'Shapes conv
 dconv_transpose_blur_supported = _supported('rw_dconv_transpose_blur_supported', 'Shapes conv_transpose3x3s2_blur_direct16 takes')
 
 
-def pack_conv_weight_direct16(weight):
-    """The weights as f16 pairs in the operand order of the direct kernels on the 16-bit matrix pipe
-    (rw_pack_dconv_weight_f32)."""
-    weight = _dev(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = lib().rw_packed_dconv_weight_elems(o, i)
-    if n <= 0:
-        raise ValueError('no direct-16 packing for a %d x %d weight' % (o, i))
-    wp = torch.empty(n, device=weight.device, dtype=torch.float32)
-    u_scale, wp.rw_u_inv = _split_scale(lib().rw_dconv_weight_absmax_f32, weight, o, i)
-    check(lib().rw_pack_dconv_weight_f32(_p(weight), _p(wp), o, i, u_scale, _stream()))
-    return wp
-
-
 def conv3x3_direct16(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None, bias=None, act=False,
                      x_amax=None, y_amax=None):
     """Stride-1 3x3 convolution as a direct sum on the 16-bit matrix pipe (exact f16 operand split, fp32 accumulation:
     rw_dconv3x3_f32); arguments, epilogue, x_amax and y_amax as conv3x3_wino4 with split weights."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-    check(lib().rw_dconv3x3_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                u_inv, _p(x_amax), _p(y_amax), _stream()))
+    y = _out(x, out_ch)
+    _conv('rw_dconv3x3_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, y=y, y_amax=y_amax)
     return y
 
 
@@ -701,62 +801,26 @@ def conv3x3_direct16_rgb_partial(x, wp, out_ch, w_scale, rgb_weight, rgb_style, 
     """conv3x3_direct16 that also leaves the channel sums of the ToRGB which reads its result (rw_dconv3x3_rgb_partial_f32):
     returns (feature map, partial images (out_ch / 32, B, 3, H, W)); rgb_combine() turns the partials into the image."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
     n_part = lib().rw_dconv3x3_rgb_partials(out_ch)
     if n_part <= 0:
         raise ValueError('no ToRGB partial sums for %d out-channels' % out_ch)
-    part = torch.empty(n_part, b, 3, h, w, device=x.device, dtype=x.dtype)
-    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, None, None, rgb_scale, part, x, out_ch)
-    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
-    y = torch.empty(b, out_ch, h, w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-    check(lib().rw_dconv3x3_rgb_partial_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                            ctypes.byref(re), u_inv, _p(x_amax), _p(y_amax), _stream()))
+    y = _out(x, out_ch)
+    part = torch.empty(n_part, x.shape[0], 3, x.shape[2], x.shape[3], device=x.device, dtype=x.dtype)
+    _conv('rw_dconv3x3_rgb_partial_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, y=y, y_amax=y_amax,
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, None, None, rgb_scale, part, x, out_ch))
     return y, part
-
-
-def rgb_combine(partials, bias, skip):
-    """ToRGB from the partial sums a convolution left (conv3x3_direct16_rgb_partial): sum over partials + bias + skip."""
-    partials = _dev(partials, 'rgb partial sums')
-    bias = _opt(bias, 'rgb bias')
-    skip = _opt(skip, 'rgb skip')
-    n, b, c, h, w = partials.shape
-    if c != 3 or (skip is not None and tuple(skip.shape) != (b, 3, h, w)):
-        raise ValueError('rgb partial / skip shapes')
-    y = torch.empty(b, 3, h, w, device=partials.device, dtype=partials.dtype)
-    check(lib().rw_rgb_combine_f32(_p(partials), n, _p(bias), _p(skip), _p(y), b, h * w, _stream()))
-    return y
 
 
 def conv3x3_direct16_to_rgb(x, wp, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
                             demod=None, noise=None, noise_w=None, bias=None, act=False, x_amax=None):
     """conv3x3_direct16 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image)."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    rgb = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
-    re, rgb_keep = _rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch)
-    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    x_amax = _amax_in(x, x_amax)
-    check(lib().rw_dconv3x3_to_rgb_f32(_p(x), _p(wp), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                       ctypes.byref(re), u_inv, _p(x_amax), _stream()))
+    rgb = _out(x, 3)
+    _conv('rw_dconv3x3_to_rgb_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax,
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch))
     return None, rgb
-
-
-def pack_conv_transpose_blur_weight_direct16(weight, k4):
-    """The four output-parity phases of conv_transpose(stride 2) followed by the 4x4 FIR k4, as f16 pairs in the operand
-    order of the direct kernel (rw_pack_dconv_transpose_blur_weight_f32)."""
-    weight = _dev(weight, 'weight')
-    k4 = _k4(k4)
-    o, i = weight.shape[-4], weight.shape[-3]
-    n = lib().rw_packed_dconv_transpose_blur_weight_elems(o, i)
-    if n <= 0:
-        raise ValueError('no direct-16 phase packing for a %d x %d transposed-conv weight' % (o, i))
-    wp = torch.empty(n, device=weight.device, dtype=torch.float32)
-    u_scale, wp.rw_u_inv = _split_scale(lib().rw_dconv_transpose_blur_weight_absmax_f32, weight, k4, o, i)
-    check(lib().rw_pack_dconv_transpose_blur_weight_f32(_p(weight), _p(k4), _p(wp), o, i, u_scale, _stream()))
-    return wp
 
 
 def conv_transpose3x3s2_blur_direct16(x, wp, out_ch, w_scale, style=None, demod=None, noise=None, noise_w=None,
@@ -764,16 +828,10 @@ def conv_transpose3x3s2_blur_direct16(x, wp, out_ch, w_scale, style=None, demod=
     """conv_transpose3x3s2 -> blur(pad 1,1) -> noise -> bias + leaky ReLU in one pass as a direct sum on the 16-bit matrix
     pipe: (B,Cin,H,W) -> (B,Cout,2H,2W); arguments as conv_transpose3x3s2_blur_wino4 with split weights."""
     x = _dev(x, 'fmap')
-    b, i, h, w = x.shape
-    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_transpose_blur_weight_direct16',
-                        split=lib().rw_packed_dconv_transpose_blur_weight_elems)
-    y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _post_scale(post_scale, b, out_ch)
-    x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-    check(lib().rw_dconv_transpose3x3s2_blur_f32(_p(x), _p(wp), _p(y), b, i, out_ch, h, w, float(w_scale),
-                                                 ctypes.byref(ep), _p(post_scale), u_inv, _p(x_amax), _p(y_amax),
-                                                 _stream()))
+    y = _out(x, out_ch, up=2)
+    _conv('rw_dconv_transpose3x3s2_blur_f32', x, _packed(wp, out_ch, x.shape[1], _UP_BLUR_DIRECT16), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, y=y,
+          post_scale=_post_scale(post_scale, x.shape[0], out_ch), y_amax=y_amax)
     return y
 
 
@@ -788,56 +846,10 @@ def conv_transpose3x3s2_blur_fused(x, wp, k4, out_ch, w_scale, style=None, demod
     the layer's weight (the plain packing: nothing is composed with the blur), k4 the 4x4 FIR; the other arguments as
     conv_transpose3x3s2_blur_direct16."""
     x = _dev(x, 'fmap')
-    k4 = _k4(k4)
-    b, i, h, w = x.shape
-    wp, u_inv = _packed(wp, out_ch, i, 'pack_conv_weight_direct16', split=lib().rw_packed_dconv_weight_elems)
-    y = torch.empty(b, out_ch, 2 * h, 2 * w, device=x.device, dtype=x.dtype)
-    ep, keep = _epilogue(style, demod, noise, noise_w, bias, act)
-    post_scale = _post_scale(post_scale, b, out_ch)
-    x_amax, y_amax = _amax_in(x, x_amax), _amax_out(y_amax, y.numel())
-    check(lib().rw_tconv_blur_f32(_p(x), _p(wp), _p(k4), _p(y), b, i, out_ch, h, w, float(w_scale), ctypes.byref(ep),
-                                  _p(post_scale), u_inv, _p(x_amax), _p(y_amax), _stream()))
-    return y
-
-
-def noise_add(x, noise, noise_w):
-    x = _dev(x, 'fmap')
-    noise = _dev(noise, 'noise')
-    noise_w = _dev(noise_w, 'noise weight')
-    b, c, h, w = x.shape
-    y = torch.empty_like(x)
-    check(lib().rw_noise_add_f32(_p(x), _p(noise), _p(noise_w), _p(y), b, c, h * w, _stream()))
-    return y
-
-
-def blur_noise_act(x, k4, noise, noise_w, bias, post_scale=None, y_amax=None):
-    """Blur(pad 1,1) + noise + bias + leaky ReLU of an upsampling layer in one pass; post_scale (B x C, optional):
-    a factor on the result -- the style of the convolution that consumes it; y_amax (hip.new_bound(result elements),
-    optional) receives the bound of the result."""
-    x = _dev(x, 'fmap')
-    k4 = _dev(k4, 'blur kernel')
-    noise = _opt(noise, 'noise')
-    noise_w = _opt(noise_w, 'noise weight')
-    bias = _opt(bias, 'bias')
-    b, c, ih, iw = x.shape
-    y = torch.empty(b, c, ih - 1, iw - 1, device=x.device, dtype=x.dtype)
-    post_scale = _post_scale(post_scale, b, c, 'channels')
-    y_amax = _amax_out(y_amax, y.numel())
-    check(lib().rw_blur_noise_act_amax_f32(_p(x), _p(k4), _p(noise), _p(noise_w), _p(bias), _p(post_scale), _p(y),
-                                           b, c, ih - 1, iw - 1, _p(y_amax), _stream()))
-    return y
-
-
-def to_rgb(x, weight, style, bias, skip, w_scale):
-    x = _dev(x, 'fmap')
-    weight = _dev(weight, 'rgb weight')
-    style = _dev(style, 'style')
-    bias = _opt(bias, 'bias')
-    skip = _opt(skip, 'skip')
-    b, c, h, w = x.shape
-    y = torch.empty(b, 3, h, w, device=x.device, dtype=x.dtype)
-    check(lib().rw_to_rgb_f32(_p(x), _p(weight), _p(style), _p(bias), _p(skip), _p(y), b, c, h * w,
-                              float(w_scale), _stream()))
+    y = _out(x, out_ch, up=2)
+    _conv('rw_tconv_blur_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
+          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, k4=_k4(k4), y=y,
+          post_scale=_post_scale(post_scale, x.shape[0], out_ch), y_amax=y_amax)
     return y
 
 
@@ -1264,91 +1276,49 @@ __all__ = [n for n in dir() if not n.startswith('_')] + ['SolveProblem', 'ConvEp
 # ------------------------------------------------------------------ the float64 forward
 # The generator's forward in double (include/rewriting_hip.h, last section): the same pieces as above on float64
 # tensors, module by module -- no packed weights, no epilogues, no routes.  Every tensor operand must be float64
-# (nothing is converted); the fp32 wrappers above keep refusing it.
+# (nothing is converted); the fp32 wrappers above keep refusing it.  The glue ops are the bodies of "generator pieces"
+# above, called with the dtype.
 _F64 = torch.float64
 
 
-def _d64(t, name):
-    return _dev(t, name, _F64)
-
-
-def _opt64(t, name):
-    return None if t is None else _dev(t, name, _F64)
-
-
 def pixel_norm_f64(x, eps=1e-8):
-    x = _d64(x, 'latent')
-    y = torch.empty_like(x)
-    check(lib().rw_pixel_norm_f64(_p(x), _p(y), x.shape[0], x.shape[1], float(eps), _stream()))
-    return y
+    return _pixel_norm_as(_F64, x, eps)
 
 
 def equal_linear_f64(x, weight, bias, w_scale, b_scale, act=False, alpha=0.2, act_scale=SQRT2):
     """x may be a strided row view (latent[:, index]): last dim contiguous."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != _F64:
-        _d64(x, 'input')
-    x = x.detach()
-    if x.ndim != 2 or x.stride(1) != 1:
-        x = x.reshape(x.shape[0], -1).contiguous()
-    weight = _d64(weight, 'weight')
-    bias = _opt64(bias, 'bias')
-    batch, in_dim = x.shape
-    out_dim = weight.shape[0]
-    if weight.shape[1] != in_dim:
-        raise ValueError('weight is %s, the input has %d features' % (tuple(weight.shape), in_dim))
-    y = torch.empty(batch, out_dim, device=x.device, dtype=_F64)
-    x_stride = x.stride(0) if batch > 1 else in_dim
-    check(lib().rw_equal_linear_f64(_p(x), _p(weight), _p(bias), _p(y), batch, in_dim, out_dim,
-                                    max(x_stride, in_dim), float(w_scale), float(b_scale), int(bool(act)),
-                                    float(alpha), float(act_scale), _stream()))
-    return y
+    return _equal_linear_as(_F64, x, weight, bias, w_scale, b_scale, act, alpha, act_scale)
 
 
 def adjust_latent_f64(w, avg, n_latent, psi):
-    w = _d64(w, 'latent')
-    avg = _opt64(avg, 'latent_avg')
-    out = torch.empty(w.shape[0], n_latent, w.shape[1], device=w.device, dtype=_F64)
-    check(lib().rw_adjust_latent_f64(_p(w), _p(avg), _p(out), w.shape[0], n_latent, w.shape[1], float(psi), _stream()))
-    return out
+    return _adjust_latent_as(_F64, w, avg, n_latent, psi)
 
 
 def style_mul_f64(x, style):
-    x = _d64(x, 'fmap')
-    style = _d64(style, 'style')
-    b, c, h, w = x.shape
-    if tuple(style.shape) != (b, c):
-        raise ValueError('style must be batch x channels')
-    y = torch.empty_like(x)
-    check(lib().rw_style_mul_f64(_p(x), _p(style), _p(y), b, c, h * w, _stream()))
-    return y
+    return _style_mul_as(_F64, x, style)
 
 
 def weight_sqsum_f64(weight, w_scale):
-    weight = _d64(weight, 'weight')
-    o, i = weight.shape[-4], weight.shape[-3]
-    taps = weight.shape[-1] * weight.shape[-2]
-    wsq = torch.empty(o, i, device=weight.device, dtype=_F64)
-    check(lib().rw_weight_sqsum_f64(_p(weight), _p(wsq), o, i, taps, float(w_scale), _stream()))
-    return wsq
+    return _weight_sqsum_as(_F64, weight, w_scale)
 
 
 def demod_f64(wsq, style, eps=1e-8):
-    wsq = _d64(wsq, 'wsq')
-    style = _d64(style, 'style')
-    b = style.shape[0]
-    o, i = wsq.shape
-    if style.shape[1] != i:
-        raise ValueError('style must be batch x in_ch')
-    out = torch.empty(b, o, device=wsq.device, dtype=_F64)
-    check(lib().rw_demod_f64(_p(wsq), _p(style), _p(out), b, o, i, float(eps), _stream()))
-    return out
+    return _demod_as(_F64, wsq, style, eps)
+
+
+def noise_add_f64(x, noise, noise_w):
+    return _noise_add_as(_F64, x, noise, noise_w)
+
+
+def to_rgb_f64(x, weight, style, bias, skip, w_scale):
+    return _to_rgb_as(_F64, x, weight, style, bias, skip, w_scale)
 
 
 def _conv_f64(entry, up, x, weight, w_scale, style, demod):
-    x = _d64(x, 'fmap')
-    weight = _d64(weight, 'weight')
-    style = _opt64(style, 'style')
-    demod = _opt64(demod, 'demod')
+    x = _dev(x, 'fmap', _F64)
+    weight = _dev(weight, 'weight', _F64)
+    style = _opt(style, 'style', _F64)
+    demod = _opt(demod, 'demod', _F64)
     b, i, h, w = x.shape
     o = weight.shape[-4]
     if tuple(weight.shape[-4:]) != (o, i, 3, 3) or weight.numel() != o * i * 9:
@@ -1373,30 +1343,3 @@ def conv_transpose3x3s2_f64(x, weight, w_scale, style=None, demod=None):
     return _conv_f64('rw_conv_transpose3x3s2_f64', True, x, weight, w_scale, style, demod)
 
 
-def noise_add_f64(x, noise, noise_w):
-    x = _d64(x, 'fmap')
-    noise = _d64(noise, 'noise')
-    noise_w = _d64(noise_w, 'noise weight')
-    b, c, h, w = x.shape
-    if noise.numel() != b * h * w:
-        raise ValueError('noise must be batch x (height * width)')
-    y = torch.empty_like(x)
-    check(lib().rw_noise_add_f64(_p(x), _p(noise), _p(noise_w), _p(y), b, c, h * w, _stream()))
-    return y
-
-
-def to_rgb_f64(x, weight, style, bias, skip, w_scale):
-    x = _d64(x, 'fmap')
-    weight = _d64(weight, 'rgb weight')
-    style = _d64(style, 'style')
-    bias = _opt64(bias, 'bias')
-    skip = _opt64(skip, 'skip')
-    b, c, h, w = x.shape
-    if weight.numel() != 3 * c or tuple(style.shape) != (b, c):
-        raise ValueError('rgb weight / style shapes')
-    if skip is not None and tuple(skip.shape) != (b, 3, h, w):
-        raise ValueError('skip shape')
-    y = torch.empty(b, 3, h, w, device=x.device, dtype=_F64)
-    check(lib().rw_to_rgb_f64(_p(x), _p(weight), _p(style), _p(bias), _p(skip), _p(y), b, c, h * w, float(w_scale),
-                              _stream()))
-    return y

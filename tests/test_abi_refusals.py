@@ -1,5 +1,5 @@
-"""What the C entries of the convolution families REFUSE, and the full tables of the pure shape / size functions,
-pinned against tests/golden/abi_refusals.json.
+"""What the C entries of the convolution families REFUSE -- the convolutions and the entries that measure and pack their
+weights -- and the full tables of the pure shape / size functions, pinned against tests/golden/abi_refusals.json.
 
 The table is recorded with this module's own recorder against a library built from the commit BEFORE a change to the
 launchers (never from the changed tree):
@@ -103,8 +103,54 @@ ENTRIES = {
 }
 
 
+
+
+# ---- the entries that measure (rw_*_absmax_f32) and pack a weight: 32 x 32 channels every form packs, `dst` = the
+# packed weight or the bound, and a channel pair the form does not pack
+def _pack_entry(unpacked, k4=False, bound=False, u_scale=False):
+    args = [('w', P)] + [('k4', P)] * k4 + [('dst', P)] * (not bound) + [('out_ch', 32), ('in_ch', 32)]
+    return dict(args=args + [('dst', P)] * bound + [('u_scale', 0.5)] * u_scale + [('stream', None)], unpacked=unpacked)
+
+
+PACK_ENTRIES = {
+    'rw_pack_conv_weight_wino_f32': _pack_entry(dict(out_ch=48)),
+    'rw_pack_conv_weight_wino4_f32': _pack_entry(dict(out_ch=24)),
+    'rw_conv_weight_wino4h_absmax_f32': _pack_entry(dict(out_ch=24), bound=True),
+    'rw_pack_conv_weight_wino4h_f32': _pack_entry(dict(out_ch=24), u_scale=True),
+    'rw_pack_conv_transpose_wino_f32': _pack_entry(dict(out_ch=24)),
+    'rw_conv_transpose_weight_winoh_absmax_f32': _pack_entry(dict(in_ch=12), bound=True),
+    'rw_pack_conv_transpose_winoh_f32': _pack_entry(dict(in_ch=12), u_scale=True),
+    'rw_pack_conv_transpose_blur_weight_wino4_f32': _pack_entry(dict(out_ch=6), k4=True),
+    'rw_conv_transpose_blur_weight_wino4h_absmax_f32': _pack_entry(dict(out_ch=6), k4=True, bound=True),
+    'rw_pack_conv_transpose_blur_weight_wino4h_f32': _pack_entry(dict(out_ch=6), k4=True, u_scale=True),
+    'rw_dconv_weight_absmax_f32': _pack_entry(dict(in_ch=24), bound=True),
+    'rw_pack_dconv_weight_f32': _pack_entry(dict(in_ch=24), u_scale=True),
+    'rw_dconv_transpose_blur_weight_absmax_f32': _pack_entry(dict(in_ch=24), k4=True, bound=True),
+    'rw_pack_dconv_transpose_blur_weight_f32': _pack_entry(dict(in_ch=24), k4=True, u_scale=True),
+}
+ENTRIES.update(PACK_ENTRIES)
+
+
+def pack_entry_cases(name):
+    spec = PACK_ENTRIES[name]
+    names = [a for a, _ in spec['args']]
+    cases = {'null_w': {'w': None}, 'null_dst': {'dst': None}, 'zero_out_ch': {'out_ch': 0},
+             'negative_in_ch': {'in_ch': -32}, 'unpacked_channels': dict(spec['unpacked'])}
+    if 'k4' in names:
+        cases['null_k4'] = {'k4': None}
+    if 'u_scale' in names:
+        cases['zero_u_scale'] = {'u_scale': 0.0}
+    # two defects at once: a bad argument is reported before channel counts the form does not pack
+    last = 'zero_u_scale' if 'u_scale' in names else 'null_dst'
+    for first in ('null_w', last):
+        cases[first + '+unpacked_channels'] = dict(cases[first], **spec['unpacked'])
+    return cases
+
+
 def entry_cases(name):
     """{case name: {argument (or 'ep.field' / 'rgb.field'): value}} -- the defects of one entry."""
+    if name in PACK_ENTRIES:
+        return pack_entry_cases(name)
     spec = ENTRIES[name]
     names = [a for a, _ in spec['args']]
     cases = {'null_x': {'x': None}, 'unsupported_shape': dict(spec['unsupported'])}
