@@ -41,7 +41,8 @@ typedef void* rw_stream_t; /* hipStream_t */
  * shapes, the point order of the packed F(4x4,3x3) weights; 4: rw_*_wino4h_*; 5: rw_dconv*; 6: rw_publish_scalar_f32.)
  * Buffers packed by an older library do not fit this one: repack, as the Python side does per weight version.
  * rw_resize_bilinear_u8 joins at 11, as rw_render_bytes_f32 and rw_png_* did: an entry that is only ADDED changes no
- * existing call, and the loader names the missing symbol of a library built before it ("stale ... no symbol"). */
+ * existing call, and the loader names the missing symbol of a library built before it ("stale ... no symbol").  So do
+ * rw_rgb_combine_up_f32 and rw_conv3x3_wino4[h]_to_rgb_up_f32 (the ToRGB skip upsampled inside its consumer). */
 int rw_abi_version(void);
 const char* rw_error_string(int code);
 
@@ -370,6 +371,15 @@ int rw_conv3x3_wino4h_f32(const float* x, const float* uf, float* y, int batch, 
 int rw_conv3x3_wino4h_to_rgb_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h, int w,
                                  float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, float u_inv,
                                  const float* x_amax, rw_stream_t stream);
+/* rw_conv3x3_wino4_to_rgb_f32 / rw_conv3x3_wino4h_to_rgb_f32 with the ToRGB's skip still one level down: skip_half
+ * (batch, 3, h / 2, w / 2) and the 4 x 4 FIR k4 that upsamples it (up 2, pads 2 / 1), upsampled in the epilogue with the
+ * bits of rw_upfirdn2d_f32; rgb->skip must be NULL.  Same image as with the materialised skip. */
+int rw_conv3x3_wino4_to_rgb_up_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h, int w,
+                                   float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb,
+                                   const float* skip_half, const float* k4, rw_stream_t stream);
+int rw_conv3x3_wino4h_to_rgb_up_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h, int w,
+                                    float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, float u_inv,
+                                    const float* x_amax, const float* skip_half, const float* k4, rw_stream_t stream);
 long long rw_packed_conv_transpose_blur_wino4h_elems(int out_ch, int in_ch);
 int rw_pack_conv_transpose_blur_weight_wino4h_f32(const float* w, const float* k4, float* uf, int out_ch, int in_ch,
                                                   float u_scale, rw_stream_t stream);
@@ -417,6 +427,11 @@ int rw_dconv3x3_rgb_partial_f32(const float* x, const float* wp, float* y, int b
                                 const float* x_amax, float* y_amax, rw_stream_t stream);
 int rw_rgb_combine_f32(const float* partials, int n_part, const float* bias, const float* skip, float* y, int batch,
                        int64_t hw, rw_stream_t stream);
+/* The same with the skip still one level down: skip_half (batch, 3, h / 2, w / 2) is upsampled inside the kernel by the
+ * 4 x 4 FIR k4 (rw_upfirdn2d_f32 with up 2, pads 2 / 1: same taps, same order) -- bit-identical to rw_upfirdn2d_f32 +
+ * rw_rgb_combine_f32, one launch and one h x w image less.  w % 4 == 0, h % 2 == 0. */
+int rw_rgb_combine_up_f32(const float* partials, int n_part, const float* bias, const float* skip_half, const float* k4,
+                          float* y, int batch, int h, int w, rw_stream_t stream);
 int rw_dconv3x3_to_rgb_supported(int out_ch, int in_ch, int h, int w);
 int rw_dconv3x3_to_rgb_f32(const float* x, const float* wp, int batch, int in_ch, int out_ch, int h, int w,
                            float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, float u_inv,

@@ -160,6 +160,14 @@ SIGNATURES = {
                                             POINTER(ConvEpilogue), POINTER(RgbEpilogue), c_float, c_void_p, c_void_p,
                                             c_void_p]),
     'rw_rgb_combine_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    'rw_rgb_combine_up_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p]),
+    'rw_conv3x3_wino4_to_rgb_up_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                               POINTER(ConvEpilogue), POINTER(RgbEpilogue), c_void_p, c_void_p,
+                                               c_void_p]),
+    'rw_conv3x3_wino4h_to_rgb_up_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                                POINTER(ConvEpilogue), POINTER(RgbEpilogue), c_float, c_void_p, c_void_p,
+                                                c_void_p, c_void_p]),
     'rw_dconv3x3_to_rgb_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rw_dconv3x3_to_rgb_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                        POINTER(ConvEpilogue), POINTER(RgbEpilogue), c_float, c_void_p, c_void_p]),

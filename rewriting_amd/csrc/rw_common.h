@@ -314,6 +314,46 @@ static inline float rw_weight_scale_of(float u_absmax) {
   return __builtin_bit_cast(float, (unsigned)(127 + 15 - eu) << 23);
 }
 
+// ---- the running RGB image upsampled where it is consumed (rgb_combine_up_kernel, the F(4x4) ToRGB epilogues).
+// acc[e] = output (oy, ox + e), e = 0..3, ox % 4 == 0, of upfirdn2d(up 2, 4 x 4 kernel, pads 2 / 1) of the hh x hw plane xm --
+// with the bits of upfirdn2d_up2k4_kernel (rw_ops.hip): from 0, kernel rows a ascending, then kernel columns c ascending,
+// taps outside the plane skipped (not added as zeros), every step the one expression acc += x * k.  kf: the 4 x 4 kernel as
+// stored; the taps are read flipped.  Output row oy takes the kernel rows a = (oy & 1), (oy & 1) + 2 at the input rows
+// (oy + a - 2) >> 1; output column ox + e the kernel columns c = (e & 1), (e & 1) + 2 at the input columns
+// (ox + e + c - 2) >> 1 = m - 1 + (e + c) / 2 with m = ox / 2: four input columns m - 1 .. m + 2 of two rows.
+__device__ __forceinline__ void rw_up2k4_row4(const float* __restrict__ xm, int hh, int hw, int oy, int ox,
+                                              const float* __restrict__ kf, float (&acc)[4]) {
+  acc[0] = acc[1] = acc[2] = acc[3] = 0.f;
+  const int m = ox >> 1;                          // m + 1 <= hw - 1: the output is 2 hw wide and ox + 4 <= 2 hw
+  const bool okl = m >= 1, okr = m + 2 < hw;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int vy = oy + (oy & 1) + 2 * j - 2, iy = vy >> 1;
+    const bool row = vy >= 0 && iy < hh;
+    // no branches: a skipped tap is a step whose result is not taken, read from a clamped address
+    const float* xr = xm + (int64_t)(row ? iy : 0) * hw + m;
+    // flipped: tap (a, c) is kf[3 - a][3 - c], a = (oy & 1) + 2 j.  Read per lane where they are used (the row depends on
+    // the lane): sixteen taps kept in scalar registers across an F(4x4) kernel's main loop cost it spills
+    const float* kr = kf + 4 * (3 - (oy & 1) - 2 * j);
+    const float k0 = kr[3], k1 = kr[2], k2 = kr[1], k3 = kr[0];
+    const float xl = xr[okl ? -1 : 0], x0 = xr[0], x1 = xr[1], x2 = xr[okr ? 2 : 1];
+    float t[4] = {acc[0], acc[1], acc[2], acc[3]};
+    t[0] += xl * k0;
+    t[0] = okl ? t[0] : acc[0];
+    t[0] += x0 * k2;
+    t[1] += x0 * k1;
+    t[1] += x1 * k3;
+    t[2] += x0 * k0;
+    t[2] += x1 * k2;
+    t[3] += x1 * k1;
+    float u = t[3];
+    u += x2 * k3;
+    t[3] = okr ? u : t[3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = row ? t[e] : acc[e];
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // The host prologue of the convolution entries: what every launcher checks, copies and finishes with.
 // ---------------------------------------------------------------------------------------

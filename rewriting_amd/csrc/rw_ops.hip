@@ -1190,6 +1190,45 @@ extern "C" int rw_rgb_combine_f32(const float* partials, int n_part, const float
   return RW_LAUNCH_RESULT();
 }
 
+// rgb_combine_kernel whose skip is still the running image one level down (h/2 x w/2): the up-2 FIR pass that used to
+// materialise it (upfirdn2d_up2k4_kernel, pads 2 / 1) happens here, in registers (rw_up2k4_row4) -- a launch and a write +
+// read of the h x w image less per ToRGB.  Same bits as the two launches: the upsampled value is added last, after the
+// partials in order and the bias.  Four output columns of one row per thread.  Scalar fp32 only.
+__global__ void __launch_bounds__(256) rgb_combine_up_kernel(const float* __restrict__ part, int n_part,
+                                                             const float* __restrict__ bias,
+                                                             const float* __restrict__ half,
+                                                             const float* __restrict__ k4, float* __restrict__ y,
+                                                             int64_t n4, int h, int w, int64_t stride4) {
+  const int w4 = w >> 2, hh = h >> 1, hw = w >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
+    float4 a = reinterpret_cast<const float4*>(part)[q];
+    for (int j = 1; j < n_part; ++j) {
+      const float4 v = reinterpret_cast<const float4*>(part)[q + j * stride4];
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    const int64_t row = q / w4;                 // (image * 3 + colour) * h + oy
+    const int64_t plane = row / h;
+    if (bias) {
+      const float bv = bias[plane % 3];
+      a.x += bv; a.y += bv; a.z += bv; a.w += bv;
+    }
+    float up[4];
+    rw_up2k4_row4(half + plane * hh * hw, hh, hw, (int)(row - plane * h), (int)(q - row * w4) * 4, k4, up);
+    a.x += up[0]; a.y += up[1]; a.z += up[2]; a.w += up[3];
+    reinterpret_cast<float4*>(y)[q] = a;
+  }
+}
+
+extern "C" int rw_rgb_combine_up_f32(const float* partials, int n_part, const float* bias, const float* skip_half,
+                                     const float* k4, float* y, int batch, int h, int w, rw_stream_t stream) {
+  RW_CHECK_ARG(partials && skip_half && k4 && y && n_part > 0 && batch > 0 && h > 0 && w > 0);
+  if (w % 4 || h % 2) return RW_ERR_UNSUPPORTED;
+  const int64_t n4 = (int64_t)batch * 3 * h * w / 4;
+  hipLaunchKernelGGL(rgb_combine_up_kernel, dim3(rw_stream_grid(n4, 256)), dim3(256), 0, rw_s(stream), partials, n_part,
+                     bias, skip_half, k4, y, n4, h, w, n4);
+  return RW_LAUNCH_RESULT();
+}
+
 // The same for maps whose pixel count is not a multiple of four (the cropped goal maps of a rewriter whose target
 // spans a ToRGB: rows of 5 x 7, ...): one pixel per thread, same order of additions.
 __global__ void __launch_bounds__(256) to_rgb_scalar_kernel(const float* __restrict__ x, const float* __restrict__ w,

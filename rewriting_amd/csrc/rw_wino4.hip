@@ -66,6 +66,9 @@ struct Wino4Problem {
   // rw_common.h); nullable: the slots + bound of the result -- the next layer's x_amax; 1 / (the packed weights' scale)
   const float* x_amax; float* y_amax;
   float u_inv;
+  // nullable: the 4 x 4 FIR of a ToRGB whose skip is still the running image one level down -- rgb_skip is then that
+  // (batch, 3, h / 2, w / 2) image, and rgb_epilogue upsamples it itself
+  const float* rgb_fir;
 };
 
 #define W4_PC 66                // patch columns: 64 + 2
@@ -1130,7 +1133,17 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
         const rw_f32x4 other = *reinterpret_cast<const rw_f32x4*>(&Ns[(wave ^ WGN) * NSZ + cc * 128 + slot]);
         const int64_t off = ((int64_t)ib * 3 + cc) * hw + pix;
         rw_f32x4 o4 = sum[cc] + other + (p.rgb_bias ? p.rgb_bias[cc] : 0.f);
-        if (p.rgb_skip) o4 += *reinterpret_cast<const rw_f32x4*>(p.rgb_skip + off);
+        if (p.rgb_fir) {                            // the skip from the image one level down
+          float up[4];
+          int uy = oy + lk, ux = ox, ub = ib, uh = p.h, uw = p.w;
+          // addresses and border tests are made here, not kept in registers across the main loop
+          asm volatile("" : "+v"(uy), "+v"(ux), "+s"(ub), "+s"(uh), "+s"(uw));
+          rw_up2k4_row4(p.rgb_skip + ((int64_t)ub * 3 + cc) * ((int64_t)(uh >> 1) * (uw >> 1)), uh >> 1, uw >> 1, uy, ux,
+                        p.rgb_fir, up);
+          o4 += rw_f32x4{up[0], up[1], up[2], up[3]};
+        } else if (p.rgb_skip) {
+          o4 += *reinterpret_cast<const rw_f32x4*>(p.rgb_skip + off);
+        }
         *reinterpret_cast<rw_f32x4*>(p.rgb_out + off) = o4;
       }
     }
@@ -1670,14 +1683,17 @@ extern "C" int rw_conv3x3_wino4_to_rgb_supported(int out_ch, int in_ch, int h, i
 
 static int wino4_to_rgb_launch(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h, int w,
                                float w_scale, const rw_conv_epilogue* ep, const rw_rgb_epilogue* rgb, bool h16,
-                               float u_inv, const float* x_amax, rw_stream_t stream) {
+                               float u_inv, const float* x_amax, const float* skip_half, const float* k4,
+                               rw_stream_t stream) {
   RW_CHECK_ARG(x && uf && rw_rgb_ok(rgb) && batch > 0 && in_ch > 0 && out_ch > 0);
+  RW_CHECK_ARG(!skip_half || (k4 && !rgb->skip));
   RW_CHECK_ARG(rw_epilogue_ok(ep));
   RW_CHECK_ARG(!h16 || (x_amax && u_inv > 0.f));
   if (!rw_conv3x3_wino4_to_rgb_supported(out_ch, in_ch, h, w) || !w4_window_aligned(x)) return RW_ERR_UNSUPPORTED;
   Wino4Problem p = {};
   wino4_fill(p, x, uf, nullptr, batch, in_ch, out_ch, h, w, w_scale, ep, u_inv, x_amax, nullptr);
   rw_fill_rgb(p, rgb);
+  if (skip_half) { p.rgb_skip = skip_half; p.rgb_fir = k4; }
   p.gpw = wino4_gpw(p, batch, 1);
   const int64_t work = (int64_t)batch * p.groups_y * (p.groups_x / p.gpw);
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
@@ -1700,12 +1716,34 @@ static int wino4_to_rgb_launch(const float* x, const float* uf, int batch, int i
 extern "C" int rw_conv3x3_wino4_to_rgb_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h,
                                            int w, float w_scale, const rw_conv_epilogue* ep,
                                            const rw_rgb_epilogue* rgb, rw_stream_t stream) {
-  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, false, 1.f, nullptr, stream);
+  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, false, 1.f, nullptr, nullptr, nullptr,
+                             stream);
 }
 
 extern "C" int rw_conv3x3_wino4h_to_rgb_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h,
                                             int w, float w_scale, const rw_conv_epilogue* ep,
                                             const rw_rgb_epilogue* rgb, float u_inv, const float* x_amax,
                                             rw_stream_t stream) {
-  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, true, u_inv, x_amax, stream);
+  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, true, u_inv, x_amax, nullptr, nullptr,
+                             stream);
+}
+
+// The two entries above with the ToRGB's skip still one level down: skip_half (batch, 3, h / 2, w / 2) and the 4 x 4 FIR k4
+// that upsamples it (up 2, pads 2 / 1); rgb->skip must be null.  Same image as with the materialised skip.
+extern "C" int rw_conv3x3_wino4_to_rgb_up_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h,
+                                              int w, float w_scale, const rw_conv_epilogue* ep,
+                                              const rw_rgb_epilogue* rgb, const float* skip_half, const float* k4,
+                                              rw_stream_t stream) {
+  RW_CHECK_ARG(skip_half && k4);
+  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, false, 1.f, nullptr, skip_half, k4,
+                             stream);
+}
+
+extern "C" int rw_conv3x3_wino4h_to_rgb_up_f32(const float* x, const float* uf, int batch, int in_ch, int out_ch, int h,
+                                               int w, float w_scale, const rw_conv_epilogue* ep,
+                                               const rw_rgb_epilogue* rgb, float u_inv, const float* x_amax,
+                                               const float* skip_half, const float* k4, rw_stream_t stream) {
+  RW_CHECK_ARG(skip_half && k4);
+  return wino4_to_rgb_launch(x, uf, batch, in_ch, out_ch, h, w, w_scale, ep, rgb, true, u_inv, x_amax, skip_half, k4,
+                             stream);
 }

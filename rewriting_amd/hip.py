@@ -303,15 +303,37 @@ def blur_noise_act(x, k4, noise, noise_w, bias, post_scale=None, y_amax=None):
     return y
 
 
+# A ToRGB's skip that is still the running image one level down: `image` (B, 3, H / 2, W / 2) and the 4 x 4 FIR `fir` that
+# Upsample would run over it (up 2, pads 2 / 1).  rgb_combine and conv3x3_wino4_to_rgb take it in the place of the
+# materialised (B, 3, H, W) skip and upsample it inside their kernel: the same bits, one launch and one image less.
+HalfSkip = _namedtuple('HalfSkip', 'image fir')
+
+
+def _half_skip(skip, b, h, w):
+    """The device tensors of a HalfSkip for a B x 3 x h x w image, shapes checked."""
+    image, fir = _dev(skip.image, 'rgb skip (half size)'), _dev(skip.fir, 'upsampling kernel')
+    if tuple(image.shape) != (b, 3, h // 2, w // 2) or h % 2 or w % 2 or tuple(fir.shape) != (4, 4):
+        raise ValueError('half-size rgb skip / kernel shapes')
+    return HalfSkip(image, fir)
+
+
 def rgb_combine(partials, bias, skip):
-    """ToRGB from the partial sums a convolution left (conv3x3_direct16_rgb_partial): sum over partials + bias + skip."""
+    """ToRGB from the partial sums a convolution left (conv3x3_direct16_rgb_partial): sum over partials + bias + skip.
+    skip: the (B, 3, H, W) image, or a HalfSkip -- upsampled inside the kernel."""
     partials = _dev(partials, 'rgb partial sums')
     bias = _opt(bias, 'rgb bias')
-    skip = _opt(skip, 'rgb skip')
     n, b, c, h, w = partials.shape
+    y = torch.empty(b, 3, h, w, device=partials.device, dtype=partials.dtype)
+    if isinstance(skip, HalfSkip):
+        if c != 3:
+            raise ValueError('rgb partial / skip shapes')
+        skip = _half_skip(skip, b, h, w)
+        check(lib().rw_rgb_combine_up_f32(_p(partials), n, _p(bias), _p(skip.image), _p(skip.fir), _p(y), b, h, w,
+                                          _stream()))
+        return y
+    skip = _opt(skip, 'rgb skip')
     if c != 3 or (skip is not None and tuple(skip.shape) != (b, 3, h, w)):
         raise ValueError('rgb partial / skip shapes')
-    y = torch.empty(b, 3, h, w, device=partials.device, dtype=partials.dtype)
     check(lib().rw_rgb_combine_f32(_p(partials), n, _p(bias), _p(skip), _p(y), b, h * w, _stream()))
     return y
 
@@ -564,14 +586,14 @@ def _conv(entries, x, packed, out_ch, w_scale, ep=None, style_demod=None, x_amax
     ones only where it has them:
 
         x, packed, [k4], [y], batch, in_ch, out_ch, h, w, w_scale, ep | (style, demod), [rgb], [impl], [post_scale],
-        [u_inv, x_amax], [y_amax], stream
+        [u_inv, x_amax], [y_amax], [skip_half, k4], stream
 
     entries: the entry's name, or (entry for a plain packing, entry for a split one) -- chosen here, once, by the scale
     that `packed` = (tensor, u_inv or None) carries (_packed).  ep / rgb: what _epilogue / _rgb_epilogue returned;
     style_demod: the two tensors of an entry without an epilogue block.  `slots`: the bracketed arguments this entry has
     -- a slot that is given as None is a null pointer, one that is not given is not in the entry's list.  A split
     packing adds u_inv, the bound of x (x_amax, measured here when None) and, where there is a y_amax slot, the buffer
-    that receives the bound of slots['y']; a plain one takes none of the three."""
+    that receives the bound of slots['y']; a plain one takes none of the three.  slots['half_skip']: a HalfSkip."""
     wp, u_inv = packed
     b, i, h, w = x.shape
     args = [_p(x), _p(wp)] + [_p(slots[s]) for s in ('k4', 'y') if s in slots] + [b, i, out_ch, h, w, float(w_scale)]
@@ -592,6 +614,8 @@ def _conv(entries, x, packed, out_ch, w_scale, ep=None, style_demod=None, x_amax
         if 'y_amax' in slots:
             y_amax = _amax_out(slots['y_amax'], slots['y'].numel())
             args.append(_p(y_amax))
+    if 'half_skip' in slots:
+        args += [_p(slots['half_skip'].image), _p(slots['half_skip'].fir)]
     entry = entries if isinstance(entries, str) else entries[u_inv is not None]
     check(getattr(lib(), entry)(*args, _stream()))
 
@@ -692,12 +716,17 @@ wino4_to_rgb_supported = _supported('rw_conv3x3_wino4_to_rgb_supported', 'Shapes
 def conv3x3_wino4_to_rgb(x, uf, out_ch, w_scale, rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, style=None,
                          demod=None, noise=None, noise_w=None, bias=None, act=False, x_amax=None):
     """conv3x3_wino4 with ToRGB in the epilogue (out_ch == 32): returns (None, rgb image); the feature map is not
-    written.  Split weights and x_amax as in conv3x3_wino4."""
+    written.  Split weights and x_amax as in conv3x3_wino4.  rgb_skip: the (B, 3, H, W) image, or a HalfSkip -- upsampled
+    in the epilogue."""
     x = _dev(x, 'fmap')
     rgb = _out(x, 3)
-    _conv(('rw_conv3x3_wino4_to_rgb_f32', 'rw_conv3x3_wino4h_to_rgb_f32'), x, _packed(uf, out_ch, x.shape[1], _WINO4),
+    entries, up = ('rw_conv3x3_wino4_to_rgb_f32', 'rw_conv3x3_wino4h_to_rgb_f32'), {}
+    if isinstance(rgb_skip, HalfSkip):
+        entries = ('rw_conv3x3_wino4_to_rgb_up_f32', 'rw_conv3x3_wino4h_to_rgb_up_f32')
+        up, rgb_skip = dict(half_skip=_half_skip(rgb_skip, x.shape[0], x.shape[2], x.shape[3])), None
+    _conv(entries, x, _packed(uf, out_ch, x.shape[1], _WINO4),
           out_ch, w_scale, _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax,
-          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch))
+          rgb=_rgb_epilogue(rgb_weight, rgb_style, rgb_bias, rgb_skip, rgb_scale, rgb, x, out_ch), **up)
     return None, rgb
 
 

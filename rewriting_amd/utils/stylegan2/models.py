@@ -173,6 +173,7 @@ def _idle():
         keep=[],            # trunk tensors the side streams still read: referenced until the join (_side_streams_joined)
         final=None,         # (last StyledConvSeq, its ToRGBF, latent index of the ToRGB) of the running forward
         image_path=False,   # inside the un-hooked forward of a whole generator (see routing.conv_algo)
+        inline_up=False,    # ... in which UpsampleO hands the running image on at half size (hip.HalfSkip): RW_RGB_INLINE_UP
         switches=None,      # routing.switches() of the running generator forward
         neighbours={},      # id(StyledConvSeq) -> _Neighbours of the running un-hooked forward (SeqStyleGAN2._topology)
         pre={},             # id(StyledConvSeq) -> (style, demod factors), id(ToRGBF) -> style: computed up front
@@ -704,8 +705,22 @@ class UpsampleO(Upsample):
         side = _rgb_stream()
         if side is None:
             return DataBag(d, output=super().forward(d.output))
+        if (_running.inline_up and d.output.dtype is torch.float32 and self.factor == 2
+                and tuple(self.kernel.shape) == (4, 4)):
+            # inside the un-hooked forward the ToRGB one level up reads the image where it is and upsamples it inside its
+            # own kernel (hip.HalfSkip); a consumer that cannot asks for this launch after all (_full_size)
+            return DataBag(d, output=hip.HalfSkip(d.output, self.kernel))
         with torch.cuda.stream(side):              # the previous RGB image was produced on this stream
             return DataBag(d, output=super().forward(d.output))
+
+
+def _full_size(skip):
+    """The running image as a tensor: the upsampling launch that UpsampleO left out (a hip.HalfSkip in the bag), issued on
+    the RGB stream as it would have been, for a ToRGB whose kernel takes the materialised image only."""
+    if not isinstance(skip, hip.HalfSkip):
+        return skip
+    with torch.cuda.stream(_rgb_stream()):
+        return op.upfirdn2d(skip.image, skip.fir, up=2, down=1, pad=(2, 1))
 
 
 class NoiseInjectionF(nn.Module):
@@ -824,11 +839,13 @@ class ToRGBF(nn.Module):
     def forward(self, d):
         if d.get('fused_rgb') is not None:          # already computed in the epilogue of the last styled conv
             return DataBag(d, output=d.fused_rgb, fused_rgb=None)
+        skip = d.get('output') if self.skip else None
+        if isinstance(skip, hip.HalfSkip) and d.get('rgb_partials') is None:
+            skip = _full_size(skip)                 # only rgb_combine upsamples the skip itself
         if _double('ToRGBF', d.fmap, weight=self.conv.weight, bias=self.bias, style=d.style,
-                   skip=d.get('output') if self.skip else None):
+                   skip=skip.image if isinstance(skip, hip.HalfSkip) else skip):
             return self._forward_f64(d)
-        skip = d.output if self.skip else None
-        if skip is not None and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
+        if torch.is_tensor(skip) and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
             up = self.upsample if hasattr(self, 'upsample') else Upsample([1, 3, 3, 1]).to(skip.device)
             if _rgb_stream() is None:
                 skip = up(skip)
@@ -1034,7 +1051,9 @@ class StyledConvSeq(nn.Sequential):
         """The last layer of the un-hooked generator, ToRGB in its epilogue: the map is never written.  Hands over `fused_rgb`."""
         _, torgb, idx = _running.final
         skip = d.output if torgb.skip else None
-        if skip is not None and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
+        if isinstance(skip, hip.HalfSkip) and route.kernel not in ('wino4', 'wino4_split'):
+            skip = _full_size(skip)                 # only the F(4x4) epilogues upsample the skip themselves
+        if torch.is_tensor(skip) and tuple(skip.shape[2:]) != tuple(d.fmap.shape[2:]):
             with _scope(final=None):        # not fused after all: as the bag came, before anything was launched
                 return self.forward(received)
         main = torch.cuda.current_stream()          # this form needs a device: without one it raises here, nothing launched
@@ -1193,7 +1212,11 @@ class SeqStyleGAN2(nn.Sequential):
             return self._forward_micro(input, mb, from_res, final)
         with contextlib.ExitStack() as scopes:
             main = scopes.enter_context(_side_streams_joined(input.device))
-            scopes.enter_context(_scope(final=final))
+            # the running image travels at half size between up_rgbK and the ToRGB that reads it only where nothing
+            # looks into the bags on the way: a forward hook of torch's on any module would
+            inline_up = (_running.image_path and _switches().rgb_inline_up
+                         and not any(m._forward_hooks or m._forward_pre_hooks for m in self.modules()))
+            scopes.enter_context(_scope(final=final, inline_up=inline_up))
             out = input
             for name, module in self._modules.items():
                 out = module(out)

@@ -43,6 +43,7 @@ Switches = namedtuple('Switches', [
     'mm_no_handover',     # RW_MM_NO_HANDOVER (on: '1'): every split kernel measures its input, no bound is handed over (diagnostics)
     'prefetch_styles',    # RW_PREFETCH_STYLES (off: '0'): styles and demodulation factors computed up front on the auxiliary stream
     'fuse_final_rgb',     # RW_FUSE_FINAL_RGB (off: '0'): ToRGB in the epilogue of the last styled convolution
+    'rgb_inline_up',      # RW_RGB_INLINE_UP (off: '0'): rgb_combine and the final F(4x4) ToRGB upsample the running image themselves
 ])
 
 
@@ -81,6 +82,7 @@ def switches():
         mm_no_handover=env('RW_MM_NO_HANDOVER') == '1',
         prefetch_styles=env('RW_PREFETCH_STYLES', '1') != '0',
         fuse_final_rgb=env('RW_FUSE_FINAL_RGB', '1') != '0',
+        rgb_inline_up=env('RW_RGB_INLINE_UP', '1') != '0',
     )
 
 
