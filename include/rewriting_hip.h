@@ -771,6 +771,46 @@ int rw_to_rgb_weight_sums_f32(const float* g, const float* x, float* scratch, fl
                               rw_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The perceptual network of the overfit loss: VF = vgg16(pretrained=True).features up to layer '20'
+ * (rewrite/ganrewrite.py:303-304), used as 1e-2 * mse_loss(VF(gt), VF(pred)) (:316-317).  Its eight convolutions with 64 .. 512
+ * channels are rw_conv3x3_wino_f32 / rw_conv3x3_f32 with w_scale 1 and no epilogue; the four entries below are the rest.
+ * float32 only, on the caller's stream, no atomics, nothing zeroed or drained: two runs give the same bits.  They join
+ * under ABI 11 like the other added entries.
+ * ------------------------------------------------------------------------------------- */
+
+/* What follows each convolution of VF (rewrite/ganrewrite.py:303-304,316-317: nn.ReLU after a biased nn.Conv2d, nn.MaxPool2d(2, 2)
+ * after three of them), in one pass:  y[b][c][p] = max(x[b][c][p] + bias[c], 0)  and, when pooled is not NULL,
+ * pooled[b][c][i][j] = the maximum of y over rows 2i, 2i + 1 and columns 2j, 2j + 1; pooled is (batch, ch, h / 2, w / 2),
+ * rounded down: an odd last row or column belongs to no window.  y may be NULL when pooled is given (the full-size map is
+ * then not stored), and y may be x.  16-byte accesses where w % 4 == 0 and x, y, pooled are 16-byte aligned, a scalar
+ * form elsewhere.  RW_ERR_BAD_ARGUMENT (nothing launched): a null x / bias, y and pooled both null, an extent < 1. */
+int rw_bias_relu_pool_f32(const float* x, const float* bias, float* y, float* pooled, int batch, int ch, int h, int w,
+                          rw_stream_t stream);
+
+/* The adjoint of rw_bias_relu_pool_f32 with respect to x (rewrite/ganrewrite.py:303-304,316-317: loss.backward() through VF),
+ * from the saved y (batch, ch, h, w).  pooled == 0: g is (batch, ch, h, w) and gx = y > 0 ? g : 0.  pooled == 1: g is
+ * (batch, ch, h / 2, w / 2); gx[p] = g[window of p] if y[p] > 0 and p is the FIRST maximum of its window in row-major order
+ * (torch's tie rule: four equal positive values send the gradient to the top-left one, an all-zero window sends nothing),
+ * else 0; positions in no window get 0.  gx (batch, ch, h, w) must be neither g nor y.  RW_ERR_BAD_ARGUMENT otherwise. */
+int rw_bias_relu_pool_grad_f32(const float* g, const float* y, float* gx, int batch, int ch, int h, int w, int pooled,
+                               rw_stream_t stream);
+
+/* The first layer of VF (rewrite/ganrewrite.py:303-304,316-317: features[0], features[1]):
+ *   y = relu(F.conv2d(x (batch, 3, h, w_), w (out_ch, 3, 3, 3) as stored, padding=1) + bias[o])
+ * 27 multiply-adds per output in the order (channel, ky, kx), then the bias.  One workgroup owns a 16 x 64 pixel tile of an
+ * image for all out-channels, whose weights sit in LDS.  RW_ERR_UNSUPPORTED (nothing launched): out_ch > 64, batch > 65535,
+ * h * w_ >= 2^31.  The MFMA forms do not take in_ch == 3. */
+int rw_conv3x3_rgb_f32(const float* x, const float* w, const float* bias, float* y, int batch, int out_ch, int h, int w_,
+                       rw_stream_t stream);
+
+/* Its adjoint to the image (rewrite/ganrewrite.py:303-304,316-317): gx (batch, 3, h, w_) = the correlation of
+ * g (batch, out_ch, h, w_) -- the gradient at the layer's output, already masked by its ReLU -- with the transposed, tap-flipped
+ * weights: gx[b][c][p] = sum_o sum_{ky,kx} w[o][c][ky][kx] g[b][o][py - ky + 1][px - kx + 1], out-channels in ascending
+ * order.  w as stored, (out_ch, 3, 3, 3).  Refusals as rw_conv3x3_rgb_f32. */
+int rw_conv3x3_rgb_input_grad_f32(const float* g, const float* w, float* gx, int batch, int out_ch, int h, int w_,
+                                  rw_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Generator forward in float64 -- the reference's generator runs after .double(): its two native ops dispatch double
  * (above) and everything else is torch.  These entries are the double forms of that torch arithmetic: every pointer is a
  * DEVICE pointer to contiguous float64, every scalar a double, every product and accumulation is in double.  The _f64

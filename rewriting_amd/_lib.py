@@ -205,6 +205,11 @@ SIGNATURES = {
                                          c_void_p]),
     'rw_to_rgb_weight_sums_scratch_elems': (ctypes.c_longlong, [c_int, c_int, c_int64]),
     'rw_to_rgb_weight_sums_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    # the perceptual network (rw_percept.hip): what its MFMA convolutions leave
+    'rw_bias_relu_pool_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rw_bias_relu_pool_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'rw_conv3x3_rgb_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'rw_conv3x3_rgb_input_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     # the float64 forward: the _f32 twin's arguments, double buffers and double scalars
     'rw_pixel_norm_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
     'rw_equal_linear_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -1299,6 +1299,91 @@ def to_rgb_weight_sums(g, x):
     return t
 
 
+# ------------------------------------------------------------------ the perceptual network (perceptual.py)
+CONV_RGB_MAX_OUT = 64           # PC_MAX_OUT of rw_percept.hip: every out-channel's weights sit in LDS
+
+
+def _fmap4(t, name):
+    t = _dev(t, name)
+    if t.dim() != 4 or 0 in t.shape:
+        raise ValueError('%s must be a non-empty (B, C, H, W) map, not %s' % (name, tuple(t.shape)))
+    return t
+
+
+def bias_relu_pool(x, bias, pool=False, keep=True, out=None):
+    """(y, pooled) of y = relu(x + bias[None, :, None, None]) and pooled = max_pool2d(y, 2, 2) in one pass
+    (rw_bias_relu_pool_f32).  pool=False: pooled is None; keep=False (with pool): the full-size map is not stored and y
+    is None; out: the tensor that receives y -- it may be x itself."""
+    x = _fmap4(x, 'fmap')
+    bias = _dev(bias, 'bias')
+    b, c, h, w = x.shape
+    if tuple(bias.shape) != (c,):
+        raise ValueError('bias must have one value per channel (%d), not %s' % (c, tuple(bias.shape)))
+    if not pool and not keep:
+        raise ValueError('bias_relu_pool: nothing to compute (pool=False, keep=False)')
+    y = None
+    if keep:
+        y = torch.empty_like(x) if out is None else _in_place(out, 'out', device=x.device)
+        if y.shape != x.shape:
+            raise ValueError('out is %s, the map %s' % (tuple(y.shape), tuple(x.shape)))
+    pooled = torch.empty(b, c, h // 2, w // 2, device=x.device, dtype=x.dtype) if pool else None
+    check(lib().rw_bias_relu_pool_f32(_p(x), _p(bias), _p(y), _p(pooled), b, c, h, w, _stream()))
+    return y, pooled
+
+
+def bias_relu_pool_grad(g, y, pooled=False):
+    """d x of bias_relu_pool from the saved y (rw_bias_relu_pool_grad_f32): g is the gradient at y (pooled=False) or at the
+    pooled map (pooled=True: routed to the first maximum of every window, where y is positive)."""
+    y = _fmap4(y, 'saved activation')
+    g = _dev(g, 'output gradient')
+    b, c, h, w = y.shape
+    want = (b, c, h // 2, w // 2) if pooled else (b, c, h, w)
+    if tuple(g.shape) != want or g.device != y.device:
+        raise ValueError('output gradient %s on %s does not belong to an activation %s on %s (pooled=%s)'
+                         % (tuple(g.shape), g.device, tuple(y.shape), y.device, bool(pooled)))
+    gx = torch.empty_like(y)
+    if g.numel() == 0:                  # a map below 2 x 2 has no window: nothing flows back
+        return gx.zero_()
+    check(lib().rw_bias_relu_pool_grad_f32(_p(g), _p(y), _p(gx), b, c, h, w, int(bool(pooled)), _stream()))
+    return gx
+
+
+def _rgb_weight(weight):
+    weight = _dev(weight, 'weight')
+    o = weight.shape[0] if weight.dim() else 0
+    if tuple(weight.shape) != (o, 3, 3, 3) or not 1 <= o <= CONV_RGB_MAX_OUT:
+        raise ValueError('the first layer\'s weight must be (out_ch <= %d, 3, 3, 3) as stored, not %s (RW_ERR_UNSUPPORTED, '
+                         'include/rewriting_hip.h)' % (CONV_RGB_MAX_OUT, tuple(weight.shape)))
+    return weight, o
+
+
+def conv3x3_rgb(x, weight, bias):
+    """relu(F.conv2d(x (B, 3, H, W), weight (out_ch, 3, 3, 3), bias, padding=1)) -- rw_conv3x3_rgb_f32."""
+    x = _fmap4(x, 'image')
+    weight, o = _rgb_weight(weight)
+    bias = _dev(bias, 'bias')
+    if x.shape[1] != 3 or tuple(bias.shape) != (o,) or weight.device != x.device or bias.device != x.device:
+        raise ValueError('conv3x3_rgb takes an image (B, 3, H, W) and a bias (%d,) on the weight\'s device, not %s / %s'
+                         % (o, tuple(x.shape), tuple(bias.shape)))
+    b, _, h, w = x.shape
+    y = torch.empty(b, o, h, w, device=x.device, dtype=x.dtype)
+    check(lib().rw_conv3x3_rgb_f32(_p(x), _p(weight), _p(bias), _p(y), b, o, h, w, _stream()))
+    return y
+
+
+def conv3x3_rgb_input_grad(g, weight):
+    """d image (B, 3, H, W) of conv3x3_rgb given g (B, out_ch, H, W), the gradient at its output already masked by the
+    ReLU -- rw_conv3x3_rgb_input_grad_f32."""
+    g = _fmap4(g, 'output gradient')
+    weight, o = _rgb_weight(weight)
+    if g.shape[1] != o or weight.device != g.device:
+        raise ValueError('output gradient %s does not belong to a weight %s' % (tuple(g.shape), tuple(weight.shape)))
+    b, _, h, w = g.shape
+    gx = torch.empty(b, 3, h, w, device=g.device, dtype=g.dtype)
+    check(lib().rw_conv3x3_rgb_input_grad_f32(_p(g), _p(weight), _p(gx), b, o, h, w, _stream()))
+    return gx
+
+
 __all__ = [n for n in dir() if not n.startswith('_')] + ['SolveProblem', 'ConvEpilogue']
 
 

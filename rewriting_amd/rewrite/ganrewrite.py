@@ -242,7 +242,7 @@ class ProgressiveGanRewriter(object):
     def apply_overfit(self, request, niter=20001, lr=0.01, update_callback=None, feature_net=None):
         """The overfit baseline (rewrite/ganrewrite.py:171-181): paste the selected object into the image itself and
         train every weight toward it (all_weights_insert).  feature_net: see there."""
-        _need_feature_net(feature_net)
+        feature_net = self._feature_net(feature_net)
         o_imgnum, o_mask = request['object']
         p_imgnum, p_mask = request['paste']
         rgb_clip, _, obj_area, _ = self.rgb_from_selection(o_imgnum, o_mask)
@@ -373,8 +373,10 @@ class ProgressiveGanRewriter(object):
         L1 on the image (cropped to bounds = (top, left, bottom, right) if given) plus 1e-2 of the mean squared
         difference of feature_net's responses.  The gradient reaches the parameters through the adjoints of
         utils/stylegan2/grad.py.  feature_net (VF of the reference: torchvision's VGG16 features[:21], whose weights have
-        to be downloaded) is the caller's: any module or function from images to feature tensors."""
-        _need_feature_net(feature_net)
+        to be downloaded) is the caller's -- any module or function from images to feature tensors -- or, when None, that
+        network on the HIP kernels (perceptual.VGG16Features) with the weights of the file the environment variable
+        RW_VGG16_WEIGHTS names, built once per rewriter."""
+        feature_net = self._feature_net(feature_net)
         x, z = self.detach(x), self.detach(z)
 
         def compute_loss():
@@ -391,6 +393,20 @@ class ProgressiveGanRewriter(object):
         nethook.set_requires_grad(True, *params)
         self._adam(params, lr, niter, compute_loss, update_callback)
         _weights_changed()
+
+    def _feature_net(self, feature_net):
+        """The caller's perceptual network, or the default one: VGG16 features[:21] on the HIP kernels with the weights of
+        the file RW_VGG16_WEIGHTS names, built once per rewriter (and again when the variable names another file)."""
+        if feature_net is not None:
+            return feature_net
+        from .. import perceptual
+        path = perceptual.default_weights()
+        if path is None:
+            _need_feature_net(None)
+        built = self.__dict__.get('_default_feature_net')
+        if built is None or built[0] != path:
+            built = self._default_feature_net = (path, perceptual.vgg16_features(path).to(self.device))
+        return built[1]
 
     # ---- context direction ----------------------------------------------------------------
     def _key_observations(self, imgnum_mask_pairs):
@@ -879,7 +895,9 @@ def _need_feature_net(feature_net):
             '(rewrite/ganrewrite.py:171-181,300-331); torchvision weights are unavailable and the '
             'path is outside the rule-editing hot path (SURVEY.md section 8a row d5) -- pass the perceptual network '
             'yourself as feature_net= (a module from images to feature maps, e.g. a VGG16 features[:21] with its '
-            'weights loaded); without one neither apply_overfit nor all_weights_insert runs')
+            'weights loaded), or name a torchvision VGG16 state dict in the environment variable RW_VGG16_WEIGHTS: '
+            'rewriting_amd.perceptual then runs that network on the HIP kernels; without either neither apply_overfit '
+            'nor all_weights_insert runs')
 
 
 def _weights_changed():
