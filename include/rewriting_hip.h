@@ -811,6 +811,54 @@ int rw_conv3x3_rgb_input_grad_f32(const float* g, const float* w, float* gx, int
                                   rw_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LPIPS and the masked edit distances (metrics/distances.py:18-59: PerceptualLoss -- models.PerceptualLoss(model='net-lin',
+ * net='vgg', spatial=True), sum(loss * w) / sum(w); :96-136: compute_dl).  The VGG16 convolutions are the entries above; these are
+ * what follows them.  float32 only, forward only, on the caller's stream, no atomics, nothing zeroed or drained, every sum in a
+ * fixed order: two runs give the same bits.  They join under ABI 11 like the other added entries.
+ * ------------------------------------------------------------------------------------- */
+
+/* One tap of LPIPS v0.1 (metrics/distances.py:23-26,51: the lpips(im0, im1) call):
+ *   d[b][p] = sum_c lin[c] (f0[b][c][p] / (sqrt(sum_c f0[b][c][p]^2) + 1e-10) - f1[b'][c][p] / (sqrt(sum_c f1[b'][c][p]^2) + 1e-10))^2
+ * f0 (batch, ch, hw), f1 (f1_batch, ch, hw) with f1_batch == batch or 1 (b' = 0: broadcast), lin (ch), d (batch, hw).  Any ch >= 1
+ * and hw >= 1.  Formed from the normalised difference as written (never from its expansion, which cancels for nearly equal
+ * maps); a pixel whose vector is zero in both maps gives 0.  Up to 8192 channels a workgroup stages its run of pixels of both
+ * maps in LDS, so that every value is read from memory once; above, the maps are read twice.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null pointer, an extent < 1, f1_batch neither batch nor 1. */
+int rw_lpips_tap_f32(const float* f0, const float* f1, const float* lin, float* d, int batch, int f1_batch, int ch,
+                     int64_t hw, rw_stream_t stream);
+
+/* Floats of the scratch buffer rw_lpips_combine_f32 (with sums) and rw_masked_l1_rgb_f32 need for `batch` images of hw pixels:
+ * one pair per workgroup, stored plainly.  -1: refused (batch < 1, hw < 1 or hw above 256 * 28 * 4096 pixels -- a term of a sum
+ * passes through at most 62 additions, metrics/distances.py:53-54's sums over an image are never serial). */
+long long rw_lpips_reduce_scratch_elems(int batch, int64_t hw);
+
+/* The tap maps of one LPIPS evaluation: d[k] is (batch, h[k], w[k]). */
+#define RW_LPIPS_MAX_TAPS 8
+typedef struct rw_lpips_maps {
+  const float* d[RW_LPIPS_MAX_TAPS];
+  int h[RW_LPIPS_MAX_TAPS];
+  int w[RW_LPIPS_MAX_TAPS];
+  int n;
+} rw_lpips_maps;
+
+/* spatial=True LPIPS and its weighted mean (metrics/distances.py:51-55):
+ *   out[b][y][x] = sum_k F.interpolate(d_k, size=(h, w), mode='bilinear', align_corners=False)[b][y][x]
+ *   sums[b] = (sum_p out[b][p] weight[b'][p], sum_p weight[b'][p])
+ * The per-axis tables come from the host (float64, rounded once): for tap k, idx + k (2h + 2w) holds the rows' first and
+ * second index (h each), then the columns' (w each); lam + k (h + w) the rows' weight of the second index, then the
+ * columns'.  Indices are clamped into the tap's map.  out (batch, h, w) and sums (batch, 2) are both optional, not both
+ * null; weight (weight_batch, h, w), weight_batch == batch or 1, nullable: all ones.  sums needs scratch of
+ * rw_lpips_reduce_scratch_elems(batch, h * w) floats.  RW_ERR_BAD_ARGUMENT: null tables, n outside 1 .. RW_LPIPS_MAX_TAPS,
+ * a null or empty tap, sums without scratch; RW_ERR_UNSUPPORTED: batch > 65535, an image the reduction refuses. */
+int rw_lpips_combine_f32(const rw_lpips_maps* taps, const int* idx, const float* lam, const float* weight, int weight_batch,
+                         float* out, float* sums, float* scratch, int batch, int h, int w, rw_stream_t stream);
+
+/* compute_dl's pixel mode (metrics/distances.py:131-133): sums[b] = (sum_p mask[b'][p] sum_c |a[b][c][p] - b[b][c][p]|, sum_p mask[b'][p])
+ * for a, b (batch, 3, hw) and mask (mask_batch, hw) float32, mask_batch == batch or 1.  scratch as above. */
+int rw_masked_l1_rgb_f32(const float* a, const float* b, const float* mask, int mask_batch, float* sums, float* scratch,
+                         int batch, int64_t hw, rw_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Generator forward in float64 -- the reference's generator runs after .double(): its two native ops dispatch double
  * (above) and everything else is torch.  These entries are the double forms of that torch arithmetic: every pointer is a
  * DEVICE pointer to contiguous float64, every scalar a double, every product and accumulation is in double.  The _f64

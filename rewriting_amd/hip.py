@@ -1384,6 +1384,86 @@ def conv3x3_rgb_input_grad(g, weight):
     return gx
 
 
+# ------------------------------------------------------------------ LPIPS and the masked edit distances (lpips.py, distances.py)
+LPIPS_MAX_TAPS = _lib.LPIPS_MAX_TAPS
+
+
+def _reduce_scratch(batch, hw, device):
+    n = lib().rw_lpips_reduce_scratch_elems(batch, hw)
+    if n < 0:
+        raise ValueError('an image of %d pixels is more than the per-image reduction takes (RW_ERR_UNSUPPORTED, '
+                         'include/rewriting_hip.h)' % hw)
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def lpips_tap(f0, f1, lin):
+    """d (B, H, W) of one LPIPS tap (rw_lpips_tap_f32): sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 with the norms
+    over the channels of a pixel; f0 (B, C, H, W), f1 (B or 1, C, H, W), lin (C,).  Read in place."""
+    f0 = _fmap4(_in_place(f0, 'tap'), 'tap')
+    f1 = _in_place(f1, 'second tap', device=f0.device)
+    lin = _in_place(lin, 'lin weight', device=f0.device)
+    b, c, h, w = f0.shape
+    if f1.dim() != 4 or tuple(f1.shape[1:]) != (c, h, w) or f1.shape[0] not in (1, b) or tuple(lin.shape) != (c,):
+        raise ValueError('lpips_tap takes two maps (B, C, H, W) and (B or 1, C, H, W) and a weight (C,), not %s / %s / %s'
+                         % (tuple(f0.shape), tuple(f1.shape), tuple(lin.shape)))
+    d = torch.empty(b, h, w, device=f0.device, dtype=torch.float32)
+    check(lib().rw_lpips_tap_f32(_p(f0), _p(f1), _p(lin), _p(d), b, f1.shape[0], c, h * w, _stream()))
+    return d
+
+
+def lpips_combine(taps, tables, size, weight=None, want_map=True, want_sums=False):
+    """(out (B, 1, H, W) or None, sums (B, 2) or None) of rw_lpips_combine_f32: out = the sum over the tap maps (B, h_k, w_k) of
+    their bilinear up-sampling to size = (H, W) with tables = (idx int32 (K, 2H + 2W), lam float32 (K, H + W)) of
+    lpips.device_tables; sums[b] = (sum out * weight, sum weight), weight (B or 1, 1, H, W) or None (all ones)."""
+    if not 1 <= len(taps) <= LPIPS_MAX_TAPS:
+        raise ValueError('lpips_combine takes 1 .. %d tap maps, not %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
+                         % (LPIPS_MAX_TAPS, len(taps)))
+    if not (want_map or want_sums):
+        raise ValueError('lpips_combine: nothing to compute (want_map=False, want_sums=False)')
+    taps = [_in_place(t, 'tap map') for t in taps]
+    device = taps[0].device
+    idx = _in_place(tables[0], 'index table', torch.int32, device)
+    lam = _in_place(tables[1], 'weight table', device=device)
+    h, w = int(size[0]), int(size[1])
+    b = taps[0].shape[0]
+    k = len(taps)
+    if h < 1 or w < 1 or tuple(idx.shape) != (k, 2 * h + 2 * w) or tuple(lam.shape) != (k, h + w):
+        raise ValueError('the tables %s / %s do not belong to %d taps and an output of %d x %d'
+                         % (tuple(idx.shape), tuple(lam.shape), k, h, w))
+    maps = _lib.LpipsMaps()
+    for n, t in enumerate(taps):
+        if t.dim() != 3 or t.shape[0] != b or 0 in t.shape or t.device != device:
+            raise ValueError('tap map %d is %s on %s; every one is (B = %d, h, w) on %s' % (n, tuple(t.shape), t.device, b, device))
+        maps.d[n], maps.h[n], maps.w[n] = t.data_ptr(), t.shape[1], t.shape[2]
+    maps.n = k
+    if weight is not None:
+        weight = _in_place(weight, 'weight', device=device)
+        if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, h, w) or weight.shape[0] not in (1, b):
+            raise ValueError('the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s' % (b, h, w, tuple(weight.shape)))
+    out = torch.empty(b, 1, h, w, device=device, dtype=torch.float32) if want_map else None
+    sums = torch.empty(b, 2, device=device, dtype=torch.float32) if want_sums else None
+    scratch = _reduce_scratch(b, h * w, device) if want_sums else None
+    check(lib().rw_lpips_combine_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(weight), weight.shape[0] if weight is not None else 0,
+                                     _p(out), _p(sums), _p(scratch), b, h, w, _stream()))
+    return out, sums
+
+
+def masked_l1(a, b, mask):
+    """(B, 2): per image (sum_p mask sum_c |a - b|, sum_p mask) for images a, b (B, 3, H, W) and mask (B or 1, H, W) float32 --
+    rw_masked_l1_rgb_f32."""
+    a = _fmap4(_in_place(a, 'images'), 'images')
+    b = _in_place(b, 'second images', device=a.device)
+    mask = _in_place(mask, 'mask', device=a.device)
+    n, c, h, w = a.shape
+    if c != 3 or b.shape != a.shape or mask.dim() != 3 or tuple(mask.shape[1:]) != (h, w) or mask.shape[0] not in (1, n):
+        raise ValueError('masked_l1 takes two image batches (B, 3, H, W) and a mask (B or 1, H, W), not %s / %s / %s'
+                         % (tuple(a.shape), tuple(b.shape), tuple(mask.shape)))
+    sums = torch.empty(n, 2, device=a.device, dtype=torch.float32)
+    scratch = _reduce_scratch(n, h * w, a.device)
+    check(lib().rw_masked_l1_rgb_f32(_p(a), _p(b), _p(mask), mask.shape[0], _p(sums), _p(scratch), n, h * w, _stream()))
+    return sums
+
+
 __all__ = [n for n in dir() if not n.startswith('_')] + ['SolveProblem', 'ConvEpilogue']
 
 

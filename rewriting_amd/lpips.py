@@ -1,0 +1,248 @@
+"""LPIPS (v0.1, ``net-lin``, ``vgg``) on the HIP kernels: the perceptual distance of the reference's edit tables.
+
+The reference wraps ``models.PerceptualLoss(model='net-lin', net='vgg', spatial=True)`` of the PerceptualSimilarity submodule
+(metrics/distances.py:18-59) and reduces its per-pixel map with a mask, ``sum(loss * w) / sum(w)``.  The submodule is not needed:
+the arithmetic is
+
+1. images in [-1, 1]; ``x' = (x - shift[c]) / scale[c]`` with ``shift = (-.030, -.088, -.188)``, ``scale = (.458, .448, .450)``;
+2. torchvision's ``vgg16().features[:30]``; the five taps are the ReLU outputs before each pool (features 3, 8, 15, 22, 29:
+   64, 128, 256, 512, 512 channels at H, H/2, H/4, H/8, H/16);
+3. per tap and pixel ``d_k = sum_c lin_k[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2`` (``hip.lpips_tap``);
+4. ``spatial=True``: the sum of the ``d_k`` up-sampled to (H, W), bilinear, ``align_corners=False``; ``spatial=False``: the sum
+   of their means; with a weight ``w``: ``sum(out * w) / sum(w)`` per image (``hip.lpips_combine``).
+
+``LPIPS`` is built from a ``perceptual.VGG16Features`` -- whose nine blocks it reuses -- and four more blocks (21 with its
+pool, 24, 26, 28).  The two images' networks run block by block side by side, and a tap is dropped as soon as its ``d_k``
+exists; maps narrower than 32 take the split-K form of the direct sum (SPLIT_K below).  Forward only, float32 on a HIP
+device only.  No weights ship: ``lpips_vgg(vgg_path, lin_path)`` loads a torchvision VGG16 state dict and the ``lin`` layers
+of LPIPS v0.1 (``lin{k}.model.1.weight``); the environment variables ``RW_VGG16_WEIGHTS`` and ``RW_LPIPS_WEIGHTS`` name the
+two files.
+"""
+import functools
+import os
+
+import numpy
+import torch
+from torch import nn
+
+from . import hip, perceptual
+
+WEIGHTS_ENV = 'RW_LPIPS_WEIGHTS'
+SHIFT = (-.030, -.088, -.188)
+SCALE = (.458, .448, .450)
+# the convolutions past perceptual.LAYERS, same columns
+TAIL_LAYERS = ((21, 512, 512, True), (24, 512, 512, False), (26, 512, 512, False), (28, 512, 512, False))
+TAPS = (2, 7, 14, 21, 28)               # the convolutions whose activated maps LPIPS reads
+CHANNELS = (64, 128, 256, 512, 512)
+# Maps narrower than SPLIT_K_BELOW take the direct sum whose four waves split K (hip.conv3x3's impl 6, the form made for
+# 4 x 4 .. 16 x 16 maps): a term's chain of additions is a quarter as long.  Against float64, 2-norm over whole maps
+# (profiles/lpips_route_accuracy.json): 1.5e-7 .. 4.0e-7 where the serial direct sum has 2.9e-7 .. 8.0e-7 and F(2x2,3x3)
+# 2.3e-7 .. 6.5e-7 -- and nearly equal pairs amplify the features' rounding by 1 / |n0 - n1|.
+SPLIT_K = 6
+SPLIT_K_BELOW = 32
+MIN_SIZE = 16                           # four pools: a 16 x 16 image leaves 1 x 1 maps at the last tap
+
+
+@functools.lru_cache(maxsize=256)
+def upsample_table(n_in, n_out):
+    """(i0, i1 int32, lam float64), each (n_out,): output sample o of ``F.interpolate(mode='bilinear', align_corners=False)``
+    along an axis of n_in samples is ``(1 - lam[o]) * x[i0[o]] + lam[o] * x[i1[o]]``.  torch's arithmetic
+    (upsample_bilinear2d) in float64: ``src = max((o + 0.5) * n_in / n_out - 0.5, 0)``, ``i0 = floor(src)``,
+    ``i1 = min(i0 + 1, n_in - 1)``, ``lam = src - i0``.  The one place it lives; read-only arrays."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError('lpips.upsample_table: lengths must be positive, not %d -> %d' % (n_in, n_out))
+    scale = n_in / n_out
+    src = numpy.maximum((numpy.arange(n_out, dtype=numpy.float64) + 0.5) * scale - 0.5, 0.0)
+    i0 = numpy.minimum(src.astype(numpy.int64), n_in - 1)
+    i1 = numpy.minimum(i0 + 1, n_in - 1)
+    lam = src - i0
+    tables = (i0.astype(numpy.int32), i1.astype(numpy.int32), lam)
+    for t in tables:
+        t.setflags(write=False)
+    return tables
+
+
+_device_tables = {}
+
+
+def device_tables(tap_sizes, size, device):
+    """(idx int32 (K, 2H + 2W), lam float32 (K, H + W)) on `device` for taps of tap_sizes = ((h_k, w_k), ...) up-sampled to
+    size = (H, W), as rw_lpips_combine_f32 reads them: per tap the rows' i0 and i1, then the columns'; the rows' lam, then the
+    columns' -- rounded to float32 here, once.  Copied once per (sizes, device)."""
+    device = torch.device(device)
+    h, w = int(size[0]), int(size[1])
+    key = (tuple((int(a), int(b)) for a, b in tap_sizes), h, w, device.type, device.index)
+    tables = _device_tables.get(key)
+    if tables is None:
+        idx = numpy.empty((len(key[0]), 2 * h + 2 * w), dtype=numpy.int32)
+        lam = numpy.empty((len(key[0]), h + w), dtype=numpy.float32)
+        for k, (hk, wk) in enumerate(key[0]):
+            y0, y1, ly = upsample_table(hk, h)
+            x0, x1, lx = upsample_table(wk, w)
+            idx[k] = numpy.concatenate([y0, y1, x0, x1])
+            lam[k] = numpy.concatenate([ly, lx]).astype(numpy.float32)
+        tables = (torch.from_numpy(idx).to(device), torch.from_numpy(lam).to(device))
+        if len(_device_tables) >= 64:
+            _device_tables.clear()
+        _device_tables[key] = tables
+    return tables
+
+
+class LPIPS(nn.Module):
+    """``forward(im0, im1, w=None, spatial=True)``: LPIPS v0.1 (vgg) of images in [-1, 1], (B, 3, H, W) float32 on a HIP device;
+    im1 may have batch 1 (its network then runs once).  The parameters are ``features.N.*`` (the VGG16Features handed in),
+    ``tail.N.*`` (N = 21, 24, 26, 28) and ``lins.k`` (C_k,); all frozen."""
+
+    def __init__(self, features=None):
+        super().__init__()
+        self.features = features if features is not None else perceptual.VGG16Features()
+        if not isinstance(self.features, perceptual.VGG16Features):
+            raise TypeError('rewriting_amd: LPIPS is built from a perceptual.VGG16Features, not %s' % type(features).__name__)
+        self.tail = nn.ModuleDict({str(index): perceptual._Block(in_ch, out_ch, pool) for index, in_ch, out_ch, pool in TAIL_LAYERS})
+        self.lins = nn.ParameterList([nn.Parameter(torch.zeros(c), requires_grad=False) for c in CHANNELS])
+        self.register_buffer('shift', torch.tensor(SHIFT).view(1, 3, 1, 1), persistent=False)
+        self.register_buffer('scale', torch.tensor(SCALE).view(1, 3, 1, 1), persistent=False)
+
+    def blocks(self):
+        """[(index in torchvision's features, block)]: the thirteen convolutions of features[:30]"""
+        head = [(index, block) for (index, _, _, _), block in zip(perceptual.LAYERS, self.features.blocks())]
+        return head + [(index, self.tail[str(index)]) for index, _, _, _ in TAIL_LAYERS]
+
+    def _check(self, im0, im1, w):
+        for name, im in (('im0', im0), ('im1', im1)):
+            if not isinstance(im, torch.Tensor) or im.dim() != 4 or im.shape[1] != 3 or 0 in im.shape:
+                raise ValueError('rewriting_amd: LPIPS takes images (B, 3, H, W), %s is %s'
+                                 % (name, tuple(im.shape) if isinstance(im, torch.Tensor) else type(im).__name__))
+            if not hip.on_device(im):
+                raise RuntimeError('rewriting_amd: LPIPS: %s is on %s; the HIP kernels need a GPU tensor (there is no CPU '
+                                   'fallback)' % (name, im.device))
+            if im.dtype != torch.float32:
+                raise RuntimeError('rewriting_amd: LPIPS: %s is %s; the metric is fp32 only -- cast with .float() (nothing is '
+                                   'converted)' % (name, im.dtype))
+            if im.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError('rewriting_amd: LPIPS is forward only (the reference uses it under no_grad, as a metric): %s '
+                                   'requires a gradient -- call it under torch.no_grad() or detach the image' % name)
+        b, _, h, wd = im0.shape
+        if tuple(im1.shape[1:]) != (3, h, wd) or im1.shape[0] not in (1, b) or im1.device != im0.device:
+            raise ValueError('rewriting_amd: LPIPS: im1 is %s on %s, im0 %s on %s -- the sizes must match, im1\'s batch may be 1'
+                             % (tuple(im1.shape), im1.device, tuple(im0.shape), im0.device))
+        if h < MIN_SIZE or wd < MIN_SIZE:
+            raise ValueError('rewriting_amd: LPIPS halves its maps four times: an image of %d x %d leaves no last tap, it must '
+                             'be at least %d x %d' % (h, wd, MIN_SIZE, MIN_SIZE))
+        if w is not None:
+            if not isinstance(w, torch.Tensor) or w.dim() != 4 or tuple(w.shape[1:]) != (1, h, wd) or w.shape[0] not in (1, b):
+                raise ValueError('rewriting_amd: LPIPS: the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s'
+                                 % (b, h, wd, tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__))
+            if not hip.on_device(w) or w.device != im0.device:
+                raise RuntimeError('rewriting_amd: LPIPS: the weight is on %s, the images on %s (there is no CPU fallback)'
+                                   % (w.device, im0.device))
+            if w.dtype != torch.float32:
+                raise RuntimeError('rewriting_amd: LPIPS: the weight is %s; the metric is fp32 only -- cast with .float()' % w.dtype)
+        for name, p in self.named_parameters():
+            if p.requires_grad:
+                raise RuntimeError('rewriting_amd: LPIPS is frozen and forward only: parameter %s requires a gradient -- call '
+                                   'requires_grad_(False) on it' % name)
+            if p.dtype != torch.float32 or p.device != im0.device:
+                raise RuntimeError('rewriting_amd: LPIPS: parameter %s is %s on %s, the images float32 on %s -- move the '
+                                   'network with .to(device)' % (name, p.dtype, p.device, im0.device))
+
+    def forward(self, im0, im1, w=None, spatial=True, taps=None):
+        """spatial=True: (B, 1, H, W), the per-pixel distance; spatial=False: (B, 1, 1, 1), the sum of the taps' means; with
+        w (B or 1, 1, H, W): (B,), ``sum(out * w, [1, 2, 3]) / sum(w, [1, 2, 3])`` (metrics/distances.py:49-56) -- the map is
+        then never written.  taps: a list that receives the five d_k (B, h_k, w_k)."""
+        self._check(im0, im1, w)
+        b, _, h, wd = im0.shape
+        with torch.no_grad():
+            x0 = (im0.detach() - self.shift) / self.scale       # not foldable into layer 0: its zero padding comes after
+            x1 = (im1.detach() - self.shift) / self.scale
+            ds = []
+            for index, block in self.blocks():
+                tap = index in TAPS
+                impl = SPLIT_K if x0.shape[3] < SPLIT_K_BELOW else None
+                y0, x0 = block.activate(x0, keep=tap, impl=impl)
+                y1, x1 = block.activate(x1, keep=tap, impl=impl)
+                if tap:
+                    ds.append(hip.lpips_tap(y0, y1, self.lins[len(ds)]))
+                del y0, y1                                      # a tap lives until its d_k exists
+            del x0, x1
+            if taps is not None:
+                taps.extend(ds)
+            sizes = tuple((d.shape[1], d.shape[2]) for d in ds)
+            if spatial:
+                out, sums = hip.lpips_combine(ds, device_tables(sizes, (h, wd), im0.device), (h, wd), weight=w,
+                                              want_map=w is None, want_sums=w is not None)
+                return out if w is None else sums[:, 0] / sums[:, 1]
+            out = 0
+            for d, size in zip(ds, sizes):                      # the same entry at the tap's own size: (sum d_k, pixels)
+                _, sums = hip.lpips_combine([d], device_tables((size,), size, im0.device), size, want_map=False, want_sums=True)
+                out = out + sums[:, 0] / sums[:, 1]
+            if w is None:
+                return out.view(b, 1, 1, 1)
+            _, sums = hip.lpips_combine([out.view(b, 1, 1).contiguous()], device_tables(((1, 1),), (h, wd), im0.device), (h, wd),
+                                        weight=w, want_map=False, want_sums=True)
+            return sums[:, 0] / sums[:, 1]
+
+
+def _lin_weights(lin_sd):
+    found = []
+    for k, c in enumerate(CHANNELS):
+        names = ('lin%d.model.1.weight' % k, 'lin%d' % k)
+        have = [n for n in names if n in lin_sd]
+        if not have:
+            raise KeyError('rewriting_amd: the state dict lacks %s (or bare %s) of LPIPS v0.1' % names)
+        value = lin_sd[have[0]]
+        if tuple(value.shape) not in ((1, c, 1, 1), (c,)):
+            raise ValueError('rewriting_amd: %r is %s, LPIPS (vgg) has (1, %d, 1, 1) there' % (have[0], tuple(value.shape), c))
+        found.append(value.detach().to(torch.float32).reshape(c))
+    return found
+
+
+def from_state_dicts(vgg_sd, lin_sd):
+    """An LPIPS with the convolutions of `vgg_sd` -- the keys ``0.weight`` ... ``28.bias``, bare or with torchvision's prefix
+    ``features.`` (``classifier.*`` is ignored) -- and the lin layers of `lin_sd`: ``lin{k}.model.1.weight`` (1, C, 1, 1) as
+    LPIPS v0.1 stores them, or bare ``lin{k}``."""
+    bare = {}
+    for key, value in vgg_sd.items():
+        if key.startswith('classifier.'):
+            continue
+        bare[key[len('features.'):] if key.startswith('features.') else key] = value
+    net = LPIPS(perceptual.from_state_dict({k: v for k, v in bare.items()
+                                            if not (k.split('.')[0].isdigit() and int(k.split('.')[0]) > perceptual.LAST_LAYER)}))
+    own = {'%d.%s' % (index, kind): (out_ch, in_ch, 3, 3) if kind == 'weight' else (out_ch,)
+           for index, in_ch, out_ch, _ in TAIL_LAYERS for kind in ('weight', 'bias')}
+    for name in bare:
+        index = name.split('.')[0]
+        if index.isdigit() and int(index) > perceptual.LAST_LAYER and name not in own:
+            raise KeyError('rewriting_amd: %r is no parameter of VGG16 features[:30] (past layer 20: %s)'
+                           % (name, ', '.join(sorted(own, key=lambda n: (int(n.split('.')[0]), n)))))
+    missing = sorted(set(own) - set(bare))
+    if missing:
+        raise KeyError('rewriting_amd: the state dict lacks %s of VGG16 features[:30]' % ', '.join(missing))
+    for name, shape in own.items():
+        if tuple(bare[name].shape) != shape:
+            raise ValueError('rewriting_amd: %r is %s, VGG16 has %s there' % (name, tuple(bare[name].shape), shape))
+        index, kind = name.split('.')
+        getattr(net.tail[index], kind).data.copy_(bare[name].detach().to(torch.float32))
+    for p, value in zip(net.lins, _lin_weights(lin_sd)):
+        p.data.copy_(value)
+    return net.eval()
+
+
+def default_weights():
+    """The file RW_LPIPS_WEIGHTS names, or None when it is unset or names no readable file."""
+    path = os.environ.get(WEIGHTS_ENV)
+    return path if path and os.path.isfile(path) and os.access(path, os.R_OK) else None
+
+
+def lpips_vgg(vgg_path=None, lin_path=None):
+    """from_state_dicts of two files, on the host: a torchvision VGG16 state dict (default: the file RW_VGG16_WEIGHTS names)
+    and the lin layers of LPIPS v0.1 (default: RW_LPIPS_WEIGHTS).  No weights ship with the package."""
+    vgg_path = vgg_path or perceptual.default_weights()
+    lin_path = lin_path or default_weights()
+    if not vgg_path or not lin_path:
+        raise FileNotFoundError('rewriting_amd: LPIPS needs a torchvision VGG16 state dict and the lin layers of LPIPS v0.1; no '
+                                'weights ship with the package -- pass both paths or set %s and %s to readable files'
+                                % (perceptual.WEIGHTS_ENV, WEIGHTS_ENV))
+    return from_state_dicts(torch.load(vgg_path, map_location='cpu', weights_only=True),
+                            torch.load(lin_path, map_location='cpu', weights_only=True))

@@ -54,22 +54,27 @@ class _Block(nn.Module):
         state['_derived'] = _DerivedWeights()       # caches are not copied or pickled
         return state
 
-    def _conv(self, x, name, out_ch, weight):
+    def _conv(self, x, name, out_ch, weight, impl=None):
         """The plain stride-1 convolution of x to out_ch channels with `weight()` (1, out_ch, in_ch, 3, 3), on the route
-        its shape takes; the packing is cached as `name`."""
+        its shape takes -- or, with impl, on that form of the direct sum (``hip.conv3x3``'s impl); the packing is cached as
+        `name`."""
         _, i, h, w = x.shape
+        if impl is not None:
+            wp = self._derived.get(name + '/direct', self.weight, lambda: hip.pack_conv_weight(weight(), 0))
+            return hip.conv3x3(x, wp, out_ch, 1.0, impl=impl)
         if hip.wino_supported(out_ch, i, h, w):
             uf = self._derived.get(name + '/wino', self.weight, lambda: hip.pack_conv_weight_wino(weight()))
             return hip.conv3x3_wino(x, uf, out_ch, 1.0)
         wp = self._derived.get(name + '/direct', self.weight, lambda: hip.pack_conv_weight(weight(), 0))
         return hip.conv3x3(x, wp, out_ch, 1.0, impl=0)
 
-    def activate(self, x, keep):
-        """(y or None, what the next block reads) of the convolution of x; keep: the full-size activated map y is wanted."""
+    def activate(self, x, keep, impl=None):
+        """(y or None, what the next block reads) of the convolution of x; keep: the full-size activated map y is wanted;
+        impl: the form of the direct sum to take instead of the route the shape takes (lpips.py)."""
         if self.in_ch == 3:
             y = hip.conv3x3_rgb(x, self.weight, self.bias)
             return y, y
-        pre = self._conv(x, 'forward', self.out_ch, lambda: self.weight.detach()[None])
+        pre = self._conv(x, 'forward', self.out_ch, lambda: self.weight.detach()[None], impl)
         y, pooled = hip.bias_relu_pool(pre, self.bias, pool=self.pool, keep=keep or not self.pool, out=pre)
         return y, (pooled if self.pool else y)
 
