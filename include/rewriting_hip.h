@@ -460,6 +460,19 @@ int rw_tconv_blur_supported(int out_ch, int in_ch, int h, int w);
 int rw_tconv_blur_f32(const float* x, const float* wp, const float* k4, float* y, int batch, int in_ch, int out_ch, int h,
                       int w, float w_scale, const rw_conv_epilogue* ep, const float* post_scale, float u_inv,
                       const float* x_amax, float* y_amax, rw_stream_t stream);
+/* The STAGED forms of rw_tconv_blur_f32 (round 12).  The one-workgroup-per-tile forms (RW_TCONV_TY 8 / 16 / 32) convert the
+ * whole in_ch window once per 16 (32) out-channels; with a scratch buffer they convert the map ONCE -- a streaming pre-pass
+ * writes it as ready operand words, rw_tconv_stage_bytes(batch, in_ch, out_ch, h, w) bytes (as many as the map; 0 where
+ * the launch would not take a staged form: its shape, its form, the environment) -- and the
+ * convolution copies its windows from there into LDS.  Same bits: the pre-pass runs the other form's arithmetic.
+ *   rw_tconv_stage_buffer(stream, ptr, bytes): the scratch of `stream` on the current device (16-byte aligned; the caller
+ *   owns it and keeps it alive until the launches that use it have run; ptr NULL with bytes 0 forgets it).  This is the one
+ *   piece of state the library keeps, and it decides nothing about results.  Not to be called while the stream is being
+ *   captured.  rw_tconv_blur_f32 takes the staged form when the stream's buffer is large enough, the form is one of the
+ *   three and in_ch >= RW_TCONV_STAGED_MIN_IN (environment; default 256); RW_TCONV_STAGED = 0 turns it off.  Both launches
+ *   go to `stream`, back to back.  The two entries join under ABI 11 like the other added entries. */
+long long rw_tconv_stage_bytes(int batch, int in_ch, int out_ch, int h, int w);
+int rw_tconv_stage_buffer(rw_stream_t stream, void* ptr, long long bytes);
 
 /* rw_conv_transpose3x3s2_wino_f32 (the F(2,2) quads of the stride-2 transposed convolution) with its 25 GEMMs on the
  * 16-bit matrix pipe and the exact f16 operand split of the wino4h entry points (rw_upwino.hip): one

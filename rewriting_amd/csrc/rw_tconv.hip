@@ -41,6 +41,7 @@
 // output where the direct 16-tap form spends 16, and a third of its LDS reads; any other FIR takes the 16-tap form.
 #include "rw_common.h"
 #include <stdio.h>
+#include <mutex>
 
 struct TconvProblem {
   const float* x; const unsigned char* wp; float* y; const float* k4;
@@ -106,7 +107,10 @@ __device__ __forceinline__ float tc_mul(float a, float b) {
   return r;
 }
 
-template <int TY, int WAVES, int NT>
+// STAGED (round 12; p.x is then the map as operand words): the window and the weights arrive by LDS-direct copies of READY operand words -- split_map_kernel
+// below has multiplied, split and laid out the whole map once -- where the other form loads fp32, converts and writes the
+// window once per 16 NT out-channels.  See "staging by copies" in the body.
+template <int TY, int WAVES, int NT, bool STAGED = false>
 __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   constexpr int THREADS = 64 * WAVES;
   constexpr int PR = TY + 2;                        // position rows
@@ -150,7 +154,8 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     rw_split_scales<14>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
   }
   const float gain = p.act ? 1.4142135623730951f : 1.f, slope = p.act ? 0.2f : 1.f;
-  for (int i = tid; i < p.in_ch; i += THREADS) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
+  if constexpr (!STAGED)                            // (STAGED: the style and in_scale are in the words)
+    for (int i = tid; i < p.in_ch; i += THREADS) St[i] = (p.style ? p.style[(int64_t)ib * p.in_ch + i] : 1.0f) * in_scale;
   if (tid < OC) {
     const int o = OC * ot + tid;
     Sc[tid] = (p.demod ? p.demod[(int64_t)ib * p.out_ch + o] * p.w_scale : p.w_scale) * out_scale * gain;
@@ -248,6 +253,64 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         *reinterpret_cast<rw_f32x4*>(dst + (tid + k * THREADS) * 16) = wraw[k];
   };
 
+  // ---- staging by copies (STAGED).  p.x holds the map as the words the window buffer takes --
+  // words[image][chunk][y][x][quad][8 halves], split_map_kernel -- so a window is copied, not converted: one
+  // `buffer_load_dwordx4 ... lds` (rw_dma_buffer_b128) moves 64 lanes x 16 bytes into 1 KB of contiguous LDS = 16 consecutive
+  // window pixels x their four 16-byte slots.  Lane (pixel, slot s) fetches quad s ^ rw_swz(column): the swizzle lives in the
+  // lane's global offset, computed once; a pixel outside the image has the out-of-range offset and lands as zeros.  The
+  // NPIX * 4 slots are NPC_S pieces, PPW per wave: piece wave + WAVES k, the ones past the end (and the last one, which would
+  // overrun the buffer) start at slot NSLOT - 64 and write bytes a sibling writes too, with the same values -- no exec mask,
+  // no wave-dependent branch.  The chunk advance is the scalar offset.  The weights come the same way
+  // (rw_dma_global_b128_s): 9 NT pieces of 1 KB, NWS per wave, clamped to the last one.
+  // Nothing but these copies and the epilogue's traffic is in the vector-memory queue of a STAGED workgroup, and the compiler
+  // cannot count them (rw_dconv.hip): the waits are written by hand.  A chunk's copies are requested during the chunk before
+  // it, behind its first position blocks, one request per block; the chunk ends with vmcnt(0) -- this wave issues nothing
+  // behind them, so N = 0 -- lgkmcnt(0) and the raw barrier.  Two buffers as before; the noise loads and the stores come
+  // after the loop, when no copy is in flight.
+  constexpr int NSLOT = NPIX * 4, NPC_S = (NSLOT + 63) / 64, PPW = (NPC_S + WAVES - 1) / WAVES;
+  constexpr int NWPC = 9 * NT, NWS = (NWPC + WAVES - 1) / WAVES;
+  static_assert(NSLOT >= 64 && NWS + PPW <= 3 * BPW, "one request behind each position block of a chunk");
+  typedef __attribute__((address_space(3))) unsigned char* lds_b;
+  const unsigned ls_base = (unsigned)(size_t)(lds_b)Ls, wl_base = (unsigned)(size_t)(lds_b)Wl;
+  // (the descriptor of rw_image_rsrc over the words of image ib, as the four integers the assembly takes)
+  const unsigned long long xw_addr = (unsigned long long)(p.x + (int64_t)ib * p.in_ch * hw);
+  const rw_i32x4 xsrc_w = {(int)(unsigned)xw_addr, (int)(unsigned)(xw_addr >> 32), (int)((int64_t)p.in_ch * hw * 4), 0x00020000};
+  int voff[PPW], sslot[PPW];                        // the lane's global byte offset within (image, chunk); the piece's first slot
+  if constexpr (STAGED) {
+#pragma unroll
+    for (int k = 0; k < PPW; ++k) {
+      const int first = 64 * (wave + WAVES * k);
+      sslot[k] = first < NSLOT - 64 ? first : NSLOT - 64;
+      const int L = sslot[k] + lane, pix = L >> 2, s = L & 3;
+      const int r = pix / TC_WC, c = pix - r * TC_WC;
+      const int iy = I0 - 2 + r, ix = J0 - 2 + c;
+      const bool ok = iy >= 0 && iy < p.h && ix >= 0 && ix < p.w;
+      voff[k] = ok ? (iy * p.w + ix) * 64 + ((s ^ rw_swz(c)) << 4) : 0x7ffffff0;
+    }
+  }
+  // request q of the copies of chunk c into buffer buf: the weight pieces first, then the window's
+  // (q is a constant wherever the position-block loops are unrolled: the comparisons fold)
+  auto copy_request = [&](int c, int buf, int q) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < NWS; ++k)
+      if (q == k) {
+        const int first = wave + WAVES * k, wpc = first < NWPC ? first : NWPC - 1;
+        const int n = wpc / 9, r = wpc - 9 * n;
+        rw_dma_global_b128_s(wl_base + (unsigned)(buf * WCH + wpc * 1024), lane * 16,
+                             wsrc + ((int64_t)n * T + 9 * c) * 1024 + r * 1024);
+      }
+#pragma unroll
+    for (int k = 0; k < PPW; ++k)
+      if (q == NWS + k)
+        rw_dma_buffer_b128(ls_base + (unsigned)(buf * BUFB + sslot[k] * 16), voff[k], xsrc_w, c * hw4 * 16);
+  };
+  auto copy_wait = [&]() __attribute__((always_inline)) {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0070);             // vmcnt(0) lgkmcnt(0): this wave's copies have landed, its LDS reads are done
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+
   // ---- this wave's position blocks: operand addresses of the lane's position q = 16 blk + lt (clamped), pixel offsets
   // (a, b) = x[i - a][j - b] at window pixel (r + 1 - a, c + 1 - b)
   // (the ROW ABOVE, a = 1; the position's own row is + TC_WC * 64: an immediate.  They include the window buffer's offset and
@@ -305,7 +368,9 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
 #if TC_PROF
       if (b < 4) { if (grp == 0) { TP_ADD(tp_g0, tp); } else if (grp == 1) { TP_ADD(tp_g1, tp); } else { TP_ADD(tp_g2, tp); } }
 #endif
-      if constexpr (grp < SI) {
+      if constexpr (STAGED) {
+        if (st) copy_request(c + 1, buf ^ 1, grp * BPW + b);        // chunk c + 1, one request behind each block
+      } else if constexpr (grp < SI) {
         if (b == 0 && st) stage_store_part(c + 1, buf ^ 1, rw_int<grp>(), rw_int<0>(), rw_int<2>());
         if (b == 1 && st) stage_store_part(c + 1, buf ^ 1, rw_int<grp>(), rw_int<2>(), rw_int<4>());
         if constexpr (BPW >= 4) {
@@ -420,10 +485,13 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
       const unsigned delta = buf ? (unsigned)-BUFB : (unsigned)BUFB;
 #pragma unroll
       for (int b = 0; b < BPW; ++b) { pb0[b] += delta; pb1[b] += delta; }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0): the requests of chunk c + 2 stay in flight across the barrier
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      if constexpr (STAGED) copy_wait();            // the copies of chunk c + 1 have landed
+      else {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0): the requests of chunk c + 2 stay in flight across the barrier
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
       TP_ADD(tp_bar, tp);
     }
   };
@@ -431,6 +499,11 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   // ---- prologue: chunk 0 requested, converted, written; chunk 1 (in_ch == 16: chunk 0 again, never converted) requested, in
   // the order of a chunk's requests, pinned -- the waits of the loop count the requests behind the one they need
   TP_NOW(tp_all);
+  if constexpr (STAGED) {                           // chunk 0 copied; chunk 1 is requested inside chunk 0
+#pragma unroll
+    for (int q = 0; q < NWS + PPW; ++q) copy_request(0, 0, q);
+    copy_wait();
+  } else {
   wstage_load(0);
 #pragma unroll
   for (int s = 0; s < SI; ++s) {
@@ -450,6 +523,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     __builtin_amdgcn_sched_barrier(0);
     wstage_load(c1);
     __builtin_amdgcn_sched_barrier(0);
+  }
   }
 
 #if TC_PROF
@@ -612,7 +686,6 @@ __global__ void __launch_bounds__(512, 1) tconv_blur_t16_kernel(const TconvProbl
 __global__ void __launch_bounds__(512, 1) tconv_blur_n32_kernel(const TconvProblem p) { tconv_body<8, 8, 2>(p); }
 // (four waves per SIMD -- <8, 8> twice per CU, <16, 16> once -- do not fit: 128 registers against 48 accumulators + ~125
 // for the operands and the epilogue, 120 - 150 spilled)
-
 // ---------------------------------------------------------------------------------------
 // Third form: the waves of a workgroup SPECIALISE and the workgroup is PERSISTENT (rw_dconv.hip's dconv_ws_body, applied to
 // the kernel above).  Measured on the forms above (profiles/r05g, layer 17): the window loads cost 2.2 ms of 7.8 (every
@@ -1636,11 +1709,127 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
   if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
 }
 
+// ---------------------------------------------------------------------------------------
+// tconv_body's three shapes (tconv_blur_t8 / t16 / n32_kernel) with the window copied from the words of split_map_kernel (STAGED).  The timing ablations TC_ABL 1, 256
+// and 512 switch parts of the register staging and mean nothing here; the others (2, 8 .. 128) work as in the forms above.
+__global__ void __launch_bounds__(256, 2) tconv_blur_t8s_kernel(const TconvProblem p) { tconv_body<8, 4, 1, true>(p); }
+__global__ void __launch_bounds__(512, 1) tconv_blur_t16s_kernel(const TconvProblem p) { tconv_body<16, 8, 1, true>(p); }
+__global__ void __launch_bounds__(512, 1) tconv_blur_n32s_kernel(const TconvProblem p) { tconv_body<8, 8, 2, true>(p); }
+
+// ---- the pre-pass of the STAGED forms: the fp32 map (batch, in_ch, h, w) -> words[image][chunk = c / 16][y][x][quad g]
+// [8 halves], word = [Vh c0..3 | Vl c0..3] of the channels 16 chunk + 4 g .. + 3 of a pixel: what stage_store_part writes into
+// the window buffer, minus the swizzle, as many bytes as the map.  The same arithmetic on the same inputs -- the per-image
+// smax, in_scale = rw_split_scales<14>(bound smax), the style times in_scale rounded first (St[]), one v_mul_f32 per value,
+// rw_split4 -- so the MFMA operands are the bits the other form makes.  A thread takes four columns of a quad's four
+// channels (four 16-byte loads) and writes four words; the four quads of a pixel sit in neighbouring lanes: 64-byte runs.
+// Grid: (h w / (256 iters), in_ch / 16, batch), h w a multiple of 512: no tail.
+struct SplitMapProblem {
+  const float* x; unsigned char* words; const float* style; const float* x_amax;
+  int batch, in_ch, h, w, iters;
+  float u_inv;
+};
+__global__ void __launch_bounds__(256) split_map_kernel(const SplitMapProblem p) {
+  __shared__ float Red[4];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ib = blockIdx.z, ch = blockIdx.y;
+  float in_scale, out_scale;
+  {
+    const float smax = rw_block_max<4>(rw_style_absmax_wave<256>(p, ib, tid), lane, wave, Red);
+    rw_split_scales<14>(rw_bound_load(p.x_amax) * smax, p.u_inv, in_scale, out_scale);
+  }
+  const int g = tid & 3, c0 = 16 * ch + 4 * g;
+  float sv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) sv[k] = (p.style ? p.style[(int64_t)ib * p.in_ch + c0 + k] : 1.0f) * in_scale;
+  const int64_t hw = (int64_t)p.h * p.w;
+  const float* xi = p.x + ((int64_t)ib * p.in_ch + c0) * hw;
+  unsigned char* wo = p.words + ((int64_t)ib * p.in_ch + 16 * ch) * hw * 4 + g * 16;
+  for (int it = 0; it < p.iters; ++it) {
+    const int64_t pix = 4 * (((int64_t)blockIdx.x * p.iters + it) * 64 + (tid >> 2));       // four pixels of one row
+    rw_f32x4 raw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) raw[k] = *reinterpret_cast<const rw_f32x4*>(xi + k * hw + pix);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      *reinterpret_cast<rw_f16x8*>(wo + (pix + e) * 64) =
+          rw_split4(tc_mul(raw[0][e], sv[0]), tc_mul(raw[1][e], sv[1]), tc_mul(raw[2][e], sv[2]), tc_mul(raw[3][e], sv[3]));
+  }
+}
+
 static bool tconv_shape_ok(int out_ch, int in_ch, int h, int w) {
   return out_ch > 0 && out_ch % 16 == 0 && in_ch >= 16 && in_ch % 16 == 0 && in_ch <= 512 && w % TC_TX == 0 && h % 16 == 0;
 }
 
 extern "C" int rw_tconv_blur_supported(int out_ch, int in_ch, int h, int w) { return tconv_shape_ok(out_ch, in_ch, h, w) ? 1 : 0; }
+
+// ---- the scratch of the STAGED forms: one buffer per (device, stream), registered by the caller, who owns it
+#ifndef RW_TCONV_STAGED_DEFAULT
+#define RW_TCONV_STAGED_DEFAULT 1          // RW_TCONV_STAGED unset: the staged forms run where a buffer is registered
+#endif
+#ifndef RW_TCONV_STAGED_MIN_IN_DEFAULT
+#define RW_TCONV_STAGED_MIN_IN_DEFAULT 256 // RW_TCONV_STAGED_MIN_IN unset: the fewest input channels that take them
+#endif
+// the form of a launch (what RW_TCONV_TY means), from the environment and the channels
+static int tconv_form(int in_ch, int out_ch) {
+  // the form: RW_TCONV_TY = 0 the specialised persistent kernel, 8 / 16 the two shapes of tconv_body; unset: by input channels -- the persistent kernel where a tile has few chunks (<= 128
+  // channels: its staging waves run ahead through the epilogue), the one-workgroup-per-CU shape where the MFMAs dominate
+  // (profiles/r05q: layer 17 6.4 against 7.1 ms, layer 15 4.6 / 4.9, layer 13 3.7 / 3.7, layer 11 3.3 / 3.2, layer 9 1.9 / 1.7)
+  // (RW_TCONV_PERSISTENT = 0 / 2: which of the two persistent kernels the automatic choice means)
+  const int persistent = rw_env_int("RW_TCONV_PERSISTENT", 0) == 2 ? 2 : 0;
+  // (RW_TCONV_N32 = "lo:hi": the input-channel range the automatic choice gives to the 32-out-channel form.  Default: none --
+  // stand-alone it ties the persistent form on layer 15 (4.2 against 4.3 ms), inside the forward the persistent form is ahead:
+  // 1526 - 1528 against 1507 - 1518 img/s, same box, interleaved, profiles/r06ak)
+  int n32_lo = 1, n32_hi = 0;
+  if (const char* ne = getenv("RW_TCONV_N32")) { if (sscanf(ne, "%d:%d", &n32_lo, &n32_hi) != 2) { n32_lo = 1; n32_hi = 0; } }
+  const int sel = rw_env_int("RW_TCONV_TY", out_ch % 32 == 0 && in_ch >= n32_lo && in_ch <= n32_hi ? 32
+                                           : (in_ch >= 32 && in_ch <= 128 ? persistent : 16));
+  return sel;
+}
+// does a launch of this form and these channels take the staged form when it finds a buffer?
+static bool tconv_staged_wanted(int sel, int in_ch, int batch) {
+  if ((sel == 0 || sel == 2 || sel == 12) && in_ch >= 32) return false;      // the persistent forms stage in their own waves
+  return rw_env_int("RW_TCONV_STAGED", RW_TCONV_STAGED_DEFAULT) != 0 &&
+         in_ch >= rw_env_int("RW_TCONV_STAGED_MIN_IN", RW_TCONV_STAGED_MIN_IN_DEFAULT) && batch <= 65535;
+}
+namespace {
+struct StageBuffer { int dev; hipStream_t stream; void* ptr; long long bytes; };
+constexpr int kStageBuffers = 64;
+StageBuffer g_stage[kStageBuffers];          // ptr == nullptr: a free entry
+std::mutex g_stage_lock;
+}
+// bytes of the scratch this launch would use: the map's own size, or 0 where no staged form runs (shape, form, environment)
+extern "C" long long rw_tconv_stage_bytes(int batch, int in_ch, int out_ch, int h, int w) {
+  if (batch <= 0 || !tconv_shape_ok(out_ch, in_ch, h, w) || (int64_t)in_ch * h * w * 4 > 0x7fffffffLL) return 0;
+  if (!tconv_staged_wanted(tconv_form(in_ch, out_ch), in_ch, batch)) return 0;
+  return (long long)batch * in_ch * h * w * 4;
+}
+extern "C" int rw_tconv_stage_buffer(rw_stream_t stream, void* ptr, long long bytes) {
+  RW_CHECK_ARG((ptr == nullptr) == (bytes == 0) && bytes >= 0 && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return RW_ERR_UNSUPPORTED;
+  std::lock_guard<std::mutex> hold(g_stage_lock);
+  StageBuffer* slot = nullptr;
+  for (StageBuffer& b : g_stage)
+    if (b.ptr && b.dev == dev && b.stream == rw_s(stream)) slot = &b;
+  if (!ptr) {
+    if (slot) *slot = StageBuffer{};
+    return 0;
+  }
+  for (StageBuffer& b : g_stage)
+    if (!slot && !b.ptr) slot = &b;
+  if (!slot) return RW_ERR_UNSUPPORTED;
+  *slot = StageBuffer{dev, rw_s(stream), ptr, bytes};
+  return 0;
+}
+static void* tconv_stage_lookup(rw_stream_t stream, long long need) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> hold(g_stage_lock);
+  for (const StageBuffer& b : g_stage)
+    if (b.ptr && b.dev == dev && b.stream == rw_s(stream)) return b.bytes >= need ? b.ptr : nullptr;
+  return nullptr;
+}
 
 extern "C" int rw_tconv_blur_f32(const float* x, const float* wp, const float* k4, float* y, int batch, int in_ch,
                                  int out_ch, int h, int w, float w_scale, const rw_conv_epilogue* ep,
@@ -1656,18 +1845,7 @@ extern "C" int rw_tconv_blur_f32(const float* x, const float* wp, const float* k
   p.post = post_scale;
   p.batch = batch; p.in_ch = in_ch; p.out_ch = out_ch; p.h = h; p.w = w; p.w_scale = w_scale; p.u_inv = u_inv;
   p.x_amax = x_amax; p.y_amax = y_amax;
-  // the form: RW_TCONV_TY = 0 the specialised persistent kernel, 8 / 16 the two shapes of tconv_body; unset: by input channels -- the persistent kernel where a tile has few chunks (<= 128
-  // channels: its staging waves run ahead through the epilogue), the one-workgroup-per-CU shape where the MFMAs dominate
-  // (profiles/r05q: layer 17 6.4 against 7.1 ms, layer 15 4.6 / 4.9, layer 13 3.7 / 3.7, layer 11 3.3 / 3.2, layer 9 1.9 / 1.7)
-  // (RW_TCONV_PERSISTENT = 0 / 2: which of the two persistent kernels the automatic choice means)
-  const int persistent = rw_env_int("RW_TCONV_PERSISTENT", 0) == 2 ? 2 : 0;
-  // (RW_TCONV_N32 = "lo:hi": the input-channel range the automatic choice gives to the 32-out-channel form.  Default: none --
-  // stand-alone it ties the persistent form on layer 15 (4.2 against 4.3 ms), inside the forward the persistent form is ahead:
-  // 1526 - 1528 against 1507 - 1518 img/s, same box, interleaved, profiles/r06ak)
-  int n32_lo = 1, n32_hi = 0;
-  if (const char* ne = getenv("RW_TCONV_N32")) { if (sscanf(ne, "%d:%d", &n32_lo, &n32_hi) != 2) { n32_lo = 1; n32_hi = 0; } }
-  const int sel = rw_env_int("RW_TCONV_TY", out_ch % 32 == 0 && in_ch >= n32_lo && in_ch <= n32_hi ? 32
-                                           : (in_ch >= 32 && in_ch <= 128 ? persistent : 16));
+  const int sel = tconv_form(in_ch, out_ch);
   if ((sel == 0 || sel == 2 || sel == 12) && in_ch >= 32) {      // 0: the specialised persistent kernel (one workgroup of eight waves per CU); 2: its pipelined form; 12: twelve waves
     p.tiles_x = w / TC_TX; p.tiles_y = h / 8; p.o_tiles = out_ch / 16;
     const int64_t tiles = (int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles;
@@ -1688,6 +1866,24 @@ extern "C" int rw_tconv_blur_f32(const float* x, const float* wp, const float* k
   const int64_t work = (int64_t)batch * p.tiles_y * p.tiles_x * p.o_tiles;
   if (work <= 0 || work > 0x7fffffff) return RW_ERR_UNSUPPORTED;
   if (y_amax && waves * work > rw_bound_slot_capacity((int64_t)batch * out_ch * 4 * h * w)) return RW_ERR_UNSUPPORTED;
+  // the staged form of the same shape: a registered buffer of the stream that holds the map's words, enough input channels
+  // for the pre-pass to pay (RW_TCONV_STAGED_MIN_IN; profiles/INDEX.md, round 12), RW_TCONV_STAGED = 0 turns it off
+  void* words = nullptr;
+  if (tconv_staged_wanted(sel, in_ch, batch)) words = tconv_stage_lookup(stream, (long long)batch * in_ch * h * w * 4);
+  if (words) {
+    SplitMapProblem sp = {};
+    sp.x = x; sp.words = static_cast<unsigned char*>(words); sp.style = p.style; sp.x_amax = x_amax;
+    sp.batch = batch; sp.in_ch = in_ch; sp.h = h; sp.w = w; sp.u_inv = u_inv;
+    const int blocks = h * w / 256;                 // h % 16 == 0, w % 32 == 0: a multiple of 2
+    sp.iters = blocks % 4 == 0 ? 4 : 2;
+    hipLaunchKernelGGL(split_map_kernel, dim3((unsigned)(blocks / sp.iters), (unsigned)(in_ch / 16), (unsigned)batch), dim3(256),
+                       0, rw_s(stream), sp);
+    p.x = reinterpret_cast<const float*>(sp.words);      // the staged kernels read the words, never the map
+    if (n32) hipLaunchKernelGGL(tconv_blur_n32s_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
+    else if (ty == 16) hipLaunchKernelGGL(tconv_blur_t16s_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
+    else hipLaunchKernelGGL(tconv_blur_t8s_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
+    return rw_finish_bound(y_amax, waves * work, stream);
+  }
   if (n32) hipLaunchKernelGGL(tconv_blur_n32_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
   else if (ty == 16) hipLaunchKernelGGL(tconv_blur_t16_kernel, dim3((unsigned)work), dim3(512), 0, rw_s(stream), p);
   else hipLaunchKernelGGL(tconv_blur_t8_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);

@@ -876,9 +876,20 @@ def conv_transpose3x3s2_blur_fused(x, wp, k4, out_ch, w_scale, style=None, demod
     conv_transpose3x3s2_blur_direct16."""
     x = _dev(x, 'fmap')
     y = _out(x, out_ch, up=2)
-    _conv('rw_tconv_blur_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
-          _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, k4=_k4(k4), y=y,
-          post_scale=_post_scale(post_scale, x.shape[0], out_ch), y_amax=y_amax)
+    # the scratch of the staged forms (the map as operand words, converted once: include/rewriting_hip.h), registered for
+    # this call alone -- the library must never hold a pointer this module has let go of; never during a capture
+    nbytes = lib().rw_tconv_stage_bytes(x.shape[0], x.shape[1], out_ch, x.shape[2], x.shape[3])
+    staged = nbytes > 0 and not torch.cuda.is_current_stream_capturing()
+    if staged:
+        ws = _workspace(nbytes, x.device)
+        check(lib().rw_tconv_stage_buffer(_stream(), _p(ws), ws.numel()))
+    try:
+        _conv('rw_tconv_blur_f32', x, _packed(wp, out_ch, x.shape[1], _DIRECT16), out_ch, w_scale,
+              _epilogue(style, demod, noise, noise_w, bias, act), x_amax=x_amax, k4=_k4(k4), y=y,
+              post_scale=_post_scale(post_scale, x.shape[0], out_ch), y_amax=y_amax)
+    finally:
+        if staged:
+            check(lib().rw_tconv_stage_buffer(_stream(), None, 0))
     return y
 
 

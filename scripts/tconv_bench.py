@@ -54,6 +54,12 @@ def main():
         a = hip.conv_transpose3x3s2_blur_fused(x, pk, k4, cout, s, y_amax=ymax, **args)
         if os.environ.get('RW_TCONV_ONLY'):           # ablation builds: the fused kernel's time alone
             row['fused_ms'] = timed(lambda: hip.conv_transpose3x3s2_blur_fused(x, pk, k4, cout, s, y_amax=ymax, **args))
+            # the scratch a staged form takes for this launch (0: none runs) and, for its pre-pass, the yardstick: a device
+            # copy of the map reads and writes the same bytes
+            row['stage_bytes'] = hip.lib().rw_tconv_stage_bytes(batch, cin, cout, res, res)
+            dst = torch.empty_like(x)
+            row['copy_ms'] = timed(lambda: dst.copy_(x))
+            del dst
             print(json.dumps({k: (float('%.4g' % v) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
             del a, x, noise
             torch.cuda.empty_cache()
