@@ -826,7 +826,7 @@ int rw_conv3x3_rgb_input_grad_f32(const float* g, const float* w, float* gx, int
 /* ---------------------------------------------------------------------------------------
  * LPIPS and the masked edit distances (metrics/distances.py:18-59: PerceptualLoss -- models.PerceptualLoss(model='net-lin',
  * net='vgg', spatial=True), sum(loss * w) / sum(w); :96-136: compute_dl).  The VGG16 convolutions are the entries above; these are
- * what follows them.  float32 only, forward only, on the caller's stream, no atomics, nothing zeroed or drained, every sum in a
+ * what follows them.  float32 only, forward only but for the two adjoints at the section's end, on the caller's stream, no atomics, nothing zeroed or drained, every sum in a
  * fixed order: two runs give the same bits.  They join under ABI 11 like the other added entries.
  * ------------------------------------------------------------------------------------- */
 
@@ -865,6 +865,46 @@ typedef struct rw_lpips_maps {
  * a null or empty tap, sums without scratch; RW_ERR_UNSUPPORTED: batch > 65535, an image the reduction refuses. */
 int rw_lpips_combine_f32(const rw_lpips_maps* taps, const int* idx, const float* lam, const float* weight, int weight_batch,
                          float* out, float* sums, float* scratch, int batch, int h, int w, rw_stream_t stream);
+
+/* LPIPS as a loss -- the perceptual term of the overfit loop (rewrite/ganrewrite.py:316-317) with the metric of
+ * metrics/distances.py:18-59 in place of the feature difference: the adjoints of the two entries above to the FIRST image's
+ * side.  The rules of this section hold: float32, fixed summation order, no atomics, nothing zeroed beforehand, the caller's
+ * stream, the same bits run to run. */
+
+/* The adjoint of rw_lpips_tap_f32 to f0 (metrics/distances.py:18-59, rewrite/ganrewrite.py:316-317).  With r0 = sqrt(sum_c f0_c^2),
+ * den0 = r0 + 1e-10 (r1, den1 likewise of f1), t_c = f0_c / den0 - f1_c / den1 and S = sum_c lin_c t_c f0_c per pixel:
+ *   out[b][j][p] = acc[b][j][p] + gd[b][p] (2 / den0) (lin_j t_j - f0_j S / (r0 den0))
+ * gd (batch, hw) is the gradient at d; acc (batch, ch, hw) is nullable (zeros) and out may be acc.  relu_mask != 0: an element
+ * with f0 <= 0 gets exactly acc (the taps are ReLU outputs).  A pixel with r0 == 0 contributes EXACTLY 0: the formula's
+ * derivative there is a 1 / 1e-10 spike and torch's autograd of it returns NaN (sqrt'(0) * 0); inside the module every
+ * element of such a pixel is masked by its ReLU.  t_c is formed from the normalised difference, as in the forward.  Domain and
+ * tiles as rw_lpips_tap_f32: any ch >= 1 and hw >= 1, f1_batch == batch or 1; up to 8192 channels both maps are read from
+ * memory once and out is written once, above that the maps are read three times.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null f0, f1, lin, gd or out, an extent < 1, f1_batch neither batch nor 1. */
+int rw_lpips_tap_grad_f32(const float* f0, const float* f1, const float* lin, const float* gd, const float* acc, float* out,
+                          int batch, int f1_batch, int ch, int64_t hw, int relu_mask, rw_stream_t stream);
+
+/* The gradients at the tap maps: d[k] (batch, h[k], w[k]) is WRITTEN. */
+typedef struct rw_lpips_grad_maps {
+  float* d[RW_LPIPS_MAX_TAPS];
+  int h[RW_LPIPS_MAX_TAPS];
+  int w[RW_LPIPS_MAX_TAPS];
+  int n;
+} rw_lpips_grad_maps;
+
+/* The adjoint of rw_lpips_combine_f32's weighted sum to every tap map (metrics/distances.py:18-59, rewrite/ganrewrite.py:316-317):
+ *   d[k][b][i][j] = gscale[b] sum_{oy in R_y(i)} wy(oy, i) sum_{ox in R_x(j)} wx(ox, j) weight[b'][oy][ox]
+ * w(o, i) = (1 - lam_o) [i0_o == i] + lam_o [i1_o == i] from idx and lam, the forward's tables; R(i) = [lo, hi) is the run of
+ * outputs that touch input i, from rng: tap after tap, the rows' lo (h[k]), the rows' hi (h[k]), the columns' lo (w[k]), the
+ * columns' hi (w[k]) -- 2 sum_k (h[k] + w[k]) ints.  Indices and ranges are clamped: a wrong table gives a wrong picture, never
+ * an access outside a map.  A row's columns are summed first, then the rows.  weight (weight_batch, h, w) is nullable: all
+ * ones; gscale (batch) is the upstream gradient of an image's mean over its sum of weights.  Identity tables at a tap's own
+ * size give the adjoint of spatial=False's mean.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): null grads, tables, rng or gscale, n outside 1 .. RW_LPIPS_MAX_TAPS, a null or empty
+ * map, an extent < 1, weight_batch neither batch nor 1; RW_ERR_UNSUPPORTED: batch > 65535. */
+int rw_lpips_combine_grad_f32(const rw_lpips_grad_maps* grads, const int* idx, const float* lam, const int* rng,
+                              const float* weight, int weight_batch, const float* gscale, int batch, int h, int w,
+                              rw_stream_t stream);
 
 /* compute_dl's pixel mode (metrics/distances.py:131-133): sums[b] = (sum_p mask[b'][p] sum_c |a[b][c][p] - b[b][c][p]|, sum_p mask[b'][p])
  * for a, b (batch, 3, hw) and mask (mask_batch, hw) float32, mask_batch == batch or 1.  scratch as above. */

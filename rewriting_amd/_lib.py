@@ -34,6 +34,9 @@ class LpipsMaps(Structure):
     _fields_ = [('d', c_void_p * LPIPS_MAX_TAPS), ('h', c_int * LPIPS_MAX_TAPS), ('w', c_int * LPIPS_MAX_TAPS), ('n', c_int)]
 
 
+LpipsGradMaps = LpipsMaps  # rw_lpips_grad_maps: the same layout, its pointers written through
+
+
 class SolveProblem(Structure):
     _fields_ = [
         ('out_ch', c_int), ('in_ch', c_int), ('h', c_int), ('w', c_int), ('rank', c_int),
@@ -224,6 +227,10 @@ SIGNATURES = {
     'rw_lpips_reduce_scratch_elems': (ctypes.c_longlong, [c_int, c_int64]),
     'rw_lpips_combine_f32': (c_int, [POINTER(LpipsMaps), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_void_p]),
+    'rw_lpips_tap_grad_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
+                                      c_int, c_void_p]),
+    'rw_lpips_combine_grad_f32': (c_int, [POINTER(LpipsGradMaps), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_int, c_int, c_int, c_void_p]),
     'rw_masked_l1_rgb_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     # the float64 forward: the _f32 twin's arguments, double buffers and double scalars
     'rw_pixel_norm_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),

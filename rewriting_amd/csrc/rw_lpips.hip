@@ -6,6 +6,7 @@
 //   lpips_combine   out[b][y][x] = sum_k bilinear(d_k)(y, x) (F.interpolate, align_corners=False, host tables) and / or, per image,
 //                   (sum out w, sum w)
 //   masked_l1_rgb   per image (sum_p mask sum_c |a - b|, sum_p mask): compute_dl's pixel mode (:131-133)
+//   lpips_tap_grad, lpips_combine_grad   the adjoints of the first two to f0 and to the tap maps: LPIPS as a loss (lpips.LPIPS.loss)
 //
 // float32 only.  Every sum runs in a fixed order, no atomics, nothing zeroed beforehand, nothing but launches on the caller's
 // stream: two runs give the same bits.  The distance of a tap is formed from the normalised DIFFERENCE as written above, never
@@ -166,6 +167,203 @@ extern "C" int rw_lpips_tap_f32(const float* f0, const float* f1, const float* l
 }
 
 // ---------------------------------------------------------------------------------------
+// The tap kernel's adjoint to f0 (LPIPS as a loss: lpips.LPIPS.loss).  With r0 = |f0|, den0 = r0 + 1e-10 (r1, den1 likewise),
+// t_c = f0_c / den0 - f1_c / den1 -- the normalised DIFFERENCE as in the forward -- and S = sum_c lin_c t_c f0_c:
+//   out[b][j][p] = acc[b][j][p] + gd[b][p] (2 / den0) (lin_j t_j - f0_j S / (r0 den0))
+// The same tile: both maps' ch x P values staged once, then THREE walks -- the norms, S, the outputs -- with the channel groups'
+// partial sums added pairwise as above.  The third walk is elementwise, so with 16-byte staging (V4) it takes the staging's
+// own mapping, a thread per (channel, quad of pixels): acc is read and out written 16 bytes per lane; each element is read
+// and written by one thread, so out may be acc.  A pixel with r0 == 0 contributes exactly 0: the formula's derivative there is
+// a 1 / eps spike (torch's autograd of the formula returns NaN, sqrt'(0) 0), and inside the module every element of such a
+// pixel is masked by its ReLU anyway.  relu_mask: an element with f0 <= 0 gets exactly acc (or 0) -- the taps are ReLU outputs,
+// and the mask pass is saved.  Per pixel the third walk reads (den0, den1, k = gd 2 / den0, m = S / (r0 den0)) from LDS.
+// ---------------------------------------------------------------------------------------
+#define LP_GRAD_RED_FLOATS 1024              // [4][256]: the partial sums, then the four per-pixel values
+
+struct LpTapGrad {
+  const float* f0; const float* f1; const float* lin; const float* gd; const float* acc; float* out;
+  int ch, p_log2, relu_mask;
+  int64_t hw, f1_stride, tiles_per_image;
+};
+
+__device__ __forceinline__ float lp_tap_grad_value(float a, float bv, float lin, float acc, float den0, float den1, float k,
+                                                   float m, int relu_mask) {
+#pragma clang fp contract(off)                   // own is rounded before it meets acc: with acc the result is acc + (the result without)
+  if ((k == 0.f && m == 0.f) || (relu_mask && !(a > 0.f))) return acc;      // a dead pixel has k = m = 0
+  const float t = a / den0 - bv / den1;
+  const float own = k * (lin * t - a * m);
+  return acc + own;
+}
+
+template <bool STAGED, bool V4>
+__global__ void __launch_bounds__(256) lpips_tap_grad_kernel(const LpTapGrad p) {
+  extern __shared__ __attribute__((aligned(16))) float lp_lds[];
+  const int tid = threadIdx.x;
+  const int P = 1 << p.p_log2, G = 256 >> p.p_log2;
+  float* t0 = lp_lds;
+  float* t1 = t0 + (STAGED ? p.ch * P : 0);
+  float* red = t1 + (STAGED ? p.ch * P : 0);
+  const int64_t tile = blockIdx.x;
+  const int64_t b = tile / p.tiles_per_image, p0 = (tile - b * p.tiles_per_image) * P;
+  const int64_t at0 = b * p.ch * p.hw + p0;                   // of f0, acc and out
+  const float* g0 = p.f0 + at0;
+  const float* g1 = p.f1 + b * p.f1_stride + p0;
+  const int valid = (int)(p.hw - p0 < P ? p.hw - p0 : P);
+  if (STAGED) {
+    if (V4) {
+      const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
+      for (int t4 = tid; t4 < quads; t4 += 1024) {
+        float4 a[4], bq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int t = t4 + 256 * j;
+          const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
+          a[j] = bq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (t < quads && 4 * q < valid) {
+            a[j] = *reinterpret_cast<const float4*>(g0 + (int64_t)c * p.hw + 4 * q);
+            bq[j] = *reinterpret_cast<const float4*>(g1 + (int64_t)c * p.hw + 4 * q);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int t = t4 + 256 * j;
+          if (t < quads) {
+            reinterpret_cast<float4*>(t0)[t] = a[j];
+            reinterpret_cast<float4*>(t1)[t] = bq[j];
+          }
+        }
+      }
+    } else {
+      const int n = p.ch << p.p_log2;
+      for (int t = tid; t < n; t += 256) {
+        const int c = t >> p.p_log2, q = t & (P - 1);
+        const bool ok = q < valid;
+        t0[t] = ok ? g0[(int64_t)c * p.hw + q] : 0.f;
+        t1[t] = ok ? g1[(int64_t)c * p.hw + q] : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+  const int px = tid & (P - 1), g = tid >> p.p_log2;
+  const bool ok = px < valid;
+  auto a_of = [&](int c) __attribute__((always_inline)) {
+    return STAGED ? t0[(c << p.p_log2) + px] : (ok ? g0[(int64_t)c * p.hw + px] : 0.f);
+  };
+  auto b_of = [&](int c) __attribute__((always_inline)) {
+    return STAGED ? t1[(c << p.p_log2) + px] : (ok ? g1[(int64_t)c * p.hw + px] : 0.f);
+  };
+  // walk 1: the norms
+  float s0 = 0.f, s1 = 0.f;
+  for (int c = g; c < p.ch; c += G) {
+    const float a = a_of(c), bv = b_of(c);
+    s0 = fmaf(a, a, s0);
+    s1 = fmaf(bv, bv, s1);
+  }
+  red[tid] = s0;
+  red[256 + tid] = s1;
+  __syncthreads();
+  for (int s = G >> 1; s > 0; s >>= 1) {
+    if (g < s) {
+      red[tid] += red[tid + (s << p.p_log2)];
+      red[256 + tid] += red[256 + tid + (s << p.p_log2)];
+    }
+    __syncthreads();
+  }
+  const float r0 = sqrtf(red[px]);
+  const float den0 = r0 + 1e-10f, den1 = sqrtf(red[256 + px]) + 1e-10f;
+  __syncthreads();
+  // walk 2: S
+  float acc = 0.f;
+  for (int c = g; c < p.ch; c += G) {
+    const float a = a_of(c);
+    const float t = a / den0 - b_of(c) / den1;
+    acc = fmaf(p.lin[c] * t, a, acc);
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = G >> 1; s > 0; s >>= 1) {
+    if (g < s) red[tid] += red[tid + (s << p.p_log2)];
+    __syncthreads();
+  }
+  const float big_s = red[px];
+  const bool live = ok && r0 > 0.f;
+  const float k = live ? p.gd[b * p.hw + p0 + px] * (2.f / den0) : 0.f;
+  const float m = live ? big_s / r0 / den0 : 0.f;
+  // walk 3: the outputs
+  if (V4) {
+    __syncthreads();                                           // every thread has read its S
+    if (g == 0) {
+      red[px] = den0;
+      red[256 + px] = den1;
+      red[512 + px] = k;
+      red[768 + px] = m;
+    }
+    __syncthreads();
+    const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
+    for (int t = tid; t < quads; t += 256) {
+      const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
+      if (4 * q >= valid) continue;                            // hw % 4 == 0: a quad is inside the map or outside it
+      const float4 a = reinterpret_cast<const float4*>(t0)[t], bq = reinterpret_cast<const float4*>(t1)[t];
+      const float4 d0 = reinterpret_cast<const float4*>(red)[q], d1 = reinterpret_cast<const float4*>(red + 256)[q];
+      const float4 kq = reinterpret_cast<const float4*>(red + 512)[q], mq = reinterpret_cast<const float4*>(red + 768)[q];
+      const int64_t at = at0 + (int64_t)c * p.hw + 4 * q;
+      float4 ac = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (p.acc) ac = *reinterpret_cast<const float4*>(p.acc + at);
+      const float lin = p.lin[c];
+      float4 o;
+      o.x = lp_tap_grad_value(a.x, bq.x, lin, ac.x, d0.x, d1.x, kq.x, mq.x, p.relu_mask);
+      o.y = lp_tap_grad_value(a.y, bq.y, lin, ac.y, d0.y, d1.y, kq.y, mq.y, p.relu_mask);
+      o.z = lp_tap_grad_value(a.z, bq.z, lin, ac.z, d0.z, d1.z, kq.z, mq.z, p.relu_mask);
+      o.w = lp_tap_grad_value(a.w, bq.w, lin, ac.w, d0.w, d1.w, kq.w, mq.w, p.relu_mask);
+      *reinterpret_cast<float4*>(p.out + at) = o;
+    }
+  } else if (ok) {
+    for (int c = g; c < p.ch; c += G) {
+      const int64_t at = at0 + (int64_t)c * p.hw + px;
+      const float ac = p.acc ? p.acc[at] : 0.f;
+      p.out[at] = lp_tap_grad_value(a_of(c), b_of(c), p.lin[c], ac, den0, den1, k, m, p.relu_mask);
+    }
+  }
+}
+
+template <bool STAGED, bool V4>
+static int lp_launch_tap_grad(const LpTapGrad& p, int64_t tiles, size_t ldsb, hipStream_t s) {
+  if (ldsb > 65536) {
+    const hipError_t e = hipFuncSetAttribute((const void*)lpips_tap_grad_kernel<STAGED, V4>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((lpips_tap_grad_kernel<STAGED, V4>), dim3((unsigned)tiles), dim3(256), ldsb, s, p);
+  return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_lpips_tap_grad_f32(const float* f0, const float* f1, const float* lin, const float* gd, const float* acc,
+                                     float* out, int batch, int f1_batch, int ch, int64_t hw, int relu_mask,
+                                     rw_stream_t stream) {
+  RW_CHECK_ARG(f0 && f1 && lin && gd && out && batch > 0 && ch > 0 && hw > 0 && (f1_batch == batch || f1_batch == 1));
+  const int dflt = 2 * (int64_t)ch * 32 <= LP_TILE_FLOATS ? LP_TILE_FLOATS : LP_WIDE_TILE_FLOATS;
+  int tile = rw_env_int("RW_LPIPS_TILE", dflt);
+  if (tile < 2 || tile > LP_MAX_TILE_FLOATS) tile = dflt;
+  const bool staged = 2 * (int64_t)ch <= tile;
+  int p_log2 = 8;
+  while (staged && p_log2 > 0 && 2 * (int64_t)ch << p_log2 > tile) --p_log2;
+  while (p_log2 > 0 && (1 << (p_log2 - 1)) >= hw) --p_log2;
+  LpTapGrad p;
+  p.f0 = f0; p.f1 = f1; p.lin = lin; p.gd = gd; p.acc = acc; p.out = out;
+  p.ch = ch; p.p_log2 = p_log2; p.relu_mask = relu_mask != 0; p.hw = hw;
+  p.f1_stride = f1_batch == 1 ? 0 : (int64_t)ch * hw;
+  p.tiles_per_image = rw_cdiv(hw, 1 << p_log2);
+  const int64_t tiles = p.tiles_per_image * batch;
+  if (tiles > 0x7fffffff) return RW_ERR_UNSUPPORTED;
+  const size_t ldsb = sizeof(float) * ((staged ? ((size_t)2 * ch << p_log2) : 0) + LP_GRAD_RED_FLOATS);
+  const bool v4 = staged && p_log2 >= 2 && hw % 4 == 0 && lp_aligned16(f0) && lp_aligned16(f1) && lp_aligned16(out) &&
+                  (!acc || lp_aligned16(acc));
+  if (!staged) return lp_launch_tap_grad<false, false>(p, tiles, ldsb, rw_s(stream));
+  if (v4) return lp_launch_tap_grad<true, true>(p, tiles, ldsb, rw_s(stream));
+  return lp_launch_tap_grad<true, false>(p, tiles, ldsb, rw_s(stream));
+}
+
+// ---------------------------------------------------------------------------------------
 // The per-image reductions (lpips_combine, masked_l1_rgb).  A thread adds its T <= LP_MAX_PER_THREAD terms in ascending pixel
 // order, the workgroup's 256 threads meet in rw_block_sum_256 (6 additions across the wave, 3 across the waves), the
 // workgroup stores its pair PLAINLY into its own slot of `scratch`, and lp_finish_kernel -- one workgroup per image --
@@ -282,6 +480,75 @@ extern "C" int rw_lpips_combine_f32(const rw_lpips_maps* taps, const int* idx, c
   p.h = h; p.w = w;
   hipLaunchKernelGGL(lpips_combine_kernel, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, rw_s(stream), p);
   if (sums) hipLaunchKernelGGL(lp_finish_kernel, dim3((unsigned)batch), dim3(256), 0, rw_s(stream), scratch, sums, nblk);
+  return RW_LAUNCH_RESULT();
+}
+
+// ---------------------------------------------------------------------------------------
+// lpips_combine's adjoint to every tap map: a GATHER per tap pixel, no scatter.
+//   gd_k[b][i][j] = gscale[b] sum_{oy in R_y(i)} wy(oy, i) sum_{ox in R_x(j)} wx(ox, j) weight[b'][oy][ox]
+// with w(o, i) = (1 - lam_o) [i0_o == i] + lam_o [i1_o == i] from the forward's tables (clamped as there; both indices equal
+// i: exactly 1) and R(i) = [lo, hi) the outputs that touch input i -- i0 and i1 do not decrease, so those are one run;
+// lpips.adjoint_table makes (lo, hi) on the host.  rng holds, tap after tap, [row lo (h_k)] [row hi (h_k)] [column lo (w_k)]
+// [column hi (w_k)]; the kernel clamps them into the output: a wrong table gives a wrong picture, never a read outside a map.
+// A row's columns are summed first (one fused multiply-add each), then the rows: a term passes through |R_x| + |R_y|
+// additions, its two weights' roundings and the product with gscale.  One thread per tap pixel, blockIdx.z the tap.
+// ---------------------------------------------------------------------------------------
+struct LpCombineGrad {
+  rw_lpips_grad_maps m;
+  const int* idx; const float* lam; const int* rng; const float* weight; const float* gscale;
+  int64_t weight_stride;
+  int h, w;
+};
+
+__device__ __forceinline__ float lp_adjoint_weight(int i0, int i1, float lam, int i) {
+  return i0 == i ? (i1 == i ? 1.f : 1.f - lam) : (i1 == i ? lam : 0.f);
+}
+
+__global__ void __launch_bounds__(256) lpips_combine_grad_kernel(const LpCombineGrad p) {
+  const int k = blockIdx.z, b = blockIdx.y;
+  const int hk = p.m.h[k], wk = p.m.w[k];
+  const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (at >= (int64_t)hk * wk) return;
+  const int i = (int)(at / wk), j = (int)(at - (int64_t)i * wk);
+  int64_t off = 0;
+  for (int t = 0; t < k; ++t) off += 2 * ((int64_t)p.m.h[t] + p.m.w[t]);
+  const int* rk = p.rng + off;
+  const int* ik = p.idx + (int64_t)k * (2 * p.h + 2 * p.w);
+  const float* lk = p.lam + (int64_t)k * (p.h + p.w);
+  const int y_lo = lp_clamp(rk[i], p.h + 1), y_hi = lp_clamp(rk[hk + i], p.h + 1);
+  const int x_lo = lp_clamp(rk[2 * hk + j], p.w + 1), x_hi = lp_clamp(rk[2 * hk + wk + j], p.w + 1);
+  const float* wt = p.weight ? p.weight + b * p.weight_stride : nullptr;
+  float v = 0.f;
+  for (int oy = y_lo; oy < y_hi; ++oy) {
+    float row = 0.f;
+    for (int ox = x_lo; ox < x_hi; ++ox) {
+      const float wx = lp_adjoint_weight(lp_clamp(ik[2 * p.h + ox], wk), lp_clamp(ik[2 * p.h + p.w + ox], wk), lk[p.h + ox], j);
+      row = fmaf(wx, wt ? wt[(int64_t)oy * p.w + ox] : 1.f, row);
+    }
+    v = fmaf(lp_adjoint_weight(lp_clamp(ik[oy], hk), lp_clamp(ik[p.h + oy], hk), lk[oy], i), row, v);
+  }
+  p.m.d[k][(int64_t)b * hk * wk + at] = p.gscale[b] * v;
+}
+
+extern "C" int rw_lpips_combine_grad_f32(const rw_lpips_grad_maps* grads, const int* idx, const float* lam, const int* rng,
+                                         const float* weight, int weight_batch, const float* gscale, int batch, int h, int w,
+                                         rw_stream_t stream) {
+  RW_CHECK_ARG(grads && idx && lam && rng && gscale && batch > 0 && h > 0 && w > 0);
+  RW_CHECK_ARG(grads->n >= 1 && grads->n <= RW_LPIPS_MAX_TAPS);
+  RW_CHECK_ARG(!weight || weight_batch == batch || weight_batch == 1);
+  int64_t most = 0;
+  for (int k = 0; k < grads->n; ++k) {
+    RW_CHECK_ARG(grads->d[k] && grads->h[k] > 0 && grads->w[k] > 0);
+    const int64_t n = (int64_t)grads->h[k] * grads->w[k];
+    most = n > most ? n : most;
+  }
+  if (batch > 65535 || h == 0x7fffffff || w == 0x7fffffff || rw_cdiv(most, 256) > 0x7fffffff) return RW_ERR_UNSUPPORTED;
+  LpCombineGrad p;
+  p.m = *grads; p.idx = idx; p.lam = lam; p.rng = rng; p.weight = weight; p.gscale = gscale;
+  p.weight_stride = weight && weight_batch == 1 ? 0 : (int64_t)h * w;
+  p.h = h; p.w = w;
+  hipLaunchKernelGGL(lpips_combine_grad_kernel, dim3((unsigned)rw_cdiv(most, 256), (unsigned)batch, (unsigned)grads->n), dim3(256),
+                     0, rw_s(stream), p);
   return RW_LAUNCH_RESULT();
 }
 

@@ -1459,6 +1459,73 @@ def lpips_combine(taps, tables, size, weight=None, want_map=True, want_sums=Fals
     return out, sums
 
 
+def lpips_tap_grad(f0, f1, lin, gd, acc=None, relu_mask=False, out=None):
+    """The adjoint of lpips_tap to f0 (rw_lpips_tap_grad_f32): acc + gd (2 / den0) (lin t - f0 S / (r0 den0)), (B, C, H, W); gd
+    (B, H, W) is the gradient at d, acc (B, C, H, W) the gradient that is already there (None: zeros), out the tensor that
+    receives the result -- it may be acc.  relu_mask: an element with f0 <= 0 gets exactly acc.  A pixel whose f0 is all zero
+    contributes exactly 0.  Read in place."""
+    f0 = _fmap4(_in_place(f0, 'tap'), 'tap')
+    f1 = _in_place(f1, 'second tap', device=f0.device)
+    lin = _in_place(lin, 'lin weight', device=f0.device)
+    gd = _in_place(gd, 'distance gradient', device=f0.device)
+    b, c, h, w = f0.shape
+    if f1.dim() != 4 or tuple(f1.shape[1:]) != (c, h, w) or f1.shape[0] not in (1, b) or tuple(lin.shape) != (c,) \
+            or tuple(gd.shape) != (b, h, w):
+        raise ValueError('lpips_tap_grad takes two maps (B, C, H, W) and (B or 1, C, H, W), a weight (C,) and a gradient (B, H, W), '
+                         'not %s / %s / %s / %s' % (tuple(f0.shape), tuple(f1.shape), tuple(lin.shape), tuple(gd.shape)))
+    if acc is not None:
+        acc = _in_place(acc, 'incoming gradient', device=f0.device)
+        if acc.shape != f0.shape:
+            raise ValueError('the incoming gradient is %s, the tap %s' % (tuple(acc.shape), tuple(f0.shape)))
+    if out is None:
+        out = torch.empty_like(f0)
+    else:
+        out = _in_place(out, 'out', device=f0.device)
+        if out.shape != f0.shape:
+            raise ValueError('out is %s, the tap %s' % (tuple(out.shape), tuple(f0.shape)))
+    check(lib().rw_lpips_tap_grad_f32(_p(f0), _p(f1), _p(lin), _p(gd), _p(acc), _p(out), b, f1.shape[0], c, h * w,
+                                      int(bool(relu_mask)), _stream()))
+    return out
+
+
+def lpips_combine_grad(tap_sizes, tables, ranges, size, gscale, weight=None):
+    """[gd_k (B, h_k, w_k)] of rw_lpips_combine_grad_f32, the adjoint of lpips_combine's ``sum(out * weight)`` to every tap map:
+    tap_sizes = ((h_k, w_k), ...), tables as lpips_combine takes them, ranges int32 (2 sum_k (h_k + w_k),) of
+    lpips.device_adjoint_tables, size = (H, W), gscale (B,) the gradient at an image's weighted sum, weight (B or 1, 1, H, W)
+    or None (all ones)."""
+    tap_sizes = [(int(a), int(b)) for a, b in tap_sizes]
+    if not 1 <= len(tap_sizes) <= LPIPS_MAX_TAPS:
+        raise ValueError('lpips_combine_grad takes 1 .. %d tap maps, not %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
+                         % (LPIPS_MAX_TAPS, len(tap_sizes)))
+    gscale = _in_place(gscale, 'gradient scale')
+    device = gscale.device
+    idx = _in_place(tables[0], 'index table', torch.int32, device)
+    lam = _in_place(tables[1], 'weight table', device=device)
+    ranges = _in_place(ranges, 'range table', torch.int32, device)
+    h, w = int(size[0]), int(size[1])
+    k = len(tap_sizes)
+    if gscale.dim() != 1 or gscale.shape[0] < 1:
+        raise ValueError('the gradient scale must be (B,), not %s' % (tuple(gscale.shape),))
+    b = gscale.shape[0]
+    if h < 1 or w < 1 or tuple(idx.shape) != (k, 2 * h + 2 * w) or tuple(lam.shape) != (k, h + w):
+        raise ValueError('the tables %s / %s do not belong to %d taps and an output of %d x %d'
+                         % (tuple(idx.shape), tuple(lam.shape), k, h, w))
+    if any(a < 1 or c < 1 for a, c in tap_sizes) or tuple(ranges.shape) != (2 * sum(a + c for a, c in tap_sizes),):
+        raise ValueError('the range table %s does not belong to taps of %s' % (tuple(ranges.shape), tap_sizes))
+    if weight is not None:
+        weight = _in_place(weight, 'weight', device=device)
+        if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, h, w) or weight.shape[0] not in (1, b):
+            raise ValueError('the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s' % (b, h, w, tuple(weight.shape)))
+    grads = [torch.empty(b, hk, wk, device=device, dtype=torch.float32) for hk, wk in tap_sizes]
+    maps = _lib.LpipsGradMaps()
+    for n, g in enumerate(grads):
+        maps.d[n], maps.h[n], maps.w[n] = g.data_ptr(), g.shape[1], g.shape[2]
+    maps.n = k
+    check(lib().rw_lpips_combine_grad_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(ranges), _p(weight),
+                                          weight.shape[0] if weight is not None else 0, _p(gscale), b, h, w, _stream()))
+    return grads
+
+
 def masked_l1(a, b, mask):
     """(B, 2): per image (sum_p mask sum_c |a - b|, sum_p mask) for images a, b (B, 3, H, W) and mask (B or 1, H, W) float32 --
     rw_masked_l1_rgb_f32."""

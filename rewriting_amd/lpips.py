@@ -13,8 +13,11 @@ the arithmetic is
 
 ``LPIPS`` is built from a ``perceptual.VGG16Features`` -- whose nine blocks it reuses -- and four more blocks (21 with its
 pool, 24, 26, 28).  The two images' networks run block by block side by side, and a tap is dropped as soon as its ``d_k``
-exists; maps narrower than 32 take the split-K form of the direct sum (SPLIT_K below).  Forward only, float32 on a HIP
-device only.  No weights ship: ``lpips_vgg(vgg_path, lin_path)`` loads a torchvision VGG16 state dict and the ``lin`` layers
+exists; maps narrower than 32 take the split-K form of the direct sum (SPLIT_K below).  float32 on a HIP device only.
+``forward`` is the metric and refuses gradients; ``loss`` is the same value per image as a LOSS, differentiable to its first
+image (``hip.lpips_combine_grad``, ``hip.lpips_tap_grad`` and the blocks' adjoints to their inputs, one autograd node for
+the whole metric), against a ``target`` whose taps are computed once; ``OverfitTerm`` is that loss as the perceptual term
+of ``all_weights_insert``.  No weights ship: ``lpips_vgg(vgg_path, lin_path)`` loads a torchvision VGG16 state dict and the ``lin`` layers
 of LPIPS v0.1 (``lin{k}.model.1.weight``); the environment variables ``RW_VGG16_WEIGHTS`` and ``RW_LPIPS_WEIGHTS`` name the
 two files.
 """
@@ -25,7 +28,10 @@ import numpy
 import torch
 from torch import nn
 
+from torch.autograd import Function
+
 from . import hip, perceptual
+from .utils.stylegan2 import grad
 
 WEIGHTS_ENV = 'RW_LPIPS_WEIGHTS'
 SHIFT = (-.030, -.088, -.188)
@@ -63,7 +69,44 @@ def upsample_table(n_in, n_out):
     return tables
 
 
+@functools.lru_cache(maxsize=256)
+def adjoint_table(n_in, n_out):
+    """(lo, hi int32), each (n_in,): the outputs o of upsample_table(n_in, n_out) that read input i -- i0[o] == i or
+    i1[o] == i -- are exactly lo[i] <= o < hi[i].  i0 and i1 do not decrease, and the outputs with i1 == i are those with
+    i0 == i - 1 (and, at the last input, with i0 == i): two adjacent runs.  An input no output reads has lo == hi.  Read-only
+    arrays."""
+    i0, i1, _ = upsample_table(n_in, n_out)
+    at = numpy.arange(int(n_in))
+    lo0, hi0 = numpy.searchsorted(i0, at, 'left'), numpy.searchsorted(i0, at, 'right')
+    lo1, hi1 = numpy.searchsorted(i1, at, 'left'), numpy.searchsorted(i1, at, 'right')
+    lo = numpy.where(hi0 > lo0, numpy.where(hi1 > lo1, numpy.minimum(lo0, lo1), lo0), lo1)
+    hi = numpy.where(hi0 > lo0, numpy.where(hi1 > lo1, numpy.maximum(hi0, hi1), hi0), hi1)
+    tables = (lo.astype(numpy.int32), hi.astype(numpy.int32))
+    for t in tables:
+        t.setflags(write=False)
+    return tables
+
+
 _device_tables = {}
+_device_adjoint_tables = {}
+
+
+def device_adjoint_tables(tap_sizes, size, device):
+    """int32 (2 sum_k (h_k + w_k),) on `device`, as rw_lpips_combine_grad_f32 reads it: tap after tap the rows' lo, the rows'
+    hi, the columns' lo, the columns' hi of adjoint_table.  Copied once per (sizes, device)."""
+    device = torch.device(device)
+    h, w = int(size[0]), int(size[1])
+    key = (tuple((int(a), int(b)) for a, b in tap_sizes), h, w, device.type, device.index)
+    table = _device_adjoint_tables.get(key)
+    if table is None:
+        parts = []
+        for hk, wk in key[0]:
+            parts.extend(adjoint_table(hk, h) + adjoint_table(wk, w))
+        table = torch.from_numpy(numpy.concatenate(parts)).to(device)
+        if len(_device_adjoint_tables) >= 64:
+            _device_adjoint_tables.clear()
+        _device_adjoint_tables[key] = table
+    return table
 
 
 def device_tables(tap_sizes, size, device):
@@ -87,6 +130,94 @@ def device_tables(tap_sizes, size, device):
             _device_tables.clear()
         _device_tables[key] = tables
     return tables
+
+
+class Target:
+    """The constant side of ``LPIPS.loss``: the five tap maps of an image batch (B or 1) and the image's size.  Made by
+    ``LPIPS.target`` once, read by every iteration."""
+
+    def __init__(self, taps, size):
+        self.taps, self.size = tuple(taps), (int(size[0]), int(size[1]))
+
+    @property
+    def batch(self):
+        return self.taps[0].shape[0]
+
+    @property
+    def device(self):
+        return self.taps[0].device
+
+
+def _evaluate(net, im0, target, w, spatial, keep):
+    """(value (B,), the thirteen activated maps of im0 or [], what the backward needs of the reduction): forward's launches
+    for im0, in forward's order, against the taps of `target`."""
+    b, _, h, wd = im0.shape
+    x0 = (im0.detach() - net.shift) / net.scale
+    ds, saved = [], []
+    for index, block in net.blocks():
+        impl = SPLIT_K if x0.shape[3] < SPLIT_K_BELOW else None
+        y0, x0 = block.activate(x0, keep=True, impl=impl)
+        if index in TAPS:
+            ds.append(hip.lpips_tap(y0, target.taps[len(ds)], net.lins[len(ds)]))
+        if keep:
+            saved.append(y0)
+        del y0
+    del x0
+    sizes = tuple((d.shape[1], d.shape[2]) for d in ds)
+    if spatial:
+        _, sums = hip.lpips_combine(ds, device_tables(sizes, (h, wd), im0.device), (h, wd), weight=w, want_map=False,
+                                    want_sums=True)
+        return sums[:, 0] / sums[:, 1], saved, sums[:, 1]
+    out = 0
+    for d, size in zip(ds, sizes):
+        _, sums = hip.lpips_combine([d], device_tables((size,), size, im0.device), size, want_map=False, want_sums=True)
+        out = out + sums[:, 0] / sums[:, 1]
+    if w is None:
+        return out, saved, None
+    _, sums = hip.lpips_combine([out.view(b, 1, 1).contiguous()], device_tables(((1, 1),), (h, wd), im0.device), (h, wd),
+                                weight=w, want_map=False, want_sums=True)
+    return sums[:, 0] / sums[:, 1], saved, sums[:, 1]
+
+
+class _LossFunction(Function):
+    """The whole metric as one node: saves im0's thirteen activated maps (five of them are the taps) and the weights' sums."""
+
+    @staticmethod
+    def forward(ctx, im0, net, target, w, spatial, trace):
+        value, saved, total = _evaluate(net, im0, target, w, spatial, keep=True)
+        if trace is not None:
+            trace.extend(saved)
+        ctx.net, ctx.target, ctx.w, ctx.spatial, ctx.total = net, target, w, spatial, total
+        ctx.save_for_backward(*saved)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        net, target, w = ctx.net, ctx.target, ctx.w
+        saved = ctx.saved_tensors
+        b, _, h, wd = saved[0].shape
+        device = saved[0].device
+        sizes = tuple((saved[n].shape[2], saved[n].shape[3]) for n, (index, _) in enumerate(net.blocks()) if index in TAPS)
+        g = g.detach().to(torch.float32).contiguous()
+        if ctx.spatial:
+            gds = hip.lpips_combine_grad(sizes, device_tables(sizes, (h, wd), device), device_adjoint_tables(sizes, (h, wd), device),
+                                         (h, wd), g / ctx.total, weight=w)
+        else:
+            if w is not None:                                   # the 1 x 1 map of the taps' means under the weight
+                one = ((1, 1),)
+                g = hip.lpips_combine_grad(one, device_tables(one, (h, wd), device), device_adjoint_tables(one, (h, wd), device),
+                                           (h, wd), g / ctx.total, weight=w)[0].view(b)
+            gds = [hip.lpips_combine_grad((size,), device_tables((size,), size, device),
+                                          device_adjoint_tables((size,), size, device), size, g / (size[0] * size[1]))[0]
+                   for size in sizes]
+        gx, k = None, len(sizes)
+        for (index, block), y in reversed(list(zip(net.blocks(), saved))):
+            gy = None if gx is None else hip.bias_relu_pool_grad(gx, y, pooled=block.pool)
+            if index in TAPS:
+                k -= 1
+                gy = hip.lpips_tap_grad(y, target.taps[k], net.lins[k], gds[k], acc=gy, relu_mask=True, out=gy)
+            gx = block.conv_input_grad(gy)
+        return gx / net.scale, None, None, None, None, None
 
 
 class LPIPS(nn.Module):
@@ -182,6 +313,64 @@ class LPIPS(nn.Module):
             _, sums = hip.lpips_combine([out.view(b, 1, 1).contiguous()], device_tables(((1, 1),), (h, wd), im0.device), (h, wd),
                                         weight=w, want_map=False, want_sums=True)
             return sums[:, 0] / sums[:, 1]
+
+
+    def target(self, im1):
+        """The taps of im1 (B or 1, 3, H, W) as a ``Target``: its network runs here, once, under no_grad."""
+        im1 = im1.detach() if isinstance(im1, torch.Tensor) else im1
+        self._check(im1, im1, None)
+        with torch.no_grad():
+            x1 = (im1 - self.shift) / self.scale
+            taps = []
+            for index, block in self.blocks():
+                impl = SPLIT_K if x1.shape[3] < SPLIT_K_BELOW else None
+                y1, x1 = block.activate(x1, keep=True, impl=impl)
+                if index in TAPS:
+                    taps.append(y1)
+                del y1
+        return Target(taps, im1.shape[2:])
+
+    def loss(self, im0, target, w=None, spatial=True, trace=None):
+        """(B,): LPIPS of im0 against `target` -- a ``Target`` or an image (B or 1, 3, H, W), whose taps are then computed
+        here -- per image: with w (B or 1, 1, H, W) ``sum(out * w) / sum(w)`` of the spatial map, without it the map's mean;
+        spatial=False: the sum of the taps' means.  The value is ``forward``'s, bit for bit (the same launches in the same
+        order).  Differentiable to im0 and to nothing else: the target, w and the parameters may not require a gradient.
+        Under no_grad, or when im0 requires none, nothing is saved.  trace: a list that receives im0's thirteen activated
+        maps (the ReLU and pool decisions of the device) when a gradient is recorded."""
+        for name, t in (('the target', target), ('the weight', w)):
+            if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+                raise RuntimeError('rewriting_amd: LPIPS.loss is differentiable to im0 only: %s requires a gradient -- detach it'
+                                   % name)
+        if not isinstance(target, Target):
+            target = self.target(target)
+        plain = im0.detach() if isinstance(im0, torch.Tensor) else im0
+        self._check(plain, plain, w)
+        if target.size != tuple(im0.shape[2:]) or target.batch not in (1, im0.shape[0]) or target.device != im0.device:
+            raise ValueError('rewriting_amd: LPIPS: the target holds %d image(s) of %d x %d on %s, im0 is %s on %s -- the sizes '
+                             'must match, the target\'s batch may be 1'
+                             % (target.batch, target.size[0], target.size[1], target.device, tuple(im0.shape), im0.device))
+        if grad.records(im0):
+            return _LossFunction.apply(im0, self, target, w, bool(spatial), trace)
+        with torch.no_grad():
+            return _evaluate(self, plain, target, w, bool(spatial), keep=False)[0]
+
+
+class OverfitTerm:
+    """``(gt, pred) -> weight * net.loss(pred, net.target(gt), spatial=spatial).mean()``: LPIPS as the perceptual term of
+    ``all_weights_insert(..., perceptual=)``.  The target is kept for as long as gt stays the same memory at the same version
+    and shape: the overfit loop hands the same image every iteration, and its network runs once."""
+
+    def __init__(self, net, weight=1.0, spatial=False):
+        if not isinstance(net, LPIPS):
+            raise TypeError('rewriting_amd: OverfitTerm is built from an lpips.LPIPS, not %s' % type(net).__name__)
+        self.net, self.weight, self.spatial = net, float(weight), bool(spatial)
+        self._key = self._gt = self._target = None
+
+    def __call__(self, gt, pred):
+        key = (gt.data_ptr(), gt._version, tuple(gt.shape), tuple(gt.stride()))
+        if key != self._key:
+            self._key, self._gt, self._target = key, gt, self.net.target(gt)    # gt is held: its memory is not handed out again
+        return self.weight * self.net.loss(pred, self._target, spatial=self.spatial).mean()
 
 
 def _lin_weights(lin_sd):

@@ -80,7 +80,11 @@ class _Block(nn.Module):
 
     def input_grad(self, g, y):
         """d input of the block from g, the gradient at what the next block read, and the saved y."""
-        g = hip.bias_relu_pool_grad(g, y, pooled=self.pool)
+        return self.conv_input_grad(hip.bias_relu_pool_grad(g, y, pooled=self.pool))
+
+    def conv_input_grad(self, g):
+        """d input of the convolution alone from g, the gradient at y already routed through the pool and masked by the ReLU
+        (lpips.py adds a tap's own gradient there first)."""
         if self.in_ch == 3:
             return hip.conv3x3_rgb_input_grad(g, self.weight)
         return self._conv(g, 'adjoint', self.in_ch, lambda: grad.transposed_weight(self.weight[None], flip=True))

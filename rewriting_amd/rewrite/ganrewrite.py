@@ -239,16 +239,19 @@ class ProgressiveGanRewriter(object):
         self.insert(goal_in, goal_out, mkey, update_callback=update_callback,
                     niter=niter, piter=piter, lr=lr)
 
-    def apply_overfit(self, request, niter=20001, lr=0.01, update_callback=None, feature_net=None):
+    def apply_overfit(self, request, niter=20001, lr=0.01, update_callback=None, feature_net=None, perceptual=None):
         """The overfit baseline (rewrite/ganrewrite.py:171-181): paste the selected object into the image itself and
-        train every weight toward it (all_weights_insert).  feature_net: see there."""
-        feature_net = self._feature_net(feature_net)
+        train every weight toward it (all_weights_insert).  feature_net, perceptual: see there."""
+        if perceptual is None:
+            feature_net = self._feature_net(feature_net)
+        else:
+            _need_callable(perceptual)
         o_imgnum, o_mask = request['object']
         p_imgnum, p_mask = request['paste']
         rgb_clip, _, obj_area, _ = self.rgb_from_selection(o_imgnum, o_mask)
         host_z, changed_rgb, bounds = self.rgbpaste_from_selection(p_imgnum, p_mask, rgb_clip, obj_area)
         self.all_weights_insert(changed_rgb, host_z, bounds=bounds, update_callback=update_callback, niter=niter, lr=lr,
-                                feature_net=feature_net)
+                                feature_net=feature_net, **({} if perceptual is None else dict(perceptual=perceptual)))
 
     def zero(self, context, amount=0.0):
         """W <- W - P(W) + amount * P(1)   (:190-195)"""
@@ -368,15 +371,24 @@ class ProgressiveGanRewriter(object):
                 del owner.forward         # the instance attribute; the class's forward is back
         _weights_changed()
 
-    def all_weights_insert(self, x, z, bounds=None, update_callback=None, niter=20001, lr=0.01, feature_net=None):
+    def all_weights_insert(self, x, z, bounds=None, update_callback=None, niter=20001, lr=0.01, feature_net=None,
+                           perceptual=None):
         """Adam over EVERY parameter of the generator toward the image x for the latent z (rewrite/ganrewrite.py:300-331):
         L1 on the image (cropped to bounds = (top, left, bottom, right) if given) plus 1e-2 of the mean squared
         difference of feature_net's responses.  The gradient reaches the parameters through the adjoints of
         utils/stylegan2/grad.py.  feature_net (VF of the reference: torchvision's VGG16 features[:21], whose weights have
         to be downloaded) is the caller's -- any module or function from images to feature tensors -- or, when None, that
         network on the HIP kernels (perceptual.VGG16Features) with the weights of the file the environment variable
-        RW_VGG16_WEIGHTS names, built once per rewriter."""
-        feature_net = self._feature_net(feature_net)
+        RW_VGG16_WEIGHTS names, built once per rewriter.  perceptual: a callable ``(gt, pred) -> scalar`` that REPLACES the
+        ``1e-2 * mse(feature_net(gt), feature_net(pred))`` term, e.g. ``lpips.OverfitTerm(net)``; feature_net is then not
+        resolved."""
+        if perceptual is None:
+            feature_net = self._feature_net(feature_net)
+
+            def perceptual(gt, pred):
+                return 1e-2 * torch.nn.functional.mse_loss(feature_net(gt), feature_net(pred))
+        else:
+            _need_callable(perceptual)
         x, z = self.detach(x), self.detach(z)
 
         def compute_loss():
@@ -386,8 +398,7 @@ class ProgressiveGanRewriter(object):
             else:
                 t, l, b, r = bounds
                 gt, pred = x[:, :, t:b, l:r], out[:, :, t:b, l:r]
-            return torch.nn.functional.l1_loss(gt, pred) + (
-                1e-2 * torch.nn.functional.mse_loss(feature_net(gt), feature_net(pred)))
+            return torch.nn.functional.l1_loss(gt, pred) + perceptual(gt, pred)
         nethook.set_requires_grad(False, self.model)
         params = list(self.model.parameters())
         nethook.set_requires_grad(True, *params)
@@ -887,6 +898,12 @@ class SeqPreStyleGanRewriter(SeqStyleGanRewriter):
 # ------------------------------------------------------------------------------------------
 # utilities
 # ------------------------------------------------------------------------------------------
+
+def _need_callable(perceptual):
+    if not callable(perceptual):
+        raise TypeError('rewriting_amd: perceptual= takes a callable (gt, pred) -> scalar loss, e.g. lpips.OverfitTerm(net), '
+                        'not %s' % type(perceptual).__name__)
+
 
 def _need_feature_net(feature_net):
     if feature_net is None:
