@@ -14,6 +14,9 @@ static inline hipStream_t rw_s(rw_stream_t s) { return (hipStream_t)s; }
 
 static inline int64_t rw_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// what a launcher asks of a pointer before it takes the kernel form with 16-byte loads or stores
+static inline bool rw_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // Compute units of the CURRENT device (queried once per device; 256 on a whole MI355X, fewer on a partitioned one): the
 // workgroup count of the persistent kernels, which own a CU each.
 static inline int rw_cu_count(void) {

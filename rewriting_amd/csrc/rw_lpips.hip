@@ -14,8 +14,6 @@
 // outside the edit, and the expansion cancels there.
 #include "rw_common.h"
 
-static inline bool lp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------
 // The tap kernel.  Memory-bound: at 1024^2 the first tap is 256 MB per image and input.  Every value comes from HBM ONCE: a
 // workgroup owns a run of P = 2^p_log2 consecutive pixels of one image and stages both maps' ch x P values in LDS (rows
@@ -36,142 +34,196 @@ static inline bool lp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0
 #define LP_MAX_TILE_FLOATS 32768             // what RW_LPIPS_TILE may ask for: 128 KB, one workgroup per CU
 #define LP_RED_FLOATS 512                    // the groups' partial sums: [2][256]
 
-struct LpTap {
-  const float* f0; const float* f1; const float* lin; float* d;
+// the tile of a workgroup, as both tap kernels read it
+struct LpTile {
+  const float* f0; const float* f1; const float* lin;
   int ch, p_log2;
   int64_t hw, f1_stride, tiles_per_image;
+};
+
+// The tile view: where this workgroup's tile lies in LDS and in the two maps, and which (pixel, channel group) this thread is.
+template <bool STAGED> struct LpTileView {
+  const LpTile& p;
+  float* t0; float* t1; float* red;              // the two staged maps [c][P] (STAGED) and the reduction floats behind them
+  const float* g0; const float* g1;              // the tile's first pixel in channel 0 of f0 and f1
+  int64_t b, p0, at0;                            // image, first pixel, and g0's offset: that of acc and out as well
+  int P, G, valid, px, g;                        // valid: the tile's pixels inside the map; tid == g * P + px
+  bool ok;                                       // px is one of them
+  __device__ __forceinline__ LpTileView(const LpTile& tile_of, float* lds) : p(tile_of) {
+    const int tid = threadIdx.x;
+    P = 1 << p.p_log2;
+    G = 256 >> p.p_log2;
+    t0 = lds;
+    t1 = t0 + (STAGED ? p.ch * P : 0);
+    red = t1 + (STAGED ? p.ch * P : 0);
+    const int64_t tile = blockIdx.x;
+    b = tile / p.tiles_per_image;
+    p0 = (tile - b * p.tiles_per_image) * P;
+    at0 = b * p.ch * p.hw + p0;
+    g0 = p.f0 + at0;
+    g1 = p.f1 + b * p.f1_stride + p0;
+    valid = (int)(p.hw - p0 < P ? p.hw - p0 : P);
+    px = tid & (P - 1);
+    g = tid >> p.p_log2;
+    ok = px < valid;
+  }
+  __device__ __forceinline__ float a_of(int c) const {
+    return STAGED ? t0[(c << p.p_log2) + px] : (ok ? g0[(int64_t)c * p.hw + px] : 0.f);
+  }
+  __device__ __forceinline__ float b_of(int c) const {
+    return STAGED ? t1[(c << p.p_log2) + px] : (ok ? g1[(int64_t)c * p.hw + px] : 0.f);
+  }
+};
+
+// The staging: both maps' ch x P values into t0 and t1, zeros past the map's end; ends behind a barrier.
+template <bool V4> __device__ __forceinline__ void lp_stage(const LpTileView<true>& v) {
+  const LpTile& p = v.p;
+  const int tid = threadIdx.x;
+  if (V4) {                                      // hw % 4 == 0 and P % 4 == 0: a quad is inside the map or outside it
+    const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
+    // four quads of each map per thread and step, all eight loads issued before the first LDS write: a full 64-channel
+    // tile is two steps, and a CU's two workgroups keep 64 KB in flight
+    for (int t4 = tid; t4 < quads; t4 += 1024) {
+      float4 a[4], bq[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int t = t4 + 256 * j;
+        const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
+        a[j] = bq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < quads && 4 * q < v.valid) {
+          a[j] = *reinterpret_cast<const float4*>(v.g0 + (int64_t)c * p.hw + 4 * q);
+          bq[j] = *reinterpret_cast<const float4*>(v.g1 + (int64_t)c * p.hw + 4 * q);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int t = t4 + 256 * j;
+        if (t < quads) {
+          reinterpret_cast<float4*>(v.t0)[t] = a[j];
+          reinterpret_cast<float4*>(v.t1)[t] = bq[j];
+        }
+      }
+    }
+  } else {
+    const int n = p.ch << p.p_log2;
+    for (int t = tid; t < n; t += 256) {
+      const int c = t >> p.p_log2, q = t & (v.P - 1);
+      const bool ok = q < v.valid;
+      v.t0[t] = ok ? v.g0[(int64_t)c * p.hw + q] : 0.f;
+      v.t1[t] = ok ? v.g1[(int64_t)c * p.hw + q] : 0.f;
+    }
+  }
+  __syncthreads();
+}
+
+// The group tree: every thread's partial sum(s) -- ROWS = 1: s0, ROWS = 2: s0 and s1 -- meet in red[r][tid] and are added
+// pairwise over the channel groups; then red[r][px] holds the pixel's sum, behind a barrier.
+template <int ROWS, bool STAGED>
+__device__ __forceinline__ void lp_group_sum(const LpTileView<STAGED>& v, float s0, float s1 = 0.f) {
+  const int tid = threadIdx.x;
+  v.red[tid] = s0;                               // tid == g * P + px
+  if (ROWS == 2) v.red[256 + tid] = s1;
+  __syncthreads();
+  for (int s = v.G >> 1; s > 0; s >>= 1) {
+    if (v.g < s) {
+      v.red[tid] += v.red[tid + (s << v.p.p_log2)];
+      if (ROWS == 2) v.red[256 + tid] += v.red[256 + tid + (s << v.p.p_log2)];
+    }
+    __syncthreads();
+  }
+}
+
+// The norms walk: (|f0|, |f1|) over the channels of this thread's pixel; red is free again when it returns.  (The square roots
+// are taken here, in front of the barrier, where the kernels had them.)
+template <bool STAGED> __device__ __forceinline__ void lp_norms(const LpTileView<STAGED>& v, float& r0, float& r1) {
+  float s0 = 0.f, s1 = 0.f;
+  for (int c = v.g; c < v.p.ch; c += v.G) {
+    const float a = v.a_of(c), bv = v.b_of(c);
+    s0 = fmaf(a, a, s0);
+    s1 = fmaf(bv, bv, s1);
+  }
+  lp_group_sum<2>(v, s0, s1);
+  r0 = sqrtf(v.red[v.px]);
+  r1 = sqrtf(v.red[256 + v.px]);
+  __syncthreads();
+}
+
+struct LpTap {
+  LpTile t;
+  float* d;
 };
 
 template <bool STAGED, bool V4>
 __global__ void __launch_bounds__(256) lpips_tap_kernel(const LpTap p) {
   extern __shared__ __attribute__((aligned(16))) float lp_lds[];
-  const int tid = threadIdx.x;
-  const int P = 1 << p.p_log2, G = 256 >> p.p_log2;
-  float* t0 = lp_lds;
-  float* t1 = t0 + (STAGED ? p.ch * P : 0);
-  float* red = t1 + (STAGED ? p.ch * P : 0);
-  const int64_t tile = blockIdx.x;
-  const int64_t b = tile / p.tiles_per_image, p0 = (tile - b * p.tiles_per_image) * P;
-  const float* g0 = p.f0 + b * p.ch * p.hw + p0;
-  const float* g1 = p.f1 + b * p.f1_stride + p0;
-  const int valid = (int)(p.hw - p0 < P ? p.hw - p0 : P);
-  if (STAGED) {
-    if (V4) {                                    // hw % 4 == 0 and P % 4 == 0: a quad is inside the map or outside it
-      const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
-      // four quads of each map per thread and step, all eight loads issued before the first LDS write: a full 64-channel
-      // tile is two steps, and a CU's two workgroups keep 64 KB in flight
-      for (int t4 = tid; t4 < quads; t4 += 1024) {
-        float4 a[4], bq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int t = t4 + 256 * j;
-          const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
-          a[j] = bq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t < quads && 4 * q < valid) {
-            a[j] = *reinterpret_cast<const float4*>(g0 + (int64_t)c * p.hw + 4 * q);
-            bq[j] = *reinterpret_cast<const float4*>(g1 + (int64_t)c * p.hw + 4 * q);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int t = t4 + 256 * j;
-          if (t < quads) {
-            reinterpret_cast<float4*>(t0)[t] = a[j];
-            reinterpret_cast<float4*>(t1)[t] = bq[j];
-          }
-        }
-      }
-    } else {
-      const int n = p.ch << p.p_log2;
-      for (int t = tid; t < n; t += 256) {
-        const int c = t >> p.p_log2, q = t & (P - 1);
-        const bool ok = q < valid;
-        t0[t] = ok ? g0[(int64_t)c * p.hw + q] : 0.f;
-        t1[t] = ok ? g1[(int64_t)c * p.hw + q] : 0.f;
-      }
-    }
-    __syncthreads();
-  }
-  const int px = tid & (P - 1), g = tid >> p.p_log2;
-  const bool ok = px < valid;
-  auto a_of = [&](int c) __attribute__((always_inline)) {
-    return STAGED ? t0[(c << p.p_log2) + px] : (ok ? g0[(int64_t)c * p.hw + px] : 0.f);
-  };
-  auto b_of = [&](int c) __attribute__((always_inline)) {
-    return STAGED ? t1[(c << p.p_log2) + px] : (ok ? g1[(int64_t)c * p.hw + px] : 0.f);
-  };
-  float s0 = 0.f, s1 = 0.f;
-  for (int c = g; c < p.ch; c += G) {
-    const float a = a_of(c), bv = b_of(c);
-    s0 = fmaf(a, a, s0);
-    s1 = fmaf(bv, bv, s1);
-  }
-  red[tid] = s0;                                 // tid == g * P + px
-  red[256 + tid] = s1;
-  __syncthreads();
-  for (int s = G >> 1; s > 0; s >>= 1) {
-    if (g < s) {
-      red[tid] += red[tid + (s << p.p_log2)];
-      red[256 + tid] += red[256 + tid + (s << p.p_log2)];
-    }
-    __syncthreads();
-  }
-  const float den0 = sqrtf(red[px]) + 1e-10f, den1 = sqrtf(red[256 + px]) + 1e-10f;    // a zero vector: 0 / (0 + eps) = 0
-  __syncthreads();
+  const LpTileView<STAGED> v(p.t, lp_lds);
+  if constexpr (STAGED) lp_stage<V4>(v);
+  float r0, r1;
+  lp_norms(v, r0, r1);
+  const float den0 = r0 + 1e-10f, den1 = r1 + 1e-10f;                    // a zero vector: 0 / (0 + eps) = 0
   float acc = 0.f;
-  for (int c = g; c < p.ch; c += G) {
-    const float t = a_of(c) / den0 - b_of(c) / den1;
-    acc = fmaf(p.lin[c], t * t, acc);
+  for (int c = v.g; c < p.t.ch; c += v.G) {
+    const float t = v.a_of(c) / den0 - v.b_of(c) / den1;
+    acc = fmaf(p.t.lin[c], t * t, acc);
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = G >> 1; s > 0; s >>= 1) {
-    if (g < s) red[tid] += red[tid + (s << p.p_log2)];
-    __syncthreads();
-  }
-  if (g == 0 && ok) p.d[b * p.hw + p0 + px] = red[px];
+  lp_group_sum<1>(v, acc);
+  if (v.g == 0 && v.ok) p.d[v.b * p.t.hw + v.p0 + v.px] = v.red[v.px];
 }
 
-template <bool STAGED, bool V4>
-static int lp_launch_tap(const LpTap& p, int64_t tiles, size_t ldsb, hipStream_t s) {
-  if (ldsb > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void*)lpips_tap_kernel<STAGED, V4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)ldsb);
+// The tile choice and everything else of a launch that depends on the shapes alone.
+struct LpTapShape {
+  int64_t tiles;
+  size_t lds_bytes;                              // the staged maps and red_floats behind them
+  bool staged, v4;                               // v4: 16-byte staging is possible as far as f0, f1 and hw go
+};
+
+// fills t and s; an error code where the launch is refused
+static int lp_tap_shape(const float* f0, const float* f1, const float* lin, int batch, int f1_batch, int ch, int64_t hw,
+                        int red_floats, LpTile* t, LpTapShape* s) {
+  const int dflt = 2 * (int64_t)ch * 32 <= LP_TILE_FLOATS ? LP_TILE_FLOATS : LP_WIDE_TILE_FLOATS;
+  int tile = rw_env_int("RW_LPIPS_TILE", dflt);
+  if (tile < 2 || tile > LP_MAX_TILE_FLOATS) tile = dflt;
+  s->staged = 2 * (int64_t)ch <= tile;
+  int p_log2 = 8;
+  while (s->staged && p_log2 > 0 && 2 * (int64_t)ch << p_log2 > tile) --p_log2;
+  while (p_log2 > 0 && (1 << (p_log2 - 1)) >= hw) --p_log2;              // a small map: more channel groups, fewer idle pixels
+  t->f0 = f0; t->f1 = f1; t->lin = lin; t->ch = ch; t->p_log2 = p_log2; t->hw = hw;
+  t->f1_stride = f1_batch == 1 ? 0 : (int64_t)ch * hw;
+  t->tiles_per_image = rw_cdiv(hw, 1 << p_log2);
+  s->tiles = t->tiles_per_image * batch;
+  if (s->tiles > 0x7fffffff) return RW_ERR_UNSUPPORTED;
+  s->lds_bytes = sizeof(float) * ((s->staged ? ((size_t)2 * ch << p_log2) : 0) + red_floats);
+  s->v4 = s->staged && p_log2 >= 2 && hw % 4 == 0 && rw_aligned16(f0) && rw_aligned16(f1);
+  return 0;
+}
+
+// kernel = the <STAGED, V4> instance of either tap kernel that s and v4 ask for
+template <class P> static int lp_launch_tap(void (*kernel)(P), const P& p, const LpTapShape& s, rw_stream_t stream) {
+  if (s.lds_bytes > 65536) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds_bytes);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL((lpips_tap_kernel<STAGED, V4>), dim3((unsigned)tiles), dim3(256), ldsb, s, p);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)s.tiles), dim3(256), s.lds_bytes, rw_s(stream), p);
   return RW_LAUNCH_RESULT();
 }
+#define LP_TAP_KERNEL(kernel, s, v4) (!(s).staged ? kernel<false, false> : (v4) ? kernel<true, true> : kernel<true, false>)
 
 extern "C" int rw_lpips_tap_f32(const float* f0, const float* f1, const float* lin, float* d, int batch, int f1_batch, int ch,
                                 int64_t hw, rw_stream_t stream) {
   RW_CHECK_ARG(f0 && f1 && lin && d && batch > 0 && ch > 0 && hw > 0 && (f1_batch == batch || f1_batch == 1));
-  const int dflt = 2 * (int64_t)ch * 32 <= LP_TILE_FLOATS ? LP_TILE_FLOATS : LP_WIDE_TILE_FLOATS;
-  int tile = rw_env_int("RW_LPIPS_TILE", dflt);
-  if (tile < 2 || tile > LP_MAX_TILE_FLOATS) tile = dflt;
-  const bool staged = 2 * (int64_t)ch <= tile;
-  int p_log2 = 8;
-  while (staged && p_log2 > 0 && 2 * (int64_t)ch << p_log2 > tile) --p_log2;
-  while (p_log2 > 0 && (1 << (p_log2 - 1)) >= hw) --p_log2;              // a small map: more channel groups, fewer idle pixels
   LpTap p;
-  p.f0 = f0; p.f1 = f1; p.lin = lin; p.d = d; p.ch = ch; p.p_log2 = p_log2; p.hw = hw;
-  p.f1_stride = f1_batch == 1 ? 0 : (int64_t)ch * hw;
-  p.tiles_per_image = rw_cdiv(hw, 1 << p_log2);
-  const int64_t tiles = p.tiles_per_image * batch;
-  if (tiles > 0x7fffffff) return RW_ERR_UNSUPPORTED;
-  const size_t ldsb = sizeof(float) * ((staged ? ((size_t)2 * ch << p_log2) : 0) + LP_RED_FLOATS);
-  const bool v4 = staged && p_log2 >= 2 && hw % 4 == 0 && lp_aligned16(f0) && lp_aligned16(f1);
-  if (!staged) return lp_launch_tap<false, false>(p, tiles, ldsb, rw_s(stream));
-  if (v4) return lp_launch_tap<true, true>(p, tiles, ldsb, rw_s(stream));
-  return lp_launch_tap<true, false>(p, tiles, ldsb, rw_s(stream));
+  LpTapShape s;
+  if (const int rc = lp_tap_shape(f0, f1, lin, batch, f1_batch, ch, hw, LP_RED_FLOATS, &p.t, &s)) return rc;
+  p.d = d;
+  return lp_launch_tap(LP_TAP_KERNEL(lpips_tap_kernel, s, s.v4), p, s, stream);
 }
 
 // ---------------------------------------------------------------------------------------
 // The tap kernel's adjoint to f0 (LPIPS as a loss: lpips.LPIPS.loss).  With r0 = |f0|, den0 = r0 + 1e-10 (r1, den1 likewise),
 // t_c = f0_c / den0 - f1_c / den1 -- the normalised DIFFERENCE as in the forward -- and S = sum_c lin_c t_c f0_c:
 //   out[b][j][p] = acc[b][j][p] + gd[b][p] (2 / den0) (lin_j t_j - f0_j S / (r0 den0))
-// The same tile: both maps' ch x P values staged once, then THREE walks -- the norms, S, the outputs -- with the channel groups'
-// partial sums added pairwise as above.  The third walk is elementwise, so with 16-byte staging (V4) it takes the staging's
+// The forward's tile, by its own pieces: lp_tap_shape chooses it, LpTileView and lp_stage lay it out, then THREE walks -- lp_norms,
+// S (lp_group_sum<1>), the outputs.  The third walk is elementwise, so with 16-byte staging (V4) it takes lp_stage's
 // own mapping, a thread per (channel, quad of pixels): acc is read and out written 16 bytes per lane; each element is read
 // and written by one thread, so out may be acc.  A pixel with r0 == 0 contributes exactly 0: the formula's derivative there is
 // a 1 / eps spike (torch's autograd of the formula returns NaN, sqrt'(0) 0), and inside the module every element of such a
@@ -181,9 +233,9 @@ extern "C" int rw_lpips_tap_f32(const float* f0, const float* f1, const float* l
 #define LP_GRAD_RED_FLOATS 1024              // [4][256]: the partial sums, then the four per-pixel values
 
 struct LpTapGrad {
-  const float* f0; const float* f1; const float* lin; const float* gd; const float* acc; float* out;
-  int ch, p_log2, relu_mask;
-  int64_t hw, f1_stride, tiles_per_image;
+  LpTile t;
+  const float* gd; const float* acc; float* out;
+  int relu_mask;
 };
 
 __device__ __forceinline__ float lp_tap_grad_value(float a, float bv, float lin, float acc, float den0, float den1, float k,
@@ -198,118 +250,47 @@ __device__ __forceinline__ float lp_tap_grad_value(float a, float bv, float lin,
 template <bool STAGED, bool V4>
 __global__ void __launch_bounds__(256) lpips_tap_grad_kernel(const LpTapGrad p) {
   extern __shared__ __attribute__((aligned(16))) float lp_lds[];
-  const int tid = threadIdx.x;
-  const int P = 1 << p.p_log2, G = 256 >> p.p_log2;
-  float* t0 = lp_lds;
-  float* t1 = t0 + (STAGED ? p.ch * P : 0);
-  float* red = t1 + (STAGED ? p.ch * P : 0);
-  const int64_t tile = blockIdx.x;
-  const int64_t b = tile / p.tiles_per_image, p0 = (tile - b * p.tiles_per_image) * P;
-  const int64_t at0 = b * p.ch * p.hw + p0;                   // of f0, acc and out
-  const float* g0 = p.f0 + at0;
-  const float* g1 = p.f1 + b * p.f1_stride + p0;
-  const int valid = (int)(p.hw - p0 < P ? p.hw - p0 : P);
-  if (STAGED) {
-    if (V4) {
-      const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
-      for (int t4 = tid; t4 < quads; t4 += 1024) {
-        float4 a[4], bq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int t = t4 + 256 * j;
-          const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
-          a[j] = bq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t < quads && 4 * q < valid) {
-            a[j] = *reinterpret_cast<const float4*>(g0 + (int64_t)c * p.hw + 4 * q);
-            bq[j] = *reinterpret_cast<const float4*>(g1 + (int64_t)c * p.hw + 4 * q);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int t = t4 + 256 * j;
-          if (t < quads) {
-            reinterpret_cast<float4*>(t0)[t] = a[j];
-            reinterpret_cast<float4*>(t1)[t] = bq[j];
-          }
-        }
-      }
-    } else {
-      const int n = p.ch << p.p_log2;
-      for (int t = tid; t < n; t += 256) {
-        const int c = t >> p.p_log2, q = t & (P - 1);
-        const bool ok = q < valid;
-        t0[t] = ok ? g0[(int64_t)c * p.hw + q] : 0.f;
-        t1[t] = ok ? g1[(int64_t)c * p.hw + q] : 0.f;
-      }
-    }
-    __syncthreads();
-  }
-  const int px = tid & (P - 1), g = tid >> p.p_log2;
-  const bool ok = px < valid;
-  auto a_of = [&](int c) __attribute__((always_inline)) {
-    return STAGED ? t0[(c << p.p_log2) + px] : (ok ? g0[(int64_t)c * p.hw + px] : 0.f);
-  };
-  auto b_of = [&](int c) __attribute__((always_inline)) {
-    return STAGED ? t1[(c << p.p_log2) + px] : (ok ? g1[(int64_t)c * p.hw + px] : 0.f);
-  };
+  const LpTile& tl = p.t;
+  const LpTileView<STAGED> v(tl, lp_lds);
+  if constexpr (STAGED) lp_stage<V4>(v);
   // walk 1: the norms
-  float s0 = 0.f, s1 = 0.f;
-  for (int c = g; c < p.ch; c += G) {
-    const float a = a_of(c), bv = b_of(c);
-    s0 = fmaf(a, a, s0);
-    s1 = fmaf(bv, bv, s1);
-  }
-  red[tid] = s0;
-  red[256 + tid] = s1;
-  __syncthreads();
-  for (int s = G >> 1; s > 0; s >>= 1) {
-    if (g < s) {
-      red[tid] += red[tid + (s << p.p_log2)];
-      red[256 + tid] += red[256 + tid + (s << p.p_log2)];
-    }
-    __syncthreads();
-  }
-  const float r0 = sqrtf(red[px]);
-  const float den0 = r0 + 1e-10f, den1 = sqrtf(red[256 + px]) + 1e-10f;
-  __syncthreads();
+  float r0, r1;
+  lp_norms(v, r0, r1);
+  const float den0 = r0 + 1e-10f, den1 = r1 + 1e-10f;
   // walk 2: S
   float acc = 0.f;
-  for (int c = g; c < p.ch; c += G) {
-    const float a = a_of(c);
-    const float t = a / den0 - b_of(c) / den1;
-    acc = fmaf(p.lin[c] * t, a, acc);
+  for (int c = v.g; c < tl.ch; c += v.G) {
+    const float a = v.a_of(c);
+    const float t = a / den0 - v.b_of(c) / den1;
+    acc = fmaf(tl.lin[c] * t, a, acc);
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = G >> 1; s > 0; s >>= 1) {
-    if (g < s) red[tid] += red[tid + (s << p.p_log2)];
-    __syncthreads();
-  }
-  const float big_s = red[px];
-  const bool live = ok && r0 > 0.f;
-  const float k = live ? p.gd[b * p.hw + p0 + px] * (2.f / den0) : 0.f;
+  lp_group_sum<1>(v, acc);
+  const float big_s = v.red[v.px];
+  const bool live = v.ok && r0 > 0.f;
+  const float k = live ? p.gd[v.b * tl.hw + v.p0 + v.px] * (2.f / den0) : 0.f;
   const float m = live ? big_s / r0 / den0 : 0.f;
   // walk 3: the outputs
   if (V4) {
+    float* red = v.red;
     __syncthreads();                                           // every thread has read its S
-    if (g == 0) {
-      red[px] = den0;
-      red[256 + px] = den1;
-      red[512 + px] = k;
-      red[768 + px] = m;
+    if (v.g == 0) {
+      red[v.px] = den0;
+      red[256 + v.px] = den1;
+      red[512 + v.px] = k;
+      red[768 + v.px] = m;
     }
     __syncthreads();
-    const int q_log2 = p.p_log2 - 2, quads = p.ch << q_log2;
-    for (int t = tid; t < quads; t += 256) {
+    const int q_log2 = tl.p_log2 - 2, quads = tl.ch << q_log2;
+    for (int t = threadIdx.x; t < quads; t += 256) {
       const int c = t >> q_log2, q = t & ((1 << q_log2) - 1);
-      if (4 * q >= valid) continue;                            // hw % 4 == 0: a quad is inside the map or outside it
-      const float4 a = reinterpret_cast<const float4*>(t0)[t], bq = reinterpret_cast<const float4*>(t1)[t];
+      if (4 * q >= v.valid) continue;                          // hw % 4 == 0: a quad is inside the map or outside it
+      const float4 a = reinterpret_cast<const float4*>(v.t0)[t], bq = reinterpret_cast<const float4*>(v.t1)[t];
       const float4 d0 = reinterpret_cast<const float4*>(red)[q], d1 = reinterpret_cast<const float4*>(red + 256)[q];
       const float4 kq = reinterpret_cast<const float4*>(red + 512)[q], mq = reinterpret_cast<const float4*>(red + 768)[q];
-      const int64_t at = at0 + (int64_t)c * p.hw + 4 * q;
+      const int64_t at = v.at0 + (int64_t)c * tl.hw + 4 * q;
       float4 ac = make_float4(0.f, 0.f, 0.f, 0.f);
       if (p.acc) ac = *reinterpret_cast<const float4*>(p.acc + at);
-      const float lin = p.lin[c];
+      const float lin = tl.lin[c];
       float4 o;
       o.x = lp_tap_grad_value(a.x, bq.x, lin, ac.x, d0.x, d1.x, kq.x, mq.x, p.relu_mask);
       o.y = lp_tap_grad_value(a.y, bq.y, lin, ac.y, d0.y, d1.y, kq.y, mq.y, p.relu_mask);
@@ -317,50 +298,25 @@ __global__ void __launch_bounds__(256) lpips_tap_grad_kernel(const LpTapGrad p) 
       o.w = lp_tap_grad_value(a.w, bq.w, lin, ac.w, d0.w, d1.w, kq.w, mq.w, p.relu_mask);
       *reinterpret_cast<float4*>(p.out + at) = o;
     }
-  } else if (ok) {
-    for (int c = g; c < p.ch; c += G) {
-      const int64_t at = at0 + (int64_t)c * p.hw + px;
+  } else if (v.ok) {
+    for (int c = v.g; c < tl.ch; c += v.G) {
+      const int64_t at = v.at0 + (int64_t)c * tl.hw + v.px;
       const float ac = p.acc ? p.acc[at] : 0.f;
-      p.out[at] = lp_tap_grad_value(a_of(c), b_of(c), p.lin[c], ac, den0, den1, k, m, p.relu_mask);
+      p.out[at] = lp_tap_grad_value(v.a_of(c), v.b_of(c), tl.lin[c], ac, den0, den1, k, m, p.relu_mask);
     }
   }
-}
-
-template <bool STAGED, bool V4>
-static int lp_launch_tap_grad(const LpTapGrad& p, int64_t tiles, size_t ldsb, hipStream_t s) {
-  if (ldsb > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void*)lpips_tap_grad_kernel<STAGED, V4>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((lpips_tap_grad_kernel<STAGED, V4>), dim3((unsigned)tiles), dim3(256), ldsb, s, p);
-  return RW_LAUNCH_RESULT();
 }
 
 extern "C" int rw_lpips_tap_grad_f32(const float* f0, const float* f1, const float* lin, const float* gd, const float* acc,
                                      float* out, int batch, int f1_batch, int ch, int64_t hw, int relu_mask,
                                      rw_stream_t stream) {
   RW_CHECK_ARG(f0 && f1 && lin && gd && out && batch > 0 && ch > 0 && hw > 0 && (f1_batch == batch || f1_batch == 1));
-  const int dflt = 2 * (int64_t)ch * 32 <= LP_TILE_FLOATS ? LP_TILE_FLOATS : LP_WIDE_TILE_FLOATS;
-  int tile = rw_env_int("RW_LPIPS_TILE", dflt);
-  if (tile < 2 || tile > LP_MAX_TILE_FLOATS) tile = dflt;
-  const bool staged = 2 * (int64_t)ch <= tile;
-  int p_log2 = 8;
-  while (staged && p_log2 > 0 && 2 * (int64_t)ch << p_log2 > tile) --p_log2;
-  while (p_log2 > 0 && (1 << (p_log2 - 1)) >= hw) --p_log2;
   LpTapGrad p;
-  p.f0 = f0; p.f1 = f1; p.lin = lin; p.gd = gd; p.acc = acc; p.out = out;
-  p.ch = ch; p.p_log2 = p_log2; p.relu_mask = relu_mask != 0; p.hw = hw;
-  p.f1_stride = f1_batch == 1 ? 0 : (int64_t)ch * hw;
-  p.tiles_per_image = rw_cdiv(hw, 1 << p_log2);
-  const int64_t tiles = p.tiles_per_image * batch;
-  if (tiles > 0x7fffffff) return RW_ERR_UNSUPPORTED;
-  const size_t ldsb = sizeof(float) * ((staged ? ((size_t)2 * ch << p_log2) : 0) + LP_GRAD_RED_FLOATS);
-  const bool v4 = staged && p_log2 >= 2 && hw % 4 == 0 && lp_aligned16(f0) && lp_aligned16(f1) && lp_aligned16(out) &&
-                  (!acc || lp_aligned16(acc));
-  if (!staged) return lp_launch_tap_grad<false, false>(p, tiles, ldsb, rw_s(stream));
-  if (v4) return lp_launch_tap_grad<true, true>(p, tiles, ldsb, rw_s(stream));
-  return lp_launch_tap_grad<true, false>(p, tiles, ldsb, rw_s(stream));
+  LpTapShape s;
+  if (const int rc = lp_tap_shape(f0, f1, lin, batch, f1_batch, ch, hw, LP_GRAD_RED_FLOATS, &p.t, &s)) return rc;
+  p.gd = gd; p.acc = acc; p.out = out; p.relu_mask = relu_mask != 0;
+  const bool v4 = s.v4 && rw_aligned16(out) && (!acc || rw_aligned16(acc));      // the third walk's 16-byte loads and stores
+  return lp_launch_tap(LP_TAP_KERNEL(lpips_tap_grad_kernel, s, v4), p, s, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -14,8 +14,6 @@
 // atomics, nothing zeroed beforehand, nothing but launches on the caller's stream: two runs give the same bits.
 #include "rw_common.h"
 
-static inline bool pc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 __device__ __forceinline__ float pc_relu(float v) { return v > 0.f ? v : 0.f; }
 
 // ---------------------------------------------------------------------------------------
@@ -77,7 +75,7 @@ __global__ void __launch_bounds__(256) percept_act_pool_kernel(const float* x, c
 extern "C" int rw_bias_relu_pool_f32(const float* x, const float* bias, float* y, float* pooled, int batch, int ch, int h,
                                      int w, rw_stream_t stream) {
   RW_CHECK_ARG(x && bias && (y || pooled) && batch > 0 && ch > 0 && h > 0 && w > 0);
-  const bool v4 = w % 4 == 0 && pc_aligned16(x) && pc_aligned16(y) && pc_aligned16(pooled);
+  const bool v4 = w % 4 == 0 && rw_aligned16(x) && rw_aligned16(y) && rw_aligned16(pooled);
   const int64_t items = (int64_t)batch * ch * ((h + 1) / 2) * (v4 ? w / 4 : (w + 1) / 2);
   const dim3 grid((unsigned)rw_stream_grid(items, 256));
   if (v4)
@@ -160,7 +158,7 @@ extern "C" int rw_bias_relu_pool_grad_f32(const float* g, const float* y, float*
                                           int pooled, rw_stream_t stream) {
   RW_CHECK_ARG(g && y && gx && batch > 0 && ch > 0 && h > 0 && w > 0 && (pooled == 0 || pooled == 1));
   RW_CHECK_ARG(g != gx && y != gx);
-  const bool v4 = w % 4 == 0 && pc_aligned16(g) && pc_aligned16(y) && pc_aligned16(gx);
+  const bool v4 = w % 4 == 0 && rw_aligned16(g) && rw_aligned16(y) && rw_aligned16(gx);
   const int64_t items = (int64_t)batch * ch * ((h + 1) / 2) * (v4 ? w / 4 : (w + 1) / 2);
   const dim3 grid((unsigned)rw_stream_grid(items, 256));
   if (v4)
@@ -349,7 +347,7 @@ extern "C" int rw_conv3x3_rgb_f32(const float* x, const float* w, const float* b
   int64_t tiles_x, tiles;
   const int refused = pc_rgb_refusal(batch, out_ch, h, w_, &tiles_x, &tiles);
   if (refused) return refused;
-  const int vec = w_ % 4 == 0 && pc_aligned16(y);
+  const int vec = w_ % 4 == 0 && rw_aligned16(y);
   hipLaunchKernelGGL(percept_conv_rgb_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, rw_s(stream), x, w, bias, y,
                      out_ch, h, w_, (int)tiles_x, vec);
   return RW_LAUNCH_RESULT();
@@ -361,7 +359,7 @@ extern "C" int rw_conv3x3_rgb_input_grad_f32(const float* g, const float* w, flo
   int64_t tiles_x, tiles;
   const int refused = pc_rgb_refusal(batch, out_ch, h, w_, &tiles_x, &tiles);
   if (refused) return refused;
-  const int vec = w_ % 4 == 0 && pc_aligned16(gx);
+  const int vec = w_ % 4 == 0 && rw_aligned16(gx);
   hipLaunchKernelGGL(percept_conv_rgb_input_grad_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(256), 0, rw_s(stream), g,
                      w, gx, out_ch, h, w_, (int)tiles_x, vec);
   return RW_LAUNCH_RESULT();

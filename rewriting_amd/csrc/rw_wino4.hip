@@ -1441,7 +1441,7 @@ static bool wino4_shape_ok(int out_ch, int in_ch, int h, int w) {
 }
 
 // the window arrives in 16-byte items (conv_wino36b_body): with w % 64 == 0 every image and row starts where the map does
-static bool w4_window_aligned(const float* x) { return ((uintptr_t)x & 15) == 0; }
+static bool w4_window_aligned(const float* x) { return rw_aligned16(x); }
 
 extern "C" int rw_conv3x3_wino4_supported(int out_ch, int in_ch, int h, int w) {
   return wino4_shape_ok(out_ch, in_ch, h, w) ? 1 : 0;

@@ -1407,16 +1407,58 @@ def _reduce_scratch(batch, hw, device):
     return torch.empty(n, device=device, dtype=torch.float32)
 
 
-def lpips_tap(f0, f1, lin):
-    """d (B, H, W) of one LPIPS tap (rw_lpips_tap_f32): sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 with the norms
-    over the channels of a pixel; f0 (B, C, H, W), f1 (B or 1, C, H, W), lin (C,).  Read in place."""
+def _lpips_tap_operands(who, f0, f1, lin, gd=None):
+    """the operands of lpips_tap (and, with gd, of lpips_tap_grad), read in place: f0 (B, C, H, W), f1 (B or 1, C, H, W), lin (C,)
+    and gd (B, H, W) on f0's device"""
     f0 = _fmap4(_in_place(f0, 'tap'), 'tap')
     f1 = _in_place(f1, 'second tap', device=f0.device)
     lin = _in_place(lin, 'lin weight', device=f0.device)
+    if gd is not None:
+        gd = _in_place(gd, 'distance gradient', device=f0.device)
     b, c, h, w = f0.shape
-    if f1.dim() != 4 or tuple(f1.shape[1:]) != (c, h, w) or f1.shape[0] not in (1, b) or tuple(lin.shape) != (c,):
-        raise ValueError('lpips_tap takes two maps (B, C, H, W) and (B or 1, C, H, W) and a weight (C,), not %s / %s / %s'
-                         % (tuple(f0.shape), tuple(f1.shape), tuple(lin.shape)))
+    if f1.dim() != 4 or tuple(f1.shape[1:]) != (c, h, w) or f1.shape[0] not in (1, b) or tuple(lin.shape) != (c,) \
+            or (gd is not None and tuple(gd.shape) != (b, h, w)):
+        raise ValueError('%s takes two maps (B, C, H, W) and (B or 1, C, H, W)%s, not %s'
+                         % (who, ' and a weight (C,)' if gd is None else ', a weight (C,) and a gradient (B, H, W)',
+                            ' / '.join(str(tuple(t.shape)) for t in (f0, f1, lin, gd) if t is not None)))
+    return f0, f1, lin, gd
+
+
+def _lpips_tables(tables, k, size, b, weight, device):
+    """(idx, lam, h, w, weight, the weight's batch or 0) of a combine call over k taps: tables of lpips.device_tables for an output
+    of size = (H, W), weight (B or 1, 1, H, W) or None, all on `device`"""
+    idx = _in_place(tables[0], 'index table', torch.int32, device)
+    lam = _in_place(tables[1], 'weight table', device=device)
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1 or tuple(idx.shape) != (k, 2 * h + 2 * w) or tuple(lam.shape) != (k, h + w):
+        raise ValueError('the tables %s / %s do not belong to %d taps and an output of %d x %d'
+                         % (tuple(idx.shape), tuple(lam.shape), k, h, w))
+    if weight is not None:
+        weight = _in_place(weight, 'weight', device=device)
+        if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, h, w) or weight.shape[0] not in (1, b):
+            raise ValueError('the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s' % (b, h, w, tuple(weight.shape)))
+    return idx, lam, h, w, weight, weight.shape[0] if weight is not None else 0
+
+
+def _lpips_maps(struct, tensors):
+    """rw_lpips_maps / rw_lpips_grad_maps of the tensors (B, h_k, w_k)"""
+    maps = struct()
+    for n, t in enumerate(tensors):
+        maps.d[n], maps.h[n], maps.w[n] = t.data_ptr(), t.shape[1], t.shape[2]
+    maps.n = len(tensors)
+    return maps
+
+
+def _lpips_tap_count(who, n):
+    if not 1 <= n <= LPIPS_MAX_TAPS:
+        raise ValueError('%s takes 1 .. %d tap maps, not %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)' % (who, LPIPS_MAX_TAPS, n))
+
+
+def lpips_tap(f0, f1, lin):
+    """d (B, H, W) of one LPIPS tap (rw_lpips_tap_f32): sum_c lin[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 with the norms
+    over the channels of a pixel; f0 (B, C, H, W), f1 (B or 1, C, H, W), lin (C,).  Read in place."""
+    f0, f1, lin, _ = _lpips_tap_operands('lpips_tap', f0, f1, lin)
+    b, c, h, w = f0.shape
     d = torch.empty(b, h, w, device=f0.device, dtype=torch.float32)
     check(lib().rw_lpips_tap_f32(_p(f0), _p(f1), _p(lin), _p(d), b, f1.shape[0], c, h * w, _stream()))
     return d
@@ -1426,36 +1468,22 @@ def lpips_combine(taps, tables, size, weight=None, want_map=True, want_sums=Fals
     """(out (B, 1, H, W) or None, sums (B, 2) or None) of rw_lpips_combine_f32: out = the sum over the tap maps (B, h_k, w_k) of
     their bilinear up-sampling to size = (H, W) with tables = (idx int32 (K, 2H + 2W), lam float32 (K, H + W)) of
     lpips.device_tables; sums[b] = (sum out * weight, sum weight), weight (B or 1, 1, H, W) or None (all ones)."""
-    if not 1 <= len(taps) <= LPIPS_MAX_TAPS:
-        raise ValueError('lpips_combine takes 1 .. %d tap maps, not %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
-                         % (LPIPS_MAX_TAPS, len(taps)))
+    _lpips_tap_count('lpips_combine', len(taps))
     if not (want_map or want_sums):
         raise ValueError('lpips_combine: nothing to compute (want_map=False, want_sums=False)')
     taps = [_in_place(t, 'tap map') for t in taps]
     device = taps[0].device
-    idx = _in_place(tables[0], 'index table', torch.int32, device)
-    lam = _in_place(tables[1], 'weight table', device=device)
-    h, w = int(size[0]), int(size[1])
     b = taps[0].shape[0]
-    k = len(taps)
-    if h < 1 or w < 1 or tuple(idx.shape) != (k, 2 * h + 2 * w) or tuple(lam.shape) != (k, h + w):
-        raise ValueError('the tables %s / %s do not belong to %d taps and an output of %d x %d'
-                         % (tuple(idx.shape), tuple(lam.shape), k, h, w))
-    maps = _lib.LpipsMaps()
+    idx, lam, h, w, weight, weight_batch = _lpips_tables(tables, len(taps), size, b, weight, device)
     for n, t in enumerate(taps):
         if t.dim() != 3 or t.shape[0] != b or 0 in t.shape or t.device != device:
             raise ValueError('tap map %d is %s on %s; every one is (B = %d, h, w) on %s' % (n, tuple(t.shape), t.device, b, device))
-        maps.d[n], maps.h[n], maps.w[n] = t.data_ptr(), t.shape[1], t.shape[2]
-    maps.n = k
-    if weight is not None:
-        weight = _in_place(weight, 'weight', device=device)
-        if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, h, w) or weight.shape[0] not in (1, b):
-            raise ValueError('the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s' % (b, h, w, tuple(weight.shape)))
+    maps = _lpips_maps(_lib.LpipsMaps, taps)
     out = torch.empty(b, 1, h, w, device=device, dtype=torch.float32) if want_map else None
     sums = torch.empty(b, 2, device=device, dtype=torch.float32) if want_sums else None
     scratch = _reduce_scratch(b, h * w, device) if want_sums else None
-    check(lib().rw_lpips_combine_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(weight), weight.shape[0] if weight is not None else 0,
-                                     _p(out), _p(sums), _p(scratch), b, h, w, _stream()))
+    check(lib().rw_lpips_combine_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(weight), weight_batch, _p(out), _p(sums),
+                                     _p(scratch), b, h, w, _stream()))
     return out, sums
 
 
@@ -1464,15 +1492,8 @@ def lpips_tap_grad(f0, f1, lin, gd, acc=None, relu_mask=False, out=None):
     (B, H, W) is the gradient at d, acc (B, C, H, W) the gradient that is already there (None: zeros), out the tensor that
     receives the result -- it may be acc.  relu_mask: an element with f0 <= 0 gets exactly acc.  A pixel whose f0 is all zero
     contributes exactly 0.  Read in place."""
-    f0 = _fmap4(_in_place(f0, 'tap'), 'tap')
-    f1 = _in_place(f1, 'second tap', device=f0.device)
-    lin = _in_place(lin, 'lin weight', device=f0.device)
-    gd = _in_place(gd, 'distance gradient', device=f0.device)
+    f0, f1, lin, gd = _lpips_tap_operands('lpips_tap_grad', f0, f1, lin, gd)
     b, c, h, w = f0.shape
-    if f1.dim() != 4 or tuple(f1.shape[1:]) != (c, h, w) or f1.shape[0] not in (1, b) or tuple(lin.shape) != (c,) \
-            or tuple(gd.shape) != (b, h, w):
-        raise ValueError('lpips_tap_grad takes two maps (B, C, H, W) and (B or 1, C, H, W), a weight (C,) and a gradient (B, H, W), '
-                         'not %s / %s / %s / %s' % (tuple(f0.shape), tuple(f1.shape), tuple(lin.shape), tuple(gd.shape)))
     if acc is not None:
         acc = _in_place(acc, 'incoming gradient', device=f0.device)
         if acc.shape != f0.shape:
@@ -1494,35 +1515,20 @@ def lpips_combine_grad(tap_sizes, tables, ranges, size, gscale, weight=None):
     lpips.device_adjoint_tables, size = (H, W), gscale (B,) the gradient at an image's weighted sum, weight (B or 1, 1, H, W)
     or None (all ones)."""
     tap_sizes = [(int(a), int(b)) for a, b in tap_sizes]
-    if not 1 <= len(tap_sizes) <= LPIPS_MAX_TAPS:
-        raise ValueError('lpips_combine_grad takes 1 .. %d tap maps, not %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
-                         % (LPIPS_MAX_TAPS, len(tap_sizes)))
+    _lpips_tap_count('lpips_combine_grad', len(tap_sizes))
     gscale = _in_place(gscale, 'gradient scale')
     device = gscale.device
-    idx = _in_place(tables[0], 'index table', torch.int32, device)
-    lam = _in_place(tables[1], 'weight table', device=device)
     ranges = _in_place(ranges, 'range table', torch.int32, device)
-    h, w = int(size[0]), int(size[1])
-    k = len(tap_sizes)
     if gscale.dim() != 1 or gscale.shape[0] < 1:
         raise ValueError('the gradient scale must be (B,), not %s' % (tuple(gscale.shape),))
     b = gscale.shape[0]
-    if h < 1 or w < 1 or tuple(idx.shape) != (k, 2 * h + 2 * w) or tuple(lam.shape) != (k, h + w):
-        raise ValueError('the tables %s / %s do not belong to %d taps and an output of %d x %d'
-                         % (tuple(idx.shape), tuple(lam.shape), k, h, w))
+    idx, lam, h, w, weight, weight_batch = _lpips_tables(tables, len(tap_sizes), size, b, weight, device)
     if any(a < 1 or c < 1 for a, c in tap_sizes) or tuple(ranges.shape) != (2 * sum(a + c for a, c in tap_sizes),):
         raise ValueError('the range table %s does not belong to taps of %s' % (tuple(ranges.shape), tap_sizes))
-    if weight is not None:
-        weight = _in_place(weight, 'weight', device=device)
-        if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, h, w) or weight.shape[0] not in (1, b):
-            raise ValueError('the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s' % (b, h, w, tuple(weight.shape)))
     grads = [torch.empty(b, hk, wk, device=device, dtype=torch.float32) for hk, wk in tap_sizes]
-    maps = _lib.LpipsGradMaps()
-    for n, g in enumerate(grads):
-        maps.d[n], maps.h[n], maps.w[n] = g.data_ptr(), g.shape[1], g.shape[2]
-    maps.n = k
-    check(lib().rw_lpips_combine_grad_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(ranges), _p(weight),
-                                          weight.shape[0] if weight is not None else 0, _p(gscale), b, h, w, _stream()))
+    maps = _lpips_maps(_lib.LpipsGradMaps, grads)
+    check(lib().rw_lpips_combine_grad_f32(ctypes.byref(maps), _p(idx), _p(lam), _p(ranges), _p(weight), weight_batch, _p(gscale),
+                                          b, h, w, _stream()))
     return grads
 
 

@@ -22,7 +22,6 @@ of LPIPS v0.1 (``lin{k}.model.1.weight``); the environment variables ``RW_VGG16_
 two files.
 """
 import functools
-import os
 
 import numpy
 import torch
@@ -87,49 +86,54 @@ def adjoint_table(n_in, n_out):
     return tables
 
 
-_device_tables = {}
-_device_adjoint_tables = {}
+_device_cache = {}
+
+
+def _on_device(build, tap_sizes, size, device):
+    """The arrays build(taps, H, W) makes on the host, as tensors on `device`: copied once per (build, sizes, device) and kept,
+    64 entries per build -- then its cache starts again."""
+    device = torch.device(device)
+    h, w = int(size[0]), int(size[1])
+    key = (tuple((int(a), int(b)) for a, b in tap_sizes), h, w, device.type, device.index)
+    cache = _device_cache.setdefault(build, {})
+    tables = cache.get(key)
+    if tables is None:
+        tables = tuple(torch.from_numpy(a).to(device) for a in build(key[0], h, w))
+        if len(cache) >= 64:
+            cache.clear()
+        cache[key] = tables
+    return tables
+
+
+def _adjoint_arrays(taps, h, w):
+    parts = []
+    for hk, wk in taps:
+        parts.extend(adjoint_table(hk, h) + adjoint_table(wk, w))
+    return (numpy.concatenate(parts),)
+
+
+def _forward_arrays(taps, h, w):
+    idx = numpy.empty((len(taps), 2 * h + 2 * w), dtype=numpy.int32)
+    lam = numpy.empty((len(taps), h + w), dtype=numpy.float32)
+    for k, (hk, wk) in enumerate(taps):
+        y0, y1, ly = upsample_table(hk, h)
+        x0, x1, lx = upsample_table(wk, w)
+        idx[k] = numpy.concatenate([y0, y1, x0, x1])
+        lam[k] = numpy.concatenate([ly, lx]).astype(numpy.float32)
+    return idx, lam
 
 
 def device_adjoint_tables(tap_sizes, size, device):
     """int32 (2 sum_k (h_k + w_k),) on `device`, as rw_lpips_combine_grad_f32 reads it: tap after tap the rows' lo, the rows'
     hi, the columns' lo, the columns' hi of adjoint_table.  Copied once per (sizes, device)."""
-    device = torch.device(device)
-    h, w = int(size[0]), int(size[1])
-    key = (tuple((int(a), int(b)) for a, b in tap_sizes), h, w, device.type, device.index)
-    table = _device_adjoint_tables.get(key)
-    if table is None:
-        parts = []
-        for hk, wk in key[0]:
-            parts.extend(adjoint_table(hk, h) + adjoint_table(wk, w))
-        table = torch.from_numpy(numpy.concatenate(parts)).to(device)
-        if len(_device_adjoint_tables) >= 64:
-            _device_adjoint_tables.clear()
-        _device_adjoint_tables[key] = table
-    return table
+    return _on_device(_adjoint_arrays, tap_sizes, size, device)[0]
 
 
 def device_tables(tap_sizes, size, device):
     """(idx int32 (K, 2H + 2W), lam float32 (K, H + W)) on `device` for taps of tap_sizes = ((h_k, w_k), ...) up-sampled to
     size = (H, W), as rw_lpips_combine_f32 reads them: per tap the rows' i0 and i1, then the columns'; the rows' lam, then the
     columns' -- rounded to float32 here, once.  Copied once per (sizes, device)."""
-    device = torch.device(device)
-    h, w = int(size[0]), int(size[1])
-    key = (tuple((int(a), int(b)) for a, b in tap_sizes), h, w, device.type, device.index)
-    tables = _device_tables.get(key)
-    if tables is None:
-        idx = numpy.empty((len(key[0]), 2 * h + 2 * w), dtype=numpy.int32)
-        lam = numpy.empty((len(key[0]), h + w), dtype=numpy.float32)
-        for k, (hk, wk) in enumerate(key[0]):
-            y0, y1, ly = upsample_table(hk, h)
-            x0, x1, lx = upsample_table(wk, w)
-            idx[k] = numpy.concatenate([y0, y1, x0, x1])
-            lam[k] = numpy.concatenate([ly, lx]).astype(numpy.float32)
-        tables = (torch.from_numpy(idx).to(device), torch.from_numpy(lam).to(device))
-        if len(_device_tables) >= 64:
-            _device_tables.clear()
-        _device_tables[key] = tables
-    return tables
+    return _on_device(_forward_arrays, tap_sizes, size, device)
 
 
 class Target:
@@ -149,34 +153,38 @@ class Target:
 
 
 def _evaluate(net, im0, target, w, spatial, keep):
-    """(value (B,), the thirteen activated maps of im0 or [], what the backward needs of the reduction): forward's launches
-    for im0, in forward's order, against the taps of `target`."""
-    b, _, h, wd = im0.shape
-    x0 = (im0.detach() - net.shift) / net.scale
+    """(value (B,), the thirteen activated maps of im0 where keep, else [], what the backward needs of the reduction):
+    forward's walk for im0 and forward's reduction, against the taps of `target`."""
     ds, saved = [], []
-    for index, block in net.blocks():
-        impl = SPLIT_K if x0.shape[3] < SPLIT_K_BELOW else None
-        y0, x0 = block.activate(x0, keep=True, impl=impl)
+    for index, y0 in net._walk(im0, 'all'):
         if index in TAPS:
             ds.append(hip.lpips_tap(y0, target.taps[len(ds)], net.lins[len(ds)]))
         if keep:
             saved.append(y0)
         del y0
-    del x0
-    sizes = tuple((d.shape[1], d.shape[2]) for d in ds)
+    value, total = _reduce(ds, (im0.shape[2], im0.shape[3]), w, spatial, want_map=False)
+    return value, saved, total
+
+
+def _reduce(ds, size, w, spatial, want_map):
+    """(value, the weights' sums (B,) the backward divides by, or None where there are none) of the five d_k for an image of
+    size = (H, W).  spatial: the map (B, 1, H, W) where want_map, else ``sum(map * w) / sum(w)`` per image (w None: ones), which
+    never writes the map.  Not spatial: the sum of the taps' means, (B, 1, 1, 1) where want_map and w is None, else (B,), under
+    w as the 1 x 1 map it is."""
+    device, sizes = ds[0].device, tuple((d.shape[1], d.shape[2]) for d in ds)
     if spatial:
-        _, sums = hip.lpips_combine(ds, device_tables(sizes, (h, wd), im0.device), (h, wd), weight=w, want_map=False,
-                                    want_sums=True)
-        return sums[:, 0] / sums[:, 1], saved, sums[:, 1]
+        out, sums = hip.lpips_combine(ds, device_tables(sizes, size, device), size, weight=w, want_map=want_map,
+                                      want_sums=not want_map)
+        return (out, None) if want_map else (sums[:, 0] / sums[:, 1], sums[:, 1])
     out = 0
-    for d, size in zip(ds, sizes):
-        _, sums = hip.lpips_combine([d], device_tables((size,), size, im0.device), size, want_map=False, want_sums=True)
+    for d, own in zip(ds, sizes):                               # the same entry at the tap's own size: (sum d_k, pixels)
+        _, sums = hip.lpips_combine([d], device_tables((own,), own, device), own, want_map=False, want_sums=True)
         out = out + sums[:, 0] / sums[:, 1]
     if w is None:
-        return out, saved, None
-    _, sums = hip.lpips_combine([out.view(b, 1, 1).contiguous()], device_tables(((1, 1),), (h, wd), im0.device), (h, wd),
-                                weight=w, want_map=False, want_sums=True)
-    return sums[:, 0] / sums[:, 1], saved, sums[:, 1]
+        return (out.view(-1, 1, 1, 1) if want_map else out), None
+    _, sums = hip.lpips_combine([out.view(-1, 1, 1).contiguous()], device_tables(((1, 1),), size, device), size, weight=w,
+                                want_map=False, want_sums=True)
+    return sums[:, 0] / sums[:, 1], sums[:, 1]
 
 
 class _LossFunction(Function):
@@ -240,17 +248,20 @@ class LPIPS(nn.Module):
         head = [(index, block) for (index, _, _, _), block in zip(perceptual.LAYERS, self.features.blocks())]
         return head + [(index, self.tail[str(index)]) for index, _, _, _ in TAIL_LAYERS]
 
+    def _walk(self, im, keep):
+        """Yields (index, y) block by block: the image's network, one block per step.  keep = 'taps': y is the activated map at
+        the five taps and whatever costs nothing elsewhere; 'all': at every block.  The walk holds no reference to a y it has
+        handed over: a map dies when its reader drops it."""
+        x = (im.detach() - self.shift) / self.scale             # not foldable into layer 0: its zero padding comes after
+        for index, block in self.blocks():
+            impl = SPLIT_K if x.shape[3] < SPLIT_K_BELOW else None
+            y, x = block.activate(x, keep=keep == 'all' or index in TAPS, impl=impl)
+            y = [y]                                             # popped as it is handed over: nothing of it stays in this frame
+            yield index, y.pop()
+
     def _check(self, im0, im1, w):
+        perceptual._check_images(self, {'im0': im0, 'im1': im1}, pools=4)
         for name, im in (('im0', im0), ('im1', im1)):
-            if not isinstance(im, torch.Tensor) or im.dim() != 4 or im.shape[1] != 3 or 0 in im.shape:
-                raise ValueError('rewriting_amd: LPIPS takes images (B, 3, H, W), %s is %s'
-                                 % (name, tuple(im.shape) if isinstance(im, torch.Tensor) else type(im).__name__))
-            if not hip.on_device(im):
-                raise RuntimeError('rewriting_amd: LPIPS: %s is on %s; the HIP kernels need a GPU tensor (there is no CPU '
-                                   'fallback)' % (name, im.device))
-            if im.dtype != torch.float32:
-                raise RuntimeError('rewriting_amd: LPIPS: %s is %s; the metric is fp32 only -- cast with .float() (nothing is '
-                                   'converted)' % (name, im.dtype))
             if im.requires_grad and torch.is_grad_enabled():
                 raise RuntimeError('rewriting_amd: LPIPS is forward only (the reference uses it under no_grad, as a metric): %s '
                                    'requires a gradient -- call it under torch.no_grad() or detach the image' % name)
@@ -258,9 +269,6 @@ class LPIPS(nn.Module):
         if tuple(im1.shape[1:]) != (3, h, wd) or im1.shape[0] not in (1, b) or im1.device != im0.device:
             raise ValueError('rewriting_amd: LPIPS: im1 is %s on %s, im0 %s on %s -- the sizes must match, im1\'s batch may be 1'
                              % (tuple(im1.shape), im1.device, tuple(im0.shape), im0.device))
-        if h < MIN_SIZE or wd < MIN_SIZE:
-            raise ValueError('rewriting_amd: LPIPS halves its maps four times: an image of %d x %d leaves no last tap, it must '
-                             'be at least %d x %d' % (h, wd, MIN_SIZE, MIN_SIZE))
         if w is not None:
             if not isinstance(w, torch.Tensor) or w.dim() != 4 or tuple(w.shape[1:]) != (1, h, wd) or w.shape[0] not in (1, b):
                 raise ValueError('rewriting_amd: LPIPS: the weight must be (B or 1, 1, H, W) = (%d or 1, 1, %d, %d), not %s'
@@ -270,61 +278,31 @@ class LPIPS(nn.Module):
                                    % (w.device, im0.device))
             if w.dtype != torch.float32:
                 raise RuntimeError('rewriting_amd: LPIPS: the weight is %s; the metric is fp32 only -- cast with .float()' % w.dtype)
-        for name, p in self.named_parameters():
-            if p.requires_grad:
-                raise RuntimeError('rewriting_amd: LPIPS is frozen and forward only: parameter %s requires a gradient -- call '
-                                   'requires_grad_(False) on it' % name)
-            if p.dtype != torch.float32 or p.device != im0.device:
-                raise RuntimeError('rewriting_amd: LPIPS: parameter %s is %s on %s, the images float32 on %s -- move the '
-                                   'network with .to(device)' % (name, p.dtype, p.device, im0.device))
 
     def forward(self, im0, im1, w=None, spatial=True, taps=None):
         """spatial=True: (B, 1, H, W), the per-pixel distance; spatial=False: (B, 1, 1, 1), the sum of the taps' means; with
         w (B or 1, 1, H, W): (B,), ``sum(out * w, [1, 2, 3]) / sum(w, [1, 2, 3])`` (metrics/distances.py:49-56) -- the map is
         then never written.  taps: a list that receives the five d_k (B, h_k, w_k)."""
         self._check(im0, im1, w)
-        b, _, h, wd = im0.shape
         with torch.no_grad():
-            x0 = (im0.detach() - self.shift) / self.scale       # not foldable into layer 0: its zero padding comes after
-            x1 = (im1.detach() - self.shift) / self.scale
-            ds = []
-            for index, block in self.blocks():
-                tap = index in TAPS
-                impl = SPLIT_K if x0.shape[3] < SPLIT_K_BELOW else None
-                y0, x0 = block.activate(x0, keep=tap, impl=impl)
-                y1, x1 = block.activate(x1, keep=tap, impl=impl)
-                if tap:
+            ds, second = [], self._walk(im1, 'taps')
+            for index, y0 in self._walk(im0, 'taps'):           # side by side, y0 then y1 (a zip would hold on to its last pair)
+                y1 = next(second)[1]
+                if index in TAPS:
                     ds.append(hip.lpips_tap(y0, y1, self.lins[len(ds)]))
                 del y0, y1                                      # a tap lives until its d_k exists
-            del x0, x1
+            del second
             if taps is not None:
                 taps.extend(ds)
-            sizes = tuple((d.shape[1], d.shape[2]) for d in ds)
-            if spatial:
-                out, sums = hip.lpips_combine(ds, device_tables(sizes, (h, wd), im0.device), (h, wd), weight=w,
-                                              want_map=w is None, want_sums=w is not None)
-                return out if w is None else sums[:, 0] / sums[:, 1]
-            out = 0
-            for d, size in zip(ds, sizes):                      # the same entry at the tap's own size: (sum d_k, pixels)
-                _, sums = hip.lpips_combine([d], device_tables((size,), size, im0.device), size, want_map=False, want_sums=True)
-                out = out + sums[:, 0] / sums[:, 1]
-            if w is None:
-                return out.view(b, 1, 1, 1)
-            _, sums = hip.lpips_combine([out.view(b, 1, 1).contiguous()], device_tables(((1, 1),), (h, wd), im0.device), (h, wd),
-                                        weight=w, want_map=False, want_sums=True)
-            return sums[:, 0] / sums[:, 1]
-
+            return _reduce(ds, (im0.shape[2], im0.shape[3]), w, spatial, want_map=w is None)[0]
 
     def target(self, im1):
         """The taps of im1 (B or 1, 3, H, W) as a ``Target``: its network runs here, once, under no_grad."""
         im1 = im1.detach() if isinstance(im1, torch.Tensor) else im1
         self._check(im1, im1, None)
         with torch.no_grad():
-            x1 = (im1 - self.shift) / self.scale
             taps = []
-            for index, block in self.blocks():
-                impl = SPLIT_K if x1.shape[3] < SPLIT_K_BELOW else None
-                y1, x1 = block.activate(x1, keep=True, impl=impl)
+            for index, y1 in self._walk(im1, 'all'):
                 if index in TAPS:
                     taps.append(y1)
                 del y1
@@ -333,8 +311,8 @@ class LPIPS(nn.Module):
     def loss(self, im0, target, w=None, spatial=True, trace=None):
         """(B,): LPIPS of im0 against `target` -- a ``Target`` or an image (B or 1, 3, H, W), whose taps are then computed
         here -- per image: with w (B or 1, 1, H, W) ``sum(out * w) / sum(w)`` of the spatial map, without it the map's mean;
-        spatial=False: the sum of the taps' means.  The value is ``forward``'s, bit for bit (the same launches in the same
-        order).  Differentiable to im0 and to nothing else: the target, w and the parameters may not require a gradient.
+        spatial=False: the sum of the taps' means.  The value is ``forward``'s, bit for bit (the same ``_walk`` and the same
+        ``_reduce``).  Differentiable to im0 and to nothing else: the target, w and the parameters may not require a gradient.
         Under no_grad, or when im0 requires none, nothing is saved.  trace: a list that receives im0's thirteen activated
         maps (the ReLU and pool decisions of the device) when a gradient is recorded."""
         for name, t in (('the target', target), ('the weight', w)):
@@ -391,28 +369,11 @@ def from_state_dicts(vgg_sd, lin_sd):
     """An LPIPS with the convolutions of `vgg_sd` -- the keys ``0.weight`` ... ``28.bias``, bare or with torchvision's prefix
     ``features.`` (``classifier.*`` is ignored) -- and the lin layers of `lin_sd`: ``lin{k}.model.1.weight`` (1, C, 1, 1) as
     LPIPS v0.1 stores them, or bare ``lin{k}``."""
-    bare = {}
-    for key, value in vgg_sd.items():
-        if key.startswith('classifier.'):
-            continue
-        bare[key[len('features.'):] if key.startswith('features.') else key] = value
-    net = LPIPS(perceptual.from_state_dict({k: v for k, v in bare.items()
-                                            if not (k.split('.')[0].isdigit() and int(k.split('.')[0]) > perceptual.LAST_LAYER)}))
-    own = {'%d.%s' % (index, kind): (out_ch, in_ch, 3, 3) if kind == 'weight' else (out_ch,)
-           for index, in_ch, out_ch, _ in TAIL_LAYERS for kind in ('weight', 'bias')}
-    for name in bare:
-        index = name.split('.')[0]
-        if index.isdigit() and int(index) > perceptual.LAST_LAYER and name not in own:
-            raise KeyError('rewriting_amd: %r is no parameter of VGG16 features[:30] (past layer 20: %s)'
-                           % (name, ', '.join(sorted(own, key=lambda n: (int(n.split('.')[0]), n)))))
-    missing = sorted(set(own) - set(bare))
-    if missing:
-        raise KeyError('rewriting_amd: the state dict lacks %s of VGG16 features[:30]' % ', '.join(missing))
-    for name, shape in own.items():
-        if tuple(bare[name].shape) != shape:
-            raise ValueError('rewriting_amd: %r is %s, VGG16 has %s there' % (name, tuple(bare[name].shape), shape))
+    net = LPIPS(perceptual.from_state_dict(vgg_sd))             # which leaves the layers past 20 to the line below
+    tail = perceptual._layer_tensors(vgg_sd, TAIL_LAYERS, lambda index: index <= perceptual.LAST_LAYER, 'features[21:30]')
+    for name, value in tail.items():
         index, kind = name.split('.')
-        getattr(net.tail[index], kind).data.copy_(bare[name].detach().to(torch.float32))
+        getattr(net.tail[index], kind).data.copy_(value)
     for p, value in zip(net.lins, _lin_weights(lin_sd)):
         p.data.copy_(value)
     return net.eval()
@@ -420,8 +381,7 @@ def from_state_dicts(vgg_sd, lin_sd):
 
 def default_weights():
     """The file RW_LPIPS_WEIGHTS names, or None when it is unset or names no readable file."""
-    path = os.environ.get(WEIGHTS_ENV)
-    return path if path and os.path.isfile(path) and os.access(path, os.R_OK) else None
+    return perceptual.default_weights(WEIGHTS_ENV)
 
 
 def lpips_vgg(vgg_path=None, lin_path=None):

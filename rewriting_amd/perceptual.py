@@ -108,6 +108,35 @@ class _BlockFunction(Function):
         return ctx.block.input_grad(g.contiguous(), y), None, None
 
 
+def _check_images(module, images, pools):
+    """What VGG16Features and lpips.LPIPS ask before their first launch: every one of images = {name: tensor} is (B, 3, H, W),
+    on a HIP device, float32 and large enough for `pools` 2x2 pools; every parameter of `module` is frozen, float32 and on
+    the images' device."""
+    who, least = type(module).__name__, 2 ** pools
+    for name, im in images.items():
+        if not isinstance(im, torch.Tensor) or im.dim() != 4 or im.shape[1] != 3 or 0 in im.shape:
+            raise ValueError('rewriting_amd: %s takes images (B, 3, H, W), %s is %s'
+                             % (who, name, tuple(im.shape) if isinstance(im, torch.Tensor) else type(im).__name__))
+        if not hip.on_device(im):
+            raise RuntimeError('rewriting_amd: %s: %s is on %s; the HIP kernels need a GPU tensor (there is no CPU fallback)'
+                               % (who, name, im.device))
+        if im.dtype != torch.float32:
+            raise RuntimeError('rewriting_amd: %s: %s is %s; the network is fp32 only -- cast with .float() (nothing is '
+                               'converted)' % (who, name, im.dtype))
+        if im.shape[2] < least or im.shape[3] < least:
+            raise ValueError('rewriting_amd: %s halves its maps %d times: %s (an image, or a bounds= crop) of %d x %d leaves '
+                             'nothing, it must be at least %d x %d' % (who, pools, name, im.shape[2], im.shape[3], least, least))
+    device = next(iter(images.values())).device
+    for name, p in module.named_parameters():
+        if p.requires_grad:
+            raise RuntimeError('rewriting_amd: %s is frozen: parameter %s requires a gradient, and the network has an adjoint '
+                               'to its input only (weight gradients are not implemented) -- call requires_grad_(False) on it'
+                               % (who, name))
+        if p.dtype != torch.float32 or p.device != device:
+            raise RuntimeError('rewriting_amd: %s: parameter %s is %s on %s, the images float32 on %s -- move the network '
+                               'with .to(device)' % (who, name, p.dtype, p.device, device))
+
+
 class VGG16Features(nn.Module):
     """torchvision's ``vgg16().features[:21]`` (VF of rewrite/ganrewrite.py:303-304): (B, 3, H, W) float32 on a HIP device
     -> (B, 512, H // 8, W // 8), the ReLU after conv4_2.  Its parameters carry torchvision's names (``0.weight`` ...
@@ -123,26 +152,7 @@ class VGG16Features(nn.Module):
 
     def forward(self, x, trace=None):
         """trace: a list that receives every block's activated map before its pool (the decisions of the device)."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3 or 0 in x.shape:
-            raise ValueError('rewriting_amd: VGG16Features takes images (B, 3, H, W), not %s'
-                             % (tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__,))
-        if x.shape[2] < 8 or x.shape[3] < 8:
-            raise ValueError('rewriting_amd: VGG16Features halves its maps three times: an image (or a bounds= crop) of %d x %d '
-                             'leaves no features, it must be at least 8 x 8' % (x.shape[2], x.shape[3]))
-        if not hip.on_device(x):
-            raise RuntimeError('rewriting_amd: VGG16Features: the input is on %s; the HIP kernels need a GPU tensor '
-                               '(there is no CPU fallback)' % x.device)
-        if x.dtype != torch.float32:
-            raise RuntimeError('rewriting_amd: VGG16Features: the input is %s; the perceptual network is fp32 only -- cast '
-                               'with .float() (nothing is converted)' % x.dtype)
-        for name, p in self.named_parameters():
-            if p.requires_grad:
-                raise RuntimeError('rewriting_amd: VGG16Features is frozen: parameter %s requires a gradient, and the '
-                                   'network has an adjoint to its input only (weight gradients are not implemented) -- '
-                                   'call requires_grad_(False) on it' % name)
-            if p.dtype != torch.float32 or p.device != x.device:
-                raise RuntimeError('rewriting_amd: VGG16Features: parameter %s is %s on %s, the input float32 on %s -- move '
-                                   'the network with .to(device)' % (name, p.dtype, p.device, x.device))
+        _check_images(self, {'the input': x}, pools=3)
         for block in self.blocks():
             if grad.records(x):
                 x = _BlockFunction.apply(x, block, trace)
@@ -157,27 +167,33 @@ def from_state_dict(sd):
     """A VGG16Features with the weights of `sd`: the bare keys ``0.weight`` ... ``19.bias``, or a whole torchvision VGG16
     state dict (``features.N.*``; its ``classifier.*`` entries and the layers past 20 are ignored)."""
     net = VGG16Features()
-    own = net.state_dict()
+    net.load_state_dict(_layer_tensors(sd, LAYERS, lambda index: index > LAST_LAYER, 'features[:21]'))
+    return net.eval()
+
+
+def _layer_tensors(sd, layers, elsewhere, part):
+    """{'N.weight', 'N.bias': float32 tensor} of the convolutions `layers` (rows as LAYERS) out of the state dict `sd`, whose
+    keys are bare or carry torchvision's prefix ``features.``.  ``classifier.*`` and a convolution N with elsewhere(N) belong to
+    others and are skipped; any other key is refused, and so are a missing key and a wrong shape, by name.  part: what the
+    messages call the layers."""
+    shapes = {'%d.%s' % (index, kind): (out_ch, in_ch, 3, 3) if kind == 'weight' else (out_ch,)
+              for index, in_ch, out_ch, _ in layers for kind in ('weight', 'bias')}
     found = {}
     for key, value in sd.items():
         name = key[len('features.'):] if key.startswith('features.') else key
-        if key.startswith('classifier.'):
-            continue
         index = name.split('.')[0]
-        if index.isdigit() and int(index) > LAST_LAYER:
+        if key.startswith('classifier.') or (index.isdigit() and elsewhere(int(index))):
             continue
-        if name not in own:
-            raise KeyError('rewriting_amd: %r is no parameter of VGG16 features[:21] (expected %s, bare or with the prefix '
-                           '"features.")' % (key, ', '.join(sorted(own, key=lambda n: (int(n.split('.')[0]), n)))))
-        if tuple(value.shape) != tuple(own[name].shape):
-            raise ValueError('rewriting_amd: %r is %s, VGG16 has %s there' % (key, tuple(value.shape),
-                                                                              tuple(own[name].shape)))
+        if name not in shapes:
+            raise KeyError('rewriting_amd: %r is no parameter of VGG16 %s (expected %s, bare or with the prefix "features.")'
+                           % (key, part, ', '.join(shapes)))
+        if tuple(value.shape) != shapes[name]:
+            raise ValueError('rewriting_amd: %r is %s, VGG16 has %s there' % (key, tuple(value.shape), shapes[name]))
         found[name] = value.detach().to(torch.float32)
-    missing = sorted(set(own) - set(found))
+    missing = sorted(set(shapes) - set(found))
     if missing:
-        raise KeyError('rewriting_amd: the state dict lacks %s of VGG16 features[:21]' % ', '.join(missing))
-    net.load_state_dict(found)
-    return net.eval()
+        raise KeyError('rewriting_amd: the state dict lacks %s of VGG16 %s' % (', '.join(missing), part))
+    return found
 
 
 def vgg16_features(path):
@@ -185,7 +201,7 @@ def vgg16_features(path):
     return from_state_dict(torch.load(path, map_location='cpu', weights_only=True))
 
 
-def default_weights():
-    """The file RW_VGG16_WEIGHTS names, or None when it is unset or names no readable file."""
-    path = os.environ.get(WEIGHTS_ENV)
+def default_weights(env=WEIGHTS_ENV):
+    """The file the environment variable `env` (RW_VGG16_WEIGHTS) names, or None when it is unset or names no readable file."""
+    path = os.environ.get(env)
     return path if path and os.path.isfile(path) and os.access(path, os.R_OK) else None

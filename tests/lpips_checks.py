@@ -88,6 +88,29 @@ def twin(sd, lins, im0, im1, dtype, w=None, spatial=True, taps=None):
     return torch.sum(out * w, [1, 2, 3]) / torch.sum(w, [1, 2, 3])
 
 
+# ---- the inputs of the kernel tests (tests/test_gpu_lpips.py, tests/test_gpu_lpips_grad.py) ----------------------------------
+def randn(shape, seed):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def on_device(t, offset=0):
+    """t on the device, `offset` floats past an allocation's start (a contiguous view: the wrappers read it in place)"""
+    flat = torch.empty(t.numel() + offset, device='cuda', dtype=t.dtype)
+    view = flat[offset:].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4 * offset
+    return view
+
+
+# The tap kernel's and its adjoint's cases: (shape of f0, batch of f1, offset of f0 in floats).  (2,64,8,8): 16-byte loads (and,
+# in the adjoint, stores), one tile per image; with f1 of batch 1; with f0 at a 4-byte offset (the scalar staging); (1,512,2,2):
+# 16 pixels per tile narrowed to 4, 64 channel groups; (1,128,5,7): an odd map, two tiles of 32 pixels, the second with three;
+# (1,256,1,1): one pixel, 256 channel groups; (1,5,3,3): fewer channels than groups; (1,64,12,12): three tiles per image, the
+# last one short; (1,8200,2,2): more channels than LDS holds -- the form that reads global memory twice
+TAP_CASES = [((2, 64, 8, 8), 2, 0), ((2, 64, 8, 8), 1, 0), ((2, 64, 8, 8), 2, 1), ((1, 512, 2, 2), 1, 0), ((1, 128, 5, 7), 1, 0),
+             ((1, 256, 1, 1), 1, 0), ((1, 5, 3, 3), 1, 0), ((1, 64, 12, 12), 1, 0), ((1, 8200, 2, 2), 1, 0)]
+
+
 # ---- the inputs of the module tests -------------------------------------------------------------------------------------
 SHAPES = [(2, 3, 32, 32), (1, 3, 20, 28), (1, 3, 16, 16)]
 KINDS = ('independent', 'near', 'box')
@@ -149,17 +172,8 @@ rel = P.rel
 
 
 def report(section, figures):
-    """into lpips.json in the directory RW_REPORT_DIR names (default: test_reports/, which git ignores)"""
-    directory = os.environ.get('RW_REPORT_DIR') or os.path.join(P.ROOT, 'test_reports')
-    os.makedirs(directory, exist_ok=True)
-    path = os.path.join(directory, 'lpips.json')
-    data = {}
-    if os.path.isfile(path):
-        with open(path) as f:
-            data = json.load(f)
-    data[section] = figures
-    with open(path, 'w') as f:
-        json.dump(data, f, indent=1, sort_keys=True)
+    """into lpips.json of perceptual_checks.report"""
+    P.report('lpips.json', section, figures)
 
 
 # ---- CPU stand-ins for the wrappers of rw_lpips.hip ----------------------------------------------------------------------

@@ -103,17 +103,8 @@ def axis_matrix(n_in, n_out, dtype=torch.float64, lam=None):
 
 
 def report(section, figures):
-    """into lpips_grad.json in the directory RW_REPORT_DIR names (default: test_reports/, which git ignores)"""
-    directory = os.environ.get('RW_REPORT_DIR') or os.path.join(P.ROOT, 'test_reports')
-    os.makedirs(directory, exist_ok=True)
-    path = os.path.join(directory, 'lpips_grad.json')
-    data = {}
-    if os.path.isfile(path):
-        with open(path) as f:
-            data = json.load(f)
-    data[section] = figures
-    with open(path, 'w') as f:
-        json.dump(data, f, indent=1, sort_keys=True)
+    """into lpips_grad.json of perceptual_checks.report"""
+    P.report('lpips_grad.json', section, figures)
 
 
 # ---- CPU stand-ins for the two adjoint wrappers --------------------------------------------------------------------------

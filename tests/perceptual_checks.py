@@ -109,15 +109,12 @@ def differing_share(got, own):
     return relu_d / max(relu_n, 1), pool_d / max(pool_n, 1)
 
 
-def report_path():
-    """perceptual.json in the directory RW_REPORT_DIR names (default: test_reports/, which git ignores)"""
+def report(file_name, section, figures):
+    """figures as `section` of file_name (perceptual.json here; lpips_checks and lpips_grad_checks name their own) in the
+    directory RW_REPORT_DIR names (default: test_reports/, which git ignores)"""
     directory = os.environ.get('RW_REPORT_DIR') or os.path.join(ROOT, 'test_reports')
     os.makedirs(directory, exist_ok=True)
-    return os.path.join(directory, 'perceptual.json')
-
-
-def report(section, figures):
-    path = report_path()
+    path = os.path.join(directory, file_name)
     data = {}
     if os.path.isfile(path):
         with open(path) as f:

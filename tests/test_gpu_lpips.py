@@ -19,30 +19,11 @@ D_REF_MAP, D_REF_TAP = 2e-5, 5e-5   # the conditions on the reference alone (tes
 EPS = L.EPS
 
 
-def randn(shape, seed):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def on_device(t, offset=0):
-    """t on the device, `offset` floats past an allocation's start (a contiguous view: the wrappers read it in place)"""
-    flat = torch.empty(t.numel() + offset, device=DEV, dtype=t.dtype)
-    view = flat[offset:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 * offset
-    return view
+randn, on_device = L.randn, L.on_device
 
 
 # ------------------------------------------------------------------------------------------ the tap kernel
-# (shape of f0, batch of f1, offset of f0 in floats).  (2,64,8,8): 16-byte loads, one tile per image; with f1 of batch 1; with f0
-# at a 4-byte offset (the scalar staging); (1,512,2,2): 16 pixels per tile narrowed to 4, 64 channel groups; (1,128,5,7): an odd
-# map, two tiles of 32 pixels, the second with three; (1,256,1,1): one pixel, 256 channel groups; (1,5,3,3): fewer channels than groups;
-# (1,64,12,12): three tiles per image, the last one short; (1,8200,2,2): more channels than LDS holds -- the form that reads
-# global memory twice
-TAP_CASES = [((2, 64, 8, 8), 2, 0), ((2, 64, 8, 8), 1, 0), ((2, 64, 8, 8), 2, 1), ((1, 512, 2, 2), 1, 0), ((1, 128, 5, 7), 1, 0),
-             ((1, 256, 1, 1), 1, 0), ((1, 5, 3, 3), 1, 0), ((1, 64, 12, 12), 1, 0), ((1, 8200, 2, 2), 1, 0)]
-
-
-@pytest.mark.parametrize('shape,f1_batch,offset', TAP_CASES)
+@pytest.mark.parametrize('shape,f1_batch,offset', L.TAP_CASES)
 def test_tap_kernel_against_the_float64_formula(shape, f1_batch, offset):
     """maps as taps are (ReLU outputs); independent, near (f1 = f0 + 1e-3 noise), a pixel all-zero in both maps (exactly 0), a
     pixel zero in one map only.  d_hip <= 8 d_ref, 2-norm, d_ref the float32 torch formula's error."""

@@ -19,27 +19,10 @@ MARGIN, D_REF_MAX = LG.MARGIN, LG.D_REF_MAX
 EPS = L.EPS
 
 
-def randn(shape, seed):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+randn, on_device = L.randn, L.on_device
 
 
-def on_device(t, offset=0):
-    """t on the device, `offset` floats past an allocation's start (a contiguous view: the wrappers read it in place)"""
-    flat = torch.empty(t.numel() + offset, device=DEV, dtype=t.dtype)
-    view = flat[offset:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 * offset
-    return view
-
-
-# ------------------------------------------------------------------------------------------ the tap adjoint
-# (shape of f0, batch of f1, offset of f0 in floats): the forward's cases (tests/test_gpu_lpips.py) -- 16-byte staging and
-# stores, f1 of batch 1, the scalar path, 64 channel groups, an odd map in two tiles, one pixel, fewer channels than groups,
-# and more channels than LDS holds (the form that reads global memory)
-TAP_CASES = [((2, 64, 8, 8), 2, 0), ((2, 64, 8, 8), 1, 0), ((2, 64, 8, 8), 2, 1), ((1, 512, 2, 2), 1, 0), ((1, 128, 5, 7), 1, 0),
-             ((1, 256, 1, 1), 1, 0), ((1, 5, 3, 3), 1, 0), ((1, 8200, 2, 2), 1, 0)]
-
-
+# ------------------------------------------------------------------------------------------ the tap adjoint: the forward's cases
 def tap_inputs(shape, f1_batch, kind, seed):
     """(f0, f1, lin, gd, dead): ReLU outputs (about half of f0's elements are 0); with more than two pixels, pixel (0, 0) is
     zero in both maps, (0, 1) in f0 only and the last one in f1 only; dead: the pixels whose f0 is all zero"""
@@ -64,7 +47,7 @@ def tap_autograd(f0, f1, lin, gd, dead, dtype):
     return leaf.grad * ~dead[:, None]
 
 
-@pytest.mark.parametrize('shape,f1_batch,offset', TAP_CASES)
+@pytest.mark.parametrize('shape,f1_batch,offset', L.TAP_CASES)
 def test_tap_adjoint_against_float64_autograd(shape, f1_batch, offset):
     """d_hip <= 8 d_ref (2-norm; d_ref the float32 autograd's error, below 1e-5 on the independent maps up to 512 channels);
     dead pixels exactly 0, a pixel zero in f1 only finite and inside the bar; acc is added exactly, out may be acc, relu_mask

@@ -145,7 +145,7 @@ def test_conv3x3_rgb_and_its_adjoint_against_float64(shape):
     err_g = (got_g.cpu().double() - want_g).abs()
     print('conv3x3_rgb_input_grad %s: worst err / bound %.3f' % (shape, (err_g / bound_g).max().item()))
     assert bool((err_g <= bound_g).all()), (err_g / bound_g).max().item()
-    P.report('rgb_layer_%dx%dx%d' % (shape[0], shape[2], shape[3]),
+    P.report('perceptual.json', 'rgb_layer_%dx%dx%d' % (shape[0], shape[2], shape[3]),
              dict(forward_err_over_bound=(err / bound).max().item(), adjoint_err_over_bound=(err_g / bound_g).max().item()))
 
 
@@ -215,7 +215,7 @@ def test_features_against_the_float64_twin(shape, launches):
                                                                          d_hip / d_ref))
         if not (d_ref < D_REF_MAX and d_hip <= MARGIN * d_ref):
             bad.append(rows[-1])
-    P.report('features_%dx%dx%d' % (shape[0], shape[2], shape[3]), rows)
+    P.report('perceptual.json', 'features_%dx%dx%d' % (shape[0], shape[2], shape[3]), rows)
     assert not bad, bad
 
 
@@ -247,7 +247,7 @@ def test_input_gradient_of_the_loss_term(shape, launches):
     relu_share, pool_share = P.differing_share(forced, own)
     print('input gradient %s: d_hip %.3e d_ref %.3e ratio %.2f; decisions differing from float64: relu %.2e pool %.2e'
           % (shape, d_hip, d_ref, d_hip / d_ref, relu_share, pool_share))
-    P.report('input_gradient_%dx%dx%d' % (shape[0], shape[2], shape[3]),
+    P.report('perceptual.json', 'input_gradient_%dx%dx%d' % (shape[0], shape[2], shape[3]),
              dict(d_hip=d_hip, d_ref=d_ref, ratio=d_hip / d_ref, loss=loss.item(), loss_float64=losses[torch.float64],
                   relu_decisions_differing=relu_share, pool_decisions_differing=pool_share))
     assert abs(loss.item() - losses[torch.float64]) <= 1e-5 * abs(losses[torch.float64])
@@ -285,7 +285,7 @@ def test_all_weights_insert_with_the_perceptual_network(default, tmp_path, monke
     gw.all_weights_insert(x, z, bounds=bounds, niter=1, lr=0.01, feature_net=net,
                           update_callback=lambda it, loss: losses.append(loss.item()))
     print('all_weights_insert (%s): loss %.8f, float64 %.8f' % ('default' if default else 'feature_net', losses[0], want))
-    P.report('all_weights_insert_%s' % ('default' if default else 'feature_net'),
+    P.report('perceptual.json', 'all_weights_insert_%s' % ('default' if default else 'feature_net'),
              dict(loss=losses[0], loss_float64=want, rel=abs(losses[0] - want) / abs(want)))
     assert len(losses) == 1 and abs(losses[0] - want) <= 1e-5 * abs(want), (losses, want)
     after = gw.model.state_dict()
