@@ -42,7 +42,8 @@ typedef void* rw_stream_t; /* hipStream_t */
  * Buffers packed by an older library do not fit this one: repack, as the Python side does per weight version.
  * rw_resize_bilinear_u8 joins at 11, as rw_render_bytes_f32 and rw_png_* did: an entry that is only ADDED changes no
  * existing call, and the loader names the missing symbol of a library built before it ("stale ... no symbol").  So do
- * rw_rgb_combine_up_f32 and rw_conv3x3_wino4[h]_to_rgb_up_f32 (the ToRGB skip upsampled inside its consumer). */
+ * rw_rgb_combine_up_f32 and rw_conv3x3_wino4[h]_to_rgb_up_f32 (the ToRGB skip upsampled inside its consumer), and
+ * rw_png_inflate_u8 / rw_png_unfilter_u8 (PNG decoding). */
 int rw_abi_version(void);
 const char* rw_error_string(int code);
 
@@ -628,6 +629,50 @@ int rw_png_encode_u8(const uint8_t* stream, const uint32_t* table, uint8_t* code
                      int height, int width, rw_stream_t stream_);
 int rw_png_compact_u8(const uint8_t* coded, const uint32_t* lengths, const uint32_t* adler, uint64_t* offsets,
                       uint32_t* head, uint8_t* bytes, int64_t capacity, int64_t segments, rw_stream_t stream_);
+
+/* PNG decoding on the device: the way back -- what PIL.Image.open(path).convert('RGB') does for every file that
+ * compute_dl reads (metrics/distances.py:67-70) and what renormalize.from_url does for a data URL (utils/renormalize.py),
+ * for a batch of files of ONE shape (H, W, channels), 8 bits a sample, not interlaced: channels 1 (grey), 3 (truecolour)
+ * or 4 (truecolour with alpha).  The host reads the chunks (signature, IHDR, CRC-32 of every chunk, the IDATs joined,
+ * IEND), checks the two bytes of the zlib header and hands over the RAW DEFLATE stream of each file (RFC 1951: the IDAT
+ * payload without its 2-byte header and 4-byte Adler trailer); it compares the trailer with the sums below.
+ *   rw_png_inflate_u8   coded: one buffer that holds every stream; span (images, 2) uint64 = offset into coded and length
+ *                       of each stream (any alignment; nothing outside a span is read).  One wave inflates one stream
+ *                       into stream + image * stride, `expect` = H (1 + channels W) bytes of it; stride >= expect, a
+ *                       multiple of 16, stream 16-byte aligned.  status (images, 4) uint32 = code, bytes produced, s1, s2:
+ *                       s1 = sum d_k and s2 = sum (n - k) d_k mod 65521 over the n bytes produced, so the stream's
+ *                       Adler-32 is (1 + s1) mod 65521 | ((n + s2) mod 65521) << 16 -- one step of the fold of
+ *                       rw_png_filter_u8's sums.  What is accepted is what zlib accepts (stored, fixed and dynamic
+ *                       blocks; its rules for code-length sets: rewriting_amd/csrc/rw_inflate_core.h); bytes after the
+ *                       final block are ignored.  The first defect ends a stream; the bytes before it are stored.
+ *   rw_png_unfilter_u8  the five filters of the PNG specification (section 9) undone, mod 256, bytes per pixel = channels;
+ *                       out (images, H, W, 3) uint8, the layout of rw_render_bytes_f32: grey is written to all three
+ *                       channels, alpha is dropped (PIL's convert('RGB') for modes L and RGBA).  An image whose status
+ *                       code is not RW_PNG_OK is skipped: its pixels are written as zeros.  A filter type above 4 sets
+ *                       RW_PNG_BAD_FILTER (the row is read as type 0; the image is not to be used).
+ * Both are integer work and one writer per byte: an image's result is the same on every run, alone or in a batch.  No
+ * global atomics, nothing zeroed first; neither kernel reads what it wrote to global memory.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null pointer, images < 1 or a grid past 31 bits, stride below the stream's
+ * length, stride or stream not 16-byte aligned (inflate).  RW_ERR_UNSUPPORTED (nothing launched): channels outside
+ * {1, 3, 4}, H or W < 1, expect < 1, a stream H (1 + channels W) of 2^31 bytes or more, W above 16 384 (the unfilter keeps
+ * one row of 4 W bytes in LDS). */
+#define RW_PNG_OK 0
+#define RW_PNG_TRUNCATED 1        /* the coded bytes end inside a block */
+#define RW_PNG_BAD_BLOCK_TYPE 2   /* BTYPE 3 */
+#define RW_PNG_STORED_LENGTH 3    /* LEN is not the complement of NLEN */
+#define RW_PNG_BAD_CODELEN_SET 4  /* code-length code over-subscribed or incomplete; repeat without a length, repeat past the count */
+#define RW_PNG_BAD_LITLEN_SET 5   /* literal/length lengths over-subscribed or incomplete; more than 286 of them */
+#define RW_PNG_BAD_DIST_SET 6     /* distance lengths over-subscribed or incomplete; more than 30 of them */
+#define RW_PNG_NO_END_OF_BLOCK 7  /* symbol 256 has no code */
+#define RW_PNG_BAD_SYMBOL 8       /* literal/length 286, 287, distance 30, 31, or bits that are no code of an incomplete set */
+#define RW_PNG_DISTANCE_TOO_FAR 9 /* a match reaches before the first byte */
+#define RW_PNG_OUTPUT_OVER 10     /* more output than expect */
+#define RW_PNG_OUTPUT_UNDER 11    /* the final block ends with less output than expect */
+#define RW_PNG_BAD_FILTER 12      /* a row's filter type is above 4 */
+int rw_png_inflate_u8(const uint8_t* coded, const uint64_t* span, uint8_t* stream, int64_t stride, int64_t expect,
+                      uint32_t* status, int64_t images, rw_stream_t stream_);
+int rw_png_unfilter_u8(const uint8_t* stream, int64_t stride, uint32_t* status, uint8_t* out, int64_t images, int height,
+                       int width, int channels, rw_stream_t stream_);
 
 /* Tiles at the UI's size: the PIL.Image.resize(size, resample=BILINEAR) of renormalize.as_url(img, size=...)
  * (utils/renormalize.py:22-32), byte for byte, for image (images, H, W, 3) uint8 -- what rw_render_bytes_f32 writes --

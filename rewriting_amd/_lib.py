@@ -114,6 +114,8 @@ SIGNATURES = {
     'rw_png_filter_u8': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_void_p]),
     'rw_png_encode_u8': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_void_p]),
     'rw_png_compact_u8': (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_void_p]),
+    'rw_png_inflate_u8': (c_int, [c_void_p] * 3 + [c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    'rw_png_unfilter_u8': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     'rw_resize_bilinear_u8': (c_int, [c_void_p] * 7 + [c_int64] + [c_int] * 6 + [c_void_p]),
     'rw_conv3x3_wino_supported': (c_int, [c_int, c_int, c_int, c_int]),
     'rw_packed_conv_weight_wino_elems': (ctypes.c_longlong, [c_int, c_int]),

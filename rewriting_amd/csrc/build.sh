@@ -23,7 +23,7 @@ if [ "$(cat "$OBJ/.flags" 2>/dev/null)" != "$FLAGS $NOPK $*" ]; then rm -f "$OBJ
 pids=()
 for src in "$HERE"/*.hip; do
   obj="$OBJ/$(basename "${src%.hip}").o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/rw_common.h" -nt "$obj" ] || [ "$HERE/../../include/rewriting_hip.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/rw_common.h" -nt "$obj" ] || [ "$HERE/rw_inflate_core.h" -nt "$obj" ] || [ "$HERE/../../include/rewriting_hip.h" -nt "$obj" ]; then
     # per-file flags: a leading comment line "// hipcc-flags: ..." in the source
     extra="$(sed -n 's|^// hipcc-flags: ||p' "$src" | head -1)"
     # a leading comment line "// hipcc-keep-packed-fp32" keeps the packed fp32 instructions for that file (rw_solve.hip: see there)

@@ -66,17 +66,27 @@ def _load_image(path):
 
 
 def compute_dl(before_dir, after_dir, seg_dir, indices, src=(1708,), srcc=2, mode='lpips', batch_size=100, net=None,
-               device='cuda', name_template='{}.png'):
+               device='cuda', name_template='{}.png', device_decode=False):
     """(total, count) of metrics/distances.py:96-136 over the pairs ``before_dir/<key>.png``, ``after_dir/<key>.png`` with the
     segmentations ``seg_dir/<key>.pth`` (a tensor whose row `srcc` is the (H, W) map) for key in indices -- `batch_size` pairs
     per device call.  total: the sum of the per-image distances (count: their number), or in 'pixel' mode the masked L1 sum
-    (count: the masks' sum)."""
+    (count: the masks' sum).  device_decode: the `before` and `after` files are decoded on the device (pngreader.read_batch,
+    as_float) instead of by PIL, one file at a time, on the host; the images, and so (total, count), are the same bit for
+    bit.  The segmentations are torch.load'ed either way."""
+    if device_decode:
+        from . import pngreader
+
+        def load(dirname, chunk):
+            return pngreader.as_float(pngreader.read_batch([os.path.join(dirname, name_template.format(k)) for k in chunk],
+                                                           device=device))
+    else:
+        def load(dirname, chunk):
+            return torch.stack([_load_image(os.path.join(dirname, name_template.format(k))) for k in chunk]).to(device)
     total, count = 0.0, 0
     keys = [int(k) for k in indices]
     for start in range(0, len(keys), batch_size):
         chunk = keys[start:start + batch_size]
-        before = torch.stack([_load_image(os.path.join(before_dir, name_template.format(k))) for k in chunk]).to(device)
-        after = torch.stack([_load_image(os.path.join(after_dir, name_template.format(k))) for k in chunk]).to(device)
+        before, after = load(before_dir, chunk), load(after_dir, chunk)
         seg = torch.stack([torch.load(os.path.join(seg_dir, '%d.pth' % k), map_location='cpu')[srcc] for k in chunk]).to(device)
         values, counts = edit_distance(before, after, seg, src, mode, net)
         total += values.double().sum().item()

@@ -1189,6 +1189,152 @@ def png_encode(bytes_bhwc, timings=None, deferred=False):
     return framers if deferred else [make() for make in framers]
 
 
+def _png_stream_of(item, index, h, w, channels):
+    """The raw deflate stream of item: item itself, or, if it is a whole PNG file (no deflate stream starts with the PNG
+    signature), the stream pngreader.parse finds in it -- refused if the file is of another shape or form"""
+    view = memoryview(item).cast('B')
+    if bytes(view[:8]) != b'\x89PNG\r\n\x1a\n':
+        return view
+    from . import pngreader
+    try:
+        parsed = pngreader.parse(view)
+    except ValueError as e:
+        raise RuntimeError('rewriting_amd: png_decode: file %d: %s' % (index, e)) from None
+    if not isinstance(parsed, pngreader.Parsed) or (parsed.h, parsed.w, parsed.channels) != (h, w, channels):
+        raise RuntimeError('rewriting_amd: png_decode: file %d is %s, not the %d x %d x %d of this call'
+                           % (index, tuple(parsed)[:3] if isinstance(parsed, pngreader.Parsed) else parsed.form, h, w, channels))
+    return parsed.span
+
+
+def _png_spans(files_or_spans, device):
+    """(coded on the device or None, packed host buffer or None, spans (B, 2) int64, device) of png_decode's first argument,
+    with its refusals"""
+    import numpy
+    if isinstance(files_or_spans, tuple) and len(files_or_spans) == 2 and isinstance(files_or_spans[0], torch.Tensor):
+        coded = _in_place(files_or_spans[0], 'coded', torch.uint8)
+        if coded.dim() != 1:
+            raise RuntimeError('rewriting_amd: png_decode takes the coded bytes as a 1-D tensor, not %s' % (tuple(coded.shape),))
+        spans = numpy.asarray(files_or_spans[1])
+        if spans.size == 0:
+            spans = spans.reshape(0, 2)
+        if spans.ndim != 2 or spans.shape[1] != 2 or spans.dtype.kind not in 'iu':
+            raise RuntimeError('rewriting_amd: png_decode takes spans (B, 2) of integers: offset and length')
+        spans = spans.astype(numpy.int64)
+        if len(spans) and (spans.min() < 0 or int((spans[:, 0] + spans[:, 1]).max()) > coded.numel()):
+            raise RuntimeError('rewriting_amd: png_decode: a span passes the coded buffer of %d bytes' % coded.numel())
+        dev, packed = coded.device, None
+    else:
+        streams = [memoryview(s).cast('B') for s in files_or_spans]
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError('rewriting_amd: png_decode decodes on a GPU (there is no CPU fallback), not on %s' % dev)
+        offsets, at = [], 0
+        for s in streams:
+            offsets.append(at)
+            at += -(-len(s) // 16) * 16
+        spans = numpy.array([[o, len(s)] for o, s in zip(offsets, streams)], dtype=numpy.int64).reshape(-1, 2)
+        packed = numpy.zeros(max(at, 16), dtype=numpy.uint8)
+        for o, s in zip(offsets, streams):
+            packed[o:o + len(s)] = numpy.frombuffer(s, dtype=numpy.uint8)
+        coded = None
+    return coded, packed, spans, dev
+
+
+def _png_inflate(coded, packed, spans, dev, expect, mark=lambda name: None):
+    """The streams (B, stride) uint8 and status (B, 4) int32, both on the device, behind rw_png_inflate_u8"""
+    if coded is None:
+        coded = torch.from_numpy(packed).to(dev)
+    span_dev = torch.from_numpy(spans).to(dev)               # non-negative int64: the bits of the uint64 the entry reads
+    mark('copy')
+    b, stride = len(spans), -(-expect // 16) * 16
+    stream = torch.empty(b, stride, device=dev, dtype=torch.uint8)
+    status = torch.empty(b, 4, device=dev, dtype=torch.int32)
+    check(lib().rw_png_inflate_u8(_p(coded), _p(span_dev), _p(stream), stride, expect, _p(status), b, _stream()))
+    mark('inflate')
+    return stream, status
+
+
+def png_inflate(files_or_spans, expect, device='cuda'):
+    """(streams (B, stride) uint8 on the device, status (B, 4) int64 numpy): rw_png_inflate_u8 alone, for raw deflate
+    streams of which `expect` bytes each are expected (row i holds them in its first `expect` bytes; stride is expect
+    rounded up to 16).  The arguments and the status are png_decode's."""
+    import numpy
+    expect = int(expect)
+    if expect < 1 or expect >= 2 ** 31:
+        raise RuntimeError('rewriting_amd: png_inflate takes streams of 1 to 2^31 - 1 bytes (RW_ERR_UNSUPPORTED, '
+                           'include/rewriting_hip.h), not %d' % expect)
+    coded, packed, spans, dev = _png_spans(files_or_spans, device)
+    if len(spans) == 0:
+        return torch.empty(0, -(-expect // 16) * 16, device=dev, dtype=torch.uint8), numpy.zeros((0, 4), dtype=numpy.int64)
+    with torch.cuda.device(dev):
+        stream, status = _png_inflate(coded, packed, spans, dev, expect)
+        return stream, status.cpu().numpy().astype(numpy.int64) & 0xffffffff
+
+
+PNG_STATUS = ('ok', 'truncated input', 'bad block type', 'stored length mismatch', 'bad code-length set',
+              'bad literal/length set', 'bad distance set', 'missing end-of-block', 'invalid symbol',
+              'distance too far back', 'more output than expected', 'less output than expected', 'bad filter type')
+PNG_MAX_WIDTH = 16384        # rw_png_unfilter_u8 keeps one row of 4 W bytes in LDS
+
+
+def png_decode(files_or_spans, h, w, channels, device='cuda', timings=None):
+    """(bytes (B, h, w, 3) uint8 on the device, status (B, 4) int64 numpy) of B PNG images of one shape class -- h rows of
+    w pixels with `channels` in {1, 3, 4} bytes each, 8 bits a sample, not interlaced: rw_png_inflate_u8 (one wave per
+    raw deflate stream) and rw_png_unfilter_u8, the way back from png_encode.  Grey comes out in all three channels and
+    alpha is dropped, as PIL's convert('RGB') does.  files_or_spans is either
+
+    * a list of raw deflate streams (bytes-like: the IDAT payload without the two bytes of the zlib header and the four
+      of the Adler trailer) or of whole PNG files of this shape, in which pngreader.parse finds that stream (the file's
+      Adler trailer is then the caller's to compare with the status: pngreader.decode does); they are packed into one host
+      buffer, each at a 16-byte boundary, and go to the device in one copy; or
+    * a pair (coded, spans): coded a 1-D uint8 tensor that is already on the device, read in place, and spans (B, 2)
+      integers on the host: offset and length of every stream inside it.
+
+    status[i] = (code, bytes produced, s1, s2): code 0 is RW_PNG_OK, the others index PNG_STATUS
+    (include/rewriting_hip.h); pngcode.adler_fold([(produced, s1, s2)]) is the Adler-32 of what was produced.  The pixels
+    of an image whose code is not 0 are zeros.  An empty batch returns an empty tensor; nothing is launched for it.  A
+    wrong dtype or device, channels outside {1, 3, 4}, an extent below 1, a stream H (1 + channels W) of 2^31 bytes or
+    more and a span that passes the buffer are refused before anything is launched.  timings: a dict that receives
+    milliseconds of the stages (copy, inflate, unfilter) from HIP events -- it synchronises; for benchmarks."""
+    import numpy
+    h, w, channels = int(h), int(w), int(channels)
+    if channels not in (1, 3, 4):
+        raise RuntimeError('rewriting_amd: png_decode takes 1 (grey), 3 (RGB) or 4 (RGBA) channels of 8 bits '
+                           '(RW_ERR_UNSUPPORTED, include/rewriting_hip.h), not %d' % channels)
+    expect = h * (1 + channels * w)
+    if h < 1 or w < 1 or expect >= 2 ** 31 or w > PNG_MAX_WIDTH:
+        raise RuntimeError('rewriting_amd: png_decode takes images of at least 1 x 1, at most %d wide, whose filtered stream '
+                           'H (1 + channels W) is below 2^31 bytes (RW_ERR_UNSUPPORTED, include/rewriting_hip.h), not %d x %d'
+                           % (PNG_MAX_WIDTH, h, w))
+    if not isinstance(files_or_spans, tuple):
+        files_or_spans = [_png_stream_of(item, i, h, w, channels) for i, item in enumerate(files_or_spans)]
+    coded, packed, spans, dev = _png_spans(files_or_spans, device)
+    b = len(spans)
+    out = torch.empty(b, h, w, 3, device=dev, dtype=torch.uint8)
+    if b == 0:
+        return out, numpy.zeros((0, 4), dtype=numpy.int64)
+    marks = []
+
+    def mark(name):
+        if timings is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            marks.append((name, event))
+
+    with torch.cuda.device(dev):
+        mark('start')
+        stream, status = _png_inflate(coded, packed, spans, dev, expect, mark)
+        stride = stream.shape[1]
+        check(lib().rw_png_unfilter_u8(_p(stream), stride, _p(status), _p(out), b, h, w, channels, _stream()))
+        mark('unfilter')
+        host = status.cpu().numpy().astype(numpy.int64) & 0xffffffff
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            for (_, before), (name, after) in zip(marks, marks[1:]):
+                timings[name] = timings.get(name, 0.0) + before.elapsed_time(after)
+    return out, host
+
+
 # ------------------------------------------------------------------ solve
 def project_weight(w, context, base=None, out=None):
     """out = base + P(w), P = projected_conv (rewrite/ganrewrite.py:806-813).  w (..., O, I, kh, kw)."""
