@@ -462,16 +462,6 @@ __global__ void __launch_bounds__(256) conv_mfma_ksplit_kernel(const ConvBatch c
 // its use, which frees the LDS and the VALU for the matrix pipe.  (FRAG = false: the per-phase
 // variant of the transposed convolution, impl 4, reads wp[tap][i][o] with dword loads.)
 // ---------------------------------------------------------------------------------------
-// Timing ablations for kernel work (build with -DRW_ABLATION, select with RW_CONV_ABL=<bits>; results
-// are WRONG when a bit is set): 1 = no LDS operand reads in the loop, 2 = no weight refills,
-// 4 = no halo fetch / staging, 8 = no barrier, 16 = no epilogue stores.  Compiled out otherwise.
-#ifdef RW_ABLATION
-#define RW_ABL(p, bit) ((p).abl & (bit))
-static int rw_abl_env() { return rw_env_int("RW_CONV_ABL", 0); }
-#else
-#define RW_ABL(p, bit) false
-static int rw_abl_env() { return 0; }
-#endif
 
 // the tile counts of a halo launch as rw_tile_digits reads them: work item -> (out-channel tile, tx, ty, image)
 struct HaloTiles { int o_tiles, tiles_x, tiles_y; };
@@ -489,7 +479,7 @@ struct HaloProblem {
   const float* style; const float* demod; const float* noise; const float* noise_w; const float* bias;
   int batch, in_ch, out_ch, h, w, oh, ow, sy, sx;
   float w_scale;
-  int act, nphase, abl;
+  int act, nphase;
   // ToRGB fused into the epilogue (rw_conv3x3_to_rgb_f32; the workgroup holds ALL out-channels): nullable
   const float* rgb_weight; const float* rgb_style; const float* rgb_bias; const float* rgb_skip; float* rgb_out;
   float rgb_scale;
@@ -561,7 +551,6 @@ __device__ __forceinline__ void rw_halo_epilogue(const HaloProblem& p, const Pha
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
       if (!live[b]) continue;
-      if (RW_ABL(p, 16) && acc[0][b][0] != 12345.f) continue;
       float* yo = p.y ? p.y + ((int64_t)ib * p.out_ch + ob) * ohw + pix[b] : nullptr;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -735,7 +724,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HaloProblem p) 
   for (int c = 0; c < n_chunks; ++c) {
     const int buf = c & 1;
     const int cn = c + 1 < n_chunks ? c + 1 : c;      // last chunk: a redundant, unused refill
-    if (!RW_ABL(p, 4)) xfetch(cn * IC);    // consumed by the staging steps at the end of the chunk
+    xfetch(cn * IC);                       // consumed by the staging steps at the end of the chunk
     const float* xs = &Xs[buf][frow][wrow0 + lr + rw_tap_off(d.dy_bits, 0) + 1][lc + rw_tap_off(d.dx_bits, 0) + 1];
     float bf[TN], bnext[TN];
 #pragma unroll
@@ -747,27 +736,26 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HaloProblem p) 
       if (nt == d.ntaps) { nt = 0; nc = cn; }
       // first k-pair of the next tap (for the last tap: re-read after the barrier, this one is unused)
       const float* xs_next = &Xs[buf][frow][wrow0 + lr + rw_tap_off(d.dy_bits, nt) + 1][lc + rw_tap_off(d.dx_bits, nt) + 1];
-      if (FRAG && KH == 1 && !RW_ABL(p, 2)) fload(an, 0, nt, nc);
+      if (FRAG && KH == 1) fload(an, 0, nt, nc);
 #pragma unroll
       for (int kp = 0; kp < KP; ++kp) {
 #pragma unroll
         for (int b = 0; b < TN; ++b)       // B fragments one k-pair ahead of the MFMAs that use them
-          if (!RW_ABL(p, 1)) bnext[b] = kp + 1 < KP ? xs[(2 * kp + 2) * XH * XW + b * RPT * XW] : xs_next[b * RPT * XW];
+          bnext[b] = kp + 1 < KP ? xs[(2 * kp + 2) * XH * XW + b * RPT * XW] : xs_next[b * RPT * XW];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
           for (int b = 0; b < TN; ++b) {
             acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kp >> 2][a][kp & 3], bf[b], acc[a][b], 0, 0, 0);
-            if (STAGE >= 0 && (STAGE * KP + kp) * MPK + a * TN + b < NST && !RW_ABL(p, 4)) {
+            if (STAGE >= 0 && (STAGE * KP + kp) * MPK + a * TN + b < NST) {
               stash_step(buf ^ 1, (STAGE * KP + kp) * MPK + a * TN + b);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
         // these weight registers are free again: refill them for the next tap, >= 1k cycles of MFMA
         // ahead of their use
-        if (RW_ABL(p, 2)) {
-        } else if (!FRAG) aload1(kp, nt, nc * IC);
+        if (!FRAG) aload1(kp, nt, nc * IC);
         else if (KH > 1 && (kp & 3) == 3) fload(av[kp >> 2], kp >> 2, nt, nc);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -788,7 +776,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HaloProblem p) 
 #pragma unroll
       for (int j = 0; j < NST; ++j) stash_step(buf ^ 1, j);
     }
-    if (!RW_ABL(p, 8)) __syncthreads();
+    __syncthreads();
   }
 
   rw_halo_epilogue<TM, TN, RPT>(p, d, acc, ib, o0 + wm0 + 4 * frow, y0 + wrow0 + lr, x0 + lc);
@@ -811,7 +799,6 @@ struct UpProblem {
   int batch, in_ch, out_ch, h, w;
   int tiles_x, tiles_y;
   float w_scale;
-  int abl;
 };
 
 template <int WGM, int WGN, int IC, int TW>
@@ -915,12 +902,12 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
     for (int kp = 0; kp < KP; ++kp) {
       int nkp = kp + 3, nc = c;
       if (nkp >= KP) { nkp -= KP; nc = cn; }
-      if (!RW_ABL(p, 2)) aload(aring[(kp + 3) & 3], nkp, nc);
+      aload(aring[(kp + 3) & 3], nkp, nc);
       // after the weight load (its wait must not drain these), and UNCONDITIONAL -- the last chunk re-fetches
       // itself: with a branch around the fetch the compiler has to count vmcnt for the path without it, and
       // every weight wait of the chunk then drains the fetch on the path with it
-      if (kp == 0 && !RW_ABL(p, 4)) xfetch(cn * IC);
-      if (kp + 1 < KP && !RW_ABL(p, 1)) {
+      if (kp == 0) xfetch(cn * IC);
+      if (kp + 1 < KP) {
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
           const float* q = xs + (2 * kp + 2) * XH * XW + b * RPT * XW;
@@ -933,7 +920,7 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   _Pragma("unroll") for (int b = 0; b < TN; ++b) acc[q][b] =                                            \
       __builtin_amdgcn_mfma_f32_32x32x2f32((sl) < 8 ? aring[kp & 3].v4[((sl) >> 2) & 1][(sl) & 3] : aring[kp & 3].s8, bv[b],  \
                                            acc[q][b], 0, 0, 0);                                        \
-  if (9 * kp + (m) >= SLOT0 && 9 * kp + (m) - SLOT0 < NST && !RW_ABL(p, 4)) {                                          \
+  if (9 * kp + (m) >= SLOT0 && 9 * kp + (m) - SLOT0 < NST) {                                                           \
     stash_step(buf ^ 1, 9 * kp + (m) - SLOT0);                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                                  \
   }
@@ -972,7 +959,6 @@ __global__ void __launch_bounds__(256, 2) conv_up_halo_kernel(const UpProblem p)
   for (int b = 0; b < TN; ++b) {
     const int yy = y0 + wrow0 + b * RPT + lr;
     if (yy >= p.h) continue;                    // row 2H comes from the strip launch
-    if (RW_ABL(p, 16) && acc[0][b][0] != 12345.f) continue;
     // row r of the tile is channel o0 + wm0 + 4 frow + (r&3) + 8(r>>2): one 64-bit address per b, the
     // per-row plane offsets are scalar
     float* yb = p.y + ((int64_t)ib * p.out_ch + o0 + wm0 + 4 * frow) * ohw + (int64_t)(2 * yy) * ow + 2 * xx;
@@ -1167,7 +1153,6 @@ static int launch_up_halo(const ConvProblem* ps, const float* wp_all, int part, 
   UpProblem u;
   u.x = c.x; u.wfrag = wp_all + (int64_t)9 * c.in_ch * c.out_ch; u.y = c.y; u.style = c.style; u.demod = c.demod;
   u.batch = c.batch; u.in_ch = c.in_ch; u.out_ch = c.out_ch; u.h = c.h; u.w = c.w; u.w_scale = c.w_scale;
-  u.abl = rw_abl_env();
   const HaloTile t = halo_tile(c.w, c.out_ch, true);
   u.tiles_x = (int)rw_cdiv(c.w, t.tw); u.tiles_y = (int)rw_cdiv(c.h, t.th);
   const dim3 grid(c.batch * u.tiles_x * u.tiles_y * (c.out_ch / t.bm)), block(256);
@@ -1220,7 +1205,7 @@ static int64_t fill_halo(HaloProblem& h, const ConvProblem* ps, int n, const flo
   h.x = c.x; h.wp = ps[0].wp; h.wfrag = wfrag; h.y = c.y; h.style = c.style; h.demod = c.demod; h.noise = c.noise;
   h.noise_w = c.noise_w; h.bias = c.bias; h.batch = c.batch; h.in_ch = c.in_ch; h.out_ch = c.out_ch;
   h.h = c.h; h.w = c.w; h.oh = c.oh; h.ow = c.ow; h.sy = c.sy; h.sx = c.sx; h.w_scale = c.w_scale;
-  h.act = c.act; h.nphase = n; h.abl = rw_abl_env();
+  h.act = c.act; h.nphase = n;
   int64_t work = 0;
   for (int q = 0; q < 4; ++q) {
     PhaseDesc& d = h.phase[q];
@@ -1562,20 +1547,20 @@ __global__ void __launch_bounds__(256, 2) conv_halo_bf16x6_kernel(const HaloProb
   for (int c = 0; c < n_chunks; ++c) {
     const int buf = c & 1;
     const int cn = c + 1 < n_chunks ? c + 1 : c;
-    if (!RW_ABL(p, 4)) xfetch(cn * IC);
+    xfetch(cn * IC);
     // one tap; UNIT >= 0 also converts and stages unit UNIT of the next chunk between the MFMAs
     auto tap = [&](int t, auto unit_tag) {
       constexpr int UNIT = decltype(unit_tag)::value;
       int nt = t + 1, nc = c;
       if (nt == 9) { nt = 0; nc = cn; }
-      if (!RW_ABL(p, 2)) aload(anxt, nt, nc);
+      aload(anxt, nt, nc);
       const int dy = rw_tap_off(d.dy_bits, t), dx = rw_tap_off(d.dx_bits, t);
       uint4 bq[TN][3];
 #pragma unroll
       for (int b = 0; b < TN; ++b)
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3)
-          bq[b][s3] = RW_ABL(p, 1) ? acur[0][s3] : Xb[buf][s3][frow][wrow0 + b + dy + 1][fcol + dx + 1];
+          bq[b][s3] = Xb[buf][s3][frow][wrow0 + b + dy + 1][fcol + dx + 1];
       __builtin_amdgcn_sched_barrier(0);
 #define RW_BF(v) __builtin_bit_cast(rw_bf16x8, v)
       // six piece products (small terms first); consecutive MFMAs go to different accumulators
@@ -1589,7 +1574,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_bf16x6_kernel(const HaloProb
             acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(RW_BF(acur[a][PA[q]]), RW_BF(bq[b][PB[q]]),
                                                                 acc[a][b], 0, 0, 0);
 #undef RW_BF
-      if (UNIT >= 0 && !RW_ABL(p, 4)) stash_unit(buf ^ 1, UNIT);      // VALU + LDS writes in the shadow of the MFMAs above
+      if (UNIT >= 0) stash_unit(buf ^ 1, UNIT);                       // VALU + LDS writes in the shadow of the MFMAs above
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int a = 0; a < TM; ++a)

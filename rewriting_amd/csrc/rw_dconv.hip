@@ -51,21 +51,7 @@ struct DconvProblem {
   const float* x_amax; float* y_amax;               // bounds (RW_BOUND_LANES floats; y: + slots), rw_common.h
 };
 
-#ifndef DC_ABL
-#define DC_ABL 0          // timing ablations (results WRONG): 1 = no staging loads, 2 = no MFMAs, 4 = no weight loads, 8 = no epilogue,
-                          // 16 = the epilogue without its global stores (specialised kernels)
-#endif
 #define DC_PW 34          // columns of the staged window
-#ifndef DC_PROF
-#define DC_PROF 0         // 1: workgroups 0 and 100 of the specialised kernels leave cycle counts in dc_prof (rw_dconv_prof)
-#endif
-#if DC_PROF
-__device__ unsigned long long dc_prof[32];
-extern "C" int rw_dconv_prof(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dc_prof), sizeof(unsigned long long) * 32);
-}
-#define DC_T() ((unsigned long long)clock64())
-#endif
 
 // (rw_swz, rw_expand, rw_pair -- the f16-pair operand helpers -- and the LDS-direct loads: rw_common.h)
 // ---- THREE piece products per multiply where four were issued (round 5).  Vl Ul is <= 2^-22 of a product whose other
@@ -75,23 +61,15 @@ extern "C" int rw_dconv_prof(unsigned long long* out) {
 // product (two register moves build the pixel operand, the weight operand is two 8-byte loads side by side).  Tap ky = 2
 // has no partner in its column and keeps its fourth product ([Ul | Ul]): 5 MFMAs per kernel column and output block
 // where 6 were issued, 240 per 16-channel chunk instead of 288 -- the kernels are paced by MFMA issue (profiles/r04s).
-// DC_PRODUCTS=4 (compile time) keeps the old form for comparison.
-#ifndef DC_PRODUCTS
-#define DC_PRODUCTS 3
-#endif
 // ---- The taps (2, 0) and (2, 1) as partners of each other (round 9).  Tap ky = 2 has no partner in its COLUMN, but the
 // same output block meets tap (2, 0) and tap (2, 1) at the same window row: [Vh(column 0) | Vh(column 1)] x [Ul(2,0) | Ul(2,1)]
 // is both taps' third product.  Column 0's Ul pass then issues only its row pairs, column 1's reads the Vh half of column
 // 0's operand word again (8 bytes per lane) beside its own, column 2 keeps [Vh | Vl] x [Ul | Ul]: 14 MFMAs per three
 // columns and output block where 15 were issued, 224 per 16-channel chunk instead of 240.  The packed weights are the
 // same -- the pair is built from pieces the kernels load anyway (the one-role kernel keeps column 0's Ul(2,0) in registers
-// into column 1, the specialised one reads it again from the chunk's weights in LDS).  DC_TAP2_PAIR=0 keeps the 15-MFMA form.
+// into column 1, the specialised one reads it again from the chunk's weights in LDS).
 // Measured (profiles/r09*, same box, interleaved): dconv_ws_w2_rgbp_kernel 3.24 -> 3.04 ms per launch inside the forward,
 // dconv_w4_kernel 0.737 -> 0.711, the 1024 forward at batch 64 1564 -> 1592 img/s.
-#ifndef DC_TAP2_PAIR
-#define DC_TAP2_PAIR 1
-#endif
-#define DC_T2P (DC_PRODUCTS == 3 && DC_TAP2_PAIR)
 
 // sum over the 16 lanes of a DPP row (every lane ends with the sum)
 __device__ __forceinline__ float dc_row_sum(float v) {
@@ -179,7 +157,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
     for (int s = S0; s < S1; ++s)
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        raw[s - S0][k] = (DC_ABL & 1) ? 1.f : __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xsrc, xoff[s], s0 + k * hw4, 0));
+        raw[s - S0][k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xsrc, xoff[s], s0 + k * hw4, 0));
   };
   auto stage_store = [&](int c, int buf, auto half_tag) __attribute__((always_inline)) {
     constexpr int S0 = decltype(half_tag)::value ? SH : 0, S1 = decltype(half_tag)::value ? SI : SH;
@@ -210,26 +188,23 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
   const unsigned char* wbase = p.wp + (int64_t)vb0 * T * 1024 + lane * 8;
   rw_f16x8 W[3][2][2];
   rw_f32x2 Wc[3][2][2];
-  rw_f32x2 Wk[2] = {};                             // DC_T2P: Ul of tap (2, 0), kept for column 1
+  rw_f32x2 Wk[2] = {};                             // Ul of tap (2, 0), kept for column 1
   auto wload = [&](int ky, int t) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
-      for (int part = 0; part < 2; ++part) {
-        if (DC_ABL & 4) Wc[ky][ob][part] = rw_f32x2{1.f, 1.f};
-        else Wc[ky][ob][part] = *reinterpret_cast<const rw_f32x2*>(wbase + ((int64_t)ob * T + t) * 1024 + part * 512);
-      }
+      for (int part = 0; part < 2; ++part)
+        Wc[ky][ob][part] = *reinterpret_cast<const rw_f32x2*>(wbase + ((int64_t)ob * T + t) * 1024 + part * 512);
   };
-  // W[ky][ob][0] = [Uh | Uh] of tap ky; DC_PRODUCTS == 3: W[0][ob][1] = [Ul(ky 0) | Ul(ky 1)], W[2][ob][1] = [Ul | Ul] of
-  // tap 2 (W[1][ob][1] unused); == 4: W[ky][ob][1] = [Ul | Ul] of tap ky.  DC_T2P: W[2][ob][1] is unused in column 0 and
-  // [Ul(2,0) | Ul(2,1)] in column 1
+  // W[ky][ob][0] = [Uh | Uh] of tap ky; W[0][ob][1] = [Ul(ky 0) | Ul(ky 1)] (W[1][ob][1] unused); W[2][ob][1] is unused in
+  // column 0, [Ul(2,0) | Ul(2,1)] in column 1 and [Ul | Ul] of tap 2 in column 2
   auto wexpand = [&](int ky, int kx) __attribute__((always_inline)) {
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob) {
       W[ky][ob][0] = rw_expand(Wc[ky][ob][0]);
-      if (DC_T2P && ky == 2 && kx == 0) Wk[ob] = Wc[2][ob][1];
-      else if (DC_T2P && ky == 2 && kx == 1) W[2][ob][1] = rw_pair(Wk[ob], Wc[2][ob][1]);
-      else if (DC_PRODUCTS == 4 || ky == 2) W[ky][ob][1] = rw_expand(Wc[ky][ob][1]);
+      if (ky == 2 && kx == 0) Wk[ob] = Wc[2][ob][1];
+      else if (ky == 2 && kx == 1) W[2][ob][1] = rw_pair(Wk[ob], Wc[2][ob][1]);
+      else if (ky == 2) W[ky][ob][1] = rw_expand(Wc[ky][ob][1]);
       else if (ky == 1) W[0][ob][1] = rw_pair(Wc[0][ob][1], Wc[1][ob][1]);       // first used in row 1
     }
   };
@@ -265,7 +240,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
     const unsigned char* lb = Ls + buf * BUFB;
     if (!LAST) stage_load(c + 1, rw_int<0>());
     rw_f16x8 bcur = bread(lb, 0, 0);
-    rw_f16x8 bprev[2] = {bcur, bcur};               // the operand one row up, per half (DC_PRODUCTS == 3)
+    rw_f16x8 bprev[2] = {bcur, bcur};               // the operand one row up, per half
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
       const bool more = !LAST || kx < 2;            // is there a next column
@@ -277,29 +252,28 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
         rw_f16x8 bnext = bcur;
         if (idx + 1 < 12) bnext = bread(lb, kx, idx + 1);
         else if (kx < 2) bnext = bread(lb, kx + 1, 0);
-        rw_f32x2 bh0 = {};                          // DC_T2P, column 1: Vh of column 0's operand of this idx
-        if (DC_T2P && kx == 1 && r >= 2 && !(DC_ABL & 2)) bh0 = bread_h(lb, 0, idx);
+        rw_f32x2 bh0 = {};                          // column 1: Vh of column 0's operand of this idx
+        if (kx == 1 && r >= 2) bh0 = bread_h(lb, 0, idx);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
           const int pr = r - ky;
           if (pr < 0 || pr > 3) continue;
           const int pb = 2 * pr + half;
-          if (DC_ABL & 2) { asm volatile("" :: "v"(bcur), "v"(W[ky][0][0]), "v"(W[ky][0][1]), "v"(W[ky][1][0]), "v"(W[ky][1][1])); continue; }
           acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][0][0], acc[0][pb], 0, 0, 0);
           acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][1][0], acc[1][pb], 0, 0, 0);
-          if (DC_T2P && ky == 2 && kx < 2) continue;          // the Vh Ul of the taps (2, 0) and (2, 1): below, in column 1
-          if (DC_PRODUCTS == 4 || ky == 2) {
+          if (ky == 2 && kx < 2) continue;                    // the Vh Ul of the taps (2, 0) and (2, 1): below, in column 1
+          if (ky == 2) {
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][0][1], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bcur, W[ky][1][1], acc[1][pb], 0, 0, 0);
           }
         }
-        if (DC_T2P && kx == 1 && r >= 2 && !(DC_ABL & 2)) {
+        if (kx == 1 && r >= 2) {
           const int pb = 2 * (r - 2) + half;
           const rw_f16x8 hh = rw_pair(rw_expand(bh0), bcur);
           acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[2][0][1], acc[0][pb], 0, 0, 0);
           acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[2][1][1], acc[1][pb], 0, 0, 0);
         }
-        if (DC_PRODUCTS == 3 && r >= 1 && r <= 4 && !(DC_ABL & 2)) {      // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
+        if (r >= 1 && r <= 4) {                                           // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
           const int pb = 2 * (r - 1) + half;
           const rw_f16x8 hh = rw_pair(bprev[half], bcur);
           acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][0][1], acc[0][pb], 0, 0, 0);
@@ -334,7 +308,6 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 
   for (int c = 0; c + 1 < NC; ++c) chunk(c, rw_int<0>());
   chunk(NC - 1, rw_int<1>());
-  if (DC_ABL & 8) { if (acc[0][0][0] != 12345.f) return; }
 
   // ---- epilogue: lane (lk, lt) holds out-channel lt of block ob, pixels 4 lk .. 4 lk + 3 of pixel block pb
   float ymax = 0.f;
@@ -463,7 +436,7 @@ __device__ __forceinline__ void dconv_body(const DconvProblem& p) {
 // 302 M MFMAs x 20.5 / 1024 SIMDs = 3.6 ms + the tiles' epilogues = 4.2 ms, where the 2.5 PFLOP/s the pipe is priced at
 // (16 cycles, 2.4 GHz) would be 2.0.  That is the same 4.2 - 4.4 ms the split F(4x4,3x3) kernel takes with a quarter of
 // the multiplies; the direct sums stay an opt-in (closer to the fp32 sum: 4e-7 against 1.1e-6).
-// (Round 9: 224 MFMAs per chunk where these figures had 240 -- DC_TAP2_PAIR above; column 1's Ul pass reads its pixel operand
+// (Round 9: 224 MFMAs per chunk where these figures had 240 -- the taps (2, 0) and (2, 1) as partners, above; column 1's Ul pass reads its pixel operand
 // as two 8-byte halves, [Vh(column 1) | Vh(column 0)], and the epilogue derives its lane values per tile: carried through
 // the chunks they were what the allocator spilled -- 4 VGPRs and 20 B / lane of scratch in the rgbp kernel, none now.)
 // ---------------------------------------------------------------------------------------
@@ -611,15 +584,10 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
       for (int q = 0; q < QW; ++q)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (DC_ABL & 1) raw[q][s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
-          else raw[q][s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + (4 * q + k) * hw4, 0));
-        }
+        for (int k = 0; k < 4; ++k)
+          raw[q][s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + (4 * q + k) * hw4, 0));
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        if (DC_ABL & 4) wraw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
-        else wraw[s][k] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + (3 * s + k) * 1024 + lane * 16);
-      }
+      for (int k = 0; k < 3; ++k) wraw[s][k] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + (3 * s + k) * 1024 + lane * 16);
     };
     // what setup() requested beside the pixels -> registers / LDS (the first wait of an interval)
     auto tables = [&]() __attribute__((always_inline)) {
@@ -669,37 +637,15 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
     for (int s = 0; s < SI; ++s) { deliver_s(0, s); __builtin_amdgcn_sched_barrier(0); request_s(s); __builtin_amdgcn_sched_barrier(0); }
     rw_lds_barrier();
-#if DC_PROF
-    unsigned long long pt_del = 0, pt_req = 0, pt_bar = 0, pt_all = DC_T();
-#endif
     for (int n = 0; n < N; ++n) {
-#if DC_PROF
-      const unsigned long long ta = DC_T();
-#endif
       // chunk n + 1 (in flight) -> LDS piece by piece, chunk n + 2 requested behind it (past the run: harmless repeats)
       tables();
       __builtin_amdgcn_sched_barrier(0);
       setup();
-#if DC_PROF
-      const unsigned long long tb = DC_T();
-#endif
 #pragma unroll
       for (int s = 0; s < SI; ++s) { deliver_s((n + 1) & 1, s); __builtin_amdgcn_sched_barrier(0); request_s(s); __builtin_amdgcn_sched_barrier(0); }
-#if DC_PROF
-      const unsigned long long tc = DC_T();
-#endif
       rw_lds_barrier();
-#if DC_PROF
-      const unsigned long long td = DC_T();
-      pt_del += tb - ta; pt_req += tc - tb; pt_bar += td - tc;
-#endif
     }
-#if DC_PROF
-    if (wave == MW && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-      unsigned long long* o = dc_prof + (blockIdx.x == 0 ? 0 : 16);
-      o[8] = DC_T() - pt_all; o[9] = pt_del; o[10] = pt_req; o[11] = pt_bar; o[12] = N;
-    }
-#endif
     if (!RGB && p.y_amax) rw_bound_store_wave(p.y_amax, 0.f);       // a staging wave produced nothing: its slot says so
     return;
   }
@@ -716,12 +662,11 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   auto bread = [&](const unsigned char* lb, int kx, int idx) __attribute__((always_inline)) {
     return *reinterpret_cast<const rw_f16x8*>(lb + bbase[kx] + ((idx >> 1) * PW + 16 * (idx & 1)) * 64);
   };
-  // DC_T2P: column 1's Ul pass (half-step 3) needs no Vl at all -- its operand is [Vh(column 1) | Vh(column 0)], the first
+  // column 1's Ul pass (half-step 3) needs no Vl at all -- its operand is [Vh(column 1) | Vh(column 0)], the first
   // 8 bytes of the two columns' words side by side: the row pairs take its first half as before, tap 2's instruction all of it
-  constexpr bool T2P1 = DC_T2P && !(DC_ABL & 2);
   auto bread_hs = [&](const unsigned char* lb, int hs, int idx) __attribute__((always_inline)) {
     const unsigned off = ((idx >> 1) * PW + 16 * (idx & 1)) * 64;
-    if (T2P1 && hs == 3)
+    if (hs == 3)
       return rw_pair(*reinterpret_cast<const rw_f32x2*>(lb + bbase[1] + off), *reinterpret_cast<const rw_f32x2*>(lb + bbase[0] + off));
     return bread(lb, hs >> 1, idx);
   };
@@ -732,15 +677,14 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   // 288 loads per chunk and CU -- three quarters of everything the CU's memory path carried, and it was full (r04q).
   rw_f16x8 W[3][2];
   rw_f32x2 Wc[3][2];
-  rw_f32x2 Wk[2] = {};                             // DC_T2P: Ul of tap (2, 0), read again in column 1's Ul pass
+  rw_f32x2 Wk[2] = {};                             // Ul of tap (2, 0), read again in column 1's Ul pass
   auto wread = [&](const unsigned char* wb, int kx, int part) __attribute__((always_inline)) {
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int ob = 0; ob < 2; ++ob) {
-        if (DC_T2P && part == 1 && ky == 2 && kx == 0) continue;       // column 0's Ul pass: row pairs only
-        if (DC_ABL & 4) Wc[ky][ob] = rw_f32x2{1.f, 1.f};
-        else Wc[ky][ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 3 * ky + kx) * 1024 + part * 512 + lane * 8);
+        if (part == 1 && ky == 2 && kx == 0) continue;                 // column 0's Ul pass: row pairs only
+        Wc[ky][ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 3 * ky + kx) * 1024 + part * 512 + lane * 8);
       }
   };
   const float noise_wg = p.noise ? p.noise_w[0] * gain : 0.f;
@@ -759,13 +703,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
   decode(tile, ot, tx, ty, ib);
   rw_lds_barrier();                                 // chunk 0 is in LDS
 
-#if DC_PROF
-  unsigned long long pt_mm = 0, pt_bar = 0, pt_epi = 0, pt_all = DC_T();
-#endif
   for (int n = 0; n < N; ++n) {
-#if DC_PROF
-    const unsigned long long ta = DC_T();
-#endif
     const unsigned char* lb = Ls + (n & 1) * BUFB;
     const unsigned char* wb = Wl + (n & 1) * WBUF;
     if (PLAIN && c == NC - 1 && p.noise) {          // the tile's noise, requested a chunk of MFMAs before its epilogue
@@ -777,22 +715,22 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
     wread(wb, 0, 0);
     bq[0] = bread(lb, 0, 0);
     bq[1] = bread(lb, 0, 1);
-    rw_f16x8 bprev[2] = {bq[0], bq[1]};             // the operand one row up, per half (DC_PRODUCTS == 3, part 1)
+    rw_f16x8 bprev[2] = {bq[0], bq[1]};             // the operand one row up, per half (part 1)
 #pragma unroll
     for (int hs = 0; hs < 6; ++hs) {
       const int kx = hs >> 1, part = hs & 1;
-      // part 0: W[ky][ob] = [Uh | Uh] of tap ky.  Part 1, DC_PRODUCTS == 3: W[0][ob] = [Ul(ky 0) | Ul(ky 1)] (meets
-      // [Vh(row r - 1) | Vh(row r)]), W[2][ob] = [Ul | Ul] of tap 2; DC_PRODUCTS == 4: [Ul | Ul] of every tap
+      // part 0: W[ky][ob] = [Uh | Uh] of tap ky.  Part 1: W[0][ob] = [Ul(ky 0) | Ul(ky 1)] (meets
+      // [Vh(row r - 1) | Vh(row r)]), W[2][ob] = [Ul | Ul] of tap 2 (column 2)
 #pragma unroll
       for (int ob = 0; ob < 2; ++ob) {
-        if (DC_PRODUCTS == 4 || part == 0) {
+        if (part == 0) {
 #pragma unroll
           for (int ky = 0; ky < 3; ++ky) W[ky][ob] = rw_expand(Wc[ky][ob]);
         } else {
           W[0][ob] = rw_pair(Wc[0][ob], Wc[1][ob]);
-          // DC_T2P: nothing in column 0; column 1: [Ul(2,1) | Ul(2,0)] (meets [Vh(column 1) | Vh(column 0)])
-          if (DC_T2P && kx == 1) W[2][ob] = rw_pair(Wc[2][ob], Wk[ob]);
-          else if (!(DC_T2P && kx == 0)) W[2][ob] = rw_expand(Wc[2][ob]);
+          // nothing in column 0; column 1: [Ul(2,1) | Ul(2,0)] (meets [Vh(column 1) | Vh(column 0)])
+          if (kx == 1) W[2][ob] = rw_pair(Wc[2][ob], Wk[ob]);
+          else if (kx != 0) W[2][ob] = rw_expand(Wc[2][ob]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -806,26 +744,19 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         else if (hs < 5) bq[(idx + 2) % 3] = bread_hs(lb, hs + 1, idx + 2 - 12);
         // Ul of tap (2, 0) again, for the next half-step: in its last row a Uh pass uses tap 2 only -- the registers of the
         // other two taps' operands are free
-        if (T2P1 && hs == 2 && idx == 10) {
+        if (hs == 2 && idx == 10) {
 #pragma unroll
-          for (int ob = 0; ob < 2; ++ob) {
-            if (DC_ABL & 4) Wk[ob] = rw_f32x2{1.f, 1.f};
-            else Wk[ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 6) * 1024 + 512 + lane * 8);
-          }
+          for (int ob = 0; ob < 2; ++ob) Wk[ob] = *reinterpret_cast<const rw_f32x2*>(wb + ((2 * wm + ob) * 9 + 6) * 1024 + 512 + lane * 8);
         }
-        if (DC_PRODUCTS == 4 || part == 0) {
+        if (part == 0) {
 #pragma unroll
           for (int ky = 0; ky < 3; ++ky) {
             const int pr = r - ky;
             if (pr < 0 || pr > 3) continue;
             const int pb = 2 * pr + half;
-            if (DC_ABL & 2) { asm volatile("" :: "v"(b), "v"(W[ky][0]), "v"(W[ky][1])); continue; }
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[ky][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[ky][1], acc[1][pb], 0, 0, 0);
           }
-        } else if (DC_ABL & 2) {
-          if (DC_T2P && kx == 0) asm volatile("" :: "v"(b), "v"(W[0][0]), "v"(W[0][1]));
-          else asm volatile("" :: "v"(b), "v"(W[0][0]), "v"(W[0][1]), "v"(W[2][0]), "v"(W[2][1]));
         } else {
           if (r >= 1 && r <= 4) {                   // Vh Ul of the taps (0, kx) on row r - 1 and (1, kx) on row r
             const int pb = 2 * (r - 1) + half;
@@ -833,7 +764,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(hh, W[0][1], acc[1][pb], 0, 0, 0);
           }
-          if (r >= 2 && !(DC_T2P && kx == 0)) {     // tap (2, kx): all four products; DC_T2P, column 1: Vh Ul of (2, 1) and (2, 0)
+          if (r >= 2 && kx != 0) {                  // tap (2, kx): all four products; column 1: Vh Ul of (2, 1) and (2, 0)
             const int pb = 2 * (r - 2) + half;
             acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[2][0], acc[0][pb], 0, 0, 0);
             acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, W[2][1], acc[1][pb], 0, 0, 0);
@@ -843,21 +774,13 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#if DC_PROF
-    const unsigned long long tb = DC_T();
-#endif
     rw_lds_barrier();
-#if DC_PROF
-    const unsigned long long tc = DC_T();
-    pt_mm += tb - ta; pt_bar += tc - tb;
-    if (c + 1 == NC) pt_epi -= tc;
-#endif
     if (++c < NC) continue;
     // ---- epilogue of the tile: lane (lk, lt) holds out-channel lt of block ob, pixels 4 lk .. 4 lk + 3 of pixel block pb
     c = 0;
     const int par = (tile - t0) & 1;
     const int y0 = ty * TR, x0 = tx * TC;
-    if (!(DC_ABL & 8)) {
+    {
       // what the epilogue derives from the lane (channel, pixel offsets, plane addresses) is derived HERE, once per tile:
       // carried through the chunks' MFMAs these values were the registers the allocator spilled
       int lane_e = lane;
@@ -892,7 +815,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
               v[ob][j] = fmaxf(u, u * slope);
               ymax = fmaxf(ymax, fabsf(v[ob][j]));
             }
-            if (!(DC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
+            *reinterpret_cast<rw_f32x4*>(yb + (int64_t)(16 * ob) * hw + pix) = v[ob];
           }
           if (RGBP) {
             rw_f32x4 sum[3];
@@ -901,7 +824,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
               for (int cc = 0; cc < 3; ++cc) sum[cc][j] = dc_row_sum(v[0][j] * cr[0][cc] + v[1][j] * cr[1][cc]);
             // every lane of the row holds the sums: lane lt == cc stores colour cc
-            if (lt < 3 && !(DC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
+            if (lt < 3) *reinterpret_cast<rw_f32x4*>(rb + pix) = lt == 0 ? sum[0] : (lt == 1 ? sum[1] : sum[2]);
           }
         }
       } else if (UP) {
@@ -928,10 +851,8 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
             q0[k] = fmaxf(u0, u0 * slope) * post; q1[k] = fmaxf(u1, u1 * slope) * post;
             ymax = fmaxf(ymax, fmaxf(fabsf(q0[k]), fabsf(q1[k])));
           }
-          if (!(DC_ABL & 16)) {
-            *reinterpret_cast<rw_f32x4*>(yb + pix) = q0;
-            *reinterpret_cast<rw_f32x4*>(yb + pix + 4) = q1;
-          }
+          *reinterpret_cast<rw_f32x4*>(yb + pix) = q0;
+          *reinterpret_cast<rw_f32x4*>(yb + pix + 4) = q1;
         }
       } else {
         const float sc[2] = {Ct[par][0][lt], Ct[par][0][lt + 16]}, bs[2] = {Ct[par][1][lt], Ct[par][1][lt + 16]};
@@ -968,16 +889,7 @@ __device__ __forceinline__ void dconv_ws_body(const DconvProblem& p) {
 #pragma unroll
       for (int pb = 0; pb < 8; ++pb) acc[ob][pb] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
     if (++tile < t1) decode(tile, ot, tx, ty, ib);
-#if DC_PROF
-    pt_epi += DC_T();
-#endif
   }
-#if DC_PROF
-  if (wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-    unsigned long long* o = dc_prof + (blockIdx.x == 0 ? 0 : 16);
-    o[0] = DC_T() - pt_all; o[1] = pt_mm; o[2] = pt_bar; o[3] = pt_epi; o[4] = N;
-  }
-#endif
   if (!RGB && p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));       // this wave's slot
 }
 

@@ -16,9 +16,6 @@
 // matter are coalesced 16-byte accesses along W (NCHW => W is the fast axis), one pass over
 // each feature map, and >> 256 workgroups.  Nothing here is reshaped into a GEMM.
 #include "rw_common.h"
-#ifndef OPS_NTS
-#define OPS_NTS 0         // A/B builds: non-temporal stores of upfirdn2d_plane (1) / to_rgb (2)
-#endif
 #include <stdlib.h>
 #include <stdint.h>
 
@@ -297,11 +294,7 @@ __global__ void __launch_bounds__(256) upfirdn2d_plane_kernel(const T* __restric
     T* yo = ym + (int64_t)oy * p.out_w + ox;
     if (vec) {
       const vec4_t o = {(T)acc[0], (T)acc[1], (T)acc[2], (T)acc[3]};
-#if OPS_NTS & 1
-      __builtin_nontemporal_store(o, reinterpret_cast<vec4_t*>(yo));
-#else
       *reinterpret_cast<vec4_t*>(yo) = o;
-#endif
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) if (ox + e < p.out_w) yo[e] = (T)acc[e];
@@ -848,15 +841,11 @@ extern "C" int rw_pack_conv_weight_f32(const float* w, float* wp, int out_ch, in
 // Workgroup = 64 x 64 output tile of one (image, channel) plane: the 67 x 67 input patch is
 // staged in LDS with coalesced row loads (the odd row length 2W+1 rules out vector loads), each
 // thread then produces 4 horizontally adjacent outputs of four rows, one 16-byte store each.
-#ifndef BL_TH
 #define BL_TH 64        // 16 / 32 / 64 / 96 / 128 rows measured: 3.1 / 3.5 / 3.9 / 3.6 / 3.3 TB/s at 32 x 1024^2 x 64
-#endif
 #define BL_TW 64
 #define BL_PITCH (BL_TW + 4)
-#ifndef BL_NT
-#define BL_NT 2           // bit 0: non-temporal loads of the (2H+1)^2 map (measured -8 %: its halo rows ARE re-read),
-                          // bit 1: non-temporal stores of the result (+9 % on the kernel: 3.77 -> 4.15 TB/s at 64 x 512^2 x 64)
-#endif
+// The (2H+1)^2 map is read with ordinary loads (non-temporal ones measured -8 %: its halo rows ARE re-read), the result
+// leaves with non-temporal stores (+9 % on the kernel: 3.77 -> 4.15 TB/s at 64 x 512^2 x 64).
 __global__ void __launch_bounds__(256) blur_noise_act_kernel(
     const float* __restrict__ x, const float* __restrict__ k4, const float* __restrict__ noise,
     const float* __restrict__ nw_ptr, const float* __restrict__ bias, float* __restrict__ y,
@@ -894,11 +883,7 @@ __global__ void __launch_bounds__(256) blur_noise_act_kernel(
       const bool rok = rr < RPP && r < BL_TH + 3 && iy >= 0 && iy < in_h;
       const float* src = xp + (int64_t)iy * in_w + ix;
       if (rok && ix >= 0 && ix + 3 < in_w) {
-#if BL_NT & 1
-        v[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_u*>(src));
-#else
         v[q] = *reinterpret_cast<const f32x4_u*>(src);
-#endif
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[q][e] = (rok && ix + e >= 0 && ix + e < in_w) ? src[e] : 0.f;
@@ -959,11 +944,7 @@ __global__ void __launch_bounds__(256) blur_noise_act_kernel(
     }
     float* yo = y + (bc * out_h + oy) * (int64_t)out_w + ox;
     if (full) {
-#if BL_NT & 2
       __builtin_nontemporal_store(rw_f32x4{res[0], res[1], res[2], res[3]}, reinterpret_cast<rw_f32x4*>(yo));
-#else
-      *reinterpret_cast<float4*>(yo) = make_float4(res[0], res[1], res[2], res[3]);
-#endif
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) if (ox + q < out_w) yo[q] = res[q];
@@ -1148,11 +1129,7 @@ __global__ void __launch_bounds__(256) to_rgb_kernel(const float* __restrict__ x
         const float4 s = reinterpret_cast<const float4*>(skip)[off];
         o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
       }
-#if OPS_NTS & 2
-      __builtin_nontemporal_store(rw_f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<rw_f32x4*>(y) + off);
-#else
       reinterpret_cast<float4*>(y)[off] = o;
-#endif
     }
   }
 }

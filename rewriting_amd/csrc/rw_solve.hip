@@ -32,10 +32,8 @@
 #define SV_KC 16
 #define SV_BM 64        // out channels per workgroup (both GEMMs)
 #define SV_BN 64        // pixels per workgroup in K1
-#ifndef SV_BNK
-#define SV_BNK 64       // weight columns per workgroup in K3 (64 or 128: one or two 32-column tiles per wave)
-#endif
-#define SV_NB (SV_BNK / 64)
+#define SV_BNK 64       // weight columns per workgroup in K3
+#define SV_NB (SV_BNK / 64)               // 32-column tiles per wave in K3: one
 #define SV_BJ (SV_KC * SV_BNK / 256)      // B elements a thread stages per chunk
 #define SV_DEPTH 4      // chunks of operands in flight per workgroup (K1, K3)
 

@@ -29,7 +29,7 @@
 // of 1.33).  Wave v owns the position blocks v, v + WAVES, ... x 4 phases (96 / 80 accumulator registers).  Per chunk: the
 // chunk's 9 KB of weights and the next window are requested a chunk ahead (weights through LDS), the window converted and
 // written behind the first / last blocks' MFMAs, one barrier per chunk.
-// THREE piece products (rw_dconv.hip, DC_PRODUCTS): the taps of a phase share the Vh Ul instruction in pairs --
+// THREE piece products (rw_dconv.hip): the taps of a phase share the Vh Ul instruction in pairs --
 // [Vh(P00) | Vh(P01)] x [Ul(t0) | Ul(t2)] and so on -- 14 MFMAs per block and chunk instead of 18, issued in three tap
 // groups (the taps on x[i][j] alone, those that also need x[i][j-1], those on the row above: six operand reads per block
 // where four would do, at most five weight operands live).
@@ -59,46 +59,12 @@ struct TconvProblem {
 #define TC_ZP 72                          // z row pitch (floats): columns 3 .. 70 are written, 4 .. 70 read
 #define TC_WCH 9216                       // bytes of a chunk's weights of one 16-channel block: 9 taps x [Uh | Ul] x 512
 
-#ifndef TC_LDS_PAD
-#define TC_LDS_PAD 0
-#endif
-#ifndef TC_ITEM_G
-#define TC_ITEM_G 1       // tconv_body: lane -> item order within a piece (1: consecutive; 4: see there)
-#endif
-#ifndef TC_AHEAD
-#define TC_AHEAD 1        // tconv_body: how many position blocks ahead the pixel operands are requested (1 or 2)
-#endif
-#ifndef TC_STAGE_PRIO
-#define TC_STAGE_PRIO 0   // persistent forms: s_setprio of the staging waves (0: none)
-#endif
-#ifndef TC_ABL
-#define TC_ABL 0          // timing ablations (results WRONG): 1 = no staging loads, 2 = no MFMAs, 8 = no epilogue,
-                          // 16 = the epilogue without its global stores, 32 = without its noise loads, 64 = without the blur
-                          // arithmetic (z written, one row read per output row), 128 = three position blocks per wave only
-#endif
-
 // [h0 h1 h2 h3 q0 q1 q2 q3]: a Vh half-word and the Vh part of a pixel word
 __device__ __forceinline__ rw_f16x8 tc_pair_hq(rw_f32x2 h, rw_f16x8 q) {
   const rw_f32x4 qq = __builtin_bit_cast(rw_f32x4, q);
   const rw_f32x4 d = {h[0], h[1], qq[0], qq[1]};
   return __builtin_bit_cast(rw_f16x8, d);
 }
-#ifndef TC_PROF
-#define TC_PROF 0         // 1: workgroups 0 and 100 leave cycle counts of wave 0 (multiplying) and wave 4 (staging) in tc_prof
-#endif
-#if TC_PROF
-__device__ unsigned long long tc_prof[64];
-extern "C" int rw_tconv_prof(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(tc_prof), sizeof(unsigned long long) * 64);
-}
-#define TP_DECL(...) unsigned long long __VA_ARGS__
-#define TP_NOW(t) t = (unsigned long long)clock64()
-#define TP_ADD(var, t) { const unsigned long long tp_n = (unsigned long long)clock64(); var += tp_n - t; t = tp_n; }
-#else
-#define TP_DECL(...)
-#define TP_NOW(t)
-#define TP_ADD(var, t)
-#endif
 // a * b as ONE v_mul_f32: left to the vectoriser, products of values that sit in different 16-byte load results become
 // v_pk_mul_f32 on register pairs assembled with two v_mov_b32 each
 __device__ __forceinline__ float tc_mul(float a, float b) {
@@ -129,13 +95,6 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   __shared__ __attribute__((aligned(16))) unsigned char Wl[2 * WCH];
   __shared__ __attribute__((aligned(16))) float St[512];
   __shared__ float Sc[OC], Bs[OC], Po[OC], Kf[16], Red[WAVES];
-#if TC_LDS_PAD
-  // (experiment / workaround, TY == 16 only: claim the rest of the CU's 160 KB of LDS so that no workgroup that uses LDS --
-  // to_rgb_kernel -- can share the CU: profiles/r05i)
-  constexpr int PADB = TY == 16 ? 163840 - 2 * BUFB - 2 * WCH - 2048 - 4 * 64 - 4 * WAVES - 64 : 16;
-  __shared__ unsigned char Pad[PADB];
-  if (p.batch < 0) Pad[threadIdx.x] = 1;           // never true: keeps the array allocated
-#endif
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -189,10 +148,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   int xoff[SI], lofa[SI], lofb[SI], lok[SI];        // LDS byte offsets of the item's pixels 0 / 2 (1 / 3: + 64); bit e of lok: pixel e is a window pixel
 #pragma unroll
   for (int s = 0; s < SI; ++s) {
-    // (TC_ITEM_G == 4: lane l takes item (l & 3) LPP / 4 + (l >> 2) of the piece -- the eight lanes of a ds_write_b128 group then
-    // write to two rows and both item parities: the four 16-byte slots the operand swizzle can give pixels 4 columns apart)
-    const int li = TC_ITEM_G == 4 ? (lane & 3) * (LPP / 4) + (lane >> 2) : lane;
-    const int it = LPP * (NSL * s + hsel) + li;
+    const int it = LPP * (NSL * s + hsel) + lane;
     const bool mine = lane < LPP && it < NITEM;
     const int r = it / IPR, j = it - r * IPR;
     const int iy = I0 - 2 + r, ix = J0 - 4 + 4 * j;                // the item lies inside the row or outside it as a whole
@@ -212,10 +168,8 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     constexpr int s = decltype(s_tag)::value, K0 = decltype(k0_tag)::value, K1 = decltype(k1_tag)::value;
     const int s0 = (16 * c + 4 * g) * hw4;
 #pragma unroll
-    for (int k = K0; k < K1; ++k) {
-      if (TC_ABL & 1) raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};
-      else raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], s0 + k * hw4, 0));
-    }
+    for (int k = K0; k < K1; ++k)
+      raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], s0 + k * hw4, 0));
   };
   // pixels E0 .. E1 - 1 of piece s converted (style, exact f16 pair split) and written
   auto stage_store_part = [&](int c, int buf, auto s_tag, auto e0_tag, auto e1_tag) __attribute__((always_inline)) {
@@ -227,10 +181,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
       const float v0 = tc_mul(raw[s][0][e], sv[0]), v1 = tc_mul(raw[s][1][e], sv[1]), v2 = tc_mul(raw[s][2][e], sv[2]),
                   v3 = tc_mul(raw[s][3][e], sv[3]);
       rw_f16x8 word = rw_split4(v0, v1, v2, v3);
-      if (TC_ABL & 256)                            // (timing ablation: no conversion arithmetic; results wrong)
-        word = __builtin_bit_cast(rw_f16x8, rw_f32x4{raw[s][0][e], raw[s][1][e], raw[s][2][e], raw[s][3][e]});
-      if (TC_ABL & 512) { asm volatile("" :: "v"(word)); }            // (timing ablation: no LDS store of the window)
-      else if (lok[s] & (1 << e)) *reinterpret_cast<rw_f16x8*>(dst + (e < 2 ? lofa[s] : lofb[s]) + (e & 1) * 64) = word;
+      if (lok[s] & (1 << e)) *reinterpret_cast<rw_f16x8*>(dst + (e < 2 ? lofa[s] : lofb[s]) + (e & 1) * 64) = word;
     }
   };
   // the chunk's weights of this workgroup's NT out-channel blocks: NT x 9216 contiguous bytes of the packed array -> LDS
@@ -347,13 +298,11 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
 #define TC_MFMA(PH, A, B) acc[b][PH] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[b][PH], 0, 0, 0)
 #define TC_UH(T_) rw_expand(*reinterpret_cast<const rw_f32x2*>(wb + (T_) * 1024))
 #define TC_UL(T_) (*reinterpret_cast<const rw_f32x2*>(wb + (T_) * 1024 + 512))
-  TP_DECL(tp = 0, tp_all = 0, tp_g0 = 0, tp_s0 = 0, tp_g1 = 0, tp_g2 = 0, tp_s1 = 0, tp_bar = 0, tp_pro = 0);
   auto chunk = [&](int c, auto last_tag) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(last_tag)::value != 0;
     const int buf = c & 1;
     const unsigned char* lb = Ls;                   // (pb0 / pb1 carry the buffer's offset)
     const unsigned char* wb = Wl + buf * WCH + lane * 8;
-    TP_NOW(tp);
     // The software pipeline: what is requested during chunk c (piece 0 behind the first tap group's blocks, piece 1 behind the
     // second group's, the weights behind the third's) belongs to chunk c + 2 and is converted / written during chunk c + 1
     // (behind the first blocks of the same groups, just before the registers are requested again): every load has a whole
@@ -365,9 +314,6 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     const int c2 = c + 2 < NC ? c + 2 : NC - 1;
     auto hook = [&](auto grp_tag, int b) __attribute__((always_inline)) {
       constexpr int grp = decltype(grp_tag)::value;
-#if TC_PROF
-      if (b < 4) { if (grp == 0) { TP_ADD(tp_g0, tp); } else if (grp == 1) { TP_ADD(tp_g1, tp); } else { TP_ADD(tp_g2, tp); } }
-#endif
       if constexpr (STAGED) {
         if (st) copy_request(c + 1, buf ^ 1, grp * BPW + b);        // chunk c + 1, one request behind each block
       } else if constexpr (grp < SI) {
@@ -383,9 +329,6 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         if (b == 0 && st) wstage_store(buf ^ 1);
         if (b == 1) wstage_load(c2);
       }
-#if TC_PROF
-      if (b < 2) { TP_ADD(tp_s0, tp); } else if (b < 4) { TP_ADD(tp_s1, tp); }
-#endif
     };
     // (operands one block ahead, the order pinned: left to itself the scheduler hoists every block's LDS reads to the top
     // of a group and spills; only the last block of a wave can be missing: NBLK > WAVES (BPW - 1))
@@ -395,59 +338,48 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
       rw_f16x8 u0[NT], u1[NT], u3[NT], u4[NT], l4[NT];
 #pragma unroll
       for (int n = 0; n < NT; ++n) { u0[n] = TB_UH(0); u1[n] = TB_UH(1); u3[n] = TB_UH(3); u4[n] = TB_UH(4); l4[n] = rw_expand(TB_UL(4)); }
-      // (TC_AHEAD blocks ahead: 1 = round 5; 2 = the pixel operands of block b + 2 requested before block b's MFMAs)
-      rw_f16x8 pc = TC_PIX(pb0[0] + TC_WC * 64), pd = pc;
-      if (TC_AHEAD == 2 && BPW > 1) pd = TC_PIX(pb0[1] + TC_WC * 64);
+      rw_f16x8 pc = TC_PIX(pb0[0] + TC_WC * 64);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        rw_f16x8 pn = TC_AHEAD == 2 ? pd : pc;
-        if (b + TC_AHEAD < BPW) pn = TC_PIX(pb0[b + TC_AHEAD] + TC_WC * 64);
+        rw_f16x8 pn = pc;
+        if (b + 1 < BPW) pn = TC_PIX(pb0[b + 1] + TC_WC * 64);
         if (b < LB || last_ok) {
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
-            if (TC_ABL & 2) { asm volatile("" :: "v"(pc), "v"(u0[n]), "v"(u1[n]), "v"(u3[n]), "v"(u4[n]), "v"(l4[n])); }
-            else {
-              TB_MFMA(3, pc, u4[n]); TB_MFMA(0, pc, u0[n]); TB_MFMA(1, pc, u1[n]); TB_MFMA(2, pc, u3[n]);
-              TB_MFMA(3, pc, l4[n]);                // (never two dependent MFMAs back to back)
-            }
+            TB_MFMA(3, pc, u4[n]); TB_MFMA(0, pc, u0[n]); TB_MFMA(1, pc, u1[n]); TB_MFMA(2, pc, u3[n]);
+            TB_MFMA(3, pc, l4[n]);                  // (never two dependent MFMAs back to back)
           }
         }
         hook(rw_int<0>(), b);
         __builtin_amdgcn_sched_barrier(0);
-        if (TC_AHEAD == 2) { pc = pd; pd = pn; } else pc = pn;
+        pc = pn;
       }
     }
-    TP_ADD(tp_g0, tp);
     __builtin_amdgcn_sched_barrier(0);
     {
       rw_f16x8 u2[NT], u5[NT], m02[NT], m35[NT];
 #pragma unroll
       for (int n = 0; n < NT; ++n) { u2[n] = TB_UH(2); u5[n] = TB_UH(5); m02[n] = rw_pair(TB_UL(0), TB_UL(2)); m35[n] = rw_pair(TB_UL(3), TB_UL(5)); }
-      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;    // Vh of x[i][j]: the first half of its word
-      rw_f16x8 qc = TC_PIX(pb1[0] + TC_WC * 64), qd = qc;
-      if (TC_AHEAD == 2 && BPW > 1) { hd = TC_VH(pb0[1] + TC_WC * 64); qd = TC_PIX(pb1[1] + TC_WC * 64); }
+      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64);             // Vh of x[i][j]: the first half of its word
+      rw_f16x8 qc = TC_PIX(pb1[0] + TC_WC * 64);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        rw_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
-        rw_f16x8 qn = TC_AHEAD == 2 ? qd : qc;
-        if (b + TC_AHEAD < BPW) { hn = TC_VH(pb0[b + TC_AHEAD] + TC_WC * 64); qn = TC_PIX(pb1[b + TC_AHEAD] + TC_WC * 64); }
+        rw_f32x2 hn = hc;
+        rw_f16x8 qn = qc;
+        if (b + 1 < BPW) { hn = TC_VH(pb0[b + 1] + TC_WC * 64); qn = TC_PIX(pb1[b + 1] + TC_WC * 64); }
         if (b < LB || last_ok) {
           const rw_f16x8 M = tc_pair_hq(hc, qc);
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
-            if (TC_ABL & 2) { asm volatile("" :: "v"(hc), "v"(qc), "v"(u2[n]), "v"(u5[n]), "v"(m02[n]), "v"(m35[n])); }
-            else {
-              TB_MFMA(0, qc, u2[n]); TB_MFMA(2, qc, u5[n]);                       // taps (0, 2), (1, 2)
-              TB_MFMA(0, M, m02[n]); TB_MFMA(2, M, m35[n]);                       // Vh Ul of (0, 0) + (0, 2); (1, 0) + (1, 2)
-            }
+            TB_MFMA(0, qc, u2[n]); TB_MFMA(2, qc, u5[n]);                         // taps (0, 2), (1, 2)
+            TB_MFMA(0, M, m02[n]); TB_MFMA(2, M, m35[n]);                         // Vh Ul of (0, 0) + (0, 2); (1, 0) + (1, 2)
           }
         }
         hook(rw_int<1>(), b);
         __builtin_amdgcn_sched_barrier(0);
-        if (TC_AHEAD == 2) { hc = hd; qc = qd; hd = hn; qd = qn; } else { hc = hn; qc = qn; }
+        hc = hn; qc = qn;
       }
     }
-    TP_ADD(tp_g1, tp);
     {
       rw_f16x8 u6[NT], u7[NT], u8[NT], m17[NT], m68[NT];
 #pragma unroll
@@ -455,32 +387,27 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         u6[n] = TB_UH(6); u7[n] = TB_UH(7); u8[n] = TB_UH(8);
         m17[n] = rw_pair(TB_UL(1), TB_UL(7)); m68[n] = rw_pair(TB_UL(6), TB_UL(8));
       }
-      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64), hd = hc;
-      rw_f16x8 qc = TC_PIX(pb0[0]), rc = TC_PIX(pb1[0]), qd = qc, rd = rc;
-      if (TC_AHEAD == 2 && BPW > 1) { hd = TC_VH(pb0[1] + TC_WC * 64); qd = TC_PIX(pb0[1]); rd = TC_PIX(pb1[1]); }
+      rw_f32x2 hc = TC_VH(pb0[0] + TC_WC * 64);
+      rw_f16x8 qc = TC_PIX(pb0[0]), rc = TC_PIX(pb1[0]);
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        rw_f32x2 hn = TC_AHEAD == 2 ? hd : hc;
-        rw_f16x8 qn = TC_AHEAD == 2 ? qd : qc, rn = TC_AHEAD == 2 ? rd : rc;
-        if (b + TC_AHEAD < BPW) { hn = TC_VH(pb0[b + TC_AHEAD] + TC_WC * 64); qn = TC_PIX(pb0[b + TC_AHEAD]); rn = TC_PIX(pb1[b + TC_AHEAD]); }
+        rw_f32x2 hn = hc;
+        rw_f16x8 qn = qc, rn = rc;
+        if (b + 1 < BPW) { hn = TC_VH(pb0[b + 1] + TC_WC * 64); qn = TC_PIX(pb0[b + 1]); rn = TC_PIX(pb1[b + 1]); }
         if (b < LB || last_ok) {
           const rw_f16x8 M02 = tc_pair_hq(hc, qc), M23 = rw_pair(qc, rc);
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
-            if (TC_ABL & 2) { asm volatile("" :: "v"(hc), "v"(qc), "v"(rc), "v"(u6[n]), "v"(u7[n]), "v"(u8[n]), "v"(m17[n]), "v"(m68[n])); }
-            else {
-              TB_MFMA(0, qc, u6[n]); TB_MFMA(1, qc, u7[n]);                       // taps (2, 0), (2, 1)
-              TB_MFMA(0, rc, u8[n]); TB_MFMA(1, M02, m17[n]);                     // tap (2, 2); Vh Ul of (0, 1) + (2, 1)
-              TB_MFMA(0, M23, m68[n]);                                            // Vh Ul of (2, 0) + (2, 2)
-            }
+            TB_MFMA(0, qc, u6[n]); TB_MFMA(1, qc, u7[n]);                         // taps (2, 0), (2, 1)
+            TB_MFMA(0, rc, u8[n]); TB_MFMA(1, M02, m17[n]);                       // tap (2, 2); Vh Ul of (0, 1) + (2, 1)
+            TB_MFMA(0, M23, m68[n]);                                              // Vh Ul of (2, 0) + (2, 2)
           }
         }
         hook(rw_int<2>(), b);
         __builtin_amdgcn_sched_barrier(0);
-        if (TC_AHEAD == 2) { hc = hd; qc = qd; rc = rd; hd = hn; qd = qn; rd = rn; } else { hc = hn; qc = qn; rc = rn; }
+        hc = hn; qc = qn; rc = rn;
       }
     }
-    TP_ADD(tp_g2, tp);
     if (!LAST) {
       const unsigned delta = buf ? (unsigned)-BUFB : (unsigned)BUFB;
 #pragma unroll
@@ -492,13 +419,11 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
-      TP_ADD(tp_bar, tp);
     }
   };
 
   // ---- prologue: chunk 0 requested, converted, written; chunk 1 (in_ch == 16: chunk 0 again, never converted) requested, in
   // the order of a chunk's requests, pinned -- the waits of the loop count the requests behind the one they need
-  TP_NOW(tp_all);
   if constexpr (STAGED) {                           // chunk 0 copied; chunk 1 is requested inside chunk 0
 #pragma unroll
     for (int q = 0; q < NWS + PPW; ++q) copy_request(0, 0, q);
@@ -526,15 +451,8 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
   }
   }
 
-#if TC_PROF
-  TP_NOW(tp); tp_pro = tp - tp_all;
-#endif
   for (int c = 0; c + 1 < NC; ++c) chunk(c, rw_int<0>());
   chunk(NC - 1, rw_int<1>());
-#if TC_PROF
-  const unsigned long long tp_loop_end = (unsigned long long)clock64();
-#endif
-  if (TC_ABL & 8) { if (acc[0][0][0][0] != 12345.f) return; }
   __syncthreads();                                  // every wave has read its last operands: the windows become the z tile
 
   // ---- epilogue, eight channels at a time
@@ -564,7 +482,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
 #pragma unroll
   for (int oy = 0; oy < SR; ++oy) {
     nzr[oy] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
-    if (sep && p.noise && !(TC_ABL & 32))
+    if (sep && p.noise)
       nzr[oy] = *reinterpret_cast<const rw_f32x4*>(p.noise + (int64_t)ib * hw2 + s_pix + (int64_t)oy * W2);
   }
 #pragma unroll
@@ -607,20 +525,16 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
           hin = *reinterpret_cast<const rw_f32x4*>(zb + (zr + 1) * TC_ZP + 4);
         }
         rw_f32x4 hsum = lo * kf[0];
-        if (!(TC_ABL & 64)) {
-          hsum += rw_f32x4{lo[1], lo[2], lo[3], hi[0]} * kf[1];
-          hsum += rw_f32x4{lo[2], lo[3], hi[0], hi[1]} * kf[2];
-          hsum += rw_f32x4{lo[3], hi[0], hi[1], hi[2]} * kf[3];
-        }
+        hsum += rw_f32x4{lo[1], lo[2], lo[3], hi[0]} * kf[1];
+        hsum += rw_f32x4{lo[2], lo[3], hi[0], hi[1]} * kf[2];
+        hsum += rw_f32x4{lo[3], hi[0], hi[1], hi[2]} * kf[3];
         hrow[zr & 3] = hsum;
         if (zr >= 3) {
           const int oy = zr - 3;                    // output row oy0 + oy: filtered rows zr - 3 .. zr
           rw_f32x4 res = hrow[(zr - 3) & 3] * kv[0];
-          if (!(TC_ABL & 64)) {
-            res += hrow[(zr - 2) & 3] * kv[1];
-            res += hrow[(zr - 1) & 3] * kv[2];
-            res += hrow[zr & 3] * kv[3];
-          }
+          res += hrow[(zr - 2) & 3] * kv[1];
+          res += hrow[(zr - 1) & 3] * kv[2];
+          res += hrow[zr & 3] * kv[3];
           const rw_f32x4 nz = nzr[oy] * noise_wg;
           rw_f32x4 v;
 #pragma unroll
@@ -629,7 +543,7 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
             v[q] = fmaxf(u, u * slope) * post;
             ymax = fmaxf(ymax, fabsf(v[q]));
           }
-          if (!(TC_ABL & 16)) *reinterpret_cast<rw_f32x4*>(yb + (int64_t)oy * W2) = v;
+          *reinterpret_cast<rw_f32x4*>(yb + (int64_t)oy * W2) = v;
         }
         __builtin_amdgcn_sched_barrier(0);
         lo = lon; hi = hin;
@@ -669,14 +583,6 @@ __device__ __forceinline__ void tconv_body(const TconvProblem& p) {
     __syncthreads();
   }
   }
-#if TC_PROF
-  if (lane == 0 && (wave == 0 || wave == 7) && (blockIdx.x == gridDim.x / 2 || blockIdx.x == gridDim.x / 2 + 777)) {
-    unsigned long long* o = tc_prof + (blockIdx.x == gridDim.x / 2 ? 0 : 32) + (wave == 0 ? 0 : 16);
-    const unsigned long long now = (unsigned long long)clock64();
-    o[0] = now - tp_all; o[1] = tp_pro; o[2] = tp_g0; o[3] = tp_s0; o[4] = tp_g1; o[5] = tp_g2; o[6] = tp_s1; o[7] = tp_bar;
-    o[8] = now - tp_loop_end; o[9] = NC;
-  }
-#endif
   if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
 }
 
@@ -704,12 +610,6 @@ __global__ void __launch_bounds__(512, 1) tconv_blur_n32_kernel(const TconvProbl
 // One raw s_barrier per chunk and two more per tile (z written -> blurred | the other eight channels written -> blurred).
 // Tile: 8 x 32 positions (16 x 64 outputs) x 16 out-channels; in_ch >= 32 (the tables are double-buffered by tile parity).
 // ---------------------------------------------------------------------------------------
-#ifndef TC_NT
-#define TC_NT 0           // pipelined form: 1 = the result leaves with non-temporal stores
-#endif
-#ifndef TC_PP_MQ
-#define TC_PP_MQ 2        // pipelined form: of a tile's four blur passes, how many the multiplying waves take (0 .. 4)
-#endif
 
 // MW multiplying waves (4: the form of round 5, one per SIMD beside a staging wave; 8: two per SIMD beside a staging wave --
 // twelve waves of at most 168 registers, which the kernel fits since the library is compiled without packed fp32 math: round 6)
@@ -865,9 +765,6 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
 
   if (wave >= MW) {
     // =========================== staging waves: channel quad g of every chunk ===========================
-#if TC_STAGE_PRIO
-    __builtin_amdgcn_s_setprio(TC_STAGE_PRIO);      // (static: the second-dispatched half loses the VALU arbitration by age otherwise)
-#endif
     const int g = wave - MW, lid = g * 64 + lane;
     const float xam = rw_bound_load(p.x_amax);
     const int hw4 = (int)hw * 4;
@@ -945,10 +842,8 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
         if (g == 0) wraw[2] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + 8 * 1024);
       }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (TC_ABL & 1) F.raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
-        else F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
-      }
+      for (int k = 0; k < 4; ++k)
+        F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
     };
     // what setup() requested beside the pixels -> registers / LDS (the first wait of an interval)
     auto tables = [&](auto tag) __attribute__((always_inline)) {
@@ -1002,39 +897,30 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     int cn = 0, e_pos = 0;                          // the tile the multiplying waves are on (its epilogue is shared)
     int e_ot, e_tx, e_ty, e_ib;
     rw_tile_digits(p, (unsigned)bx, e_ot, e_tx, e_ty, e_ib);
-    TP_DECL(tp = 0, tp_all = 0, tp_setup = 0, tp_del = 0, tp_bar = 0, tp_blur = 0, tp_ebar = 0, tp_tab = 0);
-    TP_NOW(tp); TP_NOW(tp_all);
     // interval n: chunk n + 1 (slot (n + 1) & 1, in flight for two intervals; its weights for one) -> LDS piece by piece, the
     // window of chunk n + 3 and the weights of chunk n + 2 requested behind it into the same registers (past the run:
     // harmless repeats)
     auto interval = [&](int n, auto tag) __attribute__((always_inline)) {
       tables(tag);
-      TP_ADD(tp_tab, tp);
       __builtin_amdgcn_sched_barrier(0);
       // (the strip's noise BEFORE this interval's window requests: loads return in order, and the wait for the noise at the
       // blur must leave the younger window loads in flight)
       if (STAGERS_BLUR && cn == NC - 1) noise_request(e_ty, e_tx, e_ib);
       __builtin_amdgcn_sched_barrier(0);
       setup(tag);
-      TP_ADD(tp_setup, tp);
 #pragma unroll
       for (int s = 0; s < SI; ++s) {
         deliver_s(tag, (n + 1) & 1, s); __builtin_amdgcn_sched_barrier(0);
         request_s(tag, s); __builtin_amdgcn_sched_barrier(0);
       }
-      TP_ADD(tp_del, tp);
       rw_lds_barrier();
-      TP_ADD(tp_bar, tp);
       if (++cn == NC) {                             // the tile's epilogue (the loads stay in flight)
         cn = 0;
         const int par = e_pos & 1;
         if (STAGERS_BLUR) blur(0, par, e_ot, e_tx, e_ty, e_ib);
-        TP_ADD(tp_blur, tp);
         rw_lds_barrier();                           // z is free: the multiplying waves write the other eight channels
         rw_lds_barrier();
-        TP_ADD(tp_ebar, tp);
         if (STAGERS_BLUR) blur(1, par, e_ot, e_tx, e_ty, e_ib);
-        TP_ADD(tp_blur, tp);
         ++e_pos;
         walk.advance(e_ot, e_tx, e_ty, e_ib);
       }
@@ -1042,13 +928,6 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     int n = 0;
     for (; n + 1 < N; n += 2) { interval(n, rw_int<1>()); interval(n + 1, rw_int<0>()); }
     if (n < N) interval(n, rw_int<1>());
-#if TC_PROF
-    if (wave == MW && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-      unsigned long long* o = tc_prof + (blockIdx.x == 0 ? 0 : 32);
-      o[8] = (unsigned long long)clock64() - tp_all; o[9] = tp_setup; o[10] = tp_del; o[11] = tp_bar; o[12] = tp_blur; o[13] = tp_ebar; o[14] = N;
-      o[16] = tp_tab;
-    }
-#endif
     if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
     return;
   }
@@ -1166,32 +1045,22 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
   int ot, tx, ty, ib;
   rw_tile_digits(p, (unsigned)bx, ot, tx, ty, ib);
   rw_lds_barrier();                                 // chunk 0 and the FIR are in LDS
-  TP_DECL(tp = 0, tp_all = 0, tp_mma = 0, tp_bar = 0, tp_zw = 0, tp_blur = 0, tp_ebar = 0);
-  TP_NOW(tp); TP_NOW(tp_all);
   for (int n = 0; n < N; ++n) {
     const unsigned char* lb = Ls + (n & 1) * BUFB;
     const unsigned char* wb = Wl + (n & 1) * TC_WCH + lane * 8;
     mma(lb, wb);
-    TP_ADD(tp_mma, tp);
-    if (c + 1 < NC) { ++c; rw_lds_barrier(); TP_ADD(tp_bar, tp); continue; }
+    if (c + 1 < NC) { ++c; rw_lds_barrier(); continue; }
     // ---- epilogue of the tile, eight channels at a time
     c = 0;
     const int par = pos & 1;
     noise_request(ty, tx, ib);                      // (behind the MFMAs: sixteen registers they need; the z write and a barrier cover it)
     zwrite(0);
-    TP_ADD(tp_zw, tp);
     rw_lds_barrier();                               // (the barrier of the tile's last chunk)
-    TP_ADD(tp_bar, tp);
     blur(0, par, ot, tx, ty, ib);
-    TP_ADD(tp_blur, tp);
     rw_lds_barrier();                               // every strip of the first eight channels is read: z is free again
-    TP_ADD(tp_ebar, tp);
     zwrite(1);
-    TP_ADD(tp_zw, tp);
     rw_lds_barrier();
-    TP_ADD(tp_ebar, tp);
     blur(1, par, ot, tx, ty, ib);
-    TP_ADD(tp_blur, tp);
 #pragma unroll
     for (int b = 0; b < BPW; ++b)
 #pragma unroll
@@ -1199,12 +1068,6 @@ __device__ __forceinline__ void tconv_ws_body(const TconvProblem& p) {
     ++pos;
     walk.advance(ot, tx, ty, ib);
   }
-#if TC_PROF
-  if (wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-    unsigned long long* o = tc_prof + (blockIdx.x == 0 ? 0 : 32);
-    o[0] = (unsigned long long)clock64() - tp_all; o[1] = tp_mma; o[2] = tp_bar; o[3] = tp_zw; o[4] = tp_blur; o[5] = tp_ebar; o[6] = N;
-  }
-#endif
   if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
 }
 __global__ void __launch_bounds__(512, 2) tconv_blur_ws_kernel(const TconvProblem p) { tconv_ws_body<4>(p); }
@@ -1366,9 +1229,6 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
 
   if (wave >= MW) {
     // =========================== staging + blurring waves ===========================
-#if TC_STAGE_PRIO
-    __builtin_amdgcn_s_setprio(TC_STAGE_PRIO);
-#endif
     const int g = wave - MW;
     const float xam = rw_bound_load(p.x_amax);
     const int hw4 = (int)hw * 4;
@@ -1407,8 +1267,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
       Flight& F = fl[decltype(tag)::value];
       F.first = l_c == 0 && !l_past;                              // (past the run: the last chunk again, never read)
       if (F.first) {
-        const int ib = (TC_ABL & 1024) ? 0 : l_ibn;                   // (timing ablation 1024: every tile reads image 0's first window -- cache hits)
-        const int i0 = (TC_ABL & 1024) ? 0 : l_ty * TY, j0 = (TC_ABL & 1024) ? 0 : l_tx * TC_TX;
+        const int ib = l_ibn;
+        const int i0 = l_ty * TY, j0 = l_tx * TC_TX;
         if (ib != l_ib) {
           l_ib = ib;
           const float smax = rw_style_absmax_wave(p, ib, lane);
@@ -1451,10 +1311,8 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         if (g == 0) wraw[2] = *reinterpret_cast<const rw_f32x4*>(l_wsrc + 8 * 1024);
       }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (TC_ABL & 1) F.raw[s][k] = rw_f32x4{1.f, 1.f, 1.f, 1.f};     // (timing ablation: no window loads; results wrong)
-        else F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
-      }
+      for (int k = 0; k < 4; ++k)
+        F.raw[s][k] = __builtin_bit_cast(rw_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xoff[s], l_s0 + k * hw4, 0));
     };
     auto tables = [&](auto tag) __attribute__((always_inline)) {
       Flight& F = fl[decltype(tag)::value];
@@ -1490,10 +1348,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
         const rw_f16x2 l01 = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
         const rw_f16x2 l23 = __builtin_convertvector(rw_f32x2{r2, r3}, rw_f16x2);
         rw_f16x8 word = {h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
-        if (TC_ABL & 256)                            // (timing ablation: no conversion arithmetic; results wrong)
-          word = __builtin_bit_cast(rw_f16x8, rw_f32x4{F.raw[s][0][e], F.raw[s][1][e], F.raw[s][2][e], F.raw[s][3][e]});
-        if (!(TC_ABL & 512) && ldst[s][e] >= 0) *reinterpret_cast<rw_f16x8*>(dst + ldst[s][e]) = word;
-        if (TC_ABL & 512) asm volatile("" :: "v"(word));
+        if (ldst[s][e] >= 0) *reinterpret_cast<rw_f16x8*>(dst + ldst[s][e]) = word;
       }
     };
 
@@ -1518,40 +1373,34 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     rw_tile_digits(p, (unsigned)bx, e_ot, e_tx, e_ty, e_ib);
     bool have_prev = false;                         // the tile whose z tile is in LDS, waiting to be blurred
     int b_ot = 0, b_tx = 0, b_ty = 0, b_ib = 0, b_par = 0;
-    TP_DECL(tp = 0, tp_all = 0, tp_setup = 0, tp_del = 0, tp_bar = 0, tp_blur = 0, tp_zbar = 0);
-    TP_NOW(tp); TP_NOW(tp_all);
     // interval n: chunk n + 1 -> LDS piece by piece, the window of chunk n + 3 and the weights of chunk n + 2 requested behind
     // it; then this interval's share of the previous tile's blur
     auto interval = [&](int n, auto tag) __attribute__((always_inline)) {
       tables(tag);
       __builtin_amdgcn_sched_barrier(0);
       setup(tag);
-      TP_ADD(tp_setup, tp);
 #pragma unroll
       for (int s = 0; s < SI; ++s) {
         deliver_s(tag, (n + 1) & 1, s); __builtin_amdgcn_sched_barrier(0);
         request_s(tag, s); __builtin_amdgcn_sched_barrier(0);
       }
-      TP_ADD(tp_del, tp);
       if (have_prev) {
-        // the staging waves' passes TC_PP_MQ .. 3, spread over the tile's intervals: pass MQ + k in interval [k NC / NS]
-        constexpr int NS = 4 - TC_PP_MQ;
-        const int p_lo = TC_PP_MQ + (NS * cn + NC - 1) / NC, p_hi = TC_PP_MQ + (NS * cn + NS + NC - 1) / NC;
+        // the staging waves' passes 2 and 3 (the multiplying waves take 0 and 1), spread over the tile's intervals: pass
+        // 2 + k in interval [k NC / NS]
+        constexpr int NS = 2;
+        const int p_lo = 2 + (NS * cn + NC - 1) / NC, p_hi = 2 + (NS * cn + NS + NC - 1) / NC;
 #pragma unroll 1
         for (int ps = p_lo; ps < p_hi; ++ps) blur(ps, b_par, b_ot, b_tx, b_ty, b_ib);
       }
-      TP_ADD(tp_blur, tp);
       rw_lds_barrier();
-      TP_ADD(tp_bar, tp);
       if (++cn == NC) {                             // the multiplying waves write the z tile of THEIR tile now
         cn = 0;
         b_ot = e_ot; b_tx = e_tx; b_ty = e_ty; b_ib = e_ib; b_par = e_pos & 3;
         have_prev = true;
-        if (TC_PP_MQ < 4) noise_request(b_ty, b_tx, b_ib);       // (ahead of the next interval's window requests: loads return in order)
+        noise_request(b_ty, b_tx, b_ib);                         // (ahead of the next interval's window requests: loads return in order)
         ++e_pos;
         walk.advance(e_ot, e_tx, e_ty, e_ib);
         rw_lds_barrier();                           // z is ready
-        TP_ADD(tp_zbar, tp);
       }
     };
     int n = 0;
@@ -1559,14 +1408,7 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
     if (n < N) interval(n, rw_int<1>());
     // the last tile's blur: nobody waits for it
 #pragma unroll 1
-    for (int ps = TC_PP_MQ; ps < 4; ++ps) blur(ps, b_par, b_ot, b_tx, b_ty, b_ib);
-#if TC_PROF
-    if (wave == MW && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-      unsigned long long* o = tc_prof + (blockIdx.x == 0 ? 0 : 32);
-      o[8] = (unsigned long long)clock64() - tp_all; o[9] = tp_setup; o[10] = tp_del; o[11] = tp_bar; o[12] = tp_blur; o[13] = tp_zbar; o[14] = N;
-      o[16] = 0;
-    }
-#endif
+    for (int ps = 2; ps < 4; ++ps) blur(ps, b_par, b_ot, b_tx, b_ty, b_ib);
     if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
     return;
   }
@@ -1672,27 +1514,20 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
   int ot, tx, ty, ib;
   rw_tile_digits(p, (unsigned)bx, ot, tx, ty, ib);
   rw_lds_barrier();                                 // chunk 0 and the FIR are in LDS
-  TP_DECL(tp = 0, tp_all = 0, tp_mma = 0, tp_bar = 0, tp_zw = 0, tp_zbar = 0, tp_blur = 0);
-  TP_NOW(tp); TP_NOW(tp_all);
   for (int n = 0; n < N; ++n) {
     const unsigned char* lb = Ls + (n & 1) * BUFB;
     const unsigned char* wb = Wl + (n & 1) * TC_WCH + lane * 8;
     mma(lb, wb);
-    TP_ADD(tp_mma, tp);
     rw_lds_barrier();                               // the chunk is consumed; at a tile's last chunk also: the previous tile is blurred, z is free
-    TP_ADD(tp_bar, tp);
     if (c + 1 < NC) { ++c; continue; }
     c = 0;
-    if (TC_PP_MQ > 0) noise_request(ty, tx, ib);    // (the z write and a barrier cover it)
+    noise_request(ty, tx, ib);                      // (the z write and a barrier cover it)
     zwrite();
-    TP_ADD(tp_zw, tp);
     rw_lds_barrier();                               // z is ready
-    TP_ADD(tp_zbar, tp);
-    // this role's share of the tile's blur (passes 0 .. TC_PP_MQ - 1), before the next tile's multiplies; the staging
+    // this role's share of the tile's blur (passes 0 and 1 of the four), before the next tile's multiplies; the staging
     // waves take the rest beside them
 #pragma unroll 1
-    for (int ps = 0; ps < TC_PP_MQ; ++ps) blur(ps, pos & 3, ot, tx, ty, ib);
-    TP_ADD(tp_blur, tp);
+    for (int ps = 0; ps < 2; ++ps) blur(ps, pos & 3, ot, tx, ty, ib);
     ++pos;
     walk.advance(ot, tx, ty, ib);
 #pragma unroll
@@ -1700,18 +1535,11 @@ __global__ void __launch_bounds__(512, 2) tconv_blur_pp_kernel(const TconvProble
 #pragma unroll
       for (int ph = 0; ph < 4; ++ph) acc[b][ph] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   }
-#if TC_PROF
-  if (wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) {
-    unsigned long long* o = tc_prof + (blockIdx.x == 0 ? 0 : 32);
-    o[0] = (unsigned long long)clock64() - tp_all; o[1] = tp_mma; o[2] = tp_bar; o[3] = tp_zw; o[4] = tp_blur; o[5] = tp_zbar; o[6] = N;
-  }
-#endif
   if (p.y_amax) rw_bound_store_wave(p.y_amax, rw_wave_max(ymax));
 }
 
 // ---------------------------------------------------------------------------------------
-// tconv_body's three shapes (tconv_blur_t8 / t16 / n32_kernel) with the window copied from the words of split_map_kernel (STAGED).  The timing ablations TC_ABL 1, 256
-// and 512 switch parts of the register staging and mean nothing here; the others (2, 8 .. 128) work as in the forms above.
+// tconv_body's three shapes (tconv_blur_t8 / t16 / n32_kernel) with the window copied from the words of split_map_kernel (STAGED).
 __global__ void __launch_bounds__(256, 2) tconv_blur_t8s_kernel(const TconvProblem p) { tconv_body<8, 4, 1, true>(p); }
 __global__ void __launch_bounds__(512, 1) tconv_blur_t16s_kernel(const TconvProblem p) { tconv_body<16, 8, 1, true>(p); }
 __global__ void __launch_bounds__(512, 1) tconv_blur_n32s_kernel(const TconvProblem p) { tconv_body<8, 8, 2, true>(p); }
@@ -1764,12 +1592,6 @@ static bool tconv_shape_ok(int out_ch, int in_ch, int h, int w) {
 extern "C" int rw_tconv_blur_supported(int out_ch, int in_ch, int h, int w) { return tconv_shape_ok(out_ch, in_ch, h, w) ? 1 : 0; }
 
 // ---- the scratch of the STAGED forms: one buffer per (device, stream), registered by the caller, who owns it
-#ifndef RW_TCONV_STAGED_DEFAULT
-#define RW_TCONV_STAGED_DEFAULT 1          // RW_TCONV_STAGED unset: the staged forms run where a buffer is registered
-#endif
-#ifndef RW_TCONV_STAGED_MIN_IN_DEFAULT
-#define RW_TCONV_STAGED_MIN_IN_DEFAULT 256 // RW_TCONV_STAGED_MIN_IN unset: the fewest input channels that take them
-#endif
 // the form of a launch (what RW_TCONV_TY means), from the environment and the channels
 static int tconv_form(int in_ch, int out_ch) {
   // the form: RW_TCONV_TY = 0 the specialised persistent kernel, 8 / 16 the two shapes of tconv_body; unset: by input channels -- the persistent kernel where a tile has few chunks (<= 128
@@ -1789,8 +1611,9 @@ static int tconv_form(int in_ch, int out_ch) {
 // does a launch of this form and these channels take the staged form when it finds a buffer?
 static bool tconv_staged_wanted(int sel, int in_ch, int batch) {
   if ((sel == 0 || sel == 2 || sel == 12) && in_ch >= 32) return false;      // the persistent forms stage in their own waves
-  return rw_env_int("RW_TCONV_STAGED", RW_TCONV_STAGED_DEFAULT) != 0 &&
-         in_ch >= rw_env_int("RW_TCONV_STAGED_MIN_IN", RW_TCONV_STAGED_MIN_IN_DEFAULT) && batch <= 65535;
+  // RW_TCONV_STAGED unset: the staged forms run where a buffer is registered; RW_TCONV_STAGED_MIN_IN unset: 256 is the
+  // fewest input channels that take them
+  return rw_env_int("RW_TCONV_STAGED", 1) != 0 && in_ch >= rw_env_int("RW_TCONV_STAGED_MIN_IN", 256) && batch <= 65535;
 }
 namespace {
 struct StageBuffer { int dev; hipStream_t stream; void* ptr; long long bytes; };

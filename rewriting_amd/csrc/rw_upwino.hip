@@ -53,13 +53,6 @@ struct UpWinoProblem {
   float u_inv;                  // H16: 1 / (the packed weights' scale), by value
 };
 
-#ifndef UW_ABL
-#define UW_ABL 0          // timing ablations (results WRONG): 2 = no patch pieces, 4 = no weight pieces, 8 = no epilogue;
-                          // H16: 16 = no operand split, 32 = no MFMAs, 64 = no weight reads from LDS
-#endif
-#ifndef UW_NTS
-#define UW_NTS 0          // non-temporal stores of the (2H+1)^2 map (A/B builds)
-#endif
 #define UW_PITCH 36             // row pitch of a patch channel in LDS: 33 columns + 3
 
 // NRW = 16: input maps 16 pixels wide (layer 7 of the generators: 16^2 -> 33^2, a fifth of a key-statistics sweep at
@@ -174,14 +167,12 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
   };
   // piece s = 0 .. 2 UW_PIECES - 1: channel 2 wave + s / UW_PIECES, piece s % UW_PIECES
   auto pload_piece = [&](int s) __attribute__((always_inline)) {
-    if (UW_ABL & 2) return;
     rw_dma_buffer_b32(p_dst + 256 * s, xoff[s % UW_PIECES], xsrc, p_soff + (s / UW_PIECES) * hw4);
   };
   // weights of an interval: 28 one-KB pieces [half 2][k-quad 2][7]; wave w copies pieces 7 w .. 7 w + 6
   const int kq_total = p.in_ch >> 2;
   const int a_lane = lane * 4;
   auto uload = [&](int slot, int fc) __attribute__((always_inline)) {
-    if (UW_ABL & 4) return;
     if (H16) {
       // 16 one-KB pieces [half 2][8]; wave w copies pieces 4 w .. 4 w + 3 (half w / 2)
       const float* src = p.uf + ((int64_t)((o0 >> 4) + (wave >> 1)) * (p.in_ch >> 3) + fc) * (16 * 128) + (wave & 1) * 1024;
@@ -278,17 +269,12 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
 #pragma unroll
       for (int hc = 0; hc < 4; ++hc) {
         const float t0 = T[0][v][hc], t1 = T[1][v][hc];
-        if (UW_ABL & 16) {
-          const rw_f16x2 h0 = __builtin_bit_cast(rw_f16x2, t0), h1 = __builtin_bit_cast(rw_f16x2, t1);
-          B[v][hc] = rw_f16x8{h0[0], h0[1], h1[0], h1[1], h0[0], h0[1], h1[0], h1[1]};
-        } else {
-          const rw_f16x2 hh = __builtin_convertvector(rw_f32x2{t0, t1}, rw_f16x2);
-          float r0, r1;
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hh), "v"(t0));
-          asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hh), "v"(t1));
-          const rw_f16x2 ll = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
-          B[v][hc] = rw_f16x8{hh[0], hh[1], hh[0], hh[1], ll[0], ll[1], ll[0], ll[1]};
-        }
+        const rw_f16x2 hh = __builtin_convertvector(rw_f32x2{t0, t1}, rw_f16x2);
+        float r0, r1;
+        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hh), "v"(t0));
+        asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hh), "v"(t1));
+        const rw_f16x2 ll = __builtin_convertvector(rw_f32x2{r0, r1}, rw_f16x2);
+        B[v][hc] = rw_f16x8{hh[0], hh[1], hh[0], hh[1], ll[0], ll[1], ll[0], ll[1]};
       }
     // weights: the 25 points carry 16 distinct values (E x O, O x E and O x O repeat theirs), (Uh pair, Ul pair) of
     // value wi at byte 512 wi + 8 lane (consecutive lanes 8 bytes apart: no bank conflicts -- 16 bytes apart cost
@@ -301,14 +287,12 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
     rw_u32x4 aq[2][4];
     auto aload = [&](int wi, rw_u32x4& dst) __attribute__((always_inline)) {
       // offsets of ds_read2_b64 count 8-byte units and stop at 255: one base per four values
-      if (UW_ABL & 64) { dst = rw_u32x4{ua, (unsigned)wi, ua, 1u}; return; }
       asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%2" : "=&v"(dst) : "v"(ua + (wi >> 2) * 2048), "n"((wi & 3) * 64));
     };
     auto point = [&](int xi, const rw_u32x4& a) __attribute__((always_inline)) {
       const int vr = xi < 9 ? xi / 3 : (xi < 15 ? (xi - 9) / 2 : (xi < 21 ? 1 + 2 * ((xi - 15) / 3) : 1 + 2 * ((xi - 21) / 2)));
       const int hc = xi < 9 ? xi % 3 : (xi < 15 ? 1 + 2 * ((xi - 9) % 2) : (xi < 21 ? (xi - 15) % 3 : 1 + 2 * ((xi - 21) % 2)));
-      if (UW_ABL & 32) asm volatile("" :: "v"(a), "v"(B[vr][hc]));
-      else acc[xi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rw_f16x8, a), B[vr][hc], acc[xi], 0, 0, 0);
+      acc[xi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rw_f16x8, a), B[vr][hc], acc[xi], 0, 0, 0);
     };
 #pragma unroll
     for (int e = 0; e < 4; ++e) aload(e, aq[0][e]);
@@ -382,11 +366,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         f32x4_u v = {px[r][0] * sc, px[r][1] * sc, px[r][2] * sc, px[r][3] * sc};
-#if UW_NTS
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4_u*>(yb + (int64_t)j * ohw + (int64_t)r * ow));
-#else
         *reinterpret_cast<f32x4_u*>(yb + (int64_t)j * ohw + (int64_t)r * ow) = v;
-#endif
       }
     }
 #pragma unroll
@@ -425,7 +405,7 @@ __device__ __forceinline__ void conv_up_wino_body(const UpWinoProblem& p) {
     advance();
     if (H16) compute16(ring, v & 1, c, true); else compute(ring, v & 1, c, true);
     const bool last = c == NC - 1;
-    if (last) { if (!(UW_ABL & 8) || acc[0][0] == 12345.f) group_epilogue(g); c = 0; ++g; } else { ++c; }
+    if (last) { group_epilogue(g); c = 0; ++g; } else { ++c; }
     ring = ring == 2 ? 0 : ring + 1;
     sync_interval(last);
   }

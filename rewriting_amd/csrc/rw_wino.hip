@@ -16,13 +16,6 @@
 // Kernel design: see conv_wino16_kernel below.
 #include "rw_common.h"
 
-// Timing ablations for kernel work (build a second library with -DWN_ABL=<bits>; results are WRONG when a bit is
-// set): 1 = no staging writes / transform, 2 = no barriers in the loop, 4 = no patch fetch, 8 = no B operand reads in
-// the loop, 16 = no weight loads in the loop.  0 in the product build.
-#ifndef WN_ABL
-#define WN_ABL 0
-#endif
-
 #define WN_PC 34                // patch columns
 
 struct WinoProblem {
@@ -436,12 +429,12 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
             const int xi = 4 * xq + xe;
             const int slot = kq * 32 + xq * 8 + xe * 2 + h;
             acc[xi][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[xq][h][xe], breg[xi], acc[xi][h], 0, 0, 0);
-            if (STAGE >= 1 && !(WN_ABL & 1) && slot % STRIDE == 0) {
+            if (STAGE >= 1 && slot % STRIDE == 0) {
               const int step = slot / STRIDE;
               if (step < NXS) xform_slot(buf ^ 1, step);
               else if (STAGE == 2 && step < NXS + NRAW) raw_step(buf, step - NXS);
             }
-            if (h == 1 && !(WN_ABL & 8)) {
+            if (h == 1) {
               // this B value is consumed: next k-quad of the same chunk now; next chunk only behind the barrier
               if (kq + 1 < KQ) bload(buf, kq + 1, xi);
               else if (STAGE >= 1 && slot > BAR_SLOT) bload(buf ^ 1, 0, xi);
@@ -451,18 +444,16 @@ __global__ void __launch_bounds__(256, 2) conv_wino16_kernel(const WinoProblem p
               // unconditional: the last turn of this loop fetches one virtual chunk past the run (a legal address,
               // nobody reads it).  Behind a branch, the compiler must count vmcnt for the path WITHOUT the
               // fetch, and every weight wait that follows then drains the fetch on the path with it.
-              if (STAGE == 2 && !(WN_ABL & 4)) fetch_chunk(fg, fc);
-              if (!(WN_ABL & 2)) __syncthreads();  // V[buf^1] and Rs[buf] complete; nobody reads V[buf] any more
-              if (!(WN_ABL & 8)) {
+              if (STAGE == 2) fetch_chunk(fg, fc);
+              __syncthreads();                     // V[buf^1] and Rs[buf] complete; nobody reads V[buf] any more
 #pragma unroll
-                for (int x2 = 0; x2 < 16; ++x2)
-                  if (2 * x2 + 1 <= BAR_SLOT - 32 * (KQ - 1)) bload(buf ^ 1, 0, x2);   // consumed before the barrier
-              }
+              for (int x2 = 0; x2 < 16; ++x2)
+                if (2 * x2 + 1 <= BAR_SLOT - 32 * (KQ - 1)) bload(buf ^ 1, 0, x2);     // consumed before the barrier
               __builtin_amdgcn_sched_barrier(0);
             }
           }
         }
-        if (!(WN_ABL & 16)) aload(xq, kqn);        // weights of this xi-quad for the next k-quad
+        aload(xq, kqn);                            // weights of this xi-quad for the next k-quad
         __builtin_amdgcn_sched_barrier(0);
       }
     }

@@ -32,17 +32,6 @@
 // ahead by global_load_lds and read from there (one ds_read_b128 per four points).
 #include "rw_common.h"
 
-// Timing ablations (build a second library with -DW4_ABL=<bits>; results are WRONG when a bit is set): 1 = no input
-// transform arithmetic, 2 = no patch fetch / staging, 4 = no weight copies, 8 = no output transform / stores,
-// 16 = no barriers in the loop; H16 kernels: 32 = no operand split (the three conversions per value), 64 = no MFMAs,
-// 128 = no duplication of the weight words.
-#ifndef W4_ABL
-#define W4_ABL 0
-#endif
-#ifndef W4_SETPRIO
-#define W4_SETPRIO 0      // A/B builds: wave priority (1..3) while the 36 MFMAs of a k-quad are issued
-#endif
-
 // Order of the 36 transform points in the packed weights (position -> natural index xi = 6 row + column): rows 0, 1, 2
 // first, then the second half in the order the point-split kernels want it -- positions 20..35 = rows 5, 3, 4 as far as
 // sixteen floats go, positions 18, 19 = the last two columns of row 4 -- so that BOTH halves read four whole quads
@@ -228,19 +217,10 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
       c2[r][2] = *reinterpret_cast<const rw_f32x2*>(src + r * W4_RS + 4);
     }
     float d[6][6];
-    if (!(W4_ABL & 1)) {
 #pragma unroll
-      for (int cp = 0; cp < 3; ++cp) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
-    }
+    for (int cp = 0; cp < 3; ++cp) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      if (!(W4_ABL & 1)) {
-        w4_bt_row(c2[a][0], c2[a][1], c2[a][2], d[a]);                                            // rows: (B^T d) B
-      } else {
-        d[a][0] = c2[a][0][0]; d[a][1] = c2[a][0][1]; d[a][2] = c2[a][1][0]; d[a][3] = c2[a][1][1];
-        d[a][4] = c2[a][2][0]; d[a][5] = c2[a][2][1];
-      }
-    }
+    for (int a = 0; a < 6; ++a) w4_bt_row(c2[a][0], c2[a][1], c2[a][2], d[a]);                    // rows: (B^T d) B
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
       const rw_f32x4 a = *reinterpret_cast<const rw_f32x4*>(base + q * 256);
@@ -319,22 +299,18 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
   for (int v = 0; v < VT; ++v) {
     const int buf = v & 1;
     const int ub2 = ub == 0 ? 2 : ub - 1;           // (v + 2) % 3
-    if (!(W4_ABL & 2)) {
-      stash(buf ^ 1);                               // interval v + 1 (the last one: a harmless refill)
-      fetch(fg, fc);                                // interval v + 2; past the run: legal addresses, never read
-    }
-    if (!(W4_ABL & 4)) uload(ub2, c + 2 < NC ? c + 2 : c + 2 - NC);   // weights of interval v + 2 (same slices for every group)
+    stash(buf ^ 1);                                 // interval v + 1 (the last one: a harmless refill)
+    fetch(fg, fc);                                  // interval v + 2; past the run: legal addresses, never read
+    uload(ub2, c + 2 < NC ? c + 2 : c + 2 - NC);    // weights of interval v + 2 (same slices for every group)
     compute(buf, ub);
     if (c == NC - 1) {
-      if (!(W4_ABL & 8) || acc[0][0] == 12345.f) group_epilogue(g);
+      group_epilogue(g);
       c = 0; ++g;
     } else { ++c; }
     if (++fc == NC) { fc = 0; ++fg; }
     ub = ub == 2 ? 0 : ub + 1;
-    if (!(W4_ABL & 16)) {
-      __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0), vmcnt / expcnt untouched
-      __builtin_amdgcn_s_barrier();
-    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);             // lgkmcnt(0), vmcnt / expcnt untouched
+    __builtin_amdgcn_s_barrier();
   }
 }
 
@@ -373,12 +349,13 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 //         whatever the pitch (the 8-byte read it replaces was 2-way by the same rule: 4 cycles).
 //       Per wave and interval 6 x (8 + 16) = 144 LDS cycles where pitch 68 took 6 x (4 + 4) = 48, in an interval of
 //       ~6500 cycles.  Measured on layer 18 + ToRGB (batch 64, same box and session, medians of five processes): this
-//       form 5.32 - 5.40 ms against the parent's 5.56 - 5.62; the outer columns as two 8-byte reads (-DW4_ROW3=1: 96
+//       form 5.32 - 5.40 ms against the parent's 5.56 - 5.62; the outer columns as two 8-byte reads (96
 //       cycles, three instructions per row) 5.38; from the neighbour lanes by DPP and one 4-byte read of the row's end
-//       columns (-DW4_ROW3=2: 60 cycles, twelve more vector instructions) 5.41; the padded pairs (-DW4_PAIRPAD=1, the
+//       columns (60 cycles, twelve more vector instructions) 5.41; the padded pairs (the
 //       forms with room: 120 cycles) 5.31 against 5.33 -- none outside the spread (0.1), so the two-instruction read and
-//       the unpadded slot stay.  Without any patch fetch (-DW4_ABL=2) the kernel takes 4.58 ms where the parent took
-//       4.26: 0.32 ms of the fetch's former 1.36 ms moved to the read side, 0.75 ms is still the fetch;
+//       the unpadded slot stay.  Without any patch fetch (a timing ablation) the kernel takes 4.58 ms where the parent took
+//       4.26: 0.32 ms of the fetch's former 1.36 ms moved to the read side, 0.75 ms is still the fetch.  (The
+//       alternatives and the ablation were build switches of this file up to commit 8dceca8);
 //   * weights: `global_load_lds_dwordx4`, 18 one-KB pieces per interval dealt to the eight waves;
 //   * noise of a group: four dword pieces per wave into a wave-private strip, issued FIRST in the group's second-to-last
 //     interval, so the counted wait at the end of that interval retires them.
@@ -390,43 +367,17 @@ __global__ void __launch_bounds__(256, 2) conv_wino36_kernel(const Wino4Problem 
 // weights of an interval serve four waves, the patch halo is 2 rows in 18.
 // ---------------------------------------------------------------------------------------
 #define W4B_PITCH 72          // window columns x0 - 4 .. x0 + 67: 18 aligned 16-byte items per row
-#ifndef W4_PAIRPAD
-#define W4_PAIRPAD 0      // A/B builds: conflict-free 16-byte window reads in the forms whose LDS has room (CPAD in the body)
-#endif
-#ifndef W4_ROW3
-#define W4_ROW3 0         // A/B builds: the row's outer columns by 1 = two 8-byte reads, 2 = DPP from the neighbour lanes
-#endif
-// (both measured on layer 18 + ToRGB and left off: profiles/INDEX.md, r10b)
+// (conflict-free 16-byte window reads by padded channel pairs, and the row's outer columns by two 8-byte reads or by DPP
+// from the neighbour lanes: measured on layer 18 + ToRGB and not kept: profiles/INDEX.md, r10b)
 // The six window columns of one tile in one row, as the three column pairs of the transform: rp = float 4 lt of the row,
 // the tile's columns are floats 3 .. 8.  One aligned 16-byte read of floats 4 .. 7 and one two-address read of 3 and 8.
-__device__ __forceinline__ void w4_row_read(const float* rp, rw_f32x2 (&c)[3], int eoff = 0) {
+__device__ __forceinline__ void w4_row_read(const float* rp, rw_f32x2 (&c)[3]) {
   const rw_f32x4 mid = *reinterpret_cast<const rw_f32x4*>(rp + 4);
-#if W4_ROW3 == 2
-  // A/B build: the outer columns from the neighbour tiles' lanes (a DPP row is the 16 tiles of a channel); the row's two
-  // end columns, which no lane holds, by one 4-byte read per row (eoff: float 68 for the last tile, float 3 otherwise)
-  const int edge = __float_as_int(rp[eoff]);
-  const float e0 = __int_as_float(__builtin_amdgcn_update_dpp(edge, __float_as_int(mid[3]), 0x111, 0xf, 0xf, false));
-  const float e5 = __int_as_float(__builtin_amdgcn_update_dpp(edge, __float_as_int(mid[0]), 0x101, 0xf, 0xf, false));
-#elif W4_ROW3
-  const float e0 = (*reinterpret_cast<const rw_f32x2*>(rp + 2))[1], e5 = (*reinterpret_cast<const rw_f32x2*>(rp + 8))[0];
-#else
   const float e0 = rp[3], e5 = rp[8];
-#endif
   c[0] = rw_f32x2{e0, mid[0]};
   c[1] = rw_f32x2{mid[1], mid[2]};
   c[2] = rw_f32x2{mid[3], e5};
 }
-#ifndef W4_NTS
-#define W4_NTS 0          // non-temporal stores of the output map (A/B builds)
-#endif
-#if W4_NTS
-#define W4_STORE(ptr, val) __builtin_nontemporal_store((val), reinterpret_cast<rw_f32x4*>(ptr))
-#else
-#define W4_STORE(ptr, val) (*reinterpret_cast<rw_f32x4*>(ptr) = (val))
-#endif
-#ifndef W4C_PREFETCH
-#define W4C_PREFETCH 0        // raw window of the next interval read during the MFMAs (36 more live registers)
-#endif
 // (the LDS-direct loads are inline assembly -- see the note on the compiler above: rw_dma_* in rw_common.h)
 
 // WGN tile rows per workgroup (2 WGN waves); UDEPTH = slots of the weight ring.  <4, 3>: one 512-thread workgroup per CU,
@@ -515,7 +466,6 @@ __device__ __forceinline__ void w4_at_row(const float (&t)[6], float (&v)[4]) {
 // ---------------------------------------------------------------------------------------
 // (h, h) and (l, l) of v: h = f16(v), l = f16(v - h)
 __device__ __forceinline__ void w4_split16(float v, rw_f16x2& hh, rw_f16x2& ll) {
-  if (W4_ABL & 32) { hh = __builtin_bit_cast(rw_f16x2, v); ll = hh; return; }
   hh = __builtin_convertvector(rw_f32x2{v, v}, rw_f16x2);
   float r;
   asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hh), "v"(v));     // v - (float)h, exact
@@ -524,10 +474,6 @@ __device__ __forceinline__ void w4_split16(float v, rw_f16x2& hh, rw_f16x2& ll) 
 __device__ __forceinline__ rw_f32x4 w4_mfma16(rw_u32x2 ww, rw_f16x2 hh, rw_f16x2 ll, rw_f32x4 acc) {
   const rw_f16x4 a = __builtin_bit_cast(rw_f16x4, ww);         // (w, w): the word of (position, lane) twice
   const rw_f16x4 b = {hh[0], hh[1], ll[0], ll[1]};
-  if (W4_ABL & 64) {
-    asm volatile("" :: "v"(a), "v"(b));
-    return acc;
-  }
   return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, acc, 0, 0, 0);
 }
 // the word Uh | Ul << 16 of u (already scaled)
@@ -539,7 +485,7 @@ __device__ __forceinline__ unsigned w4_pack16(float u) {
 
 template <int WGN, int UDEPTH, int MODE, bool STYLE, bool PS = false, bool H16 = false>
 __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
-  static_assert(!PS || (WGN == 2 && UDEPTH == 2), "the point split is written for the <2, 2> shape");
+  static_assert(!PS || (WGN == 2 && UDEPTH == 2 && H16), "the point split is written for the <2, 2> shape on the 16-bit pipe");
   constexpr bool UP = MODE == 1, RGB = MODE == 2;
   // floats of a wave's share of the noise strips (RGB: also the exchange buffer; UP: the 8 x 128 output-resolution
   // strip of a tile row is shared by the two out-channel waves, 512 floats each)
@@ -556,11 +502,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   constexpr int PPW = 4 * PIECES / WAVES;         // patch pieces per wave and interval
   static_assert(4 * PIECES % WAVES == 0, "patch pieces divide among the waves");
   constexpr int UPW = (9 * WGM + WAVES - 1) / WAVES;      // weight pieces per wave and interval (at most)
-  // channels (0, 1) and (2, 3) of a ring slot a multiple of 64 floats apart (slot order 0, 2, pad, 1, 3), where the LDS has
-  // the 384 bytes: see the bank notes above the body
-  constexpr int CPAD = W4_PAIRPAD && !UP ? 64 - 2 * CSZ % 64 : 0;
-  constexpr int PSZ = 4 * CSZ + CPAD;             // floats per patch ring slot
-  auto chan_off = [](int c) __attribute__((always_inline)) { return CPAD ? (c & 1) * (2 * CSZ + CPAD) + (c >> 1) * CSZ : c * CSZ; };
+  constexpr int PSZ = 4 * CSZ;                    // floats per patch ring slot
   constexpr int USZ = WGM * 9 * 256;              // floats per weight ring slot
   __shared__ __attribute__((aligned(16))) float Ps[3 * PSZ];
   __shared__ __attribute__((aligned(16))) float Us[UDEPTH * USZ];
@@ -659,7 +601,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   auto pload_begin = [&](int ring, int fg, int fc) __attribute__((always_inline)) {
     if (fc == 0) set_group(fg);
     p_soff = (4 * fc + pch) * hw4;
-    p_dst = ps_base + (unsigned)((ring * PSZ + chan_off(pch)) * 4);
+    p_dst = ps_base + (unsigned)((ring * PSZ + pch * CSZ) * 4);
   };
   auto pload_piece = [&](int s) __attribute__((always_inline)) {
     rw_dma_buffer_b128(p_dst + 16 * piece_item0(s), xoff[s], xsrc, p_soff);
@@ -706,8 +648,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   for (int xi = 0; xi < 36; ++xi) acc[xi] = rw_f32x4{0.f, 0.f, 0.f, 0.f};
   float ymax = 0.f;                 // H16: max |result| of this lane -> p.y_amax
 
-  const int item_off = chan_off(lk) + (4 * wn) * W4B_PITCH + 4 * lt;
-  const int edge_off = lt == 15 ? 8 : 3 - 4 * lt;   // W4_ROW3 == 2 only (w4_row_read)
+  const int item_off = lk * CSZ + (4 * wn) * W4B_PITCH + 4 * lt;
   auto compute = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
     constexpr bool SPREAD = decltype(spread_tag)::value != 0;
     const float* base = &Us[uring * USZ + wm * (9 * 256) + a_lane];
@@ -720,32 +661,21 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      w4_row_read(src + r * W4B_PITCH, c2[r], edge_off);
+      w4_row_read(src + r * W4B_PITCH, c2[r]);
       if (STYLE) { c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv; }
     }
     float d[6][6];
 #pragma unroll
-    for (int cp = 0; cp < 3; ++cp)
-      if (!(W4_ABL & 1)) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
+    for (int cp = 0; cp < 3; ++cp) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      if (!(W4_ABL & 1)) {
-        w4_bt_row(c2[a][0], c2[a][1], c2[a][2], d[a]);
-      } else {
-        d[a][0] = c2[a][0][0]; d[a][1] = c2[a][0][1]; d[a][2] = c2[a][1][0]; d[a][3] = c2[a][1][1];
-        d[a][4] = c2[a][2][0]; d[a][5] = c2[a][2][1];
-      }
-    }
+    for (int a = 0; a < 6; ++a) w4_bt_row(c2[a][0], c2[a][1], c2[a][2], d[a]);
     // weights two quads ahead (an LDS read issued right in front of its MFMAs costs the wave its latency nine times
     // per interval; two waves per SIMD do not hide that)
-#if W4_SETPRIO
-    __builtin_amdgcn_s_setprio(W4_SETPRIO);
-#endif
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
       const rw_f32x4 a = a4[q % 3];
       if (q + 3 < 9) a4[q % 3] = *reinterpret_cast<const rw_f32x4*>(base + (q + 3) * 256);
-      if (SPREAD && !(W4_ABL & 2)) {
+      if (SPREAD) {
         if (2 * q < PPW) pload_piece(2 * q);
         if (2 * q + 1 < PPW) pload_piece(2 * q + 1);
       }
@@ -756,9 +686,6 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
         acc[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], d[xi / 6][xi % 6], acc[xi], 0, 0, 0);
       }
     }
-#if W4_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
   };
 
   // H16: the same interval on v_mfma_f32_16x16x16_f16 (see the note above the body).  Points in the packed order
@@ -767,7 +694,6 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   // (position, lane) into both registers of the operand.
   auto aread = [&](unsigned addr, auto pos_tag, rw_u32x2& dst) __attribute__((always_inline)) {
     constexpr int POS = decltype(pos_tag)::value;
-    if (W4_ABL & 128) { dst = rw_u32x2{addr, (unsigned)POS}; return; }
     asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%2" : "=&v"(dst) : "v"(addr), "n"(POS));
   };
   auto compute16 = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
@@ -778,15 +704,14 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     rw_f32x2 c2[6][3];
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-      w4_row_read(src + r * W4B_PITCH, c2[r], edge_off);
+      w4_row_read(src + r * W4B_PITCH, c2[r]);
       c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv;
     }
     rw_u32x2 aq[2][6];
     aread(ua, rw_int<0>(), aq[0][0]); aread(ua, rw_int<1>(), aq[0][1]); aread(ua, rw_int<2>(), aq[0][2]);
     aread(ua, rw_int<3>(), aq[0][3]); aread(ua, rw_int<4>(), aq[0][4]); aread(ua, rw_int<5>(), aq[0][5]);
 #pragma unroll
-    for (int cp = 0; cp < 3; ++cp)
-      if (!(W4_ABL & 1)) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
+    for (int cp = 0; cp < 3; ++cp) w4_bt2(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp]);
     float d[6][6];
     auto batch = [&](auto bt_tag) __attribute__((always_inline)) {
       constexpr int BT = decltype(bt_tag)::value;
@@ -797,12 +722,11 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
         aread(ua, rw_int<6 * BT + 8>(), nxt[2]); aread(ua, rw_int<6 * BT + 9>(), nxt[3]);
         aread(ua, rw_int<6 * BT + 10>(), nxt[4]); aread(ua, rw_int<6 * BT + 11>(), nxt[5]);
         // this batch's reads are older than the six just issued
-        if (!(W4_ABL & 128))
-          asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
-      } else if (!(W4_ABL & 128)) {
+        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
+      } else {
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
       }
-      if (SPREAD && !(W4_ABL & 2)) {
+      if (SPREAD) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
           if (2 * BT + t < PPW) pload_piece(2 * BT + t);
@@ -813,14 +737,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
         const int xi = w4_nat(pos);
         const int ra = xi / 6;
         // first point of a row in the packed order: positions 0, 6, 12 (rows 0, 1, 2), 18 (row 4), 20 (row 5), 26 (row 3)
-        if (pos == 0 || pos == 6 || pos == 12 || pos == 18 || pos == 20 || pos == 26) {
-          if (!(W4_ABL & 1)) {
-            w4_bt_row(c2[ra][0], c2[ra][1], c2[ra][2], d[ra]);
-          } else {
-            d[ra][0] = c2[ra][0][0]; d[ra][1] = c2[ra][0][1]; d[ra][2] = c2[ra][1][0]; d[ra][3] = c2[ra][1][1];
-            d[ra][4] = c2[ra][2][0]; d[ra][5] = c2[ra][2][1];
-          }
-        }
+        if (pos == 0 || pos == 6 || pos == 12 || pos == 18 || pos == 20 || pos == 26)
+          w4_bt_row(c2[ra][0], c2[ra][1], c2[ra][2], d[ra]);
         rw_f16x2 hh, ll;
         w4_split16(d[ra][xi % 6], hh, ll);
         acc[xi] = w4_mfma16(cur[e], hh, ll, acc[xi]);
@@ -835,59 +753,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
   const float ps_cA = wm ? 1.f : 4.f, ps_cB = wm ? 2.f : 1.f, ps_cC = wm ? 2.f : 4.f;
   const int ps_row = wm * W4B_PITCH;               // patch rows wm, wm + 2, wm + 4 feed the single row
   const int ps_quad = wm * (5 * 256), ps_half = 4 * 256 + 2 * wm;       // weight quads 5 wm .. + 3; half quad
-  auto compute_ps = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
-    constexpr bool SPREAD = decltype(spread_tag)::value != 0;
-    const float* base = &Us[uring * USZ + a_lane];                        // block 1: + 9 * 256
-    const float* src = &Ps[ring * PSZ + item_off];
-    const float sv = St[4 * kq + lk];
-    rw_f32x4 a4[2][2];
-    a4[0][0] = *reinterpret_cast<const rw_f32x4*>(base + ps_quad);
-    a4[0][1] = *reinterpret_cast<const rw_f32x4*>(base + 9 * 256 + ps_quad);
-    // rows: [0..2] = patch rows wm, wm + 2, wm + 4; [3..6] = patch rows 1..4
-    rw_f32x2 c2[7][3];
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-      const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      w4_row_read(rp, c2[r], edge_off);
-      if (STYLE) { c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv; }
-    }
-    rw_f32x2 hrow[3][3];
-#pragma unroll
-    for (int cp = 0; cp < 3; ++cp)
-      w4_bt2_rows(c2[0][cp], c2[1][cp], c2[2][cp], c2[3][cp], c2[4][cp], c2[5][cp], c2[6][cp], ps_cA, ps_cB, ps_cC,
-                  hrow[0][cp], hrow[1][cp], hrow[2][cp]);
-    float d[3][6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) w4_bt_row(hrow[a][0], hrow[a][1], hrow[a][2], d[a]);
-    // four whole quads (local points 0..15), then the half quad (16, 17); weights one quad ahead
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const rw_f32x4 a0 = a4[q & 1][0], a1 = a4[q & 1][1];
-      if (q + 1 < 4) {
-        a4[(q + 1) & 1][0] = *reinterpret_cast<const rw_f32x4*>(base + ps_quad + (q + 1) * 256);
-        a4[(q + 1) & 1][1] = *reinterpret_cast<const rw_f32x4*>(base + 9 * 256 + ps_quad + (q + 1) * 256);
-      } else if (q + 1 == 4) {
-        const rw_f32x2 h0 = *reinterpret_cast<const rw_f32x2*>(base + ps_half);
-        const rw_f32x2 h1 = *reinterpret_cast<const rw_f32x2*>(base + 9 * 256 + ps_half);
-        a4[0][0] = rw_f32x4{h0[0], h0[1], 0.f, 0.f};
-        a4[0][1] = rw_f32x4{h1[0], h1[1], 0.f, 0.f};
-      }
-      if (SPREAD && !(W4_ABL & 2)) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          if (3 * q + t < PPW) pload_piece(3 * q + t);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int e = 0; e < (q < 4 ? 4 : 2); ++e) {
-        const int le = 4 * q + e;
-        acc[le] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], d[le / 6][le % 6], acc[le], 0, 0, 0);
-        acc[18 + le] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], d[le / 6][le % 6], acc[18 + le], 0, 0, 0);
-      }
-    }
-  };
-
-  // H16 + PS: as compute_ps; every value is split once and meets the weight words of both blocks.  Local point le of
+  // H16 + PS: every value is split once and meets the weight words of both blocks.  Local point le of
   // wave wm sits at packed position 20 wm + le (le < 16) resp. 16 + 2 wm + (le - 16): two wave-uniform bases, the
   // position within them an immediate; block 1 is 36 positions further.
   auto compute16_ps = [&](int ring, int uring, int kq, auto spread_tag) __attribute__((always_inline)) {
@@ -903,7 +769,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
       const float* rp = r < 3 ? src + ps_row + 2 * r * W4B_PITCH : src + (r - 2) * W4B_PITCH;
-      w4_row_read(rp, c2[r], edge_off);
+      w4_row_read(rp, c2[r]);
       c2[r][0] *= sv; c2[r][1] *= sv; c2[r][2] *= sv;
     }
     rw_f32x2 hrow[3][3];
@@ -921,12 +787,11 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
         aread(L0 < 16 ? ua : ub, rw_int<L0>(), nxt[0]); aread(L0 < 16 ? ua : ub, rw_int<L0 + 36>(), nxt[1]);
         aread(L1 < 16 ? ua : ub, rw_int<L1>(), nxt[2]); aread(L1 < 16 ? ua : ub, rw_int<L1 + 36>(), nxt[3]);
         aread(L2 < 16 ? ua : ub, rw_int<L2>(), nxt[4]); aread(L2 < 16 ? ua : ub, rw_int<L2 + 36>(), nxt[5]);
-        if (!(W4_ABL & 128))
-          asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
-      } else if (!(W4_ABL & 128)) {
+        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
+      } else {
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) :: "memory");
       }
-      if (SPREAD && !(W4_ABL & 2)) {
+      if (SPREAD) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
           if (2 * BT + t < PPW) pload_piece(2 * BT + t);
@@ -1045,8 +910,8 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
           q0[k] = fmaxf(u0, u0 * slope) * post; q1[k] = fmaxf(u1, u1 * slope) * post;
           if (H16) ymax = fmaxf(ymax, fmaxf(fabsf(q0[k]), fabsf(q1[k])));
         }
-        W4_STORE(yb + off, q0);
-        W4_STORE(yb + off + 4, q1);
+        *reinterpret_cast<rw_f32x4*>(yb + off) = q0;
+        *reinterpret_cast<rw_f32x4*>(yb + off + 4) = q1;
       }
     }
 #pragma unroll
@@ -1175,7 +1040,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
           v[k] = fmaxf(u, u * slope);
         }
         if (H16) ymax = fmaxf(fmaxf(ymax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        W4_STORE(yb + (int64_t)j * hw + (int64_t)r * p.w, v);
+        *reinterpret_cast<rw_f32x4*>(yb + (int64_t)j * hw + (int64_t)r * p.w) = v;
       }
     }
 #pragma unroll
@@ -1196,7 +1061,7 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     } else {
       if (stores) W4_WAIT(PPW + UPW - 1 + NST); else W4_WAIT(PPW + UPW - 1);
     }
-    if (!(W4_ABL & 16)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
   };
 
   // ---- prologue: the tables (ordinary loads and LDS writes) are complete before any LDS-direct load is issued --
@@ -1221,22 +1086,21 @@ __device__ __forceinline__ void conv_wino36b_body(const Wino4Problem& p) {
     if (p.noise && c == NC - 2) nload(g);           // older than this interval's pieces: retired by its wait
     static_assert(2 * 9 >= PPW, "two patch pieces per weight quad cover the wave's share");
     if (UDEPTH == 2) {
-      if (!(W4_ABL & 4)) uload((v + 1) & 1, c + 1 < NC ? c + 1 : 0);      // weights of interval v + 1
+      uload((v + 1) & 1, c + 1 < NC ? c + 1 : 0);                         // weights of interval v + 1
       pload_begin(ring2, fg, fc);                   // past the run: legal addresses, never read
       // ... issues the patch pieces of v + 2 between its MFMAs
       if (H16 && PS) compute16_ps(ring, v & 1, c, rw_int<1>());
       else if (H16) compute16(ring, v & 1, c, rw_int<1>());
-      else if (!PS) compute(ring, v & 1, c, rw_int<1>());
-      else compute_ps(ring, v & 1, c, rw_int<1>());
+      else compute(ring, v & 1, c, rw_int<1>());
     } else {
-      if (!(W4_ABL & 2)) pload(ring2, fg, fc);
-      if (!(W4_ABL & 4)) uload(ring2, fc);
+      pload(ring2, fg, fc);
+      uload(ring2, fc);
       if (H16) compute16(ring, ring, c, rw_int<0>());
       else compute(ring, ring, c, rw_int<0>());
     }
     const bool last = c == NC - 1;
     if (last) {
-      if (!(W4_ABL & 8) || acc[0][0] == 12345.f) group_epilogue(g, v & 1);
+      group_epilogue(g, v & 1);
       c = 0; ++g;
     } else { ++c; }
     if (++fc == NC) { fc = 0; ++fg; }
@@ -1287,29 +1151,14 @@ static bool w4h_point_split(int in_ch) {
   return mode < 0 ? in_ch >= 64 : mode != 0;
 }
 
-// The same six with the 36 points split between the two out-channel waves (PS above).  MEASURED FLAT (same box, batch
+// The six fp32 kernels with the 36 points split between the two out-channel waves (PS above) MEASURED FLAT (same box, batch
 // 64, ms per 10 steps, split off / on: layers 10-16 173.3 / 172.8, layer 17 107.0 / 109.9, layer 18 + ToRGB 56.8 / 57.9;
 // profiles/r03_w4_point_split.log): the ~220 vector cycles it saves per k-quad and wave are given back by what it adds -- a
 // seventh patch row read, weights only one quad ahead (16 registers are gone), per group eight raw barriers and the swap
 // -- and by what does not shrink: the LDS counters (profiles/r03_pmc_lds_summary_b64.json) show the LDS itself at 25 % of
 // its bandwidth (32 B/clk per CU), so the interval is paced by its dependent chain (landed pieces -> barrier -> LDS reads
-// -> transform -> MFMAs), not by a throughput that fewer instructions would relieve.  Built only with -DW4_PSPLIT=1
-// (RW_W4_PSPLIT=1 then selects it at run time); the kernel tests pass in both modes.
-#ifndef W4_PSPLIT
-#define W4_PSPLIT 0
-#endif
-#if W4_PSPLIT
-__global__ void __launch_bounds__(256, 2) conv_wino36b_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 0, true, true>(p); }
-__global__ void __launch_bounds__(256, 2) conv_wino36b_ns_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 0, false, true>(p); }
-__global__ void __launch_bounds__(256, 2) conv_up_wino36_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 1, true, true>(p); }
-__global__ void __launch_bounds__(256, 2) conv_up_wino36_ns_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 1, false, true>(p); }
-__global__ void __launch_bounds__(256, 2) conv_wino36_rgb_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 2, true, true>(p); }
-__global__ void __launch_bounds__(256, 2) conv_wino36_rgb_ns_ps_kernel(const Wino4Problem p) { conv_wino36b_body<2, 2, 2, false, true>(p); }
-static bool w4_point_split() {
-  static const bool on = rw_env_is("RW_W4_PSPLIT", '1');
-  return on;
-}
-#endif
+// -> transform -> MFMAs), not by a throughput that fewer instructions would relieve.  They are not kept: only the H16 kernels
+// above split the points (the fp32 ones lived in this file, behind a build switch, up to commit 8dceca8).
 
 // G g G^T of one 3x3 kernel g[3 ky + kx]: the 36 values u[6 a + b]
 __device__ __forceinline__ void w4_weight_points(const float* g, float (&u)[36]) {
@@ -1527,12 +1376,6 @@ static int conv3x3_wino4_launch(const float* x, const float* uf, float* y, int b
     return RW_LAUNCH_RESULT();
   }
   if (version == 3 && in_ch <= 512) {
-#if W4_PSPLIT
-    if (w4_point_split()) {
-      if (p.style) hipLaunchKernelGGL(conv_wino36b_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-      else hipLaunchKernelGGL(conv_wino36b_ns_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-    } else
-#endif
     if (p.style) hipLaunchKernelGGL((conv_wino36b_kernel<2, 2>), dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     else hipLaunchKernelGGL(conv_wino36b_ns_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     return RW_LAUNCH_RESULT();
@@ -1629,12 +1472,6 @@ static int up_wino4_launch(const float* x, const float* uf, float* y, int batch,
     else hipLaunchKernelGGL(conv_up_wino36h_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     return rw_finish_bound(y_amax, 4 * work, stream);
   }
-#if W4_PSPLIT
-  if (w4_point_split()) {
-    if (p.style) hipLaunchKernelGGL(conv_up_wino36_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-    else hipLaunchKernelGGL(conv_up_wino36_ns_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  } else
-#endif
   if (p.style) hipLaunchKernelGGL(conv_up_wino36_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
   else hipLaunchKernelGGL(conv_up_wino36_ns_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
   return RW_LAUNCH_RESULT();
@@ -1702,12 +1539,6 @@ static int wino4_to_rgb_launch(const float* x, const float* uf, int batch, int i
     else hipLaunchKernelGGL(conv_wino36h_rgb_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
     return RW_LAUNCH_RESULT();
   }
-#if W4_PSPLIT
-  if (w4_point_split()) {
-    if (p.style) hipLaunchKernelGGL(conv_wino36_rgb_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-    else hipLaunchKernelGGL(conv_wino36_rgb_ns_ps_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
-  } else
-#endif
   if (p.style) hipLaunchKernelGGL(conv_wino36_rgb_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
   else hipLaunchKernelGGL(conv_wino36_rgb_ns_kernel, dim3((unsigned)work), dim3(256), 0, rw_s(stream), p);
   return RW_LAUNCH_RESULT();

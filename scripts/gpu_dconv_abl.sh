@@ -1,16 +1,10 @@
 #!/bin/bash
-# direct-16 kernels: where does the time go?  (1) batch-64 check against the fp32 direct kernel, (2) timing ablations
-# (scripts/probe/abl/lib_dcabl_<bits>.so: 1 = no staging loads, 2 = no MFMAs, 4 = no weight loads, 8 = no epilogue),
-# (3) SQ / TCC counters of the product.   bash scripts/gpu_dconv_abl.sh <tag>
+# direct-16 kernels: where does the time go?  (1) batch-64 check against the fp32 direct kernel, (2) SQ / TCC counters of
+# the product.   bash scripts/gpu_dconv_abl.sh <tag>   (the timing-ablation builds this script once timed too left the
+# sources with their build switch; their figures: profiles/r04p)
 TAG=${1:-r04p}; OUT=gpurun_out/$TAG; mkdir -p $OUT; R=$PWD; export TMPDIR=/tmp
 export RW_LAYERS=${RW_LAYERS:-layer14,layer16,layer17,layer18}
 echo "== product (with checks on layer16)"; RW_CHECK=1 python scripts/dconv_bench.py 2>&1 | grep layer | tee $OUT/product.jsonl
-for a in $ABLS; do
-  echo "== DC_ABL=$a"; RW_HIP_LIB=$R/scripts/probe/abl/lib_dcabl_$a.so python scripts/dconv_bench.py 2>&1 | grep layer | python -c "
-import sys, json
-for l in sys.stdin:
-    d = json.loads(l); print(d['layer'], {k: v for k, v in d.items() if k.endswith('_ms')})" | tee $OUT/abl_$a.txt
-done
 i=0
 for SET in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES" \
            "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS" \

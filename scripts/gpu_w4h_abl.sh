@@ -1,15 +1,12 @@
 #!/bin/bash
-# Round 4: where does the time of the split-operand F(4x4,3x3) kernels go?  (1) timing ablations (libraries built with
-# -DW4_ABL=<bits> under scripts/probe/abl/lib_w4habl_<bits>.so, results WRONG), (2) SQ counters of the product.
-# bash scripts/gpu_w4h_abl.sh <tag>
+# Round 4: where does the time of the split-operand F(4x4,3x3) kernels go?  (1) the product per layer, point split off
+# and on, (2) SQ counters of the product.   bash scripts/gpu_w4h_abl.sh <tag>   (the timing-ablation builds this script
+# once timed too left the sources with their build switch; their figures: profiles/r04c_w4h_ablation_ms.json)
 TAG=${1:-r04c}; OUT=gpurun_out/$TAG; mkdir -p $OUT; R=$PWD; export TMPDIR=/tmp
 export RW_BATCH=64 RW_ALGO=winograd4 RW_LAYERS=${RW_LAYERS:-layer10,layer14,layer18} RW_W4_MM=split
 for ps in 0 1; do
   export RW_W4H_PS=$ps
   echo "== product ps=$ps"; RW_OUT=$TAG/abl_product_ps$ps.json python scripts/conv_bench.py 2>&1 | grep layer | cut -c1-22,120-175
-  for a in $ABLS; do
-    echo "== W4_ABL=$a ps=$ps"; RW_HIP_LIB=$R/scripts/probe/abl/lib_w4habl_$a.so RW_OUT=$TAG/abl_${a}_ps$ps.json python scripts/conv_bench.py 2>&1 | grep layer | cut -c1-22,120-175
-  done
 done
 i=0
 for SET in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES" \

@@ -24,7 +24,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "rewriting_amd/csrc"
-HEADERS = [CSRC + "/rw_common.h", "include/rewriting_hip.h"]
+HEADERS = [CSRC + "/rw_common.h", CSRC + "/rw_inflate_core.h", "include/rewriting_hip.h"]
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result".split()
 NOPK = "-Xclang -target-feature -Xclang -packed-fp32-ops".split()
 # --ops: floating-point arithmetic (the _dpp forms included), conversions and selects; matrix instructions; lane permutes

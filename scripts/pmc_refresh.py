@@ -15,7 +15,7 @@ T = json.load(open(path))
 dst = 'profiles/%s_pmc_summary_b64.json' % tag
 shutil.copy(summary, os.path.join(ROOT, dst))
 src = ('%s (rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace, one pass per counter, bench.py --full --steps 2 --warmup 1 --no-extra '
-       '--no-cpu-baseline, the default kernel selection: scripts/gpu_r05_measure.sh %s "prof pmc"); raw FETCH_SIZE + WRITE_SIZE bytes averaged over '
+       '--no-cpu-baseline, the default kernel selection: scripts/pmc_round.sh %s); raw FETCH_SIZE + WRITE_SIZE bytes averaged over '
        'the launches of the kernel name (not doubled; the doubled figure is the upper bound)' % (dst, tag))
 for k in kernels:
     r = S[k]
