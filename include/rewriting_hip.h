@@ -1012,6 +1012,65 @@ int rw_to_rgb_f64(const double* x, const double* w, const double* style, const d
                   const double* skip, double* y, int batch, int in_ch, int64_t hw, double w_scale,
                   rw_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The Frechet distance on the device -- replaces numpy.cov's consumers and scipy.linalg.sqrtm in
+ * calculate_frechet_distance (metrics/fid.py:60-61,137-187):
+ *   d^2 = |mu1 - mu2|^2 + Tr S1 + Tr S2 - 2 Tr sqrt(S1 S2),   Tr sqrt(S1 S2) = sum_i sqrt(mu_i(F^T S2 F)),  S1 = F F^T,
+ * an eigenvalue problem of two symmetric PSD matrices, solved by a float64 block one-sided (Hestenes) Jacobi iteration.
+ * Every pointer is a DEVICE pointer to contiguous float64 unless stated.  The entries are added at ABI 11 as the PNG and
+ * resize entries were: an entry that is only added changes no existing call.
+ *
+ * The working arrays g and v are n x n, row-major, ROW j holding COLUMN j of G and of V: g starts as the symmetric
+ * matrix S (zero-padded to n, a multiple of the block width and at least two blocks), v as the identity; at convergence
+ * the column norms of G = S V are the eigenvalues and V the eigenvectors.
+ *
+ * Rotation rule, stated once.  Columns x, y with squared norms a, b and inner product gamma are rotated when
+ *   |gamma| > RW_JACOBI_TOL(n) sqrt(a) sqrt(b)      and      max(a, b) > RW_JACOBI_FLOOR(n)^2 max_j |column j of S|^2.
+ * TOL: a computed inner product of n terms differs from the exact one by at most n eps |x| |y| (eps = 2^-52), so a cosine
+ * below n eps is not known to differ from zero, and a rotation by it would be repeated for ever.  sqrt(a) sqrt(b) is
+ * formed, not sqrt(a b): the product of two squared norms overflows for large inputs.  FLOOR: a column that is zero in exact
+ * arithmetic (a rank-deficient S) carries the rounding of the rotations that emptied it, n eps of the largest column at
+ * most per sweep; two such columns have a cosine of order one and would rotate for ever, and their norms are below what
+ * the input determines (the eigenvalue they stand for is known to n eps lambda_max only).  The largest column of the
+ * INPUT is the reference: it lies within sqrt(n) of lambda_max and needs no reduction during the iteration.
+ * ------------------------------------------------------------------------------------- */
+#define RW_JACOBI_TOL(n)   ((double)(n) * 0x1p-52)
+#define RW_JACOBI_FLOOR(n) ((double)(n) * 0x1p-52)
+
+/* One step (one launch) of a sweep: workgroup k takes the block pair k of round `step` of the circle method over the
+ * n / block column blocks (rounded up to even; blocks - 1 steps make a sweep in which every block meets every other once,
+ * the block that meets the dummy of an odd count has a bye), forms the Gram matrix of its 2 block columns on
+ * v_mfma_f64_16x16x4_f64, diagonalises it in LDS (bounded cyclic two-sided Jacobi, rotations accumulated from the identity,
+ * columns then ordered by decreasing norm) and applies the factor to its columns of g and, if v is not NULL, of v.
+ * block is 8 or 16.  norms_sq (n): rw_colnorm_f64(mode 1) of the INPUT, the same for every step.  slots: m / 2 ints for
+ * THIS step, m = blocks rounded up to even; workgroup k stores its rotation count to slots[k] with a plain store (0 for a
+ * bye), or -1 if its columns hold a non-finite value -- it then changes nothing.  No atomics; no workgroup waits for
+ * another.  RW_ERR_BAD_ARGUMENT: a null g, norms_sq or slots, block not 8 or 16, n < 2 block or no multiple of it, step
+ * outside 0 .. m - 2; RW_ERR_UNSUPPORTED: g or v not 32-byte aligned. */
+int rw_jacobi_step_f64(double* g, double* v, int n, int block, int step, const double* norms_sq, int* slots,
+                       rw_stream_t stream);
+
+/* The slots of a sweep reduced: out[0] = the sum of the counts, out[1] = how many slots say non-finite (out: two 64-bit
+ * integers on the device).  What the host reads once per sweep. */
+int rw_jacobi_count_i32(const int* slots, int64_t nslots, long long* out, rw_stream_t stream);
+
+/* out[j] = the norm of row j of g (n x n) -- column j of G, the eigenvalue at convergence (mode 0); its square (mode 1);
+ * its square root (mode 2: the scale of F = V diag(sqrt(lambda))).  One wave per row, a fixed order of the sum. */
+int rw_colnorm_f64(const double* g, double* out, int n, int mode, rw_stream_t stream);
+
+/* C (m x n) = diag(row_scale) op(A) op(B) diag(col_scale), all row-major: op(A) is m x k (trans_a: A is stored k x m),
+ * op(B) is k x n (trans_b: B is stored n x k); row_scale (m) and col_scale (n) nullable.  v_mfma_f64_16x16x4_f64, no split
+ * of k: the same bits from run to run.  It forms T = diag(sqrt(lambda)) V^T S2 and B = T V diag(sqrt(lambda)).  C must not
+ * alias A or B. */
+int rw_gemm_f64(const double* a, const double* b, double* c, int m, int n, int k, int trans_a, int trans_b,
+                const double* row_scale, const double* col_scale, rw_stream_t stream);
+
+/* out[0 .. 4] = { d^2, |mu1 - mu2|^2, Tr S1, Tr S2, sum_i sqrt(max(ev[i], 0)) } with
+ * d^2 = ((|mu1 - mu2|^2 + Tr S1) + Tr S2) - 2 sum sqrt(ev) (the order of metrics/fid.py:186-187); mu (n), S (n x n), ev (n_ev).
+ * One workgroup, every sum in a fixed order. */
+int rw_frechet_finish_f64(const double* mu1, const double* mu2, const double* s1, const double* s2, const double* ev,
+                          int n, int n_ev, double* out, rw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

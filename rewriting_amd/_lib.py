@@ -251,6 +251,13 @@ SIGNATURES = {
                                  c_void_p]),
     'rw_to_rgb_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_int64, c_double, c_void_p]),
+    # the Frechet distance (rw_frechet.hip): block Jacobi step, its slots, column norms, f64 GEMM, the final sums
+    'rw_jacobi_step_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rw_jacobi_count_i32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    'rw_colnorm_f64': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'rw_gemm_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p]),
+    'rw_frechet_finish_f64': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

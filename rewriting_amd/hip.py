@@ -1767,3 +1767,132 @@ def conv_transpose3x3s2_f64(x, weight, w_scale, style=None, demod=None):
     return _conv_f64('rw_conv_transpose3x3s2_f64', True, x, weight, w_scale, style, demod)
 
 
+# ------------------------------------------------------------------ the Frechet distance on the device
+# rw_frechet.hip: a float64 block one-sided Jacobi eigensolver for symmetric PSD matrices, the f64 GEMM and the final
+# sums (include/rewriting_hip.h, last section).  torch allocates, pads, sorts and slices; every sum and every rotation
+# is the library's.
+JACOBI_BLOCK = 16               # columns per block (8 or 16): the faster of the two on the MI355X, profiles/frechet_distance.json
+JACOBI_MAX_SWEEPS = 40
+
+
+def jacobi_padded_order(n, block=None):
+    """The order the kernels run at: a multiple of the block width, at least one block pair."""
+    block = JACOBI_BLOCK if block is None else block
+    return max(2 * block, -(-n // block) * block)
+
+
+def _square_f64(t, name):
+    """The refusals of the eigensolver and the distance, the device last (so that they read the same on any host)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor' % name)
+    if t.dim() != 2 or t.shape[0] != t.shape[1] or t.shape[0] < 1:
+        raise ValueError('%s must be a square matrix, it is %s' % (name, tuple(t.shape)))
+    if t.dtype != torch.float64:
+        raise RuntimeError('rewriting_amd: %s is %s; this entry takes torch.float64 (nothing is converted)' % (name, t.dtype))
+    if not t.is_contiguous():
+        raise ValueError('%s must be contiguous (nothing is copied)' % name)
+    if not t.is_cuda:
+        raise RuntimeError('rewriting_amd: %s is on %s; the HIP kernels need a GPU tensor (there is no CPU fallback)'
+                           % (name, t.device))
+    return t.detach()
+
+
+def _padded(s, npad):
+    n = s.shape[0]
+    g = torch.zeros(npad, npad, dtype=_F64, device=s.device)
+    g[:n, :n] = s
+    return g
+
+
+def colnorm_f64(g, mode=0):
+    """Norms of the rows of g (mode 0), their squares (1) or their square roots (2)."""
+    g = _dev(g, 'matrix', _F64)
+    out = torch.empty(g.shape[0], dtype=_F64, device=g.device)
+    check(lib().rw_colnorm_f64(_p(g), _p(out), g.shape[0], mode, _stream()))
+    return out
+
+
+def _jacobi_solve(g, vectors, max_sweeps, block):
+    """Block Jacobi on the padded array g (rows = columns of G), in place.  Returns (v or None, sweeps); reads two integers
+    per sweep and nothing else."""
+    npad = g.shape[0]
+    blocks = npad // block
+    m = blocks + (blocks & 1)
+    v = torch.eye(npad, dtype=_F64, device=g.device) if vectors else None
+    norms_sq = colnorm_f64(g, 1)
+    slots = torch.empty((m - 1) * (m // 2), dtype=torch.int32, device=g.device)
+    out = torch.empty(2, dtype=torch.int64, device=g.device)
+    step_fn, stream = lib().rw_jacobi_step_f64, _stream()
+    for sweep in range(1, max_sweeps + 1):
+        for step in range(m - 1):
+            check(step_fn(_p(g), _p(v), npad, block, step, _p(norms_sq),
+                          ctypes.c_void_p(slots.data_ptr() + 4 * step * (m // 2)), stream))
+        check(lib().rw_jacobi_count_i32(_p(slots), slots.numel(), _p(out), stream))
+        count, bad = out.tolist()
+        if bad:
+            raise ValueError('the matrix holds a non-finite value')
+        if count == 0:
+            return v, sweep
+    raise RuntimeError('rewriting_amd: the Jacobi iteration did not converge in %d sweeps (%d rotations in the last one)'
+                       % (max_sweeps, count))
+
+
+def eigh_psd_f64(S, vectors=True, max_sweeps=JACOBI_MAX_SWEEPS, block=None):
+    """(eigenvalues ascending, eigenvectors as columns or None, sweeps) of a symmetric PSD float64 matrix on the device by
+    the block one-sided Jacobi of rw_frechet.hip.  Refuses non-square, non-float64, non-contiguous, host and non-finite
+    input; raises when ``max_sweeps`` is reached without convergence."""
+    S = _square_f64(S, 'S')
+    block = JACOBI_BLOCK if block is None else block
+    n = S.shape[0]
+    npad = jacobi_padded_order(n, block)
+    g = _padded(S, npad)
+    v, sweeps = _jacobi_solve(g, vectors, max_sweeps, block)
+    lam = colnorm_f64(g, 0)
+    if not vectors:
+        return torch.sort(lam).values[npad - n:], None, sweeps      # the padding's columns stay exact zeros
+    keep = ~(v[:, n:] != 0).any(1)                                   # ... and their vectors unit vectors past row n
+    lam, v = lam[keep], v[keep, :n]
+    lam, order = torch.sort(lam)
+    return lam, v[order].t(), sweeps
+
+
+def gemm_f64(a, b, trans_a=False, trans_b=False, row_scale=None, col_scale=None):
+    """diag(row_scale) op(a) op(b) diag(col_scale) in float64."""
+    a, b = _dev(a, 'a', _F64), _dev(b, 'b', _F64)
+    m, k = (a.shape[1], a.shape[0]) if trans_a else a.shape
+    k2, n = (b.shape[1], b.shape[0]) if trans_b else b.shape
+    if a.dim() != 2 or b.dim() != 2 or k != k2:
+        raise ValueError('shapes do not multiply: op(a) %d x %d, op(b) %d x %d' % (m, k, k2, n))
+    row_scale, col_scale = _opt(row_scale, 'row_scale', _F64), _opt(col_scale, 'col_scale', _F64)
+    if (row_scale is not None and row_scale.numel() != m) or (col_scale is not None and col_scale.numel() != n):
+        raise ValueError('row_scale must have %d entries and col_scale %d' % (m, n))
+    c = torch.empty(m, n, dtype=_F64, device=a.device)
+    check(lib().rw_gemm_f64(_p(a), _p(b), _p(c), m, n, k, int(trans_a), int(trans_b), _p(row_scale), _p(col_scale), _stream()))
+    return c
+
+
+def frechet_distance_f64(mu1, sigma1, mu2, sigma2, max_sweeps=JACOBI_MAX_SWEEPS, block=None, parts=None):
+    """d^2 = |mu1 - mu2|^2 + Tr(S1 + S2 - 2 sqrt(S1 S2)) of float64 device tensors as a Python float: eigh(S1) -> T =
+    diag(sqrt(lambda)) V^T S2 -> B = T V diag(sqrt(lambda)) -> eigenvalues of B -> the sums, one copy to the host at the
+    end.  ``parts``: a dict that receives the sweeps of both solves and the five sums."""
+    sigma1, sigma2 = _square_f64(sigma1, 'sigma1'), _square_f64(sigma2, 'sigma2')
+    mu1, mu2 = _dev(mu1, 'mu1', _F64), _dev(mu2, 'mu2', _F64)
+    n = sigma1.shape[0]
+    if sigma2.shape != sigma1.shape or mu1.shape != (n,) or mu2.shape != (n,):
+        raise ValueError('mu must be (%d,) and sigma (%d, %d) for both sets' % (n, n, n))
+    block = JACOBI_BLOCK if block is None else block
+    npad = jacobi_padded_order(n, block)
+    g = _padded(sigma1, npad)
+    v, sweeps1 = _jacobi_solve(g, True, max_sweeps, block)
+    root = colnorm_f64(g, 2)
+    t = gemm_f64(v, _padded(sigma2, npad), row_scale=root)
+    bmat = gemm_f64(t, v, trans_b=True, col_scale=root)
+    _, sweeps2 = _jacobi_solve(bmat, False, max_sweeps, block)
+    ev = colnorm_f64(bmat, 0)
+    out = torch.empty(5, dtype=_F64, device=g.device)
+    check(lib().rw_frechet_finish_f64(_p(mu1), _p(mu2), _p(sigma1), _p(sigma2), _p(ev), n, npad, _p(out), _stream()))
+    sums = out.tolist()
+    if parts is not None:
+        parts.update(sweeps=(sweeps1, sweeps2), order=npad, block=block,
+                     sums=dict(zip(('d2', 'dmu2', 'tr1', 'tr2', 'tr_sqrt'), sums)))
+    return sums[0]

@@ -80,18 +80,53 @@ class FeatureStatistics:
         self.count = int(round(packed[-1].item()))
         return self
 
-    def mean_cov(self):
+    def mean_cov(self, device=False):
         """(mu, sigma) as numpy float64, sigma unbiased like numpy.cov(act, rowvar=False)
-        (metrics/fid.py:60-61)."""
+        (metrics/fid.py:60-61).  ``device=True``: the same two as float64 tensors where the sums live -- what
+        ``frechet_distance`` takes without a round trip through the host."""
         n = self.count
         mu = self.sum / n
         sigma = (self.outer - n * torch.outer(mu, mu)) / (n - 1)
+        if device:
+            return mu, sigma
         return mu.cpu().numpy(), sigma.cpu().numpy()
 
 
-def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+def _frechet_distance_device(mu1, sigma1, mu2, sigma2, device):
+    """The inputs as contiguous float64 tensors on ``device`` (or on the device the tensors among them share), then
+    hip.frechet_distance_f64."""
+    tensors = [t for t in (mu1, sigma1, mu2, sigma2) if isinstance(t, torch.Tensor)]
+    if device is None:
+        devices = {t.device for t in tensors}
+        if len(devices) != 1:
+            raise ValueError('the inputs are on %s: pass device=' % sorted(str(d) for d in devices))
+        device = devices.pop()
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('rewriting_amd: frechet_distance(device=%s): the HIP kernels need a GPU (there is no CPU '
+                           'fallback); leave device=None for the host route' % device)
+
+    def put(x, dims):
+        x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(numpy.asarray(x, dtype=numpy.float64))
+        x = x.to(device=device, dtype=torch.float64)
+        x = x.reshape((1,) * (dims - x.dim()) + tuple(x.shape)) if x.dim() < dims else x     # atleast_1d / atleast_2d
+        return x.contiguous()
+    mu1, mu2, sigma1, sigma2 = put(mu1, 1), put(mu2, 1), put(sigma1, 2), put(sigma2, 2)
+    assert mu1.shape == mu2.shape and sigma1.shape == sigma2.shape
+    return hip.frechet_distance_f64(mu1, sigma1, mu2, sigma2)
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6, device=None):
     """d^2 = |mu1-mu2|^2 + Tr(S1 + S2 - 2 sqrt(S1 S2)) with the reference's singular-product retry and
-    imaginary-part check (metrics/fid.py:137-187)."""
+    imaginary-part check (metrics/fid.py:137-187).
+
+    With ``device=None`` and host inputs this is the scipy route, unchanged.  With device tensors, or with ``device=``
+    given, the distance is computed on the device (hip.frechet_distance_f64: Tr sqrt(S1 S2) as the sum of the square
+    roots of the eigenvalues of F^T S2 F, S1 = F F^T, by two block Jacobi solves) and returned as a Python float with
+    one copy to the host.  ``eps`` and the imaginary-part check have no counterpart there: the eigenvalues are column
+    norms, so the value is real and finite by construction for finite input, singular products included."""
+    if device is not None or any(isinstance(t, torch.Tensor) and t.is_cuda for t in (mu1, sigma1, mu2, sigma2)):
+        return _frechet_distance_device(mu1, sigma1, mu2, sigma2, device)
     from scipy import linalg
     mu1, mu2 = numpy.atleast_1d(mu1), numpy.atleast_1d(mu2)
     sigma1, sigma2 = numpy.atleast_2d(sigma1), numpy.atleast_2d(sigma2)
