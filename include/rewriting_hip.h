@@ -1071,6 +1071,57 @@ int rw_gemm_f64(const double* a, const double* b, double* c, int m, int n, int k
 int rw_frechet_finish_f64(const double* mu1, const double* mu2, const double* s1, const double* s2, const double* ev,
                           int n, int n_ev, double* out, rw_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The Inception-v3 pool3 features of the FID row (metrics/fid.py:67-84,90-131: the activations of pool_3 that
+ * calculate_activation_statistics, :40-62, reduces; :190-193: the images clamped on their way in).  rewriting_amd/inception.py
+ * walks the network over these four entries.  float32, NCHW, contiguous, on the caller's stream; no atomics, no memsets,
+ * every sum in a fixed order: two runs give the same bits.  A shape an entry does not take is refused before any launch,
+ * never clamped.  They join at ABI 11 like the entries before them: added only, no existing call changes.
+ * ------------------------------------------------------------------------------------- */
+
+/* Floats of the packed form of a (out_ch, in_ch, kh, kw) weight: K = in_ch kh kw rounded up to 16 times out_ch rounded up to
+ * 64; 0 for a shape the convolution refuses (kh or kw outside 1 .. 7, an extent < 1). */
+long long rw_conv2d_packed_weight_elems(int out_ch, int in_ch, int kh, int kw);
+
+/* wp[k][m] = weight[m][k], k = (channel, tap row, tap column) as stored, zero in the padding: what rw_conv2d_f32 reads
+ * with 16-byte loads and no bound.  Once per weight version (the batch-norm fold of metrics/fid.py:31-37's frozen graph is
+ * the host's, before this). */
+int rw_pack_conv2d_weight_f32(const float* weight, float* wp, int out_ch, int in_ch, int kh, int kw, rw_stream_t stream);
+
+/* y[:, c_off : c_off + out_ch] = act(conv2d(x, weight, stride, padding (ph, pw)) + bias) for x (batch, in_ch, h, w) and y
+ * (batch, c_total, oh, ow), oh = (h + 2 ph - kh) / stride + 1: the convolutions of the pool_3 graph (metrics/fid.py:67-84),
+ * whose blocks concatenate by writing their slice.  wp from rw_pack_conv2d_weight_f32, 16-byte aligned; bias (out_ch)
+ * nullable; relu 0 / 1.  An implicit GEMM over K = in_ch kh kw on v_mfma_f32_32x32x2_f32 -- exact f32 products, chains of
+ * 64 products from zero added to the total in ascending k; ragged out_ch, positions and K are masked, a tap outside the
+ * map is an exact zero and reads nothing.  The other channels of y are not touched.  y must not overlap x.
+ * RW_ERR_BAD_ARGUMENT (nothing launched): a null x / wp / y, an extent < 1, a slice outside 0 .. c_total.
+ * RW_ERR_UNSUPPORTED (nothing launched): kh or kw > 7, a stride outside {1, 2}, ph >= kh or pw >= kw or negative, a map
+ * smaller than the kernel, wp not 16-byte aligned, batch oh ow or h w above 2^30, out_ch above 64 x 65535. */
+int rw_conv2d_f32(const float* x, const float* wp, const float* bias, float* y, int batch, int in_ch, int h, int w,
+                  int out_ch, int kh, int kw, int stride, int ph, int pw, int relu, int c_off, int c_total,
+                  rw_stream_t stream);
+
+/* The 3 x 3 poolings of the pool_3 graph (metrics/fid.py:67-84) into y[:, c_off : c_off + ch] of (batch, c_total, oh, ow).
+ * mode 0: max, stride 2, no padding, oh = (h - 3) / 2 + 1 (RW_ERR_UNSUPPORTED for h or w < 3); mode 1: average, stride 1,
+ * pad 1, divided by the number of taps inside the map (count_include_pad=False, the FID graph's variant); mode 2: max,
+ * stride 1, pad 1.  A padded tap is never looked at: an all-negative window stays negative.  Taps in ascending (row,
+ * column) order. */
+int rw_pool3x3_f32(const float* x, float* y, int batch, int ch, int h, int w, int mode, int c_off, int c_total,
+                   rw_stream_t stream);
+
+/* y (batch, ch) = the mean of every h x w map of x: pool_3 itself (metrics/fid.py:69-70).  One wave per map, lane l sums the
+ * elements l, l + 64, ... and the lanes are added by a fixed butterfly, in double, rounded once.  RW_ERR_UNSUPPORTED: h w
+ * above 2^24. */
+int rw_global_avgpool_f32(const float* x, float* y, int batch, int ch, int h, int w, rw_stream_t stream);
+
+/* y (batch, 3, out_h, out_w) = the network's input from images: float (batch, 3, in_h, in_w) clamped to [-1, 1]
+ * (metrics/fid.py:190-193, pt_to_np) when is_bytes == 0, bytes (batch, in_h, in_w, 3) mapped by x / 127.5 - 1 otherwise (what
+ * rw_render_bytes_f32 and rw_png_unfilter_u8 leave).  Resized with the arithmetic of F.interpolate(mode='bilinear',
+ * align_corners=False): source coordinate (d + 0.5) in / out - 0.5 clamped at 0, no antialiasing -- NOT the Pillow tables of
+ * rw_resize_bilinear_u8.  An image of the output's size passes through with the same bits. */
+int rw_inception_input_f32(const void* images, float* y, int batch, int in_h, int in_w, int out_h, int out_w, int is_bytes,
+                           rw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

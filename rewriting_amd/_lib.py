@@ -258,6 +258,13 @@ SIGNATURES = {
     'rw_gemm_f64': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                             c_void_p]),
     'rw_frechet_finish_f64': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]),
+    # the Inception-v3 pool3 features (rw_inception.hip): general convolution, 3x3 poolings, global average, the input
+    'rw_conv2d_packed_weight_elems': (ctypes.c_longlong, [c_int] * 4),
+    'rw_pack_conv2d_weight_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    'rw_conv2d_f32': (c_int, [c_void_p] * 4 + [c_int] * 13 + [c_void_p]),
+    'rw_pool3x3_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    'rw_global_avgpool_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    'rw_inception_input_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
 }
 
 _lib = None

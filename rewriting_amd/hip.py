@@ -1896,3 +1896,139 @@ def frechet_distance_f64(mu1, sigma1, mu2, sigma2, max_sweeps=JACOBI_MAX_SWEEPS,
         parts.update(sweeps=(sweeps1, sweeps2), order=npad, block=block,
                      sums=dict(zip(('d2', 'dmu2', 'tr1', 'tr2', 'tr_sqrt'), sums)))
     return sums[0]
+
+
+# ------------------------------------------------------------------ the Inception-v3 pool3 features (inception.py)
+CONV2D_MAX_TAP = 7              # IC_MAX_TAP of rw_inception.hip
+POOL_MODES = {'max_s2': 0, 'avg': 1, 'max_s1': 2}
+
+
+def _pair(v, name):
+    """(a, b) of an int or a pair of ints."""
+    if isinstance(v, int):
+        return v, v
+    if len(v) != 2 or not all(isinstance(e, int) for e in v):
+        raise ValueError('%s must be an int or a pair of ints, not %r' % (name, v))
+    return int(v[0]), int(v[1])
+
+
+def _slice_out(out, c_off, b, ch, oh, ow, like):
+    """(the tensor written, c_off, c_total) of a result of `ch` channels: a new (b, ch, oh, ow) tensor, or the channels
+    [c_off, c_off + ch) of ``out`` (b, c_total, oh, ow), which is written where it lies."""
+    if out is None:
+        if c_off:
+            raise ValueError('c_off=%d needs the tensor it counts in: pass out=' % c_off)
+        return torch.empty(b, ch, oh, ow, device=like.device, dtype=torch.float32), 0, ch
+    out = _in_place(out, 'out', device=like.device)
+    if out.dim() != 4 or out.shape[0] != b or tuple(out.shape[2:]) != (oh, ow):
+        raise ValueError('out must be (%d, c_total, %d, %d), not %s' % (b, oh, ow, tuple(out.shape)))
+    if not isinstance(c_off, int) or c_off < 0 or c_off + ch > out.shape[1]:
+        raise ValueError('c_off=%r: channels [c_off, c_off + %d) do not lie in out\'s %d' % (c_off, ch, out.shape[1]))
+    return out, c_off, out.shape[1]
+
+
+def conv2d_out_size(h, w, kernel, stride, padding):
+    """(oh, ow) of conv2d, after the checks rw_conv2d_f32 makes of the kernel, the stride and the padding."""
+    (kh, kw), (ph, pw) = kernel, padding
+    if not (1 <= kh <= CONV2D_MAX_TAP and 1 <= kw <= CONV2D_MAX_TAP):
+        raise ValueError('the kernel must be within %d x %d, not %d x %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
+                         % (CONV2D_MAX_TAP, CONV2D_MAX_TAP, kh, kw))
+    if stride not in (1, 2):
+        raise ValueError('stride must be 1 or 2, not %r' % (stride,))
+    if not (0 <= ph < kh and 0 <= pw < kw):
+        raise ValueError('padding must be below the kernel (%d, %d), not (%d, %d)' % (kh, kw, ph, pw))
+    if h + 2 * ph < kh or w + 2 * pw < kw:
+        raise ValueError('fmap of %d x %d is smaller than the kernel %d x %d with padding (%d, %d)' % (h, w, kh, kw, ph, pw))
+    return (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
+
+
+def conv2d_pack_weight(weight):
+    """The packed form of a (out_ch, in_ch, kh, kw) weight that ``conv2d`` reads (rw_pack_conv2d_weight_f32); once per
+    weight version."""
+    weight = _dev(weight, 'weight')
+    if weight.dim() != 4 or 0 in weight.shape:
+        raise ValueError('weight must be a non-empty (out_ch, in_ch, kh, kw), not %s' % (tuple(weight.shape),))
+    o, i, kh, kw = weight.shape
+    n = lib().rw_conv2d_packed_weight_elems(o, i, kh, kw)
+    if n <= 0:
+        raise ValueError('weight %s: the kernel must be within %d x %d (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
+                         % (tuple(weight.shape), CONV2D_MAX_TAP, CONV2D_MAX_TAP))
+    wp = torch.empty(n, device=weight.device, dtype=torch.float32)
+    check(lib().rw_pack_conv2d_weight_f32(_p(weight), _p(wp), o, i, kh, kw, _stream()))
+    return wp
+
+
+def conv2d(x, wp, weight_shape, bias=None, stride=1, padding=0, relu=False, out=None, c_off=0):
+    """act(F.conv2d(x, weight, bias, stride, padding)) -- rw_conv2d_f32.  wp = conv2d_pack_weight(weight), weight_shape
+    the (out_ch, in_ch, kh, kw) it was packed from; padding an int or (ph, pw).  With ``out=`` (B, c_total, oh, ow) the
+    result is written to its channels [c_off, c_off + out_ch) and ``out`` is returned; its other channels are not touched."""
+    x = _fmap4(x, 'fmap')
+    wp = _dev(wp, 'packed weight')
+    o, i, kh, kw = (int(e) for e in weight_shape)
+    ph, pw = _pair(padding, 'padding')
+    b, c, h, w = x.shape
+    if c != i:
+        raise ValueError('fmap has %d channels, the weight takes %d' % (c, i))
+    oh, ow = conv2d_out_size(h, w, (kh, kw), stride, (ph, pw))
+    if wp.device != x.device or wp.numel() != lib().rw_conv2d_packed_weight_elems(o, i, kh, kw):
+        raise ValueError('packed weight of %d floats on %s does not belong to a weight %s on %s'
+                         % (wp.numel(), wp.device, (o, i, kh, kw), x.device))
+    bias = _opt(bias, 'bias')
+    if bias is not None and (tuple(bias.shape) != (o,) or bias.device != x.device):
+        raise ValueError('bias must have one value per out-channel (%d) on %s, not %s on %s'
+                         % (o, x.device, tuple(bias.shape), bias.device))
+    y, c_off, c_total = _slice_out(out, c_off, b, o, oh, ow, x)
+    check(lib().rw_conv2d_f32(_p(x), _p(wp), _p(bias), _p(y), b, i, h, w, o, kh, kw, int(stride), ph, pw, int(bool(relu)),
+                              c_off, c_total, _stream()))
+    return y if out is None else out
+
+
+def pool3x3(x, mode, out=None, c_off=0):
+    """The 3x3 poolings of the Inception graph (rw_pool3x3_f32).  mode 'max_s2' (0): max_pool2d(x, 3, 2); 'avg' (1):
+    avg_pool2d(x, 3, 1, 1, count_include_pad=False); 'max_s1' (2): max_pool2d(x, 3, 1, 1).  ``out=`` / ``c_off=`` as in
+    ``conv2d``."""
+    x = _fmap4(x, 'fmap')
+    mode = POOL_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('mode must be one of %s or 0 / 1 / 2, not %r' % (sorted(POOL_MODES), mode))
+    b, c, h, w = x.shape
+    if mode == 0 and (h < 3 or w < 3):
+        raise ValueError('fmap of %d x %d has no 3 x 3 window' % (h, w))
+    oh, ow = ((h - 3) // 2 + 1, (w - 3) // 2 + 1) if mode == 0 else (h, w)
+    y, c_off, c_total = _slice_out(out, c_off, b, c, oh, ow, x)
+    check(lib().rw_pool3x3_f32(_p(x), _p(y), b, c, h, w, mode, c_off, c_total, _stream()))
+    return y if out is None else out
+
+
+def global_avgpool(x):
+    """(B, C) means of the maps of x (B, C, H, W) -- rw_global_avgpool_f32."""
+    x = _fmap4(x, 'fmap')
+    b, c, h, w = x.shape
+    y = torch.empty(b, c, device=x.device, dtype=torch.float32)
+    check(lib().rw_global_avgpool_f32(_p(x), _p(y), b, c, h, w, _stream()))
+    return y
+
+
+INCEPTION_SIZE = 299
+
+
+def inception_input(images, size=INCEPTION_SIZE):
+    """The Inception network's input (B, 3, oh, ow) float32 (rw_inception_input_f32) from ``images``: float32 (B, 3, H, W),
+    clamped to [-1, 1], or uint8 (B, H, W, 3) -- what render_bytes / png_decode yield -- mapped by x / 127.5 - 1; resized
+    like F.interpolate(mode='bilinear', align_corners=False) to ``size`` (an int or (oh, ow)), or kept at its size with
+    ``size=None``."""
+    if not isinstance(images, torch.Tensor):
+        raise TypeError('images must be a torch.Tensor')
+    is_bytes = images.dtype == torch.uint8
+    images = _dev(images, 'images', torch.uint8 if is_bytes else torch.float32)
+    if images.dim() != 4 or 0 in images.shape or images.shape[3 if is_bytes else 1] != 3:
+        raise ValueError('images must be float32 (B, 3, H, W) or uint8 (B, H, W, 3), not %s %s'
+                         % (images.dtype, tuple(images.shape)))
+    b = images.shape[0]
+    h, w = (images.shape[1], images.shape[2]) if is_bytes else (images.shape[2], images.shape[3])
+    oh, ow = (h, w) if size is None else _pair(size, 'size')
+    if oh < 1 or ow < 1:
+        raise ValueError('size must be positive, not %r' % (size,))
+    y = torch.empty(b, 3, oh, ow, device=images.device, dtype=torch.float32)
+    check(lib().rw_inception_input_f32(_p(images), _p(y), b, h, w, oh, ow, int(is_bytes), _stream()))
+    return y

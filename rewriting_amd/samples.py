@@ -1,8 +1,10 @@
 """Sample-set generation and Frechet statistics -- the "next" rows SURVEY.md section 8f.3 marks
 after the hot path: sharded per-seed generator passes (metrics/sample.py:32-37,
 metrics/sample_edited.py:55-59) and the reduction + distance of metrics/fid.py:40-62,137-187.
-The feature extractor stays pluggable (the reference's TF Inception graph is downloaded at run
-time and is unavailable here): any callable images -> (B, F) features.
+The feature extractor stays pluggable: any callable images -> (B, F) features.  The one that ships
+is ``inception.FIDInception`` (the pool3 features of the reference's Inception graph, on the HIP
+kernels; its weights are the caller's file); ``activation_statistics`` runs an extractor over image
+batches and ``fid`` takes two sets of statistics to their distance without leaving the device.
 """
 import warnings
 
@@ -38,13 +40,21 @@ def generate(model_fn, model, seeds, batch=32, offset=0, device=None, shard=None
 
 class FeatureStatistics:
     """Running sum f and sum f f^T of feature rows, kept in float64; ``allreduce_`` pools the raw sums
-    of all ranks with one RCCL all-reduce (F=2048: 33.5 MB)."""
+    of all ranks with one RCCL all-reduce (F=2048: 33.5 MB).
 
-    def __init__(self, dim=None):
+    ``exact=True`` (opt-in; ``activation_statistics`` takes it): device features are widened to float64 before their
+    products, and a batch's f^T f is ``hip.gemm_f64`` (the f64 MFMA) instead of the fp32 MFMA block.  The fp32 block
+    rounds every entry to 2^-24 of |f|^2, which is noise of that size in every eigenvalue of the covariance -- harmless
+    for a full-rank set, but a set with fewer samples than features has a thousand eigenvalues that should be zero, and
+    the matrix square root of the Frechet distance sees them: six 75 x 75 images against themselves gave d^2 = -3.6e-4
+    on Tr S = 1.76 through the fp32 block."""
+
+    def __init__(self, dim=None, exact=False):
         self.count = 0
         self.sum = None
         self.outer = None
         self._dim = dim
+        self.exact = bool(exact)
 
     def add(self, feats):
         feats = feats.detach()
@@ -54,7 +64,10 @@ class FeatureStatistics:
         if self.sum is None:
             self.sum = torch.zeros(f, dtype=torch.float64, device=feats.device)
             self.outer = torch.zeros(f, f, dtype=torch.float64, device=feats.device)
-        if hip.on_device(feats) and feats.dtype == torch.float32 and f % 4 == 0:
+        if hip.on_device(feats) and self.exact:
+            d = feats.double().contiguous()
+            self.outer += hip.gemm_f64(d, d, trans_a=True)                          # f64 MFMA, a fixed order
+        elif hip.on_device(feats) and feats.dtype == torch.float32 and f % 4 == 0:
             block = torch.zeros(f, f, dtype=torch.float32, device=feats.device)
             hip.second_moment_accumulate(block, feats.contiguous(), nchw=False)    # fp32 MFMA per batch
             self.outer += block.double()                                            # fp64 across batches
@@ -90,6 +103,30 @@ class FeatureStatistics:
         if device:
             return mu, sigma
         return mu.cpu().numpy(), sigma.cpu().numpy()
+
+
+def activation_statistics(batches, net):
+    """``fid.calculate_activation_statistics`` (metrics/fid.py:40-62) as running sums: every batch of ``batches`` -- an
+    iterable of image tensors, or of the (seeds, images) pairs ``generate`` yields -- goes through ``net`` (any callable
+    images -> (B, F) features, e.g. ``inception.FIDInception``) and its features into a ``FeatureStatistics(exact=True)``
+    -- float64 products, as numpy.cov of the reference's float64 activations has them -- which is returned.  Images,
+    features and sums stay where ``net`` leaves them."""
+    stats = FeatureStatistics(exact=True)
+    with torch.no_grad():
+        for batch in batches:
+            images = batch[1] if isinstance(batch, (tuple, list)) else batch
+            stats.add(net(images))
+    if stats.count == 0:
+        raise ValueError('activation_statistics: no batch of images')
+    return stats
+
+
+def fid(stats_a, stats_b):
+    """The Frechet distance of two ``FeatureStatistics`` on the device their sums live on: ``mean_cov(device=True)`` of
+    both, then ``frechet_distance`` there (metrics/fid.py:196-210 behind the activations)."""
+    mu_a, sigma_a = stats_a.mean_cov(device=True)
+    mu_b, sigma_b = stats_b.mean_cov(device=True)
+    return frechet_distance(mu_a, sigma_a, mu_b, sigma_b, device=mu_a.device)
 
 
 def _frechet_distance_device(mu1, sigma1, mu2, sigma2, device):
