@@ -1122,6 +1122,71 @@ int rw_global_avgpool_f32(const float* x, float* y, int batch, int ch, int h, in
 int rw_inception_input_f32(const void* images, float* y, int batch, int in_h, int in_w, int out_h, int out_w, int is_bytes,
                            rw_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The face-parsing BiSeNet of the edit-distance rows for faces (metrics/load_seg.py:11-35 FaceSegementer.segment_batch;
+ * metrics/face-parsing.PyTorch/model.py, resnet.py) and the "pixels correctly modified" count of
+ * metrics/seg_correct_mod.py:40-65.  rewriting_amd/faceparse.py walks the network over rw_conv2d_f32, rw_global_avgpool_f32
+ * and these entries.  float32, NCHW, contiguous, on the caller's stream; no atomics, no memsets, every sum in a fixed order:
+ * two runs give the same bits.  A shape an entry does not take is refused before any launch, never clamped; an INDEX read
+ * from a table is clamped into the map it addresses, so that a wrong table gives a wrong picture and never a read outside
+ * it.  They join at ABI 11 like the entries before them: added only, no existing call changes.
+ * ------------------------------------------------------------------------------------- */
+
+/* y = act((conv2d(x) + bias) + res) with res and y (batch, out_ch, oh, ow): the tail of a BasicBlock (resnet.py:36-48).
+ * rw_conv2d_f32's kernel, sums and refusals (its c_off = 0, c_total = out_ch); the sum in k, then + bias, then + res, then
+ * the ReLU.  y may be res itself (every element is read and then written by the same thread); y must not overlap x.
+ * RW_ERR_BAD_ARGUMENT: a null res (rw_conv2d_f32 is the form without one). */
+int rw_conv2d_add_f32(const float* x, const float* wp, const float* bias, const float* res, float* y, int batch, int in_ch,
+                      int h, int w, int out_ch, int kh, int kw, int stride, int ph, int pw, int relu, rw_stream_t stream);
+
+/* y (batch, ch, oh, ow) = F.max_pool2d(x, 3, 2, 1), oh = (h - 1) / 2 + 1: the pooling of the ResNet stem (resnet.py:64,74),
+ * any h, w >= 1.  A padded tap is never looked at: an all-negative window stays negative.  RW_ERR_UNSUPPORTED: h or w above
+ * 2^20. */
+int rw_maxpool3x3s2p1_f32(const float* x, float* y, int batch, int ch, int h, int w, rw_stream_t stream);
+
+/* y[b, c, oy, ox] = x[b, c, r, q] s + a with r = row[oy], q = col[ox]: every element-wise step of the context path and the
+ * fusion module (model.py:76-83 the gate of an attention-refinement module, :111-122 its sum with the pooled vector or the
+ * coarser map and the nearest-neighbour step to the next size, :203-209 feat atten + feat) and the image's nearest-neighbour
+ * resize to the working size (load_seg.py:27).  x (batch, ch, h, w), y (batch, ch, oh, ow).
+ *   row (oh), col (ow): int32 nearest-neighbour tables made by the host; a null table keeps that axis' index and needs
+ *     oh == h (ow == w).  Entries are clamped into the map.
+ *   s = 1 / (1 + expf(-gate[b, c])), gate (batch, ch); a null gate: no multiply at all.
+ *   a = add_map[b, c, r, q] (a map of x's size; it may be x) or add_vec[b, c] or, both null, nothing.
+ * The product is rounded, then the sum (torch's mul followed by add; no fused multiply-add).  With gate and both adds null it
+ * is a gather and equals F.interpolate(x, size) of float32 bit for bit.  Columns that keep their index, w a multiple of 4 and
+ * 16-byte aligned pointers take 16-byte accesses.  y must not overlap x or add_map.
+ * RW_ERR_BAD_ARGUMENT: add_map and add_vec both given; a null table on an axis that changes its size.
+ * RW_ERR_UNSUPPORTED: a side above 2^20, a map above 2^30 elements, batch ch above 2^31 - 1. */
+int rw_gate_resample_f32(const float* x, const float* gate, const float* add_map, const float* add_vec, const int* row,
+                         const int* col, float* y, int batch, int ch, int h, int w, int oh, int ow, rw_stream_t stream);
+
+/* y (batch, ch, oh, ow) = F.interpolate(x, (oh, ow), mode='bilinear', align_corners=True) (model.py:251).  idx int32
+ * (2 oh + 2 ow): the rows' i0, the rows' i1, the columns' i0, the columns' i1; lam float32 (oh + ow): the rows', the
+ * columns' -- made by the host (faceparse.align_corners_table), laid out as rw_lpips_combine_f32 reads its own.  The value is
+ * (1 - lr) ((1 - lc) v00 + lc v01) + lr ((1 - lc) v10 + lc v11), every product and sum rounded on its own.  A map of the
+ * output's size passes through bit for bit. */
+int rw_bilinear_ac_f32(const float* x, float* y, int batch, int ch, int h, int w, int oh, int ow, const int* idx,
+                       const float* lam, rw_stream_t stream);
+
+/* labels (batch, 1, OH, OW) int64: at each pixel the lowest class index that attains the maximum of the n samples
+ * rw_bilinear_ac_f32 would take of logits (batch, n, h, w) at the working-size pixel (pick_row[oy], pick_col[ox]) of its
+ * (H, W) output -- the argmax(0) of load_seg.py:30-31 followed by the nearest-neighbour F.interpolate(masks, og_size).long()
+ * of :33-34, without the (n, H, W) scores in memory; the same device function forms the sample, so the labels equal the
+ * arg-max of that entry's output bit for bit.  idx, lam: that entry's tables for (h, w) -> (H, W); pick_row (OH), pick_col
+ * (OW): int32 nearest tables, a null one needs OH == H (OW == W).  A NaN wins, the first one first, as in numpy.argmax.
+ * RW_ERR_UNSUPPORTED: n above 64. */
+int rw_seg_labels_i64(const float* logits, long long* labels, int batch, int n, int h, int w, int H, int W, const int* idx,
+                      const float* lam, const int* pick_row, const int* pick_col, int OH, int OW, rw_stream_t stream);
+
+/* out (batch, 2) int64 = (total, count) of seg_correct_mod.py:51-62 per image: count = the pixels whose `before` label is one
+ * of src, total = those of them whose `after` label is one of tgt.  before, after: int64 device maps of hw labels per image,
+ * image b at before + b before_stride (elements) -- a channel of a (B, C, H, W) tensor without a copy.  src (n_src), tgt
+ * (n_tgt): HOST arrays of 1 .. 16 int64 labels each, copied into the launch.  One workgroup per image, integer sums.
+ * RW_ERR_BAD_ARGUMENT: a null pointer, an empty set, a stride below hw.  RW_ERR_UNSUPPORTED: a set above 16 labels. */
+int rw_seg_correct_counts_i64(const long long* before, const long long* after, int batch, long long hw,
+                              long long before_stride, long long after_stride, const long long* src, int n_src,
+                              const long long* tgt, int n_tgt, long long* out, rw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,14 @@ SIGNATURES = {
     'rw_pool3x3_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     'rw_global_avgpool_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     'rw_inception_input_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    # the face-parsing BiSeNet and the segmentation counts (rw_faceparse.hip; the residual convolution: rw_inception.hip)
+    'rw_conv2d_add_f32': (c_int, [c_void_p] * 5 + [c_int] * 11 + [c_void_p]),
+    'rw_maxpool3x3s2p1_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    'rw_gate_resample_f32': (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p]),
+    'rw_bilinear_ac_f32': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p]),
+    'rw_seg_labels_i64': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    'rw_seg_correct_counts_i64': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, POINTER(c_int64), c_int,
+                                          POINTER(c_int64), c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

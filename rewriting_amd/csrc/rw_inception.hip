@@ -20,7 +20,9 @@
 // about 1.5e-6 of the result.  Here a chain runs over IC_KB = 4 chunks (64 products) from zero and is then added to the
 // total -- two levels, both in ascending k, the same order in every run: about 3e-7 at K = 4032 by the same estimate
 // (DESIGN.md section 8.11).  No atomics, no memsets, no split over workgroups.
-// Epilogue: + bias[m], optional ReLU, stored to channel c_off + m of an output with c_total channels.
+// Epilogue: + bias[m], then + res (the shortcut of a residual block, face-parsing.PyTorch/resnet.py:36-48; nullable), optional
+// ReLU, stored to channel c_off + m of an output with c_total channels.  res has the output's own layout and may be the
+// output itself: every element is read and then written by the same thread.
 #include <math.h>
 #include "rw_common.h"
 
@@ -34,6 +36,7 @@ struct ic_conv_problem {
   const float* x;
   const float* wp;
   const float* bias;
+  const float* res;          // nullable: added after the bias, before the ReLU; indexed as y is
   float* y;
   int in_ch, h, w, out_ch, kh, kw, stride, ph, pw, oh, ow, relu, c_off, c_total;
   int K, Kp, Mp, N;
@@ -114,12 +117,14 @@ template <int NT> __global__ void __launch_bounds__(256) conv2d_f32_kernel(ic_co
     const int n = n0 + wn * 32 * NT + 32 * j + (lane & 31);
     if (n >= p.N) continue;
     const int b = n / ohw, pos = n - b * ohw;
-    float* yb = p.y + ((int64_t)b * p.c_total + p.c_off) * ohw + pos;
+    const int64_t yo = ((int64_t)b * p.c_total + p.c_off) * ohw + pos;
+    float* yb = p.y + yo;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + wm * 32 + rw_mfma32_row(r, lane >> 5);
       if (m >= p.out_ch) continue;
       float v = acc[j][r] + (p.bias ? p.bias[m] : 0.f);
+      if (p.res) v += p.res[yo + (int64_t)m * ohw];
       if (p.relu) v = fmaxf(v, 0.f);
       yb[(int64_t)m * ohw] = v;
     }
@@ -156,9 +161,9 @@ extern "C" int rw_pack_conv2d_weight_f32(const float* weight, float* wp, int out
   return RW_LAUNCH_RESULT();
 }
 
-extern "C" int rw_conv2d_f32(const float* x, const float* wp, const float* bias, float* y, int batch, int in_ch, int h,
-                             int w, int out_ch, int kh, int kw, int stride, int ph, int pw, int relu, int c_off,
-                             int c_total, rw_stream_t stream) {
+static int ic_conv2d(const float* x, const float* wp, const float* bias, const float* res, float* y, int batch, int in_ch,
+                     int h, int w, int out_ch, int kh, int kw, int stride, int ph, int pw, int relu, int c_off, int c_total,
+                     rw_stream_t stream) {
   RW_CHECK_ARG(x && wp && y && batch >= 1 && h >= 1 && w >= 1);
   RW_CHECK_ARG(out_ch >= 1 && in_ch >= 1 && kh >= 1 && kw >= 1);
   RW_CHECK_ARG(c_off >= 0 && c_total >= 1 && (int64_t)c_off + out_ch <= c_total);
@@ -171,7 +176,7 @@ extern "C" int rw_conv2d_f32(const float* x, const float* wp, const float* bias,
   const int64_t N = (int64_t)batch * oh * ow;
   if (N > (1 << 30) || (int64_t)h * w > (1 << 30)) return RW_ERR_UNSUPPORTED;  // positions and a plane in 31 bits
   ic_conv_problem p;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y;
+  p.x = x; p.wp = wp; p.bias = bias; p.res = res; p.y = y;
   p.in_ch = in_ch; p.h = h; p.w = w; p.out_ch = out_ch; p.kh = kh; p.kw = kw; p.stride = stride; p.ph = ph; p.pw = pw;
   p.oh = oh; p.ow = ow; p.relu = relu ? 1 : 0; p.c_off = c_off; p.c_total = c_total;
   p.K = in_ch * kh * kw;
@@ -186,6 +191,20 @@ extern "C" int rw_conv2d_f32(const float* x, const float* wp, const float* bias,
   else
     conv2d_f32_kernel<1><<<dim3((unsigned)rw_cdiv(N, 64), (unsigned)m_tiles), 256, 0, rw_s(stream)>>>(p);
   return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_conv2d_f32(const float* x, const float* wp, const float* bias, float* y, int batch, int in_ch, int h,
+                             int w, int out_ch, int kh, int kw, int stride, int ph, int pw, int relu, int c_off,
+                             int c_total, rw_stream_t stream) {
+  return ic_conv2d(x, wp, bias, nullptr, y, batch, in_ch, h, w, out_ch, kh, kw, stride, ph, pw, relu, c_off, c_total, stream);
+}
+
+// y = act((conv + bias) + res): the tail of a BasicBlock (face-parsing.PyTorch/resnet.py:36-48); res and y (batch, out_ch, oh, ow)
+extern "C" int rw_conv2d_add_f32(const float* x, const float* wp, const float* bias, const float* res, float* y, int batch,
+                                 int in_ch, int h, int w, int out_ch, int kh, int kw, int stride, int ph, int pw, int relu,
+                                 rw_stream_t stream) {
+  RW_CHECK_ARG(res);
+  return ic_conv2d(x, wp, bias, res, y, batch, in_ch, h, w, out_ch, kh, kw, stride, ph, pw, relu, 0, out_ch, stream);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -10,7 +10,9 @@ Three modes, named as the reference's command line names them:
 
 ``edit_distance`` takes device tensors and a whole batch at once, where the reference loops image by image (the images of a
 batch do not interact); ``compute_dl`` walks two directories of PNG files and one of segmentations, as the reference does,
-and returns its ``(total, count)``.
+and returns its ``(total, count)`` -- or, given a ``segmenter`` (faceparse.FaceSegmenter), segments the `before` images on
+the device instead of reading a directory.  ``correct_modification`` is the "pixels correctly modified" count of
+metrics/seg_correct_mod.py:40-65 over two batches of label maps.
 """
 import os
 
@@ -66,13 +68,18 @@ def _load_image(path):
 
 
 def compute_dl(before_dir, after_dir, seg_dir, indices, src=(1708,), srcc=2, mode='lpips', batch_size=100, net=None,
-               device='cuda', name_template='{}.png', device_decode=False):
+               device='cuda', name_template='{}.png', device_decode=False, segmenter=None):
     """(total, count) of metrics/distances.py:96-136 over the pairs ``before_dir/<key>.png``, ``after_dir/<key>.png`` with the
     segmentations ``seg_dir/<key>.pth`` (a tensor whose row `srcc` is the (H, W) map) for key in indices -- `batch_size` pairs
     per device call.  total: the sum of the per-image distances (count: their number), or in 'pixel' mode the masked L1 sum
     (count: the masks' sum).  device_decode: the `before` and `after` files are decoded on the device (pngreader.read_batch,
     as_float) instead of by PIL, one file at a time, on the host; the images, and so (total, count), are the same bit for
-    bit.  The segmentations are torch.load'ed either way."""
+    bit.  The segmentations are torch.load'ed either way -- unless seg_dir is None and `segmenter` is given: then the
+    segmentation of a batch is ``segmenter.segment_batch(before)[:, srcc]`` on the device (faceparse.FaceSegmenter, the
+    reference's metrics/seg_stats.py run ahead of time; srcc=0 for faces).  Exactly one of seg_dir and segmenter is given."""
+    if (seg_dir is None) == (segmenter is None):
+        raise ValueError('rewriting_amd: compute_dl takes the segmentations from seg_dir (.pth files) or from segmenter '
+                         '(segment_batch on the device): pass exactly one of them, not %s' % ('both' if segmenter else 'neither'))
     if device_decode:
         from . import pngreader
 
@@ -87,8 +94,24 @@ def compute_dl(before_dir, after_dir, seg_dir, indices, src=(1708,), srcc=2, mod
     for start in range(0, len(keys), batch_size):
         chunk = keys[start:start + batch_size]
         before, after = load(before_dir, chunk), load(after_dir, chunk)
-        seg = torch.stack([torch.load(os.path.join(seg_dir, '%d.pth' % k), map_location='cpu')[srcc] for k in chunk]).to(device)
+        if segmenter is not None:
+            seg = segmenter.segment_batch(before)[:, srcc]
+        else:
+            seg = torch.stack([torch.load(os.path.join(seg_dir, '%d.pth' % k), map_location='cpu')[srcc] for k in chunk]).to(device)
         values, counts = edit_distance(before, after, seg, src, mode, net)
         total += values.double().sum().item()
         count += int(round(counts.double().sum().item()))
     return total, count
+
+
+def correct_modification(before_seg, after_seg, src, tgt, srcc=0, tgtc=0):
+    """(total, count), two Python ints, of metrics/seg_correct_mod.py:51-62 for one batch: count = the pixels whose label in
+    before_seg is one of ``src``, total = those of them whose label in after_seg is one of ``tgt``.  The maps are int64
+    (B, H, W) or (B, C, H, W) on the device, of which the channels srcc / tgtc are read; src and tgt name 1 .. 16 labels
+    each."""
+    for name, labels in (('src', src), ('tgt', tgt)):
+        if not 1 <= len(labels) <= hip.SEG_MAX_SET:
+            raise ValueError('rewriting_amd: correct_modification: %s must name 1 .. %d labels, not %d'
+                             % (name, hip.SEG_MAX_SET, len(labels)))
+    sums = hip.seg_correct_counts(before_seg, after_seg, src, tgt, srcc, tgtc).sum(0).tolist()
+    return int(sums[0]), int(sums[1])

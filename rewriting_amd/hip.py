@@ -1958,10 +1958,9 @@ def conv2d_pack_weight(weight):
     return wp
 
 
-def conv2d(x, wp, weight_shape, bias=None, stride=1, padding=0, relu=False, out=None, c_off=0):
-    """act(F.conv2d(x, weight, bias, stride, padding)) -- rw_conv2d_f32.  wp = conv2d_pack_weight(weight), weight_shape
-    the (out_ch, in_ch, kh, kw) it was packed from; padding an int or (ph, pw).  With ``out=`` (B, c_total, oh, ow) the
-    result is written to its channels [c_off, c_off + out_ch) and ``out`` is returned; its other channels are not touched."""
+def _conv2d_operands(x, wp, weight_shape, bias, stride, padding):
+    """(x, wp, bias, the shape arguments of rw_conv2d_f32 from batch to pw, (oh, ow)) after the checks conv2d and conv2d_add
+    share."""
     x = _fmap4(x, 'fmap')
     wp = _dev(wp, 'packed weight')
     o, i, kh, kw = (int(e) for e in weight_shape)
@@ -1969,7 +1968,7 @@ def conv2d(x, wp, weight_shape, bias=None, stride=1, padding=0, relu=False, out=
     b, c, h, w = x.shape
     if c != i:
         raise ValueError('fmap has %d channels, the weight takes %d' % (c, i))
-    oh, ow = conv2d_out_size(h, w, (kh, kw), stride, (ph, pw))
+    size = conv2d_out_size(h, w, (kh, kw), stride, (ph, pw))
     if wp.device != x.device or wp.numel() != lib().rw_conv2d_packed_weight_elems(o, i, kh, kw):
         raise ValueError('packed weight of %d floats on %s does not belong to a weight %s on %s'
                          % (wp.numel(), wp.device, (o, i, kh, kw), x.device))
@@ -1977,9 +1976,16 @@ def conv2d(x, wp, weight_shape, bias=None, stride=1, padding=0, relu=False, out=
     if bias is not None and (tuple(bias.shape) != (o,) or bias.device != x.device):
         raise ValueError('bias must have one value per out-channel (%d) on %s, not %s on %s'
                          % (o, x.device, tuple(bias.shape), bias.device))
-    y, c_off, c_total = _slice_out(out, c_off, b, o, oh, ow, x)
-    check(lib().rw_conv2d_f32(_p(x), _p(wp), _p(bias), _p(y), b, i, h, w, o, kh, kw, int(stride), ph, pw, int(bool(relu)),
-                              c_off, c_total, _stream()))
+    return x, wp, bias, (b, i, h, w, o, kh, kw, int(stride), ph, pw), size
+
+
+def conv2d(x, wp, weight_shape, bias=None, stride=1, padding=0, relu=False, out=None, c_off=0):
+    """act(F.conv2d(x, weight, bias, stride, padding)) -- rw_conv2d_f32.  wp = conv2d_pack_weight(weight), weight_shape
+    the (out_ch, in_ch, kh, kw) it was packed from; padding an int or (ph, pw).  With ``out=`` (B, c_total, oh, ow) the
+    result is written to its channels [c_off, c_off + out_ch) and ``out`` is returned; its other channels are not touched."""
+    x, wp, bias, shape, (oh, ow) = _conv2d_operands(x, wp, weight_shape, bias, stride, padding)
+    y, c_off, c_total = _slice_out(out, c_off, shape[0], shape[4], oh, ow, x)
+    check(lib().rw_conv2d_f32(_p(x), _p(wp), _p(bias), _p(y), *shape, int(bool(relu)), c_off, c_total, _stream()))
     return y if out is None else out
 
 
@@ -2032,3 +2038,163 @@ def inception_input(images, size=INCEPTION_SIZE):
     y = torch.empty(b, 3, oh, ow, device=images.device, dtype=torch.float32)
     check(lib().rw_inception_input_f32(_p(images), _p(y), b, h, w, oh, ow, int(is_bytes), _stream()))
     return y
+
+
+# ------------------------------------------------------------------ the face-parsing BiSeNet (faceparse.py) and the counts
+SEG_MAX_CLASSES = 64            # FP_MAX_CLASSES of rw_faceparse.hip
+SEG_MAX_SET = 16                # FP_MAX_SET
+
+
+def conv2d_add(x, wp, weight_shape, bias, res, stride=1, padding=0, relu=False, out=None):
+    """act((F.conv2d(x, weight, bias, stride, padding)) + res) -- rw_conv2d_add_f32, the tail of a residual block; the
+    operands of ``conv2d`` and res (B, out_ch, oh, ow).  ``out=`` is written where it lies and returned; it may be ``res``
+    itself."""
+    x, wp, bias, shape, (oh, ow) = _conv2d_operands(x, wp, weight_shape, bias, stride, padding)
+    res = _in_place(res, 'res', device=x.device)
+    want = (shape[0], shape[4], oh, ow)
+    if tuple(res.shape) != want:
+        raise ValueError('res must be %s, the shape of the convolution\'s output, not %s' % (want, tuple(res.shape)))
+    if out is None:
+        y = torch.empty(want, device=x.device, dtype=torch.float32)
+    else:
+        y = _in_place(out, 'out', device=x.device)
+        if tuple(y.shape) != want:
+            raise ValueError('out must be %s, not %s' % (want, tuple(y.shape)))
+    check(lib().rw_conv2d_add_f32(_p(x), _p(wp), _p(bias), _p(res), _p(y), *shape, int(bool(relu)), _stream()))
+    return y if out is None else out
+
+
+def maxpool3x3s2p1(x):
+    """F.max_pool2d(x, 3, 2, 1) -- rw_maxpool3x3s2p1_f32: (B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)."""
+    x = _fmap4(x, 'fmap')
+    b, c, h, w = x.shape
+    y = torch.empty(b, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1, device=x.device, dtype=torch.float32)
+    check(lib().rw_maxpool3x3s2p1_f32(_p(x), _p(y), b, c, h, w, _stream()))
+    return y
+
+
+def _index_table(t, n, name, device):
+    """an int32 (n,) table on `device`, or None"""
+    if t is None:
+        return None
+    t = _dev(t, name, torch.int32)
+    if tuple(t.shape) != (n,) or t.device != device:
+        raise ValueError('%s must be int32 (%d,) on %s, not %s on %s' % (name, n, device, tuple(t.shape), t.device))
+    return t
+
+
+def gate_resample(x, gate=None, add_map=None, add_vec=None, rows=None, cols=None):
+    """y[b, c, oy, ox] = x[b, c, rows[oy], cols[ox]] * sigmoid(gate[b, c]) + (add_map[b, c, rows[oy], cols[ox]] or
+    add_vec[b, c]) -- rw_gate_resample_f32.  rows / cols: int32 nearest-neighbour tables on x's device (faceparse.nearest_table),
+    their lengths the output's size; None keeps that axis.  gate, add_vec: (B, C) or (B, C, 1, 1); add_map: a map of x's
+    shape (it may be x); each of the three is optional, add_map and add_vec exclude each other.  With only tables it is
+    F.interpolate(x, size) (nearest), bit for bit."""
+    x = _fmap4(x, 'fmap')
+    b, c, h, w = x.shape
+
+    def per_channel(t, name):
+        t = _opt(t, name)
+        if t is not None and (t.numel() != b * c or tuple(t.shape[:2]) != (b, c) or t.device != x.device):
+            raise ValueError('%s must be (%d, %d) or (%d, %d, 1, 1) on %s, not %s on %s'
+                             % (name, b, c, b, c, x.device, tuple(t.shape), t.device))
+        return t
+    gate, add_vec = per_channel(gate, 'gate'), per_channel(add_vec, 'add_vec')
+    if add_map is not None and add_vec is not None:
+        raise ValueError('add_map and add_vec exclude each other (RW_ERR_BAD_ARGUMENT, include/rewriting_hip.h)')
+    add_map = _opt(add_map, 'add_map')
+    if add_map is not None and (add_map.shape != x.shape or add_map.device != x.device):
+        raise ValueError('add_map must be a map of the fmap\'s shape %s on %s, not %s on %s'
+                         % (tuple(x.shape), x.device, tuple(add_map.shape), add_map.device))
+    oh = h if rows is None else int(rows.numel()) if isinstance(rows, torch.Tensor) else -1
+    ow = w if cols is None else int(cols.numel()) if isinstance(cols, torch.Tensor) else -1
+    rows, cols = _index_table(rows, oh, 'rows', x.device), _index_table(cols, ow, 'cols', x.device)
+    if oh < 1 or ow < 1:
+        raise ValueError('rows and cols must not be empty')
+    y = torch.empty(b, c, oh, ow, device=x.device, dtype=torch.float32)
+    check(lib().rw_gate_resample_f32(_p(x), _p(gate), _p(add_map), _p(add_vec), _p(rows), _p(cols), _p(y), b, c, h, w, oh, ow,
+                                     _stream()))
+    return y
+
+
+def _ac_tables(idx, lam, oh, ow, device):
+    idx, lam = _dev(idx, 'idx', torch.int32), _dev(lam, 'lam')
+    if tuple(idx.shape) != (2 * oh + 2 * ow,) or tuple(lam.shape) != (oh + ow,) or idx.device != device or lam.device != device:
+        raise ValueError('idx must be int32 (%d,) and lam float32 (%d,) on %s -- faceparse.device_ac_tables -- not %s on %s and '
+                         '%s on %s' % (2 * oh + 2 * ow, oh + ow, device, tuple(idx.shape), idx.device, tuple(lam.shape),
+                                       lam.device))
+    return idx, lam
+
+
+def bilinear_ac(x, size, idx, lam):
+    """F.interpolate(x, size, mode='bilinear', align_corners=True) -- rw_bilinear_ac_f32.  (idx, lam) =
+    faceparse.device_ac_tables((H, W), size, device)."""
+    x = _fmap4(x, 'fmap')
+    b, c, h, w = x.shape
+    oh, ow = _pair(size, 'size')
+    if oh < 1 or ow < 1:
+        raise ValueError('size must be positive, not %r' % (size,))
+    idx, lam = _ac_tables(idx, lam, oh, ow, x.device)
+    y = torch.empty(b, c, oh, ow, device=x.device, dtype=torch.float32)
+    check(lib().rw_bilinear_ac_f32(_p(x), _p(y), b, c, h, w, oh, ow, _p(idx), _p(lam), _stream()))
+    return y
+
+
+def seg_labels(logits, size, idx, lam, pick_rows=None, pick_cols=None):
+    """(B, 1, OH, OW) int64: the arg-max over the classes of bilinear_ac(logits, size, idx, lam) -- the lowest index among
+    equals, a NaN first -- read at the pixels (pick_rows[oy], pick_cols[ox]) (int32 nearest tables; None keeps that axis) --
+    rw_seg_labels_i64; the up-sampled scores are not written."""
+    logits = _fmap4(logits, 'logits')
+    b, n, h, w = logits.shape
+    if n > SEG_MAX_CLASSES:
+        raise ValueError('logits have %d classes, at most %d are taken (RW_ERR_UNSUPPORTED, include/rewriting_hip.h)'
+                         % (n, SEG_MAX_CLASSES))
+    H, W = _pair(size, 'size')
+    if H < 1 or W < 1:
+        raise ValueError('size must be positive, not %r' % (size,))
+    idx, lam = _ac_tables(idx, lam, H, W, logits.device)
+    OH = H if pick_rows is None else int(pick_rows.numel()) if isinstance(pick_rows, torch.Tensor) else -1
+    OW = W if pick_cols is None else int(pick_cols.numel()) if isinstance(pick_cols, torch.Tensor) else -1
+    pick_rows = _index_table(pick_rows, OH, 'pick_rows', logits.device)
+    pick_cols = _index_table(pick_cols, OW, 'pick_cols', logits.device)
+    if OH < 1 or OW < 1:
+        raise ValueError('pick_rows and pick_cols must not be empty')
+    labels = torch.empty(b, 1, OH, OW, device=logits.device, dtype=torch.int64)
+    check(lib().rw_seg_labels_i64(_p(logits), _p(labels), b, n, h, w, H, W, _p(idx), _p(lam), _p(pick_rows), _p(pick_cols),
+                                  OH, OW, _stream()))
+    return labels
+
+
+def _label_set(labels, name):
+    labels = [int(v) for v in labels]
+    if not 1 <= len(labels) <= SEG_MAX_SET:
+        raise ValueError('%s must name 1 .. %d labels, not %d' % (name, SEG_MAX_SET, len(labels)))
+    return (ctypes.c_int64 * len(labels))(*labels), len(labels)
+
+
+def _label_maps(t, channel, name):
+    """(the contiguous int64 tensor, the pointer of its channel `channel`, elements per image, H W)"""
+    t = _dev(t, name, torch.int64)
+    if t.dim() not in (3, 4) or 0 in t.shape:
+        raise ValueError('%s must be a non-empty int64 (B, H, W) or (B, C, H, W), not %s' % (name, tuple(t.shape)))
+    channels = t.shape[1] if t.dim() == 4 else 1
+    if not isinstance(channel, int) or not 0 <= channel < channels:
+        raise ValueError('%s has %d channel(s), channel %r is none of them' % (name, channels, channel))
+    hw = t.shape[-2] * t.shape[-1]
+    return t, ctypes.c_void_p(t.data_ptr() + 8 * channel * hw), channels * hw, hw
+
+
+def seg_correct_counts(before, after, src, tgt, srcc=0, tgtc=0):
+    """(B, 2) int64 (total, count) per image -- rw_seg_correct_counts_i64: count = the pixels whose ``before`` label is in
+    ``src``, total = those of them whose ``after`` label is in ``tgt`` (1 .. 16 labels each).  before, after: int64
+    (B, H, W) or (B, C, H, W) with the channel srcc / tgtc, read where they lie."""
+    src, n_src = _label_set(src, 'src')
+    tgt, n_tgt = _label_set(tgt, 'tgt')
+    before, bp, bstride, hw = _label_maps(before, srcc, 'before')
+    after, ap, astride, ahw = _label_maps(after, tgtc, 'after')
+    if after.shape[0] != before.shape[0] or tuple(after.shape[-2:]) != tuple(before.shape[-2:]) or after.device != before.device:
+        raise ValueError('before %s on %s and after %s on %s must agree in batch, size and device'
+                         % (tuple(before.shape), before.device, tuple(after.shape), after.device))
+    out = torch.empty(before.shape[0], 2, device=before.device, dtype=torch.int64)
+    check(lib().rw_seg_correct_counts_i64(bp, ap, before.shape[0], hw, bstride, astride, src, n_src, tgt, n_tgt, _p(out),
+                                          _stream()))
+    return out
