@@ -960,7 +960,8 @@ int rw_masked_l1_rgb_f32(const float* a, const float* b, const float* mask, int 
  * Generator forward in float64 -- the reference's generator runs after .double(): its two native ops dispatch double
  * (above) and everything else is torch.  These entries are the double forms of that torch arithmetic: every pointer is a
  * DEVICE pointer to contiguous float64, every scalar a double, every product and accumulation is in double.  The _f64
- * twins take the arguments of their _f32 entries.  Forward only, one module per launch.
+ * twins take the arguments of their _f32 entries (the glue ops are the same kernel bodies, instantiated for double).
+ * Forward only, one module per launch.
  * ------------------------------------------------------------------------------------- */
 
 /* PixelNormL: y = x * rsqrt(mean(x^2, dim=1) + eps)      (models.py:609-614) */

@@ -38,20 +38,27 @@ static inline int rw_stream_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
-__device__ __forceinline__ float rw_wave_sum(float v) {
+// one 4-byte index inside an image's maps: what a kernel that indexes with an int asks of its launcher
+static inline bool rw_fits_31(int64_t n) { return n > 0 && n < (1LL << 31); }
+
+// The 64-lane butterfly, for any type __shfl_xor takes (float, double, the 4- and 8-byte integers); every lane ends
+// with the result.
+template <typename T> __device__ __forceinline__ T rw_wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
 
-__device__ __forceinline__ float rw_wave_max(float v) {
+__device__ __forceinline__ float rw_max2(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double rw_max2(double a, double b) { return fmax(a, b); }
+template <typename T> __device__ __forceinline__ T rw_wave_max(T v) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  for (int off = 32; off > 0; off >>= 1) v = rw_max2(v, __shfl_xor(v, off, 64));
   return v;
 }
 
 // Block-wide sum for 256-thread blocks (4 waves); result valid in every thread.
-__device__ __forceinline__ float rw_block_sum_256(float v, float* lds4) {
+template <typename T> __device__ __forceinline__ T rw_block_sum_256(T v, T* lds4) {
   v = rw_wave_sum(v);
   const int wave = threadIdx.x >> 6;
   __syncthreads();

@@ -1,234 +1,12 @@
 // hipcc-flags: -fno-slp-vectorize
-// The float64 forward of the generator: the _f64 twins of the mapping-network pieces, ApplyStyle, the demodulation
-// factors, NoiseInjectionF and ToRGB, and the two 3x3 convolutions on v_mfma_f64_16x16x4_f64.  Every operand, every
-// product and every accumulation is a double; nothing here is shared with the fp32 path, which this file leaves as it
-// is.  The double path runs module by module (no epilogues, no packed weights, no routes) and sets no speed bar: the
-// kernels are the plain forms of their fp32 twins.
+// What only the float64 forward of the generator has: the two 3x3 convolutions on v_mfma_f64_16x16x4_f64 (and their
+// any-shape form).  Every operand, every product and every accumulation is a double.  The glue ops of the double path
+// -- the mapping-network pieces, ApplyStyle, the demodulation factors, NoiseInjectionF, ToRGB -- are the double
+// instantiations of the bodies in rw_ops.hip.  The double path runs module by module (no epilogues, no packed weights,
+// no routes) and sets no speed bar.
 #include "rw_common.h"
 
 typedef double rw_f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double rw_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// one 4-byte index inside an image's maps: what the kernels below use per lane
-static inline bool rw_fits_31(int64_t n) { return n > 0 && n < (1LL << 31); }
-
-// ---------------------------------------------------------------------------------------
-// Mapping network pieces
-// ---------------------------------------------------------------------------------------
-// PixelNormL (models.py:609-614): one wave per latent row.
-__global__ void __launch_bounds__(256) pixel_norm_f64_kernel(const double* __restrict__ x, double* __restrict__ y,
-                                                             int batch, int dim, double eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= batch) return;
-  const double* xr = x + (int64_t)row * dim;
-  double ss = 0.0;
-  for (int i = lane; i < dim; i += 64) { const double v = xr[i]; ss += v * v; }
-  ss = rw_wave_sum_f64(ss);
-  const double r = 1.0 / sqrt(ss / (double)dim + eps);
-  for (int i = lane; i < dim; i += 64) y[(int64_t)row * dim + i] = xr[i] * r;
-}
-
-extern "C" int rw_pixel_norm_f64(const double* x, double* y, int batch, int dim, double eps, rw_stream_t stream) {
-  RW_CHECK_ARG(x && y && batch > 0 && dim > 0);
-  hipLaunchKernelGGL(pixel_norm_f64_kernel, dim3((batch + 3) / 4), dim3(256), 0, rw_s(stream), x, y, batch, dim, eps);
-  return RW_LAUNCH_RESULT();
-}
-
-// EqualLinear (models.py:503-511): one wave per (batch row, output feature), any in_dim; the weight is scaled
-// before the product, as the reference scales it before F.linear.
-__global__ void __launch_bounds__(256) equal_linear_f64_kernel(
-    const double* __restrict__ x, const double* __restrict__ w, const double* __restrict__ bias,
-    double* __restrict__ y, int batch, int in_dim, int out_dim, int64_t x_stride, double w_scale,
-    double b_scale, int act, double alpha, double act_scale) {
-  const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (idx >= (int64_t)batch * out_dim) return;
-  const int b = (int)(idx / out_dim), o = (int)(idx % out_dim);
-  const double* xr = x + (int64_t)b * x_stride;
-  const double* wr = w + (int64_t)o * in_dim;
-  double acc = 0.0;
-  for (int i = lane; i < in_dim; i += 64) acc += xr[i] * (wr[i] * w_scale);
-  acc = rw_wave_sum_f64(acc);
-  if (lane == 0) {
-    double v = acc + (bias ? bias[o] * b_scale : 0.0);
-    if (act) v = ((v > 0.0) ? v : v * alpha) * act_scale;
-    y[idx] = v;
-  }
-}
-
-extern "C" int rw_equal_linear_f64(const double* x, const double* w, const double* bias, double* y,
-                                   int batch, int in_dim, int out_dim, int64_t x_stride,
-                                   double w_scale, double b_scale, int act, double alpha,
-                                   double act_scale, rw_stream_t stream) {
-  RW_CHECK_ARG(x && w && y && batch > 0 && in_dim > 0 && out_dim > 0 && x_stride >= in_dim);
-  const int64_t waves = (int64_t)batch * out_dim;
-  if (!rw_fits_31(rw_cdiv(waves, 4))) return RW_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(equal_linear_f64_kernel, dim3((unsigned)rw_cdiv(waves, 4)), dim3(256), 0, rw_s(stream), x, w, bias,
-                     y, batch, in_dim, out_dim, x_stride, w_scale, b_scale, act, alpha, act_scale);
-  return RW_LAUNCH_RESULT();
-}
-
-// AdjustLatent (models.py:570-583)
-__global__ void __launch_bounds__(256) adjust_latent_f64_kernel(const double* __restrict__ w,
-                                                                const double* __restrict__ avg,
-                                                                double* __restrict__ out, int batch, int n_latent,
-                                                                int dim, double psi) {
-  const int64_t total = (int64_t)batch * n_latent * dim;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int d = (int)(idx % dim);
-    const int b = (int)(idx / ((int64_t)n_latent * dim));
-    double v = w[(int64_t)b * dim + d];
-    if (avg) { const double a = avg[d]; v = a + psi * (v - a); }
-    out[idx] = v;
-  }
-}
-
-extern "C" int rw_adjust_latent_f64(const double* w, const double* avg, double* out, int batch, int n_latent, int dim,
-                                    double psi, rw_stream_t stream) {
-  RW_CHECK_ARG(w && out && batch > 0 && n_latent > 0 && dim > 0);
-  const int64_t total = (int64_t)batch * n_latent * dim;
-  hipLaunchKernelGGL(adjust_latent_f64_kernel, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, avg,
-                     out, batch, n_latent, dim, psi);
-  return RW_LAUNCH_RESULT();
-}
-
-// ---------------------------------------------------------------------------------------
-// ApplyStyle / NoiseInjectionF
-// ---------------------------------------------------------------------------------------
-// y[row][p] = style[row] * x[row][p]                                  (ApplyStyle, rows = b*C + c)
-// y[b][c][p] = x[b][c][p] + nw * noise[b][p]                          (NoiseInjectionF)
-template <int MODE>  // 0 = style multiply, 1 = noise add
-__global__ void __launch_bounds__(256) row_broadcast_f64_kernel(
-    const double* __restrict__ x, const double* __restrict__ aux, const double* __restrict__ nw_ptr,
-    double* __restrict__ y, int64_t rows, int channels, int64_t hw) {
-  const int64_t total = rows * hw;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const double nw = (MODE == 1) ? nw_ptr[0] : 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t row = i / hw;
-    if (MODE == 0) {
-      y[i] = aux[row] * x[i];
-    } else {
-      const int64_t b = row / channels;
-      y[i] = x[i] + nw * aux[b * hw + (i - row * hw)];
-    }
-  }
-}
-
-extern "C" int rw_style_mul_f64(const double* x, const double* style, double* y, int batch, int channels, int64_t hw,
-                                rw_stream_t stream) {
-  RW_CHECK_ARG(x && style && y && batch > 0 && channels > 0 && hw > 0);
-  const int64_t rows = (int64_t)batch * channels;
-  hipLaunchKernelGGL(row_broadcast_f64_kernel<0>, dim3(rw_stream_grid(rows * hw, 256)), dim3(256), 0, rw_s(stream), x,
-                     style, (const double*)nullptr, y, rows, channels, hw);
-  return RW_LAUNCH_RESULT();
-}
-
-extern "C" int rw_noise_add_f64(const double* x, const double* noise, const double* noise_w, double* y, int batch,
-                                int channels, int64_t hw, rw_stream_t stream) {
-  RW_CHECK_ARG(x && noise && noise_w && y && batch > 0 && channels > 0 && hw > 0);
-  const int64_t rows = (int64_t)batch * channels;
-  hipLaunchKernelGGL(row_broadcast_f64_kernel<1>, dim3(rw_stream_grid(rows * hw, 256)), dim3(256), 0, rw_s(stream), x,
-                     noise, noise_w, y, rows, channels, hw);
-  return RW_LAUNCH_RESULT();
-}
-
-// ---------------------------------------------------------------------------------------
-// Demodulation factors (DemodulatedConv2dF.forward, models.py:320-328)
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) weight_sqsum_f64_kernel(const double* __restrict__ w, double* __restrict__ wsq,
-                                                               int64_t pairs, int taps, double w_scale) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (int64_t)gridDim.x * blockDim.x) {
-    double acc = 0.0;
-    for (int t = 0; t < taps; ++t) { const double v = w_scale * w[i * taps + t]; acc += v * v; }
-    wsq[i] = acc;
-  }
-}
-
-extern "C" int rw_weight_sqsum_f64(const double* w, double* wsq, int out_ch, int in_ch, int taps, double w_scale,
-                                   rw_stream_t stream) {
-  RW_CHECK_ARG(w && wsq && out_ch > 0 && in_ch > 0 && taps > 0);
-  const int64_t pairs = (int64_t)out_ch * in_ch;
-  hipLaunchKernelGGL(weight_sqsum_f64_kernel, dim3(rw_stream_grid(pairs, 256)), dim3(256), 0, rw_s(stream), w, wsq,
-                     pairs, taps, w_scale);
-  return RW_LAUNCH_RESULT();
-}
-
-// one wave per (b, o)
-__global__ void __launch_bounds__(256) demod_f64_kernel(const double* __restrict__ wsq, const double* __restrict__ style,
-                                                        double* __restrict__ demod, int batch, int out_ch, int in_ch,
-                                                        double eps) {
-  const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (idx >= (int64_t)batch * out_ch) return;
-  const int b = (int)(idx / out_ch), o = (int)(idx % out_ch);
-  double acc = 0.0;
-  for (int i = lane; i < in_ch; i += 64) {
-    const double s = style[(int64_t)b * in_ch + i];
-    acc += (s * s) * wsq[(int64_t)o * in_ch + i];
-  }
-  acc = rw_wave_sum_f64(acc);
-  if (lane == 0) demod[idx] = 1.0 / sqrt(acc + eps);
-}
-
-extern "C" int rw_demod_f64(const double* wsq, const double* style, double* demod, int batch, int out_ch, int in_ch,
-                            double eps, rw_stream_t stream) {
-  RW_CHECK_ARG(wsq && style && demod && batch > 0 && out_ch > 0 && in_ch > 0);
-  const int64_t waves = (int64_t)batch * out_ch;
-  if (!rw_fits_31(rw_cdiv(waves, 4))) return RW_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(demod_f64_kernel, dim3((unsigned)rw_cdiv(waves, 4)), dim3(256), 0, rw_s(stream), wsq, style, demod,
-                     batch, out_ch, in_ch, eps);
-  return RW_LAUNCH_RESULT();
-}
-
-// ---------------------------------------------------------------------------------------
-// ToRGB (models.py:628-655): one pixel per thread, the 3 x C modulated weight rows of this image in LDS.
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) to_rgb_f64_kernel(const double* __restrict__ x, const double* __restrict__ w,
-                                                         const double* __restrict__ style,
-                                                         const double* __restrict__ bias,
-                                                         const double* __restrict__ skip, double* __restrict__ y,
-                                                         int in_ch, int64_t hw, double w_scale) {
-  extern __shared__ double wm64[];  // [3][in_ch]
-  const int b = blockIdx.y;
-  for (int t = threadIdx.x; t < 3 * in_ch; t += 256) wm64[t] = w_scale * w[t] * style[(int64_t)b * in_ch + t % in_ch];
-  __syncthreads();
-  const double* xb = x + (int64_t)b * in_ch * hw;
-  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < hw; q += (int64_t)gridDim.x * 256) {
-    double a[3] = {0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (int i = 0; i < in_ch; ++i) {
-      const double v = xb[(int64_t)i * hw + q];
-      a[0] += wm64[i] * v; a[1] += wm64[in_ch + i] * v; a[2] += wm64[2 * in_ch + i] * v;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int64_t off = ((int64_t)b * 3 + c) * hw + q;
-      double o = a[c] + (bias ? bias[c] : 0.0);
-      if (skip) o += skip[off];
-      y[off] = o;
-    }
-  }
-}
-
-extern "C" int rw_to_rgb_f64(const double* x, const double* w, const double* style, const double* bias,
-                             const double* skip, double* y, int batch, int in_ch, int64_t hw, double w_scale,
-                             rw_stream_t stream) {
-  RW_CHECK_ARG(x && w && style && y && batch > 0 && in_ch > 0 && hw > 0);
-  if (batch > 65535 || (int64_t)3 * in_ch * sizeof(double) > 48 * 1024) return RW_ERR_UNSUPPORTED;   // in_ch <= 2048
-  int gs = (int)rw_cdiv(hw, 256);
-  if (gs > 2048) gs = 2048;
-  hipLaunchKernelGGL(to_rgb_f64_kernel, dim3(gs, batch), dim3(256), 3 * in_ch * sizeof(double), rw_s(stream), x, w,
-                     style, bias, skip, y, in_ch, hw, w_scale);
-  return RW_LAUNCH_RESULT();
-}
 
 // ---------------------------------------------------------------------------------------
 // The 3x3 convolutions (DemodulatedConv2dF, models.py:313-329) on the weight as stored, W[o][i][ky][kx]:

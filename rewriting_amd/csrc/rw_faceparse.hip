@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(256) seg_correct_counts_kernel(const long long
     total += fp_in_set(ap[i], tgt) ? 1 : 0;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
+  for (int off = 32; off > 0; off >>= 1) {           // (two sums per step, not rw_wave_sum twice: the code differs)
     total += __shfl_xor(total, off, 64);
     count += __shfl_xor(count, off, 64);
   }

@@ -28,17 +28,6 @@ typedef double rw_f64x4 __attribute__((ext_vector_type(4)));
 
 #define RW_JACOBI_INNER_SWEEPS 10
 
-__device__ __forceinline__ double rw_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double rw_wave_max_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // pair k of round r of the circle method over `count` players (count rounded up to even; hi >= count: a bye)
 __host__ __device__ __forceinline__ void rw_circle_pair(int count, int r, int k, int& lo, int& hi) {
   const int m = count + (count & 1);
@@ -77,7 +66,7 @@ __global__ void __launch_bounds__(256) jacobi_step_f64_kernel(double* __restrict
   // the largest squared column norm of the input: what the noise floor is relative to
   double mx = 0.0;
   for (int j = tid; j < n; j += 256) mx = fmax(mx, norms_sq[j]);
-  mx = rw_wave_max_f64(mx);
+  mx = rw_wave_max(mx);
   if (lane == 0) red[wave] = mx;
   if (tid < 4) flags[tid] = 0;
   __syncthreads();
@@ -288,7 +277,7 @@ __global__ void __launch_bounds__(256) colnorm_f64_kernel(const double* __restri
   const double* gr = g + (int64_t)row * n;
   double acc = 0.0;
   for (int i = lane; i < n; i += 64) { const double x = gr[i]; acc += x * x; }
-  acc = rw_wave_sum_f64(acc);
+  acc = rw_wave_sum(acc);
   if (lane == 0) out[row] = mode == 1 ? acc : (mode == 2 ? sqrt(sqrt(acc)) : sqrt(acc));
 }
 
@@ -402,7 +391,7 @@ __global__ void __launch_bounds__(256) frechet_finish_f64_kernel(const double* _
   for (int i = tid; i < n_ev; i += 256) acc[3] += sqrt(fmax(ev[i], 0.0));
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const double s = rw_wave_sum_f64(acc[q]);
+    const double s = rw_wave_sum(acc[q]);
     if (lane == 0) red[q][wave] = s;
   }
   __syncthreads();

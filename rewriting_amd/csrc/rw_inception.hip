@@ -264,8 +264,7 @@ __global__ void __launch_bounds__(256) global_avgpool_f32_kernel(const float* __
   const float* xp = x + map * hw;
   double sum = 0.0;
   for (int64_t i = lane; i < hw; i += 64) sum += (double)xp[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  sum = rw_wave_sum(sum);
   if (lane == 0) y[map] = (float)(sum / (double)hw);
 }
 

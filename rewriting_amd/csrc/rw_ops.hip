@@ -137,22 +137,6 @@ extern "C" int rw_fused_bias_act_f64(const double* x, const double* b, const dou
   return rw_fused_bias_act<double>(x, b, ref, y, n, step_b, size_b, act, grad, alpha, scale, stream);
 }
 
-// the double forms of rw_common.h's float reductions (bias_grad_kernel<double>)
-__device__ __forceinline__ double rw_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double rw_block_sum_256(double v, double* lds4) {
-  v = rw_wave_sum(v);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds4[wave] = v;
-  __syncthreads();
-  return lds4[0] + lds4[1] + lds4[2] + lds4[3];
-}
-
 // grad_bias[c] = sum_{outer, inner} g[o][c][i]        (op/fused_act.py:32-39); halves are summed in float, as
 // torch.sum sums them
 template <typename T>
@@ -430,29 +414,45 @@ extern "C" int rw_upfirdn2d_f64(const double* x, const double* k, double* y, int
 }
 
 // ---------------------------------------------------------------------------------------
+// The glue ops of the generator -- the mapping-network pieces, ApplyStyle / NoiseInjection, the demodulation factors and
+// the scalar ToRGB -- take float and double: one body on T per op, every operand, product and sum a T, behind the _f32
+// and the _f64 entry.  Where the two types differ, a typed helper or the entry says so.
+// ---------------------------------------------------------------------------------------
+// 1 / sqrt(v), each type in the expression its kernels were written with
+__device__ __forceinline__ float rw_rsqrt(float v) { return rsqrtf(v); }
+__device__ __forceinline__ double rw_rsqrt(double v) { return 1.0 / sqrt(v); }
+
+// ---------------------------------------------------------------------------------------
 // Mapping network pieces
 // ---------------------------------------------------------------------------------------
 // PixelNormL (models.py:609-614): one wave per latent row.
-__global__ void __launch_bounds__(256) pixel_norm_kernel(const float* __restrict__ x,
-                                                         float* __restrict__ y, int batch, int dim,
-                                                         float eps) {
+template <typename T>
+__global__ void __launch_bounds__(256) pixel_norm_kernel(const T* __restrict__ x, T* __restrict__ y, int batch, int dim,
+                                                         T eps) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= batch) return;
-  const float* xr = x + (int64_t)row * dim;
-  float ss = 0.f;
-  for (int i = lane; i < dim; i += 64) { const float v = xr[i]; ss += v * v; }
+  const T* xr = x + (int64_t)row * dim;
+  T ss = T(0);
+  for (int i = lane; i < dim; i += 64) { const T v = xr[i]; ss += v * v; }
   ss = rw_wave_sum(ss);
-  const float r = rsqrtf(ss / (float)dim + eps);
+  const T r = rw_rsqrt(ss / (T)dim + eps);
   for (int i = lane; i < dim; i += 64) y[(int64_t)row * dim + i] = xr[i] * r;
 }
 
-extern "C" int rw_pixel_norm_f32(const float* x, float* y, int batch, int dim, float eps,
-                                 rw_stream_t stream) {
+template <typename T>
+static int rw_pixel_norm(const T* x, T* y, int batch, int dim, T eps, rw_stream_t stream) {
   RW_CHECK_ARG(x && y && batch > 0 && dim > 0);
-  hipLaunchKernelGGL(pixel_norm_kernel, dim3((batch + 3) / 4), dim3(256), 0, rw_s(stream), x, y,
-                     batch, dim, eps);
+  hipLaunchKernelGGL(pixel_norm_kernel<T>, dim3((batch + 3) / 4), dim3(256), 0, rw_s(stream), x, y, batch, dim, eps);
   return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_pixel_norm_f32(const float* x, float* y, int batch, int dim, float eps, rw_stream_t stream) {
+  return rw_pixel_norm<float>(x, y, batch, dim, eps, stream);
+}
+
+extern "C" int rw_pixel_norm_f64(const double* x, double* y, int batch, int dim, double eps, rw_stream_t stream) {
+  return rw_pixel_norm<double>(x, y, batch, dim, eps, stream);
 }
 
 // EqualLinear (models.py:503-511).  One wave per output feature: the weight row stays in
@@ -576,29 +576,75 @@ extern "C" int rw_equal_linear_f32(const float* x, const float* w, const float* 
   return RW_LAUNCH_RESULT();
 }
 
+// EqualLinear (models.py:503-511): one wave per (batch row, output feature), any in_dim; the weight is scaled
+// before the product, as the reference scales it before F.linear.
+// (Its own algorithm, not an instantiation: the fp32 kernels hold a weight row in registers or feed the f32 MFMA.)
+__global__ void __launch_bounds__(256) equal_linear_f64_kernel(
+    const double* __restrict__ x, const double* __restrict__ w, const double* __restrict__ bias,
+    double* __restrict__ y, int batch, int in_dim, int out_dim, int64_t x_stride, double w_scale,
+    double b_scale, int act, double alpha, double act_scale) {
+  const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (idx >= (int64_t)batch * out_dim) return;
+  const int b = (int)(idx / out_dim), o = (int)(idx % out_dim);
+  const double* xr = x + (int64_t)b * x_stride;
+  const double* wr = w + (int64_t)o * in_dim;
+  double acc = 0.0;
+  for (int i = lane; i < in_dim; i += 64) acc += xr[i] * (wr[i] * w_scale);
+  acc = rw_wave_sum(acc);
+  if (lane == 0) {
+    double v = acc + (bias ? bias[o] * b_scale : 0.0);
+    if (act) v = ((v > 0.0) ? v : v * alpha) * act_scale;
+    y[idx] = v;
+  }
+}
+
+extern "C" int rw_equal_linear_f64(const double* x, const double* w, const double* bias, double* y,
+                                   int batch, int in_dim, int out_dim, int64_t x_stride,
+                                   double w_scale, double b_scale, int act, double alpha,
+                                   double act_scale, rw_stream_t stream) {
+  RW_CHECK_ARG(x && w && y && batch > 0 && in_dim > 0 && out_dim > 0 && x_stride >= in_dim);
+  const int64_t waves = (int64_t)batch * out_dim;
+  if (!rw_fits_31(rw_cdiv(waves, 4))) return RW_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(equal_linear_f64_kernel, dim3((unsigned)rw_cdiv(waves, 4)), dim3(256), 0, rw_s(stream), x, w, bias,
+                     y, batch, in_dim, out_dim, x_stride, w_scale, b_scale, act, alpha, act_scale);
+  return RW_LAUNCH_RESULT();
+}
+
 // AdjustLatent (models.py:570-583)
-__global__ void __launch_bounds__(256) adjust_latent_kernel(const float* __restrict__ w,
-                                                            const float* __restrict__ avg,
-                                                            float* __restrict__ out, int batch,
-                                                            int n_latent, int dim, float psi) {
+template <typename T>
+__global__ void __launch_bounds__(256) adjust_latent_kernel(const T* __restrict__ w, const T* __restrict__ avg,
+                                                            T* __restrict__ out, int batch, int n_latent, int dim,
+                                                            T psi) {
   const int64_t total = (int64_t)batch * n_latent * dim;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int d = (int)(idx % dim);
     const int b = (int)(idx / ((int64_t)n_latent * dim));
-    float v = w[(int64_t)b * dim + d];
-    if (avg) { const float a = avg[d]; v = a + psi * (v - a); }
+    T v = w[(int64_t)b * dim + d];
+    if (avg) { const T a = avg[d]; v = a + psi * (v - a); }
     out[idx] = v;
   }
 }
 
-extern "C" int rw_adjust_latent_f32(const float* w, const float* avg, float* out, int batch,
-                                    int n_latent, int dim, float psi, rw_stream_t stream) {
+template <typename T>
+static int rw_adjust_latent(const T* w, const T* avg, T* out, int batch, int n_latent, int dim, T psi,
+                            rw_stream_t stream) {
   RW_CHECK_ARG(w && out && batch > 0 && n_latent > 0 && dim > 0);
   const int64_t total = (int64_t)batch * n_latent * dim;
-  hipLaunchKernelGGL(adjust_latent_kernel, dim3(rw_stream_grid(total, 256)), dim3(256), 0,
-                     rw_s(stream), w, avg, out, batch, n_latent, dim, psi);
+  hipLaunchKernelGGL(adjust_latent_kernel<T>, dim3(rw_stream_grid(total, 256)), dim3(256), 0, rw_s(stream), w, avg,
+                     out, batch, n_latent, dim, psi);
   return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_adjust_latent_f32(const float* w, const float* avg, float* out, int batch, int n_latent, int dim,
+                                    float psi, rw_stream_t stream) {
+  return rw_adjust_latent<float>(w, avg, out, batch, n_latent, dim, psi, stream);
+}
+
+extern "C" int rw_adjust_latent_f64(const double* w, const double* avg, double* out, int batch, int n_latent, int dim,
+                                    double psi, rw_stream_t stream) {
+  return rw_adjust_latent<double>(w, avg, out, batch, n_latent, dim, psi, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -606,27 +652,36 @@ extern "C" int rw_adjust_latent_f32(const float* w, const float* avg, float* out
 // ---------------------------------------------------------------------------------------
 // y[row][p] = x[row][p] * rowscale[row]                               (ApplyStyle)
 // y[b][c][p] = x[b][c][p] + nw * noise[b][p]   (rows = b*C + c)       (NoiseInjectionF)
-template <int MODE>  // 0 = style multiply, 1 = noise add
+// MODE: 0 = style multiply, 1 = noise add
+// The 16-byte branch (rows that are whole float4s) is fp32 only, and so the fp32 launch is sized in 16-byte pieces
+// (+ 1: never none), the fp64 launch in elements.
+static inline int64_t rw_row_broadcast_items(const float*, int64_t total) { return total / 4 + 1; }
+static inline int64_t rw_row_broadcast_items(const double*, int64_t total) { return total; }
+
+template <typename T, int MODE>
 __global__ void __launch_bounds__(256) row_broadcast_kernel(
-    const float* __restrict__ x, const float* __restrict__ aux, const float* __restrict__ nw_ptr,
-    float* __restrict__ y, int64_t rows, int channels, int64_t hw) {
+    const T* __restrict__ x, const T* __restrict__ aux, const T* __restrict__ nw_ptr,
+    T* __restrict__ y, int64_t rows, int channels, int64_t hw) {
+  constexpr bool F32 = sizeof(T) == sizeof(float);
   const int64_t total = rows * hw;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float nw = (MODE == 1) ? nw_ptr[0] : 0.f;
-  if ((hw & 3) == 0) {
-    const int64_t hw4 = hw >> 2, total4 = total >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += stride) {
-      const int64_t row = i / hw4;
-      float4 v = reinterpret_cast<const float4*>(x)[i];
-      if (MODE == 0) {
-        const float s = aux[row];
-        v.x = s * v.x; v.y = s * v.y; v.z = s * v.z; v.w = s * v.w;
-      } else {
-        const int64_t b = row / channels;
-        const float4 nz = reinterpret_cast<const float4*>(aux)[b * hw4 + (i - row * hw4)];
-        v.x = v.x + nw * nz.x; v.y = v.y + nw * nz.y; v.z = v.z + nw * nz.z; v.w = v.w + nw * nz.w;
+  const T nw = (MODE == 1) ? nw_ptr[0] : T(0);
+  if (F32 && (hw & 3) == 0) {
+    if constexpr (F32) {
+      const int64_t hw4 = hw >> 2, total4 = total >> 2;
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += stride) {
+        const int64_t row = i / hw4;
+        float4 v = reinterpret_cast<const float4*>(x)[i];
+        if (MODE == 0) {
+          const float s = aux[row];
+          v.x = s * v.x; v.y = s * v.y; v.z = s * v.z; v.w = s * v.w;
+        } else {
+          const int64_t b = row / channels;
+          const float4 nz = reinterpret_cast<const float4*>(aux)[b * hw4 + (i - row * hw4)];
+          v.x = v.x + nw * nz.x; v.y = v.y + nw * nz.y; v.z = v.z + nw * nz.z; v.w = v.w + nw * nz.w;
+        }
+        reinterpret_cast<float4*>(y)[i] = v;
       }
-      reinterpret_cast<float4*>(y)[i] = v;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -641,63 +696,94 @@ __global__ void __launch_bounds__(256) row_broadcast_kernel(
   }
 }
 
-extern "C" int rw_style_mul_f32(const float* x, const float* style, float* y, int batch,
-                                int channels, int64_t hw, rw_stream_t stream) {
-  RW_CHECK_ARG(x && style && y && batch > 0 && channels > 0 && hw > 0);
+template <int MODE, typename T>
+static int rw_row_broadcast(const T* x, const T* aux, const T* nw, T* y, int batch, int channels, int64_t hw,
+                            rw_stream_t stream) {
+  RW_CHECK_ARG(x && aux && (MODE == 0 || nw) && y && batch > 0 && channels > 0 && hw > 0);
   const int64_t rows = (int64_t)batch * channels;
-  hipLaunchKernelGGL(row_broadcast_kernel<0>, dim3(rw_stream_grid(rows * hw / 4 + 1, 256)),
-                     dim3(256), 0, rw_s(stream), x, style, (const float*)nullptr, y, rows, channels, hw);
+  hipLaunchKernelGGL((row_broadcast_kernel<T, MODE>), dim3(rw_stream_grid(rw_row_broadcast_items(x, rows * hw), 256)),
+                     dim3(256), 0, rw_s(stream), x, aux, nw, y, rows, channels, hw);
   return RW_LAUNCH_RESULT();
 }
 
-extern "C" int rw_noise_add_f32(const float* x, const float* noise, const float* noise_w, float* y,
-                                int batch, int channels, int64_t hw, rw_stream_t stream) {
-  RW_CHECK_ARG(x && noise && noise_w && y && batch > 0 && channels > 0 && hw > 0);
-  const int64_t rows = (int64_t)batch * channels;
-  hipLaunchKernelGGL(row_broadcast_kernel<1>, dim3(rw_stream_grid(rows * hw / 4 + 1, 256)),
-                     dim3(256), 0, rw_s(stream), x, noise, noise_w, y, rows, channels, hw);
-  return RW_LAUNCH_RESULT();
+extern "C" int rw_style_mul_f32(const float* x, const float* style, float* y, int batch, int channels, int64_t hw,
+                                rw_stream_t stream) {
+  return rw_row_broadcast<0>(x, style, (const float*)nullptr, y, batch, channels, hw, stream);
+}
+
+extern "C" int rw_style_mul_f64(const double* x, const double* style, double* y, int batch, int channels, int64_t hw,
+                                rw_stream_t stream) {
+  return rw_row_broadcast<0>(x, style, (const double*)nullptr, y, batch, channels, hw, stream);
+}
+
+extern "C" int rw_noise_add_f32(const float* x, const float* noise, const float* noise_w, float* y, int batch,
+                                int channels, int64_t hw, rw_stream_t stream) {
+  return rw_row_broadcast<1>(x, noise, noise_w, y, batch, channels, hw, stream);
+}
+
+extern "C" int rw_noise_add_f64(const double* x, const double* noise, const double* noise_w, double* y, int batch,
+                                int channels, int64_t hw, rw_stream_t stream) {
+  return rw_row_broadcast<1>(x, noise, noise_w, y, batch, channels, hw, stream);
 }
 
 // ---------------------------------------------------------------------------------------
 // Demodulation factors (DemodulatedConv2dF.forward, models.py:320-328)
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) weight_sqsum_kernel(const float* __restrict__ w,
-                                                           float* __restrict__ wsq, int64_t pairs,
-                                                           int taps, float w_scale) {
+template <typename T>
+__global__ void __launch_bounds__(256) weight_sqsum_kernel(const T* __restrict__ w, T* __restrict__ wsq, int64_t pairs,
+                                                           int taps, T w_scale) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs;
        i += (int64_t)gridDim.x * blockDim.x) {
-    float acc = 0.f;
-    for (int t = 0; t < taps; ++t) { const float v = w_scale * w[i * taps + t]; acc += v * v; }
+    T acc = T(0);
+    for (int t = 0; t < taps; ++t) { const T v = w_scale * w[i * taps + t]; acc += v * v; }
     wsq[i] = acc;
   }
 }
 
-extern "C" int rw_weight_sqsum_f32(const float* w, float* wsq, int out_ch, int in_ch, int taps,
-                                   float w_scale, rw_stream_t stream) {
+template <typename T>
+static int rw_weight_sqsum(const T* w, T* wsq, int out_ch, int in_ch, int taps, T w_scale, rw_stream_t stream) {
   RW_CHECK_ARG(w && wsq && out_ch > 0 && in_ch > 0 && taps > 0);
   const int64_t pairs = (int64_t)out_ch * in_ch;
-  hipLaunchKernelGGL(weight_sqsum_kernel, dim3(rw_stream_grid(pairs, 256)), dim3(256), 0,
-                     rw_s(stream), w, wsq, pairs, taps, w_scale);
+  hipLaunchKernelGGL(weight_sqsum_kernel<T>, dim3(rw_stream_grid(pairs, 256)), dim3(256), 0, rw_s(stream), w, wsq,
+                     pairs, taps, w_scale);
   return RW_LAUNCH_RESULT();
 }
 
+extern "C" int rw_weight_sqsum_f32(const float* w, float* wsq, int out_ch, int in_ch, int taps, float w_scale,
+                                   rw_stream_t stream) {
+  return rw_weight_sqsum<float>(w, wsq, out_ch, in_ch, taps, w_scale, stream);
+}
+
+extern "C" int rw_weight_sqsum_f64(const double* w, double* wsq, int out_ch, int in_ch, int taps, double w_scale,
+                                   rw_stream_t stream) {
+  return rw_weight_sqsum<double>(w, wsq, out_ch, in_ch, taps, w_scale, stream);
+}
+
 // one wave per (b, o): 64-lane butterfly for the per-channel reduction
-__global__ void __launch_bounds__(256) demod_kernel(const float* __restrict__ wsq,
-                                                    const float* __restrict__ style,
-                                                    float* __restrict__ demod, int batch, int out_ch,
-                                                    int in_ch, float eps) {
+template <typename T>
+__global__ void __launch_bounds__(256) demod_kernel(const T* __restrict__ wsq, const T* __restrict__ style,
+                                                    T* __restrict__ demod, int batch, int out_ch, int in_ch, T eps) {
   const int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (idx >= (int64_t)batch * out_ch) return;
   const int b = (int)(idx / out_ch), o = (int)(idx % out_ch);
-  float acc = 0.f;
+  T acc = T(0);
   for (int i = lane; i < in_ch; i += 64) {
-    const float s = style[(int64_t)b * in_ch + i];
+    const T s = style[(int64_t)b * in_ch + i];
     acc += (s * s) * wsq[(int64_t)o * in_ch + i];
   }
   acc = rw_wave_sum(acc);
-  if (lane == 0) demod[idx] = rsqrtf(acc + eps);
+  if (lane == 0) demod[idx] = rw_rsqrt(acc + eps);
+}
+
+// (the arguments are the entry's, checked there)
+template <typename T>
+static int rw_demod_butterfly(const T* wsq, const T* style, T* demod, int batch, int out_ch, int in_ch, T eps,
+                              rw_stream_t stream) {
+  const int64_t waves = (int64_t)batch * out_ch;
+  hipLaunchKernelGGL(demod_kernel<T>, dim3((unsigned)rw_cdiv(waves, 4)), dim3(256), 0, rw_s(stream), wsq, style, demod,
+                     batch, out_ch, in_ch, eps);
+  return RW_LAUNCH_RESULT();
 }
 
 // the same on the matrix pipe (in_ch % 16 == 0, out_ch % 16 == 0): a 16 (batch) x 16 (out) tile per wave, operands and
@@ -747,10 +833,15 @@ extern "C" int rw_demod_f32(const float* wsq, const float* style, float* demod, 
                        demod, batch, out_ch, in_ch, eps);
     return RW_LAUNCH_RESULT();
   }
-  const int64_t waves = (int64_t)batch * out_ch;
-  hipLaunchKernelGGL(demod_kernel, dim3((unsigned)rw_cdiv(waves, 4)), dim3(256), 0, rw_s(stream),
-                     wsq, style, demod, batch, out_ch, in_ch, eps);
-  return RW_LAUNCH_RESULT();
+  return rw_demod_butterfly<float>(wsq, style, demod, batch, out_ch, in_ch, eps, stream);
+}
+
+// (no matrix-pipe form; the wave count must fit the grid)
+extern "C" int rw_demod_f64(const double* wsq, const double* style, double* demod, int batch, int out_ch, int in_ch,
+                            double eps, rw_stream_t stream) {
+  RW_CHECK_ARG(wsq && style && demod && batch > 0 && out_ch > 0 && in_ch > 0);
+  if (!rw_fits_31(rw_cdiv((int64_t)batch * out_ch, 4))) return RW_ERR_UNSUPPORTED;
+  return rw_demod_butterfly<double>(wsq, style, demod, batch, out_ch, in_ch, eps, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1208,43 +1299,67 @@ extern "C" int rw_rgb_combine_up_f32(const float* partials, int n_part, const fl
 
 // The same for maps whose pixel count is not a multiple of four (the cropped goal maps of a rewriter whose target
 // spans a ToRGB: rows of 5 x 7, ...): one pixel per thread, same order of additions.
-__global__ void __launch_bounds__(256) to_rgb_scalar_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ style,
-                                                            const float* __restrict__ bias,
-                                                            const float* __restrict__ skip, float* __restrict__ y,
-                                                            int in_ch, int64_t hw, float w_scale) {
-  extern __shared__ float wm[];  // [3][in_ch]
+// It is also the ToRGB of the double path, at any pixel count.
+// (The dynamic LDS is an extern array, which has one element type per name.)
+__device__ __forceinline__ float* rw_to_rgb_lds(const float*) { extern __shared__ float wm[]; return wm; }
+__device__ __forceinline__ double* rw_to_rgb_lds(const double*) { extern __shared__ double wm64[]; return wm64; }
+// channel i of a pixel, v = its sample, into the three sums
+template <typename T> __device__ __forceinline__ void rw_to_rgb_add(const T* wm, int in_ch, int i, T v, T (&a)[3]) {
+  a[0] += wm[i] * v; a[1] += wm[in_ch + i] * v; a[2] += wm[2 * in_ch + i] * v;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) to_rgb_scalar_kernel(const T* __restrict__ x, const T* __restrict__ w,
+                                                            const T* __restrict__ style, const T* __restrict__ bias,
+                                                            const T* __restrict__ skip, T* __restrict__ y, int in_ch,
+                                                            int64_t hw, T w_scale) {
+  T* wm = rw_to_rgb_lds(x);  // [3][in_ch]
   const int b = blockIdx.y;
   for (int t = threadIdx.x; t < 3 * in_ch; t += 256) wm[t] = w_scale * w[t] * style[(int64_t)b * in_ch + t % in_ch];
   __syncthreads();
-  const float* xb = x + (int64_t)b * in_ch * hw;
+  const T* xb = x + (int64_t)b * in_ch * hw;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < hw; q += (int64_t)gridDim.x * 256) {
-    float a[3] = {0.f, 0.f, 0.f};
-    for (int i = 0; i < in_ch; ++i) {
-      const float v = xb[(int64_t)i * hw + q];
-      a[0] += wm[i] * v; a[1] += wm[in_ch + i] * v; a[2] += wm[2 * in_ch + i] * v;
+    T a[3] = {T(0), T(0), T(0)};
+    if constexpr (sizeof(T) == sizeof(double)) {   // the double loop asks for four channels per trip, the float loop for none
+#pragma unroll 4
+      for (int i = 0; i < in_ch; ++i) rw_to_rgb_add(wm, in_ch, i, xb[(int64_t)i * hw + q], a);
+    } else {
+      for (int i = 0; i < in_ch; ++i) rw_to_rgb_add(wm, in_ch, i, xb[(int64_t)i * hw + q], a);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int64_t off = ((int64_t)b * 3 + c) * hw + q;
-      float o = a[c] + (bias ? bias[c] : 0.f);
+      T o = a[c] + (bias ? bias[c] : T(0));
       if (skip) o += skip[off];
       y[off] = o;
     }
   }
 }
 
+// (the arguments are the entry's, checked there)
+template <typename T>
+static int rw_to_rgb_scalar(const T* x, const T* w, const T* style, const T* bias, const T* skip, T* y, int batch,
+                            int in_ch, int64_t hw, T w_scale, rw_stream_t stream) {
+  int gs = (int)rw_cdiv(hw, 256);
+  if (gs > 2048) gs = 2048;
+  hipLaunchKernelGGL(to_rgb_scalar_kernel<T>, dim3(gs, batch), dim3(256), 3 * in_ch * sizeof(T), rw_s(stream), x, w,
+                     style, bias, skip, y, in_ch, hw, w_scale);
+  return RW_LAUNCH_RESULT();
+}
+
+extern "C" int rw_to_rgb_f64(const double* x, const double* w, const double* style, const double* bias,
+                             const double* skip, double* y, int batch, int in_ch, int64_t hw, double w_scale,
+                             rw_stream_t stream) {
+  RW_CHECK_ARG(x && w && style && y && batch > 0 && in_ch > 0 && hw > 0);
+  if (batch > 65535 || (int64_t)3 * in_ch * sizeof(double) > 48 * 1024) return RW_ERR_UNSUPPORTED;   // in_ch <= 2048
+  return rw_to_rgb_scalar<double>(x, w, style, bias, skip, y, batch, in_ch, hw, w_scale, stream);
+}
+
 extern "C" int rw_to_rgb_f32(const float* x, const float* w, const float* style, const float* bias,
                              const float* skip, float* y, int batch, int in_ch, int64_t hw,
                              float w_scale, rw_stream_t stream) {
   RW_CHECK_ARG(x && w && style && y && batch > 0 && in_ch > 0 && hw > 0);
-  if (hw % 4) {
-    int gs = (int)rw_cdiv(hw, 256);
-    if (gs > 2048) gs = 2048;
-    hipLaunchKernelGGL(to_rgb_scalar_kernel, dim3(gs, batch), dim3(256), 3 * in_ch * sizeof(float), rw_s(stream), x, w,
-                       style, bias, skip, y, in_ch, hw, w_scale);
-    return RW_LAUNCH_RESULT();
-  }
+  if (hw % 4) return rw_to_rgb_scalar<float>(x, w, style, bias, skip, y, batch, in_ch, hw, w_scale, stream);
   int gx = (int)rw_cdiv(hw / 4, 256);
   const int cap = (256 * 8 + batch - 1) / batch;
   if (gx > cap) gx = cap;

@@ -93,12 +93,6 @@ struct pd_source {
   }
 };
 
-__device__ __forceinline__ unsigned pd_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // The output of one stream: the window ring in LDS, the global stream behind it.  pos <= expect always (the core asks
 // produced() first), so everything below `pos` may be stored.
 struct pd_sink {
@@ -127,7 +121,7 @@ struct pd_sink {
         c1 += d;
         c2 += (PD_CHUNK - ((unsigned)lane * 16 + e)) * d;
       }
-      fold(PD_CHUNK, pd_wave_sum(c1), pd_wave_sum(c2));
+      fold(PD_CHUNK, rw_wave_sum(c1), rw_wave_sum(c2));
       flushed += PD_CHUNK;
     }
   }
@@ -141,7 +135,7 @@ struct pd_sink {
       c1 += d;
       c2 += (m - i) * d;
     }
-    fold(m, pd_wave_sum(c1), pd_wave_sum(c2));
+    fold(m, rw_wave_sum(c1), rw_wave_sum(c2));
     flushed = pos;
   }
 

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Does the working tree generate the device code that <rev> generated?
 
-    scripts/isa_diff.py [--keep DIR] [--ops] <rev> [rewriting_amd/csrc/rw_x.hip ...]      (default: every .hip of rewriting_amd/csrc)
+    scripts/isa_diff.py [--keep DIR] [--ops] [--rename OLD=NEW ...] <rev> [rewriting_amd/csrc/rw_x.hip ...]      (default: every .hip of rewriting_amd/csrc)
 
 The sources of <rev> (git show <rev>:path) go into a temporary directory; both sides are compiled to gfx950 assembly
 with the library's own flags (csrc/build.sh, the file's "// hipcc-flags:" line, + --cuda-device-only -S), at most 16
 compilations at a time.  The listings are split at the function symbols and compared as text, kernel by kernel: the
 instruction text and the .amdhsa_* resource block (registers, scratch, LDS).  The lines that name the compilation
-unit's __hip_cuid_ symbol are dropped -- they differ between two builds of unchanged code.  Per kernel one line,
+unit's __hip_cuid_ symbol are dropped -- they differ between two builds of unchanged code -- and so is the function index
+inside local labels.  --rename compares a kernel of <rev> with the one that carries another symbol now.  Per kernel one line,
 "same", or "differs" with both instruction counts and both resource blocks; exit status 1 if anything differs.
 --ops adds, per differing kernel, the arithmetic mnemonics whose counts changed (ARITH below: floating-point VALU
 operations, conversions, selects, MFMAs, lane permutes -- integer address arithmetic, moves, waits and nops are not
@@ -46,15 +47,25 @@ def compile_asm(tree, rel, out):
     return out
 
 
-def split_listing(path):
-    """{symbol: [lines]} for every function, {kernel: [.amdhsa_ lines]}, and the lines outside both."""
+# local labels carry the function's index in its file (.LBB10_6, BB10_9 in comments, .Lfunc_end10, .LJTI10_0), which moves
+# when a kernel is added, removed or reordered in front of it: the index is dropped
+LOCAL_LABEL = re.compile(r"(\.L|\b)(BB|JTI|func_begin|func_end)\d+")
+
+
+def split_listing(path, rename=()):
+    """{symbol: [lines]} for every function, {kernel: [.amdhsa_ lines]}, and the lines outside both; rename: (old, new)
+    pairs of symbols, applied to every line."""
     funcs, res, rest = {}, {}, []
     cur = kern = None
     with open(path) as f:
         for line in f:
-            line = line.rstrip()
+            line = re.sub(r"\s+;", " ;", LOCAL_LABEL.sub(r"\1\2", line.rstrip()))    # (comments are padded to a column)
+            for old, new in rename:
+                line = line.replace(old, new)
             if "__hip_cuid_" in line:
                 continue
+            if cur is not None and re.match(r"\s*(\.text$|\.section\s+\.text\.)", line):
+                continue                 # back to the code section: ".text", or the own section of a template instantiation
             m = re.match(r"\s*\.type\s+(\S+),@function", line)
             if m:
                 cur = m.group(1)
@@ -113,7 +124,10 @@ def main():
     ap.add_argument("files", nargs="*")
     ap.add_argument("--ops", action="store_true", help="per differing kernel: the arithmetic mnemonics whose counts changed")
     ap.add_argument("--keep", metavar="DIR", help="keep both listings of every file in DIR (<file>.old.s, <file>.new.s)")
+    ap.add_argument("--rename", metavar="OLD=NEW", action="append", default=[],
+                    help="a symbol of <rev> and its name in the working tree (a kernel that became a template instantiation)")
     args = ap.parse_args()
+    rename = [tuple(r.split("=", 1)) for r in args.rename]
     files = [os.path.relpath(os.path.abspath(f), ROOT) for f in args.files]
     if not files:
         files = sorted(CSRC + "/" + f for f in os.listdir(os.path.join(ROOT, CSRC)) if f.endswith(".hip"))
@@ -136,7 +150,7 @@ def main():
                 jobs[rel] = (pool.submit(compile_asm, os.path.join(tmp, "old"), rel, os.path.join(lst, base + ".old.s")),
                              pool.submit(compile_asm, ROOT, rel, os.path.join(lst, base + ".new.s")))
             for rel in files:
-                old_f, old_r, old_x = split_listing(jobs[rel][0].result())
+                old_f, old_r, old_x = split_listing(jobs[rel][0].result(), rename)
                 new_f, new_r, new_x = split_listing(jobs[rel][1].result())
                 print("%s  (%d lines of assembly at %s, %d now)" % (
                     rel, sum(map(len, old_f.values())) + len(old_x), args.rev, sum(map(len, new_f.values())) + len(new_x)))
